@@ -13,7 +13,11 @@ rank as in configs[2], no data-path collective in the timed region, weak scaling
 starts; `value_full_path` is the rate of the whole boundary protocol from pinned host memory (parse_header +
 transfer + decode), which the boundary hands over -- never `value`. After the timed loop the planes of every
 distinct image are compared with the CPU oracle (`verified`). Rank 0 prints ONE JSON line; DESIGN.md section 4
-defines every field.
+defines every field. `ms_per_step` is the wall time of one timed step.
+
+`--dump-outputs DIR` writes what the timed path decoded in its last step -- the planes of every image of the batch, a
+fixed seeded sample of each -- to DIR/plane<c>.npy (float32, at most 64 MB; `dump_outputs`). The inputs are seeded, so
+two builds run with the same arguments can be compared array for array.
 
 `roofline` is the destuff+Huffman PASS the north star names: SURVEY.md 8(d)'s algorithmic bytes of that pass
 (B_dh = stuffed scan bytes + 128 B per data unit) x the images of one launch / the SUM of the average durations of
@@ -35,10 +39,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-
-# The HIP runtime multiplexes streams onto 4 hardware queues by default, which caps the number of
-# kernels in flight at 4 (profiles/r01_early_kernel_stats_streams_4queues.csv). One decode per stream needs more.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s (spec)
 SIMDS, VALU_CYCLES, SHADER_HZ = 1024, 4, 2.4e9  # 256 CUs x 4 SIMDs; a wave64 VALU instruction issues over 4 cycles
@@ -93,6 +93,9 @@ def parse_args():
                     help="N = 1: calls per point of `batch_curve` (one batched call of 1 .. 64 images, device time per image); 0 = skip")
     ap.add_argument("--shard-iters", type=int, default=200,
                     help="N = 1: iterations of `config3_rank_shard` (BASELINE configs[2]'s per-rank 8 images through the whole protocol); 0 = skip")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the planes the last step decoded to DIR/plane<c>.npy (float32, a fixed "
+                         "seeded sample of every image of the batch, at most 64 MB in all; see dump_outputs)")
     return ap.parse_args()
 
 
@@ -614,6 +617,43 @@ def timed_steps(torch, bset, steps, warmup, barrier):
     return time.perf_counter() - t0
 
 
+DUMP_BYTES = 60 << 20  # --dump-outputs: values of all ranks together (64 MB less room for the .npy headers)
+DUMP_SEED = 20261015
+
+
+def dump_outputs(torch, bset, out_dir, rank, world):
+    """--dump-outputs: what the timed path handed its caller in the last step -- the planes of every image of the rank's batch
+    -- as DIR/plane<c>.npy (DIR/rank<r>_plane<c>.npy for N > 1), float32 [batch, m_c]: row i holds component c of image i at
+    m_c positions of its plane (row-major flat indices). Where the whole batch fits in the budget that is every sample in
+    order; otherwise each image gets its own positions, drawn once from numpy.random.default_rng(DUMP_SEED + rank) and
+    sorted, m_c in proportion to the plane's size. Same arguments, same inputs, same positions: two builds compare
+    file for file."""
+    import numpy as np
+
+    slots = bset.slots
+    sizes = [p.numel() for p in slots[0].planes]
+    nb = len(slots)
+    per_image = max(len(sizes), DUMP_BYTES // 4 // world // nb)  # float32 values per image
+    rng = np.random.default_rng(DUMP_SEED + rank)
+    flat = bset.planes_flat.view(nb, bset.per_image)
+    os.makedirs(out_dir, exist_ok=True)
+    written, off = {}, 0
+    for c, n in enumerate(sizes):
+        m = n if sum(sizes) <= per_image else max(1, per_image * n // sum(sizes))
+        if m >= n:
+            vals = flat[:, off:off + n]
+        else:
+            pos = np.sort(np.stack([rng.choice(n, m, replace=False) for _ in range(nb)]), axis=1)
+            idx = torch.from_numpy(pos + off).to(flat.device)
+            vals = torch.gather(flat, 1, idx)
+        a = vals.to(torch.float32).cpu().numpy()
+        name = ("rank%d_plane%d" % (rank, c)) if world > 1 else ("plane%d" % c)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = list(a.shape)
+        off += n
+    return {"dir": os.path.abspath(out_dir), "arrays": written, "dtype": "float32", "seed": DUMP_SEED + rank}
+
+
 def serialized_stage_us(args, bset):
     """Average duration of every stage over `--roofline-launches` launches of ONE group (64 images by default) on one
     stream with nothing else on the chip: HIP events the library records on the launch stream between its launches."""
@@ -961,6 +1001,8 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     images_per_step = world * args.batch * args.rounds
     value = images_per_step * args.steps / elapsed
+    # before anything else writes into the planes (the gather leg reuses them)
+    dumped = dump_outputs(torch, bset, args.dump_outputs, rank, world) if args.dump_outputs else None
 
     # every distinct image of the timed batch against the oracle
     verified, nverified = None, 0
@@ -1032,6 +1074,8 @@ def main():
             "roofline_e2e": e2e,
             "kernels": kernels,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if gather is not None:
             out["gather"] = gather
         if segment_shard is not None:
