@@ -17,6 +17,8 @@
  *   jpeggpu_ext_planes_to_rgbi         chroma replication + YCbCr -> interleaved RGB8 (util/util.h:62-104)
  *   jpeggpu_ext_upsample_planes        nearest-neighbour chroma replication on the device, the integer
  *                                      part of the reference's host helper util/util.h:62-91
+ *   jpeggpu_ext_set_scale              decode at 1/2, 1/4 or 1/8 size (libjpeg's scale_num / scale_denom), bit-exact with
+ *                                      libjpeg-turbo's reduced IDCTs
  */
 #ifndef JPEGGPU_JPEGGPU_EXT_H_
 #define JPEGGPU_JPEGGPU_EXT_H_
@@ -145,6 +147,23 @@ enum jpeggpu_status jpeggpu_ext_get_shard_rows(jpeggpu_decoder_t decoder, int co
 enum jpeggpu_status jpeggpu_ext_set_device_scan(jpeggpu_decoder_t decoder, int enable);
 enum jpeggpu_status jpeggpu_ext_get_device_status(
     jpeggpu_decoder_t decoder, const void* d_tmp, jpeggpu_stream_t stream, enum jpeggpu_status* status);
+
+/* Scaled decoding (libjpeg's scale_num = 1, scale_denom = d): scale_denom 1 (the default), 2, 4 or 8, anything else
+ * JPEGGPU_INVALID_ARGUMENT. Takes effect at the next jpeggpu_decoder_parse_header, like jpeggpu_ext_set_device_scan. With
+ * denominator d, parse_header reports sizes_x[c] = ceil(W * h_c / (h_max * d)) (libjpeg's downsampled_width at that
+ * scale), likewise sizes_y, and jpeggpu_decoder_decode / jpeggpu_ext_decode_batch write planes of those sizes (the pitch
+ * checks use them). Every entry point works on a scaled decoder: a batch may mix items of any scales, 1 included; the
+ * device marker scan; jpeggpu_ext_set_segment_shard, whose jpeggpu_ext_get_shard_rows then reports rows of the scaled
+ * plane (a band is whole MCU rows, 8 v_c / d rows each); jpeggpu_ext_upsample_planes and jpeggpu_ext_planes_to_rgbi given
+ * the scaled img_info and the scaled width and height.
+ *   - Every component is scaled by the same factor: the planes keep their native subsampling. (libjpeg-turbo's raw-data
+ *     output may upscale chroma through its IDCT instead; only 4:4:4 and grayscale files are directly comparable with
+ *     libjpeg's.)
+ *   - The arithmetic is that of libjpeg-turbo's jidctred.c (jpeg_idct_4x4, jpeg_idct_2x2, jpeg_idct_1x1): dequantisation
+ *     in full int, its range limit (a 10-bit wrap, then the clamp). Scale 1 is the full-size IDCT as before.
+ *   - Only the IDCT stage changes: subsequence choice, transfer, the Huffman kernels and jpeggpu_decoder_get_buffer_size
+ *     (d_tmp sizing) do not depend on the scale. */
+enum jpeggpu_status jpeggpu_ext_set_scale(jpeggpu_decoder_t decoder, int scale_denom);
 
 /* Stage timing: when enabled, jpeggpu_decoder_decode records HIP events on the caller's stream
  * between its launches; after the stream has been synchronised jpeggpu_ext_get_stage_ms returns the

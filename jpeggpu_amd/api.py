@@ -133,6 +133,8 @@ def lib():
     L.jpeggpu_ext_get_shard_rows.argtypes = [dec, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.jpeggpu_ext_self_test.argtypes = [C.c_void_p]
     L.jpeggpu_ext_set_device_scan.argtypes = [dec, C.c_int]
+    if hasattr(L, "jpeggpu_ext_set_scale"):  # (experimental builds of older trees, JPEGGPU_LIB, lack it)
+        L.jpeggpu_ext_set_scale.argtypes = [dec, C.c_int]
     L.jpeggpu_ext_get_device_status.argtypes = [dec, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
     L.jpeggpu_ext_parse_headers.argtypes = [C.POINTER(ParseItem), C.c_int, C.c_int, C.POINTER(C.c_int)]
     L.jpeggpu_ext_planes_to_rgbi.argtypes = [
@@ -208,6 +210,11 @@ class Decoder:
         """False / 0: host walk; True / 1: marker scan on the device, status via device_status(); 2: checked --
         decode() waits for the stream and raises the device's status (what JPEGGPU_DEVICE_SCAN=2 selects)."""
         _check(lib().jpeggpu_ext_set_device_scan(self._h, int(on)), "jpeggpu_ext_set_device_scan")
+
+    def set_scale(self, scale_denom: int):
+        """Decode the next parsed images at 1 / scale_denom (1, 2, 4 or 8): planes of ceil(size / scale_denom), the
+        arithmetic of libjpeg-turbo's reduced IDCTs (jpeggpu_ext_set_scale)."""
+        _check(lib().jpeggpu_ext_set_scale(self._h, int(scale_denom)), "jpeggpu_ext_set_scale")
 
     def set_segment_shard(self, rank: int, world: int):
         """Decode only restart segments [rank * n / world, (rank + 1) * n / world) of the next parsed images."""
@@ -339,14 +346,17 @@ def self_test(stream: int = 0) -> None:
     _check(lib().jpeggpu_ext_self_test(stream), "jpeggpu_ext_self_test")
 
 
-def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp=False, device_scan=False):
+def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp=False, device_scan=False, scale=1):
     """Convenience wrapper used by tests: full call sequence on torch's current stream, returns the
     planes as torch uint8 tensors on `device` (torch is only the allocator / stream provider). With
-    `device_scan` the restart markers are found on the device and a status it reports there is raised."""
+    `device_scan` the restart markers are found on the device and a status it reports there is raised.
+    `scale`: 1, 2, 4 or 8 -- planes at 1 / scale (Decoder.set_scale)."""
     import torch
 
     dec = Decoder(subseq_bytes)
     try:
+        if scale != 1:
+            dec.set_scale(scale)
         if device_scan:
             dec.set_device_scan(True)
         info = dec.parse_header(data)

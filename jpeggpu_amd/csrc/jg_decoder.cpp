@@ -122,6 +122,11 @@ struct Decoder {
     bool parsed         = false;
     int shard_rank = 0, shard_world = 1; // jpeggpu_ext_set_segment_shard
     int device_scan     = 0;     // jpeggpu_ext_set_device_scan: 0 off, 1 on (status via jpeggpu_ext_get_device_status), 2 on and checked by decode
+    // jpeggpu_ext_set_scale: planes at 1 / 2^scale_log2. The request takes effect at the next parse_header (`scale_log2`:
+    // that of the parsed image); it changes the plane sizes and the IDCT stage only, never the plan or the Huffman path.
+    int scale_log2_request = 0;
+    int scale_log2         = 0;
+    int scaled(int size) const { return (size + (1 << scale_log2) - 1) >> scale_log2; } // ceil(size / 2^scale_log2)
 
     std::vector<ScanJob> jobs; // scratch of the last decode
 
@@ -418,7 +423,7 @@ jpeggpu_status build_jobs(
     if (!d.parsed) return JPEGGPU_INVALID_ARGUMENT;
     const Stream& s = d.reader.s;
     for (int c = 0; c < s.num_comp; ++c) {
-        if (!img->image[c] || img->pitch[c] < s.comp[c].size_x) return JPEGGPU_INVALID_ARGUMENT;
+        if (!img->image[c] || img->pitch[c] < d.scaled(s.comp[c].size_x)) return JPEGGPU_INVALID_ARGUMENT;
     }
     if (!d_tmp || (reinterpret_cast<uintptr_t>(d_tmp) & 255)) return JPEGGPU_INVALID_ARGUMENT;
     if (tmp_size < d.plan.total) return JPEGGPU_INTERNAL_ERROR;
@@ -467,6 +472,7 @@ jpeggpu_status build_jobs(
         ip.du_per_mcu  = sc.du_per_mcu;
         ip.mcus_x      = sc.mcus_x;
         ip.first_mcu   = sc.first_mcu;
+        ip.scale_log2  = static_cast<uint8_t>(d.scale_log2);
         {
             const MagicDiv a = magic_div(static_cast<uint32_t>(sc.du_per_mcu)), b = magic_div(static_cast<uint32_t>(sc.mcus_x));
             ip.du_per_mcu_mul = a.mul, ip.du_per_mcu_shift = a.shift;
@@ -486,8 +492,8 @@ jpeggpu_status build_jobs(
             const Component& fc = s.comp[c.comp_idx];
             ip.comp_h[a]        = c.h;
             ip.comp_v[a]        = c.v;
-            ip.size_x[a]        = fc.size_x;
-            ip.size_y[a]        = fc.size_y;
+            ip.size_x[a]        = d.scaled(fc.size_x);
+            ip.size_y[a]        = d.scaled(fc.size_y);
             ip.pitch[a]         = img->pitch[c.comp_idx];
             ip.qidx[a]          = fc.qidx;
             ip.plane[a]         = img->image[c.comp_idx];
@@ -731,6 +737,7 @@ enum jpeggpu_status jpeggpu_decoder_parse_header(
     if (!decoder || !img_info || !data) return JPEGGPU_INVALID_ARGUMENT;
     Decoder& d = decoder->d;
     d.parsed   = false;
+    d.scale_log2 = d.scale_log2_request;
     jpeggpu_status st;
     try {
         const int ask = d.subseq_request > 0 ? d.subseq_request : -d.batch_hint; // 0 / -N: chosen per image for N images per call
@@ -747,8 +754,8 @@ enum jpeggpu_status jpeggpu_decoder_parse_header(
     std::memset(img_info, 0, sizeof(*img_info));
     img_info->num_components = s.num_comp;
     for (int c = 0; c < s.num_comp; ++c) {
-        img_info->sizes_x[c]       = s.comp[c].size_x;
-        img_info->sizes_y[c]       = s.comp[c].size_y;
+        img_info->sizes_x[c]       = d.scaled(s.comp[c].size_x); // libjpeg's downsampled_width at the scale
+        img_info->sizes_y[c]       = d.scaled(s.comp[c].size_y);
         img_info->subsampling.x[c] = s.comp[c].hs;
         img_info->subsampling.y[c] = s.comp[c].vs;
     }
@@ -846,16 +853,18 @@ enum jpeggpu_status jpeggpu_ext_get_shard_rows(jpeggpu_decoder_t decoder, int co
     const jg::Stream& s = d.reader.s;
     if (component < 0 || component >= s.num_comp) return JPEGGPU_INVALID_ARGUMENT;
     const jg::Component& fc = s.comp[component];
+    const int size_y = d.scaled(fc.size_y);
     *first_row = 0;
-    *num_rows  = fc.size_y;
+    *num_rows  = size_y;
     const jg::Scan& sc = s.scans[0];
     if (sc.total_segments == 0) return JPEGGPU_SUCCESS; // no shard: every row
     int v = 1;
     for (int a = 0; a < sc.num_comp; ++a)
         if (sc.comp[a].comp_idx == component) v = sc.comp[a].v;
-    const int row0 = sc.first_mcu / sc.mcus_x * 8 * v, row1 = (sc.first_mcu + sc.shard_mcus) / sc.mcus_x * 8 * v;
-    *first_row = std::min(row0, fc.size_y);
-    *num_rows  = std::min(row1, fc.size_y) - *first_row;
+    const int rows_per_mcu_row = (8 >> d.scale_log2) * v; // whole MCU rows: 8 v / scale rows each
+    const int row0 = sc.first_mcu / sc.mcus_x * rows_per_mcu_row, row1 = (sc.first_mcu + sc.shard_mcus) / sc.mcus_x * rows_per_mcu_row;
+    *first_row = std::min(row0, size_y);
+    *num_rows  = std::min(row1, size_y) - *first_row;
     return JPEGGPU_SUCCESS;
 }
 
@@ -950,6 +959,16 @@ enum jpeggpu_status jpeggpu_ext_set_device_scan(jpeggpu_decoder_t decoder, int e
 {
     if (!decoder || enable < 0 || enable > 2) return JPEGGPU_INVALID_ARGUMENT;
     decoder->d.device_scan = enable;
+    return JPEGGPU_SUCCESS;
+}
+
+enum jpeggpu_status jpeggpu_ext_set_scale(jpeggpu_decoder_t decoder, int scale_denom)
+{
+    if (!decoder) return JPEGGPU_INVALID_ARGUMENT;
+    int lg = 0;
+    while (lg <= 3 && (1 << lg) != scale_denom) ++lg;
+    if (lg > 3) return JPEGGPU_INVALID_ARGUMENT; // 1, 2, 4 or 8
+    decoder->d.scale_log2_request = lg;
     return JPEGGPU_SUCCESS;
 }
 

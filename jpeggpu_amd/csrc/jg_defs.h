@@ -371,14 +371,19 @@ struct IdctParams {
     uint8_t du_comp[kMaxDuPerMcu]; // scan-component index of each data unit in the MCU
     uint8_t du_dx[kMaxDuPerMcu];   // block column inside the MCU
     uint8_t du_dy[kMaxDuPerMcu];   // block row inside the MCU
+    uint8_t scale_log2;            // jpeggpu_ext_set_scale: planes at 1 / 2^scale_log2 (0: full size, idct_kernel; else idct_scaled_kernel)
     int comp_h[kMaxComp];          // blocks per MCU horizontally (1 when non-interleaved)
     int comp_v[kMaxComp];
-    int size_x[kMaxComp];          // visible plane size (crop)
+    int size_x[kMaxComp];          // visible plane size (crop), at the scale above
     int size_y[kMaxComp];
     int pitch[kMaxComp];
     int qidx[kMaxComp];            // quantisation table index
     uint8_t* plane[kMaxComp];
 };
+
+static_assert(offsetof(IdctParams, scale_log2) == offsetof(IdctParams, du_comp) + 3 * kMaxDuPerMcu &&
+                  offsetof(IdctParams, comp_h) == offsetof(IdctParams, du_comp) + 32,
+              "the scale sits in what was padding: the layout of every other field, and sizeof(ScanJob), are unchanged");
 
 /// Division by a runtime constant: for 2 <= d and n < 2^31, with L = ceil(log2 d) and
 /// M = ceil(2^(31+L) / d) (< 2^32), floor(n / d) == (mulhi(n, M) >> (L - 1)): the error term

@@ -8,6 +8,7 @@
 //   huff_write              final decode -> symbol stream, absolute DC (reference decode_huffman.cu:627-682)
 //   idct_kernel             gather + dequant + 8x8 fixed-point IDCT in stream order
 //                                                                    (reference idct.cu:44-223 + decode_transpose.cu:41-132)
+//   idct_scaled_kernel      the same at 1/2, 1/4, 1/8 size: libjpeg-turbo's reduced IDCTs (jidctred.c; jpeggpu_ext_set_scale)
 //
 // Everything is integer / bit-serial: no MFMA. Every kernel takes a job source: one ScanJob by
 // value (drop-in API) or an array indexed by blockIdx.y (batch API: one launch per stage for many
@@ -158,6 +159,17 @@ struct JobArrayLow {
     __device__ __forceinline__ const ScanJob& get() const { return jobs[blockIdx.y]; }
 };
 
+/// A batch's jobs as idct_kernel sees them when the batch mixes scales (jpeggpu_ext_set_scale): a scaled job reads as the
+/// empty job below (no data units), so that only the full-size ones are decoded at full size.
+__device__ ScanJob g_no_job;
+struct JobArrayFullSize {
+    const ScanJob* jobs;
+    __device__ __forceinline__ const ScanJob& get() const
+    {
+        const ScanJob& j = jobs[blockIdx.y];
+        return j.ip.scale_log2 == 0 ? j : g_no_job;
+    }
+};
 struct JobSingle {
     // One job that lives in device memory, whatever blockIdx.y is: the lone decode of a device-scanned image (the
     // second dimension of the multi-hypothesis kernels' grid is the hypothesis).
@@ -2573,6 +2585,202 @@ __global__ __launch_bounds__(256) void idct_kernel(JS js)
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// scaled decoding (jpeggpu_ext_set_scale): the reduced inverse DCTs of libjpeg-turbo's jidctred.c
+// ------------------------------------------------------------------------------------------------
+
+/// libjpeg's post-IDCT range limit (the sample_range_limit table indexed with x & RANGE_MASK, RANGE_MASK = 1023): x
+/// wrapped to a 10-bit signed value, clamped to -128..127, plus 128.
+__device__ __forceinline__ uint32_t range_limit(int x)
+{
+    const int w = static_cast<int>(static_cast<uint32_t>(x) << 22) >> 22;
+    return static_cast<uint32_t>(min(max(w, -128), 127) + 128);
+}
+
+/// jidctred.c's DESCALE: (x + 2^(n-1)) >> n, 64-bit (JLONG).
+template <int n>
+__device__ __forceinline__ long long descale(long long x)
+{
+    return (x + (1ll << (n - 1))) >> n;
+}
+
+constexpr int kRedConstBits = 13, kRedPass1Bits = 2; // jidctred.c CONST_BITS, PASS1_BITS
+
+/// The 4-point part of jpeg_idct_4x4 (both passes), from the inputs of rows / columns 0, 1, 2, 3, 5, 6, 7:
+/// outputs 0..3 before their DESCALE.
+__device__ __forceinline__ void idct4_red(long long v0, long long v1, long long v2, long long v3, long long v5, long long v6, long long v7,
+                                          long long (&o)[4])
+{
+    const long long t0 = v0 * (1ll << (kRedConstBits + 1));
+    const long long t2 = v2 * 15137 - v6 * 6270;                       // FIX(1.847759065), FIX(0.765366865)
+    const long long t10 = t0 + t2, t12 = t0 - t2;
+    const long long a = -v7 * 1730 + v5 * 11893 - v3 * 17799 + v1 * 8697; // FIX(0.211164243), (1.451774981), (2.172734803), (1.061594337)
+    const long long b = -v7 * 4176 - v5 * 4926 + v3 * 7373 + v1 * 20995;  // FIX(0.509795579), (0.601344887), (0.899976223), (2.562915447)
+    o[0] = t10 + b;
+    o[3] = t10 - b;
+    o[1] = t12 + a;
+    o[2] = t12 - a;
+}
+
+/// The 2-point part of jpeg_idct_2x2 (both passes), from the inputs of rows / columns 0, 1, 3, 5, 7: outputs 0, 1 before
+/// their DESCALE.
+__device__ __forceinline__ void idct2_red(long long v0, long long v1, long long v3, long long v5, long long v7, long long (&o)[2])
+{
+    const long long t10 = v0 * (1ll << (kRedConstBits + 2));
+    const long long t0  = -v7 * 5906 + v5 * 6967 - v3 * 10426 + v1 * 29692; // FIX(0.720959822), (0.850430095), (1.272758580), (3.624509785)
+    o[0] = t10 + t0;
+    o[1] = t10 - t0;
+}
+
+constexpr int kScaledDuPerWg = kIdctDuPerWg; // one data unit per lane, the grid of idct_kernel
+
+/// Scaled decode: one data unit per lane writes an N x N block, N = 8 >> kLg, at (block column * N, block row * N) of its
+/// plane, clipped to the scaled plane size. One instantiation per scale, launched for the scales a call holds: jobs of
+/// another scale (one job per blockIdx.y) leave at once. (One kernel that branched on the job's scale needed the
+/// registers of its largest branch, 151 VGPRs, for the 1/8 path as well.)
+///   * 1/8 (jpeg_idct_1x1): a gather and a store -- the unit's table record, its first (DC) entry, one quantiser. Units in
+///     stream order are neighbouring blocks of an MCU row, so neighbouring lanes store neighbouring bytes of a few rows.
+///   * 1/4, 1/2 (jpeg_idct_2x2, jpeg_idct_4x4): the unit's entries (and escapes, as in idct_kernel's rare path) are
+///     de-zigzagged into the lane's own column of LDS, a mask of 64 bits says which slots hold one (nothing to zero),
+///     and the two passes run in registers with jidctred.c's integer arithmetic: dequantisation in full int, 64-bit
+///     products, a 32-bit workspace between the passes, the range limit above.
+template <class JS, int kLg>
+__global__ __launch_bounds__(256) void idct_scaled_kernel(JS js)
+{
+    __shared__ int16_t s_coef[64][kScaledDuPerWg]; // [natural index][lane]: coefficients as stored, not yet dequantised
+    __shared__ uint16_t s_q[4 * 64];               // the quantisation tables, natural order
+    __shared__ uint8_t s_nat[64];                  // zig-zag index -> natural index
+
+    const JobView J(js.get());
+    const IdctParams& ip = J.ip;
+    constexpr int lg     = kLg;
+    const int du0        = blockIdx.x * kScaledDuPerWg;
+    const int num_du     = ip.num_du;
+    if (ip.scale_log2 != kLg || du0 >= num_du) return; // (uniform)
+    const int t  = threadIdx.x;
+    const int du = min(du0 + t, num_du - 1);
+
+    // geometry (idct_kernel's, at N pixels per block side)
+    const int rel = static_cast<int>(magic_quot(du, ip.du_per_mcu_mul, ip.du_per_mcu_shift));
+    const int k   = du - rel * ip.du_per_mcu;
+    const int mcu = rel + ip.first_mcu;
+    const int my  = static_cast<int>(magic_quot(mcu, ip.mcus_x_mul, ip.mcus_x_shift));
+    const int mx  = mcu - my * ip.mcus_x;
+    const int sc  = ip.du_comp[k];
+    const int n   = 8 >> lg;
+    const int x0  = (mx * ip.comp_h[sc] + ip.du_dx[k]) * n;
+    const int y0  = (my * ip.comp_v[sc] + ip.du_dy[k]) * n;
+    const int vx  = min(ip.size_x[sc] - x0, n), vy = min(ip.size_y[sc] - y0, n);
+    const bool active = du0 + t < num_du && vx > 0 && vy > 0;
+    const int pitch   = ip.pitch[sc];
+    const int qbase   = (ip.qidx[sc] & 3) * 64;
+    JG_GLOBAL uint8_t* const out = as_global(ip.plane[sc]) + static_cast<int64_t>(y0) * pitch + x0;
+
+    const uint2_t rec = ld_global(J.du_tab + du);
+    // a table entry that was never written (corrupt stream) must not lead out of the buffer: 127 entries from here stay inside
+    const uint64_t limit = J.sym_entries - 10 * kSymSectorStride;
+    const uint32_t first = static_cast<uint32_t>(rec.x < limit ? rec.x : limit);
+    const uint32_t cnt   = rec.y & 0x7Fu;
+    const auto entry_at  = [&](uint32_t index) -> uint32_t { return J.sym[index]; };
+    const int dc         = static_cast<int16_t>(entry_at(first)); // the unit's first entry: its DC coefficient, absolute
+
+    if constexpr (lg == 3) { // 1/8: jpeg_idct_1x1
+        if (active) *out = static_cast<uint8_t>(range_limit(static_cast<int>(descale<3>(static_cast<long long>(dc) * J.qtables[qbase]))));
+        return;
+    }
+
+    s_q[t] = J.qtables[t];
+    if (t < 64) {
+        constexpr uint8_t nat[64] = JG_ORDER_NATURAL;
+        s_nat[t] = nat[t];
+    }
+    __syncthreads();
+    if (!active) return;
+
+    // the unit's AC entries, eight loads at a time (the clamp above keeps entries up to 127 + 8 inside the buffer)
+    uint64_t mask  = 0;
+    const bool esc = (rec.y & kUnitHasEscape) != 0;
+    for (uint32_t i0 = 1; i0 < cnt; i0 += 8) {
+        uint32_t e[9];
+#pragma unroll
+        for (int j = 0; j < 9; ++j) { // (sym_advance, written out: a call here widens what the compiler knows of that function's
+                                      // argument in idct_kernel, and its code there changed)
+            const uint32_t w = (first & (kSymSectorEntries - 1u)) + i0 + j;
+            e[j]             = entry_at((first & ~(kSymSectorEntries - 1u)) + (w / kSymSectorEntries) * kSymSectorStride + (w & (kSymSectorEntries - 1u)));
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const uint32_t zz = sym_entry_index(e[j]);
+            if (i0 + j < cnt && zz != 0) { // index 0 behind the DC: the escape of the coefficient in front
+                const int v       = esc && i0 + j + 1 < cnt && sym_entry_index(e[j + 1]) == 0 ? sym_entry_value(e[j], e[j + 1]) : sym_entry_value(e[j]);
+                const uint32_t nt = s_nat[zz];
+                s_coef[nt][t]     = static_cast<int16_t>(v);
+                mask |= 1ull << nt;
+            }
+        }
+    }
+    // dequantised coefficient (row, col): DEQUANTIZE in full int
+    const auto coef = [&](int row, int col) -> long long {
+        const int i = row * 8 + col;
+        const int c = i == 0 ? dc : ((mask >> i) & 1u) ? s_coef[i][t] : 0;
+        return static_cast<long long>(c * static_cast<int>(s_q[qbase + i]));
+    };
+
+    if constexpr (lg == 1) { // 1/2: jpeg_idct_4x4 (column 4 and, in the second pass, workspace column 4 are never used)
+        int ws[4][8];
+#pragma unroll
+        for (int col = 0; col < 8; ++col) {
+            if (col == 4) continue;
+            long long o[4];
+            idct4_red(coef(0, col), coef(1, col), coef(2, col), coef(3, col), coef(5, col), coef(6, col), coef(7, col), o);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) ws[r][col] = static_cast<int>(descale<kRedConstBits - kRedPass1Bits + 1>(o[r]));
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            long long o[4];
+            idct4_red(ws[r][0], ws[r][1], ws[r][2], ws[r][3], ws[r][5], ws[r][6], ws[r][7], o);
+            uint32_t px = 0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) px |= range_limit(static_cast<int>(descale<kRedConstBits + kRedPass1Bits + 3 + 1>(o[c]))) << (8 * c);
+            if (r < vy) {
+                JG_GLOBAL uint8_t* row = out + static_cast<int64_t>(r) * pitch;
+                if (vx == 4 && (reinterpret_cast<uintptr_t>(row) & 3u) == 0) {
+                    *reinterpret_cast<JG_GLOBAL uint32_t*>(row) = px;
+                } else {
+                    for (int c = 0; c < vx; ++c) row[c] = static_cast<uint8_t>(px >> (8 * c));
+                }
+            }
+        }
+    } else { // 1/4: jpeg_idct_2x2 (rows and columns 0, 1, 3, 5, 7)
+        int ws[2][8];
+#pragma unroll
+        for (int col = 0; col < 8; ++col) {
+            if (col == 2 || col == 4 || col == 6) continue;
+            long long o[2];
+            idct2_red(coef(0, col), coef(1, col), coef(3, col), coef(5, col), coef(7, col), o);
+#pragma unroll
+            for (int r = 0; r < 2; ++r) ws[r][col] = static_cast<int>(descale<kRedConstBits - kRedPass1Bits + 2>(o[r]));
+        }
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            long long o[2];
+            idct2_red(ws[r][0], ws[r][1], ws[r][3], ws[r][5], ws[r][7], o);
+            const uint32_t p0 = range_limit(static_cast<int>(descale<kRedConstBits + kRedPass1Bits + 3 + 2>(o[0])));
+            const uint32_t p1 = range_limit(static_cast<int>(descale<kRedConstBits + kRedPass1Bits + 3 + 2>(o[1])));
+            if (r < vy) {
+                JG_GLOBAL uint8_t* row = out + static_cast<int64_t>(r) * pitch;
+                if (vx == 2 && (reinterpret_cast<uintptr_t>(row) & 1u) == 0) {
+                    *reinterpret_cast<JG_GLOBAL uint16_t*>(row) = static_cast<uint16_t>(p0 | p1 << 8);
+                } else {
+                    row[0] = static_cast<uint8_t>(p0);
+                    if (vx == 2) row[1] = static_cast<uint8_t>(p1);
+                }
+            }
+        }
+    }
+}
+
 /// Chroma replication: each lane produces 4 consecutive output pixels of one row.
 __global__ __launch_bounds__(256) void upsample_kernel(
     const uint8_t* __restrict__ src, int src_pitch, int src_w, int src_h,
@@ -2740,7 +2948,20 @@ hipError_t launch_any(Stage stage, const JS& js, const JobExtent& e, int grid_y,
         return hipGetLastError();
     case kStageIdct:
         if (e.max_idct_blocks == 0) return hipSuccess;
-        idct_kernel<JS><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(js);
+        // full-size jobs: idct_kernel; scaled ones (jpeggpu_ext_set_scale): idct_scaled_kernel, one launch per scale present.
+        // Only a batch can hold several; its idct_kernel then sees the scaled jobs as empty.
+        if (e.scales == 1u) {
+            idct_kernel<JS><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(js);
+        } else if (e.scales & 1u) {
+            if constexpr (std::is_same<JS, JobArray>::value)
+                idct_kernel<JobArrayFullSize><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(JobArrayFullSize{js.jobs});
+            else
+                return hipErrorInvalidValue; // the scans of one image share its scale
+        }
+        static_assert(kScaledDuPerWg == kIdctDuPerWg, "one grid for both");
+        if (e.scales & 2u) idct_scaled_kernel<JS, 1><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(js);
+        if (e.scales & 4u) idct_scaled_kernel<JS, 2><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(js);
+        if (e.scales & 8u) idct_scaled_kernel<JS, 3><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(js);
         return hipGetLastError();
     case kStageSyncIntra:
     case kStageSyncInter:
@@ -2809,6 +3030,7 @@ void extend(JobExtent& e, const ScanJob& job)
     e.max_seq         = job.num_seq > e.max_seq ? job.num_seq : e.max_seq;
     const int blocks  = (job.ip.num_du + kIdctDuPerWg - 1) / kIdctDuPerWg;
     e.max_idct_blocks = blocks > e.max_idct_blocks ? blocks : e.max_idct_blocks;
+    e.scales |= 1u << job.ip.scale_log2;
     e.max_tab_bytes   = job.sp.tab_bytes > e.max_tab_bytes ? job.sp.tab_bytes : e.max_tab_bytes;
     e.max_tab_bytes_sync = job.sp.tab_bytes_sync > e.max_tab_bytes_sync ? job.sp.tab_bytes_sync : e.max_tab_bytes_sync;
     e.subseq_words    = job.sp.subseq_words;

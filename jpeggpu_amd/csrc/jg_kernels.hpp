@@ -31,6 +31,7 @@ struct JobExtent {
     int max_tail_part   = 0; // subsequences in the largest tail part of any job
     int max_idct_blocks = 0;
     int subseq_words    = 0; // identical for every job of a launch
+    uint32_t scales     = 0; // bit s: a job decodes at 1 / 2^s (IdctParams::scale_log2)
     uint32_t max_tab_bytes = 0;      // largest write-pass table pack
     uint32_t max_tab_bytes_sync = 0; // largest sync pack
     bool fuse_tail_write = false;    // batch launches: the tail kernel's parts and the write pass's sequences as ONE launch
