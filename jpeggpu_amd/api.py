@@ -110,8 +110,7 @@ def lib():
     L.jpeggpu_decoder_cleanup.argtypes = [dec]
     L.jpeggpu_ext_set_subsequence_bytes.argtypes = [dec, C.c_int]
     L.jpeggpu_ext_set_batched.argtypes = [dec, C.c_int]
-    if hasattr(L, "jpeggpu_ext_set_batch_hint"):  # (a library built before round 5, loaded through JPEGGPU_LIB for an A/B run, has none)
-        L.jpeggpu_ext_set_batch_hint.argtypes = [dec, C.c_int]
+    L.jpeggpu_ext_set_batch_hint.argtypes = [dec, C.c_int]
     L.jpeggpu_ext_get_layout.argtypes = [dec, C.POINTER(ExtLayout)]
     L.jpeggpu_ext_set_profiling.argtypes = [dec, C.c_int]
     L.jpeggpu_ext_get_stage_ms.argtypes = [dec, C.POINTER(C.c_float)]
@@ -123,9 +122,8 @@ def lib():
     L.jpeggpu_ext_batch_set_profiling.argtypes = [C.c_void_p, C.c_int]
     L.jpeggpu_ext_batch_set_sync_iterations.argtypes = [C.c_void_p, C.c_int]
     L.jpeggpu_ext_batch_set_overlap.argtypes = [C.c_void_p, C.c_int]
-    if hasattr(L, "jpeggpu_ext_batch_set_fused_tail"):  # (experimental builds of older trees, JPEGGPU_LIB, lack it)
-        L.jpeggpu_ext_batch_set_fused_tail.argtypes = [C.c_void_p, C.c_int]
-        L.jpeggpu_ext_fused_tail_timeouts.argtypes = [C.POINTER(C.c_uint)]
+    L.jpeggpu_ext_batch_set_fused_tail.argtypes = [C.c_void_p, C.c_int]
+    L.jpeggpu_ext_fused_tail_timeouts.argtypes = [C.POINTER(C.c_uint)]
     L.jpeggpu_ext_batch_get_stage_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.jpeggpu_ext_upsample_planes.argtypes = [
         C.POINTER(ImgInfo), C.POINTER(Img), C.POINTER(Img), C.c_int, C.c_int, C.c_void_p]
@@ -133,8 +131,7 @@ def lib():
     L.jpeggpu_ext_get_shard_rows.argtypes = [dec, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.jpeggpu_ext_self_test.argtypes = [C.c_void_p]
     L.jpeggpu_ext_set_device_scan.argtypes = [dec, C.c_int]
-    if hasattr(L, "jpeggpu_ext_set_scale"):  # (experimental builds of older trees, JPEGGPU_LIB, lack it)
-        L.jpeggpu_ext_set_scale.argtypes = [dec, C.c_int]
+    L.jpeggpu_ext_set_scale.argtypes = [dec, C.c_int]
     L.jpeggpu_ext_get_device_status.argtypes = [dec, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
     L.jpeggpu_ext_parse_headers.argtypes = [C.POINTER(ParseItem), C.c_int, C.c_int, C.POINTER(C.c_int)]
     L.jpeggpu_ext_planes_to_rgbi.argtypes = [
@@ -186,10 +183,7 @@ class Decoder:
     def set_batch_hint(self, images_per_call: int):
         """About how many images of this kind share one jpeggpu_ext_decode_batch call (0: decoded on its own). The plan
         of the next parsed images -- subsequence size, multi-hypothesis speculation -- is made for a launch of that size."""
-        if hasattr(lib(), "jpeggpu_ext_set_batch_hint"):
-            _check(lib().jpeggpu_ext_set_batch_hint(self._h, int(images_per_call)), "jpeggpu_ext_set_batch_hint")
-        else:
-            self.set_batched(images_per_call > 0)
+        _check(lib().jpeggpu_ext_set_batch_hint(self._h, int(images_per_call)), "jpeggpu_ext_set_batch_hint")
 
     def parse_header(self, data, size=None) -> ImgInfo:
         """`data`: bytes, a numpy uint8 array, or an integer host address (then `size` is required).

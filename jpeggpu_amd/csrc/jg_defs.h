@@ -37,20 +37,14 @@ constexpr int kSeqSubseqBatch  = kSeqLanes - kSeqOverlapBatch;
 // lanes: 1024 590 us / 23.7 k (the 1024-lane kernel, two workgroups to a CU), 768 258 / 27.7 k, 512 250 / 27.0 k,
 // 384 390 / 26.4 k; with the flows spread over the four waves: 512 237, 640 212, 768 232, 900 223, 960 219, 1260 230,
 // 1920 241 us, images/s 27.8 ... 28.7 k, rising slowly with the size.
-#ifndef JG_TAIL_PART
-#define JG_TAIL_PART 960
-#endif
-constexpr int kTailPartSubseq = JG_TAIL_PART;
+constexpr int kTailPartSubseq = 960;
 // A batched call of fewer subsequences than this does not fill the chip (256 CUs x 5 workgroups of 255 lanes hold
 // 326 000): what it waits for is the chain of dependent flow iterations, as a lone decode does, and its sequence kernel
 // keeps every flow in the workgroup (jg_decoder.cpp, decode_batch_impl; jg_kernels.hip, JobArrayLow). Measured per call of
 // cfg-2 images at 256 bytes (11 400 subsequences each; us, flows kept / one iteration + marks + tail kernel, round 5):
 // 2: 530 / 567, 4: 561 / 613, 8: 626 / 678, 16: 828 / 878, 24: 1194 / 1113, 32: 1502 / 1408, 64: 2833 / 2418; the
 // reference's photo 16: 1034 / 1121, 32: 1895 / 1668.
-#ifndef JG_KEEP_FLOWS_BELOW
-#define JG_KEEP_FLOWS_BELOW 220000
-#endif
-constexpr long long kKeepFlowsBelowSubseq = JG_KEEP_FLOWS_BELOW;
+constexpr long long kKeepFlowsBelowSubseq = 220000;
 constexpr int kDestuffWin   = 4096; // stuffed bytes handled by one destuff workgroup (256 lanes x 16 B)
 
 /// Zig-zag index -> raster index inside a data unit (T.81 figure A.6; reference src/defs.hpp:94-102).
@@ -95,10 +89,7 @@ constexpr int kDestuffWin   = 4096; // stuffed bytes handled by one destuff work
 /// A lane keeps the entry of the data unit it is in; at the end of a data unit it loads the next one.
 /// This replaces per-symbol table selection arithmetic by one LDS read per symbol.
 constexpr int kLutBitsDc   = 9;
-#ifndef JG_LUT_BITS_AC
-#define JG_LUT_BITS_AC 11
-#endif
-constexpr int kLutBitsAc   = JG_LUT_BITS_AC;
+constexpr int kLutBitsAc   = 11;
 constexpr int kSubBits     = 5;
 constexpr int kSubTableSize = 2 << kSubBits; // bytes
 constexpr int kMaxSubTables = 16;
@@ -320,14 +311,11 @@ struct ScanParams {
 ///   kMhNoPool when the pool was full); mh_known[sub]: the table entry of sub is a state of the chain (an entry the
 ///   chain hopped over without pool entries is filled by the flow from upstream).
 constexpr int kMhMaxHyp        = 8;    // 4-bit candidate index; more data units per MCU: plain speculation
-#ifndef JG_MH_STEPS
-#define JG_MH_STEPS 8
-#endif
-constexpr int kMhSteps         = JG_MH_STEPS; // subsequences a candidate's flow runs before it gives up
+constexpr int kMhSteps         = 8;    // subsequences a candidate's flow runs before it gives up
 // the step count sits in a 4-bit link field and the pool hands out kMhSteps - 1 entries per flow; a run of entries the
 // chain hops over (kMhSteps - 1) must be shorter than the overlap zone of huff_sync_intra, or entries at the start of a
 // sequence would get their n / DC sums from no flow
-static_assert(kMhSteps >= 2 && kMhSteps <= 15 && kMhSteps - 1 < kSeqOverlap, "JG_MH_STEPS: link field, pool reservation, overlap zone");
+static_assert(kMhSteps >= 2 && kMhSteps <= 15 && kMhSteps - 1 < kSeqOverlap, "kMhSteps: link field, pool reservation, overlap zone");
 constexpr int kMhMaxSegSubseq  = 1024; // the chain walk of a segment -- or of one BLOCK of a longer segment -- happens in LDS
 /// Segments longer than that (a scan without restart markers is ONE segment) are walked BLOCK-WISE: every block of up to
 /// kMhMaxSegSubseq subsequences first works out, for each of the 64 nodes (candidate h, row 0..7) the chain can enter it

@@ -342,15 +342,9 @@ JG_HD inline void decode_subsequence(
 }
 
 /// Iterations of the write pass's loop between two DC SLOTS (below).
-#ifndef JG_WRITE_DC_PERIOD
-#define JG_WRITE_DC_PERIOD 4
-#endif
-constexpr int kWriteDcPeriod = JG_WRITE_DC_PERIOD; // a power of two
+constexpr int kWriteDcPeriod = 4; // a power of two
 /// ... and between two RARE SLOTS.
-#ifndef JG_WRITE_RARE_PERIOD
-#define JG_WRITE_RARE_PERIOD 8
-#endif
-constexpr int kWriteRarePeriod = JG_WRITE_RARE_PERIOD; // a power of two
+constexpr int kWriteRarePeriod = 8; // a power of two
 
 JG_HD inline uint32_t bit_mask(int s)
 {
@@ -451,7 +445,7 @@ JG_HD inline int extend_bits(uint32_t bits, int s)
 ///     window leaving its row -- WAITS for a rare slot, every kWriteRarePeriod-th iteration, and only there the wave
 ///     asks whether any lane has such a thing. A lane meets one less than three times per 256-byte subsequence, so the
 ///     waiting is cheap (3.5 iterations each); asked in every iteration the wave found some lane's in 27 % of them and
-///     ran the block's ~40 instructions (tools/probe/write_lane_iters.py).
+///     ran the block's ~40 instructions (EXPERIMENTS.md, "The write pass's loop, five rebuilds", item 4).
 ///   * Every kWriteDcPeriod-th iteration has a DC SLOT: the lanes that stand at the start of a data unit close the
 ///     record of the unit they finished, test the stop rule, load the next unit's cursor entry (tables, component),
 ///     decode the DC symbol and add it to the component's predictor. A lane that reaches a unit's end between two
@@ -474,7 +468,7 @@ JG_HD inline void decode_units(
     const ScanParams& sp,
     Sink& sink,
     int max_iters,
-    int* iters_out = nullptr) // probe builds: [0] iterations the lane's wave stayed in the loop, [1] symbols the lane decoded,
+    int* iters_out = nullptr) // the host emulation: [0] iterations the lane's wave stayed in the loop, [1] symbols the lane decoded,
                               // [2] times the wave took the rare block, [3] times this lane was a reason for it
 {
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -21,7 +21,6 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <type_traits>
 
 #include "jg_bytes.h"
@@ -438,9 +437,6 @@ struct GlobalFetch {
     }
     __device__ __forceinline__ uint32_t load(const Pos& q) const
     {
-#if defined(JG_EXP_FAKE_REFILL) // timing experiments only: no memory operation in the symbol loops (results are garbage)
-        if (kCrossRows) return q.off * 2654435761u ^ (q.off >> 7);
-#endif
         return *reinterpret_cast<JG_GLOBAL const uint32_t*>(reinterpret_cast<JG_GLOBAL const uint8_t*>(scan32) + q.off);
     }
     __device__ __forceinline__ uint32_t cook(uint32_t v, const Pos&) const { return v; }
@@ -545,32 +541,6 @@ struct RowWindow {
         last += step;
     }
 };
-
-#if defined(JG_PROBE)
-// Probe builds only (python jpeggpu_amd/build.py out.so -DJG_PROBE): 100 MHz time stamps of the passes of
-// huff_sync_intra, 64 per workgroup; read back with jpeggpu_probe_read (tools/probe/sync_stamps.py).
-__device__ uint32_t g_probe[4096 * 64];
-// huff_write: [0] sum over lanes of loop iterations (low 32 bits), [1] high bits, [2] largest, [3] lanes (tools/probe/write_iters.py)
-__device__ unsigned long long g_probe_write[4];
-// huff_write, the launch's first job, by subsequence: loop iterations of the lane's wave, then (from 1 << 16) symbols the
-// lane decoded (tools/probe/write_lane_iters.py)
-__device__ uint16_t g_probe_lane_iters[1 << 17];
-__device__ uint32_t g_probe_lane_rare[1 << 15]; // times the lane's wave took the rare block | times the lane asked for it << 16
-// huff_sync_tail, jobs 0..15 x parts 0..7 of a launch: 100 MHz stamps [0] start, [1] flow list built, [2 + k] after
-// trip k of the flow loop (all groups), [63] = flows | trips << 16 (tools/probe/tail_stamps.py)
-__device__ uint32_t g_probe_tail[128 * 64];
-#define JG_TAIL_STAMP(i, v)                                                                               \
-    do {                                                                                                  \
-        if (threadIdx.x == 0 && blockIdx.y < 16 && blockIdx.x < 8 && (i) < 64) g_probe_tail[(blockIdx.y * 8 + blockIdx.x) * 64 + (i)] = (v); \
-    } while (0)
-#define JG_STAMP(i)                                                                                       \
-    do {                                                                                                  \
-        if (threadIdx.x == 0 && blockIdx.x < 4096 && (i) < 64) g_probe[blockIdx.x * 64 + (i)] = static_cast<uint32_t>(wall_clock64()); \
-    } while (0)
-#else
-#define JG_STAMP(i) do { } while (0)
-#define JG_TAIL_STAMP(i, v) do { } while (0)
-#endif
 
 /// A pointer every lane of the wave holds the same value of, moved to scalar registers where the compiler cannot see that
 /// (huff_tail_write, whose job follows from a ticket): free where it can.
@@ -731,10 +701,8 @@ __global__ __launch_bounds__(T) void huff_sync_intra(JS js)
     const int img_first = first_sub - OV;                    // subsequence of lane 0
     const int img_end   = min(T, sp.num_subseq - img_first); // lanes below this have a subsequence
 
-    JG_STAMP(0);
     load_tables(s_tab, J.tables_sync, sp);
     __syncthreads();
-    JG_STAMP(1);
 
     constexpr int kBits = W * 32;
     const int sub       = img_first + t;
@@ -785,7 +753,6 @@ __global__ __launch_bounds__(T) void huff_sync_intra(JS js)
         s_cz[t] = st.c | (st.z << 8);
     }
     __syncthreads();
-    JG_STAMP(2);
 
     // Flow passes. Lane t first decodes subsequence j = t + 1 from the own exit state. With a state-only
     // speculative pass (and with the multi-hypothesis table) it also does so if j opens a restart segment -- from the
@@ -861,7 +828,6 @@ __global__ __launch_bounds__(T) void huff_sync_intra(JS js)
         }
         flowing = go;
         if (go) flowing = flow_step(++j);
-        JG_STAMP(3 + iter);
     }
     // Flows cut short by the iteration cap continue in huff_sync_tail from the entry they reached
     // last: mark that entry (flows still inside the overlap zone belong to the previous workgroup).
@@ -896,10 +862,7 @@ __global__ __launch_bounds__(T) void huff_sync_intra(JS js)
 /// Sequences a workgroup of the batch kernel takes, each on T of its lanes, all behind ONE copy of the table pack: what
 /// a CU holds of this kernel is bound by LDS, most of it the pack, and the kernel's time by how many waves a SIMD has to
 /// choose from (5 -> 4 workgroups per CU cost 21 %, round 4): two sequences per pack are 8 waves per SIMD instead of 5.
-#ifndef JG_BATCH_SEQ_PER_WG
-#define JG_BATCH_SEQ_PER_WG 2
-#endif
-constexpr int kBatchSeqPerWg = JG_BATCH_SEQ_PER_WG;
+constexpr int kBatchSeqPerWg = 2;
 struct SeqLdsBatch {
     static constexpr uint32_t kState = 0;
     static constexpr uint32_t kOne   = (6 * (T + 1) * 4 + 64 + 15) / 16 * 16; // one sequence's 5 state arrays / scan scratch
@@ -969,11 +932,9 @@ __global__ __launch_bounds__(T * kBatchSeqPerWg) void huff_sync_intra_batch(JS j
     // latencies that used to follow the copy)
     const int lane_seg = J.seg_idx[active ? sub : 0];
 
-    JG_STAMP(0);
     load_tables(s_tab, J.tables_sync, sp);
     const Segment lane_segment = ld_global(J.segments + lane_seg);
     __syncthreads();
-    JG_STAMP(1);
 
     // Multi-hypothesis speculation (jg_defs.h): the table this kernel starts from was written by huff_mh_resolve -- for
     // every subsequence the candidate state the chain of links passes through -- instead of being speculated here. The
@@ -1020,7 +981,6 @@ __global__ __launch_bounds__(T * kBatchSeqPerWg) void huff_sync_intra_batch(JS j
         s_cz[t] = st.c | (st.z << 8);
     }
     __syncthreads();
-    JG_STAMP(2);
 
     // Flow passes. Lane t first decodes subsequence j = t + 1 from the own exit state. With a state-only
     // speculative pass (and with the multi-hypothesis table) it also does so if j opens a restart segment -- from the
@@ -1065,7 +1025,6 @@ __global__ __launch_bounds__(T * kBatchSeqPerWg) void huff_sync_intra_batch(JS j
             flowing = false;
         }
         const bool more = __syncthreads_or(flowing && j + 1 < lim);
-        JG_STAMP(3 + iter);
         if (!more) break;
     }
     // Flows cut short by the iteration cap continue in huff_sync_tail from the entry they reached
@@ -1428,13 +1387,8 @@ __global__ __launch_bounds__(256) void huff_mh_resolve(JS js)
 /// kernel lives must not hold the wave slots other streams' kernels need (16-wave workgroups held 3/4 of them: -8 %
 /// throughput with overlapping streams). A scan without restart markers is one part with thousands of flows: 1024
 /// lanes, or its ordered groups of flows would run one after the other.
-#ifndef JG_TAIL_LANES_SMALL
-#define JG_TAIL_LANES_SMALL 256
-#endif
-#ifndef JG_TAIL_LARGE_FROM
-#define JG_TAIL_LARGE_FROM 4096 // (1024-lane workgroups fit two to a CU: parts of ~1060 subsequences in them took 590 us per 64 images)
-#endif
-constexpr int kTailLanesSmall = JG_TAIL_LANES_SMALL, kTailLanesLarge = 1024, kTailLargeFrom = JG_TAIL_LARGE_FROM;
+constexpr int kTailLanesLarge = 1024;
+constexpr int kTailLargeFrom  = 4096; // (1024-lane workgroups fit two to a CU: parts of ~1060 subsequences in them took 590 us per 64 images)
 
 /// tails[b] (huff_seq_tails below: the sums of n and of the DC differences over the subsequences of sequence b that belong
 /// to the segment still open at b's end) for the sequences whose LAST subsequence lies in [lo, hi): a part is a run of whole
@@ -1506,19 +1460,16 @@ __device__ __forceinline__ void tail_part(const JobView& J, int part, uint8_t* s
     int* s_cz      = s_pz + TL;                    // its c | z << 8
     uint8_t* s_tab = reinterpret_cast<uint8_t*>(s_cz + TL);
 
-#if !defined(JG_NO_TAIL_PRIO)
     // A part is a chain of dependent instructions of a few lanes: where its waves share a SIMD with the waves of throughput
     // kernels (other streams' launches; the writers of huff_tail_write) they go first -- what they ask of the issue slots is
     // next to nothing, and everything downstream waits for them.
     __builtin_amdgcn_s_setprio(3);
-#endif
     ScanParams sp          = J.sp;
     sp.use_sync_pack();
     JG_GLOBAL const uint32_t* scan32 = reinterpret_cast<JG_GLOBAL const uint32_t*>(J.destuffed);
     const int lo           = J.tail_parts[part];
     const int hi           = J.tail_parts[part + 1];
     const int tid          = threadIdx.x;
-    JG_TAIL_STAMP(0, static_cast<uint32_t>(wall_clock64()));
 
     // Ordered list of flow origins in [lo, hi): the marks huff_sync_intra left, and the sequence boundaries at which the
     // exit state the following sequence's workgroup assumed for its predecessor (bnd_p / bnd_cz) is not the one stored:
@@ -1559,8 +1510,6 @@ __device__ __forceinline__ void tail_part(const JobView& J, int part, uint8_t* s
     }
     load_tables(s_tab, J.tables_sync, sp);
     __syncthreads(); // list and tables visible to the whole workgroup
-    JG_TAIL_STAMP(1, static_cast<uint32_t>(wall_clock64()));
-    [[maybe_unused]] int trips = 0;
 
     NoSink sink;
     for (int g = 0; g < count; g += TL) {
@@ -1608,11 +1557,6 @@ __device__ __forceinline__ void tail_part(const JobView& J, int part, uint8_t* s
             // that makes this iteration's state stores visible to the next one)
             int rank;
             const int total = block_rank<TL>(flowing, s_wave, rank);
-            if (trips < 30) {
-                JG_TAIL_STAMP(2 + trips, static_cast<uint32_t>(wall_clock64()));
-                JG_TAIL_STAMP(32 + trips, static_cast<uint32_t>(__syncthreads_count(live))); // flows of the trip
-            }
-            ++trips;
             if (total == 0) break;
             if (flowing) {
                 s_j[rank]  = j;
@@ -1629,7 +1573,6 @@ __device__ __forceinline__ void tail_part(const JobView& J, int part, uint8_t* s
         }
         __syncthreads();
     }
-    JG_TAIL_STAMP(63, static_cast<uint32_t>(count) | static_cast<uint32_t>(trips) << 16);
     if constexpr (kFusedTails) {
         __syncthreads(); // every flow's stores are done and visible to the workgroup
         part_seq_tails<TL, kCoherent>(J, lo, hi, s_red);
@@ -1701,20 +1644,13 @@ constexpr int kRingWords    = 16;                         // 32-bit words of a l
 constexpr int kRingStride   = (kRingWords + 1) * 4;       // bytes from one lane's ring to the next: 17 words, an odd number of banks
 constexpr int kStageEntries = 2 * kRingWords;             // entries the ring holds (a power of two)
 constexpr int kFlushEntries = kSymSectorEntries;          // entries per flush: 16 = one 32-byte sector
-#ifndef JG_WRITE_FLUSH_PERIOD
-#define JG_WRITE_FLUSH_PERIOD 12
-#endif
-constexpr int kWriteFlushPeriod = JG_WRITE_FLUSH_PERIOD;  // iterations between two flush points
+constexpr int kWriteFlushPeriod = 12;                     // iterations between two flush points
 // what a flush point leaves behind (less than a sector) + what arrives until the next one (one entry per iteration and
 // one per DC slot; an ESCAPE entry, which no photograph has, flushes for itself when a sector is waiting: one more)
 // must fit the ring
 static_assert(kFlushEntries - 1 + kWriteFlushPeriod + (kWriteFlushPeriod + kWriteDcPeriod - 1) / kWriteDcPeriod + 1 <= kStageEntries, "the write-combining ring would overflow");
-#ifndef JG_UNIT_TURN
-#define JG_UNIT_TURN 1
-#endif
-constexpr int kUnitTurn = JG_UNIT_TURN;                   // flush points between two stores of data-unit records (a power of two)
-// A DC slot adds at most one waiting record, a turn leaves at most three, StreamSink holds eight.
-static_assert(3 + kUnitTurn * ((kWriteFlushPeriod + kWriteDcPeriod - 1) / kWriteDcPeriod) <= 8, "waiting unit records would overflow");
+// A DC slot adds at most one waiting record, a flush point leaves at most three, StreamSink holds eight.
+static_assert(3 + (kWriteFlushPeriod + kWriteDcPeriod - 1) / kWriteDcPeriod <= 8, "waiting unit records would overflow");
 
 /// Sink of the write pass: a compact symbol stream instead of a dense coefficient buffer (jg_defs.h). Every lane
 /// appends 16-bit entries to its own region, contiguous per data unit, and records {first entry, count} per
@@ -1770,7 +1706,7 @@ struct StreamSink {
     }
     /// DC slot, a lane at the start of a data unit: the unit it finished since the previous slot (if it has started
     /// one) is complete -- its entry count joins the waiting records at the top. At most one per slot, three between
-    /// flush points; every kUnitTurn-th flush point leaves at most three waiting: eight places are enough.
+    /// flush points; every flush point leaves at most three waiting: eight places are enough.
     __device__ __forceinline__ void unit_boundary()
     {
         if (started) {
@@ -1820,9 +1756,6 @@ struct StreamSink {
             off += k < n ? cnt & 0x7Fu : 0u;
         }
         JG_GLOBAL uint2_t* dst = du_tab + rec_du;
-#if defined(JG_EXP_NO_UNIT_STORES) // traffic experiments only (tools/probe/pmc_lib.sh): results are wrong
-        if (rec[0].x == 0xFFFFFFFEu)
-#endif
         if (n == 4 && (rec_du & 3) == 0) { // a whole, aligned sector of the table
             st_global(reinterpret_cast<JG_GLOBAL uint4*>(dst), make_uint4(rec[0].x, rec[0].y, rec[1].x, rec[1].y));
             st_global(reinterpret_cast<JG_GLOBAL uint4*>(dst) + 1, make_uint4(rec[2].x, rec[2].y, rec[3].x, rec[3].y));
@@ -1851,21 +1784,17 @@ struct StreamSink {
         for (int k = 0; k < kFlushEntries / 2; ++k) e[k] = *reinterpret_cast<const LdsWord*>(static_cast<uintptr_t>(r + k * 4));
         static_assert(kFlushEntries == 16, "a flush is one sector of the interleaved stream");
         JG_GLOBAL uint4* dst = reinterpret_cast<JG_GLOBAL uint4*>(sym + sym_at(base, flushed));
-#if defined(JG_EXP_NO_SECTOR_STORES)
-        if (e[0] == 0xFFFFFFFEu && e[1] == 0x12345678u)
-#endif
         if (flushed < cur_end) { // a region cannot overflow on a valid stream; a corrupt one loses what lies beyond it
             st_global(dst, make_uint4(e[0], e[1], e[2], e[3]));
             st_global(dst + 1, make_uint4(e[4], e[5], e[6], e[7]));
         }
         flushed += kFlushEntries;
     }
-    /// Every kFlushPeriod-th iteration, the same one for every lane of the wave; `no` counts them. The unit records
-    /// take every kUnitTurn-th.
-    __device__ __forceinline__ void flush_point(int no)
+    /// Every kFlushPeriod-th iteration, the same one for every lane of the wave; the argument counts them.
+    __device__ __forceinline__ void flush_point(int)
     {
         if (started && emitted - flushed >= static_cast<uint32_t>(kFlushEntries)) flush_sector();
-        if ((no & (kUnitTurn - 1)) == 0) flush_units();
+        flush_units();
     }
     /// After the loop: everything that is left, rounded up to whole sectors (the entries behind the
     /// last valid one are never read: the data-unit table bounds every gather).
@@ -2047,20 +1976,7 @@ __device__ __forceinline__ void write_sequence(const JobView& J, int seq, uint8_
     constexpr int kItersPerBitX2 = kWriteDcPeriod > 2 ? kWriteDcPeriod : 2; // iterations per TWO bits, worst case
     constexpr int kMaxIters      = kItersPerBitX2 * (W * 32 + 64 * 32) / 2 + 2 * kWriteRarePeriod;
     static_assert(kWriteRarePeriod <= 11, "a symbol that waits for the rare slot must not wait longer than its bits allow for");
-#if defined(JG_PROBE)
-    int iters[4] = {0, 0, 0, 0};
-    decode_units(st, words, s_tab, sp, sink, kMaxIters, iters);
-    atomicAdd(&g_probe_write[0], static_cast<unsigned long long>(iters[0]));
-    atomicMax(&g_probe_write[2], static_cast<unsigned long long>(iters[0]));
-    atomicAdd(&g_probe_write[3], 1ull);
-    if (blockIdx.y == 0 && sub < (1 << 16)) {
-        g_probe_lane_iters[sub]             = static_cast<uint16_t>(iters[0]);
-        g_probe_lane_iters[(1 << 16) + sub] = static_cast<uint16_t>(iters[1]);
-        if (sub < (1 << 15)) g_probe_lane_rare[sub] = static_cast<uint32_t>(iters[2]) | static_cast<uint32_t>(iters[3]) << 16;
-    }
-#else
     decode_units(st, words, s_tab, sp, sink, kMaxIters);
-#endif
     sink.finish();
 }
 
@@ -2411,15 +2327,6 @@ __global__ __launch_bounds__(256) void idct_kernel(JS js)
     asm volatile("" : "+v"(zero4)); // four registers that stay zero: the compiler would set them up again in every iteration
     const uint2* const px_mine = &s_px[0][t & 31][t >> 5];
     const uint8_t* const qcol_mine = reinterpret_cast<const uint8_t*>(s_qcol) + r * 16;
-#ifndef JG_IDCT_PAIRS
-#define JG_IDCT_PAIRS 2
-#endif
-#ifndef JG_IDCT_DEPTH
-#define JG_IDCT_DEPTH 2
-#endif
-#ifndef JG_IDCT_UNCOND
-#define JG_IDCT_UNCOND 1
-#endif
     // Entry PAIRS per lane, fetched kDepth iterations ahead: the lane reads the aligned 32-bit words r, r + 8, ... of
     // the sector row its unit starts in, counted from the word that holds the unit's first entry. Eight words further
     // is the same word of the next sector (one 32-byte sector = 16 entries = 8 words): +2048 bytes. With an odd first
@@ -2428,31 +2335,30 @@ __global__ __launch_bounds__(256) void idct_kernel(JS js)
     // without branches around the loads the compiler can count them, and the wait for one iteration's words leaves
     // the next one's in flight. (Up to round 4 the lanes read single entries under a compare and a branch each: twice
     // the loads, twice the address arithmetic, and one wait for everything.)
-    constexpr int kPairs = JG_IDCT_PAIRS;
+    constexpr int kPairs = 2;
     static_assert(kPairs * kSymSectorStride * 2 <= 4096 + 2048, "immediate offsets of the loads");
-    constexpr int kDepth = JG_IDCT_DEPTH; // iterations the fetches run ahead
+    constexpr int kDepth = 2; // iterations the fetches run ahead
     uint32_t pre[kIdctIters + kDepth][kPairs];
     const auto entry_at = [&](uint32_t index) -> uint32_t {
         return *reinterpret_cast<JG_GLOBAL const uint16_t*>(reinterpret_cast<JG_GLOBAL const uint8_t*>(J.sym) + index * 2u);
     };
     // Entry j of the unit sits in half (j + odd) & 1 of word (j + odd) / 2 counted as above; a lane's word k holds
     // the entries jb + 16 k and jb + 16 k + 1, jb = 2 r - odd.
-    const auto prefetch = [&](uint32_t first, uint32_t cnt, uint32_t (&out)[kPairs]) {
+    const auto prefetch = [&](uint32_t first, uint32_t (&out)[kPairs]) {
         // the word that holds the unit's first entry, r words on; past the end of the 8-word sector: the next sector
         const uint32_t word = first >> 1;
         const uint32_t over = ((word & 7u) + static_cast<uint32_t>(r)) & 8u;
         const uint32_t base = word * 4u + static_cast<uint32_t>(r) * 4u + over * ((kSymSectorStride * 2u - 32u) / 8u);
-        const int jb        = 2 * r - static_cast<int>(first & 1u);
         JG_GLOBAL const uint8_t* stream = reinterpret_cast<JG_GLOBAL const uint8_t*>(J.sym);
 #pragma unroll
         for (int k = 0; k < kPairs; ++k)
-            out[k] = (JG_IDCT_UNCOND || jb + 16 * k < static_cast<int>(cnt)) ? *reinterpret_cast<JG_GLOBAL const uint32_t*>(stream + (base + k * (kSymSectorStride * 2u))) : 0u;
+            out[k] = *reinterpret_cast<JG_GLOBAL const uint32_t*>(stream + (base + k * (kSymSectorStride * 2u)));
     };
 
     {
         // (the first entries: asked for behind the geometry's loads, so that waiting for those does not wait for these)
 #pragma unroll
-        for (int d = 0; d < kDepth; ++d) prefetch(toff[d], tcnt[d] & 0x7Fu, pre[d]);
+        for (int d = 0; d < kDepth; ++d) prefetch(toff[d], pre[d]);
         const int sc = static_cast<int>(from_lane(gk, unit_byte));
         const int dx = static_cast<int>(from_lane(10 + gk, unit_byte)), dy = static_cast<int>(from_lane(20 + gk, unit_byte));
         const int comp_h = static_cast<int>(from_lane(sc, comp_word)), comp_v = static_cast<int>(from_lane(4 + sc, comp_word));
@@ -2476,7 +2382,7 @@ __global__ __launch_bounds__(256) void idct_kernel(JS js)
         uint32_t ex[kPairs];
 #pragma unroll
         for (int k = 0; k < kPairs; ++k) ex[k] = pre[it][k];
-        if (it + kDepth < kIdctIters) prefetch(toff[it + kDepth], tcnt[it + kDepth] & 0x7Fu, pre[it + kDepth]); // in flight while this one computes
+        if (it + kDepth < kIdctIters) prefetch(toff[it + kDepth], pre[it + kDepth]); // in flight while this one computes
         // The 8 lanes of a data unit sit in one wave and LDS executes a wave's instructions in order,
         // so the phases below need no workgroup barrier among themselves; only the pixel re-mapping
         // at the end crosses waves (one barrier per iteration, buffers alternate).
@@ -2900,17 +2806,12 @@ hipError_t launch_huff(Stage stage, const JS& js, const JobExtent& e, int grid_y
                 constexpr int TL = kTailLanesLarge;
                 huff_sync_tail<W, TL, JS><<<dim3(e.max_tail_parts, grid_y), TL, 3 * TL * 4 + e.max_tab_bytes_sync, stream>>>(js);
             } else {
-                constexpr int TL = kTailLanesSmall;
-                huff_sync_tail<W, TL, JS><<<dim3(e.max_tail_parts, grid_y), TL, 3 * TL * 4 + e.max_tab_bytes_sync, stream>>>(js);
+                huff_sync_tail<W, T, JS><<<dim3(e.max_tail_parts, grid_y), T, 3 * T * 4 + e.max_tab_bytes_sync, stream>>>(js);
             }
         }
         break;
     case kStageWrite: {
         size_t lds = WriteLds::kTabs + e.max_tab_bytes;
-#if defined(JG_PROBE) // occupancy experiments: JPEGGPU_EXP_EXTRA_LDS bytes of LDS nobody uses (fewer workgroups per CU)
-        if (const char* x = std::getenv("JPEGGPU_EXP_EXTRA_LDS")) lds += static_cast<size_t>(std::atoi(x));
-        if ((err = allow_lds(huff_write<W, JS>, lds)) != hipSuccess) return err;
-#endif
         if constexpr (std::is_same<JS, JobArray>::value) {
             if (fuses_tail_write(e, grid_y)) { // the parts of the tail kernel and the sequences of the write pass, by ticket
                 const size_t tail_lds = 3 * T * 4 + e.max_tab_bytes_sync;
@@ -2979,43 +2880,6 @@ hipError_t launch_any(Stage stage, const JS& js, const JobExtent& e, int grid_y,
 }
 
 } // namespace
-
-#if defined(JG_PROBE)
-extern "C" __attribute__((visibility("default"))) int jpeggpu_probe_read_write(unsigned long long* dst4, int clear)
-{
-    if (hipMemcpyFromSymbol(dst4, HIP_SYMBOL(g_probe_write), sizeof(g_probe_write)) != hipSuccess) return 1;
-    if (clear) {
-        void* p = nullptr;
-        if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_probe_write)) != hipSuccess || hipMemset(p, 0, sizeof(g_probe_write)) != hipSuccess) return 2;
-    }
-    return 0;
-}
-
-extern "C" __attribute__((visibility("default"))) int jpeggpu_probe_read_lane_iters(uint16_t* dst, size_t count)
-{
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_probe_lane_iters), count * 2) == hipSuccess ? 0 : 1;
-}
-
-extern "C" __attribute__((visibility("default"))) int jpeggpu_probe_read_lane_rare(uint32_t* dst, size_t count)
-{
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_probe_lane_rare), count * 4) == hipSuccess ? 0 : 1;
-}
-
-extern "C" __attribute__((visibility("default"))) int jpeggpu_probe_read_tail(uint32_t* dst, size_t count)
-{
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_probe_tail), count * 4) == hipSuccess ? 0 : 1;
-}
-
-extern "C" __attribute__((visibility("default"))) int jpeggpu_probe_read(void* dst, size_t bytes, int clear)
-{
-    if (hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_probe), bytes) != hipSuccess) return 1;
-    if (clear) {
-        void* p = nullptr;
-        if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_probe)) != hipSuccess || hipMemset(p, 0, sizeof(g_probe)) != hipSuccess) return 2;
-    }
-    return 0;
-}
-#endif
 
 hipError_t read_fuse_timeouts(unsigned int* count)
 {

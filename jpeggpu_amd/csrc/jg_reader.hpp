@@ -101,10 +101,7 @@ constexpr int kSubseqAutoLone = 0, kSubseqAutoBatched = -kBatchHintFull;
 /// Calls of so few images get the plan of a lone decode (multi-hypothesis tables, the lone decode's subsequence size) and
 /// jpeggpu_ext_decode_batch decodes them one by one: the chip is empty either way, and what such a call waits for is the
 /// chain of dependent passes the speculation shortens (jg_defs.h).
-#ifndef JG_LONE_PLAN_IMAGES
-#define JG_LONE_PLAN_IMAGES 1
-#endif
-constexpr int kLonePlanImages = JG_LONE_PLAN_IMAGES;
+constexpr int kLonePlanImages = 1;
 inline bool lone_plan(int images_per_call) { return images_per_call <= kLonePlanImages; }
 
 /// Subsequence size for an image whose first scan has `scan_bytes_bound` bytes at most, in `segments` restart segments,
