@@ -19,6 +19,8 @@
  *                                      part of the reference's host helper util/util.h:62-91
  *   jpeggpu_ext_set_scale              decode at 1/2, 1/4 or 1/8 size (libjpeg's scale_num / scale_denom), bit-exact with
  *                                      libjpeg-turbo's reduced IDCTs
+ *   jpeggpu_ext_set_idct               full-size IDCT: the reference's (default) or libjpeg-turbo's jpeg_idct_islow
+ *   jpeggpu_ext_planes_to_rgbi_fancy   libjpeg's fancy chroma upsampling + integer YCbCr -> interleaved RGB8
  */
 #ifndef JPEGGPU_JPEGGPU_EXT_H_
 #define JPEGGPU_JPEGGPU_EXT_H_
@@ -165,6 +167,21 @@ enum jpeggpu_status jpeggpu_ext_get_device_status(
  *     (d_tmp sizing) do not depend on the scale. */
 enum jpeggpu_status jpeggpu_ext_set_scale(jpeggpu_decoder_t decoder, int scale_denom);
 
+/* The full-size inverse DCT. JPEGGPU_EXT_IDCT_REFERENCE (the default) is the reference's fixed-point transform;
+ * JPEGGPU_EXT_IDCT_ISLOW is libjpeg-turbo's jpeg_idct_islow (jidctint.c), the IDCT of Pillow, torchvision and OpenCV:
+ * dequantisation in full int, CONST_BITS = 13, PASS1_BITS = 2, a 32-bit workspace between the passes and its
+ * 10-bit-wrapping range limit. Planes decoded with it equal libjpeg's (jpeg_read_raw_data) bit for bit; with
+ * jpeggpu_ext_planes_to_rgbi_fancy on top, so does the RGB output (jpeg_read_scanlines, JCS_RGB). Any other value:
+ * JPEGGPU_INVALID_ARGUMENT.
+ *   - Takes effect at the next jpeggpu_decoder_parse_header, like jpeggpu_ext_set_scale, and only at scale 1 (the reduced
+ *     IDCTs are libjpeg's already).
+ *   - Only the IDCT stage changes: plane sizes, jpeggpu_decoder_get_buffer_size, transfer, the Huffman kernels, segment
+ *     shards and the device marker scan behave as with the reference IDCT. A batch may mix methods and scales.
+ *   - The environment's JPEGGPU_IDCT=islow, read at jpeggpu_decoder_startup, selects it for a caller of the drop-in API
+ *     alone. */
+enum jpeggpu_ext_idct { JPEGGPU_EXT_IDCT_REFERENCE = 0, JPEGGPU_EXT_IDCT_ISLOW = 1 };
+enum jpeggpu_status jpeggpu_ext_set_idct(jpeggpu_decoder_t decoder, enum jpeggpu_ext_idct method);
+
 /* Stage timing: when enabled, jpeggpu_decoder_decode records HIP events on the caller's stream
  * between its launches; after the stream has been synchronised jpeggpu_ext_get_stage_ms returns the
  * mean milliseconds per stage (summed over scans) of the decodes since the previous call (at most the
@@ -275,6 +292,24 @@ enum jpeggpu_status jpeggpu_ext_parse_headers(
  * reference's host helper conv_to_rgbi (util/util.h:62-104). dst[y * dst_pitch + 3 * x + {0,1,2}] = R,G,B.
  * JPEGGPU_NOT_SUPPORTED for 2 or 4 components, as the helper. */
 enum jpeggpu_status jpeggpu_ext_planes_to_rgbi(
+    const struct jpeggpu_img_info* info,
+    const struct jpeggpu_img* src,
+    uint8_t* dst,
+    int dst_pitch,
+    int width,
+    int height,
+    jpeggpu_stream_t stream);
+
+/* The same contract and return codes as jpeggpu_ext_planes_to_rgbi, with libjpeg's arithmetic: fancy upsampling
+ * (jdsample.c, do_fancy_upsampling on) and the integer YCbCr -> RGB conversion of jdcolor.c. Per component, by the ratio
+ * h_max / h_c, v_max / v_c: 1x1 a copy; 2x1 h2v1_fancy_upsample; 2x2 h2v2_fancy_upsample (both replication instead when
+ * the plane is at most 2 samples wide); 1x2 h1v2_fancy_upsample; other integral ratios replication; a non-integral ratio
+ * JPEGGPU_NOT_SUPPORTED. The plane's edges are those of info's sizes (libjpeg's downsampled_width / _height): the samples
+ * beyond them are copies of the edge samples. R = Y + ((91881 Cr + 2^15) >> 16), G = Y + ((-22554 Cb - 46802 Cr + 2^15)
+ * >> 16), B = Y + ((116130 Cb + 2^15) >> 16), Cb and Cr centred on 128, each clamped to 0..255; one component is copied
+ * to R, G and B. On planes of a JPEGGPU_EXT_IDCT_ISLOW decode this is what libjpeg-turbo (and Pillow's
+ * Image.convert("RGB")) returns. */
+enum jpeggpu_status jpeggpu_ext_planes_to_rgbi_fancy(
     const struct jpeggpu_img_info* info,
     const struct jpeggpu_img* src,
     uint8_t* dst,

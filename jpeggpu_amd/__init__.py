@@ -11,9 +11,11 @@ from .api import (  # noqa: F401
     JpegGpuError,
     Status,
     decode_to_planes,
+    decode_to_rgb,
     fused_tail_timeouts,
     lib,
     parse_headers,
+    planes_to_rgb,
     self_test,
     status_string,
 )

@@ -14,6 +14,7 @@ from . import build as _build
 
 MAX_COMP = 4
 STAGES = ("front", "destuff", "sync_intra", "sync_inter", "tails", "write", "idct")
+IDCT_METHODS = {"reference": 0, "islow": 1}  # enum jpeggpu_ext_idct
 
 
 class Status(enum.IntEnum):
@@ -132,9 +133,12 @@ def lib():
     L.jpeggpu_ext_self_test.argtypes = [C.c_void_p]
     L.jpeggpu_ext_set_device_scan.argtypes = [dec, C.c_int]
     L.jpeggpu_ext_set_scale.argtypes = [dec, C.c_int]
+    L.jpeggpu_ext_set_idct.argtypes = [dec, C.c_int]
     L.jpeggpu_ext_get_device_status.argtypes = [dec, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
     L.jpeggpu_ext_parse_headers.argtypes = [C.POINTER(ParseItem), C.c_int, C.c_int, C.POINTER(C.c_int)]
     L.jpeggpu_ext_planes_to_rgbi.argtypes = [
+        C.POINTER(ImgInfo), C.POINTER(Img), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.jpeggpu_ext_planes_to_rgbi_fancy.argtypes = [
         C.POINTER(ImgInfo), C.POINTER(Img), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     _lib = L
     return L
@@ -209,6 +213,13 @@ class Decoder:
         """Decode the next parsed images at 1 / scale_denom (1, 2, 4 or 8): planes of ceil(size / scale_denom), the
         arithmetic of libjpeg-turbo's reduced IDCTs (jpeggpu_ext_set_scale)."""
         _check(lib().jpeggpu_ext_set_scale(self._h, int(scale_denom)), "jpeggpu_ext_set_scale")
+
+    def set_idct(self, method: str):
+        """The full-size IDCT of the next parsed images: "reference" (the default) or "islow", libjpeg-turbo's
+        jpeg_idct_islow, the transform of Pillow, torchvision and OpenCV (jpeggpu_ext_set_idct)."""
+        if method not in IDCT_METHODS:
+            raise ValueError("idct method %r is not one of %s" % (method, ", ".join(IDCT_METHODS)))
+        _check(lib().jpeggpu_ext_set_idct(self._h, IDCT_METHODS[method]), "jpeggpu_ext_set_idct")
 
     def set_segment_shard(self, rank: int, world: int):
         """Decode only restart segments [rank * n / world, (rank + 1) * n / world) of the next parsed images."""
@@ -340,17 +351,20 @@ def self_test(stream: int = 0) -> None:
     _check(lib().jpeggpu_ext_self_test(stream), "jpeggpu_ext_self_test")
 
 
-def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp=False, device_scan=False, scale=1):
+def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp=False, device_scan=False, scale=1,
+                     idct="reference"):
     """Convenience wrapper used by tests: full call sequence on torch's current stream, returns the
     planes as torch uint8 tensors on `device` (torch is only the allocator / stream provider). With
     `device_scan` the restart markers are found on the device and a status it reports there is raised.
-    `scale`: 1, 2, 4 or 8 -- planes at 1 / scale (Decoder.set_scale)."""
+    `scale`: 1, 2, 4 or 8 -- planes at 1 / scale (Decoder.set_scale). `idct`: "reference" or "islow" (Decoder.set_idct)."""
     import torch
 
     dec = Decoder(subseq_bytes)
     try:
         if scale != 1:
             dec.set_scale(scale)
+        if idct != "reference":
+            dec.set_idct(idct)
         if device_scan:
             dec.set_device_scan(True)
         info = dec.parse_header(data)
@@ -370,6 +384,41 @@ def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp
         return planes, info
     finally:
         dec.cleanup()
+
+
+def planes_to_rgb(planes, info, fancy=True, device=None):
+    """Planes of a 1- or 3-component image (as decode_to_planes returns them) -> (H, W, 3) uint8 tensor at the full image
+    size, on torch's current stream: jpeggpu_ext_planes_to_rgbi_fancy (libjpeg's fancy upsampling and integer colour
+    conversion) or, with fancy=False, jpeggpu_ext_planes_to_rgbi (the reference's helper)."""
+    import torch
+
+    n = info.num_components
+    device = planes[0].device if device is None else torch.device(device)
+    hmax, vmax = max(info.subsampling.x[:n]), max(info.subsampling.y[:n])
+    # img_info has no frame size; the plane of a component with the largest factor has exactly the frame's extent
+    width = info.sizes_x[[c for c in range(n) if info.subsampling.x[c] == hmax][0]]
+    height = info.sizes_y[[c for c in range(n) if info.subsampling.y[c] == vmax][0]]
+    src = Img()
+    for c in range(n):
+        src.image[c], src.pitch[c] = planes[c].data_ptr(), planes[c].stride(0)
+    out = torch.empty((height, width, 3), dtype=torch.uint8, device=device)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    fn = lib().jpeggpu_ext_planes_to_rgbi_fancy if fancy else lib().jpeggpu_ext_planes_to_rgbi
+    _check(fn(C.byref(info), C.byref(src), out.data_ptr(), 3 * width, width, height, stream),
+           "jpeggpu_ext_planes_to_rgbi_fancy" if fancy else "jpeggpu_ext_planes_to_rgbi")
+    return out
+
+
+def decode_to_rgb(data: bytes, device="cuda:0", device_scan=False):
+    """Decode a 1- or 3-component JPEG to an (H, W, 3) uint8 tensor on `device` the way libjpeg-turbo does: the ISLOW
+    IDCT at full size, then fancy upsampling and the integer YCbCr -> RGB conversion. Meant to equal
+    np.asarray(PIL.Image.open(f).convert("RGB")) (INTEGRATION.md, "Matching Pillow / torchvision")."""
+    import torch
+
+    planes, info = decode_to_planes(data, device=device, device_scan=device_scan, idct="islow")
+    rgb = planes_to_rgb(planes, info, fancy=True)
+    torch.cuda.synchronize(torch.device(device))
+    return rgb
 
 
 def parse_headers(decoders, buffers, num_threads=4):

@@ -127,6 +127,10 @@ struct Decoder {
     int scale_log2_request = 0;
     int scale_log2         = 0;
     int scaled(int size) const { return (size + (1 << scale_log2) - 1) >> scale_log2; } // ceil(size / 2^scale_log2)
+    // jpeggpu_ext_set_idct (or JPEGGPU_IDCT at startup): the full-size IDCT, taking effect at the next parse_header like the
+    // scale. It changes the IDCT stage only, and only at scale 1 (the reduced IDCTs are libjpeg's already).
+    uint8_t idct_method_request = kIdctReference;
+    uint8_t idct_method         = kIdctReference;
 
     std::vector<ScanJob> jobs; // scratch of the last decode
 
@@ -473,6 +477,7 @@ jpeggpu_status build_jobs(
         ip.mcus_x      = sc.mcus_x;
         ip.first_mcu   = sc.first_mcu;
         ip.scale_log2  = static_cast<uint8_t>(d.scale_log2);
+        ip.idct_method = d.scale_log2 == 0 ? d.idct_method : kIdctReference;
         {
             const MagicDiv a = magic_div(static_cast<uint32_t>(sc.du_per_mcu)), b = magic_div(static_cast<uint32_t>(sc.mcus_x));
             ip.du_per_mcu_mul = a.mul, ip.du_per_mcu_shift = a.shift;
@@ -712,6 +717,12 @@ enum jpeggpu_status jpeggpu_decoder_startup(jpeggpu_decoder_t* decoder)
         if ((*decoder)->d.device_scan == 0 && !off)
             std::fprintf(stderr, "jpeggpu: JPEGGPU_DEVICE_SCAN=\"%s\" is not one of 0, off, 1, 2, checked, async: the device scan stays off\n", e);
     }
+    // JPEGGPU_IDCT=islow: libjpeg's ISLOW IDCT at full size for a caller of the drop-in API alone (jpeggpu_ext_set_idct)
+    if (const char* e = std::getenv("JPEGGPU_IDCT")) {
+        if (std::strcmp(e, "islow") == 0) (*decoder)->d.idct_method_request = jg::kIdctIslow;
+        else if (e[0] != 0 && std::strcmp(e, "reference") != 0)
+            std::fprintf(stderr, "jpeggpu: JPEGGPU_IDCT=\"%s\" is not one of reference, islow: the reference IDCT stays in use\n", e);
+    }
     return JPEGGPU_SUCCESS;
 }
 
@@ -738,6 +749,7 @@ enum jpeggpu_status jpeggpu_decoder_parse_header(
     Decoder& d = decoder->d;
     d.parsed   = false;
     d.scale_log2 = d.scale_log2_request;
+    d.idct_method = d.idct_method_request;
     jpeggpu_status st;
     try {
         const int ask = d.subseq_request > 0 ? d.subseq_request : -d.batch_hint; // 0 / -N: chosen per image for N images per call
@@ -969,6 +981,15 @@ enum jpeggpu_status jpeggpu_ext_set_scale(jpeggpu_decoder_t decoder, int scale_d
     while (lg <= 3 && (1 << lg) != scale_denom) ++lg;
     if (lg > 3) return JPEGGPU_INVALID_ARGUMENT; // 1, 2, 4 or 8
     decoder->d.scale_log2_request = lg;
+    return JPEGGPU_SUCCESS;
+}
+
+enum jpeggpu_status jpeggpu_ext_set_idct(jpeggpu_decoder_t decoder, enum jpeggpu_ext_idct method)
+{
+    if (!decoder) return JPEGGPU_INVALID_ARGUMENT;
+    const int m = static_cast<int>(method);
+    if (m != JPEGGPU_EXT_IDCT_REFERENCE && m != JPEGGPU_EXT_IDCT_ISLOW) return JPEGGPU_INVALID_ARGUMENT;
+    decoder->d.idct_method_request = m == JPEGGPU_EXT_IDCT_ISLOW ? jg::kIdctIslow : jg::kIdctReference;
     return JPEGGPU_SUCCESS;
 }
 
@@ -1341,6 +1362,33 @@ enum jpeggpu_status jpeggpu_ext_planes_to_rgbi(
         sy_max = info->subsampling.y[c] > sy_max ? info->subsampling.y[c] : sy_max;
     }
     const hipError_t err = jg::launch_rgbi(
+        src->image, src->pitch, info->sizes_x, info->sizes_y, info->subsampling.x, info->subsampling.y,
+        sx_max, sy_max, nc, dst, dst_pitch, width, height, stream);
+    return err == hipSuccess ? JPEGGPU_SUCCESS : JPEGGPU_INTERNAL_ERROR;
+}
+
+enum jpeggpu_status jpeggpu_ext_planes_to_rgbi_fancy(
+    const struct jpeggpu_img_info* info,
+    const struct jpeggpu_img* src,
+    uint8_t* dst,
+    int dst_pitch,
+    int width,
+    int height,
+    jpeggpu_stream_t stream)
+{
+    if (!info || !src || !dst || width <= 0 || height <= 0 || dst_pitch < 3 * width) return JPEGGPU_INVALID_ARGUMENT;
+    const int nc = info->num_components;
+    if (nc != 1 && nc != 3) return JPEGGPU_NOT_SUPPORTED; // as jpeggpu_ext_planes_to_rgbi
+    int sx_max = 0, sy_max = 0;
+    for (int c = 0; c < nc; ++c) {
+        if (info->subsampling.x[c] < 1 || info->subsampling.y[c] < 1) return JPEGGPU_INVALID_ARGUMENT;
+        if (!src->image[c] || src->pitch[c] < info->sizes_x[c] || info->sizes_x[c] < 1 || info->sizes_y[c] < 1) return JPEGGPU_INVALID_ARGUMENT;
+        sx_max = info->subsampling.x[c] > sx_max ? info->subsampling.x[c] : sx_max;
+        sy_max = info->subsampling.y[c] > sy_max ? info->subsampling.y[c] : sy_max;
+    }
+    for (int c = 0; c < nc; ++c) // libjpeg upsamples by integral ratios only (jdsample.c)
+        if (sx_max % info->subsampling.x[c] != 0 || sy_max % info->subsampling.y[c] != 0) return JPEGGPU_NOT_SUPPORTED;
+    const hipError_t err = jg::launch_rgbi_fancy(
         src->image, src->pitch, info->sizes_x, info->sizes_y, info->subsampling.x, info->subsampling.y,
         sx_max, sy_max, nc, dst, dst_pitch, width, height, stream);
     return err == hipSuccess ? JPEGGPU_SUCCESS : JPEGGPU_INTERNAL_ERROR;

@@ -360,6 +360,7 @@ struct IdctParams {
     uint8_t du_dx[kMaxDuPerMcu];   // block column inside the MCU
     uint8_t du_dy[kMaxDuPerMcu];   // block row inside the MCU
     uint8_t scale_log2;            // jpeggpu_ext_set_scale: planes at 1 / 2^scale_log2 (0: full size, idct_kernel; else idct_scaled_kernel)
+    uint8_t idct_method;           // jpeggpu_ext_set_idct, full-size jobs only (0 on a scaled one): kIdctReference or kIdctIslow
     int comp_h[kMaxComp];          // blocks per MCU horizontally (1 when non-interleaved)
     int comp_v[kMaxComp];
     int size_x[kMaxComp];          // visible plane size (crop), at the scale above
@@ -370,8 +371,12 @@ struct IdctParams {
 };
 
 static_assert(offsetof(IdctParams, scale_log2) == offsetof(IdctParams, du_comp) + 3 * kMaxDuPerMcu &&
+                  offsetof(IdctParams, idct_method) == offsetof(IdctParams, du_comp) + 3 * kMaxDuPerMcu + 1 &&
                   offsetof(IdctParams, comp_h) == offsetof(IdctParams, du_comp) + 32,
-              "the scale sits in what was padding: the layout of every other field, and sizeof(ScanJob), are unchanged");
+              "the scale and the IDCT method sit in what was padding: the layout of every other field, and sizeof(ScanJob), are unchanged");
+
+/// IdctParams::idct_method (jpeggpu_ext_idct): the reference's fixed-point transform, or libjpeg's jpeg_idct_islow.
+constexpr uint8_t kIdctReference = 0, kIdctIslow = 1;
 
 /// Division by a runtime constant: for 2 <= d and n < 2^31, with L = ceil(log2 d) and
 /// M = ceil(2^(31+L) / d) (< 2^32), floor(n / d) == (mulhi(n, M) >> (L - 1)): the error term

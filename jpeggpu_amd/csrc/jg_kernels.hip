@@ -9,6 +9,8 @@
 //   idct_kernel             gather + dequant + 8x8 fixed-point IDCT in stream order
 //                                                                    (reference idct.cu:44-223 + decode_transpose.cu:41-132)
 //   idct_scaled_kernel      the same at 1/2, 1/4, 1/8 size: libjpeg-turbo's reduced IDCTs (jidctred.c; jpeggpu_ext_set_scale)
+//   idct_kernel<IslowJobs<..>>  full size with libjpeg-turbo's jpeg_idct_islow (jidctint.c; jpeggpu_ext_set_idct)
+//   fancy_rgbi_kernel       libjpeg's fancy chroma upsampling + integer YCbCr -> interleaved RGB (jdsample.c, jdcolor.c)
 //
 // Everything is integer / bit-serial: no MFMA. Every kernel takes a job source: one ScanJob by
 // value (drop-in API) or an array indexed by blockIdx.y (batch API: one launch per stage for many
@@ -167,6 +169,17 @@ struct JobArrayFullSize {
     {
         const ScanJob& j = jobs[blockIdx.y];
         return j.ip.scale_log2 == 0 ? j : g_no_job;
+    }
+};
+/// The same when the batch's full-size jobs mix IDCT methods (jpeggpu_ext_set_idct): the instantiation of method kMethod
+/// sees the full-size jobs of that method; every other job reads as g_no_job.
+template <uint8_t kMethod>
+struct JobArrayFullSizeOf {
+    const ScanJob* jobs;
+    __device__ __forceinline__ const ScanJob& get() const
+    {
+        const ScanJob& j = jobs[blockIdx.y];
+        return j.ip.scale_log2 == 0 && j.ip.idct_method == kMethod ? j : g_no_job;
     }
 };
 struct JobSingle {
@@ -2224,6 +2237,83 @@ __device__ __forceinline__ uint32_t mul_lo_u16x2(uint32_t a, uint32_t b)
     return __builtin_bit_cast(uint32_t, static_cast<u16x2>(__builtin_bit_cast(u16x2, a) * __builtin_bit_cast(u16x2, b)));
 }
 
+/// libjpeg's post-IDCT range limit (the sample_range_limit table indexed with x & RANGE_MASK, RANGE_MASK = 1023): x
+/// wrapped to a 10-bit signed value, clamped to -128..127, plus 128.
+__device__ __forceinline__ uint32_t range_limit(int x)
+{
+    const int w = static_cast<int>(static_cast<uint32_t>(x) << 22) >> 22;
+    return static_cast<uint32_t>(min(max(w, -128), 127) + 128);
+}
+
+/// The transform idct_kernel applies is a policy of its job source: the reference's (idct8 above) for the plain sources,
+/// libjpeg-turbo's jpeg_idct_islow (jidctint.c) for IslowJobs<JS>, which the launch picks for jobs of jpeggpu_ext_set_idct's
+/// JPEGGPU_EXT_IDCT_ISLOW. Both share everything else of the kernel: the unit records, the entry gather and prefetch, the
+/// zig-zag placement, the geometry and the coalesced pixel stores.
+struct IdctReference {
+    static constexpr bool kIslow = false;
+};
+struct IdctIslow {
+    static constexpr bool kIslow = true;
+};
+template <class JS>
+struct IslowJobs {
+    JS js;
+    __device__ __forceinline__ const ScanJob& get() const { return js.get(); }
+};
+template <class JS>
+struct IdctOf {
+    using type = IdctReference;
+};
+template <class JS>
+struct IdctOf<IslowJobs<JS>> {
+    using type = IdctIslow;
+};
+
+/// One 8-point pass of jpeg_idct_islow (jidctint.c, CONST_BITS = 13): the eight outputs before their DESCALE, in T (int:
+/// wrapping 32-bit arithmetic, the library is built with -fwrapv; long long: jidctint.c's JLONG). Output i is row i of a
+/// column (pass 1) or column i of a row (pass 2).
+template <class T>
+__device__ __forceinline__ void islow8(const T (&in)[8], T (&out)[8])
+{
+    // even part: the rotator is sqrt(2) c(-6)
+    const T z1   = (in[2] + in[6]) * T(4433);       // FIX_0_541196100
+    const T tmp2 = z1 + in[6] * T(-15137);           // FIX_1_847759065
+    const T tmp3 = z1 + in[2] * T(6270);             // FIX_0_765366865
+    const T tmp0 = (in[0] + in[4]) * T(1 << 13);     // LEFT_SHIFT(.., CONST_BITS)
+    const T tmp1 = (in[0] - in[4]) * T(1 << 13);
+    const T tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+    // odd part
+    T t0 = in[7], t1 = in[5], t2 = in[3], t3 = in[1];
+    T o1 = t0 + t3, o2 = t1 + t2, o3 = t0 + t2, o4 = t1 + t3;
+    const T z5 = (o3 + o4) * T(9633);                // FIX_1_175875602
+    t0 = t0 * T(2446);                               // FIX_0_298631336
+    t1 = t1 * T(16819);                              // FIX_2_053119869
+    t2 = t2 * T(25172);                              // FIX_3_072711026
+    t3 = t3 * T(12299);                              // FIX_1_501321110
+    o1 = o1 * T(-7373);                              // FIX_0_899976223
+    o2 = o2 * T(-20995);                             // FIX_2_562915447
+    o3 = o3 * T(-16069) + z5;                        // FIX_1_961570560
+    o4 = o4 * T(-3196) + z5;                         // FIX_0_390180644
+    t0 += o1 + o3;
+    t1 += o2 + o4;
+    t2 += o2 + o3;
+    t3 += o1 + o4;
+    out[0] = tmp10 + t3, out[7] = tmp10 - t3;
+    out[1] = tmp11 + t2, out[6] = tmp11 - t2;
+    out[2] = tmp12 + t1, out[5] = tmp12 - t1;
+    out[3] = tmp13 + t0, out[4] = tmp13 - t0;
+}
+
+/// Dequantised inputs a pass-1 column may hold for the 32-bit pass 1 to be exact. Every output of islow8 is a sum
+/// sum_k c_k in[k] with integer coefficients c_k fixed by the constants above; the largest sum_k |c_k| over the eight
+/// outputs is 61,214 (outputs 2 and 5: 8192 + 8192 from in[0], in[4] and 4,433 + 10,704 from in[2], in[6], the even
+/// part's 31,521; 6,437 + 11,362 + 2,261 + 9,633 from in[1], in[3], in[5], in[7], the odd part's 29,693), and DESCALE
+/// adds 2^10. With |in[k]| <= 32,767, |output| + 2^10 <= 61,214 * 32,767 + 1,024 = 2,005,800,162 < 2^31: the true sum fits
+/// an int, and wrapping 32-bit arithmetic, exact modulo 2^32 whatever the order of its operations, gives it exactly.
+/// (tests/test_libjpeg_ref.py checks the bound on every sign pattern at +-32,767.) Pass 2 never needs 64 bits: its
+/// result goes through range_limit, which reads bits 18..27 of the sum only, and those are the same modulo 2^32.
+constexpr int kIslowPass1Max = 32767;
+
 /// One data unit per 8 lanes, kIdctIters groups of 32 units per workgroup. The unit's entries are
 /// gathered from the symbol stream (aligned 4-byte reads of two entries) and de-zigzagged on the
 /// way into LDS; everything else is zero. The lane of the column pass dequantises its column when it
@@ -2236,10 +2326,16 @@ __device__ __forceinline__ uint32_t mul_lo_u16x2(uint32_t a, uint32_t b)
 /// ([column][row]: zeroing is one 16-byte write, the column pass one 16-byte read), all table
 /// entries of the workgroup are loaded up front, and the first entries of each lane are fetched two
 /// iterations ahead.
+///
+/// With IslowJobs<JS> (IdctIslow) only the arithmetic differs: dequantisation in full int, jidctint.c's two passes
+/// (islow8) with a 32-bit workspace between them, DESCALE by 11 and by 18, the range limit.
 template <class JS>
 __global__ __launch_bounds__(256) void idct_kernel(JS js)
 {
+    using X = typename IdctOf<JS>::type;
     __shared__ __attribute__((aligned(16))) int16_t s_blk[kIdctDuPerBlock][kIdctDuStride]; // [unit][col * 8 + row]
+    // ISLOW: the int workspace between the passes, [unit][row * 8 + col] (+8: as s_blk)
+    __shared__ __attribute__((aligned(16))) int s_ws[X::kIslow ? kIdctDuPerBlock : 1][X::kIslow ? kIdctDuStride : 4];
     // [quantisation table][column][row]: the 16 bytes a lane of the column pass multiplies its column with
     // ((int16)(coef * q), reference idct.cu:178-180: the low 16 bits of the product, whatever the signs)
     __shared__ __attribute__((aligned(16))) uint16_t s_qcol[4 * 64];
@@ -2436,6 +2532,54 @@ __global__ __launch_bounds__(256) void idct_kernel(JS js)
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        uint2 o;
+        if constexpr (X::kIslow) {
+            int v[8];
+            {
+                int c[8], q[8];
+                unpack8(*reinterpret_cast<const uint4*>(blk + r * 8), c); // column r
+                const uint4 qc = *reinterpret_cast<const uint4*>(qcol_mine + qoff);
+                const uint32_t qw[4] = {qc.x, qc.y, qc.z, qc.w};
+#pragma unroll
+                for (int i = 0; i < 8; ++i) q[i] = static_cast<int>((qw[i >> 1] >> (16 * (i & 1))) & 0xFFFFu);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) v[i] = c[i] * q[i]; // DEQUANTIZE in full int: |int16 * uint16| < 2^31
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // every column is read before the next iteration zeroes the block
+            bool small = true;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) small = small && static_cast<uint32_t>(v[i] + kIslowPass1Max) <= 2u * kIslowPass1Max;
+            int* const ws = s_ws[dl];
+            if (__builtin_expect(__ballot(!small) == 0, 1)) { // pass 1 in 32 bits: exact (kIslowPass1Max)
+                int p[8];
+                islow8(v, p);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) ws[i * 8 + r] = (p[i] + (1 << 10)) >> 11; // DESCALE(.., CONST_BITS - PASS1_BITS), now [row][col]
+            } else { // a coefficient the bound does not cover (16-bit quantisers, corrupt streams): jidctint.c's JLONG
+                long long w[8], p[8];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) w[i] = v[i];
+                islow8(w, p);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) ws[i * 8 + r] = static_cast<int>((p[i] + (1ll << 10)) >> 11); // the int workspace keeps the low 32 bits
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            int w[8];
+            {
+                const uint4 a = *reinterpret_cast<const uint4*>(ws + r * 8), b = *reinterpret_cast<const uint4*>(ws + r * 8 + 4); // row r
+                const uint32_t u[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+                for (int i = 0; i < 8; ++i) w[i] = static_cast<int>(u[i]);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // row reads precede the next iteration's workspace stores
+            int p[8];
+            islow8(w, p); // wrapping 32-bit: only bits 18..27 of each sum count (kIslowPass1Max)
+            uint32_t px[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) px[i] = range_limit((p[i] + (1 << 17)) >> 18); // DESCALE(.., CONST_BITS + PASS1_BITS + 3)
+            o.x = px[0] | px[1] << 8 | px[2] << 16 | px[3] << 24;
+            o.y = px[4] | px[5] << 8 | px[6] << 16 | px[7] << 24;
+        } else {
         int v[8];
         {
             uint4 col      = *reinterpret_cast<const uint4*>(blk + r * 8); // column r
@@ -2452,9 +2596,9 @@ __global__ __launch_bounds__(256) void idct_kernel(JS js)
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // row reads precede the next iteration's zeroing
         idct8<0x8000 + (128 << 16)>(v);
 
-        uint2 o;
         o.x = finish_pixels(v[0], v[1], v[2], v[3]);
         o.y = finish_pixels(v[4], v[5], v[6], v[7]);
+        }
         // A lane holds row r of unit dl; storing that directly makes every wave store touch ~40 cache
         // lines (8 units x 8 rows). Re-map through LDS: lane -> (row t / 32, unit t % 32), so that
         // consecutive lanes write the neighbouring 8-byte segments of one image row.
@@ -2494,14 +2638,6 @@ __global__ __launch_bounds__(256) void idct_kernel(JS js)
 // ------------------------------------------------------------------------------------------------
 // scaled decoding (jpeggpu_ext_set_scale): the reduced inverse DCTs of libjpeg-turbo's jidctred.c
 // ------------------------------------------------------------------------------------------------
-
-/// libjpeg's post-IDCT range limit (the sample_range_limit table indexed with x & RANGE_MASK, RANGE_MASK = 1023): x
-/// wrapped to a 10-bit signed value, clamped to -128..127, plus 128.
-__device__ __forceinline__ uint32_t range_limit(int x)
-{
-    const int w = static_cast<int>(static_cast<uint32_t>(x) << 22) >> 22;
-    return static_cast<uint32_t>(min(max(w, -128), 127) + 128);
-}
 
 /// jidctred.c's DESCALE: (x + 2^(n-1)) >> n, 64-bit (JLONG).
 template <int n>
@@ -2758,6 +2894,110 @@ __global__ __launch_bounds__(256) void rgbi_kernel(RgbiParams p, uint8_t* __rest
     }
 }
 
+/// libjpeg's fancy upsampling (jdsample.c, do_fancy_upsampling) + its integer YCbCr -> RGB (jdcolor.c, ycc_rgb_convert),
+/// interleaved 8-bit output: what libjpeg-turbo gives a caller that asks for JCS_RGB. Per component, by the ratio of the
+/// largest sampling factors to its own (FancyComp::mode, chosen on the host): a copy or replication (int_upsample),
+/// h2v1_fancy_upsample, h2v2_fancy_upsample or h1v2_fancy_upsample. Samples outside the plane -- the column left of the
+/// first and right of the last, the row above the first and below the last -- are copies of the edge samples, which
+/// is what libjpeg's edge formulas and context rows amount to; the plane's extent is libjpeg's downsampled_width /
+/// downsampled_height (jpeggpu_decoder_parse_header's sizes), so no padding sample is read.
+///
+/// One workgroup: an output tile of kFancyTileW x kFancyTileH pixels. It stages each component's samples under the tile
+/// with a one-sample halo in LDS (loads clamped to the plane: that is the edge rule), then each lane converts a 2 x 4
+/// quad -- 4 pixels of 2 rows -- and stores each row's 12 bytes; the 64 lanes of a wave store 768 contiguous bytes.
+enum FancyMode : int { kFancyReplicate = 0, kFancyH2V1 = 1, kFancyH2V2 = 2, kFancyH1V2 = 3 };
+struct FancyComp {
+    const uint8_t* plane;
+    int pitch, w, h;
+    int hr, vr; // output pixels per sample: h_max / h_c, v_max / v_c
+    int mode;   // FancyMode
+};
+struct FancyParams {
+    FancyComp comp[3];
+    int ncomp; // 1 (grey to R, G, B) or 3
+};
+constexpr int kFancyTileW = 256, kFancyTileH = 8;
+constexpr int kFancyLdsW = kFancyTileW + 4, kFancyLdsH = kFancyTileH + 2; // samples under a tile at ratio 1, with the halo
+
+/// Sample (gx, gy) of a staged component, in global sample coordinates relative to the staged origin (bx, by)
+__device__ __forceinline__ int fancy_at(const uint8_t (&t)[kFancyLdsH][kFancyLdsW], int gx, int gy) { return t[gy][gx]; }
+
+/// The upsampled value of output pixel (x, y) of a staged component; (bx, by): global sample coordinates of t[0][0].
+__device__ __forceinline__ int fancy_sample(const FancyComp& c, const uint8_t (&t)[kFancyLdsH][kFancyLdsW], int bx, int by, int x, int y)
+{
+    switch (c.mode) {
+    case kFancyH2V1: {
+        const int i = (x >> 1) - bx, j = y - by, odd = x & 1;
+        return (3 * fancy_at(t, i, j) + fancy_at(t, odd ? i + 1 : i - 1, j) + 1 + odd) >> 2;
+    }
+    case kFancyH2V2: {
+        const int i = (x >> 1) - bx, j = (y >> 1) - by, odd = x & 1, dj = (y & 1) ? 1 : -1, di = odd ? 1 : -1;
+        const int here = 3 * fancy_at(t, i, j) + fancy_at(t, i, j + dj);      // column sums: 3 near + far row
+        const int side = 3 * fancy_at(t, i + di, j) + fancy_at(t, i + di, j + dj);
+        return (3 * here + side + 8 - odd) >> 4;
+    }
+    case kFancyH1V2: {
+        const int i = x - bx, j = (y >> 1) - by, below = y & 1;
+        return (3 * fancy_at(t, i, j) + fancy_at(t, i, below ? j + 1 : j - 1) + 1 + below) >> 2;
+    }
+    default: return fancy_at(t, x / c.hr - bx, y / c.vr - by);
+    }
+}
+
+__device__ __forceinline__ uint32_t clamp255(int v) { return static_cast<uint32_t>(min(max(v, 0), 255)); }
+
+__global__ __launch_bounds__(256) void fancy_rgbi_kernel(FancyParams p, uint8_t* __restrict__ dst, int dst_pitch, int width, int height)
+{
+    __shared__ uint8_t s_t[3][kFancyLdsH][kFancyLdsW];
+    const int t  = threadIdx.x;
+    const int x0 = blockIdx.x * kFancyTileW, y0 = blockIdx.y * kFancyTileH;
+    int bx[3], by[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const FancyComp& c = p.comp[k];
+        // samples floor(x0 / hr) - 1 .. floor((x0 + 255) / hr) + 1: at most 256 + 2 columns and 8 + 2 rows (ratio 1)
+        bx[k] = x0 / c.hr - 1;
+        by[k] = y0 / c.vr - 1;
+        if (k >= p.ncomp) continue;
+        const int nx = (x0 + kFancyTileW - 1) / c.hr + 2 - bx[k], ny = (y0 + kFancyTileH - 1) / c.vr + 2 - by[k];
+        for (int j = 0; j < ny; ++j) {
+            const uint8_t* row = c.plane + static_cast<size_t>(min(max(by[k] + j, 0), c.h - 1)) * c.pitch;
+            for (int i = t; i < nx; i += 256) s_t[k][j][i] = row[min(max(bx[k] + i, 0), c.w - 1)];
+        }
+    }
+    __syncthreads();
+    const int x = x0 + 4 * (t & 63);
+    if (x >= width) return;
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+        const int y = y0 + 2 * (t >> 6) + dy;
+        if (y >= height) break;
+        uint32_t out[12];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int xi = min(x + i, width - 1);
+            const int Y  = fancy_sample(p.comp[0], s_t[0], bx[0], by[0], xi, y);
+            if (p.ncomp == 3) {
+                const int cb = fancy_sample(p.comp[1], s_t[1], bx[1], by[1], xi, y) - 128;
+                const int cr = fancy_sample(p.comp[2], s_t[2], bx[2], by[2], xi, y) - 128;
+                out[3 * i + 0] = clamp255(Y + ((91881 * cr + (1 << 15)) >> 16));                // FIX(1.40200)
+                out[3 * i + 1] = clamp255(Y + ((-22554 * cb - 46802 * cr + (1 << 15)) >> 16)); // FIX(0.34414), FIX(0.71414)
+                out[3 * i + 2] = clamp255(Y + ((116130 * cb + (1 << 15)) >> 16));               // FIX(1.77200)
+            } else {
+                out[3 * i + 0] = out[3 * i + 1] = out[3 * i + 2] = static_cast<uint32_t>(Y);
+            }
+        }
+        uint8_t* drow = dst + static_cast<size_t>(y) * dst_pitch + static_cast<size_t>(x) * 3;
+        if (x + 4 <= width && (reinterpret_cast<uintptr_t>(drow) & 3) == 0) {
+            uint32_t* d = reinterpret_cast<uint32_t*>(drow);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) d[k] = out[4 * k] | out[4 * k + 1] << 8 | out[4 * k + 2] << 16 | out[4 * k + 3] << 24;
+        } else {
+            for (int i = 0; i < 12 && x + i / 3 < width; ++i) drow[i] = static_cast<uint8_t>(out[i]);
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // launches
 // ------------------------------------------------------------------------------------------------
@@ -2849,15 +3089,33 @@ hipError_t launch_any(Stage stage, const JS& js, const JobExtent& e, int grid_y,
         return hipGetLastError();
     case kStageIdct:
         if (e.max_idct_blocks == 0) return hipSuccess;
-        // full-size jobs: idct_kernel; scaled ones (jpeggpu_ext_set_scale): idct_scaled_kernel, one launch per scale present.
-        // Only a batch can hold several; its idct_kernel then sees the scaled jobs as empty.
-        if (e.scales == 1u) {
-            idct_kernel<JS><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(js);
-        } else if (e.scales & 1u) {
-            if constexpr (std::is_same<JS, JobArray>::value)
-                idct_kernel<JobArrayFullSize><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(JobArrayFullSize{js.jobs});
-            else
-                return hipErrorInvalidValue; // the scans of one image share its scale
+        // full-size jobs: idct_kernel, one instantiation per IDCT method present (jpeggpu_ext_set_idct); scaled ones
+        // (jpeggpu_ext_set_scale): idct_scaled_kernel, one launch per scale present. Only a batch can hold several kinds;
+        // each instantiation then sees the other kinds' jobs as empty. A call without ISLOW jobs launches what it did before.
+        if (e.scales & 1u) {
+            const bool alone = e.scales == 1u; // no scaled job
+            constexpr bool batch = std::is_same<JS, JobArray>::value;
+            if (e.methods == (1u << kIdctReference)) {
+                if (alone) {
+                    idct_kernel<JS><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(js);
+                } else {
+                    if constexpr (batch)
+                        idct_kernel<JobArrayFullSize><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(JobArrayFullSize{js.jobs});
+                    else
+                        return hipErrorInvalidValue; // the scans of one image share its scale
+                }
+            } else if (e.methods == (1u << kIdctIslow) && alone) {
+                idct_kernel<IslowJobs<JS>><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(IslowJobs<JS>{js});
+            } else {
+                if constexpr (batch) {
+                    using Ref = JobArrayFullSizeOf<kIdctReference>;
+                    using Islow = IslowJobs<JobArrayFullSizeOf<kIdctIslow>>;
+                    if (e.methods & (1u << kIdctReference)) idct_kernel<Ref><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(Ref{js.jobs});
+                    idct_kernel<Islow><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(Islow{{js.jobs}});
+                } else {
+                    return hipErrorInvalidValue; // the scans of one image share its scale and method
+                }
+            }
         }
         static_assert(kScaledDuPerWg == kIdctDuPerWg, "one grid for both");
         if (e.scales & 2u) idct_scaled_kernel<JS, 1><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(js);
@@ -2895,6 +3153,7 @@ void extend(JobExtent& e, const ScanJob& job)
     const int blocks  = (job.ip.num_du + kIdctDuPerWg - 1) / kIdctDuPerWg;
     e.max_idct_blocks = blocks > e.max_idct_blocks ? blocks : e.max_idct_blocks;
     e.scales |= 1u << job.ip.scale_log2;
+    if (job.ip.scale_log2 == 0) e.methods |= 1u << job.ip.idct_method;
     e.max_tab_bytes   = job.sp.tab_bytes > e.max_tab_bytes ? job.sp.tab_bytes : e.max_tab_bytes;
     e.max_tab_bytes_sync = job.sp.tab_bytes_sync > e.max_tab_bytes_sync ? job.sp.tab_bytes_sync : e.max_tab_bytes_sync;
     e.subseq_words    = job.sp.subseq_words;
@@ -3014,6 +3273,35 @@ hipError_t launch_rgbi(
     p.ncomp = ncomp;
     const dim3 grid((width + 1023) / 1024, height);
     rgbi_kernel<<<grid, 256, 0, stream>>>(p, dst, dst_pitch, width, height);
+    return hipGetLastError();
+}
+
+hipError_t launch_rgbi_fancy(
+    const uint8_t* const* planes, const int* pitch, const int* w, const int* h, const int* num_x, const int* num_y,
+    int den_x, int den_y, int ncomp, uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream)
+{
+    if (width <= 0 || height <= 0) return hipSuccess;
+    FancyParams p{};
+    p.ncomp = ncomp;
+    for (int c = 0; c < 3; ++c) {
+        const int cc = c < ncomp ? c : 0;
+        FancyComp& f = p.comp[c];
+        if (num_x[cc] < 1 || num_y[cc] < 1 || den_x % num_x[cc] != 0 || den_y % num_y[cc] != 0) return hipErrorInvalidValue; // non-integral
+        if (w[cc] < 1 || h[cc] < 1) return hipErrorInvalidValue;
+        f.plane = planes[cc];
+        f.pitch = pitch[cc];
+        f.w     = w[cc];
+        f.h     = h[cc];
+        f.hr    = den_x / num_x[cc];
+        f.vr    = den_y / num_y[cc];
+        // jdsample.c, jinit_upsampler: 2h1v and 2h2v take the fancy path only on planes wider than 2 samples
+        if (f.hr == 2 && f.vr == 1 && f.w > 2) f.mode = kFancyH2V1;
+        else if (f.hr == 2 && f.vr == 2 && f.w > 2) f.mode = kFancyH2V2;
+        else if (f.hr == 1 && f.vr == 2) f.mode = kFancyH1V2;
+        else f.mode = kFancyReplicate;
+    }
+    const dim3 grid((width + kFancyTileW - 1) / kFancyTileW, (height + kFancyTileH - 1) / kFancyTileH);
+    fancy_rgbi_kernel<<<grid, 256, 0, stream>>>(p, dst, dst_pitch, width, height);
     return hipGetLastError();
 }
 

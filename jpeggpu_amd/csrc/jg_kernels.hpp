@@ -32,6 +32,7 @@ struct JobExtent {
     int max_idct_blocks = 0;
     int subseq_words    = 0; // identical for every job of a launch
     uint32_t scales     = 0; // bit s: a job decodes at 1 / 2^s (IdctParams::scale_log2)
+    uint32_t methods    = 0; // bit m: a full-size job takes IDCT method m (IdctParams::idct_method)
     uint32_t max_tab_bytes = 0;      // largest write-pass table pack
     uint32_t max_tab_bytes_sync = 0; // largest sync pack
     bool fuse_tail_write = false;    // batch launches: the tail kernel's parts and the write pass's sequences as ONE launch
@@ -73,6 +74,12 @@ hipError_t launch_upsample(
 /// Nearest-neighbour replication + YCbCr -> interleaved RGB8 (reference host helper util/util.h:62-104);
 /// `ncomp` 1 (grey copied to R, G, B) or 3.
 hipError_t launch_rgbi(
+    const uint8_t* const* planes, const int* pitch, const int* w, const int* h, const int* num_x, const int* num_y,
+    int den_x, int den_y, int ncomp, uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream);
+
+/// libjpeg's fancy upsampling + integer YCbCr -> interleaved RGB8 (jdsample.c, jdcolor.c); same arguments as launch_rgbi.
+/// hipErrorInvalidValue if a component's sampling factors do not divide the largest ones.
+hipError_t launch_rgbi_fancy(
     const uint8_t* const* planes, const int* pitch, const int* w, const int* h, const int* num_x, const int* num_y,
     int den_x, int den_y, int ncomp, uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream);
 
