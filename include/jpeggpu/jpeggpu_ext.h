@@ -21,6 +21,9 @@
  *                                      libjpeg-turbo's reduced IDCTs
  *   jpeggpu_ext_set_idct               full-size IDCT: the reference's (default) or libjpeg-turbo's jpeg_idct_islow
  *   jpeggpu_ext_planes_to_rgbi_fancy   libjpeg's fancy chroma upsampling + integer YCbCr -> interleaved RGB8
+ *   jpeggpu_ext_set_crop /             decode only a rectangle of the image: a window of each plane, the restart segments
+ *   jpeggpu_ext_get_crop               outside it skipped (nvJPEG's ROI decode, libjpeg-turbo's jpeg_crop_scanline)
+ *   jpeggpu_ext_crop_to_rgbi_fancy     the rectangle as interleaved RGB8, equal to that part of planes_to_rgbi_fancy's image
  */
 #ifndef JPEGGPU_JPEGGPU_EXT_H_
 #define JPEGGPU_JPEGGPU_EXT_H_
@@ -182,6 +185,35 @@ enum jpeggpu_status jpeggpu_ext_set_scale(jpeggpu_decoder_t decoder, int scale_d
 enum jpeggpu_ext_idct { JPEGGPU_EXT_IDCT_REFERENCE = 0, JPEGGPU_EXT_IDCT_ISLOW = 1 };
 enum jpeggpu_status jpeggpu_ext_set_idct(jpeggpu_decoder_t decoder, enum jpeggpu_ext_idct method);
 
+/* Cropped decoding: decode only the rectangle x, y, width x height (>= 0; 0 x 0 clears it) of the image AT THE DECODER'S
+ * SCALE -- the RGB image jpeggpu_ext_planes_to_rgbi_fancy makes of the scaled planes. Takes effect at the next
+ * jpeggpu_decoder_parse_header, like jpeggpu_ext_set_scale. Negative values, or a zero in only one of width / height:
+ * JPEGGPU_INVALID_ARGUMENT from the setter; a rectangle that does not lie inside the image: JPEGGPU_INVALID_ARGUMENT from
+ * parse_header; together with jpeggpu_ext_set_segment_shard (world > 1): JPEGGPU_NOT_SUPPORTED from parse_header.
+ *   - The decoder writes a WINDOW of each plane: the slice of the uncropped plane that holds every sample libjpeg's fancy
+ *     upsampler reads for the rectangle. For component c, hr = h_max / h_c, vr = v_max / v_c, the needed columns are
+ *     floor(x / hr) - 1 .. floor((x + width - 1) / hr) + 1 clipped to the plane (rows likewise with vr; every component gets
+ *     this one-sample halo). The frame's MCU columns [mx0, mx1) and rows [my0, my1) are the fewest that hold the needed
+ *     samples of every component (an MCU column is 8 h_c / scale_denom samples of component c); the window of c starts at
+ *     (mx0 * 8 h_c / d, my0 * 8 v_c / d) and ends behind its last needed sample.
+ *   - parse_header reports the windows' sizes in sizes_x / sizes_y, and decode (and jpeggpu_ext_decode_batch, whose items
+ *     may mix cropped and uncropped decoders, scales and IDCT methods) writes planes of those sizes (the pitch checks use
+ *     them). jpeggpu_ext_get_crop, after parse_header, says where the windows lie.
+ *   - A file of one scan with restart markers (any interval), walked on the host: parse_header keeps only the restart
+ *     segments that hold the window's MCUs, so transfer copies only their bytes and the Huffman kernels decode only them
+ *     (jpeggpu_ext_get_layout: transferred_bytes, num_segments, num_subsequences; get_buffer_size may shrink). Without restart
+ *     markers, with several scans or with the device scan the whole scan is Huffman-decoded; the IDCT always transforms
+ *     the window's MCUs only. */
+struct jpeggpu_ext_crop_info {
+    int x, y, width, height;         /* the rectangle (without a crop: the whole image at the scale) */
+    int origin_x[JPEGGPU_MAX_COMP];  /* each component's window origin in its full plane */
+    int origin_y[JPEGGPU_MAX_COMP];
+    int full_x[JPEGGPU_MAX_COMP];    /* each component's full plane size at the scale */
+    int full_y[JPEGGPU_MAX_COMP];
+};
+enum jpeggpu_status jpeggpu_ext_set_crop(jpeggpu_decoder_t decoder, int x, int y, int width, int height);
+enum jpeggpu_status jpeggpu_ext_get_crop(jpeggpu_decoder_t decoder, struct jpeggpu_ext_crop_info* info);
+
 /* Stage timing: when enabled, jpeggpu_decoder_decode records HIP events on the caller's stream
  * between its launches; after the stream has been synchronised jpeggpu_ext_get_stage_ms returns the
  * mean milliseconds per stage (summed over scans) of the decodes since the previous call (at most the
@@ -316,6 +348,19 @@ enum jpeggpu_status jpeggpu_ext_planes_to_rgbi_fancy(
     int dst_pitch,
     int width,
     int height,
+    jpeggpu_stream_t stream);
+
+/* jpeggpu_ext_planes_to_rgbi_fancy for the rectangle of a cropped decode: `info` and `src` are the windows parse_header
+ * reported and decode wrote, `crop` what jpeggpu_ext_get_crop returned. Writes crop->width x crop->height pixels, equal to
+ * rows y.., columns x.. of what jpeggpu_ext_planes_to_rgbi_fancy makes of the uncropped planes (the fancy / replicate choice
+ * is made on the full plane sizes). JPEGGPU_NOT_SUPPORTED for 2 or 4 components or non-integral sampling ratios;
+ * JPEGGPU_INVALID_ARGUMENT if a window does not hold the samples the rectangle reads. */
+enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_fancy(
+    const struct jpeggpu_img_info* info,
+    const struct jpeggpu_ext_crop_info* crop,
+    const struct jpeggpu_img* src,
+    uint8_t* dst,
+    int dst_pitch,
     jpeggpu_stream_t stream);
 
 #ifdef __cplusplus

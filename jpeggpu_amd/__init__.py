@@ -6,10 +6,12 @@ ctypes bindings with the reference's function names, argument meaning and status
 """
 from .api import (  # noqa: F401
     Batch,
+    CropInfo,
     Decoder,
     ImgInfo,
     JpegGpuError,
     Status,
+    crop_to_rgb,
     decode_to_planes,
     decode_to_rgb,
     fused_tail_timeouts,

@@ -40,6 +40,14 @@ class Img(C.Structure):
     _fields_ = [("image", C.c_void_p * MAX_COMP), ("pitch", C.c_int * MAX_COMP)]
 
 
+class CropInfo(C.Structure):
+    """struct jpeggpu_ext_crop_info: the rectangle, each component's window origin in its full plane, the full plane sizes
+    (all at the decoder's scale)."""
+    _fields_ = [("x", C.c_int), ("y", C.c_int), ("width", C.c_int), ("height", C.c_int),
+                ("origin_x", C.c_int * MAX_COMP), ("origin_y", C.c_int * MAX_COMP),
+                ("full_x", C.c_int * MAX_COMP), ("full_y", C.c_int * MAX_COMP)]
+
+
 class ExtScanLayout(C.Structure):
     _fields_ = [
         ("num_components", C.c_int), ("component_idx", C.c_int * MAX_COMP),
@@ -140,6 +148,10 @@ def lib():
         C.POINTER(ImgInfo), C.POINTER(Img), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.jpeggpu_ext_planes_to_rgbi_fancy.argtypes = [
         C.POINTER(ImgInfo), C.POINTER(Img), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.jpeggpu_ext_set_crop.argtypes = [dec, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.jpeggpu_ext_get_crop.argtypes = [dec, C.POINTER(CropInfo)]
+    L.jpeggpu_ext_crop_to_rgbi_fancy.argtypes = [
+        C.POINTER(ImgInfo), C.POINTER(CropInfo), C.POINTER(Img), C.c_void_p, C.c_int, C.c_void_p]
     _lib = L
     return L
 
@@ -220,6 +232,17 @@ class Decoder:
         if method not in IDCT_METHODS:
             raise ValueError("idct method %r is not one of %s" % (method, ", ".join(IDCT_METHODS)))
         _check(lib().jpeggpu_ext_set_idct(self._h, IDCT_METHODS[method]), "jpeggpu_ext_set_idct")
+
+    def set_crop(self, x: int, y: int, w: int, h: int):
+        """Decode only the rectangle (x, y, w, h) of the image at the decoder's scale from the next parse_header on
+        (0, 0, 0, 0: the whole image again). The planes are then windows of the full planes (crop_info says where)."""
+        _check(lib().jpeggpu_ext_set_crop(self._h, int(x), int(y), int(w), int(h)), "jpeggpu_ext_set_crop")
+
+    def crop_info(self) -> CropInfo:
+        """jpeggpu_ext_get_crop of the last parsed image."""
+        ci = CropInfo()
+        _check(lib().jpeggpu_ext_get_crop(self._h, C.byref(ci)), "jpeggpu_ext_get_crop")
+        return ci
 
     def set_segment_shard(self, rank: int, world: int):
         """Decode only restart segments [rank * n / world, (rank + 1) * n / world) of the next parsed images."""
@@ -352,11 +375,13 @@ def self_test(stream: int = 0) -> None:
 
 
 def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp=False, device_scan=False, scale=1,
-                     idct="reference"):
+                     idct="reference", crop=None):
     """Convenience wrapper used by tests: full call sequence on torch's current stream, returns the
     planes as torch uint8 tensors on `device` (torch is only the allocator / stream provider). With
     `device_scan` the restart markers are found on the device and a status it reports there is raised.
-    `scale`: 1, 2, 4 or 8 -- planes at 1 / scale (Decoder.set_scale). `idct`: "reference" or "islow" (Decoder.set_idct)."""
+    `scale`: 1, 2, 4 or 8 -- planes at 1 / scale (Decoder.set_scale). `idct`: "reference" or "islow" (Decoder.set_idct).
+    `crop`: (x, y, w, h) -- only the planes' windows for that rectangle are decoded (Decoder.set_crop), and the CropInfo
+    is returned as well: (planes, info, crop_info)."""
     import torch
 
     dec = Decoder(subseq_bytes)
@@ -367,6 +392,8 @@ def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp
             dec.set_idct(idct)
         if device_scan:
             dec.set_device_scan(True)
+        if crop is not None:
+            dec.set_crop(*crop)
         info = dec.parse_header(data)
         n = dec.get_buffer_size()
         tmp = torch.empty(n + 256, dtype=torch.uint8, device=device)
@@ -379,6 +406,11 @@ def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp
         torch.cuda.synchronize(torch.device(device))
         if device_scan:
             _check(int(dec.device_status(base, stream)), "device-side marker scan")
+        if crop is not None:
+            crop_info = dec.crop_info()
+            if return_tmp:
+                return planes, info, crop_info, tmp, base, dec.layout()
+            return planes, info, crop_info
         if return_tmp:
             return planes, info, tmp, base, dec.layout()
         return planes, info
@@ -409,12 +441,36 @@ def planes_to_rgb(planes, info, fancy=True, device=None):
     return out
 
 
-def decode_to_rgb(data: bytes, device="cuda:0", device_scan=False):
-    """Decode a 1- or 3-component JPEG to an (H, W, 3) uint8 tensor on `device` the way libjpeg-turbo does: the ISLOW
-    IDCT at full size, then fancy upsampling and the integer YCbCr -> RGB conversion. Meant to equal
-    np.asarray(PIL.Image.open(f).convert("RGB")) (INTEGRATION.md, "Matching Pillow / torchvision")."""
+def crop_to_rgb(planes, info, crop_info, device=None):
+    """The window planes of a cropped decode (decode_to_planes(..., crop=...)) -> (h, w, 3) uint8 tensor of the rectangle,
+    equal to that part of planes_to_rgb's image of the uncropped planes (jpeggpu_ext_crop_to_rgbi_fancy)."""
     import torch
 
+    n = info.num_components
+    device = planes[0].device if device is None else torch.device(device)
+    src = Img()
+    for c in range(n):
+        src.image[c], src.pitch[c] = planes[c].data_ptr(), planes[c].stride(0)
+    w, h = crop_info.width, crop_info.height
+    out = torch.empty((h, w, 3), dtype=torch.uint8, device=device)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    _check(lib().jpeggpu_ext_crop_to_rgbi_fancy(C.byref(info), C.byref(crop_info), C.byref(src), out.data_ptr(), 3 * w, stream),
+           "jpeggpu_ext_crop_to_rgbi_fancy")
+    return out
+
+
+def decode_to_rgb(data: bytes, device="cuda:0", device_scan=False, crop=None):
+    """Decode a 1- or 3-component JPEG to an (H, W, 3) uint8 tensor on `device` the way libjpeg-turbo does: the ISLOW
+    IDCT at full size, then fancy upsampling and the integer YCbCr -> RGB conversion. Meant to equal
+    np.asarray(PIL.Image.open(f).convert("RGB")) (INTEGRATION.md, "Matching Pillow / torchvision"). With `crop` = (x, y,
+    w, h) only that rectangle is decoded: an (h, w, 3) tensor equal to decode_to_rgb(data)[y:y + h, x:x + w]."""
+    import torch
+
+    if crop is not None:
+        planes, info, crop_info = decode_to_planes(data, device=device, device_scan=device_scan, idct="islow", crop=crop)
+        rgb = crop_to_rgb(planes, info, crop_info)
+        torch.cuda.synchronize(torch.device(device))
+        return rgb
     planes, info = decode_to_planes(data, device=device, device_scan=device_scan, idct="islow")
     rgb = planes_to_rgb(planes, info, fancy=True)
     torch.cuda.synchronize(torch.device(device))

@@ -131,6 +131,20 @@ struct Decoder {
     // scale. It changes the IDCT stage only, and only at scale 1 (the reduced IDCTs are libjpeg's already).
     uint8_t idct_method_request = kIdctReference;
     uint8_t idct_method         = kIdctReference;
+    // jpeggpu_ext_set_crop: the rectangle {x, y, width, height} asked for (width 0: none), taking effect at the next
+    // parse_header like the scale; `crop`: what the parsed image got. The decoder writes a WINDOW of each plane (jpeggpu_ext.h).
+    int crop_request[4] = {0, 0, 0, 0};
+    struct Crop {
+        bool on = false;
+        int x = 0, y = 0, w = 0, h = 0;       // the rectangle, in pixels of the image at the scale
+        int mx0 = 0, my0 = 0, mx1 = 0, my1 = 0; // the frame MCUs the windows start in / end behind
+        int ox[kMaxComp]{}, oy[kMaxComp]{};   // window origin in the component's plane
+        int wx[kMaxComp]{}, wy[kMaxComp]{};   // window size
+    } crop;
+    int plane_x(int c) const { return crop.on ? crop.wx[c] : scaled(reader.s.comp[c].size_x); } // what decode writes
+    int plane_y(int c) const { return crop.on ? crop.wy[c] : scaled(reader.s.comp[c].size_y); }
+    bool set_crop_window();
+    IdctWindow scan_window(const Scan& sc) const;
 
     std::vector<ScanJob> jobs; // scratch of the last decode
 
@@ -152,6 +166,55 @@ struct Decoder {
     void make_plan();
     bool fill_blob();
 };
+
+/// The windows of a crop (jpeggpu_ext.h, jpeggpu_ext_set_crop) from the request and the parsed frame; false if the
+/// rectangle does not lie inside the image at the scale.
+bool Decoder::set_crop_window()
+{
+    const Stream& s = reader.s;
+    Crop c;
+    c.on = true;
+    c.x = crop_request[0], c.y = crop_request[1], c.w = crop_request[2], c.h = crop_request[3];
+    if (c.x + static_cast<long long>(c.w) > scaled(s.size_x) || c.y + static_cast<long long>(c.h) > scaled(s.size_y)) return false;
+    const int n = 8 >> scale_log2; // samples per block side at the scale
+    int lo_x[kMaxComp], hi_x[kMaxComp], lo_y[kMaxComp], hi_y[kMaxComp];
+    c.mx0 = c.my0 = 1 << 30;
+    for (int k = 0; k < s.num_comp; ++k) {
+        const Component& fc = s.comp[k];
+        // samples of the rectangle, plus the one-sample halo of the upsamplers, clipped to the plane
+        lo_x[k] = std::max(static_cast<int>(static_cast<long long>(c.x) * fc.hs / s.hs_max) - 1, 0);
+        hi_x[k] = std::min(static_cast<int>(static_cast<long long>(c.x + c.w - 1) * fc.hs / s.hs_max) + 1, scaled(fc.size_x) - 1);
+        lo_y[k] = std::max(static_cast<int>(static_cast<long long>(c.y) * fc.vs / s.vs_max) - 1, 0);
+        hi_y[k] = std::min(static_cast<int>(static_cast<long long>(c.y + c.h - 1) * fc.vs / s.vs_max) + 1, scaled(fc.size_y) - 1);
+        c.mx0 = std::min(c.mx0, lo_x[k] / (n * fc.hs)), c.mx1 = std::max(c.mx1, hi_x[k] / (n * fc.hs) + 1);
+        c.my0 = std::min(c.my0, lo_y[k] / (n * fc.vs)), c.my1 = std::max(c.my1, hi_y[k] / (n * fc.vs) + 1);
+    }
+    for (int k = 0; k < s.num_comp; ++k) {
+        const Component& fc = s.comp[k];
+        c.ox[k] = c.mx0 * n * fc.hs, c.oy[k] = c.my0 * n * fc.vs;
+        c.wx[k] = hi_x[k] + 1 - c.ox[k], c.wy[k] = hi_y[k] + 1 - c.oy[k];
+    }
+    crop = c;
+    return true;
+}
+
+/// The IDCT window of one scan of a cropped image (IdctWindow): the frame's MCU window for an interleaved scan, the block
+/// window that holds the component's window for a non-interleaved one. Zero without a crop.
+IdctWindow Decoder::scan_window(const Scan& sc) const
+{
+    IdctWindow w{};
+    if (!crop.on) return w;
+    if (sc.num_comp > 1) {
+        w.mx0 = crop.mx0, w.my0 = crop.my0, w.mcus_x = crop.mx1 - crop.mx0, w.mcus_y = crop.my1 - crop.my0;
+    } else {
+        const int c = sc.comp[0].comp_idx, n = 8 >> scale_log2;
+        w.mx0 = crop.ox[c] / n, w.my0 = crop.oy[c] / n;
+        w.mcus_x = (crop.ox[c] + crop.wx[c] + n - 1) / n - w.mx0, w.mcus_y = (crop.oy[c] + crop.wy[c] + n - 1) / n - w.my0;
+    }
+    const MagicDiv m = magic_div(static_cast<uint32_t>(w.mcus_x));
+    w.mcus_x_mul = m.mul, w.mcus_x_shift = m.shift;
+    return w;
+}
 
 void Decoder::make_plan()
 {
@@ -427,7 +490,7 @@ jpeggpu_status build_jobs(
     if (!d.parsed) return JPEGGPU_INVALID_ARGUMENT;
     const Stream& s = d.reader.s;
     for (int c = 0; c < s.num_comp; ++c) {
-        if (!img->image[c] || img->pitch[c] < d.scaled(s.comp[c].size_x)) return JPEGGPU_INVALID_ARGUMENT;
+        if (!img->image[c] || img->pitch[c] < d.plane_x(c)) return JPEGGPU_INVALID_ARGUMENT;
     }
     if (!d_tmp || (reinterpret_cast<uintptr_t>(d_tmp) & 255)) return JPEGGPU_INVALID_ARGUMENT;
     if (tmp_size < d.plan.total) return JPEGGPU_INTERNAL_ERROR;
@@ -497,12 +560,14 @@ jpeggpu_status build_jobs(
             const Component& fc = s.comp[c.comp_idx];
             ip.comp_h[a]        = c.h;
             ip.comp_v[a]        = c.v;
-            ip.size_x[a]        = d.scaled(fc.size_x);
-            ip.size_y[a]        = d.scaled(fc.size_y);
+            ip.size_x[a]        = d.plane_x(c.comp_idx); // (cropped: the window, and the window's units below)
+            ip.size_y[a]        = d.plane_y(c.comp_idx);
             ip.pitch[a]         = img->pitch[c.comp_idx];
             ip.qidx[a]          = fc.qidx;
             ip.plane[a]         = img->image[c.comp_idx];
         }
+        job.win = d.scan_window(sc);
+        if (job.win.mcus_x) ip.num_du = job.win.mcus_x * job.win.mcus_y * sc.du_per_mcu;
         job.bytes      = base + plan.off_bytes;
         job.chunks     = reinterpret_cast<const DestuffChunk*>(blob + pl.blob_chunks);
         job.segments   = reinterpret_cast<const Segment*>(blob + pl.blob_segments);
@@ -750,6 +815,12 @@ enum jpeggpu_status jpeggpu_decoder_parse_header(
     d.parsed   = false;
     d.scale_log2 = d.scale_log2_request;
     d.idct_method = d.idct_method_request;
+    d.crop.on     = false;
+    const bool crop = d.crop_request[2] > 0;
+    if (crop && d.shard_world > 1) {
+        d.logger.log("a crop and a segment shard do not go together\n");
+        return JPEGGPU_NOT_SUPPORTED;
+    }
     jpeggpu_status st;
     try {
         const int ask = d.subseq_request > 0 ? d.subseq_request : -d.batch_hint; // 0 / -N: chosen per image for N images per call
@@ -760,14 +831,27 @@ enum jpeggpu_status jpeggpu_decoder_parse_header(
     }
     if (st != JPEGGPU_SUCCESS) return st;
     const jg::Stream& s = d.reader.s;
+    if (crop) {
+        if (!d.set_crop_window()) {
+            d.logger.log("crop %d,%d %dx%d does not lie inside the image\n", d.crop_request[0], d.crop_request[1], d.crop_request[2], d.crop_request[3]);
+            return JPEGGPU_INVALID_ARGUMENT;
+        }
+        // one host-walked scan with restart markers: keep only the segments that hold the window's MCUs
+        const jg::Scan& sc = s.scans[0];
+        if (s.num_scans == 1 && s.restart_interval > 0 && !sc.device_walk && !sc.segments.empty()) {
+            const jg::IdctWindow w = d.scan_window(sc);
+            const int m0 = w.my0 * sc.mcus_x + w.mx0, m1 = (w.my0 + w.mcus_y - 1) * sc.mcus_x + w.mx0 + w.mcus_x - 1;
+            d.reader.cut_segments(m0 / sc.mcus_per_segment, m1 / sc.mcus_per_segment + 1);
+        }
+    }
     if (d.device_scan)
         d.logger.log("device-side marker scan: %s (jpeggpu_ext_set_device_scan / JPEGGPU_DEVICE_SCAN)\n",
                      d.device_scan == 2 ? "checked -- jpeggpu_decoder_decode waits for the stream and returns the device's status" : "asynchronous");
     std::memset(img_info, 0, sizeof(*img_info));
     img_info->num_components = s.num_comp;
     for (int c = 0; c < s.num_comp; ++c) {
-        img_info->sizes_x[c]       = d.scaled(s.comp[c].size_x); // libjpeg's downsampled_width at the scale
-        img_info->sizes_y[c]       = d.scaled(s.comp[c].size_y);
+        img_info->sizes_x[c]       = d.plane_x(c); // libjpeg's downsampled_width at the scale (cropped: the window's)
+        img_info->sizes_y[c]       = d.plane_y(c);
         img_info->subsampling.x[c] = s.comp[c].hs;
         img_info->subsampling.y[c] = s.comp[c].vs;
     }
@@ -990,6 +1074,34 @@ enum jpeggpu_status jpeggpu_ext_set_idct(jpeggpu_decoder_t decoder, enum jpeggpu
     const int m = static_cast<int>(method);
     if (m != JPEGGPU_EXT_IDCT_REFERENCE && m != JPEGGPU_EXT_IDCT_ISLOW) return JPEGGPU_INVALID_ARGUMENT;
     decoder->d.idct_method_request = m == JPEGGPU_EXT_IDCT_ISLOW ? jg::kIdctIslow : jg::kIdctReference;
+    return JPEGGPU_SUCCESS;
+}
+
+enum jpeggpu_status jpeggpu_ext_set_crop(jpeggpu_decoder_t decoder, int x, int y, int width, int height)
+{
+    if (!decoder || x < 0 || y < 0 || width < 0 || height < 0 || (width == 0) != (height == 0)) return JPEGGPU_INVALID_ARGUMENT;
+    int* r = decoder->d.crop_request;
+    r[0] = width ? x : 0, r[1] = width ? y : 0, r[2] = width, r[3] = height; // 0 x 0: no crop
+    return JPEGGPU_SUCCESS;
+}
+
+enum jpeggpu_status jpeggpu_ext_get_crop(jpeggpu_decoder_t decoder, struct jpeggpu_ext_crop_info* info)
+{
+    if (!decoder || !info) return JPEGGPU_INVALID_ARGUMENT;
+    const Decoder& d = decoder->d;
+    if (!d.parsed) return JPEGGPU_INVALID_ARGUMENT;
+    const jg::Stream& s = d.reader.s;
+    std::memset(info, 0, sizeof(*info));
+    info->x      = d.crop.on ? d.crop.x : 0;
+    info->y      = d.crop.on ? d.crop.y : 0;
+    info->width  = d.crop.on ? d.crop.w : d.scaled(s.size_x);
+    info->height = d.crop.on ? d.crop.h : d.scaled(s.size_y);
+    for (int c = 0; c < s.num_comp; ++c) {
+        info->origin_x[c] = d.crop.on ? d.crop.ox[c] : 0;
+        info->origin_y[c] = d.crop.on ? d.crop.oy[c] : 0;
+        info->full_x[c]   = d.scaled(s.comp[c].size_x);
+        info->full_y[c]   = d.scaled(s.comp[c].size_y);
+    }
     return JPEGGPU_SUCCESS;
 }
 
@@ -1391,6 +1503,44 @@ enum jpeggpu_status jpeggpu_ext_planes_to_rgbi_fancy(
     const hipError_t err = jg::launch_rgbi_fancy(
         src->image, src->pitch, info->sizes_x, info->sizes_y, info->subsampling.x, info->subsampling.y,
         sx_max, sy_max, nc, dst, dst_pitch, width, height, stream);
+    return err == hipSuccess ? JPEGGPU_SUCCESS : JPEGGPU_INTERNAL_ERROR;
+}
+
+enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_fancy(
+    const struct jpeggpu_img_info* info,
+    const struct jpeggpu_ext_crop_info* crop,
+    const struct jpeggpu_img* src,
+    uint8_t* dst,
+    int dst_pitch,
+    jpeggpu_stream_t stream)
+{
+    if (!info || !crop || !src || !dst || crop->width <= 0 || crop->height <= 0 || crop->x < 0 || crop->y < 0 || dst_pitch < 3 * crop->width)
+        return JPEGGPU_INVALID_ARGUMENT;
+    const int nc = info->num_components;
+    if (nc != 1 && nc != 3) return JPEGGPU_NOT_SUPPORTED; // as jpeggpu_ext_planes_to_rgbi_fancy
+    int sx_max = 0, sy_max = 0;
+    for (int c = 0; c < nc; ++c) {
+        if (info->subsampling.x[c] < 1 || info->subsampling.y[c] < 1) return JPEGGPU_INVALID_ARGUMENT;
+        if (!src->image[c] || src->pitch[c] < info->sizes_x[c] || info->sizes_x[c] < 1 || info->sizes_y[c] < 1) return JPEGGPU_INVALID_ARGUMENT;
+        if (crop->origin_x[c] < 0 || crop->origin_y[c] < 0 || crop->origin_x[c] + info->sizes_x[c] > crop->full_x[c] ||
+            crop->origin_y[c] + info->sizes_y[c] > crop->full_y[c])
+            return JPEGGPU_INVALID_ARGUMENT; // the window must lie inside the plane
+        sx_max = info->subsampling.x[c] > sx_max ? info->subsampling.x[c] : sx_max;
+        sy_max = info->subsampling.y[c] > sy_max ? info->subsampling.y[c] : sy_max;
+    }
+    for (int c = 0; c < nc; ++c) // libjpeg upsamples by integral ratios only (jdsample.c)
+        if (sx_max % info->subsampling.x[c] != 0 || sy_max % info->subsampling.y[c] != 0) return JPEGGPU_NOT_SUPPORTED;
+    for (int c = 0; c < nc; ++c) { // every sample the rectangle reads, and its halo, clipped to the plane, is in the window
+        const int hr = sx_max / info->subsampling.x[c], vr = sy_max / info->subsampling.y[c];
+        const int lo_x = std::max(crop->x / hr - 1, 0), hi_x = std::min((crop->x + crop->width - 1) / hr + 1, crop->full_x[c] - 1);
+        const int lo_y = std::max(crop->y / vr - 1, 0), hi_y = std::min((crop->y + crop->height - 1) / vr + 1, crop->full_y[c] - 1);
+        if (lo_x < crop->origin_x[c] || hi_x >= crop->origin_x[c] + info->sizes_x[c] || lo_y < crop->origin_y[c] ||
+            hi_y >= crop->origin_y[c] + info->sizes_y[c])
+            return JPEGGPU_INVALID_ARGUMENT;
+    }
+    const hipError_t err = jg::launch_crop_rgbi_fancy(
+        src->image, src->pitch, info->sizes_x, info->sizes_y, crop->origin_x, crop->origin_y, crop->full_x, info->subsampling.x,
+        info->subsampling.y, sx_max, sy_max, nc, crop->x, crop->y, dst, dst_pitch, crop->width, crop->height, stream);
     return err == hipSuccess ? JPEGGPU_SUCCESS : JPEGGPU_INTERNAL_ERROR;
 }
 

@@ -375,6 +375,17 @@ static_assert(offsetof(IdctParams, scale_log2) == offsetof(IdctParams, du_comp) 
                   offsetof(IdctParams, comp_h) == offsetof(IdctParams, du_comp) + 32,
               "the scale and the IDCT method sit in what was padding: the layout of every other field, and sizeof(ScanJob), are unchanged");
 
+/// Cropped decoding (jpeggpu_ext_set_crop): the IDCT transforms the MCUs [mx0, mx0 + mcus_x) x [my0, my0 + mcus_y) of the
+/// scan's MCU grid only (for a non-interleaved scan: its block grid) and stores them relative to the window's top-left
+/// corner. Window unit w is MCU (mx0 + wm % mcus_x, my0 + wm / mcus_x), wm = w / du_per_mcu, data unit w % du_per_mcu of
+/// it; IdctParams::num_du then counts the window's units, and IdctParams::size_x / size_y / plane describe the window
+/// planes. mcus_x == 0: no window, unit w is stream unit w (every job the plain instantiations see).
+struct IdctWindow {
+    int mx0, my0;
+    int mcus_x, mcus_y;
+    uint32_t mcus_x_mul, mcus_x_shift; // magic_div(mcus_x)
+};
+
 /// IdctParams::idct_method (jpeggpu_ext_idct): the reference's fixed-point transform, or libjpeg's jpeg_idct_islow.
 constexpr uint8_t kIdctReference = 0, kIdctIslow = 1;
 
@@ -439,6 +450,7 @@ struct ScanJob {
     IdctParams ip;
     int* bnd_p;                  // [num_seq] exit state of the subsequence in front of sequence b as b's workgroup assumed it
     int* bnd_cz;                 //   (-1: nothing to say): a boundary where it equals the stored state needs no flow
+    IdctWindow win;              // jpeggpu_ext_set_crop: the MCUs the IDCT transforms (win.mcus_x == 0: every one)
 };
 
 } // namespace jg

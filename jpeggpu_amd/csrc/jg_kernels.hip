@@ -2269,6 +2269,45 @@ struct IdctOf<IslowJobs<JS>> {
     using type = IdctIslow;
 };
 
+/// Which data units the IDCT kernels transform is a policy of the job source as well: every unit of the job in stream
+/// order for the plain sources, the units of the job's MCU window (jpeggpu_ext_set_crop, IdctWindow) for CropJobs<JS>,
+/// which the launch picks when a call holds a cropped job. That instantiation decodes a job without a window as the plain
+/// one does, so one launch serves a batch of both kinds.
+template <class JS>
+struct CropJobs {
+    JS js;
+    __device__ __forceinline__ const ScanJob& get() const { return js.get(); }
+};
+template <class JS>
+struct IsCropped : std::false_type {
+};
+template <class JS>
+struct IsCropped<CropJobs<JS>> : std::true_type {
+};
+template <class JS>
+struct IsCropped<IslowJobs<JS>> : IsCropped<JS> {
+};
+
+/// Unit w of a cropped job's window (IdctWindow): its index in the job's stream order (the data-unit table) and the
+/// column and row of its MCU inside the window. A job without a window: unit w itself, and the MCU in the frame.
+struct WindowUnit {
+    int stream, mx, my, k;
+};
+__device__ __forceinline__ WindowUnit window_unit(const IdctParams& ip, const IdctWindow& win, int w)
+{
+    const int wm = static_cast<int>(magic_quot(w, ip.du_per_mcu_mul, ip.du_per_mcu_shift));
+    const int k  = w - wm * ip.du_per_mcu;
+    if (win.mcus_x == 0) {
+        const int mcu = wm + ip.first_mcu;
+        const int my  = static_cast<int>(magic_quot(mcu, ip.mcus_x_mul, ip.mcus_x_shift));
+        return WindowUnit{w, mcu - my * ip.mcus_x, my, k};
+    }
+    const int my  = static_cast<int>(magic_quot(wm, win.mcus_x_mul, win.mcus_x_shift));
+    const int mx  = wm - my * win.mcus_x;
+    const int mcu = (win.my0 + my) * ip.mcus_x + win.mx0 + mx;
+    return WindowUnit{(mcu - ip.first_mcu) * ip.du_per_mcu + k, mx, my, k};
+}
+
 /// One 8-point pass of jpeg_idct_islow (jidctint.c, CONST_BITS = 13): the eight outputs before their DESCALE, in T (int:
 /// wrapping 32-bit arithmetic, the library is built with -fwrapv; long long: jidctint.c's JLONG). Output i is row i of a
 /// column (pass 1) or column i of a row (pass 2).
@@ -2333,6 +2372,7 @@ template <class JS>
 __global__ __launch_bounds__(256) void idct_kernel(JS js)
 {
     using X = typename IdctOf<JS>::type;
+    constexpr bool kCrop = IsCropped<JS>::value;
     __shared__ __attribute__((aligned(16))) int16_t s_blk[kIdctDuPerBlock][kIdctDuStride]; // [unit][col * 8 + row]
     // ISLOW: the int workspace between the passes, [unit][row * 8 + col] (+8: as s_blk)
     __shared__ __attribute__((aligned(16))) int s_ws[X::kIslow ? kIdctDuPerBlock : 1][X::kIslow ? kIdctDuStride : 4];
@@ -2373,7 +2413,11 @@ __global__ __launch_bounds__(256) void idct_kernel(JS js)
     // row in front of the first iteration, in a workgroup that lives for eight iterations.
     uint2_t rec[kIdctIters];
 #pragma unroll
-    for (int it = 0; it < kIdctIters; ++it) rec[it] = ld_global(J.du_tab + min(du0 + it * kIdctDuPerBlock + dl, num_du - 1));
+    for (int it = 0; it < kIdctIters; ++it) {
+        const int w = min(du0 + it * kIdctDuPerBlock + dl, num_du - 1);
+        if constexpr (kCrop) rec[it] = ld_global(J.du_tab + window_unit(ip, js.get().win, w).stream); // (a window unit: its MCU's place in the stream)
+        else rec[it] = ld_global(J.du_tab + w);
+    }
     // (and the lane's byte and word of the job's geometry tables, below)
     const uint32_t unit_byte = reinterpret_cast<const uint8_t*>(ip.du_comp)[t & 31];
     const uint32_t comp_word = reinterpret_cast<const uint32_t*>(ip.comp_h)[t & 31];
@@ -2385,7 +2429,7 @@ __global__ __launch_bounds__(256) void idct_kernel(JS js)
     // compiler's to count, and the first entries below travel while the geometry is worked out.
     const int gdu  = min(du0 + t, num_du - 1);
     const int grel = static_cast<int>(magic_quot(gdu, ip.du_per_mcu_mul, ip.du_per_mcu_shift));
-    const int gk   = gdu - grel * ip.du_per_mcu;
+    int gk         = gdu - grel * ip.du_per_mcu;
     // What the unit's place depends on sits in two small tables of the job: the MCU's units (component, block column,
     // block row: three arrays of 10 bytes) and the components (six arrays of 4 ints, then 4 plane pointers). Lane L of
     // every half wave loads byte L of the first and word L of the second -- loads that depend on nothing -- and a unit
@@ -2401,8 +2445,12 @@ __global__ __launch_bounds__(256) void idct_kernel(JS js)
                   "32 words from comp_h on");
     const auto from_lane = [](int lane, uint32_t v) { return static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(lane * 4, static_cast<int>(v))); };
     const int gmcu = grel + ip.first_mcu;
-    const int gmy  = static_cast<int>(magic_quot(gmcu, ip.mcus_x_mul, ip.mcus_x_shift));
-    const int gmx  = gmcu - gmy * ip.mcus_x;
+    int gmy        = static_cast<int>(magic_quot(gmcu, ip.mcus_x_mul, ip.mcus_x_shift));
+    int gmx        = gmcu - gmy * ip.mcus_x;
+    if constexpr (kCrop) { // the MCU's column and row in the window, whose top-left corner ip.plane is
+        const WindowUnit u = window_unit(ip, js.get().win, gdu);
+        gk = u.k, gmx = u.mx, gmy = u.my;
+    }
     // a table entry that was never written (corrupt stream) must not lead out of the buffer
     uint32_t toff[kIdctIters], tcnt[kIdctIters];
     const uint64_t limit = J.sym_entries - 10 * kSymSectorStride; // a 128-entry gather from here stays inside
@@ -2700,14 +2748,20 @@ __global__ __launch_bounds__(256) void idct_scaled_kernel(JS js)
     const int num_du     = ip.num_du;
     if (ip.scale_log2 != kLg || du0 >= num_du) return; // (uniform)
     const int t  = threadIdx.x;
-    const int du = min(du0 + t, num_du - 1);
+    int du = min(du0 + t, num_du - 1);
 
     // geometry (idct_kernel's, at N pixels per block side)
-    const int rel = static_cast<int>(magic_quot(du, ip.du_per_mcu_mul, ip.du_per_mcu_shift));
-    const int k   = du - rel * ip.du_per_mcu;
-    const int mcu = rel + ip.first_mcu;
-    const int my  = static_cast<int>(magic_quot(mcu, ip.mcus_x_mul, ip.mcus_x_shift));
-    const int mx  = mcu - my * ip.mcus_x;
+    int k, mx, my;
+    if constexpr (IsCropped<JS>::value) { // a window unit (idct_kernel): its MCU's place in the stream, and in the window
+        const WindowUnit u = window_unit(ip, js.get().win, du);
+        du = u.stream, k = u.k, mx = u.mx, my = u.my;
+    } else {
+        const int rel = static_cast<int>(magic_quot(du, ip.du_per_mcu_mul, ip.du_per_mcu_shift));
+        k             = du - rel * ip.du_per_mcu;
+        const int mcu = rel + ip.first_mcu;
+        my            = static_cast<int>(magic_quot(mcu, ip.mcus_x_mul, ip.mcus_x_shift));
+        mx            = mcu - my * ip.mcus_x;
+    }
     const int sc  = ip.du_comp[k];
     const int n   = 8 >> lg;
     const int x0  = (mx * ip.comp_h[sc] + ip.du_dx[k]) * n;
@@ -2946,6 +3000,17 @@ __device__ __forceinline__ int fancy_sample(const FancyComp& c, const uint8_t (&
 
 __device__ __forceinline__ uint32_t clamp255(int v) { return static_cast<uint32_t>(min(max(v, 0), 255)); }
 
+/// Cropped output (jpeggpu_ext_crop_to_rgbi_fancy): output pixel (x, y) is pixel (x + win.x, y + win.y) of the image, and
+/// each FancyComp describes the component's decoded WINDOW (jpeggpu_ext_set_crop): its plane, its size, and in `win` the
+/// window's origin in the component's full plane. The samples are clamped to the window instead of the plane: for every
+/// sample an output pixel of the rectangle reads, that is the same clamp, because the window holds the rectangle's samples
+/// and their one-sample halo, clipped to the plane. (The fancy / replicate choice, FancyComp::mode, is made on the full
+/// plane sizes.)
+struct FancyWindow {
+    int x, y;         // the rectangle's top-left pixel in the image
+    int ox[3], oy[3]; // each component's window origin in its plane
+};
+
 __global__ __launch_bounds__(256) void fancy_rgbi_kernel(FancyParams p, uint8_t* __restrict__ dst, int dst_pitch, int width, int height)
 {
     __shared__ uint8_t s_t[3][kFancyLdsH][kFancyLdsW];
@@ -2980,6 +3045,63 @@ __global__ __launch_bounds__(256) void fancy_rgbi_kernel(FancyParams p, uint8_t*
             if (p.ncomp == 3) {
                 const int cb = fancy_sample(p.comp[1], s_t[1], bx[1], by[1], xi, y) - 128;
                 const int cr = fancy_sample(p.comp[2], s_t[2], bx[2], by[2], xi, y) - 128;
+                out[3 * i + 0] = clamp255(Y + ((91881 * cr + (1 << 15)) >> 16));                // FIX(1.40200)
+                out[3 * i + 1] = clamp255(Y + ((-22554 * cb - 46802 * cr + (1 << 15)) >> 16)); // FIX(0.34414), FIX(0.71414)
+                out[3 * i + 2] = clamp255(Y + ((116130 * cb + (1 << 15)) >> 16));               // FIX(1.77200)
+            } else {
+                out[3 * i + 0] = out[3 * i + 1] = out[3 * i + 2] = static_cast<uint32_t>(Y);
+            }
+        }
+        uint8_t* drow = dst + static_cast<size_t>(y) * dst_pitch + static_cast<size_t>(x) * 3;
+        if (x + 4 <= width && (reinterpret_cast<uintptr_t>(drow) & 3) == 0) {
+            uint32_t* d = reinterpret_cast<uint32_t*>(drow);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) d[k] = out[4 * k] | out[4 * k + 1] << 8 | out[4 * k + 2] << 16 | out[4 * k + 3] << 24;
+        } else {
+            for (int i = 0; i < 12 && x + i / 3 < width; ++i) drow[i] = static_cast<uint8_t>(out[i]);
+        }
+    }
+}
+
+/// fancy_rgbi_kernel for a rectangle of the image (FancyWindow): the same tiles and arithmetic, on image coordinates
+/// offset by the rectangle's origin, with the loads clamped to the window.
+__global__ __launch_bounds__(256) void crop_rgbi_fancy_kernel(FancyParams p, FancyWindow win, uint8_t* __restrict__ dst, int dst_pitch, int width, int height)
+{
+    __shared__ uint8_t s_t[3][kFancyLdsH][kFancyLdsW];
+    const int t  = threadIdx.x;
+    const int x0 = blockIdx.x * kFancyTileW, y0 = blockIdx.y * kFancyTileH;
+    const int ix0 = x0 + win.x, iy0 = y0 + win.y; // the tile's origin in the image
+    int bx[3], by[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const FancyComp& c = p.comp[k];
+        // samples floor(x0 / hr) - 1 .. floor((x0 + 255) / hr) + 1: at most 256 + 2 columns and 8 + 2 rows (ratio 1)
+        bx[k] = ix0 / c.hr - 1;
+        by[k] = iy0 / c.vr - 1;
+        if (k >= p.ncomp) continue;
+        const int nx = (ix0 + kFancyTileW - 1) / c.hr + 2 - bx[k], ny = (iy0 + kFancyTileH - 1) / c.vr + 2 - by[k];
+        const int ox = win.ox[k], oy = win.oy[k];
+        for (int j = 0; j < ny; ++j) {
+            const uint8_t* row = c.plane + static_cast<size_t>(min(max(by[k] + j - oy, 0), c.h - 1)) * c.pitch;
+            for (int i = t; i < nx; i += 256) s_t[k][j][i] = row[min(max(bx[k] + i - ox, 0), c.w - 1)];
+        }
+    }
+    __syncthreads();
+    const int x = x0 + 4 * (t & 63);
+    if (x >= width) return;
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+        const int y = y0 + 2 * (t >> 6) + dy;
+        if (y >= height) break;
+        const int iy = y + win.y;
+        uint32_t out[12];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int xi = min(x + i, width - 1) + win.x;
+            const int Y  = fancy_sample(p.comp[0], s_t[0], bx[0], by[0], xi, iy);
+            if (p.ncomp == 3) {
+                const int cb = fancy_sample(p.comp[1], s_t[1], bx[1], by[1], xi, iy) - 128;
+                const int cr = fancy_sample(p.comp[2], s_t[2], bx[2], by[2], xi, iy) - 128;
                 out[3 * i + 0] = clamp255(Y + ((91881 * cr + (1 << 15)) >> 16));                // FIX(1.40200)
                 out[3 * i + 1] = clamp255(Y + ((-22554 * cb - 46802 * cr + (1 << 15)) >> 16)); // FIX(0.34414), FIX(0.71414)
                 out[3 * i + 2] = clamp255(Y + ((116130 * cb + (1 << 15)) >> 16));               // FIX(1.77200)
@@ -3071,6 +3193,47 @@ hipError_t launch_huff(Stage stage, const JS& js, const JobExtent& e, int grid_y
     return hipGetLastError();
 }
 
+/// The IDCT stage of a launch; G: the job sources' geometry (Plain: every unit in stream order, CropJobs: MCU windows).
+template <class X>
+using Plain = X;
+template <template <class> class G, class JS>
+hipError_t launch_idct(const JS& js, const JobExtent& e, int grid_y, hipStream_t stream)
+{
+    // full-size jobs: idct_kernel, one instantiation per IDCT method present (jpeggpu_ext_set_idct); scaled ones
+    // (jpeggpu_ext_set_scale): idct_scaled_kernel, one launch per scale present. Only a batch can hold several kinds;
+    // each instantiation then sees the other kinds' jobs as empty. A call without ISLOW jobs launches what it did before.
+    if (e.scales & 1u) {
+        const bool alone = e.scales == 1u; // no scaled job
+        constexpr bool batch = std::is_same<JS, JobArray>::value;
+        if (e.methods == (1u << kIdctReference)) {
+            if (alone) {
+                idct_kernel<G<JS>><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(G<JS>{js});
+            } else {
+                if constexpr (batch)
+                    idct_kernel<G<JobArrayFullSize>><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(G<JobArrayFullSize>{JobArrayFullSize{js.jobs}});
+                else
+                    return hipErrorInvalidValue; // the scans of one image share its scale
+            }
+        } else if (e.methods == (1u << kIdctIslow) && alone) {
+            idct_kernel<IslowJobs<G<JS>>><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(IslowJobs<G<JS>>{G<JS>{js}});
+        } else {
+            if constexpr (batch) {
+                using Ref = G<JobArrayFullSizeOf<kIdctReference>>;
+                using Islow = IslowJobs<G<JobArrayFullSizeOf<kIdctIslow>>>;
+                if (e.methods & (1u << kIdctReference)) idct_kernel<Ref><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(Ref{{js.jobs}});
+                idct_kernel<Islow><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(Islow{{{js.jobs}}});
+            } else {
+                return hipErrorInvalidValue; // the scans of one image share its scale and method
+            }
+        }
+    }
+    static_assert(kScaledDuPerWg == kIdctDuPerWg, "one grid for both");
+    if (e.scales & 2u) idct_scaled_kernel<G<JS>, 1><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(G<JS>{js});
+    if (e.scales & 4u) idct_scaled_kernel<G<JS>, 2><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(G<JS>{js});
+    if (e.scales & 8u) idct_scaled_kernel<G<JS>, 3><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(G<JS>{js});
+    return hipGetLastError();
+}
+
 template <class JS>
 hipError_t launch_any(Stage stage, const JS& js, const JobExtent& e, int grid_y, hipStream_t stream)
 {
@@ -3089,39 +3252,8 @@ hipError_t launch_any(Stage stage, const JS& js, const JobExtent& e, int grid_y,
         return hipGetLastError();
     case kStageIdct:
         if (e.max_idct_blocks == 0) return hipSuccess;
-        // full-size jobs: idct_kernel, one instantiation per IDCT method present (jpeggpu_ext_set_idct); scaled ones
-        // (jpeggpu_ext_set_scale): idct_scaled_kernel, one launch per scale present. Only a batch can hold several kinds;
-        // each instantiation then sees the other kinds' jobs as empty. A call without ISLOW jobs launches what it did before.
-        if (e.scales & 1u) {
-            const bool alone = e.scales == 1u; // no scaled job
-            constexpr bool batch = std::is_same<JS, JobArray>::value;
-            if (e.methods == (1u << kIdctReference)) {
-                if (alone) {
-                    idct_kernel<JS><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(js);
-                } else {
-                    if constexpr (batch)
-                        idct_kernel<JobArrayFullSize><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(JobArrayFullSize{js.jobs});
-                    else
-                        return hipErrorInvalidValue; // the scans of one image share its scale
-                }
-            } else if (e.methods == (1u << kIdctIslow) && alone) {
-                idct_kernel<IslowJobs<JS>><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(IslowJobs<JS>{js});
-            } else {
-                if constexpr (batch) {
-                    using Ref = JobArrayFullSizeOf<kIdctReference>;
-                    using Islow = IslowJobs<JobArrayFullSizeOf<kIdctIslow>>;
-                    if (e.methods & (1u << kIdctReference)) idct_kernel<Ref><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(Ref{js.jobs});
-                    idct_kernel<Islow><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(Islow{{js.jobs}});
-                } else {
-                    return hipErrorInvalidValue; // the scans of one image share its scale and method
-                }
-            }
-        }
-        static_assert(kScaledDuPerWg == kIdctDuPerWg, "one grid for both");
-        if (e.scales & 2u) idct_scaled_kernel<JS, 1><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(js);
-        if (e.scales & 4u) idct_scaled_kernel<JS, 2><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(js);
-        if (e.scales & 8u) idct_scaled_kernel<JS, 3><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(js);
-        return hipGetLastError();
+        // a call that holds a cropped job (jpeggpu_ext_set_crop) launches the CropJobs instantiations, for all of its jobs
+        return e.crop ? launch_idct<CropJobs>(js, e, grid_y, stream) : launch_idct<Plain>(js, e, grid_y, stream);
     case kStageSyncIntra:
     case kStageSyncInter:
     case kStageWrite:
@@ -3154,6 +3286,7 @@ void extend(JobExtent& e, const ScanJob& job)
     e.max_idct_blocks = blocks > e.max_idct_blocks ? blocks : e.max_idct_blocks;
     e.scales |= 1u << job.ip.scale_log2;
     if (job.ip.scale_log2 == 0) e.methods |= 1u << job.ip.idct_method;
+    if (job.win.mcus_x != 0) e.crop = true;
     e.max_tab_bytes   = job.sp.tab_bytes > e.max_tab_bytes ? job.sp.tab_bytes : e.max_tab_bytes;
     e.max_tab_bytes_sync = job.sp.tab_bytes_sync > e.max_tab_bytes_sync ? job.sp.tab_bytes_sync : e.max_tab_bytes_sync;
     e.subseq_words    = job.sp.subseq_words;
@@ -3302,6 +3435,41 @@ hipError_t launch_rgbi_fancy(
     }
     const dim3 grid((width + kFancyTileW - 1) / kFancyTileW, (height + kFancyTileH - 1) / kFancyTileH);
     fancy_rgbi_kernel<<<grid, 256, 0, stream>>>(p, dst, dst_pitch, width, height);
+    return hipGetLastError();
+}
+
+hipError_t launch_crop_rgbi_fancy(
+    const uint8_t* const* planes, const int* pitch, const int* win_w, const int* win_h, const int* win_x, const int* win_y,
+    const int* full_w, const int* num_x, const int* num_y, int den_x, int den_y, int ncomp, int x, int y,
+    uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream)
+{
+    if (width <= 0 || height <= 0) return hipSuccess;
+    FancyParams p{};
+    FancyWindow win{};
+    p.ncomp = ncomp;
+    win.x   = x;
+    win.y   = y;
+    for (int c = 0; c < 3; ++c) {
+        const int cc = c < ncomp ? c : 0;
+        FancyComp& f = p.comp[c];
+        if (num_x[cc] < 1 || num_y[cc] < 1 || den_x % num_x[cc] != 0 || den_y % num_y[cc] != 0) return hipErrorInvalidValue; // non-integral
+        if (win_w[cc] < 1 || win_h[cc] < 1 || full_w[cc] < 1) return hipErrorInvalidValue;
+        f.plane   = planes[cc];
+        f.pitch   = pitch[cc];
+        f.w       = win_w[cc]; // the window: what the loads are clamped to
+        f.h       = win_h[cc];
+        f.hr      = den_x / num_x[cc];
+        f.vr      = den_y / num_y[cc];
+        win.ox[c] = win_x[cc];
+        win.oy[c] = win_y[cc];
+        // the choice of launch_rgbi_fancy, on the FULL plane's width
+        if (f.hr == 2 && f.vr == 1 && full_w[cc] > 2) f.mode = kFancyH2V1;
+        else if (f.hr == 2 && f.vr == 2 && full_w[cc] > 2) f.mode = kFancyH2V2;
+        else if (f.hr == 1 && f.vr == 2) f.mode = kFancyH1V2;
+        else f.mode = kFancyReplicate;
+    }
+    const dim3 grid((width + kFancyTileW - 1) / kFancyTileW, (height + kFancyTileH - 1) / kFancyTileH);
+    crop_rgbi_fancy_kernel<<<grid, 256, 0, stream>>>(p, win, dst, dst_pitch, width, height);
     return hipGetLastError();
 }
 

@@ -33,6 +33,7 @@ struct JobExtent {
     int subseq_words    = 0; // identical for every job of a launch
     uint32_t scales     = 0; // bit s: a job decodes at 1 / 2^s (IdctParams::scale_log2)
     uint32_t methods    = 0; // bit m: a full-size job takes IDCT method m (IdctParams::idct_method)
+    bool crop           = false; // a job has an MCU window (jpeggpu_ext_set_crop, ScanJob::win): the IDCT's CropJobs instantiations
     uint32_t max_tab_bytes = 0;      // largest write-pass table pack
     uint32_t max_tab_bytes_sync = 0; // largest sync pack
     bool fuse_tail_write = false;    // batch launches: the tail kernel's parts and the write pass's sequences as ONE launch
@@ -82,6 +83,13 @@ hipError_t launch_rgbi(
 hipError_t launch_rgbi_fancy(
     const uint8_t* const* planes, const int* pitch, const int* w, const int* h, const int* num_x, const int* num_y,
     int den_x, int den_y, int ncomp, uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream);
+/// launch_rgbi_fancy for a rectangle of the image at (x, y), width x height pixels, from the planes' WINDOWS of a cropped
+/// decode (jpeggpu_ext_set_crop): window sizes, their origins in the full planes, and the full planes' widths (which choose
+/// between fancy upsampling and replication, as for the whole image).
+hipError_t launch_crop_rgbi_fancy(
+    const uint8_t* const* planes, const int* pitch, const int* win_w, const int* win_h, const int* win_x, const int* win_y,
+    const int* full_w, const int* num_x, const int* num_y, int den_x, int den_y, int ncomp, int x, int y,
+    uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream);
 
 } // namespace jg
 

@@ -721,9 +721,8 @@ jpeggpu_status Reader::walk_scan(Scan& scan, const Logger& log)
 
 /// Keep only this decoder's share of the scan's restart segments (segments are independent for the
 /// Huffman decode and for DC prediction, reference src/decode_dc.cu:119-144): segments [rank * n / world,
-/// (rank + 1) * n / world), renumbered from 0, with the destuff work list, the transferred byte range and the tail
-/// parts cut to them. Needs a single scan whose restart interval is a whole number of MCU rows, so that a run of
-/// segments is a horizontal band of every plane.
+/// (rank + 1) * n / world) (cut_segments). Needs a single scan whose restart interval is a whole number of MCU rows, so
+/// that a run of segments is a horizontal band of every plane.
 jpeggpu_status Reader::apply_segment_shard(int rank, int world, const Logger& log)
 {
     if (s.num_scans != 1 || s.restart_interval == 0) {
@@ -738,9 +737,19 @@ jpeggpu_status Reader::apply_segment_shard(int rank, int world, const Logger& lo
     const int n = static_cast<int>(scan.segments.size());
     const int a = static_cast<int>(static_cast<long long>(n) * rank / world);
     const int b = static_cast<int>(static_cast<long long>(n) * (rank + 1) / world);
+    scan.first_segment  = a;
+    scan.total_segments = n;
+    cut_segments(a, b);
+    return JPEGGPU_SUCCESS;
+}
+
+/// Keep restart segments [a, b) of the single, host-walked scan, renumbered from 0, with the destuff work list, the
+/// transferred byte range and the tail parts cut to them; data unit 0 of what is left lies in MCU first_mcu = a * restart
+/// interval. The segment shard and the crop (jpeggpu_ext_set_crop) cut with it.
+void Reader::cut_segments(int a, int b)
+{
+    Scan& scan           = s.scans[0];
     const int total_mcus = scan.mcus_x * scan.mcus_y;
-    scan.first_segment   = a;
-    scan.total_segments  = n;
     scan.first_mcu       = a * scan.mcus_per_segment;
     scan.shard_mcus      = std::min(b * scan.mcus_per_segment, total_mcus) - std::min(a * scan.mcus_per_segment, total_mcus);
     scan.num_du          = scan.shard_mcus * scan.du_per_mcu;
@@ -750,7 +759,7 @@ jpeggpu_status Reader::apply_segment_shard(int rank, int world, const Logger& lo
         scan.tail_parts.assign(1, 0);
         scan.num_subseq = 0;
         s.xfer_end      = s.xfer_begin;
-        return JPEGGPU_SUCCESS;
+        return;
     }
     const uint32_t first_sub = static_cast<uint32_t>(scan.segments[a].subseq_offset);
     const uint32_t dst_shift = first_sub * static_cast<uint32_t>(subseq_bytes_);
@@ -781,7 +790,6 @@ jpeggpu_status Reader::apply_segment_shard(int rank, int world, const Logger& lo
     for (const Segment& seg : scan.segments)
         if (seg.subseq_offset - scan.tail_parts.back() >= kTailPartSubseq) scan.tail_parts.push_back(seg.subseq_offset);
     scan.tail_parts.push_back(scan.num_subseq);
-    return JPEGGPU_SUCCESS;
 }
 
 jpeggpu_status Reader::parse(const uint8_t* data, size_t size, int subseq_bytes, const Logger& log, bool device_scan,

@@ -149,6 +149,8 @@ struct Reader {
     jpeggpu_status parse(const uint8_t* data, size_t size, int subseq_bytes, const Logger& log, bool device_scan = false,
                          int shard_rank = 0, int shard_world = 1);
     int subseq_bytes() const { return subseq_bytes_; }
+    /// Keep restart segments [a, b) of the parsed image's single, host-walked scan (jg_reader.cpp).
+    void cut_segments(int a, int b);
 
     Stream s;
 
