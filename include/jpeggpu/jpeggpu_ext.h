@@ -24,6 +24,8 @@
  *   jpeggpu_ext_set_crop /             decode only a rectangle of the image: a window of each plane, the restart segments
  *   jpeggpu_ext_get_crop               outside it skipped (nvJPEG's ROI decode, libjpeg-turbo's jpeg_crop_scanline)
  *   jpeggpu_ext_crop_to_rgbi_fancy     the rectangle as interleaved RGB8, equal to that part of planes_to_rgbi_fancy's image
+ *   jpeggpu_ext_resize_to_rgb          a batch of (cropped) images resized to one size, NHWC or NCHW, with the arithmetic
+ *                                      of Pillow's BILINEAR / BICUBIC Image.resize (torchvision's RandomResizedCrop)
  */
 #ifndef JPEGGPU_JPEGGPU_EXT_H_
 #define JPEGGPU_JPEGGPU_EXT_H_
@@ -362,6 +364,62 @@ enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_fancy(
     uint8_t* dst,
     int dst_pitch,
     jpeggpu_stream_t stream);
+
+/* Batched resize to one size (a training pipeline's Resize + CenterCrop or RandomResizedCrop): each item's RGB -- what
+ * jpeggpu_ext_crop_to_rgbi_fancy makes of a cropped decode's windows, or jpeggpu_ext_planes_to_rgbi_fancy of whole
+ * planes -- resampled to out_w x out_h with the arithmetic of Pillow's Image.resize((out_w, out_h), BILINEAR | BICUBIC),
+ * into ONE uint8 tensor: n x out_h x out_w x 3 (JPEGGPU_EXT_NHWC) or n x 3 x out_h x out_w (JPEGGPU_EXT_NCHW). On planes
+ * of a JPEGGPU_EXT_IDCT_ISLOW decode at scale 1 the result equals Image.open(f).convert("RGB").crop(box).resize(...).
+ * Items may mix scales, IDCT methods, sampling layouts, cropped and whole images, 1 and 3 components.
+ *   - Pillow's arithmetic, per direction of input size `in` and output size `out` (in double): scale = in / out,
+ *     fs = max(scale, 1), support = fs (bilinear) or 2 fs (bicubic, a = -0.5); output coordinate x has center = (x + 0.5)
+ *     scale, first = max((int)(center - support + 0.5), 0) and count = min((int)(center + support + 0.5), in) - first
+ *     taps; tap j weighs filter((j + first - center + 0.5) * (1 / fs)), divided by the sum of the weights (in tap order)
+ *     when it is not 0, then (int)(w 2^22 + 0.5) ((int)(w 2^22 - 0.5) if negative). A pass computes
+ *     clamp_0..255((2^21 + sum w_j p_j) >> 22). The horizontal pass comes first, over the rows the vertical taps read
+ *     only, and its result is clamped to 8 bits; a direction whose size does not change is skipped. Equality with Pillow
+ *     is tested (tests/test_resize_host.py).
+ *   - Two launches per call (not one per item), stream-ordered on `stream`: the horizontal pass reads the planes' windows
+ *     directly -- the items' full-resolution RGB is never written to memory -- and leaves its rows in `d_scratch`; the
+ *     vertical pass writes `dst`. `d_scratch`: caller-owned device memory of at least jpeggpu_ext_resize_scratch_size
+ *     bytes, private to the stream until the call has executed. The host may reuse `items` (and what they point to) as
+ *     soon as the call returns: their descriptors and the weight tables are copied from internal page-locked staging
+ *     (a ring of four: the fifth call in a row waits until the copy of the first has executed). `stream` must belong to
+ *     the current device.
+ *   - JPEGGPU_NOT_SUPPORTED: a filter other than the two, an item of 2 or 4 components or with non-integral sampling
+ *     ratios. JPEGGPU_INVALID_ARGUMENT: NULL pointers, n, out_w or out_h <= 0 (or n > 65535), an unknown layout, an item
+ *     whose windows do not hold its rectangle's samples (the checks of jpeggpu_ext_crop_to_rgbi_fancy), scratch_size too
+ *     small. Every check is made before anything is enqueued; on an error nothing is written. */
+struct jpeggpu_ext_resize_item {
+    const struct jpeggpu_img_info* info;       /* as parse_header reported it (a cropped decode: the windows) */
+    const struct jpeggpu_ext_crop_info* crop;  /* jpeggpu_ext_get_crop's result; NULL: the whole image */
+    const struct jpeggpu_img* src;             /* the decoded planes */
+};
+enum jpeggpu_ext_filter { JPEGGPU_EXT_FILTER_BILINEAR = 0, JPEGGPU_EXT_FILTER_BICUBIC = 1 };
+enum jpeggpu_ext_output_layout { JPEGGPU_EXT_NHWC = 0, JPEGGPU_EXT_NCHW = 1 };
+/* Bytes of d_scratch a call needs (the descriptors, the weight tables, and per item the horizontal pass's rows:
+ * out_w x 3 bytes, padded to 16, for each rectangle row the vertical taps read); 0 for arguments the call would refuse.
+ * It only grows with n for the same items. */
+size_t jpeggpu_ext_resize_scratch_size(
+    const struct jpeggpu_ext_resize_item* items, int n, int out_w, int out_h, enum jpeggpu_ext_filter filter);
+enum jpeggpu_status jpeggpu_ext_resize_to_rgb(
+    const struct jpeggpu_ext_resize_item* items,
+    int n,
+    int out_w,
+    int out_h,
+    enum jpeggpu_ext_filter filter,
+    enum jpeggpu_ext_output_layout layout,
+    uint8_t* dst,
+    void* d_scratch,
+    size_t scratch_size,
+    jpeggpu_stream_t stream);
+/* The weight table the kernels use for input size `in` -> output size `out` (host only, no device needed): for output
+ * coordinate x, taps first[x] .. first[x] + count[x] - 1 with weights[x * max_taps + j] (22 fraction bits; entries beyond
+ * count[x] are set to 0). max_taps must be at least 2 ceil(support) + 1 (support: fs for bilinear, 2 fs for bicubic, as
+ * above). JPEGGPU_INVALID_ARGUMENT for NULL pointers, in or out <= 0 or too small a max_taps; JPEGGPU_NOT_SUPPORTED for
+ * another filter. */
+enum jpeggpu_status jpeggpu_ext_resize_weights(
+    int in, int out, enum jpeggpu_ext_filter filter, int* first, int* count, int* weights, int max_taps);
 
 #ifdef __cplusplus
 }

@@ -13,11 +13,15 @@ from .api import (  # noqa: F401
     Status,
     crop_to_rgb,
     decode_to_planes,
+    decode_resized,
     decode_to_rgb,
     fused_tail_timeouts,
     lib,
     parse_headers,
     planes_to_rgb,
+    resize_scratch_size,
+    resize_to_rgb,
+    resize_weights,
     self_test,
     status_string,
 )

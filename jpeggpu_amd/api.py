@@ -15,6 +15,8 @@ from . import build as _build
 MAX_COMP = 4
 STAGES = ("front", "destuff", "sync_intra", "sync_inter", "tails", "write", "idct")
 IDCT_METHODS = {"reference": 0, "islow": 1}  # enum jpeggpu_ext_idct
+FILTERS = {"bilinear": 0, "bicubic": 1}  # enum jpeggpu_ext_filter
+LAYOUTS = {"NHWC": 0, "NCHW": 1}  # enum jpeggpu_ext_output_layout
 
 
 class Status(enum.IntEnum):
@@ -46,6 +48,11 @@ class CropInfo(C.Structure):
     _fields_ = [("x", C.c_int), ("y", C.c_int), ("width", C.c_int), ("height", C.c_int),
                 ("origin_x", C.c_int * MAX_COMP), ("origin_y", C.c_int * MAX_COMP),
                 ("full_x", C.c_int * MAX_COMP), ("full_y", C.c_int * MAX_COMP)]
+
+
+class ResizeItem(C.Structure):
+    """struct jpeggpu_ext_resize_item: a decoded image's info and planes, and its crop (NULL: the whole image)."""
+    _fields_ = [("info", C.POINTER(ImgInfo)), ("crop", C.POINTER(CropInfo)), ("src", C.POINTER(Img))]
 
 
 class ExtScanLayout(C.Structure):
@@ -152,6 +159,12 @@ def lib():
     L.jpeggpu_ext_get_crop.argtypes = [dec, C.POINTER(CropInfo)]
     L.jpeggpu_ext_crop_to_rgbi_fancy.argtypes = [
         C.POINTER(ImgInfo), C.POINTER(CropInfo), C.POINTER(Img), C.c_void_p, C.c_int, C.c_void_p]
+    L.jpeggpu_ext_resize_scratch_size.restype = C.c_size_t
+    L.jpeggpu_ext_resize_scratch_size.argtypes = [C.POINTER(ResizeItem), C.c_int, C.c_int, C.c_int, C.c_int]
+    L.jpeggpu_ext_resize_to_rgb.argtypes = [
+        C.POINTER(ResizeItem), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.jpeggpu_ext_resize_weights.argtypes = [
+        C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
     _lib = L
     return L
 
@@ -494,3 +507,138 @@ def parse_headers(decoders, buffers, num_threads=4):
     st = (C.c_int * n)()
     _check(lib().jpeggpu_ext_parse_headers(items, n, num_threads, st), "jpeggpu_ext_parse_headers")
     return infos
+
+
+def _size_hw(size):
+    """torchvision's convention: an int is a square, a pair is (height, width)."""
+    if isinstance(size, int):
+        return size, size
+    h, w = size
+    return int(h), int(w)
+
+
+def resize_max_taps(in_size, out_size, filt="bilinear"):
+    """The row stride jpeggpu_ext_resize_weights needs: 2 ceil(support) + 1 (Pillow's ksize)."""
+    import math
+
+    return 2 * int(math.ceil({"bilinear": 1.0, "bicubic": 2.0}[filt] * max(in_size / out_size, 1.0))) + 1
+
+
+def resize_weights(in_size, out_size, filt="bilinear"):
+    """jpeggpu_ext_resize_weights (host only): the table the resize kernels use for in_size -> out_size, as numpy int32
+    (first[out], count[out], weights[out, max_taps]) with 22 fraction bits."""
+    import numpy as np
+
+    if filt not in FILTERS:
+        raise ValueError("filter %r is not one of %s" % (filt, ", ".join(FILTERS)))
+    k = resize_max_taps(in_size, out_size, filt)
+    first, count = np.zeros(max(out_size, 1), np.int32), np.zeros(max(out_size, 1), np.int32)
+    w = np.zeros((max(out_size, 1), k), np.int32)
+    ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+    _check(lib().jpeggpu_ext_resize_weights(int(in_size), int(out_size), FILTERS[filt], ptr(first), ptr(count), ptr(w), k),
+           "jpeggpu_ext_resize_weights")
+    return first, count, w
+
+
+def _resize_items(planes_list, infos, crop_infos):
+    """(ResizeItem array, objects to keep alive) of decoded images; crop_infos[i] None: the whole image."""
+    n = len(planes_list)
+    items = (ResizeItem * n)()
+    keep = []
+    for i in range(n):
+        src = Img()
+        for c, p in enumerate(planes_list[i]):
+            src.image[c], src.pitch[c] = p.data_ptr(), p.stride(0)
+        ci = crop_infos[i] if crop_infos is not None else None
+        items[i].info = C.pointer(infos[i])
+        items[i].crop = C.pointer(ci) if ci is not None else None
+        items[i].src = C.pointer(src)
+        keep.append((src, infos[i], ci))
+    return items, keep
+
+
+def resize_scratch_size(planes_list, infos, size, crop_infos=None, filt="bilinear"):
+    """jpeggpu_ext_resize_scratch_size of these items (0 if the call would refuse them)."""
+    h, w = _size_hw(size)
+    items, _keep = _resize_items(planes_list, infos, crop_infos)
+    return lib().jpeggpu_ext_resize_scratch_size(items, len(planes_list), w, h, FILTERS[filt])
+
+
+def resize_to_rgb(planes_list, infos, size, crop_infos=None, filt="bilinear", layout="NHWC", out=None):
+    """jpeggpu_ext_resize_to_rgb on torch's current stream: every decoded image i
+    (planes_list[i], infos[i], and crop_infos[i] from a cropped decode, or None for the whole image) resampled to `size`
+    (int: square; (h, w)) with Pillow's BILINEAR or BICUBIC arithmetic. Returns a uint8 tensor of n x h x w x 3 ("NHWC")
+    or n x 3 x h x w ("NCHW"), `out` if given (contiguous, of that shape)."""
+    import torch
+
+    if filt not in FILTERS:
+        raise ValueError("filter %r is not one of %s" % (filt, ", ".join(FILTERS)))
+    if layout not in LAYOUTS:
+        raise ValueError("layout %r is not one of %s" % (layout, ", ".join(LAYOUTS)))
+    h, w = _size_hw(size)
+    n = len(planes_list)
+    device = planes_list[0][0].device
+    items, _keep = _resize_items(planes_list, infos, crop_infos)
+    shape = (n, h, w, 3) if layout == "NHWC" else (n, 3, h, w)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=device)
+    elif tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous uint8 tensor of shape %s" % (shape,))
+    need = lib().jpeggpu_ext_resize_scratch_size(items, n, w, h, FILTERS[filt])
+    scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    _check(lib().jpeggpu_ext_resize_to_rgb(items, n, w, h, FILTERS[filt], LAYOUTS[layout], out.data_ptr(), scratch.data_ptr(),
+                                           need, stream), "jpeggpu_ext_resize_to_rgb")
+    # the scratch tensor is freed by torch's caching allocator in stream order: it is not reused before the launches ran
+    return out
+
+
+def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", device="cuda:0"):
+    """A training pipeline's decode: every JPEG of `datas` decoded with libjpeg-turbo's arithmetic (ISLOW IDCT, fancy
+    upsampling), only the rectangle crops[i] = (x, y, w, h) of it (None: the whole image), in ONE jpeggpu_ext_decode_batch
+    call, then resized to `size` (int: square; (h, w)) with Pillow's BILINEAR or BICUBIC arithmetic by one
+    jpeggpu_ext_resize_to_rgb call. Returns an n x h x w x 3 ("NHWC") or n x 3 x h x w ("NCHW") uint8 tensor equal to
+    Pillow's Image.open(f).convert("RGB").crop((x, y, x + w, y + h)).resize((w_out, h_out), filter) of every image
+    (INTEGRATION.md, "RandomResizedCrop equal to torchvision on Pillow")."""
+    import torch
+
+    dev = torch.device(device)
+    n = len(datas)
+    crops = [None] * n if crops is None else list(crops)
+    if len(crops) != n:
+        raise ValueError("crops must have one entry per image")
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    decs, entries, planes_list, infos, cis, keep = [], [], [], [], [], []
+    try:
+        scans = 0
+        for data, crop in zip(datas, crops):
+            dec = Decoder()
+            decs.append(dec)
+            dec.set_batch_hint(n)
+            dec.set_idct("islow")
+            if crop is not None:
+                dec.set_crop(*crop)
+            info = dec.parse_header(data)
+            scans += dec.layout().num_scans
+            nb = dec.get_buffer_size()
+            tmp = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
+            base = (tmp.data_ptr() + 255) // 256 * 256
+            planes = [torch.empty((info.sizes_y[c], info.sizes_x[c]), dtype=torch.uint8, device=dev)
+                      for c in range(info.num_components)]
+            dec.transfer(base, nb, stream)
+            keep.append(tmp)
+            entries.append((dec, [p.data_ptr() for p in planes], [p.stride(0) for p in planes], base, nb))
+            planes_list.append(planes)
+            infos.append(info)
+            cis.append(dec.crop_info() if crop is not None else None)
+        batch = Batch(scans)
+        scratch = torch.empty(batch.scratch_size, dtype=torch.uint8, device=dev)
+        batch.set_items(entries)
+        batch.decode(scratch.data_ptr(), stream)
+        out = resize_to_rgb(planes_list, infos, size, cis, filt, layout)
+        torch.cuda.synchronize(dev)
+        batch.destroy()
+        return out
+    finally:
+        for dec in decs:
+            dec.cleanup()

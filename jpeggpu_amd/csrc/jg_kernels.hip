@@ -11,6 +11,8 @@
 //   idct_scaled_kernel      the same at 1/2, 1/4, 1/8 size: libjpeg-turbo's reduced IDCTs (jidctred.c; jpeggpu_ext_set_scale)
 //   idct_kernel<IslowJobs<..>>  full size with libjpeg-turbo's jpeg_idct_islow (jidctint.c; jpeggpu_ext_set_idct)
 //   fancy_rgbi_kernel       libjpeg's fancy chroma upsampling + integer YCbCr -> interleaved RGB (jdsample.c, jdcolor.c)
+//   resize_h_kernel /       batched resize to one size with Pillow's BILINEAR / BICUBIC arithmetic: the horizontal taps
+//   resize_v_kernel         straight from the planes' windows (fancy RGB in LDS), then the vertical taps (jpeggpu_ext_resize_to_rgb)
 //
 // Everything is integer / bit-serial: no MFMA. Every kernel takes a job source: one ScanJob by
 // value (drop-in API) or an array indexed by blockIdx.y (batch API: one launch per stage for many
@@ -3000,6 +3002,14 @@ __device__ __forceinline__ int fancy_sample(const FancyComp& c, const uint8_t (&
 
 __device__ __forceinline__ uint32_t clamp255(int v) { return static_cast<uint32_t>(min(max(v, 0), 255)); }
 
+/// jdcolor.c's ycc_rgb_convert of one pixel, Cb and Cr centred on 128: R, G, B into rgb[0..2].
+__device__ __forceinline__ void ycc_rgb(int Y, int cb, int cr, uint32_t* rgb)
+{
+    rgb[0] = clamp255(Y + ((91881 * cr + (1 << 15)) >> 16));                // FIX(1.40200)
+    rgb[1] = clamp255(Y + ((-22554 * cb - 46802 * cr + (1 << 15)) >> 16)); // FIX(0.34414), FIX(0.71414)
+    rgb[2] = clamp255(Y + ((116130 * cb + (1 << 15)) >> 16));               // FIX(1.77200)
+}
+
 /// Cropped output (jpeggpu_ext_crop_to_rgbi_fancy): output pixel (x, y) is pixel (x + win.x, y + win.y) of the image, and
 /// each FancyComp describes the component's decoded WINDOW (jpeggpu_ext_set_crop): its plane, its size, and in `win` the
 /// window's origin in the component's full plane. The samples are clamped to the window instead of the plane: for every
@@ -3045,9 +3055,7 @@ __global__ __launch_bounds__(256) void fancy_rgbi_kernel(FancyParams p, uint8_t*
             if (p.ncomp == 3) {
                 const int cb = fancy_sample(p.comp[1], s_t[1], bx[1], by[1], xi, y) - 128;
                 const int cr = fancy_sample(p.comp[2], s_t[2], bx[2], by[2], xi, y) - 128;
-                out[3 * i + 0] = clamp255(Y + ((91881 * cr + (1 << 15)) >> 16));                // FIX(1.40200)
-                out[3 * i + 1] = clamp255(Y + ((-22554 * cb - 46802 * cr + (1 << 15)) >> 16)); // FIX(0.34414), FIX(0.71414)
-                out[3 * i + 2] = clamp255(Y + ((116130 * cb + (1 << 15)) >> 16));               // FIX(1.77200)
+                ycc_rgb(Y, cb, cr, &out[3 * i]);
             } else {
                 out[3 * i + 0] = out[3 * i + 1] = out[3 * i + 2] = static_cast<uint32_t>(Y);
             }
@@ -3102,9 +3110,7 @@ __global__ __launch_bounds__(256) void crop_rgbi_fancy_kernel(FancyParams p, Fan
             if (p.ncomp == 3) {
                 const int cb = fancy_sample(p.comp[1], s_t[1], bx[1], by[1], xi, iy) - 128;
                 const int cr = fancy_sample(p.comp[2], s_t[2], bx[2], by[2], xi, iy) - 128;
-                out[3 * i + 0] = clamp255(Y + ((91881 * cr + (1 << 15)) >> 16));                // FIX(1.40200)
-                out[3 * i + 1] = clamp255(Y + ((-22554 * cb - 46802 * cr + (1 << 15)) >> 16)); // FIX(0.34414), FIX(0.71414)
-                out[3 * i + 2] = clamp255(Y + ((116130 * cb + (1 << 15)) >> 16));               // FIX(1.77200)
+                ycc_rgb(Y, cb, cr, &out[3 * i]);
             } else {
                 out[3 * i + 0] = out[3 * i + 1] = out[3 * i + 2] = static_cast<uint32_t>(Y);
             }
@@ -3116,6 +3122,172 @@ __global__ __launch_bounds__(256) void crop_rgbi_fancy_kernel(FancyParams p, Fan
             for (int k = 0; k < 3; ++k) d[k] = out[4 * k] | out[4 * k + 1] << 8 | out[4 * k + 2] << 16 | out[4 * k + 3] << 24;
         } else {
             for (int i = 0; i < 12 && x + i / 3 < width; ++i) drow[i] = static_cast<uint8_t>(out[i]);
+        }
+    }
+}
+
+/// Taps of a horizontal-pass workgroup's columns: int32 weights[columns][taps], from LDS when they fit
+/// (kResizeLdsTaps per column) or else straight from the table; RGB of a chunk: one dword (R | G << 8 | B << 16) per pixel.
+/// A product of a weight (|w| < 2^23: normalised weights stay below 1.2) and a sample fits v_mul_i32_i24.
+constexpr int kResizeLdsTaps = 64;
+template <class W>
+__device__ __forceinline__ void resize_taps_h(const W* w, const uint32_t* px, int j0, int j1, int (&acc)[3])
+{
+#pragma unroll 4
+    for (int j = j0; j < j1; ++j) {
+        const int wj = w[j];
+        const uint32_t v = px[j];
+        acc[0] += __mul24(wj, static_cast<int>(v & 255u));
+        acc[1] += __mul24(wj, static_cast<int>((v >> 8) & 255u));
+        acc[2] += __mul24(wj, static_cast<int>((v >> 16) & 255u));
+    }
+}
+
+/// Batched resize (jpeggpu_ext_resize_to_rgb), pass 1: the horizontal taps, read from the planes' windows. A workgroup
+/// owns kResizeHTileW output columns of kResizeHTileH rectangle rows of one item (found by a search of the items' first
+/// tiles). The input columns those columns' taps read are converted to RGB in chunks of up to kFancyTileW: the window
+/// samples under a chunk are staged with their halo exactly as crop_rgbi_fancy_kernel stages a tile, each pixel gets
+/// fancy_sample and ycc_rgb into LDS, and each lane accumulates its output pixel's taps that fall in the chunk. The
+/// result is clamped to uint8 (Pillow keeps its intermediate image in 8 bits) and written to the item's `mid` rows; the
+/// crop's full-resolution RGB never leaves LDS.
+__global__ __launch_bounds__(256) void resize_h_kernel(const ResizeJob* __restrict__ jobs, const int* __restrict__ first_tile, int n, int out_w)
+{
+    __shared__ uint8_t s_t[3][kFancyLdsH][kFancyLdsW];
+    __shared__ uint32_t s_rgb[kResizeHTileH][kFancyTileW];
+    __shared__ int s_w[kResizeHTileW * kResizeLdsTaps];
+    const int b = blockIdx.x;
+    int lo = 0, hi = n - 1; // the last item whose first tile is <= b
+    while (lo < hi) {
+        const int m = (lo + hi + 1) >> 1;
+        if (first_tile[m] <= b) lo = m;
+        else hi = m - 1;
+    }
+    const ResizeJob& J = jobs[lo];
+    const int col_tiles = (out_w + kResizeHTileW - 1) / kResizeHTileW;
+    const int tile = b - first_tile[lo], ty = tile / col_tiles, tx = tile - ty * col_tiles;
+    const int r0 = J.row0 + ty * kResizeHTileH;                  // the tile's first rectangle row
+    const int nr = min(kResizeHTileH, J.row0 + J.rows - r0);
+    const int ox0 = tx * kResizeHTileW, ox1 = min(ox0 + kResizeHTileW, out_w) - 1;
+    const int* __restrict__ tab = J.tab_x;
+    const int a = tab[2 * ox0], e = tab[2 * ox1] + tab[2 * ox1 + 1]; // input columns [a, e) (first and last are monotone)
+    FancyComp comp[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) comp[k] = FancyComp{J.plane[k], J.pitch[k], J.w[k], J.h[k], J.hr[k], J.vr[k], J.mode[k]};
+    const int t = threadIdx.x, r = t / kResizeHTileW, col = t % kResizeHTileW, ox = ox0 + col;
+    const bool mine = r < nr && ox < out_w;
+    const int taps = J.taps_x;
+    const bool lds_w = taps <= kResizeLdsTaps;
+    const int* __restrict__ wts = tab + 2 * out_w + static_cast<size_t>(ox0) * taps; // the tile's columns are consecutive
+    if (lds_w) // made visible by the chunk loop's first barrier
+        for (int q = t; q < (ox1 - ox0 + 1) * taps; q += 256) s_w[q] = wts[q];
+    int f = 0, cnt = 0;
+    if (mine) {
+        f   = tab[2 * ox];
+        cnt = tab[2 * ox + 1];
+    }
+    int acc[3] = {0, 0, 0};
+    for (int c0 = a; c0 < e; c0 += kFancyTileW) {
+        const int cw  = min(kFancyTileW, e - c0);
+        const int ix0 = c0 + J.x, iy0 = r0 + J.y; // the chunk's origin in the image
+        int bx[3], by[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            bx[k] = ix0 / comp[k].hr - 1;
+            by[k] = iy0 / comp[k].vr - 1;
+            if (k >= J.ncomp) continue;
+            const int nx = (ix0 + cw - 1) / comp[k].hr + 2 - bx[k], ny = (iy0 + nr - 1) / comp[k].vr + 2 - by[k];
+            for (int j = 0; j < ny; ++j) {
+                const uint8_t* row = comp[k].plane + static_cast<size_t>(min(max(by[k] + j - J.oy[k], 0), comp[k].h - 1)) * comp[k].pitch;
+                for (int i = t; i < nx; i += 256) s_t[k][j][i] = row[min(max(bx[k] + i - J.ox[k], 0), comp[k].w - 1)];
+            }
+        }
+        __syncthreads();
+        for (int q = t; q < kResizeHTileH * kFancyTileW; q += 256) {
+            const int qy = q / kFancyTileW, qx = q % kFancyTileW;
+            if (qy >= nr || qx >= cw) continue;
+            const int xi = ix0 + qx, yi = iy0 + qy;
+            uint32_t rgb[3];
+            const int Y = fancy_sample(comp[0], s_t[0], bx[0], by[0], xi, yi);
+            if (J.ncomp == 3) {
+                const int cb = fancy_sample(comp[1], s_t[1], bx[1], by[1], xi, yi) - 128;
+                const int cr = fancy_sample(comp[2], s_t[2], bx[2], by[2], xi, yi) - 128;
+                ycc_rgb(Y, cb, cr, rgb);
+            } else {
+                rgb[0] = rgb[1] = rgb[2] = static_cast<uint32_t>(Y);
+            }
+            s_rgb[qy][qx] = rgb[0] | rgb[1] << 8 | rgb[2] << 16;
+        }
+        __syncthreads();
+        if (mine) { // taps j0 .. j1 - 1 of the column, relative to its first, lie in this chunk
+            const int j0 = max(f, c0) - f, j1 = min(f + cnt, c0 + cw) - f;
+            const uint32_t* px = &s_rgb[r][f - c0];
+            if (lds_w) resize_taps_h(&s_w[col * taps], px, j0, j1, acc);
+            else resize_taps_h(wts + static_cast<size_t>(col) * taps, px, j0, j1, acc);
+        }
+        __syncthreads();
+    }
+    if (mine) {
+        uint8_t* o = J.mid + static_cast<size_t>(r0 - J.row0 + r) * J.mid_pitch + 3 * ox;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[c] = static_cast<uint8_t>(clamp255((acc[c] + (1 << 21)) >> 22));
+    }
+}
+
+/// Batched resize, pass 2: the vertical taps over the items' `mid` rows, one item per blockIdx.y. Each lane makes 4
+/// consecutive output pixels of one row (3 dword loads per tap row), so a wave stores 768 contiguous bytes in NHWC, or
+/// 256 per channel plane in NCHW.
+__global__ __launch_bounds__(256) void resize_v_kernel(const ResizeJob* __restrict__ jobs, int out_w, int out_h, int layout, uint8_t* __restrict__ dst)
+{
+    const ResizeJob& J = jobs[blockIdx.y];
+    const int col_tiles = (out_w + kResizeVTileW - 1) / kResizeVTileW;
+    const int t = threadIdx.x;
+    const int x = (blockIdx.x % col_tiles) * kResizeVTileW + 4 * (t & 63);
+    const int y = (blockIdx.x / col_tiles) * kResizeVTileH + (t >> 6);
+    if (x >= out_w || y >= out_h) return;
+    const int* __restrict__ tab = J.tab_y;
+    const int f = tab[2 * y] - J.row0, cnt = tab[2 * y + 1];
+    const int* __restrict__ wts = tab + 2 * out_h + static_cast<size_t>(y) * J.taps_y;
+    const int np = min(4, out_w - x); // pixels of this lane
+    int acc[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) acc[k] = 0;
+    for (int j = 0; j < cnt; ++j) {
+        const int w = wts[j];
+        const uint8_t* s = J.mid + static_cast<size_t>(f + j) * J.mid_pitch + 3 * x; // 4-byte aligned: mid_pitch % 16 == 0
+        if (np == 4) {
+            const uint32_t* s4 = reinterpret_cast<const uint32_t*>(s);
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                const uint32_t v = s4[d];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[4 * d + k] += __mul24(w, static_cast<int>((v >> (8 * k)) & 255u));
+            }
+        } else {
+            for (int k = 0; k < 3 * np; ++k) acc[k] += __mul24(w, static_cast<int>(s[k]));
+        }
+    }
+    uint32_t o[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) o[k] = clamp255((acc[k] + (1 << 21)) >> 22);
+    const size_t item = blockIdx.y;
+    if (layout == 0) {
+        uint8_t* d = dst + ((item * out_h + y) * out_w + x) * 3;
+        if (np == 4 && (reinterpret_cast<uintptr_t>(d) & 3) == 0) {
+            uint32_t* d4 = reinterpret_cast<uint32_t*>(d);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) d4[k] = o[4 * k] | o[4 * k + 1] << 8 | o[4 * k + 2] << 16 | o[4 * k + 3] << 24;
+        } else {
+            for (int k = 0; k < 3 * np; ++k) d[k] = static_cast<uint8_t>(o[k]);
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            uint8_t* d = dst + ((item * 3 + c) * out_h + y) * out_w + x;
+            if (np == 4 && (reinterpret_cast<uintptr_t>(d) & 3) == 0) {
+                *reinterpret_cast<uint32_t*>(d) = o[c] | o[3 + c] << 8 | o[6 + c] << 16 | o[9 + c] << 24;
+            } else {
+                for (int i = 0; i < np; ++i) d[i] = static_cast<uint8_t>(o[3 * i + c]);
+            }
         }
     }
 }
@@ -3470,6 +3642,26 @@ hipError_t launch_crop_rgbi_fancy(
     }
     const dim3 grid((width + kFancyTileW - 1) / kFancyTileW, (height + kFancyTileH - 1) / kFancyTileH);
     crop_rgbi_fancy_kernel<<<grid, 256, 0, stream>>>(p, win, dst, dst_pitch, width, height);
+    return hipGetLastError();
+}
+
+int fancy_mode(int hr, int vr, int full_w)
+{
+    // jdsample.c, jinit_upsampler: 2h1v and 2h2v take the fancy path only on planes wider than 2 samples
+    if (hr == 2 && vr == 1 && full_w > 2) return kFancyH2V1;
+    if (hr == 2 && vr == 2 && full_w > 2) return kFancyH2V2;
+    if (hr == 1 && vr == 2) return kFancyH1V2;
+    return kFancyReplicate;
+}
+
+hipError_t launch_resize(
+    const ResizeJob* d_jobs, const int* d_first_tile, int n, int h_tiles, int out_w, int out_h, int layout,
+    uint8_t* dst, hipStream_t stream)
+{
+    if (n <= 0 || h_tiles <= 0 || out_w <= 0 || out_h <= 0) return hipSuccess;
+    resize_h_kernel<<<h_tiles, 256, 0, stream>>>(d_jobs, d_first_tile, n, out_w);
+    const int v_tiles = ((out_w + kResizeVTileW - 1) / kResizeVTileW) * ((out_h + kResizeVTileH - 1) / kResizeVTileH);
+    resize_v_kernel<<<dim3(v_tiles, n), 256, 0, stream>>>(d_jobs, out_w, out_h, layout, dst);
     return hipGetLastError();
 }
 

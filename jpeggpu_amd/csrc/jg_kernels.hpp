@@ -91,6 +91,43 @@ hipError_t launch_crop_rgbi_fancy(
     const int* full_w, const int* num_x, const int* num_y, int den_x, int den_y, int ncomp, int x, int y,
     uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream);
 
+/// launch_rgbi_fancy's per-component choice (FancyMode) for the ratios hr = h_max / h_c, vr = v_max / v_c and a full
+/// plane `full_w` samples wide.
+int fancy_mode(int hr, int vr, int full_w);
+
+/// One item of a batched resize (launch_resize), in device memory: a rectangle of a decoded image, given as the planes'
+/// windows the way launch_crop_rgbi_fancy takes them, resampled to out_w x out_h RGB by two separable passes whose weight
+/// tables the host computed (jpeggpu_ext_resize_weights). A table of n output coordinates with `taps` taps each is
+/// int32 {first, count}[n] followed by int32 weights[n][taps] (22 fraction bits).
+struct ResizeJob {
+    const uint8_t* plane[3]; // the windows (grey: every entry is component 0)
+    int pitch[3], w[3], h[3];
+    int hr[3], vr[3], mode[3]; // output pixels per sample, FancyMode
+    int ox[3], oy[3];          // each window's origin in its full plane
+    int x, y;                  // the rectangle's top-left pixel in the image
+    int ncomp;                 // 1 or 3
+    int row0, rows;            // rectangle rows row0 .. row0 + rows - 1: the rows the vertical taps read
+    int taps_x, taps_y;
+    const int* tab_x;          // out_w columns
+    const int* tab_y;          // out_h rows
+    uint8_t* mid;              // rows x out_w RGB of the horizontal pass, rows mid_pitch bytes apart
+    int mid_pitch;             // a multiple of 16
+    int pad_;
+};
+constexpr int kResizeHTileW = 32, kResizeHTileH = 8; // horizontal pass: output columns x rows per workgroup
+constexpr int kResizeVTileW = 256, kResizeVTileH = 4; // vertical pass: output pixels x rows per workgroup
+/// Horizontal-pass workgroups of one item.
+inline int resize_h_tiles(int rows, int out_w)
+{
+    return ((rows + kResizeHTileH - 1) / kResizeHTileH) * ((out_w + kResizeHTileW - 1) / kResizeHTileW);
+}
+/// The two passes for `n` items: `d_jobs` ResizeJob[n] and `d_first_tile` int[n] (each item's first horizontal-pass
+/// workgroup; `h_tiles` of them in all) in device memory. `layout` 0: dst is n x out_h x out_w x 3 (NHWC), 1: n x 3 x out_h
+/// x out_w (NCHW).
+hipError_t launch_resize(
+    const ResizeJob* d_jobs, const int* d_first_tile, int n, int h_tiles, int out_w, int out_h, int layout,
+    uint8_t* dst, hipStream_t stream);
+
 } // namespace jg
 
 #endif // JG_KERNELS_HPP_
