@@ -1,5 +1,7 @@
 """Shared matrix of synthetic inputs (reference coverage: test/test.sh:31-43 sampling variants and
 grayscale; plus what it never tests)."""
+import numpy as np
+
 from tools import jpegsynth
 
 S420 = ((2, 2), (1, 1), (1, 1))
@@ -89,3 +91,96 @@ def matrix():
         "cfg5_small": jpegsynth.config(5, small=True),
     }
     return cases
+
+
+class SlowSync:
+    """An entropy-coded stream that does not resynchronise by itself (slow_sync below): the file, the bit length of a
+    data unit of each component and of an MCU when the data are zeros, the restart interval, and how far a flow must
+    run at least (`min_distance`, in subsequences, measured by tests/test_slow_sync_host.py)."""
+
+    def __init__(self, data, unit_bits, mcu_bits, restart_interval, min_distance):
+        self.data, self.unit_bits, self.mcu_bits = data, unit_bits, mcu_bits
+        self.restart_interval, self.min_distance = restart_interval, min_distance
+
+
+DC_Q = 64  # DC quantiser of the slow-sync files
+
+
+def _zero_tables(d, a):
+    """A DC table whose category 0 has the d-bit code 0...0 (category 1 the (d + 1)-bit code 10...0) and an AC table
+    whose symbol (0, 1) has the a-bit code 0...0 (end of block 10...0). On all-zero bits a data unit whose 63 AC
+    coefficients are -1 (value bit 0) and whose DC difference is 0 is then d + 63 (a + 1) bits long. (No code is all
+    ones: libjpeg refuses a table without room for one.)"""
+    dc = [0] * 16
+    dc[d - 1], dc[d] = 1, 1
+    ac = [0] * 16
+    ac[a - 1], ac[a] = 1, 1
+    return (dc, [0, 1]), (ac, [0x01, 0x00])
+
+
+def _minus_one_blocks(by, bx):
+    b = np.full((by, bx, 64), -1, np.int16)
+    b[:, :, 0] = 0
+    return b
+
+
+def _zero_stream(width, height, sampling, dc_bits, interleaved=True, restart_interval=0, watermark=0):
+    """Every component codes DC difference 0 and 63 AC coefficients -1 with the zero codes of _zero_tables (dc_bits[c],
+    a = 1), so the entropy-coded data are zero bits only. `watermark` K > 0: in every K-th MCU the first data unit of
+    each component instead has DC 1 (difference +1, and -1 in the component's next data unit: category 1). The DC
+    quantiser is DC_Q, so a marked block is DC_Q / 8 levels brighter than the others and the planes show where each
+    marked data unit was placed; the AC quantisers are 1."""
+    hmax = max(h for h, _ in sampling)
+    vmax = max(v for _, v in sampling)
+    mx, my = -(-width // (8 * hmax)), -(-height // (8 * vmax))
+    blocks = []
+    for h, v in sampling:
+        if interleaved and len(sampling) > 1:
+            by, bx = my * v, mx * h
+        else:
+            by, bx = -(-(-(-height * v // vmax)) // 8), -(-(-(-width * h // hmax)) // 8)
+        blocks.append(_minus_one_blocks(by, bx))
+    if watermark:
+        mcu = np.arange(mx * my)
+        marked = mcu[mcu % watermark == watermark - 1]
+        for c, (h, v) in enumerate(sampling):
+            blocks[c][(marked // mx) * v, (marked % mx) * h, 0] = 1
+    tabs = [_zero_tables(d, 1) for d in dc_bits]
+    q = np.ones(64, np.uint8)
+    q[0] = DC_Q
+    return jpegsynth.encode_custom(width, height, sampling, blocks, [t[0] for t in tabs], [t[1] for t in tabs],
+                                   qtables=[q] * len(sampling), interleaved=interleaved, restart_interval=restart_interval)
+
+
+def slow_sync():
+    """name -> SlowSync: streams on which a speculative decode that starts at a wrong bit offset does not meet the true
+    path for hundreds of subsequences (flows across sequences, through one tail part of over a thousand subsequences
+    and across multi-hypothesis blocks; a tail part is cut only at a segment start, so no flow leaves one). A decode that
+    starts from (c, z) = (0, 0) at a subsequence start parses the zero bits as valid data units on a grid of its own;
+    it is on the true path only where that grid is the true MCU grid, i.e. where the subsequence start is a multiple of
+    the (odd) MCU bit length: once every mcu_bits subsequences."""
+    S420 = ((2, 2), (1, 1), (1, 1))
+    u = lambda d: d + 126
+    out = {}
+    # grayscale, L = 127, ~0.5 MP (130 KB of zero bytes)
+    out["gray_127"] = SlowSync(_zero_stream(1024, 512, ((1, 1),), (1,)), [127], 127, 0, 120)
+    # 4:2:0, Cr's DC code one bit longer: MCU of 4 * 127 + 127 + 128 = 763 bits, ~1 MP
+    l420 = 6 * 126 + 4 + 1 + 2
+    out["s420_763"] = SlowSync(_zero_stream(1024, 1024, S420, (1, 1, 2)), [u(1), u(1), u(2)], l420, 0, 700)
+    # restart segments longer than the distance (4 segments) and much shorter (48 MCUs, ~36 kbit each): there the
+    # restart markers end the flows. These two and the next file carry marks every 1000th MCU (_zero_stream): misplaced
+    # data units show in their planes, and the marks' one bits leave flows of several hundred subsequences
+    mk = dict(watermark=1000)
+    out["s420_763_dri1024"] = SlowSync(_zero_stream(1024, 1024, S420, (1, 1, 2), restart_interval=1024, **mk), [u(1), u(1), u(2)], l420, 1024, 300)
+    out["s420_763_dri48"] = SlowSync(_zero_stream(1024, 1024, S420, (1, 1, 2), restart_interval=48, **mk), [u(1), u(1), u(2)], l420, 48, 60)
+    out["s420_763_mark1000"] = SlowSync(_zero_stream(1024, 1024, S420, (1, 1, 2), **mk), [u(1), u(1), u(2)], l420, 0, 300)
+    # 4 components, 8 data units per MCU (2x2, 2x1, 1x1, 1x1): 8 * 126 + 4 + 2 + 1 + 2 = 1017 bits, no restart markers;
+    # 2 304 MCUs, no marks: the scan is over 1 100 subsequences long even at 256 bytes, so at every size the distance
+    # exceeds 960 subsequences (the size kTailPartSubseq would give a part if the scan had restart markers) and the
+    # scan is one tail part and, at 32 to 128 bytes, more than one multi-hypothesis block
+    l4 = 8 * 126 + 4 * 1 + 2 * 1 + 1 + 2
+    out["four_1017"] = SlowSync(_zero_stream(768, 768, ((2, 2), (2, 1), (1, 1), (1, 1)), (1, 1, 1, 2)), [u(1), u(1), u(1), u(2)], l4, 0, 970)
+    # three scans of one component each; the last (4x the samples of each other, L = 127) is the slow one, the others
+    # (L = 128) resynchronise at once
+    out["ni_last_127"] = SlowSync(_zero_stream(1024, 512, ((1, 1), (1, 1), (2, 2)), (2, 2, 1), interleaved=False), [u(2), u(2), u(1)], None, 0, 120)
+    return out

@@ -574,3 +574,133 @@ size_t js_encode_blocks(const int16_t* coef, int blocks_x, int blocks_y, const u
 {
     return js_encode_blocks_opt(coef, blocks_x, blocks_y, q, restart_interval, 0, out, cap);
 }
+
+/* A baseline JPEG of 1..4 components made of GIVEN quantised blocks with GIVEN Huffman tables: any sampling factors,
+ * one interleaved scan or one scan per component, any restart interval. Lets a test choose the code lengths, and with
+ * them the bit length of every data unit (tests/cases.py, slow_sync).
+ *   coef[c]  int16 [bh[c]][bw[c]][64], natural order, DC absolute; block (by, bx) of component c is the block at block
+ *            row by, column bx of its plane (rounded up to whole MCUs of an interleaved scan);
+ *   tabs     8 tables of 16 + 256 bytes, BITS then HUFFVAL: DC tables 0..3, then AC tables 0..3;
+ *   q        4 quantisation tables of 64 entries, natural order.
+ * Returns 0 on bad parameters, a symbol without a code, or a full buffer. */
+typedef struct {
+    int width, height, ncomp;
+    int hs[4], vs[4];
+    int bw[4], bh[4];
+    int dc_tab[4], ac_tab[4], q_tab[4];
+    int interleaved, restart_interval;
+} js_custom;
+
+size_t js_encode_custom(const js_custom* p, const int16_t* const* coef, const uint8_t* tabs, const uint8_t* q, uint8_t* out, size_t cap)
+{
+    bitw w = {out, 0, cap, 0, 0, 0};
+    htab t[8];
+    int hmax = 1, vmax = 1, nc = p->ncomp;
+    if (nc < 1 || nc > 4 || p->width < 1 || p->height < 1 || p->width > 65535 || p->height > 65535) return 0;
+    for (int c = 0; c < nc; ++c) {
+        if (p->hs[c] < 1 || p->hs[c] > 4 || p->vs[c] < 1 || p->vs[c] > 4) return 0;
+        if (p->dc_tab[c] < 0 || p->dc_tab[c] > 3 || p->ac_tab[c] < 0 || p->ac_tab[c] > 3 || p->q_tab[c] < 0 || p->q_tab[c] > 3) return 0;
+        if (p->hs[c] > hmax) hmax = p->hs[c];
+        if (p->vs[c] > vmax) vmax = p->vs[c];
+    }
+    for (int k = 0; k < 8; ++k) {
+        int n = 0;
+        memset(&t[k], 0, sizeof(t[k]));
+        memcpy(t[k].bits, tabs + k * 272, 16);
+        for (int l = 0; l < 16; ++l) n += t[k].bits[l];
+        if (n > 256) return 0;
+        memcpy(t[k].vals, tabs + k * 272 + 16, (size_t)n);
+        htab_finish(&t[k]);
+    }
+    const int mcus_x = ceil_div(p->width, 8 * hmax), mcus_y = ceil_div(p->height, 8 * vmax);
+    const int il_all = p->interleaved && nc > 1;
+    for (int c = 0; c < nc; ++c) {
+        const int need_w = il_all ? mcus_x * p->hs[c] : ceil_div(ceil_div(p->width * p->hs[c], hmax), 8);
+        const int need_h = il_all ? mcus_y * p->vs[c] : ceil_div(ceil_div(p->height * p->vs[c], vmax), 8);
+        if (p->bw[c] < need_w || p->bh[c] < need_h) return 0;
+    }
+
+    put_marker(&w, 0xD8);
+    put_marker(&w, 0xDB);
+    put_u16(&w, 2 + 4 * 65);
+    for (int k = 0; k < 4; ++k) {
+        put_byte_raw(&w, k);
+        for (int i = 0; i < 64; ++i) put_byte_raw(&w, q[k * 64 + kZigzag[i]]);
+    }
+    put_marker(&w, 0xC0);
+    put_u16(&w, 8 + 3 * nc);
+    put_byte_raw(&w, 8);
+    put_u16(&w, p->height);
+    put_u16(&w, p->width);
+    put_byte_raw(&w, nc);
+    for (int c = 0; c < nc; ++c) {
+        put_byte_raw(&w, c + 1);
+        put_byte_raw(&w, p->hs[c] << 4 | p->vs[c]);
+        put_byte_raw(&w, p->q_tab[c]);
+    }
+    if (p->restart_interval) {
+        put_marker(&w, 0xDD);
+        put_u16(&w, 4);
+        put_u16(&w, p->restart_interval);
+    }
+    const int nscans = il_all || nc == 1 ? 1 : nc;
+    for (int sidx = 0; sidx < nscans; ++sidx) {
+        const int c0 = nscans == 1 ? 0 : sidx, c1 = nscans == 1 ? nc : sidx + 1, il = c1 - c0 > 1;
+        int used[8] = {0};
+        for (int c = c0; c < c1; ++c) used[p->dc_tab[c]] = used[4 + p->ac_tab[c]] = 1;
+        for (int k = 0; k < 8; ++k) {
+            if (!used[k]) continue;
+            put_marker(&w, 0xC4);
+            put_u16(&w, 2 + 1 + 16 + t[k].count);
+            put_byte_raw(&w, (k >= 4) << 4 | (k & 3));
+            for (int i = 0; i < 16; ++i) put_byte_raw(&w, t[k].bits[i]);
+            for (int i = 0; i < t[k].count; ++i) put_byte_raw(&w, t[k].vals[i]);
+        }
+        put_marker(&w, 0xDA);
+        put_u16(&w, 6 + 2 * (c1 - c0));
+        put_byte_raw(&w, c1 - c0);
+        for (int c = c0; c < c1; ++c) {
+            put_byte_raw(&w, c + 1);
+            put_byte_raw(&w, p->dc_tab[c] << 4 | p->ac_tab[c]);
+        }
+        put_byte_raw(&w, 0);
+        put_byte_raw(&w, 63);
+        put_byte_raw(&w, 0);
+        const int mx = il ? mcus_x : ceil_div(ceil_div(p->width * p->hs[c0], hmax), 8);
+        const int my = il ? mcus_y : ceil_div(ceil_div(p->height * p->vs[c0], vmax), 8);
+        for (int pass = 0; pass < 2; ++pass) { /* 0: every symbol must have a code; 1: write */
+            long fdc[4][256], fac[4][256];
+            int pred[4] = {0, 0, 0, 0}, rst = 0, count = 0;
+            memset(fdc, 0, sizeof(fdc));
+            memset(fac, 0, sizeof(fac));
+            for (int m = 0; m < mx * my; ++m) {
+                if (p->restart_interval && count == p->restart_interval) {
+                    if (pass) {
+                        flush_bits(&w);
+                        put_marker(&w, 0xD0 + (rst++ & 7));
+                    }
+                    memset(pred, 0, sizeof(pred));
+                    count = 0;
+                }
+                ++count;
+                const int mcx = m % mx, mcy = m / mx;
+                for (int c = c0; c < c1; ++c) {
+                    const int h = il ? p->hs[c] : 1, v = il ? p->vs[c] : 1;
+                    for (int dy = 0; dy < v; ++dy)
+                        for (int dx = 0; dx < h; ++dx) {
+                            const int16_t* b = coef[c] + ((size_t)(mcy * v + dy) * p->bw[c] + (size_t)(mcx * h + dx)) * 64;
+                            if (pass) code_block(&w, b, &pred[c], &t[p->dc_tab[c]], &t[4 + p->ac_tab[c]], NULL, NULL);
+                            else code_block(NULL, b, &pred[c], NULL, NULL, fdc[c], fac[c]);
+                        }
+                }
+            }
+            if (!pass)
+                for (int c = c0; c < c1; ++c)
+                    for (int s = 0; s < 256; ++s)
+                        if ((fdc[c][s] && !t[p->dc_tab[c]].size[s]) || (fac[c][s] && !t[4 + p->ac_tab[c]].size[s])) return 0;
+        }
+        flush_bits(&w);
+    }
+    put_marker(&w, 0xD9);
+    return w.overflow ? 0 : w.n;
+}

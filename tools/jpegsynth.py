@@ -14,6 +14,13 @@ class _Params(C.Structure):
                 ("optimize", C.c_int), ("noise", C.c_int), ("fill_bytes", C.c_int), ("seed", C.c_uint64), ("qmax", C.c_int)]
 
 
+class _Custom(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("ncomp", C.c_int),
+                ("hs", C.c_int * 4), ("vs", C.c_int * 4), ("bw", C.c_int * 4), ("bh", C.c_int * 4),
+                ("dc_tab", C.c_int * 4), ("ac_tab", C.c_int * 4), ("q_tab", C.c_int * 4),
+                ("interleaved", C.c_int), ("restart_interval", C.c_int)]
+
+
 def build(force=False):
     src = os.path.join(_HERE, "jpegsynth.c")
     if force or not os.path.exists(_LIB) or os.path.getmtime(_LIB) < os.path.getmtime(src):
@@ -33,6 +40,8 @@ def _load():
         _lib.js_encode.argtypes = [C.POINTER(_Params), C.c_void_p, C.c_size_t]
         _lib.js_encode_blocks_opt.restype = C.c_size_t
         _lib.js_encode_blocks_opt.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+        _lib.js_encode_custom.restype = C.c_size_t
+        _lib.js_encode_custom.argtypes = [C.POINTER(_Custom), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     return _lib
 
 
@@ -52,6 +61,50 @@ def encode_blocks(coef, blocks_x, q, restart_interval=0, optimize=False) -> byte
     if m == 0:
         raise RuntimeError("jpegsynth: encode_blocks failed")
     return buf.raw[:m]
+
+
+def encode_custom(width, height, sampling, blocks, dc_tables, ac_tables, tables=None, qtables=None, interleaved=True,
+                  restart_interval=0) -> bytes:
+    """A baseline JPEG of the given quantised blocks coded with the given Huffman tables.
+
+    sampling: one (h, v) pair per component (1..4); blocks: per component int16 [blocks_y, blocks_x, 64], natural order,
+    DC absolute, at least the component's blocks (whole MCUs of an interleaved scan); dc_tables / ac_tables: up to four
+    (BITS, HUFFVAL) pairs each, BITS 16 counts of codes per length; tables: (dc id, ac id) per component, default the
+    component index; qtables: up to four uint8 [64] natural order; component c uses qtables[c] if there is one, else
+    table 0 (all ones when qtables is None).
+    interleaved=False: one scan per component. Raises if a symbol the blocks need has no code."""
+    import numpy as np
+
+    nc = len(sampling)
+    assert 1 <= nc <= 4 and len(blocks) == nc
+    p = _Custom()
+    p.width, p.height, p.ncomp = width, height, nc
+    p.interleaved, p.restart_interval = int(interleaved), restart_interval
+    tables = tables or [(c, c) for c in range(nc)]
+    keep = []
+    ptrs = (C.c_void_p * 4)()
+    for c, (h, v) in enumerate(sampling):
+        b = np.ascontiguousarray(blocks[c], dtype=np.int16)
+        assert b.ndim == 3 and b.shape[2] == 64
+        keep.append(b)
+        ptrs[c] = b.ctypes.data
+        p.hs[c], p.vs[c], p.bh[c], p.bw[c] = h, v, b.shape[0], b.shape[1]
+        p.dc_tab[c], p.ac_tab[c] = tables[c]
+        p.q_tab[c] = c if qtables is not None and len(qtables) > c else 0
+    tabs = np.zeros((8, 272), np.uint8)
+    for k, (bits, vals) in enumerate(list(dc_tables)[:4]):
+        tabs[k, :16], tabs[k, 16:16 + len(vals)] = bits, vals
+    for k, (bits, vals) in enumerate(list(ac_tables)[:4]):
+        tabs[4 + k, :16], tabs[4 + k, 16:16 + len(vals)] = bits, vals
+    q = np.ones((4, 64), np.uint8)
+    for k, t in enumerate(qtables or []):
+        q[k] = t
+    cap = 4096 + sum(b.size for b in keep) * 4
+    buf = C.create_string_buffer(cap)
+    n = _load().js_encode_custom(C.byref(p), ptrs, tabs.ctypes.data, q.ctypes.data, buf, cap)
+    if n == 0:
+        raise RuntimeError("jpegsynth: encode_custom failed (bad parameters, a symbol without a code, or a full buffer)")
+    return buf.raw[:n]
 
 
 def encode(width, height, sampling=((2, 2), (1, 1), (1, 1)), interleaved=True, restart_interval=0,
