@@ -184,3 +184,97 @@ def slow_sync():
     # (L = 128) resynchronise at once
     out["ni_last_127"] = SlowSync(_zero_stream(1024, 512, ((1, 1), (1, 1), (2, 2)), (2, 2, 1), interleaved=False), [u(2), u(2), u(1)], None, 0, 120)
     return out
+
+
+# Sampling layouts of tests/cases.sampling_sweep(): name -> (h, v) per component. Every luma factor with h v <= 8 over
+# 1x1 chroma, then chroma factors above 1, a chroma plane larger than luma (luma itself upsampled), Cb and Cr with
+# different factors, and 2-D ratios. All have integral ratios h_max / h_c, v_max / v_c.
+SWEEP_LAYOUTS = {"y%dx%d" % (h, v): ((h, v), (1, 1), (1, 1)) for h in range(1, 5) for v in range(1, 5) if h * v <= 8}
+SWEEP_LAYOUTS.update({
+    "y2x2_c1x2": ((2, 2), (1, 2), (1, 2)),
+    "y2x2_c2x1": ((2, 2), (2, 1), (2, 1)),
+    "y4x1_c2x1": ((4, 1), (2, 1), (2, 1)),
+    "y1x4_c1x2": ((1, 4), (1, 2), (1, 2)),
+    "y1x1_cb2x2": ((1, 1), (2, 2), (1, 1)),
+    "y2x2_cr2x1": ((2, 2), (1, 1), (2, 1)),
+    "y1x1_c2x1": ((1, 1), (2, 1), (2, 1)),
+    "y2x1_cb1x2": ((2, 1), (1, 2), (1, 1)),
+    "y1x2_cb2x1": ((1, 2), (2, 1), (1, 1)),
+    "y2x2_cb2x2": ((2, 2), (2, 2), (1, 1)),  # 9 units: every MCU size from 3 to 10
+})
+# layouts that also get a non-interleaved and a restart-marker variant: the 10-unit MCUs, the ratios of 3 and the
+# layouts in which luma is upsampled
+SWEEP_VARIANTS = ("y4x2", "y2x4", "y3x1", "y1x3", "y3x2", "y2x3", "y1x1_cb2x2", "y1x1_c2x1", "y2x1_cb1x2", "y1x2_cb2x1")
+# layouts with vmax 3 or 4 that also get a restart interval of one MCU row (what a segment shard cuts into bands)
+SWEEP_ROW_DRI = ("y1x3", "y2x3", "y1x4", "y2x4", "y1x4_c1x2")
+# layouts that also get a tiny size at which a chroma plane (or luma, where it is upsampled) is at most 2 samples wide
+SWEEP_TINY = ("y2x1", "y2x2", "y4x1_c2x1", "y2x2_c1x2", "y1x1_cb2x2", "y1x1_c2x1", "y2x1_cb1x2", "y1x2_cb2x1", "y4x2")
+
+
+def sweep_size(hmax, vmax, kind):
+    """Width and height of a sweep file: the last MCU column and row are partial and (for a factor above 1) hold wholly
+    invisible blocks. "a": one pixel into the last MCU, so h_max - 1 blocks of it are invisible; "b": the partial block
+    is the MCU's last but one (5 pixels of it visible, h_max >= 3), its first (h_max = 2) or its only one."""
+    def edge(f, mcus, kind):
+        return 8 * f * mcus + (1 if kind == "a" else 8 * (f - 1) - 3 if f > 1 else 5)
+    if kind == "a":
+        return edge(hmax, max(2, 72 // (8 * hmax)), "a"), edge(vmax, max(2, 48 // (8 * vmax)), "a")
+    return edge(hmax, max(1, 40 // (8 * hmax)), "b"), edge(vmax, max(1, 32 // (8 * vmax)), "b")
+
+
+def sweep_restart_interval(mcus_x):
+    """The smallest interval >= 2 that does not divide the MCU row: segments start in the middle of MCU rows."""
+    ri = 2
+    while mcus_x % ri == 0:
+        ri += 1
+    return ri
+
+
+def sweep_is_planes_only(name):
+    """Files of the sweep that the RGB calls refuse (a non-integral ratio, 2 or 4 components): checked as planes only."""
+    return name.startswith("po_")
+
+
+def sweep_is_refused(name):
+    """Files of the sweep that parse_header refuses (JPEGGPU_INVALID_JPEG)."""
+    return name.startswith("refuse_")
+
+
+def sampling_sweep():
+    """name -> bytes: every legal sampling layout of baseline JPEG that the matrix lacks (T.81 A.1.1: factors 1..4, at
+    most 10 data units per MCU), each at two sizes (sweep_size), some at a tiny size, and, for SWEEP_VARIANTS, as
+    one scan per component ("_ni") and with restart markers that cut MCU rows ("_dri"); row-interval restart files
+    ("_rowdri") for SWEEP_ROW_DRI. Names with "po_" are files whose planes are checked but that have no RGB (a
+    non-integral ratio, 2 or 4 components); "refuse_" an 11-unit MCU parse_header must refuse. Kept apart from matrix()
+    so that the matrix loops do not grow; every file decodes on the oracle in a few milliseconds."""
+    e = jpegsynth.encode
+    out = {}
+    seed = 300
+    for name, samp in SWEEP_LAYOUTS.items():
+        hmax, vmax = max(h for h, _ in samp), max(v for _, v in samp)
+        for kind in ("a", "b"):
+            w, h = sweep_size(hmax, vmax, kind)
+            seed += 1
+            out["%s_%s" % (name, kind)] = e(w, h, samp, seed=seed)
+        if name in SWEEP_TINY:
+            seed += 1
+            out[name + "_tiny"] = e(3, 5, samp, seed=seed)
+        w, h = sweep_size(hmax, vmax, "a")
+        mcus_x = -(-w // (8 * hmax))
+        if name in SWEEP_VARIANTS:
+            seed += 1
+            out[name + "_ni"] = e(w, h, samp, interleaved=False, seed=seed)
+            seed += 1
+            out[name + "_dri"] = e(w, h, samp, restart_interval=sweep_restart_interval(mcus_x), seed=seed)
+        if name in SWEEP_ROW_DRI:
+            seed += 1
+            out[name + "_rowdri"] = e(w, h, samp, restart_interval=mcus_x, seed=seed)
+    # planes only: a non-integral ratio (3 over 2), a second component larger than the first (10 units per MCU), four
+    # components in 8 units per MCU
+    out["po_y3x1_cb2x1"] = e(77, 45, ((3, 1), (2, 1), (1, 1)), seed=401)
+    out["po_y3x1_cb2x1_dri"] = e(77, 45, ((3, 1), (2, 1), (1, 1)), restart_interval=2, seed=402)
+    out["po_two_1x1_3x3"] = e(61, 53, ((1, 1), (3, 3)), seed=403)
+    out["po_four_8du"] = e(69, 37, ((2, 2), (2, 1), (1, 1), (1, 1)), seed=404)
+    # 9 + 1 + 1 = 11 data units per MCU: not a legal interleaved scan (T.81 B.2.3)
+    out["refuse_11du"] = e(48, 48, ((3, 3), (1, 1), (1, 1)), seed=405)
+    return out
