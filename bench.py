@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- images/s of the baseline-JPEG decode hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 One "step" = `--rounds` passes of the hot path (destuff -> Huffman sync / write -> IDCT, through
 jpeggpu_ext_decode_batch by default or the drop-in jpeggpu_decoder_decode with --mode streams) over the rank's
@@ -10,14 +10,17 @@ rank as in configs[2], no data-path collective in the timed region, weak scaling
 2048 images, so the timed region is about 1.5 s.
 
 `value` is the rate with inputs (entropy-coded bytes + table blobs) resident in HBM when the timed region
-starts; `value_full_path` is the rate of the whole boundary protocol from pinned host memory (parse_header +
-transfer + decode), which the boundary hands over -- never `value`. After the timed loop the planes of every
-distinct image are compared with the CPU oracle (`verified`). Rank 0 prints ONE JSON line; DESIGN.md section 4
-defines every field. `ms_per_step` is the wall time of one timed step.
+starts. Rank 0 prints ONE JSON line; DESIGN.md section 4 defines every field. `ms_per_step` is the wall time of one
+timed step. A plain run does only what these need: set-up, the warm-up and timed steps, --dump-outputs, the line.
 
 `--dump-outputs DIR` writes what the timed path decoded in its last step -- the planes of every image of the batch, a
 fixed seeded sample of each -- to DIR/plane<c>.npy (float32, at most 64 MB; `dump_outputs`). The inputs are seeded, so
 two builds run with the same arguments can be compared array for array.
+
+`--full` adds everything else the line can carry (every leg runs after the timed steps but the CPU baseline, first):
+`value_full_path`, the rate of the whole boundary protocol from pinned host memory (parse_header + transfer +
+decode), which the boundary hands over -- never `value`; `verified`, the planes of every distinct image compared
+with the CPU oracle after the timed loop; and the legs below.
 
 `roofline` is the destuff+Huffman PASS the north star names: SURVEY.md 8(d)'s algorithmic bytes of that pass
 (B_dh = stuffed scan bytes + 128 B per data unit) x the images of one launch / the SUM of the average durations of
@@ -25,8 +28,8 @@ the pass's kernels, measured in this run from serialized launches with HIP event
 HBM peak. `kernels` lists every kernel with the bytes it really has to move. `cpu_baseline` is libjpeg-turbo on this
 box's host cores, timed BEFORE this process touches the GPU (its worker processes are spawned, not forked).
 
-For N > 1 the driver launches this file with torch.distributed.run, one rank per GPU (RCCL); the line then also
-carries `gather`: BASELINE.json configs[2] itself -- 64 images sharded over the ranks, decoded, and collected
+For N > 1 the driver launches this file with torch.distributed.run, one rank per GPU (RCCL); with --full the line then
+also carries `gather`: BASELINE.json configs[2] itself -- 64 images sharded over the ranks, decoded, and collected
 on rank 0, the gather of round k on a side stream while round k + 1 decodes.
 """
 import argparse
@@ -49,7 +52,7 @@ PASS_STAGES = ("front", "destuff", "sync_intra", "sync_inter", "tails", "write")
 PHOTO = os.path.join(ROOT, "tests", "golden", "IMG_6510.JPG")
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -96,7 +99,28 @@ def parse_args():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the planes the last step decoded to DIR/plane<c>.npy (float32, a fixed "
                          "seeded sample of every image of the batch, at most 64 MB in all; see dump_outputs)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline figure: CPU baseline, oracle check, roofline, latency, "
+                         "full path, other configurations, batch curve, rank shard, and for N > 1 gather and segment shard; "
+                         "without it the options of those legs have no effect")
+    args = ap.parse_args(argv)
+    if not args.full:
+        lean(args)
+    return args
+
+
+# the options of the legs a plain run skips: 0 skips each of them
+EXTRA_LEGS = ("gather_rounds", "segment_shard_rounds", "latency_iters", "roofline_launches", "other_configs", "photo_steps",
+              "e2e_rounds", "curve_iters", "shard_iters")
+
+
+def lean(args):
+    """A plain run (no --full) does only what `value` and `ms_per_step` need: it sets up, warms up, times the steps,
+    writes --dump-outputs and prints the line. The CPU baseline, the oracle check and every other leg are off, and their
+    fields are absent or null as when each is switched off on its own."""
+    args.no_cpu = args.no_verify = True
+    for k in EXTRA_LEGS:
+        setattr(args, k, 0)
 
 
 def make_images(args, rank, world):
@@ -107,10 +131,23 @@ def make_images(args, rank, world):
         with open(PHOTO, "rb") as f:
             return [f.read()]
     from jpeggpu_amd import shard
-    from tools import jpegsynth
 
     seeds = shard.shard_indices(args.unique * world, rank, world)
-    return [jpegsynth.config(2, seed=s) for s in seeds]
+    # one image takes seconds of a core to encode: the rank's share of the host's cores encodes them side by side, in
+    # spawned processes (nothing here has touched the GPU yet, and the children never do)
+    procs = min(len(seeds), max(1, usable_cores() // world))
+    if procs <= 1:
+        return [_synth_cfg2(s) for s in seeds]
+    import multiprocessing as mp
+
+    with mp.get_context("spawn").Pool(procs) as pool:
+        return pool.map(_synth_cfg2, seeds, chunksize=1)
+
+
+def _synth_cfg2(seed):
+    from tools import jpegsynth
+
+    return jpegsynth.config(2, seed=seed)
 
 
 class Slot:

@@ -861,8 +861,8 @@ def test_config3_batch_of_64_twelve_megapixel_images(torch_cuda):
 
 
 def test_bench_multi_rank_control_flow_over_gloo(torch_cuda):
-    """bench.py's own N > 1 path -- sharding by rank, max-over-ranks timing, oracle verification reduced over the
-    ranks, the configs[2] leg with its gather -- as two ranks on this one GPU (JPEGGPU_BENCH_BACKEND=gloo: the
+    """bench.py's own N > 1 path with --full -- sharding by rank, max-over-ranks timing, oracle verification reduced over
+    the ranks, the configs[2] leg with its gather -- as two ranks on this one GPU (JPEGGPU_BENCH_BACKEND=gloo: the
     collectives run on CPU tensors; the driver's multi-GPU runs use RCCL)."""
     import json
     import os
@@ -880,7 +880,7 @@ def test_bench_multi_rank_control_flow_over_gloo(torch_cuda):
     env = dict(os.environ, JPEGGPU_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_PORT=str(port))
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
            "--batch", "8", "--rounds", "1", "--unique", "2", "--latency-iters", "0", "--other-configs", "0", "--no-cpu", "--e2e-rounds", "0",
            "--roofline-launches", "2", "--gather-rounds", "2", "--segment-shard-rounds", "2"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
@@ -899,6 +899,37 @@ def test_bench_multi_rank_control_flow_over_gloo(torch_cuda):
     assert d["roofline"]["frac"] > 0
     sh = d["segment_shard"]  # one 39 MP image over the two ranks by restart segments
     assert sh["assembled_equals_whole_decode"] is True and len(sh["rows_of_plane_0_per_rank"]) == 2 and sh["value"] > 0
+
+
+def test_bench_plain_run_times_and_dumps_only(torch_cuda, tmp_path):
+    """A plain `python bench.py --gpus 1 ...` (no --full): the headline fields and the dumped planes of the last timed
+    step, and none of the legs --full adds."""
+    import json
+    import subprocess
+    import sys
+
+    from tests.conftest import ROOT
+
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--batch", "8", "--rounds", "1", "--unique", "2", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["value"] > 0 and d["unit"] == "images/s" and d["higher_is_better"] is True and d["ms_per_step"] > 0
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["config"]["images_per_step"] == 8
+    assert abs(d["value"] - 8 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert d["verified"] is None and d["roofline"] is None and d["kernels"] == {}
+    for k in ("cpu_baseline", "latency_ms", "latency_ms_device_scan", "pcie_inclusive", "value_full_path", "other_configs",
+              "batch_curve", "config3_rank_shard", "gather", "segment_shard"):
+        assert k not in d, k
+    arrays = d["dumped_outputs"]["arrays"]
+    assert sorted(arrays) == ["plane0", "plane1", "plane2"]
+    for name, shape in arrays.items():
+        a = np.load(out / (name + ".npy"))
+        assert list(a.shape) == shape and shape[0] == 8 and a.dtype == np.float32
+    # the planes are zeroed before the warm-up: what was dumped was decoded by the timed steps
+    assert all(np.load(out / (name + ".npy")).max() > 0 for name in arrays)
 
 
 def test_scan_larger_than_16_mib(torch_cuda):
