@@ -172,6 +172,44 @@ enum jpeggpu_status jpeggpu_ext_get_device_status(
  *     (d_tmp sizing) do not depend on the scale. */
 enum jpeggpu_status jpeggpu_ext_set_scale(jpeggpu_decoder_t decoder, int scale_denom);
 
+/* How a scaled decode sizes its components. JPEGGPU_EXT_SCALE_UNIFORM (the default) is the behaviour described above: every
+ * component at 1/d. JPEGGPU_EXT_SCALE_LIBJPEG is libjpeg-turbo's own (jdmaster.c), which is what Pillow's
+ * Image.draft("RGB", size) + convert("RGB") returns: each component has its own IDCT output size S_c, so that the IDCT
+ * does as much of the chroma upsampling as it can. With S_min = 8 / d,
+ *     S_c = S_min;  while (S_c < 8 && (h_max S_min) % (h_c S_c 2) == 0 && (v_max S_min) % (v_c S_c 2) == 0) S_c *= 2;
+ * 4:2:0 at 1/2 is luma 4x4 and chroma 8x8 (at 1/4: 2x2 and 4x4, at 1/8: 1x1 and 2x2): chroma planes of the luma's size.
+ * 4:4:4, 4:2:2 and 4:4:0 keep one size for all components. Any other value: JPEGGPU_INVALID_ARGUMENT. Takes effect at the
+ * next jpeggpu_decoder_parse_header, like the scale; at scale 1 it changes nothing. At a scale below 1, in this mode:
+ *   - sizes_x[c] = ceil(W h_c S_c / (8 h_max)), sizes_y likewise; subsampling.x[c] / y[c] report the EFFECTIVE factors
+ *     h_c S_c / S_min and v_c S_c / S_min -- the subsampling the planes really have -- so that every consumer that forms
+ *     max / factor (jpeggpu_ext_planes_to_rgbi_fancy, jpeggpu_ext_crop_to_rgbi_fancy, jpeggpu_ext_resize_to_rgb,
+ *     jpeggpu_ext_upsample_planes) sees the ratio that is left.
+ *   - blocks of size 8 are transformed with jpeg_idct_islow whatever jpeggpu_ext_set_idct says, the smaller ones with
+ *     jidctred.c's transforms as in the uniform mode.
+ *   - RGB equal to libjpeg's: jpeggpu_ext_planes_to_rgbi_fancy / jpeggpu_ext_crop_to_rgbi_fancy on the reported img_info
+ *     at 1/2 and 1/4; at 1/8 libjpeg replicates what subsampling is left instead (jdsample.c: no fancy upsampling when
+ *     min_DCT_scaled_size is 1): jpeggpu_ext_planes_to_rgbi_replicate / jpeggpu_ext_crop_to_rgbi_replicate below.
+ *     jpeggpu_ext_get_scale_info says which applies.
+ *   - jpeggpu_ext_set_crop: the rectangle is in pixels of the image at 1/d as before; window origins, sizes, halos and
+ *     the MCU window are computed with each component's own block size and effective factors.
+ *   - jpeggpu_ext_set_segment_shard works: a band is whole MCU rows, v_c S_c rows of component c each
+ *     (jpeggpu_ext_get_shard_rows). The device marker scan and jpeggpu_ext_decode_batch (any mix of modes, scales, crops and
+ *     IDCT methods) work as in the uniform mode, and jpeggpu_decoder_get_buffer_size does not depend on the mode.
+ * The environment's JPEGGPU_SCALE_MODE=libjpeg, read at jpeggpu_decoder_startup, selects it for a caller of the drop-in
+ * API alone. */
+enum jpeggpu_ext_scale_mode { JPEGGPU_EXT_SCALE_UNIFORM = 0, JPEGGPU_EXT_SCALE_LIBJPEG = 1 };
+enum jpeggpu_status jpeggpu_ext_set_scale_mode(jpeggpu_decoder_t decoder, enum jpeggpu_ext_scale_mode mode);
+/* Of the parsed image: the scale, the mode, each component's block size S_c (8 / d for all in the uniform mode), and
+ * whether libjpeg upsamples what subsampling is left with its fancy upsamplers (1) or replicates (0: the LIBJPEG mode at
+ * 1/8). JPEGGPU_INVALID_ARGUMENT before parse_header. */
+struct jpeggpu_ext_scale_info {
+    int scale_denom;
+    int mode; /* enum jpeggpu_ext_scale_mode */
+    int block_size[JPEGGPU_MAX_COMP];
+    int fancy_upsampling;
+};
+enum jpeggpu_status jpeggpu_ext_get_scale_info(jpeggpu_decoder_t decoder, struct jpeggpu_ext_scale_info* info);
+
 /* The full-size inverse DCT. JPEGGPU_EXT_IDCT_REFERENCE (the default) is the reference's fixed-point transform;
  * JPEGGPU_EXT_IDCT_ISLOW is libjpeg-turbo's jpeg_idct_islow (jidctint.c), the IDCT of Pillow, torchvision and OpenCV:
  * dequantisation in full int, CONST_BITS = 13, PASS1_BITS = 2, a 32-bit workspace between the passes and its
@@ -365,6 +403,27 @@ enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_fancy(
     int dst_pitch,
     jpeggpu_stream_t stream);
 
+/* jpeggpu_ext_planes_to_rgbi_fancy and jpeggpu_ext_crop_to_rgbi_fancy with every component REPLICATED (jdsample.c's
+ * int_upsample and its h2v1 / h2v2 special cases: sample x / hr, y / vr) and the same integer colour conversion: libjpeg's
+ * output where fancy upsampling is off, i.e. for planes of a JPEGGPU_EXT_SCALE_LIBJPEG decode at 1/8 that have subsampling
+ * left (4:2:2, 4:4:0, 4:1:1 ...; jpeggpu_ext_scale_info.fancy_upsampling == 0). Same contracts and return codes. This is
+ * not jpeggpu_ext_planes_to_rgbi, whose colour arithmetic is the reference helper's. */
+enum jpeggpu_status jpeggpu_ext_planes_to_rgbi_replicate(
+    const struct jpeggpu_img_info* info,
+    const struct jpeggpu_img* src,
+    uint8_t* dst,
+    int dst_pitch,
+    int width,
+    int height,
+    jpeggpu_stream_t stream);
+enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_replicate(
+    const struct jpeggpu_img_info* info,
+    const struct jpeggpu_ext_crop_info* crop,
+    const struct jpeggpu_img* src,
+    uint8_t* dst,
+    int dst_pitch,
+    jpeggpu_stream_t stream);
+
 /* Batched resize to one size (a training pipeline's Resize + CenterCrop or RandomResizedCrop): each item's RGB -- what
  * jpeggpu_ext_crop_to_rgbi_fancy makes of a cropped decode's windows, or jpeggpu_ext_planes_to_rgbi_fancy of whole
  * planes -- resampled to out_w x out_h with the arithmetic of Pillow's Image.resize((out_w, out_h), BILINEAR | BICUBIC),
@@ -386,6 +445,9 @@ enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_fancy(
  *     soon as the call returns: their descriptors and the weight tables are copied from internal page-locked staging
  *     (a ring of four: the fifth call in a row waits until the copy of the first has executed). `stream` must belong to
  *     the current device.
+ *   - Items of a JPEGGPU_EXT_SCALE_LIBJPEG decode are described by their img_info like any other. The item has no room for
+ *     "replicate": an item of that mode at 1/8 with subsampling left gets fancy upsampling here, which is not libjpeg's
+ *     output (jpeggpu_ext_get_scale_info: fancy_upsampling == 0); decode such an image at 1/4 instead.
  *   - JPEGGPU_NOT_SUPPORTED: a filter other than the two, an item of 2 or 4 components or with non-integral sampling
  *     ratios. JPEGGPU_INVALID_ARGUMENT: NULL pointers, n, out_w or out_h <= 0 (or n > 65535), an unknown layout, an item
  *     whose windows do not hold its rectangle's samples (the checks of jpeggpu_ext_crop_to_rgbi_fancy), scratch_size too

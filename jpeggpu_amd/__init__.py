@@ -10,11 +10,13 @@ from .api import (  # noqa: F401
     Decoder,
     ImgInfo,
     JpegGpuError,
+    ScaleInfo,
     Status,
     crop_to_rgb,
     decode_to_planes,
     decode_resized,
     decode_to_rgb,
+    draft_scale,
     fused_tail_timeouts,
     lib,
     parse_headers,

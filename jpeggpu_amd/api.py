@@ -17,6 +17,7 @@ STAGES = ("front", "destuff", "sync_intra", "sync_inter", "tails", "write", "idc
 IDCT_METHODS = {"reference": 0, "islow": 1}  # enum jpeggpu_ext_idct
 FILTERS = {"bilinear": 0, "bicubic": 1}  # enum jpeggpu_ext_filter
 LAYOUTS = {"NHWC": 0, "NCHW": 1}  # enum jpeggpu_ext_output_layout
+SCALE_MODES = {"uniform": 0, "libjpeg": 1}  # enum jpeggpu_ext_scale_mode
 
 
 class Status(enum.IntEnum):
@@ -48,6 +49,12 @@ class CropInfo(C.Structure):
     _fields_ = [("x", C.c_int), ("y", C.c_int), ("width", C.c_int), ("height", C.c_int),
                 ("origin_x", C.c_int * MAX_COMP), ("origin_y", C.c_int * MAX_COMP),
                 ("full_x", C.c_int * MAX_COMP), ("full_y", C.c_int * MAX_COMP)]
+
+
+class ScaleInfo(C.Structure):
+    """struct jpeggpu_ext_scale_info: the scale and mode of the parsed image, each component's block size, and whether
+    libjpeg upsamples what subsampling is left with its fancy upsamplers (0: it replicates -- the libjpeg mode at 1/8)."""
+    _fields_ = [("scale_denom", C.c_int), ("mode", C.c_int), ("block_size", C.c_int * MAX_COMP), ("fancy_upsampling", C.c_int)]
 
 
 class ResizeItem(C.Structure):
@@ -149,16 +156,20 @@ def lib():
     L.jpeggpu_ext_set_device_scan.argtypes = [dec, C.c_int]
     L.jpeggpu_ext_set_scale.argtypes = [dec, C.c_int]
     L.jpeggpu_ext_set_idct.argtypes = [dec, C.c_int]
+    L.jpeggpu_ext_set_scale_mode.argtypes = [dec, C.c_int]
+    L.jpeggpu_ext_get_scale_info.argtypes = [dec, C.POINTER(ScaleInfo)]
     L.jpeggpu_ext_get_device_status.argtypes = [dec, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
     L.jpeggpu_ext_parse_headers.argtypes = [C.POINTER(ParseItem), C.c_int, C.c_int, C.POINTER(C.c_int)]
     L.jpeggpu_ext_planes_to_rgbi.argtypes = [
         C.POINTER(ImgInfo), C.POINTER(Img), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.jpeggpu_ext_planes_to_rgbi_fancy.argtypes = [
         C.POINTER(ImgInfo), C.POINTER(Img), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.jpeggpu_ext_planes_to_rgbi_replicate.argtypes = L.jpeggpu_ext_planes_to_rgbi_fancy.argtypes
     L.jpeggpu_ext_set_crop.argtypes = [dec, C.c_int, C.c_int, C.c_int, C.c_int]
     L.jpeggpu_ext_get_crop.argtypes = [dec, C.POINTER(CropInfo)]
     L.jpeggpu_ext_crop_to_rgbi_fancy.argtypes = [
         C.POINTER(ImgInfo), C.POINTER(CropInfo), C.POINTER(Img), C.c_void_p, C.c_int, C.c_void_p]
+    L.jpeggpu_ext_crop_to_rgbi_replicate.argtypes = L.jpeggpu_ext_crop_to_rgbi_fancy.argtypes
     L.jpeggpu_ext_resize_scratch_size.restype = C.c_size_t
     L.jpeggpu_ext_resize_scratch_size.argtypes = [C.POINTER(ResizeItem), C.c_int, C.c_int, C.c_int, C.c_int]
     L.jpeggpu_ext_resize_to_rgb.argtypes = [
@@ -238,6 +249,19 @@ class Decoder:
         """Decode the next parsed images at 1 / scale_denom (1, 2, 4 or 8): planes of ceil(size / scale_denom), the
         arithmetic of libjpeg-turbo's reduced IDCTs (jpeggpu_ext_set_scale)."""
         _check(lib().jpeggpu_ext_set_scale(self._h, int(scale_denom)), "jpeggpu_ext_set_scale")
+
+    def set_scale_mode(self, mode: str):
+        """How the next parsed images are scaled: "uniform" (the default: every component at 1 / scale) or "libjpeg" --
+        libjpeg-turbo's per-component IDCT sizes, what Pillow's draft() decodes (jpeggpu_ext_set_scale_mode)."""
+        if mode not in SCALE_MODES:
+            raise ValueError("scale mode %r is not one of %s" % (mode, ", ".join(SCALE_MODES)))
+        _check(lib().jpeggpu_ext_set_scale_mode(self._h, SCALE_MODES[mode]), "jpeggpu_ext_set_scale_mode")
+
+    def scale_info(self) -> ScaleInfo:
+        """jpeggpu_ext_get_scale_info of the last parsed image."""
+        si = ScaleInfo()
+        _check(lib().jpeggpu_ext_get_scale_info(self._h, C.byref(si)), "jpeggpu_ext_get_scale_info")
+        return si
 
     def set_idct(self, method: str):
         """The full-size IDCT of the next parsed images: "reference" (the default) or "islow", libjpeg-turbo's
@@ -387,20 +411,34 @@ def self_test(stream: int = 0) -> None:
     _check(lib().jpeggpu_ext_self_test(stream), "jpeggpu_ext_self_test")
 
 
+def draft_scale(width, height, requested):
+    """The scale Pillow's JpegImageFile.draft(mode, requested) picks for a width x height JPEG: min(width // rw,
+    height // rh) rounded down to 8, 4, 2 or 1 (requested = (rw, rh), each clamped to the image). Pure Python."""
+    rw, rh = requested
+    rw, rh = min(int(rw), width), min(int(rh), height)
+    if rw < 1 or rh < 1:
+        raise ValueError("requested size must be positive")
+    s = min(width // rw, height // rh)
+    return 8 if s >= 8 else 4 if s >= 4 else 2 if s >= 2 else 1
+
+
 def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp=False, device_scan=False, scale=1,
-                     idct="reference", crop=None):
+                     idct="reference", crop=None, scale_mode="uniform"):
     """Convenience wrapper used by tests: full call sequence on torch's current stream, returns the
     planes as torch uint8 tensors on `device` (torch is only the allocator / stream provider). With
     `device_scan` the restart markers are found on the device and a status it reports there is raised.
     `scale`: 1, 2, 4 or 8 -- planes at 1 / scale (Decoder.set_scale). `idct`: "reference" or "islow" (Decoder.set_idct).
     `crop`: (x, y, w, h) -- only the planes' windows for that rectangle are decoded (Decoder.set_crop), and the CropInfo
-    is returned as well: (planes, info, crop_info)."""
+    is returned as well: (planes, info, crop_info). `scale_mode`: "uniform" or "libjpeg" (Decoder.set_scale_mode); the
+    returned info then carries the planes' effective sampling factors."""
     import torch
 
     dec = Decoder(subseq_bytes)
     try:
         if scale != 1:
             dec.set_scale(scale)
+        if scale_mode != "uniform":
+            dec.set_scale_mode(scale_mode)
         if idct != "reference":
             dec.set_idct(idct)
         if device_scan:
@@ -431,10 +469,12 @@ def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp
         dec.cleanup()
 
 
-def planes_to_rgb(planes, info, fancy=True, device=None):
+def planes_to_rgb(planes, info, fancy=True, device=None, replicate=False):
     """Planes of a 1- or 3-component image (as decode_to_planes returns them) -> (H, W, 3) uint8 tensor at the full image
     size, on torch's current stream: jpeggpu_ext_planes_to_rgbi_fancy (libjpeg's fancy upsampling and integer colour
-    conversion) or, with fancy=False, jpeggpu_ext_planes_to_rgbi (the reference's helper)."""
+    conversion) or, with fancy=False, jpeggpu_ext_planes_to_rgbi (the reference's helper). `replicate`:
+    jpeggpu_ext_planes_to_rgbi_replicate -- libjpeg's conversion with replication, its output at 1/8 in the libjpeg scale
+    mode."""
     import torch
 
     n = info.num_components
@@ -448,15 +488,15 @@ def planes_to_rgb(planes, info, fancy=True, device=None):
         src.image[c], src.pitch[c] = planes[c].data_ptr(), planes[c].stride(0)
     out = torch.empty((height, width, 3), dtype=torch.uint8, device=device)
     stream = torch.cuda.current_stream(device).cuda_stream
-    fn = lib().jpeggpu_ext_planes_to_rgbi_fancy if fancy else lib().jpeggpu_ext_planes_to_rgbi
-    _check(fn(C.byref(info), C.byref(src), out.data_ptr(), 3 * width, width, height, stream),
-           "jpeggpu_ext_planes_to_rgbi_fancy" if fancy else "jpeggpu_ext_planes_to_rgbi")
+    name = "jpeggpu_ext_planes_to_rgbi_replicate" if replicate else "jpeggpu_ext_planes_to_rgbi_fancy" if fancy else "jpeggpu_ext_planes_to_rgbi"
+    _check(getattr(lib(), name)(C.byref(info), C.byref(src), out.data_ptr(), 3 * width, width, height, stream), name)
     return out
 
 
-def crop_to_rgb(planes, info, crop_info, device=None):
+def crop_to_rgb(planes, info, crop_info, device=None, replicate=False):
     """The window planes of a cropped decode (decode_to_planes(..., crop=...)) -> (h, w, 3) uint8 tensor of the rectangle,
-    equal to that part of planes_to_rgb's image of the uncropped planes (jpeggpu_ext_crop_to_rgbi_fancy)."""
+    equal to that part of planes_to_rgb's image of the uncropped planes (jpeggpu_ext_crop_to_rgbi_fancy, or with
+    `replicate` jpeggpu_ext_crop_to_rgbi_replicate)."""
     import torch
 
     n = info.num_components
@@ -467,25 +507,35 @@ def crop_to_rgb(planes, info, crop_info, device=None):
     w, h = crop_info.width, crop_info.height
     out = torch.empty((h, w, 3), dtype=torch.uint8, device=device)
     stream = torch.cuda.current_stream(device).cuda_stream
-    _check(lib().jpeggpu_ext_crop_to_rgbi_fancy(C.byref(info), C.byref(crop_info), C.byref(src), out.data_ptr(), 3 * w, stream),
-           "jpeggpu_ext_crop_to_rgbi_fancy")
+    name = "jpeggpu_ext_crop_to_rgbi_replicate" if replicate else "jpeggpu_ext_crop_to_rgbi_fancy"
+    _check(getattr(lib(), name)(C.byref(info), C.byref(crop_info), C.byref(src), out.data_ptr(), 3 * w, stream), name)
     return out
 
 
-def decode_to_rgb(data: bytes, device="cuda:0", device_scan=False, crop=None):
+def _needs_replication(info, scale):
+    """libjpeg replicates instead of fancy upsampling at 1/8 (jdsample.c); it matters where subsampling is left."""
+    n = info.num_components
+    return scale == 8 and (len(set(info.subsampling.x[:n])) > 1 or len(set(info.subsampling.y[:n])) > 1)
+
+
+def decode_to_rgb(data: bytes, device="cuda:0", device_scan=False, crop=None, scale=1):
     """Decode a 1- or 3-component JPEG to an (H, W, 3) uint8 tensor on `device` the way libjpeg-turbo does: the ISLOW
     IDCT at full size, then fancy upsampling and the integer YCbCr -> RGB conversion. Meant to equal
     np.asarray(PIL.Image.open(f).convert("RGB")) (INTEGRATION.md, "Matching Pillow / torchvision"). With `crop` = (x, y,
-    w, h) only that rectangle is decoded: an (h, w, 3) tensor equal to decode_to_rgb(data)[y:y + h, x:x + w]."""
+    w, h) only that rectangle is decoded: an (h, w, 3) tensor equal to decode_to_rgb(data)[y:y + h, x:x + w].
+    `scale` = d in 2, 4, 8: the image at 1/d as libjpeg-turbo scales it (the libjpeg scale mode: per-component IDCT sizes,
+    replication instead of fancy upsampling at 1/8), equal to im.draft("RGB", (W // d, H // d)); im.convert("RGB") in
+    Pillow; `crop` is then in pixels of that image."""
     import torch
 
+    kw = dict(device=device, device_scan=device_scan, idct="islow", scale=scale, scale_mode="libjpeg")
     if crop is not None:
-        planes, info, crop_info = decode_to_planes(data, device=device, device_scan=device_scan, idct="islow", crop=crop)
-        rgb = crop_to_rgb(planes, info, crop_info)
+        planes, info, crop_info = decode_to_planes(data, crop=crop, **kw)
+        rgb = crop_to_rgb(planes, info, crop_info, replicate=_needs_replication(info, scale))
         torch.cuda.synchronize(torch.device(device))
         return rgb
-    planes, info = decode_to_planes(data, device=device, device_scan=device_scan, idct="islow")
-    rgb = planes_to_rgb(planes, info, fancy=True)
+    planes, info = decode_to_planes(data, **kw)
+    rgb = planes_to_rgb(planes, info, fancy=True, replicate=_needs_replication(info, scale))
     torch.cuda.synchronize(torch.device(device))
     return rgb
 
@@ -593,13 +643,17 @@ def resize_to_rgb(planes_list, infos, size, crop_infos=None, filt="bilinear", la
     return out
 
 
-def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", device="cuda:0"):
+def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", device="cuda:0", scales=None):
     """A training pipeline's decode: every JPEG of `datas` decoded with libjpeg-turbo's arithmetic (ISLOW IDCT, fancy
     upsampling), only the rectangle crops[i] = (x, y, w, h) of it (None: the whole image), in ONE jpeggpu_ext_decode_batch
     call, then resized to `size` (int: square; (h, w)) with Pillow's BILINEAR or BICUBIC arithmetic by one
     jpeggpu_ext_resize_to_rgb call. Returns an n x h x w x 3 ("NHWC") or n x 3 x h x w ("NCHW") uint8 tensor equal to
     Pillow's Image.open(f).convert("RGB").crop((x, y, x + w, y + h)).resize((w_out, h_out), filter) of every image
-    (INTEGRATION.md, "RandomResizedCrop equal to torchvision on Pillow")."""
+    ("RandomResizedCrop equal to torchvision on Pillow"). `scales[i]` in 1, 2, 4, 8 (default 1): image i is
+    decoded at that scale the way libjpeg-turbo does (decode_to_rgb's `scale`; draft_scale gives Pillow's choice), crops[i]
+    is in pixels of the image at that scale, and the result equals im.draft("RGB", ...); im.convert("RGB").crop(...)
+    .resize(...). A ValueError for an image that libjpeg would upsample by replication (1/8 with subsampling left, e.g.
+    4:2:2): the batched resize does not reproduce that; use scale 4 for it."""
     import torch
 
     dev = torch.device(device)
@@ -607,18 +661,28 @@ def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", devi
     crops = [None] * n if crops is None else list(crops)
     if len(crops) != n:
         raise ValueError("crops must have one entry per image")
+    scales = [1] * n if scales is None else [int(s) for s in scales]
+    if len(scales) != n or any(s not in (1, 2, 4, 8) for s in scales):
+        raise ValueError("scales must have one entry of 1, 2, 4 or 8 per image")
     stream = torch.cuda.current_stream(dev).cuda_stream
     decs, entries, planes_list, infos, cis, keep = [], [], [], [], [], []
     try:
         scans = 0
-        for data, crop in zip(datas, crops):
+        for i, (data, crop, scale) in enumerate(zip(datas, crops, scales)):
             dec = Decoder()
             decs.append(dec)
             dec.set_batch_hint(n)
             dec.set_idct("islow")
+            if scale != 1:
+                dec.set_scale(scale)
+                dec.set_scale_mode("libjpeg")
             if crop is not None:
                 dec.set_crop(*crop)
             info = dec.parse_header(data)
+            if _needs_replication(info, scale):
+                raise ValueError("image %d at scale 1/8 has subsampling left (%s x %s): libjpeg replicates there, which the "
+                                 "batched resize does not reproduce" % (i, list(info.subsampling.x[:info.num_components]),
+                                                                      list(info.subsampling.y[:info.num_components])))
             scans += dec.layout().num_scans
             nb = dec.get_buffer_size()
             tmp = torch.empty(nb + 256, dtype=torch.uint8, device=dev)

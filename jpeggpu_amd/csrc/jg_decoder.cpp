@@ -130,6 +130,32 @@ struct Decoder {
     int scale_log2_request = 0;
     int scale_log2         = 0;
     int scaled(int size) const { return (size + (1 << scale_log2) - 1) >> scale_log2; } // ceil(size / 2^scale_log2)
+    // jpeggpu_ext_set_scale_mode (or JPEGGPU_SCALE_MODE at startup), taking effect at the next parse_header like the scale.
+    // `draft`: the parsed image is decoded in JPEGGPU_EXT_SCALE_LIBJPEG mode at a scale below 1: component c has blocks of
+    // 8 >> blk_lg[c] samples (jdmaster.c's DCT_scaled_size, set_block_sizes). Otherwise blk_lg[c] == scale_log2 for all.
+    int scale_mode_request = 0;
+    int scale_mode         = 0;
+    bool draft             = false;
+    int blk_lg[kMaxComp]   = {0, 0, 0, 0};
+    void set_block_sizes();
+    int blk(int c) const { return 8 >> blk_lg[c]; }                                           // samples per block side
+    int eff_hs(int c) const { return reader.s.comp[c].hs << (scale_log2 - blk_lg[c]); }      // h_c S_c / S_min: the sampling
+    int eff_vs(int c) const { return reader.s.comp[c].vs << (scale_log2 - blk_lg[c]); }      //   factor the planes really have
+    // the component's whole plane at the scale: ceil(W h_c S_c / (8 h_max)) in draft mode, ceil(plane / d) otherwise
+    int full_x(int c) const
+    {
+        const Stream& s = reader.s;
+        if (!draft) return scaled(s.comp[c].size_x);
+        const long long den = 8ll * s.hs_max;
+        return static_cast<int>((static_cast<long long>(s.size_x) * s.comp[c].hs * blk(c) + den - 1) / den);
+    }
+    int full_y(int c) const
+    {
+        const Stream& s = reader.s;
+        if (!draft) return scaled(s.comp[c].size_y);
+        const long long den = 8ll * s.vs_max;
+        return static_cast<int>((static_cast<long long>(s.size_y) * s.comp[c].vs * blk(c) + den - 1) / den);
+    }
     // jpeggpu_ext_set_idct (or JPEGGPU_IDCT at startup): the full-size IDCT, taking effect at the next parse_header like the
     // scale. It changes the IDCT stage only, and only at scale 1 (the reduced IDCTs are libjpeg's already).
     uint8_t idct_method_request = kIdctReference;
@@ -144,8 +170,8 @@ struct Decoder {
         int ox[kMaxComp]{}, oy[kMaxComp]{};   // window origin in the component's plane
         int wx[kMaxComp]{}, wy[kMaxComp]{};   // window size
     } crop;
-    int plane_x(int c) const { return crop.on ? crop.wx[c] : scaled(reader.s.comp[c].size_x); } // what decode writes
-    int plane_y(int c) const { return crop.on ? crop.wy[c] : scaled(reader.s.comp[c].size_y); }
+    int plane_x(int c) const { return crop.on ? crop.wx[c] : full_x(c); } // what decode writes
+    int plane_y(int c) const { return crop.on ? crop.wy[c] : full_y(c); }
     bool set_crop_window();
     IdctWindow scan_window(const Scan& sc) const;
 
@@ -170,6 +196,24 @@ struct Decoder {
     bool fill_blob();
 };
 
+/// Each component's block size for the parsed image. JPEGGPU_EXT_SCALE_LIBJPEG at a scale below 1: jdmaster.c's rule -- from
+/// S_min = 8 / d, a component's size doubles while it stays below 8 and the doubled block still divides what the largest
+/// sampling factors span, in both directions. Where that leaves every component at S_min (4:4:4, grey, 4:2:2 and the like)
+/// the image is decoded as in JPEGGPU_EXT_SCALE_UNIFORM mode: the planes are the same.
+void Decoder::set_block_sizes()
+{
+    const Stream& s = reader.s;
+    const int mn    = 8 >> scale_log2;
+    draft           = false;
+    for (int c = 0; c < s.num_comp; ++c) {
+        int size = mn;
+        if (scale_mode == JPEGGPU_EXT_SCALE_LIBJPEG)
+            while (size < 8 && (s.hs_max * mn) % (s.comp[c].hs * size * 2) == 0 && (s.vs_max * mn) % (s.comp[c].vs * size * 2) == 0) size *= 2;
+        blk_lg[c] = size == 8 ? 0 : size == 4 ? 1 : size == 2 ? 2 : 3;
+        if (size != mn) draft = true;
+    }
+}
+
 /// The windows of a crop (jpeggpu_ext.h, jpeggpu_ext_set_crop) from the request and the parsed frame; false if the
 /// rectangle does not lie inside the image at the scale.
 bool Decoder::set_crop_window()
@@ -179,21 +223,24 @@ bool Decoder::set_crop_window()
     c.on = true;
     c.x = crop_request[0], c.y = crop_request[1], c.w = crop_request[2], c.h = crop_request[3];
     if (c.x + static_cast<long long>(c.w) > scaled(s.size_x) || c.y + static_cast<long long>(c.h) > scaled(s.size_y)) return false;
-    const int n = 8 >> scale_log2; // samples per block side at the scale
     int lo_x[kMaxComp], hi_x[kMaxComp], lo_y[kMaxComp], hi_y[kMaxComp];
     c.mx0 = c.my0 = 1 << 30;
     for (int k = 0; k < s.num_comp; ++k) {
         const Component& fc = s.comp[k];
+        // samples per block side at the scale (draft mode: the component's own), and the sampling factors its plane has
+        // there (eff_hs: what is left of h_max / h_c once the IDCT has done its part)
+        const int n = blk(k), hs = eff_hs(k), vs = eff_vs(k);
         // samples of the rectangle, plus the one-sample halo of the upsamplers, clipped to the plane
-        lo_x[k] = std::max(static_cast<int>(static_cast<long long>(c.x) * fc.hs / s.hs_max) - 1, 0);
-        hi_x[k] = std::min(static_cast<int>(static_cast<long long>(c.x + c.w - 1) * fc.hs / s.hs_max) + 1, scaled(fc.size_x) - 1);
-        lo_y[k] = std::max(static_cast<int>(static_cast<long long>(c.y) * fc.vs / s.vs_max) - 1, 0);
-        hi_y[k] = std::min(static_cast<int>(static_cast<long long>(c.y + c.h - 1) * fc.vs / s.vs_max) + 1, scaled(fc.size_y) - 1);
+        lo_x[k] = std::max(static_cast<int>(static_cast<long long>(c.x) * hs / s.hs_max) - 1, 0);
+        hi_x[k] = std::min(static_cast<int>(static_cast<long long>(c.x + c.w - 1) * hs / s.hs_max) + 1, full_x(k) - 1);
+        lo_y[k] = std::max(static_cast<int>(static_cast<long long>(c.y) * vs / s.vs_max) - 1, 0);
+        hi_y[k] = std::min(static_cast<int>(static_cast<long long>(c.y + c.h - 1) * vs / s.vs_max) + 1, full_y(k) - 1);
         c.mx0 = std::min(c.mx0, lo_x[k] / (n * fc.hs)), c.mx1 = std::max(c.mx1, hi_x[k] / (n * fc.hs) + 1);
         c.my0 = std::min(c.my0, lo_y[k] / (n * fc.vs)), c.my1 = std::max(c.my1, hi_y[k] / (n * fc.vs) + 1);
     }
     for (int k = 0; k < s.num_comp; ++k) {
         const Component& fc = s.comp[k];
+        const int n = blk(k);
         c.ox[k] = c.mx0 * n * fc.hs, c.oy[k] = c.my0 * n * fc.vs;
         c.wx[k] = hi_x[k] + 1 - c.ox[k], c.wy[k] = hi_y[k] + 1 - c.oy[k];
     }
@@ -210,7 +257,7 @@ IdctWindow Decoder::scan_window(const Scan& sc) const
     if (sc.num_comp > 1) {
         w.mx0 = crop.mx0, w.my0 = crop.my0, w.mcus_x = crop.mx1 - crop.mx0, w.mcus_y = crop.my1 - crop.my0;
     } else {
-        const int c = sc.comp[0].comp_idx, n = 8 >> scale_log2;
+        const int c = sc.comp[0].comp_idx, n = blk(c);
         w.mx0 = crop.ox[c] / n, w.my0 = crop.oy[c] / n;
         w.mcus_x = (crop.ox[c] + crop.wx[c] + n - 1) / n - w.mx0, w.mcus_y = (crop.oy[c] + crop.wy[c] + n - 1) / n - w.my0;
     }
@@ -542,7 +589,7 @@ jpeggpu_status build_jobs(
         ip.du_per_mcu  = sc.du_per_mcu;
         ip.mcus_x      = sc.mcus_x;
         ip.first_mcu   = sc.first_mcu;
-        ip.scale_log2  = static_cast<uint8_t>(d.scale_log2);
+        ip.scale_log2  = static_cast<uint8_t>(d.draft ? kDraftScale | d.scale_log2 : d.scale_log2);
         ip.idct_method = d.scale_log2 == 0 ? d.idct_method : kIdctReference;
         {
             const MagicDiv a = magic_div(static_cast<uint32_t>(sc.du_per_mcu)), b = magic_div(static_cast<uint32_t>(sc.mcus_x));
@@ -568,6 +615,19 @@ jpeggpu_status build_jobs(
             ip.pitch[a]         = img->pitch[c.comp_idx];
             ip.qidx[a]          = fc.qidx;
             ip.plane[a]         = img->image[c.comp_idx];
+        }
+        if (d.draft) { // the units of the MCU by block size (IdctDraft)
+            IdctDraft& dr = job.draft;
+            dr.on         = 1;
+            for (int k = 0; k < sc.du_per_mcu; ++k) {
+                const int lg                   = d.blk_lg[sc.comp[ip.du_comp[k]].comp_idx];
+                dr.comp_lg[ip.du_comp[k]]      = static_cast<uint8_t>(lg);
+                dr.k[lg][dr.n[lg]++]           = static_cast<uint8_t>(k);
+            }
+            for (int lg = 0; lg < 4; ++lg) {
+                const MagicDiv m = magic_div(dr.n[lg]);
+                dr.mul[lg] = m.mul, dr.shift[lg] = m.shift;
+            }
         }
         job.win = d.scan_window(sc);
         if (job.win.mcus_x) ip.num_du = job.win.mcus_x * job.win.mcus_y * sc.du_per_mcu;
@@ -1033,6 +1093,12 @@ enum jpeggpu_status jpeggpu_decoder_startup(jpeggpu_decoder_t* decoder)
         else if (e[0] != 0 && std::strcmp(e, "reference") != 0)
             std::fprintf(stderr, "jpeggpu: JPEGGPU_IDCT=\"%s\" is not one of reference, islow: the reference IDCT stays in use\n", e);
     }
+    // JPEGGPU_SCALE_MODE=libjpeg: libjpeg's per-component block sizes for scaled decodes (jpeggpu_ext_set_scale_mode)
+    if (const char* e = std::getenv("JPEGGPU_SCALE_MODE")) {
+        if (std::strcmp(e, "libjpeg") == 0) (*decoder)->d.scale_mode_request = JPEGGPU_EXT_SCALE_LIBJPEG;
+        else if (e[0] != 0 && std::strcmp(e, "uniform") != 0)
+            std::fprintf(stderr, "jpeggpu: JPEGGPU_SCALE_MODE=\"%s\" is not one of uniform, libjpeg: the uniform mode stays in use\n", e);
+    }
     return JPEGGPU_SUCCESS;
 }
 
@@ -1060,6 +1126,8 @@ enum jpeggpu_status jpeggpu_decoder_parse_header(
     d.parsed   = false;
     d.scale_log2 = d.scale_log2_request;
     d.idct_method = d.idct_method_request;
+    d.scale_mode  = d.scale_mode_request;
+    d.draft       = false;
     d.crop.on     = false;
     const bool crop = d.crop_request[2] > 0;
     if (crop && d.shard_world > 1) {
@@ -1076,6 +1144,7 @@ enum jpeggpu_status jpeggpu_decoder_parse_header(
     }
     if (st != JPEGGPU_SUCCESS) return st;
     const jg::Stream& s = d.reader.s;
+    d.set_block_sizes();
     if (crop) {
         if (!d.set_crop_window()) {
             d.logger.log("crop %d,%d %dx%d does not lie inside the image\n", d.crop_request[0], d.crop_request[1], d.crop_request[2], d.crop_request[3]);
@@ -1097,8 +1166,8 @@ enum jpeggpu_status jpeggpu_decoder_parse_header(
     for (int c = 0; c < s.num_comp; ++c) {
         img_info->sizes_x[c]       = d.plane_x(c); // libjpeg's downsampled_width at the scale (cropped: the window's)
         img_info->sizes_y[c]       = d.plane_y(c);
-        img_info->subsampling.x[c] = s.comp[c].hs;
-        img_info->subsampling.y[c] = s.comp[c].vs;
+        img_info->subsampling.x[c] = d.eff_hs(c); // (draft mode: the factors the planes have, h_c S_c / S_min)
+        img_info->subsampling.y[c] = d.eff_vs(c);
     }
     d.data      = data;
     d.data_size = size;
@@ -1193,8 +1262,7 @@ enum jpeggpu_status jpeggpu_ext_get_shard_rows(jpeggpu_decoder_t decoder, int co
     if (!d.parsed) return JPEGGPU_INVALID_ARGUMENT;
     const jg::Stream& s = d.reader.s;
     if (component < 0 || component >= s.num_comp) return JPEGGPU_INVALID_ARGUMENT;
-    const jg::Component& fc = s.comp[component];
-    const int size_y = d.scaled(fc.size_y);
+    const int size_y = d.full_y(component);
     *first_row = 0;
     *num_rows  = size_y;
     const jg::Scan& sc = s.scans[0];
@@ -1202,7 +1270,7 @@ enum jpeggpu_status jpeggpu_ext_get_shard_rows(jpeggpu_decoder_t decoder, int co
     int v = 1;
     for (int a = 0; a < sc.num_comp; ++a)
         if (sc.comp[a].comp_idx == component) v = sc.comp[a].v;
-    const int rows_per_mcu_row = (8 >> d.scale_log2) * v; // whole MCU rows: 8 v / scale rows each
+    const int rows_per_mcu_row = d.blk(component) * v; // whole MCU rows: v blocks of the component's size at the scale each
     const int row0 = sc.first_mcu / sc.mcus_x * rows_per_mcu_row, row1 = (sc.first_mcu + sc.shard_mcus) / sc.mcus_x * rows_per_mcu_row;
     *first_row = std::min(row0, size_y);
     *num_rows  = std::min(row1, size_y) - *first_row;
@@ -1313,6 +1381,29 @@ enum jpeggpu_status jpeggpu_ext_set_scale(jpeggpu_decoder_t decoder, int scale_d
     return JPEGGPU_SUCCESS;
 }
 
+enum jpeggpu_status jpeggpu_ext_set_scale_mode(jpeggpu_decoder_t decoder, enum jpeggpu_ext_scale_mode mode)
+{
+    if (!decoder) return JPEGGPU_INVALID_ARGUMENT;
+    const int m = static_cast<int>(mode);
+    if (m != JPEGGPU_EXT_SCALE_UNIFORM && m != JPEGGPU_EXT_SCALE_LIBJPEG) return JPEGGPU_INVALID_ARGUMENT;
+    decoder->d.scale_mode_request = m;
+    return JPEGGPU_SUCCESS;
+}
+
+enum jpeggpu_status jpeggpu_ext_get_scale_info(jpeggpu_decoder_t decoder, struct jpeggpu_ext_scale_info* info)
+{
+    if (!decoder || !info) return JPEGGPU_INVALID_ARGUMENT;
+    const Decoder& d = decoder->d;
+    if (!d.parsed) return JPEGGPU_INVALID_ARGUMENT;
+    std::memset(info, 0, sizeof(*info));
+    info->scale_denom = 1 << d.scale_log2;
+    info->mode        = d.scale_mode;
+    for (int c = 0; c < d.reader.s.num_comp; ++c) info->block_size[c] = d.blk(c);
+    // jdsample.c: do_fancy_upsampling && min_DCT_scaled_size > 1
+    info->fancy_upsampling = !(d.scale_mode == JPEGGPU_EXT_SCALE_LIBJPEG && d.scale_log2 == 3);
+    return JPEGGPU_SUCCESS;
+}
+
 enum jpeggpu_status jpeggpu_ext_set_idct(jpeggpu_decoder_t decoder, enum jpeggpu_ext_idct method)
 {
     if (!decoder) return JPEGGPU_INVALID_ARGUMENT;
@@ -1344,8 +1435,8 @@ enum jpeggpu_status jpeggpu_ext_get_crop(jpeggpu_decoder_t decoder, struct jpegg
     for (int c = 0; c < s.num_comp; ++c) {
         info->origin_x[c] = d.crop.on ? d.crop.ox[c] : 0;
         info->origin_y[c] = d.crop.on ? d.crop.oy[c] : 0;
-        info->full_x[c]   = d.scaled(s.comp[c].size_x);
-        info->full_y[c]   = d.scaled(s.comp[c].size_y);
+        info->full_x[c]   = d.full_x(c);
+        info->full_y[c]   = d.full_y(c);
     }
     return JPEGGPU_SUCCESS;
 }
@@ -1724,14 +1815,10 @@ enum jpeggpu_status jpeggpu_ext_planes_to_rgbi(
     return err == hipSuccess ? JPEGGPU_SUCCESS : JPEGGPU_INTERNAL_ERROR;
 }
 
-enum jpeggpu_status jpeggpu_ext_planes_to_rgbi_fancy(
-    const struct jpeggpu_img_info* info,
-    const struct jpeggpu_img* src,
-    uint8_t* dst,
-    int dst_pitch,
-    int width,
-    int height,
-    jpeggpu_stream_t stream)
+namespace {
+enum jpeggpu_status planes_to_rgbi_libjpeg(
+    const struct jpeggpu_img_info* info, const struct jpeggpu_img* src, uint8_t* dst, int dst_pitch, int width, int height,
+    jpeggpu_stream_t stream, bool replicate)
 {
     if (!info || !src || !dst || width <= 0 || height <= 0 || dst_pitch < 3 * width) return JPEGGPU_INVALID_ARGUMENT;
     const int nc = info->num_components;
@@ -1747,17 +1834,13 @@ enum jpeggpu_status jpeggpu_ext_planes_to_rgbi_fancy(
         if (sx_max % info->subsampling.x[c] != 0 || sy_max % info->subsampling.y[c] != 0) return JPEGGPU_NOT_SUPPORTED;
     const hipError_t err = jg::launch_rgbi_fancy(
         src->image, src->pitch, info->sizes_x, info->sizes_y, info->subsampling.x, info->subsampling.y,
-        sx_max, sy_max, nc, dst, dst_pitch, width, height, stream);
+        sx_max, sy_max, nc, dst, dst_pitch, width, height, stream, replicate);
     return err == hipSuccess ? JPEGGPU_SUCCESS : JPEGGPU_INTERNAL_ERROR;
 }
 
-enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_fancy(
-    const struct jpeggpu_img_info* info,
-    const struct jpeggpu_ext_crop_info* crop,
-    const struct jpeggpu_img* src,
-    uint8_t* dst,
-    int dst_pitch,
-    jpeggpu_stream_t stream)
+enum jpeggpu_status crop_to_rgbi_libjpeg(
+    const struct jpeggpu_img_info* info, const struct jpeggpu_ext_crop_info* crop, const struct jpeggpu_img* src, uint8_t* dst,
+    int dst_pitch, jpeggpu_stream_t stream, bool replicate)
 {
     if (!info || !crop || !src || !dst || crop->width <= 0 || crop->height <= 0 || crop->x < 0 || crop->y < 0 || dst_pitch < 3 * crop->width)
         return JPEGGPU_INVALID_ARGUMENT;
@@ -1785,8 +1868,37 @@ enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_fancy(
     }
     const hipError_t err = jg::launch_crop_rgbi_fancy(
         src->image, src->pitch, info->sizes_x, info->sizes_y, crop->origin_x, crop->origin_y, crop->full_x, info->subsampling.x,
-        info->subsampling.y, sx_max, sy_max, nc, crop->x, crop->y, dst, dst_pitch, crop->width, crop->height, stream);
+        info->subsampling.y, sx_max, sy_max, nc, crop->x, crop->y, dst, dst_pitch, crop->width, crop->height, stream, replicate);
     return err == hipSuccess ? JPEGGPU_SUCCESS : JPEGGPU_INTERNAL_ERROR;
+}
+} // namespace
+
+enum jpeggpu_status jpeggpu_ext_planes_to_rgbi_fancy(
+    const struct jpeggpu_img_info* info, const struct jpeggpu_img* src, uint8_t* dst, int dst_pitch, int width, int height,
+    jpeggpu_stream_t stream)
+{
+    return planes_to_rgbi_libjpeg(info, src, dst, dst_pitch, width, height, stream, false);
+}
+
+enum jpeggpu_status jpeggpu_ext_planes_to_rgbi_replicate(
+    const struct jpeggpu_img_info* info, const struct jpeggpu_img* src, uint8_t* dst, int dst_pitch, int width, int height,
+    jpeggpu_stream_t stream)
+{
+    return planes_to_rgbi_libjpeg(info, src, dst, dst_pitch, width, height, stream, true);
+}
+
+enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_fancy(
+    const struct jpeggpu_img_info* info, const struct jpeggpu_ext_crop_info* crop, const struct jpeggpu_img* src, uint8_t* dst,
+    int dst_pitch, jpeggpu_stream_t stream)
+{
+    return crop_to_rgbi_libjpeg(info, crop, src, dst, dst_pitch, stream, false);
+}
+
+enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_replicate(
+    const struct jpeggpu_img_info* info, const struct jpeggpu_ext_crop_info* crop, const struct jpeggpu_img* src, uint8_t* dst,
+    int dst_pitch, jpeggpu_stream_t stream)
+{
+    return crop_to_rgbi_libjpeg(info, crop, src, dst, dst_pitch, stream, true);
 }
 
 enum jpeggpu_status jpeggpu_ext_self_test(jpeggpu_stream_t stream)

@@ -359,7 +359,8 @@ struct IdctParams {
     uint8_t du_comp[kMaxDuPerMcu]; // scan-component index of each data unit in the MCU
     uint8_t du_dx[kMaxDuPerMcu];   // block column inside the MCU
     uint8_t du_dy[kMaxDuPerMcu];   // block row inside the MCU
-    uint8_t scale_log2;            // jpeggpu_ext_set_scale: planes at 1 / 2^scale_log2 (0: full size, idct_kernel; else idct_scaled_kernel)
+    uint8_t scale_log2;            // jpeggpu_ext_set_scale: planes at 1 / 2^scale_log2 (0: full size, idct_kernel; else idct_scaled_kernel);
+                                   // kDraftScale | log2 of the denominator: a job of JPEGGPU_EXT_SCALE_LIBJPEG (IdctDraft below)
     uint8_t idct_method;           // jpeggpu_ext_set_idct, full-size jobs only (0 on a scaled one): kIdctReference or kIdctIslow
     int comp_h[kMaxComp];          // blocks per MCU horizontally (1 when non-interleaved)
     int comp_v[kMaxComp];
@@ -385,6 +386,24 @@ struct IdctWindow {
     int mcus_x, mcus_y;
     uint32_t mcus_x_mul, mcus_x_shift; // magic_div(mcus_x)
 };
+
+/// Scaled decoding in libjpeg's own way (jpeggpu_ext_set_scale_mode, JPEGGPU_EXT_SCALE_LIBJPEG): every component has its
+/// own block size S_c = 8 >> comp_lg (jdmaster.c: the IDCT does as much of the chroma upsampling as it can), so the units
+/// of one MCU differ in size. The IDCT stage takes the units of ONE size per launch: class lg (0: 8x8 with the ISLOW
+/// arithmetic in idct_kernel's layout, 1..3: idct_scaled_kernel's 4x4, 2x2, 1x1) holds n[lg] units of every MCU, the data
+/// units k[lg][0 .. n[lg]) of it, and unit w of the class is unit k[lg][w % n[lg]] of MCU w / n[lg] of the job (of its
+/// window, for a cropped one). Such a job carries IdctParams::scale_log2 = kDraftScale | log2 d, which every kernel of
+/// the other jobs reads as "not mine"; `on` is what the draft instantiations ask.
+constexpr uint8_t kDraftScale = 4;
+struct IdctDraft {
+    uint8_t on;
+    uint8_t n[4];
+    uint8_t k[4][kMaxDuPerMcu];
+    uint8_t comp_lg[kMaxComp]; // per scan component
+    uint8_t pad_[3];
+    uint32_t mul[4], shift[4]; // magic_div(n[lg])
+};
+static_assert(sizeof(IdctDraft) == 84, "1 + 4 + 40 + 4 + 3 bytes, then eight words");
 
 /// IdctParams::idct_method (jpeggpu_ext_idct): the reference's fixed-point transform, or libjpeg's jpeg_idct_islow.
 constexpr uint8_t kIdctReference = 0, kIdctIslow = 1;
@@ -451,6 +470,7 @@ struct ScanJob {
     int* bnd_p;                  // [num_seq] exit state of the subsequence in front of sequence b as b's workgroup assumed it
     int* bnd_cz;                 //   (-1: nothing to say): a boundary where it equals the stored state needs no flow
     IdctWindow win;              // jpeggpu_ext_set_crop: the MCUs the IDCT transforms (win.mcus_x == 0: every one)
+    IdctDraft draft;             // jpeggpu_ext_set_scale_mode: the unit classes of a JPEGGPU_EXT_SCALE_LIBJPEG job (draft.on == 0: none)
 };
 
 } // namespace jg

@@ -10,6 +10,8 @@
 //                                                                    (reference idct.cu:44-223 + decode_transpose.cu:41-132)
 //   idct_scaled_kernel      the same at 1/2, 1/4, 1/8 size: libjpeg-turbo's reduced IDCTs (jidctred.c; jpeggpu_ext_set_scale)
 //   idct_kernel<IslowJobs<..>>  full size with libjpeg-turbo's jpeg_idct_islow (jidctint.c; jpeggpu_ext_set_idct)
+//   ..<DraftJobs<..>>       the units of one block size of a job in libjpeg's scale mode, whose components differ in size
+//                                                                    (jdmaster.c; jpeggpu_ext_set_scale_mode)
 //   fancy_rgbi_kernel       libjpeg's fancy chroma upsampling + integer YCbCr -> interleaved RGB (jdsample.c, jdcolor.c)
 //   resize_h_kernel /       batched resize to one size with Pillow's BILINEAR / BICUBIC arithmetic: the horizontal taps
 //   resize_v_kernel         straight from the planes' windows (fancy RGB in LDS), then the vertical taps (jpeggpu_ext_resize_to_rgb)
@@ -2310,6 +2312,52 @@ __device__ __forceinline__ WindowUnit window_unit(const IdctParams& ip, const Id
     return WindowUnit{(mcu - ip.first_mcu) * ip.du_per_mcu + k, mx, my, k};
 }
 
+/// The units of ONE block size of a JPEGGPU_EXT_SCALE_LIBJPEG job (IdctDraft, jg_defs.h) are what the IDCT kernels
+/// transform for DraftJobs<JS>: idct_kernel<IslowJobs<DraftJobs<JS>>> the 8x8 ones, idct_scaled_kernel<DraftJobs<JS>, lg>
+/// the reduced ones. Every other job counts no units of any size there (draft_num_du), so one launch per size serves a
+/// batch of any mix; a job's MCU window is honoured whether the call holds cropped jobs or not. Only jobs of that mode
+/// reach these instantiations.
+template <class JS>
+struct DraftJobs {
+    JS js;
+    __device__ __forceinline__ const ScanJob& get() const { return js.get(); }
+};
+template <class JS>
+struct IsDraft : std::false_type {
+};
+template <class JS>
+struct IsDraft<DraftJobs<JS>> : std::true_type {
+};
+template <class JS>
+struct IsDraft<IslowJobs<JS>> : IsDraft<JS> {
+};
+/// Units of class kLg in the job: its MCUs (the window's, for a cropped job: IdctParams::num_du counts those) times the
+/// class's units per MCU. 0 for a job of another kind and for one the device front end refused (num_du == 0).
+template <int kLg>
+__device__ __forceinline__ int draft_num_du(const ScanJob& j)
+{
+    if (!j.draft.on) return 0;
+    return static_cast<int>(magic_quot(static_cast<uint32_t>(j.ip.num_du), j.ip.du_per_mcu_mul, j.ip.du_per_mcu_shift)) * j.draft.n[kLg];
+}
+/// Unit w of class kLg: window_unit's answer for data unit k[kLg][w % n] of MCU w / n.
+template <int kLg>
+__device__ __forceinline__ WindowUnit draft_unit(const ScanJob& j, int w)
+{
+    const IdctParams& ip  = j.ip;
+    const IdctWindow& win = j.win;
+    const int wm = static_cast<int>(magic_quot(w, j.draft.mul[kLg], j.draft.shift[kLg]));
+    const int k  = j.draft.k[kLg][w - wm * j.draft.n[kLg]];
+    if (win.mcus_x == 0) {
+        const int mcu = wm + ip.first_mcu;
+        const int my  = static_cast<int>(magic_quot(mcu, ip.mcus_x_mul, ip.mcus_x_shift));
+        return WindowUnit{wm * ip.du_per_mcu + k, mcu - my * ip.mcus_x, my, k};
+    }
+    const int my  = static_cast<int>(magic_quot(wm, win.mcus_x_mul, win.mcus_x_shift));
+    const int mx  = wm - my * win.mcus_x;
+    const int mcu = (win.my0 + my) * ip.mcus_x + win.mx0 + mx;
+    return WindowUnit{(mcu - ip.first_mcu) * ip.du_per_mcu + k, mx, my, k};
+}
+
 /// One 8-point pass of jpeg_idct_islow (jidctint.c, CONST_BITS = 13): the eight outputs before their DESCALE, in T (int:
 /// wrapping 32-bit arithmetic, the library is built with -fwrapv; long long: jidctint.c's JLONG). Output i is row i of a
 /// column (pass 1) or column i of a row (pass 2).
@@ -2375,6 +2423,8 @@ __global__ __launch_bounds__(256) void idct_kernel(JS js)
 {
     using X = typename IdctOf<JS>::type;
     constexpr bool kCrop = IsCropped<JS>::value;
+    constexpr bool kDraft = IsDraft<JS>::value; // the 8x8 units of a JPEGGPU_EXT_SCALE_LIBJPEG job (draft_unit)
+    static_assert(!kDraft || X::kIslow, "blocks of size 8 of that mode take the ISLOW arithmetic");
     __shared__ __attribute__((aligned(16))) int16_t s_blk[kIdctDuPerBlock][kIdctDuStride]; // [unit][col * 8 + row]
     // ISLOW: the int workspace between the passes, [unit][row * 8 + col] (+8: as s_blk)
     __shared__ __attribute__((aligned(16))) int s_ws[X::kIslow ? kIdctDuPerBlock : 1][X::kIslow ? kIdctDuStride : 4];
@@ -2402,7 +2452,10 @@ __global__ __launch_bounds__(256) void idct_kernel(JS js)
     const JobView J(js.get());
     const IdctParams& ip = J.ip;
     const int du0        = blockIdx.x * kIdctDuPerWg;
-    const int num_du     = ip.num_du;
+    const int num_du     = [&] {
+        if constexpr (kDraft) return draft_num_du<0>(js.get());
+        else return ip.num_du;
+    }();
     if (du0 >= num_du) return;
 
     const int t  = threadIdx.x;
@@ -2417,7 +2470,8 @@ __global__ __launch_bounds__(256) void idct_kernel(JS js)
 #pragma unroll
     for (int it = 0; it < kIdctIters; ++it) {
         const int w = min(du0 + it * kIdctDuPerBlock + dl, num_du - 1);
-        if constexpr (kCrop) rec[it] = ld_global(J.du_tab + window_unit(ip, js.get().win, w).stream); // (a window unit: its MCU's place in the stream)
+        if constexpr (kDraft) rec[it] = ld_global(J.du_tab + draft_unit<0>(js.get(), w).stream);
+        else if constexpr (kCrop) rec[it] = ld_global(J.du_tab + window_unit(ip, js.get().win, w).stream); // (a window unit: its MCU's place in the stream)
         else rec[it] = ld_global(J.du_tab + w);
     }
     // (and the lane's byte and word of the job's geometry tables, below)
@@ -2451,6 +2505,10 @@ __global__ __launch_bounds__(256) void idct_kernel(JS js)
     int gmx        = gmcu - gmy * ip.mcus_x;
     if constexpr (kCrop) { // the MCU's column and row in the window, whose top-left corner ip.plane is
         const WindowUnit u = window_unit(ip, js.get().win, gdu);
+        gk = u.k, gmx = u.mx, gmy = u.my;
+    }
+    if constexpr (kDraft) {
+        const WindowUnit u = draft_unit<0>(js.get(), gdu);
         gk = u.k, gmx = u.mx, gmy = u.my;
     }
     // a table entry that was never written (corrupt stream) must not lead out of the buffer
@@ -2746,15 +2804,21 @@ __global__ __launch_bounds__(256) void idct_scaled_kernel(JS js)
     const JobView J(js.get());
     const IdctParams& ip = J.ip;
     constexpr int lg     = kLg;
+    constexpr bool kDraft = IsDraft<JS>::value; // the units of this size of a JPEGGPU_EXT_SCALE_LIBJPEG job (draft_unit)
     const int du0        = blockIdx.x * kScaledDuPerWg;
-    const int num_du     = ip.num_du;
-    if (ip.scale_log2 != kLg || du0 >= num_du) return; // (uniform)
+    int num_du           = ip.num_du;
+    if constexpr (kDraft) num_du = draft_num_du<kLg>(js.get());
+    else if (ip.scale_log2 != kLg) return; // (uniform)
+    if (du0 >= num_du) return;
     const int t  = threadIdx.x;
     int du = min(du0 + t, num_du - 1);
 
     // geometry (idct_kernel's, at N pixels per block side)
     int k, mx, my;
-    if constexpr (IsCropped<JS>::value) { // a window unit (idct_kernel): its MCU's place in the stream, and in the window
+    if constexpr (kDraft) {
+        const WindowUnit u = draft_unit<kLg>(js.get(), du);
+        du = u.stream, k = u.k, mx = u.mx, my = u.my;
+    } else if constexpr (IsCropped<JS>::value) { // a window unit (idct_kernel): its MCU's place in the stream, and in the window
         const WindowUnit u = window_unit(ip, js.get().win, du);
         du = u.stream, k = u.k, mx = u.mx, my = u.my;
     } else {
@@ -3403,6 +3467,13 @@ hipError_t launch_idct(const JS& js, const JobExtent& e, int grid_y, hipStream_t
     if (e.scales & 2u) idct_scaled_kernel<G<JS>, 1><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(G<JS>{js});
     if (e.scales & 4u) idct_scaled_kernel<G<JS>, 2><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(G<JS>{js});
     if (e.scales & 8u) idct_scaled_kernel<G<JS>, 3><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(G<JS>{js});
+    // jobs of JPEGGPU_EXT_SCALE_LIBJPEG: one launch per block size their components have (IdctDraft; blocks past a class's
+    // units leave at once: the grid is that of all units)
+    using D = DraftJobs<JS>;
+    if (e.draft_sizes & 1u) idct_kernel<IslowJobs<D>><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(IslowJobs<D>{D{js}});
+    if (e.draft_sizes & 2u) idct_scaled_kernel<D, 1><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(D{js});
+    if (e.draft_sizes & 4u) idct_scaled_kernel<D, 2><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(D{js});
+    if (e.draft_sizes & 8u) idct_scaled_kernel<D, 3><<<dim3(e.max_idct_blocks, grid_y), 256, 0, stream>>>(D{js});
     return hipGetLastError();
 }
 
@@ -3458,6 +3529,9 @@ void extend(JobExtent& e, const ScanJob& job)
     e.max_idct_blocks = blocks > e.max_idct_blocks ? blocks : e.max_idct_blocks;
     e.scales |= 1u << job.ip.scale_log2;
     if (job.ip.scale_log2 == 0) e.methods |= 1u << job.ip.idct_method;
+    if (job.draft.on)
+        for (int lg = 0; lg < 4; ++lg)
+            if (job.draft.n[lg]) e.draft_sizes |= 1u << lg;
     if (job.win.mcus_x != 0) e.crop = true;
     e.max_tab_bytes   = job.sp.tab_bytes > e.max_tab_bytes ? job.sp.tab_bytes : e.max_tab_bytes;
     e.max_tab_bytes_sync = job.sp.tab_bytes_sync > e.max_tab_bytes_sync ? job.sp.tab_bytes_sync : e.max_tab_bytes_sync;
@@ -3583,7 +3657,7 @@ hipError_t launch_rgbi(
 
 hipError_t launch_rgbi_fancy(
     const uint8_t* const* planes, const int* pitch, const int* w, const int* h, const int* num_x, const int* num_y,
-    int den_x, int den_y, int ncomp, uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream)
+    int den_x, int den_y, int ncomp, uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream, bool replicate)
 {
     if (width <= 0 || height <= 0) return hipSuccess;
     FancyParams p{};
@@ -3604,6 +3678,7 @@ hipError_t launch_rgbi_fancy(
         else if (f.hr == 2 && f.vr == 2 && f.w > 2) f.mode = kFancyH2V2;
         else if (f.hr == 1 && f.vr == 2) f.mode = kFancyH1V2;
         else f.mode = kFancyReplicate;
+        if (replicate) f.mode = kFancyReplicate; // jdsample.c: no fancy upsampling at min_DCT_scaled_size 1
     }
     const dim3 grid((width + kFancyTileW - 1) / kFancyTileW, (height + kFancyTileH - 1) / kFancyTileH);
     fancy_rgbi_kernel<<<grid, 256, 0, stream>>>(p, dst, dst_pitch, width, height);
@@ -3613,7 +3688,7 @@ hipError_t launch_rgbi_fancy(
 hipError_t launch_crop_rgbi_fancy(
     const uint8_t* const* planes, const int* pitch, const int* win_w, const int* win_h, const int* win_x, const int* win_y,
     const int* full_w, const int* num_x, const int* num_y, int den_x, int den_y, int ncomp, int x, int y,
-    uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream)
+    uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream, bool replicate)
 {
     if (width <= 0 || height <= 0) return hipSuccess;
     FancyParams p{};
@@ -3639,6 +3714,7 @@ hipError_t launch_crop_rgbi_fancy(
         else if (f.hr == 2 && f.vr == 2 && full_w[cc] > 2) f.mode = kFancyH2V2;
         else if (f.hr == 1 && f.vr == 2) f.mode = kFancyH1V2;
         else f.mode = kFancyReplicate;
+        if (replicate) f.mode = kFancyReplicate;
     }
     const dim3 grid((width + kFancyTileW - 1) / kFancyTileW, (height + kFancyTileH - 1) / kFancyTileH);
     crop_rgbi_fancy_kernel<<<grid, 256, 0, stream>>>(p, win, dst, dst_pitch, width, height);

@@ -31,7 +31,8 @@ struct JobExtent {
     int max_tail_part   = 0; // subsequences in the largest tail part of any job
     int max_idct_blocks = 0;
     int subseq_words    = 0; // identical for every job of a launch
-    uint32_t scales     = 0; // bit s: a job decodes at 1 / 2^s (IdctParams::scale_log2)
+    uint32_t scales     = 0; // bit s: a job decodes at 1 / 2^s (IdctParams::scale_log2; bits kDraftScale + 1 ..: jobs of the next line)
+    uint32_t draft_sizes = 0; // bit lg: a JPEGGPU_EXT_SCALE_LIBJPEG job has components of block size 8 >> lg (IdctDraft)
     uint32_t methods    = 0; // bit m: a full-size job takes IDCT method m (IdctParams::idct_method)
     bool crop           = false; // a job has an MCU window (jpeggpu_ext_set_crop, ScanJob::win): the IDCT's CropJobs instantiations
     uint32_t max_tab_bytes = 0;      // largest write-pass table pack
@@ -79,17 +80,19 @@ hipError_t launch_rgbi(
     int den_x, int den_y, int ncomp, uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream);
 
 /// libjpeg's fancy upsampling + integer YCbCr -> interleaved RGB8 (jdsample.c, jdcolor.c); same arguments as launch_rgbi.
-/// hipErrorInvalidValue if a component's sampling factors do not divide the largest ones.
+/// hipErrorInvalidValue if a component's sampling factors do not divide the largest ones. `replicate`: every component is
+/// replicated (libjpeg at 1/8 scale: jdsample.c turns fancy upsampling off when min_DCT_scaled_size is 1); the colour
+/// conversion stays jdcolor.c's.
 hipError_t launch_rgbi_fancy(
     const uint8_t* const* planes, const int* pitch, const int* w, const int* h, const int* num_x, const int* num_y,
-    int den_x, int den_y, int ncomp, uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream);
+    int den_x, int den_y, int ncomp, uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream, bool replicate = false);
 /// launch_rgbi_fancy for a rectangle of the image at (x, y), width x height pixels, from the planes' WINDOWS of a cropped
 /// decode (jpeggpu_ext_set_crop): window sizes, their origins in the full planes, and the full planes' widths (which choose
 /// between fancy upsampling and replication, as for the whole image).
 hipError_t launch_crop_rgbi_fancy(
     const uint8_t* const* planes, const int* pitch, const int* win_w, const int* win_h, const int* win_x, const int* win_y,
     const int* full_w, const int* num_x, const int* num_y, int den_x, int den_y, int ncomp, int x, int y,
-    uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream);
+    uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream, bool replicate = false);
 
 /// launch_rgbi_fancy's per-component choice (FancyMode) for the ratios hr = h_max / h_c, vr = v_max / v_c and a full
 /// plane `full_w` samples wide.
