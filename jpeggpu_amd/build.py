@@ -7,7 +7,7 @@ ROOT = os.path.dirname(_HERE)
 CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libjpeggpu.so")
-SOURCES = ["jg_kernels.hip", "jg_front.hip", "jg_decoder.cpp", "jg_reader.cpp"]
+SOURCES = ["jg_kernels.hip", "jg_output.hip", "jg_front.hip", "jg_decoder.cpp", "jg_output.cpp", "jg_reader.cpp"]
 
 
 def _mode_path(lib_path):
@@ -62,13 +62,13 @@ def check_refill(extra_flags=(), verbose=False):
     return check_refill_text(device_assembly(extra_flags, verbose))
 
 
-def device_assembly(extra_flags=(), verbose=False):
-    """The gfx950 assembly of jg_kernels.hip, as lines."""
+def device_assembly(extra_flags=(), verbose=False, source="jg_kernels.hip"):
+    """The gfx950 assembly of one .hip file under csrc/, as lines."""
     import tempfile
 
     with tempfile.TemporaryDirectory() as tmp:
-        asm = os.path.join(tmp, "jg_kernels.s")
-        cmd = _base_cmd(extra_flags) + ["--offload-device-only", "-S", os.path.join(CSRC, "jg_kernels.hip"), "-o", asm]
+        asm = os.path.join(tmp, os.path.splitext(source)[0] + ".s")
+        cmd = _base_cmd(extra_flags) + ["--offload-device-only", "-S", os.path.join(CSRC, source), "-o", asm]
         if verbose:
             print(" ".join(cmd))
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)

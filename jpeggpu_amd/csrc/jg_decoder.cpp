@@ -12,6 +12,7 @@
 #include "jg_kernels.hpp"
 #include "jg_reader.hpp"
 #include "jg_selftest_data.h"
+#include "jg_staging.hpp"
 
 #include <jpeggpu/jpeggpu.h>
 #include <jpeggpu/jpeggpu_ext.h>
@@ -25,7 +26,6 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
-#include <mutex>
 #include <thread>
 #include <new>
 #include <vector>
@@ -33,44 +33,6 @@
 namespace jg {
 
 namespace {
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-/// Host staging memory for the table blob: page-locked when a HIP device is present (so the copy
-/// enqueued by transfer is asynchronous), pageable otherwise (header parsing needs no GPU).
-struct StagingBuffer {
-    uint8_t* ptr  = nullptr;
-    size_t cap    = 0;
-    bool pinned   = false;
-
-    bool reserve(size_t n)
-    {
-        if (n <= cap) return true;
-        release();
-        const size_t want = align_up(n + n / 2, 4096);
-        void* p           = nullptr;
-        if (hipHostMalloc(&p, want, hipHostMallocDefault) == hipSuccess && p) {
-            pinned = true;
-        } else {
-            (void)hipGetLastError();
-            p      = std::malloc(want);
-            pinned = false;
-        }
-        if (!p) return false;
-        ptr = static_cast<uint8_t*>(p);
-        cap = want;
-        return true;
-    }
-    void release()
-    {
-        if (ptr) {
-            if (pinned) (void)hipHostFree(ptr);
-            else std::free(ptr);
-        }
-        ptr = nullptr;
-        cap = 0;
-    }
-};
 
 struct ScanPlan {
     // offsets inside the blob (and, shifted by off_blob, inside d_tmp)
@@ -806,248 +768,6 @@ jpeggpu_status do_decode(Decoder& d, jpeggpu_img* img, void* d_tmp, size_t tmp_s
 
 } // namespace
 
-namespace jg {
-namespace {
-
-// ------------------------------------------------------------------------------------------------
-// batched resize (jpeggpu_ext_resize_to_rgb): Pillow's weight tables, the items' descriptors, the scratch layout
-// ------------------------------------------------------------------------------------------------
-
-constexpr int kResizePrecision = 22; // fraction bits of a weight (Pillow's PRECISION_BITS for 8-bit images)
-
-double resize_support(int filter) { return filter == JPEGGPU_EXT_FILTER_BILINEAR ? 1.0 : 2.0; }
-
-/// Pillow's bilinear (triangle) and bicubic (a = -0.5) filters, term by term.
-double resize_filter(int filter, double x)
-{
-#pragma clang fp contract(off)
-    if (x < 0.0) x = -x;
-    if (filter == JPEGGPU_EXT_FILTER_BILINEAR) return x < 1.0 ? 1.0 - x : 0.0;
-    const double a = -0.5;
-    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-    return 0.0;
-}
-
-/// Pillow's ksize: the most taps an output coordinate of in -> out can get.
-int resize_max_taps(int in, int out, int filter)
-{
-#pragma clang fp contract(off)
-    const double scale = static_cast<double>(in) / out;
-    const double fs    = scale < 1.0 ? 1.0 : scale;
-    return static_cast<int>(std::ceil(resize_support(filter) * fs)) * 2 + 1;
-}
-
-/// Taps first .. first + count - 1 of output coordinate x.
-void resize_bounds(int in, int out, int filter, int x, int* first, int* count)
-{
-#pragma clang fp contract(off)
-    const double scale   = static_cast<double>(in) / out;
-    const double fs      = scale < 1.0 ? 1.0 : scale;
-    const double support = resize_support(filter) * fs;
-    const double center  = (x + 0.5) * scale;
-    const int lo         = std::max(static_cast<int>(center - support + 0.5), 0);
-    const int hi         = std::min(static_cast<int>(center + support + 0.5), in);
-    *first               = lo;
-    *count               = hi - lo;
-}
-
-/// The table of in -> out (in != out) into first / count / w[out][stride], stride >= resize_max_taps; Pillow's
-/// precompute_coeffs + normalize_coeffs_8bpc.
-void resize_table(int in, int out, int filter, int* first, int* count, int* w, int stride)
-{
-#pragma clang fp contract(off)
-    const double scale = static_cast<double>(in) / out;
-    const double fs    = scale < 1.0 ? 1.0 : scale;
-    const double ss    = 1.0 / fs;
-    const double one   = static_cast<double>(1 << kResizePrecision);
-    std::vector<double> k(static_cast<size_t>(stride));
-    for (int x = 0; x < out; ++x) {
-        int lo = 0, n = 0;
-        resize_bounds(in, out, filter, x, &lo, &n);
-        const double center = (x + 0.5) * scale;
-        double sum          = 0.0;
-        for (int j = 0; j < n; ++j) {
-            k[j] = resize_filter(filter, ((j + lo) - center + 0.5) * ss);
-            sum += k[j];
-        }
-        if (sum != 0.0)
-            for (int j = 0; j < n; ++j) k[j] /= sum;
-        first[x] = lo;
-        count[x] = n;
-        int* row = w + static_cast<size_t>(x) * stride;
-        for (int j = 0; j < stride; ++j)
-            row[j] = j >= n ? 0 : k[j] < 0 ? static_cast<int>(-0.5 + k[j] * one) : static_cast<int>(0.5 + k[j] * one);
-    }
-}
-
-/// A direction whose size does not change: one tap of weight 1 (Pillow skips the pass; the result is the same).
-void resize_identity(int size, int* first, int* count, int* w, int stride)
-{
-    for (int x = 0; x < size; ++x) {
-        first[x] = x;
-        count[x] = 1;
-        for (int j = 0; j < stride; ++j) w[static_cast<size_t>(x) * stride + j] = j == 0 ? 1 << kResizePrecision : 0;
-    }
-}
-
-int resize_taps(int in, int out, int filter) { return in == out ? 1 : resize_max_taps(in, out, filter); }
-
-/// Table bytes of one direction: {first, count}[out] + weights[out][taps]
-size_t resize_table_bytes(int in, int out, int filter)
-{
-    return sizeof(int) * static_cast<size_t>(out) * (2 + static_cast<size_t>(resize_taps(in, out, filter)));
-}
-
-/// One item's checks (those of jpeggpu_ext_crop_to_rgbi_fancy, the whole image standing in for a missing crop) and its
-/// descriptor, without the table and scratch pointers; `in_w` x `in_h` is the rectangle.
-jpeggpu_status resize_item(const jpeggpu_ext_resize_item& it, ResizeJob& job, int& in_w, int& in_h)
-{
-    const jpeggpu_img_info* info = it.info;
-    if (!info || !it.src) return JPEGGPU_INVALID_ARGUMENT;
-    const int nc = info->num_components;
-    if (nc != 1 && nc != 3) return JPEGGPU_NOT_SUPPORTED; // as jpeggpu_ext_planes_to_rgbi_fancy
-    int sx_max = 0, sy_max = 0;
-    for (int c = 0; c < nc; ++c) {
-        if (info->subsampling.x[c] < 1 || info->subsampling.y[c] < 1) return JPEGGPU_INVALID_ARGUMENT;
-        if (!it.src->image[c] || it.src->pitch[c] < info->sizes_x[c] || info->sizes_x[c] < 1 || info->sizes_y[c] < 1)
-            return JPEGGPU_INVALID_ARGUMENT;
-        sx_max = std::max(sx_max, info->subsampling.x[c]);
-        sy_max = std::max(sy_max, info->subsampling.y[c]);
-    }
-    for (int c = 0; c < nc; ++c) // libjpeg upsamples by integral ratios only (jdsample.c)
-        if (sx_max % info->subsampling.x[c] != 0 || sy_max % info->subsampling.y[c] != 0) return JPEGGPU_NOT_SUPPORTED;
-    jpeggpu_ext_crop_info ci{};
-    if (it.crop) {
-        ci = *it.crop;
-    } else { // the whole image: a plane of the largest factors has the image's extent
-        for (int c = 0; c < nc; ++c) {
-            if (info->subsampling.x[c] == sx_max) ci.width = info->sizes_x[c];
-            if (info->subsampling.y[c] == sy_max) ci.height = info->sizes_y[c];
-            ci.full_x[c] = info->sizes_x[c];
-            ci.full_y[c] = info->sizes_y[c];
-        }
-    }
-    if (ci.width <= 0 || ci.height <= 0 || ci.x < 0 || ci.y < 0) return JPEGGPU_INVALID_ARGUMENT;
-    for (int c = 0; c < nc; ++c) {
-        if (ci.origin_x[c] < 0 || ci.origin_y[c] < 0 || ci.origin_x[c] + info->sizes_x[c] > ci.full_x[c] ||
-            ci.origin_y[c] + info->sizes_y[c] > ci.full_y[c])
-            return JPEGGPU_INVALID_ARGUMENT; // the window must lie inside the plane
-        // every sample the rectangle reads, and its halo, clipped to the plane, is in the window
-        const int hr = sx_max / info->subsampling.x[c], vr = sy_max / info->subsampling.y[c];
-        const int lo_x = std::max(ci.x / hr - 1, 0), hi_x = std::min((ci.x + ci.width - 1) / hr + 1, ci.full_x[c] - 1);
-        const int lo_y = std::max(ci.y / vr - 1, 0), hi_y = std::min((ci.y + ci.height - 1) / vr + 1, ci.full_y[c] - 1);
-        if (lo_x < ci.origin_x[c] || hi_x >= ci.origin_x[c] + info->sizes_x[c] || lo_y < ci.origin_y[c] ||
-            hi_y >= ci.origin_y[c] + info->sizes_y[c])
-            return JPEGGPU_INVALID_ARGUMENT;
-    }
-    job = ResizeJob{};
-    for (int k = 0; k < 3; ++k) {
-        const int cc  = k < nc ? k : 0;
-        job.plane[k]  = it.src->image[cc];
-        job.pitch[k]  = it.src->pitch[cc];
-        job.w[k]      = info->sizes_x[cc];
-        job.h[k]      = info->sizes_y[cc];
-        job.hr[k]     = sx_max / info->subsampling.x[cc];
-        job.vr[k]     = sy_max / info->subsampling.y[cc];
-        job.mode[k]   = fancy_mode(job.hr[k], job.vr[k], ci.full_x[cc]); // on the FULL plane's width
-        job.ox[k]     = ci.origin_x[cc];
-        job.oy[k]     = ci.origin_y[cc];
-    }
-    job.x     = ci.x;
-    job.y     = ci.y;
-    job.ncomp = nc;
-    in_w      = ci.width;
-    in_h      = ci.height;
-    return JPEGGPU_SUCCESS;
-}
-
-/// Where everything of one call sits in d_scratch: the descriptors, each item's first tile, the tables (together the
-/// part the host stages and copies, `head` bytes), then each item's horizontal-pass rows.
-struct ResizePlan {
-    std::vector<ResizeJob> jobs;
-    std::vector<int> first_tile, in_w, in_h;
-    std::vector<size_t> off_tab_x, off_tab_y, off_mid;
-    size_t off_first = 0, head = 0, total = 0;
-    int h_tiles      = 0;
-};
-
-jpeggpu_status plan_resize(
-    const jpeggpu_ext_resize_item* items, int n, int out_w, int out_h, int filter, ResizePlan& p)
-{
-    if (!items || n <= 0 || n > 65535 || out_w <= 0 || out_h <= 0) return JPEGGPU_INVALID_ARGUMENT;
-    if (filter != JPEGGPU_EXT_FILTER_BILINEAR && filter != JPEGGPU_EXT_FILTER_BICUBIC) return JPEGGPU_NOT_SUPPORTED;
-    try {
-        p.jobs.resize(n);
-        p.first_tile.resize(n);
-        p.in_w.resize(n);
-        p.in_h.resize(n);
-        p.off_tab_x.resize(n);
-        p.off_tab_y.resize(n);
-        p.off_mid.resize(n);
-    } catch (const std::bad_alloc&) {
-        return JPEGGPU_OUT_OF_HOST_MEMORY;
-    }
-    size_t off     = align_up(sizeof(ResizeJob) * n, 256);
-    p.off_first    = off;
-    off            = align_up(off + sizeof(int) * n, 256);
-    int64_t tiles  = 0;
-    const int pitch = static_cast<int>(align_up(3 * static_cast<size_t>(out_w), 16));
-    for (int i = 0; i < n; ++i) {
-        const jpeggpu_status st = resize_item(items[i], p.jobs[i], p.in_w[i], p.in_h[i]);
-        if (st != JPEGGPU_SUCCESS) return st;
-        p.off_tab_x[i] = off;
-        off += align_up(resize_table_bytes(p.in_w[i], out_w, filter), 16);
-        p.off_tab_y[i] = off;
-        off += align_up(resize_table_bytes(p.in_h[i], out_h, filter), 16);
-        // the rectangle rows the vertical taps read (all of them when the height does not change)
-        ResizeJob& j = p.jobs[i];
-        j.taps_x     = resize_taps(p.in_w[i], out_w, filter);
-        j.taps_y     = resize_taps(p.in_h[i], out_h, filter);
-        j.mid_pitch  = pitch;
-        if (p.in_h[i] == out_h) {
-            j.row0 = 0;
-            j.rows = out_h;
-        } else {
-            int f0 = 0, n0 = 0, f1 = 0, n1 = 0;
-            resize_bounds(p.in_h[i], out_h, filter, 0, &f0, &n0);
-            resize_bounds(p.in_h[i], out_h, filter, out_h - 1, &f1, &n1);
-            j.row0 = f0;
-            j.rows = f1 + n1 - f0;
-        }
-        p.first_tile[i] = static_cast<int>(tiles);
-        tiles += resize_h_tiles(j.rows, out_w);
-        if (tiles > INT32_MAX) return JPEGGPU_INVALID_ARGUMENT;
-    }
-    p.head  = off;
-    p.h_tiles = static_cast<int>(tiles);
-    for (int i = 0; i < n; ++i) {
-        p.off_mid[i] = off;
-        off          = align_up(off + static_cast<size_t>(p.jobs[i].rows) * pitch, 256);
-    }
-    p.total = off + 256; // room to align the caller's pointer
-    return JPEGGPU_SUCCESS;
-}
-
-/// Page-locked staging of the descriptors and tables: a ring of four per process, as the batch handle keeps its own.
-/// Never destroyed (the HIP runtime may be gone when static objects are).
-struct ResizeStaging {
-    static constexpr int kRing = 4;
-    std::mutex mu;
-    StagingBuffer buf[kRing];
-    hipEvent_t copied[kRing] = {};
-    bool in_use[kRing]       = {};
-    int next                 = 0;
-};
-ResizeStaging& resize_staging()
-{
-    static ResizeStaging* s = new ResizeStaging;
-    return *s;
-}
-
-} // namespace
-} // namespace jg
-
 extern "C" {
 
 const char* jpeggpu_get_status_string(enum jpeggpu_status stat)
@@ -1761,146 +1481,6 @@ enum jpeggpu_status jpeggpu_ext_batch_get_stage_ms(jpeggpu_batch_t batch, float*
     return JPEGGPU_SUCCESS;
 }
 
-enum jpeggpu_status jpeggpu_ext_upsample_planes(
-    const struct jpeggpu_img_info* info,
-    const struct jpeggpu_img* src,
-    struct jpeggpu_img* dst,
-    int width,
-    int height,
-    jpeggpu_stream_t stream)
-{
-    if (!info || !src || !dst || width <= 0 || height <= 0) return JPEGGPU_INVALID_ARGUMENT;
-    const int nc = info->num_components;
-    if (nc < 1 || nc > JPEGGPU_MAX_COMP) return JPEGGPU_INVALID_ARGUMENT;
-    int sx_max = 0, sy_max = 0;
-    for (int c = 0; c < nc; ++c) {
-        if (info->subsampling.x[c] < 1 || info->subsampling.y[c] < 1) return JPEGGPU_INVALID_ARGUMENT;
-        sx_max = info->subsampling.x[c] > sx_max ? info->subsampling.x[c] : sx_max;
-        sy_max = info->subsampling.y[c] > sy_max ? info->subsampling.y[c] : sy_max;
-    }
-    for (int c = 0; c < nc; ++c) {
-        if (!src->image[c] || !dst->image[c] || dst->pitch[c] < width || src->pitch[c] < info->sizes_x[c])
-            return JPEGGPU_INVALID_ARGUMENT;
-        const hipError_t err = jg::launch_upsample(
-            src->image[c], src->pitch[c], info->sizes_x[c], info->sizes_y[c],
-            dst->image[c], dst->pitch[c], width, height,
-            info->subsampling.x[c], sx_max, info->subsampling.y[c], sy_max, stream);
-        if (err != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
-    }
-    return JPEGGPU_SUCCESS;
-}
-
-enum jpeggpu_status jpeggpu_ext_planes_to_rgbi(
-    const struct jpeggpu_img_info* info,
-    const struct jpeggpu_img* src,
-    uint8_t* dst,
-    int dst_pitch,
-    int width,
-    int height,
-    jpeggpu_stream_t stream)
-{
-    if (!info || !src || !dst || width <= 0 || height <= 0 || dst_pitch < 3 * width) return JPEGGPU_INVALID_ARGUMENT;
-    const int nc = info->num_components;
-    if (nc != 1 && nc != 3) return JPEGGPU_NOT_SUPPORTED; // as the reference's helper (util/util.h:42-45)
-    int sx_max = 0, sy_max = 0;
-    for (int c = 0; c < nc; ++c) {
-        if (info->subsampling.x[c] < 1 || info->subsampling.y[c] < 1) return JPEGGPU_INVALID_ARGUMENT;
-        if (!src->image[c] || src->pitch[c] < info->sizes_x[c]) return JPEGGPU_INVALID_ARGUMENT;
-        sx_max = info->subsampling.x[c] > sx_max ? info->subsampling.x[c] : sx_max;
-        sy_max = info->subsampling.y[c] > sy_max ? info->subsampling.y[c] : sy_max;
-    }
-    const hipError_t err = jg::launch_rgbi(
-        src->image, src->pitch, info->sizes_x, info->sizes_y, info->subsampling.x, info->subsampling.y,
-        sx_max, sy_max, nc, dst, dst_pitch, width, height, stream);
-    return err == hipSuccess ? JPEGGPU_SUCCESS : JPEGGPU_INTERNAL_ERROR;
-}
-
-namespace {
-enum jpeggpu_status planes_to_rgbi_libjpeg(
-    const struct jpeggpu_img_info* info, const struct jpeggpu_img* src, uint8_t* dst, int dst_pitch, int width, int height,
-    jpeggpu_stream_t stream, bool replicate)
-{
-    if (!info || !src || !dst || width <= 0 || height <= 0 || dst_pitch < 3 * width) return JPEGGPU_INVALID_ARGUMENT;
-    const int nc = info->num_components;
-    if (nc != 1 && nc != 3) return JPEGGPU_NOT_SUPPORTED; // as jpeggpu_ext_planes_to_rgbi
-    int sx_max = 0, sy_max = 0;
-    for (int c = 0; c < nc; ++c) {
-        if (info->subsampling.x[c] < 1 || info->subsampling.y[c] < 1) return JPEGGPU_INVALID_ARGUMENT;
-        if (!src->image[c] || src->pitch[c] < info->sizes_x[c] || info->sizes_x[c] < 1 || info->sizes_y[c] < 1) return JPEGGPU_INVALID_ARGUMENT;
-        sx_max = info->subsampling.x[c] > sx_max ? info->subsampling.x[c] : sx_max;
-        sy_max = info->subsampling.y[c] > sy_max ? info->subsampling.y[c] : sy_max;
-    }
-    for (int c = 0; c < nc; ++c) // libjpeg upsamples by integral ratios only (jdsample.c)
-        if (sx_max % info->subsampling.x[c] != 0 || sy_max % info->subsampling.y[c] != 0) return JPEGGPU_NOT_SUPPORTED;
-    const hipError_t err = jg::launch_rgbi_fancy(
-        src->image, src->pitch, info->sizes_x, info->sizes_y, info->subsampling.x, info->subsampling.y,
-        sx_max, sy_max, nc, dst, dst_pitch, width, height, stream, replicate);
-    return err == hipSuccess ? JPEGGPU_SUCCESS : JPEGGPU_INTERNAL_ERROR;
-}
-
-enum jpeggpu_status crop_to_rgbi_libjpeg(
-    const struct jpeggpu_img_info* info, const struct jpeggpu_ext_crop_info* crop, const struct jpeggpu_img* src, uint8_t* dst,
-    int dst_pitch, jpeggpu_stream_t stream, bool replicate)
-{
-    if (!info || !crop || !src || !dst || crop->width <= 0 || crop->height <= 0 || crop->x < 0 || crop->y < 0 || dst_pitch < 3 * crop->width)
-        return JPEGGPU_INVALID_ARGUMENT;
-    const int nc = info->num_components;
-    if (nc != 1 && nc != 3) return JPEGGPU_NOT_SUPPORTED; // as jpeggpu_ext_planes_to_rgbi_fancy
-    int sx_max = 0, sy_max = 0;
-    for (int c = 0; c < nc; ++c) {
-        if (info->subsampling.x[c] < 1 || info->subsampling.y[c] < 1) return JPEGGPU_INVALID_ARGUMENT;
-        if (!src->image[c] || src->pitch[c] < info->sizes_x[c] || info->sizes_x[c] < 1 || info->sizes_y[c] < 1) return JPEGGPU_INVALID_ARGUMENT;
-        if (crop->origin_x[c] < 0 || crop->origin_y[c] < 0 || crop->origin_x[c] + info->sizes_x[c] > crop->full_x[c] ||
-            crop->origin_y[c] + info->sizes_y[c] > crop->full_y[c])
-            return JPEGGPU_INVALID_ARGUMENT; // the window must lie inside the plane
-        sx_max = info->subsampling.x[c] > sx_max ? info->subsampling.x[c] : sx_max;
-        sy_max = info->subsampling.y[c] > sy_max ? info->subsampling.y[c] : sy_max;
-    }
-    for (int c = 0; c < nc; ++c) // libjpeg upsamples by integral ratios only (jdsample.c)
-        if (sx_max % info->subsampling.x[c] != 0 || sy_max % info->subsampling.y[c] != 0) return JPEGGPU_NOT_SUPPORTED;
-    for (int c = 0; c < nc; ++c) { // every sample the rectangle reads, and its halo, clipped to the plane, is in the window
-        const int hr = sx_max / info->subsampling.x[c], vr = sy_max / info->subsampling.y[c];
-        const int lo_x = std::max(crop->x / hr - 1, 0), hi_x = std::min((crop->x + crop->width - 1) / hr + 1, crop->full_x[c] - 1);
-        const int lo_y = std::max(crop->y / vr - 1, 0), hi_y = std::min((crop->y + crop->height - 1) / vr + 1, crop->full_y[c] - 1);
-        if (lo_x < crop->origin_x[c] || hi_x >= crop->origin_x[c] + info->sizes_x[c] || lo_y < crop->origin_y[c] ||
-            hi_y >= crop->origin_y[c] + info->sizes_y[c])
-            return JPEGGPU_INVALID_ARGUMENT;
-    }
-    const hipError_t err = jg::launch_crop_rgbi_fancy(
-        src->image, src->pitch, info->sizes_x, info->sizes_y, crop->origin_x, crop->origin_y, crop->full_x, info->subsampling.x,
-        info->subsampling.y, sx_max, sy_max, nc, crop->x, crop->y, dst, dst_pitch, crop->width, crop->height, stream, replicate);
-    return err == hipSuccess ? JPEGGPU_SUCCESS : JPEGGPU_INTERNAL_ERROR;
-}
-} // namespace
-
-enum jpeggpu_status jpeggpu_ext_planes_to_rgbi_fancy(
-    const struct jpeggpu_img_info* info, const struct jpeggpu_img* src, uint8_t* dst, int dst_pitch, int width, int height,
-    jpeggpu_stream_t stream)
-{
-    return planes_to_rgbi_libjpeg(info, src, dst, dst_pitch, width, height, stream, false);
-}
-
-enum jpeggpu_status jpeggpu_ext_planes_to_rgbi_replicate(
-    const struct jpeggpu_img_info* info, const struct jpeggpu_img* src, uint8_t* dst, int dst_pitch, int width, int height,
-    jpeggpu_stream_t stream)
-{
-    return planes_to_rgbi_libjpeg(info, src, dst, dst_pitch, width, height, stream, true);
-}
-
-enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_fancy(
-    const struct jpeggpu_img_info* info, const struct jpeggpu_ext_crop_info* crop, const struct jpeggpu_img* src, uint8_t* dst,
-    int dst_pitch, jpeggpu_stream_t stream)
-{
-    return crop_to_rgbi_libjpeg(info, crop, src, dst, dst_pitch, stream, false);
-}
-
-enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_replicate(
-    const struct jpeggpu_img_info* info, const struct jpeggpu_ext_crop_info* crop, const struct jpeggpu_img* src, uint8_t* dst,
-    int dst_pitch, jpeggpu_stream_t stream)
-{
-    return crop_to_rgbi_libjpeg(info, crop, src, dst, dst_pitch, stream, true);
-}
-
 enum jpeggpu_status jpeggpu_ext_self_test(jpeggpu_stream_t stream)
 {
     // One small decode through the public calls, planes hashed against constants. The write pass refills its bit window
@@ -1984,90 +1564,6 @@ enum jpeggpu_status jpeggpu_ext_parse_headers(
     for (int i = 0; i < num_items; ++i)
         if (statuses[i] != JPEGGPU_SUCCESS) return statuses[i];
     return JPEGGPU_SUCCESS;
-}
-
-size_t jpeggpu_ext_resize_scratch_size(
-    const struct jpeggpu_ext_resize_item* items, int n, int out_w, int out_h, enum jpeggpu_ext_filter filter)
-{
-    jg::ResizePlan p;
-    return jg::plan_resize(items, n, out_w, out_h, filter, p) == JPEGGPU_SUCCESS ? p.total : 0;
-}
-
-enum jpeggpu_status jpeggpu_ext_resize_weights(
-    int in, int out, enum jpeggpu_ext_filter filter, int* first, int* count, int* weights, int max_taps)
-{
-    if (filter != JPEGGPU_EXT_FILTER_BILINEAR && filter != JPEGGPU_EXT_FILTER_BICUBIC) return JPEGGPU_NOT_SUPPORTED;
-    if (!first || !count || !weights || in <= 0 || out <= 0 || max_taps < jg::resize_max_taps(in, out, filter))
-        return JPEGGPU_INVALID_ARGUMENT;
-    try {
-        if (in == out) jg::resize_identity(out, first, count, weights, max_taps);
-        else jg::resize_table(in, out, filter, first, count, weights, max_taps);
-    } catch (const std::bad_alloc&) {
-        return JPEGGPU_OUT_OF_HOST_MEMORY;
-    }
-    return JPEGGPU_SUCCESS;
-}
-
-enum jpeggpu_status jpeggpu_ext_resize_to_rgb(
-    const struct jpeggpu_ext_resize_item* items,
-    int n,
-    int out_w,
-    int out_h,
-    enum jpeggpu_ext_filter filter,
-    enum jpeggpu_ext_output_layout layout,
-    uint8_t* dst,
-    void* d_scratch,
-    size_t scratch_size,
-    jpeggpu_stream_t stream)
-{
-    jg::ResizePlan p;
-    const jpeggpu_status st = jg::plan_resize(items, n, out_w, out_h, filter, p);
-    if (st != JPEGGPU_SUCCESS) return st;
-    if (!dst || !d_scratch || (layout != JPEGGPU_EXT_NHWC && layout != JPEGGPU_EXT_NCHW) || scratch_size < p.total)
-        return JPEGGPU_INVALID_ARGUMENT;
-    uint8_t* base = reinterpret_cast<uint8_t*>(jg::align_up(reinterpret_cast<uintptr_t>(d_scratch), 256));
-    jg::ResizeStaging& rs = jg::resize_staging();
-    std::lock_guard<std::mutex> lock(rs.mu);
-    const int r = rs.next;
-    // the staging buffer may still be the source of a copy enqueued kRing calls ago
-    if (rs.in_use[r] && hipEventSynchronize(rs.copied[r]) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
-    rs.in_use[r] = false;
-    if (!rs.buf[r].reserve(p.head)) return JPEGGPU_OUT_OF_HOST_MEMORY;
-    uint8_t* h = rs.buf[r].ptr;
-    try {
-        for (int i = 0; i < n; ++i) {
-            jg::ResizeJob& j = p.jobs[i];
-            j.tab_x          = reinterpret_cast<const int*>(base + p.off_tab_x[i]);
-            j.tab_y          = reinterpret_cast<const int*>(base + p.off_tab_y[i]);
-            j.mid            = base + p.off_mid[i];
-            const int dims[2][3] = {{p.in_w[i], out_w, j.taps_x}, {p.in_h[i], out_h, j.taps_y}};
-            const size_t offs[2] = {p.off_tab_x[i], p.off_tab_y[i]};
-            for (int d = 0; d < 2; ++d) {
-                const int in = dims[d][0], out = dims[d][1], taps = dims[d][2];
-                std::vector<int> fc(2 * static_cast<size_t>(out)), cnt(out);
-                int* t = reinterpret_cast<int*>(h + offs[d]);
-                if (in == out) jg::resize_identity(out, fc.data(), cnt.data(), t + 2 * out, taps);
-                else jg::resize_table(in, out, filter, fc.data(), cnt.data(), t + 2 * out, taps);
-                for (int x = 0; x < out; ++x) {
-                    t[2 * x]     = fc[x];
-                    t[2 * x + 1] = cnt[x];
-                }
-            }
-        }
-    } catch (const std::bad_alloc&) {
-        return JPEGGPU_OUT_OF_HOST_MEMORY;
-    }
-    std::memcpy(h, p.jobs.data(), sizeof(jg::ResizeJob) * n);
-    std::memcpy(h + p.off_first, p.first_tile.data(), sizeof(int) * n);
-    if (!rs.copied[r] && hipEventCreateWithFlags(&rs.copied[r], hipEventDisableTiming) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
-    if (hipMemcpyAsync(base, h, p.head, hipMemcpyHostToDevice, stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
-    if (hipEventRecord(rs.copied[r], stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
-    rs.in_use[r] = true;
-    rs.next      = (r + 1) % jg::ResizeStaging::kRing;
-    const hipError_t err = jg::launch_resize(
-        reinterpret_cast<const jg::ResizeJob*>(base), reinterpret_cast<const int*>(base + p.off_first), n, p.h_tiles, out_w, out_h,
-        layout, dst, stream);
-    return err == hipSuccess ? JPEGGPU_SUCCESS : JPEGGPU_INTERNAL_ERROR;
 }
 
 } // extern "C"

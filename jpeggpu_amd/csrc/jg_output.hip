@@ -1,0 +1,405 @@
+// jg_output.hip -- gfx950 (CDNA4, wave64) kernels of the RGB output stage: from decoded planes to what a caller looks at.
+//
+//   upsample_kernel         nearest-neighbour chroma replication, planes to planes
+//   rgbi_kernel             replication + the JFIF matrix in float -> interleaved RGB (the reference's conv_to_rgbi)
+//   fancy_rgbi_kernel       libjpeg's fancy chroma upsampling + integer YCbCr -> interleaved RGB (jdsample.c, jdcolor.c),
+//                           of a whole image (<false>) or of a rectangle read from the planes' windows (<true>)
+//   resize_h_kernel /       batched resize to one size with Pillow's BILINEAR / BICUBIC arithmetic: the horizontal taps
+//   resize_v_kernel         straight from the planes' windows (fancy RGB in LDS), then the vertical taps (jpeggpu_ext_resize_to_rgb)
+//
+// Nothing here is shared with the decode path (jg_kernels.hip): the stage reads finished planes.
+#include "jg_output.hpp"
+
+#include <hip/hip_runtime.h>
+
+namespace jg {
+
+namespace {
+
+/// The 4-pixel store of every RGB kernel: R, G, B of `np` (1..4) consecutive pixels, out[3 * i + c], to `drow`. Three
+/// dwords when all four pixels are there and `drow` is aligned (a wave then writes 768 contiguous bytes), bytes otherwise.
+__device__ __forceinline__ void store_rgb4(uint8_t* drow, const uint32_t (&out)[12], int np)
+{
+    if (np == 4 && (reinterpret_cast<uintptr_t>(drow) & 3) == 0) {
+        uint32_t* d = reinterpret_cast<uint32_t*>(drow);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) d[k] = out[4 * k] | out[4 * k + 1] << 8 | out[4 * k + 2] << 16 | out[4 * k + 3] << 24;
+    } else {
+        for (int i = 0; i < 3 * np; ++i) drow[i] = static_cast<uint8_t>(out[i]);
+    }
+}
+
+/// Chroma replication: each lane produces 4 consecutive output pixels of one row.
+__global__ __launch_bounds__(256) void upsample_kernel(
+    const uint8_t* __restrict__ src, int src_pitch, int src_w, int src_h,
+    uint8_t* __restrict__ dst, int dst_pitch, int dst_w, int dst_h,
+    int num_x, int den_x, int num_y, int den_y)
+{
+    const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    const int y  = blockIdx.y;
+    if (x0 >= dst_w || y >= dst_h) return;
+    const int sy        = min(y * num_y / den_y, src_h - 1);
+    const uint8_t* srow = src + static_cast<size_t>(sy) * src_pitch;
+    uint8_t* drow       = dst + static_cast<size_t>(y) * dst_pitch + x0;
+    uint32_t px[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) px[i] = srow[min((x0 + i) * num_x / den_x, src_w - 1)];
+    if (x0 + 4 <= dst_w && (reinterpret_cast<uintptr_t>(drow) & 3) == 0) {
+        *reinterpret_cast<uint32_t*>(drow) = px[0] | px[1] << 8 | px[2] << 16 | px[3] << 24;
+    } else {
+        for (int i = 0; i < 4 && x0 + i < dst_w; ++i) drow[i] = static_cast<uint8_t>(px[i]);
+    }
+}
+
+/// Chroma replication + YCbCr -> RGB, interleaved 8-bit output; the arithmetic of the reference's host
+/// helper `conv_to_rgbi` (util/util.h:62-104): nearest-neighbour replication, the JFIF matrix in float,
+/// roundf, clamp. Each lane produces 4 consecutive pixels (12 bytes) of one row. With one component the
+/// sample is copied to R, G and B (util.h:47-58).
+struct RgbiParams {
+    const uint8_t* plane[3];
+    int pitch[3], w[3], h[3];
+    int num_x[3], num_y[3]; // sampling factors; the maxima are the denominators
+    int den_x, den_y;
+    int ncomp;
+};
+
+__global__ __launch_bounds__(256) void rgbi_kernel(RgbiParams p, uint8_t* __restrict__ dst, int dst_pitch, int width, int height)
+{
+    const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    const int y  = blockIdx.y;
+    if (x0 >= width || y >= height) return;
+    uint32_t out[12];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int x = min(x0 + i, width - 1);
+        float v[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int cc = c < p.ncomp ? c : 0;
+            const int sy = min(y * p.num_y[cc] / p.den_y, p.h[cc] - 1);
+            const int sx = min(x * p.num_x[cc] / p.den_x, p.w[cc] - 1);
+            v[c]         = static_cast<float>(p.plane[cc][static_cast<size_t>(sy) * p.pitch[cc] + sx]);
+        }
+        float r = v[0], g = v[0], b = v[0];
+        if (p.ncomp == 3) {
+            r = v[0] + 1.402f * (v[2] - 128.f);
+            g = v[0] - .344136f * (v[1] - 128.f) - .714136f * (v[2] - 128.f);
+            b = v[0] + 1.772f * (v[1] - 128.f);
+        }
+        out[3 * i + 0] = static_cast<uint32_t>(fmaxf(0.f, fminf(roundf(r), 255.f)));
+        out[3 * i + 1] = static_cast<uint32_t>(fmaxf(0.f, fminf(roundf(g), 255.f)));
+        out[3 * i + 2] = static_cast<uint32_t>(fmaxf(0.f, fminf(roundf(b), 255.f)));
+    }
+    store_rgb4(dst + static_cast<size_t>(y) * dst_pitch + static_cast<size_t>(x0) * 3, out, min(4, width - x0));
+}
+
+// ------------------------------------------------------------------------------------------------
+// libjpeg's fancy upsampling (jdsample.c, do_fancy_upsampling) + its integer YCbCr -> RGB (jdcolor.c, ycc_rgb_convert):
+// what libjpeg-turbo gives a caller that asks for JCS_RGB. Per component, by the ratio of the largest sampling factors to
+// its own (FancyComp::mode, chosen on the host): a copy or replication (int_upsample), h2v1_fancy_upsample,
+// h2v2_fancy_upsample or h1v2_fancy_upsample. Samples outside the plane -- the column left of the first and right of the
+// last, the row above the first and below the last -- are copies of the edge samples, which is what libjpeg's edge
+// formulas and context rows amount to; the plane's extent is libjpeg's downsampled_width / downsampled_height
+// (jpeggpu_decoder_parse_header's sizes), so no padding sample is read.
+//
+// Three steps, each written once: fancy_stage puts the samples under a tile of image pixels, with a one-sample halo, in
+// LDS; fancy_pixel makes the RGB of one image pixel from the staged tiles; store_rgb4 writes four of them.
+// ------------------------------------------------------------------------------------------------
+
+constexpr int kFancyTileW = 256, kFancyTileH = 8;
+constexpr int kFancyLdsW = kFancyTileW + 4, kFancyLdsH = kFancyTileH + 2; // samples under a tile at ratio 1, with the halo
+using FancyTile  = uint8_t[kFancyLdsH][kFancyLdsW];
+using FancyTiles = FancyTile[3];
+
+/// Stage the samples under the image pixels (ix0, iy0) .. (ix0 + cw - 1, iy0 + ch - 1), cw <= kFancyTileW and ch <=
+/// kFancyTileH: per component, samples floor(ix0 / hr) - 1 .. floor((ix0 + cw - 1) / hr) + 1 and the rows alike, at most
+/// 256 + 2 columns and 8 + 2 rows (ratio 1). (bx, by)[k]: full-plane coordinates of tiles[k][0][0]. The loads are clamped
+/// to the window: that is the edge rule. `kWindowed` false: the windows are the full planes (origin 0), a compile-time
+/// fact. The caller's barrier makes the tiles visible.
+template <bool kWindowed>
+__device__ __forceinline__ void fancy_stage(const FancySource& s, FancyTiles& tiles, int ix0, int iy0, int cw, int ch, int (&bx)[3], int (&by)[3])
+{
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const FancyComp& c = s.comp[k];
+        bx[k] = ix0 / c.hr - 1;
+        by[k] = iy0 / c.vr - 1;
+        if (k >= s.ncomp) continue;
+        const int nx = (ix0 + cw - 1) / c.hr + 2 - bx[k], ny = (iy0 + ch - 1) / c.vr + 2 - by[k];
+        const int ox = kWindowed ? c.ox : 0, oy = kWindowed ? c.oy : 0;
+        for (int j = 0; j < ny; ++j) {
+            const uint8_t* row = c.plane + static_cast<size_t>(min(max(by[k] + j - oy, 0), c.h - 1)) * c.pitch;
+            for (int i = t; i < nx; i += 256) tiles[k][j][i] = row[min(max(bx[k] + i - ox, 0), c.w - 1)];
+        }
+    }
+}
+
+/// The upsampled value of image pixel (x, y) of a staged component; (bx, by): full-plane coordinates of t[0][0].
+__device__ __forceinline__ int fancy_sample(const FancyComp& c, const FancyTile& t, int bx, int by, int x, int y)
+{
+    switch (c.mode) {
+    case kFancyH2V1: {
+        const int i = (x >> 1) - bx, j = y - by, odd = x & 1;
+        return (3 * t[j][i] + t[j][odd ? i + 1 : i - 1] + 1 + odd) >> 2;
+    }
+    case kFancyH2V2: {
+        const int i = (x >> 1) - bx, j = (y >> 1) - by, odd = x & 1, dj = (y & 1) ? 1 : -1, di = odd ? 1 : -1;
+        const int here = 3 * t[j][i] + t[j + dj][i];      // column sums: 3 near + far row
+        const int side = 3 * t[j][i + di] + t[j + dj][i + di];
+        return (3 * here + side + 8 - odd) >> 4;
+    }
+    case kFancyH1V2: {
+        const int i = x - bx, j = (y >> 1) - by, below = y & 1;
+        return (3 * t[j][i] + t[below ? j + 1 : j - 1][i] + 1 + below) >> 2;
+    }
+    default: return t[y / c.vr - by][x / c.hr - bx];
+    }
+}
+
+__device__ __forceinline__ uint32_t clamp255(int v) { return static_cast<uint32_t>(min(max(v, 0), 255)); }
+
+/// R, G, B of image pixel (x, y) from the staged tiles: jdcolor.c's ycc_rgb_convert, or the grey sample three times.
+__device__ __forceinline__ void fancy_pixel(const FancySource& s, const FancyTiles& tiles, const int (&bx)[3], const int (&by)[3], int x, int y, uint32_t* rgb)
+{
+    const int Y = fancy_sample(s.comp[0], tiles[0], bx[0], by[0], x, y);
+    if (s.ncomp == 3) {
+        const int cb = fancy_sample(s.comp[1], tiles[1], bx[1], by[1], x, y) - 128;
+        const int cr = fancy_sample(s.comp[2], tiles[2], bx[2], by[2], x, y) - 128;
+        rgb[0] = clamp255(Y + ((91881 * cr + (1 << 15)) >> 16));                // FIX(1.40200)
+        rgb[1] = clamp255(Y + ((-22554 * cb - 46802 * cr + (1 << 15)) >> 16)); // FIX(0.34414), FIX(0.71414)
+        rgb[2] = clamp255(Y + ((116130 * cb + (1 << 15)) >> 16));               // FIX(1.77200)
+    } else {
+        rgb[0] = rgb[1] = rgb[2] = static_cast<uint32_t>(Y);
+    }
+}
+
+/// Interleaved 8-bit RGB of the source's rectangle: output pixel (x, y) is image pixel (x + p.x, y + p.y). One
+/// workgroup: an output tile of kFancyTileW x kFancyTileH pixels; each lane converts a 2 x 4 quad -- 4 pixels of 2 rows
+/// -- and stores each row's 12 bytes. `kWindowed` false is the whole image, whose window and rectangle terms are zero
+/// and cost nothing.
+template <bool kWindowed>
+__global__ __launch_bounds__(256) void fancy_rgbi_kernel(FancySource p, uint8_t* __restrict__ dst, int dst_pitch, int width, int height)
+{
+    __shared__ FancyTiles s_t;
+    const int t  = threadIdx.x;
+    const int x0 = blockIdx.x * kFancyTileW, y0 = blockIdx.y * kFancyTileH;
+    const int px = kWindowed ? p.x : 0, py = kWindowed ? p.y : 0;
+    int bx[3], by[3];
+    fancy_stage<kWindowed>(p, s_t, x0 + px, y0 + py, kFancyTileW, kFancyTileH, bx, by);
+    __syncthreads();
+    const int x = x0 + 4 * (t & 63);
+    if (x >= width) return;
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+        const int y = y0 + 2 * (t >> 6) + dy;
+        if (y >= height) break;
+        uint32_t out[12];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) fancy_pixel(p, s_t, bx, by, min(x + i, width - 1) + px, y + py, &out[3 * i]);
+        store_rgb4(dst + static_cast<size_t>(y) * dst_pitch + static_cast<size_t>(x) * 3, out, min(4, width - x));
+    }
+}
+
+/// Taps of a horizontal-pass workgroup's columns: int32 weights[columns][taps], from LDS when they fit
+/// (kResizeLdsTaps per column) or else straight from the table; RGB of a chunk: one dword (R | G << 8 | B << 16) per pixel.
+/// A product of a weight (|w| < 2^23: normalised weights stay below 1.2) and a sample fits v_mul_i32_i24.
+constexpr int kResizeLdsTaps = 64;
+template <class W>
+__device__ __forceinline__ void resize_taps_h(const W* w, const uint32_t* px, int j0, int j1, int (&acc)[3])
+{
+#pragma unroll 4
+    for (int j = j0; j < j1; ++j) {
+        const int wj = w[j];
+        const uint32_t v = px[j];
+        acc[0] += __mul24(wj, static_cast<int>(v & 255u));
+        acc[1] += __mul24(wj, static_cast<int>((v >> 8) & 255u));
+        acc[2] += __mul24(wj, static_cast<int>((v >> 16) & 255u));
+    }
+}
+
+/// Batched resize (jpeggpu_ext_resize_to_rgb), pass 1: the horizontal taps, read from the planes' windows. A workgroup
+/// owns kResizeHTileW output columns of kResizeHTileH rectangle rows of one item (found by a search of the items' first
+/// tiles). The input columns those columns' taps read are converted to RGB in chunks of up to kFancyTileW: the window
+/// samples under a chunk are staged with their halo (fancy_stage), each pixel gets fancy_pixel into LDS, and each lane
+/// accumulates its output pixel's taps that fall in the chunk. The result is clamped to uint8 (Pillow keeps its
+/// intermediate image in 8 bits) and written to the item's `mid` rows; the crop's full-resolution RGB never leaves LDS.
+__global__ __launch_bounds__(256) void resize_h_kernel(const ResizeJob* __restrict__ jobs, const int* __restrict__ first_tile, int n, int out_w)
+{
+    __shared__ FancyTiles s_t;
+    __shared__ uint32_t s_rgb[kResizeHTileH][kFancyTileW];
+    __shared__ int s_w[kResizeHTileW * kResizeLdsTaps];
+    const int b = blockIdx.x;
+    int lo = 0, hi = n - 1; // the last item whose first tile is <= b
+    while (lo < hi) {
+        const int m = (lo + hi + 1) >> 1;
+        if (first_tile[m] <= b) lo = m;
+        else hi = m - 1;
+    }
+    const ResizeJob& J = jobs[lo];
+    const int col_tiles = (out_w + kResizeHTileW - 1) / kResizeHTileW;
+    const int tile = b - first_tile[lo], ty = tile / col_tiles, tx = tile - ty * col_tiles;
+    const int r0 = J.row0 + ty * kResizeHTileH;                  // the tile's first rectangle row
+    const int nr = min(kResizeHTileH, J.row0 + J.rows - r0);
+    const int ox0 = tx * kResizeHTileW, ox1 = min(ox0 + kResizeHTileW, out_w) - 1;
+    const int* __restrict__ tab = J.tab_x;
+    const int a = tab[2 * ox0], e = tab[2 * ox1] + tab[2 * ox1 + 1]; // input columns [a, e) (first and last are monotone)
+    const FancySource& src = J.src;
+    const int t = threadIdx.x, r = t / kResizeHTileW, col = t % kResizeHTileW, ox = ox0 + col;
+    const bool mine = r < nr && ox < out_w;
+    const int taps = J.taps_x;
+    const bool lds_w = taps <= kResizeLdsTaps;
+    const int* __restrict__ wts = tab + 2 * out_w + static_cast<size_t>(ox0) * taps; // the tile's columns are consecutive
+    if (lds_w) // made visible by the chunk loop's first barrier
+        for (int q = t; q < (ox1 - ox0 + 1) * taps; q += 256) s_w[q] = wts[q];
+    int f = 0, cnt = 0;
+    if (mine) {
+        f   = tab[2 * ox];
+        cnt = tab[2 * ox + 1];
+    }
+    int acc[3] = {0, 0, 0};
+    for (int c0 = a; c0 < e; c0 += kFancyTileW) {
+        const int cw  = min(kFancyTileW, e - c0);
+        const int ix0 = c0 + src.x, iy0 = r0 + src.y; // the chunk's origin in the image
+        int bx[3], by[3];
+        fancy_stage<true>(src, s_t, ix0, iy0, cw, nr, bx, by);
+        __syncthreads();
+        for (int q = t; q < kResizeHTileH * kFancyTileW; q += 256) {
+            const int qy = q / kFancyTileW, qx = q % kFancyTileW;
+            if (qy >= nr || qx >= cw) continue;
+            uint32_t rgb[3];
+            fancy_pixel(src, s_t, bx, by, ix0 + qx, iy0 + qy, rgb);
+            s_rgb[qy][qx] = rgb[0] | rgb[1] << 8 | rgb[2] << 16;
+        }
+        __syncthreads();
+        if (mine) { // taps j0 .. j1 - 1 of the column, relative to its first, lie in this chunk
+            const int j0 = max(f, c0) - f, j1 = min(f + cnt, c0 + cw) - f;
+            const uint32_t* px = &s_rgb[r][f - c0];
+            if (lds_w) resize_taps_h(&s_w[col * taps], px, j0, j1, acc);
+            else resize_taps_h(wts + static_cast<size_t>(col) * taps, px, j0, j1, acc);
+        }
+        __syncthreads();
+    }
+    if (mine) {
+        uint8_t* o = J.mid + static_cast<size_t>(r0 - J.row0 + r) * J.mid_pitch + 3 * ox;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[c] = static_cast<uint8_t>(clamp255((acc[c] + (1 << 21)) >> 22));
+    }
+}
+
+/// Batched resize, pass 2: the vertical taps over the items' `mid` rows, one item per blockIdx.y. Each lane makes 4
+/// consecutive output pixels of one row (3 dword loads per tap row), so a wave stores 768 contiguous bytes in NHWC, or
+/// 256 per channel plane in NCHW.
+__global__ __launch_bounds__(256) void resize_v_kernel(const ResizeJob* __restrict__ jobs, int out_w, int out_h, int layout, uint8_t* __restrict__ dst)
+{
+    const ResizeJob& J = jobs[blockIdx.y];
+    const int col_tiles = (out_w + kResizeVTileW - 1) / kResizeVTileW;
+    const int t = threadIdx.x;
+    const int x = (blockIdx.x % col_tiles) * kResizeVTileW + 4 * (t & 63);
+    const int y = (blockIdx.x / col_tiles) * kResizeVTileH + (t >> 6);
+    if (x >= out_w || y >= out_h) return;
+    const int* __restrict__ tab = J.tab_y;
+    const int f = tab[2 * y] - J.row0, cnt = tab[2 * y + 1];
+    const int* __restrict__ wts = tab + 2 * out_h + static_cast<size_t>(y) * J.taps_y;
+    const int np = min(4, out_w - x); // pixels of this lane
+    int acc[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) acc[k] = 0;
+    for (int j = 0; j < cnt; ++j) {
+        const int w = wts[j];
+        const uint8_t* s = J.mid + static_cast<size_t>(f + j) * J.mid_pitch + 3 * x; // 4-byte aligned: mid_pitch % 16 == 0
+        if (np == 4) {
+            const uint32_t* s4 = reinterpret_cast<const uint32_t*>(s);
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                const uint32_t v = s4[d];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[4 * d + k] += __mul24(w, static_cast<int>((v >> (8 * k)) & 255u));
+            }
+        } else {
+            for (int k = 0; k < 3 * np; ++k) acc[k] += __mul24(w, static_cast<int>(s[k]));
+        }
+    }
+    uint32_t o[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) o[k] = clamp255((acc[k] + (1 << 21)) >> 22);
+    const size_t item = blockIdx.y;
+    if (layout == 0) {
+        store_rgb4(dst + ((item * out_h + y) * out_w + x) * 3, o, np);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            uint8_t* d = dst + ((item * 3 + c) * out_h + y) * out_w + x;
+            if (np == 4 && (reinterpret_cast<uintptr_t>(d) & 3) == 0) {
+                *reinterpret_cast<uint32_t*>(d) = o[c] | o[3 + c] << 8 | o[6 + c] << 16 | o[9 + c] << 24;
+            } else {
+                for (int i = 0; i < np; ++i) d[i] = static_cast<uint8_t>(o[3 * i + c]);
+            }
+        }
+    }
+}
+
+} // namespace
+
+// ------------------------------------------------------------------------------------------------
+// launches
+// ------------------------------------------------------------------------------------------------
+
+hipError_t launch_upsample(
+    const uint8_t* src, int src_pitch, int src_w, int src_h,
+    uint8_t* dst, int dst_pitch, int dst_w, int dst_h,
+    int num_x, int den_x, int num_y, int den_y, hipStream_t stream)
+{
+    if (dst_w <= 0 || dst_h <= 0) return hipSuccess;
+    const dim3 grid((dst_w + 1023) / 1024, dst_h);
+    upsample_kernel<<<grid, 256, 0, stream>>>(
+        src, src_pitch, src_w, src_h, dst, dst_pitch, dst_w, dst_h, num_x, den_x, num_y, den_y);
+    return hipGetLastError();
+}
+
+hipError_t launch_rgbi(
+    const uint8_t* const* planes, const int* pitch, const int* w, const int* h, const int* num_x, const int* num_y,
+    int den_x, int den_y, int ncomp, uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream)
+{
+    if (width <= 0 || height <= 0) return hipSuccess;
+    RgbiParams p{};
+    for (int c = 0; c < 3; ++c) {
+        const int cc = c < ncomp ? c : 0;
+        p.plane[c] = planes[cc];
+        p.pitch[c] = pitch[cc];
+        p.w[c]     = w[cc];
+        p.h[c]     = h[cc];
+        p.num_x[c] = num_x[cc];
+        p.num_y[c] = num_y[cc];
+    }
+    p.den_x = den_x;
+    p.den_y = den_y;
+    p.ncomp = ncomp;
+    const dim3 grid((width + 1023) / 1024, height);
+    rgbi_kernel<<<grid, 256, 0, stream>>>(p, dst, dst_pitch, width, height);
+    return hipGetLastError();
+}
+
+hipError_t launch_rgbi_fancy(const FancySource& src, uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream)
+{
+    if (width <= 0 || height <= 0) return hipSuccess;
+    bool windowed = src.x != 0 || src.y != 0;
+    for (const FancyComp& c : src.comp) windowed = windowed || c.ox != 0 || c.oy != 0;
+    const dim3 grid((width + kFancyTileW - 1) / kFancyTileW, (height + kFancyTileH - 1) / kFancyTileH);
+    if (windowed) fancy_rgbi_kernel<true><<<grid, 256, 0, stream>>>(src, dst, dst_pitch, width, height);
+    else fancy_rgbi_kernel<false><<<grid, 256, 0, stream>>>(src, dst, dst_pitch, width, height);
+    return hipGetLastError();
+}
+
+hipError_t launch_resize(
+    const ResizeJob* d_jobs, const int* d_first_tile, int n, int h_tiles, int out_w, int out_h, int layout,
+    uint8_t* dst, hipStream_t stream)
+{
+    if (n <= 0 || h_tiles <= 0 || out_w <= 0 || out_h <= 0) return hipSuccess;
+    resize_h_kernel<<<h_tiles, 256, 0, stream>>>(d_jobs, d_first_tile, n, out_w);
+    const int v_tiles = ((out_w + kResizeVTileW - 1) / kResizeVTileW) * ((out_h + kResizeVTileH - 1) / kResizeVTileH);
+    resize_v_kernel<<<dim3(v_tiles, n), 256, 0, stream>>>(d_jobs, out_w, out_h, layout, dst);
+    return hipGetLastError();
+}
+
+} // namespace jg

@@ -1,0 +1,87 @@
+// jg_output.hpp -- launch interface of the RGB output stage (jg_output.hip; all launches are asynchronous on `stream`).
+#ifndef JG_OUTPUT_HPP_
+#define JG_OUTPUT_HPP_
+
+#include <hip/hip_runtime_api.h>
+
+#include <cstdint>
+
+namespace jg {
+
+/// Nearest-neighbour replication of one plane: dst[y][x] = src[y * num_y / den_y][x * num_x / den_x]
+/// (integer part of the reference's host helper util/util.h:62-91).
+hipError_t launch_upsample(
+    const uint8_t* src, int src_pitch, int src_w, int src_h,
+    uint8_t* dst, int dst_pitch, int dst_w, int dst_h,
+    int num_x, int den_x, int num_y, int den_y, hipStream_t stream);
+
+/// Nearest-neighbour replication + YCbCr -> interleaved RGB8 (reference host helper util/util.h:62-104);
+/// `ncomp` 1 (grey copied to R, G, B) or 3.
+hipError_t launch_rgbi(
+    const uint8_t* const* planes, const int* pitch, const int* w, const int* h, const int* num_x, const int* num_y,
+    int den_x, int den_y, int ncomp, uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream);
+
+/// How libjpeg upsamples a component (jdsample.c, jinit_upsampler), by the ratios hr = h_max / h_c, vr = v_max / v_c and
+/// the width of its FULL plane: 2h1v and 2h2v take the fancy path only on planes wider than 2 samples.
+enum FancyMode : int { kFancyReplicate = 0, kFancyH2V1 = 1, kFancyH2V2 = 2, kFancyH1V2 = 3 };
+inline int fancy_mode(int hr, int vr, int full_w)
+{
+    if (hr == 2 && vr == 1 && full_w > 2) return kFancyH2V1;
+    if (hr == 2 && vr == 2 && full_w > 2) return kFancyH2V2;
+    if (hr == 1 && vr == 2) return kFancyH1V2;
+    return kFancyReplicate;
+}
+
+/// What the libjpeg-exact conversions read: a rectangle of an image whose top-left pixel is (x, y), given as each
+/// component's decoded WINDOW (jpeggpu_ext_set_crop) -- its plane, its size and its origin in the component's full plane.
+/// Loads are clamped to the window: for every sample a pixel of the rectangle reads that is libjpeg's clamp to the plane,
+/// because the window holds the rectangle's samples and their one-sample halo, clipped to the plane (the host checks
+/// it). A whole image is the case origin 0, window = full plane, rectangle at (0, 0). Built by the host
+/// (jg_output.cpp, fancy_source), read by the kernels.
+struct FancyComp {
+    const uint8_t* plane;
+    int pitch, w, h; // the window
+    int ox, oy;      // its origin in the full plane
+    int hr, vr;      // output pixels per sample: h_max / h_c, v_max / v_c
+    int mode;        // FancyMode
+};
+struct FancySource {
+    FancyComp comp[3]; // grey: every entry is component 0
+    int x, y;
+    int ncomp;         // 1 (grey to R, G, B) or 3
+};
+
+/// libjpeg's fancy upsampling + integer YCbCr -> interleaved RGB8 (jdsample.c, jdcolor.c) of the width x height pixels
+/// at the source's rectangle origin.
+hipError_t launch_rgbi_fancy(const FancySource& src, uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream);
+
+/// One item of a batched resize (launch_resize), in device memory: a source rectangle resampled to out_w x out_h RGB by
+/// two separable passes whose weight tables the host computed (jpeggpu_ext_resize_weights). A table of n output
+/// coordinates with `taps` taps each is int32 {first, count}[n] followed by int32 weights[n][taps] (22 fraction bits).
+struct ResizeJob {
+    FancySource src;
+    int row0, rows;            // rectangle rows row0 .. row0 + rows - 1: the rows the vertical taps read
+    int taps_x, taps_y;
+    const int* tab_x;          // out_w columns
+    const int* tab_y;          // out_h rows
+    uint8_t* mid;              // rows x out_w RGB of the horizontal pass, rows mid_pitch bytes apart
+    int mid_pitch;             // a multiple of 16
+    int pad_;
+};
+constexpr int kResizeHTileW = 32, kResizeHTileH = 8; // horizontal pass: output columns x rows per workgroup
+constexpr int kResizeVTileW = 256, kResizeVTileH = 4; // vertical pass: output pixels x rows per workgroup
+/// Horizontal-pass workgroups of one item.
+inline int resize_h_tiles(int rows, int out_w)
+{
+    return ((rows + kResizeHTileH - 1) / kResizeHTileH) * ((out_w + kResizeHTileW - 1) / kResizeHTileW);
+}
+/// The two passes for `n` items: `d_jobs` ResizeJob[n] and `d_first_tile` int[n] (each item's first horizontal-pass
+/// workgroup; `h_tiles` of them in all) in device memory. `layout` 0: dst is n x out_h x out_w x 3 (NHWC), 1: n x 3 x out_h
+/// x out_w (NCHW).
+hipError_t launch_resize(
+    const ResizeJob* d_jobs, const int* d_first_tile, int n, int h_tiles, int out_w, int out_h, int layout,
+    uint8_t* dst, hipStream_t stream);
+
+} // namespace jg
+
+#endif // JG_OUTPUT_HPP_

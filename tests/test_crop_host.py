@@ -245,8 +245,10 @@ def test_crop_kernels_use_no_scratch(L):
     from tests.test_libjpeg_ref import _kernel_metadata
 
     meta = _kernel_metadata(jbuild.device_assembly())
-    crop = {k: v for k, v in meta.items() if "CropJobs" in k or "crop_rgbi_fancy_kernel" in k}
-    assert sum("crop_rgbi_fancy_kernel" in k for k in crop) == 1
+    crop = {k: v for k, v in meta.items() if "CropJobs" in k}
+    # the cropped colour conversion: the windowed instantiation of fancy_rgbi_kernel (jg_output.hip)
+    crop.update({k: v for k, v in _kernel_metadata(jbuild.device_assembly(source="jg_output.hip")).items() if "fancy_rgbi_kernelILb1E" in k})
+    assert sum("fancy_rgbi_kernelILb1E" in k for k in crop) == 1
     assert sum("idct_kernel" in k for k in crop) >= 9 and sum("idct_scaled_kernel" in k for k in crop) >= 12, sorted(crop)
     for k, v in crop.items():
         assert v.get("private_seg_size", 1) == 0 and v.get("uses_dynamic_stack", 0) == 0, (k, v)

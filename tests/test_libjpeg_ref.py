@@ -156,9 +156,14 @@ def _kernel_metadata(text):
 
 def test_new_kernels_use_no_scratch():
     meta = _kernel_metadata(jbuild.device_assembly())
+    output = _kernel_metadata(jbuild.device_assembly(source="jg_output.hip"))  # the colour kernels have their own file
     islow = {k: v for k, v in meta.items() if "idct_kernel" in k and "IslowJobs" in k}
-    fancy = {k: v for k, v in meta.items() if "fancy_rgbi_kernel" in k}
-    assert len(islow) >= 5 and len(fancy) == 1, sorted(meta)  # four job sources and the mixed batch's view
-    for k, v in {**islow, **fancy}.items():
+    fancy = {k: v for k, v in output.items() if "fancy_rgbi_kernel" in k}
+    resize = {k: v for k, v in output.items() if "resize_h_kernel" in k or "resize_v_kernel" in k}
+    assert len(islow) >= 5, sorted(meta)  # four job sources and the mixed batch's view
+    # fancy_rgbi_kernel<false>: the whole image; <true>: a rectangle read from the planes' windows
+    assert len(fancy) == 2 and sum("fancy_rgbi_kernelILb0E" in k for k in fancy) == 1 and sum("fancy_rgbi_kernelILb1E" in k for k in fancy) == 1, sorted(output)
+    assert sum("resize_h_kernel" in k for k in resize) == 1 and sum("resize_v_kernel" in k for k in resize) == 1, sorted(output)
+    for k, v in {**islow, **fancy, **resize}.items():
         assert v.get("private_seg_size", 1) == 0 and v.get("uses_dynamic_stack", 0) == 0, (k, v)
         assert v["num_vgpr"] <= 128, (k, v)
