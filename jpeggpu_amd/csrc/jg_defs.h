@@ -101,17 +101,25 @@ constexpr int kAcTableSize = (2 << kLutBitsAc) + kHuffAuxSize; // 4384, plus sec
 /// above. The state-only passes (speculation, flows) use the SYNC pack: the same tables with 32-bit first-level
 /// entries, low half = the entry above, high half = a MULTI-SYMBOL entry of the same shape for the same window
 /// bits:
-///     bits 0..4   total length of ALL the symbols it stands for (every code with its magnitude bits lies inside
-///                 the LB index bits)
+///     bits 0..4   total length of ALL the symbols it stands for: every code lies inside the LB index bits, and so do
+///                 the magnitude bits of all but the LAST symbol, whose magnitude may reach past the index (a
+///                 state-only pass skips an AC magnitude unread, and the code alone fixes its length): at most
+///                 LB + 15 = 26 bits
 ///     bits 5..8   zig-zag advance of all but the last of them (at most 15)
 ///     bits 9..15  zig-zag advance of all of them (an end-of-block, which can only be the last, counts 63)
 /// -- as many AC symbols as fit, decoded with this same table, which is right as long as the data unit does not end
 /// in front of the last of them: the symbol loop takes the high half unless index + advance of the earlier symbols
 /// reaches 64 (jg_huff_core.h). Where no second symbol fits the high half repeats the low one (its bits 5..8 are
-/// then a category; a test that fails for it falls back to the same entry). A state-only pass then takes ~1.6
-/// symbols per step on photographic data. DC tables and the second-level tables hold single symbols only.
+/// then a category; a test that fails for it falls back to the same entry). A state-only pass then takes ~1.8
+/// symbols per step on photographic data (1.6 while the last symbol's magnitude had to lie inside the index too:
+/// EXPERIMENTS.md). DC tables and the second-level tables hold single symbols only.
 constexpr int kSyncEntryBytes = 4;
 constexpr int kMultiMaxPre    = 15;
+/// Most bits a multi-symbol entry may stand for: the 5-bit length field, the 31 bits the main loop of
+/// decode_subsequence keeps in front of its end, and the 32 bits a BitWindow may consume between two looks all hold 31.
+constexpr int kSyncMultiMaxBits = 31;
+static_assert(kLutBitsAc + 15 <= kSyncMultiMaxBits && kSyncMultiMaxBits < (1 << 5),
+              "a multi-symbol entry: codes inside the index, the last symbol's magnitude (category <= 15) behind it");
 constexpr int kDcTableSizeSync = (kSyncEntryBytes << kLutBitsDc) + kHuffAuxSize;
 constexpr int kAcTableSizeSync = (kSyncEntryBytes << kLutBitsAc) + kHuffAuxSize;
 

@@ -286,9 +286,11 @@ JG_HD inline void decode_subsequence(
     } while (0)
     {
         // State-only passes walk the SYNC pack (jg_defs.h): 32-bit first-level entries whose high half stands for
-        // as many AC symbols as lie inside the index bits. While at least 31 bits are left in front of `end_bit`
-        // whatever an entry stands for fits (a symbol takes at most 16 + 15 bits, a multi-symbol entry at most the 11
-        // index bits), so the main loop does not ask; it takes the high half unless the data unit would end in
+        // as many AC symbols as have their codes inside the index bits. While at least 31 bits are left in front of
+        // `end_bit` whatever an entry stands for fits (a symbol takes at most 16 + 15 bits, a multi-symbol entry at most
+        // the 11 index bits + the 15 magnitude bits of its last symbol, kSyncMultiMaxBits at the very most: within the
+        // 32 bits a BitWindow may consume between two looks), so the main loop does not ask; it stays at or in front
+        // of `end_bit`, so what it looks at past the row is what it was (GlobalFetch). It takes the high half unless the data unit would end in
         // front of the last of its symbols -- index + advance of the earlier ones reaching 64: the following
         // symbol is then a DC symbol of the next unit, not what the AC table made of those bits -- and the low
         // half, the first symbol alone, otherwise. The symbols committed are exactly those of the one-symbol-per-

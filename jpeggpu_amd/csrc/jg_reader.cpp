@@ -168,19 +168,30 @@ void widen_huff_table(const std::vector<uint8_t>& t, bool is_dc, std::vector<uin
         uint32_t multi        = single; // no second symbol: the high half repeats the low one
         if (!is_dc && (single & 31u) != 0) {
             // Decode greedily inside the lb index bits: a symbol counts if its code AND its magnitude bits lie
-            // inside them (its first-level entry then does not depend on the bits behind the index).
+            // inside them (its first-level entry then does not depend on the bits behind the index). The LAST symbol
+            // of an entry only needs its CODE inside them: a state-only pass skips an AC magnitude without looking at
+            // it, and the code alone fixes run and category, hence the total length and the advance, whatever the
+            // bits behind the index are. The look-up below shifts zeros in behind what is left of the index; an entry
+            // whose code is no longer than the index bits that are left does not depend on them.
             uint32_t bits = 0, pre = 0, total_adv = 0;
             int count = 0;
             while (true) {
                 const uint32_t e   = lut[(idx << bits) & (n - 1u)];
                 const uint32_t len = e & 31u, adv = e >> 9;
-                if (len == 0 || bits + len > static_cast<uint32_t>(lb)) break;
+                if (len == 0) break;
+                const bool inside = bits + len <= static_cast<uint32_t>(lb);
+                // magnitude bits behind the index: the code inside it, the whole entry inside its length field and the
+                // main loop's guard (jg_defs.h, kSyncMultiMaxBits)
+                const bool as_last = !inside && bits + (len - ((e >> 5) & 15u)) <= static_cast<uint32_t>(lb);
+                if (!inside && !as_last) break;
                 if (count > 0 && total_adv > static_cast<uint32_t>(kMultiMaxPre)) break; // the earlier symbols' advance has four bits
+                if (bits + len > static_cast<uint32_t>(kSyncMultiMaxBits)) break; // cannot happen (static_assert in jg_defs.h): refuse rather than wrap
                 pre = total_adv;
                 total_adv += adv;
                 bits += len;
                 ++count;
-                if (adv == kEobAdvance) break; // end of block: whatever follows belongs to the next data unit
+                // end of block: whatever follows belongs to the next data unit; as_last: what follows starts behind the index
+                if (adv == kEobAdvance || as_last) break;
             }
             if (count >= 2) multi = bits | pre << 5 | total_adv << 9;
         }

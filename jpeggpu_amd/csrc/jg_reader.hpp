@@ -192,7 +192,8 @@ struct Reader {
 void build_huff_table(
     std::vector<uint8_t>& t, const uint8_t (&num_codes)[16], const uint8_t* huffval, int count, bool is_dc);
 /// The sync-pack form of a table built by build_huff_table: 32-bit first-level entries with multi-symbol high
-/// halves (jg_defs.h), everything behind the first level unchanged.
+/// halves (jg_defs.h: every code inside the index bits, the last symbol's magnitude bits possibly behind them),
+/// everything behind the first level unchanged.
 void widen_huff_table(const std::vector<uint8_t>& t, bool is_dc, std::vector<uint8_t>& out);
 
 } // namespace jg
