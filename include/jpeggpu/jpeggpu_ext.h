@@ -26,6 +26,10 @@
  *   jpeggpu_ext_crop_to_rgbi_fancy     the rectangle as interleaved RGB8, equal to that part of planes_to_rgbi_fancy's image
  *   jpeggpu_ext_resize_to_rgb          a batch of (cropped) images resized to one size, NHWC or NCHW, with the arithmetic
  *                                      of Pillow's BILINEAR / BICUBIC Image.resize (torchvision's RandomResizedCrop)
+ *   jpeggpu_ext_get_color_space        the colour model of the parsed file -- grey, YCbCr, RGB, CMYK or YCCK -- by libjpeg's
+ *                                      rules (JFIF and Adobe segments, component ids)
+ *   jpeggpu_ext_*_cs                   the libjpeg-exact RGB calls above for a given colour model: the RGB Pillow's
+ *                                      Image.convert("RGB") makes of files of all five
  */
 #ifndef JPEGGPU_JPEGGPU_EXT_H_
 #define JPEGGPU_JPEGGPU_EXT_H_
@@ -482,6 +486,98 @@ enum jpeggpu_status jpeggpu_ext_resize_to_rgb(
  * another filter. */
 enum jpeggpu_status jpeggpu_ext_resize_weights(
     int in, int out, enum jpeggpu_ext_filter filter, int* first, int* count, int* weights, int max_taps);
+
+/* Colour models. jpeggpu_decoder_parse_header looks at the application segments in front of the first scan and at the
+ * frame's component ids, and jpeggpu_ext_get_color_space reports what libjpeg (jdapimin.c, default_decompress_parms) and
+ * therefore Pillow take the file for (JPEGGPU_INVALID_ARGUMENT before parse_header):
+ *   1 component   GRAY.
+ *   3 components  a JFIF APP0 segment (length >= 16, "JFIF\0") says YCBCR, even beside an Adobe segment; otherwise an
+ *                 Adobe APP14 segment (length >= 14, "Adobe"; its transform flag is data byte 11): 0 is RGB, anything else
+ *                 YCBCR; otherwise the component ids 'R', 'G', 'B' are RGB, anything else YCBCR.
+ *   4 components  an Adobe segment with transform 0, or none: CMYK; any other transform: YCCK.
+ *   2 components  UNKNOWN: there is no RGB of such a file.
+ * A short or malformed APPn segment is skipped like any other APPn and says nothing. Nothing of the decode depends on the
+ * model: the planes are the file's components either way.
+ *
+ * The calls below are jpeggpu_ext_planes_to_rgbi_fancy, _replicate, jpeggpu_ext_crop_to_rgbi_fancy, _replicate,
+ * jpeggpu_ext_resize_scratch_size and jpeggpu_ext_resize_to_rgb with the model as an argument (the resize: one per item,
+ * colors[n]; a call may mix models) -- the same upsampling per component, the fourth included, the same contracts, checks
+ * and return codes, and then per pixel, of the upsampled samples s_0 ..:
+ *   GRAY   s_0 three times.                    YCBCR  jdcolor.c's ycc_rgb_convert, as above.
+ *   RGB    s_0, s_1, s_2 as they are.
+ *   CMYK   the samples are taken for Adobe's inverted ones, as Pillow always does: with the inks c_i = 255 - s_i and
+ *          K = s_3, out_i = K - (((t >> 8) + t) >> 8), t = c_i K + 128 -- Pillow's cmyk2rgb, nk - MULDIV255(c, nk).
+ *   YCCK   (r, g, b) = ycc_rgb_convert(s_0, s_1, s_2), then the CMYK rule with the inks c_i = r, g, b and K = s_3
+ *          (libjpeg hands out 255 - r ... in place of the samples, and Pillow inverts those like any CMYK file's).
+ * On planes of a JPEGGPU_EXT_IDCT_ISLOW decode with the model jpeggpu_ext_get_color_space reported, this is
+ * Image.open(f).convert("RGB") for every file Pillow opens as L, RGB or CMYK (in the JPEGGPU_EXT_SCALE_LIBJPEG mode: after
+ * draft()). Embedded ICC profiles and EXIF orientation are ignored, as convert("RGB") ignores them.
+ * JPEGGPU_NOT_SUPPORTED: a model that does not fit info's component count (GRAY 1, YCBCR and RGB 3, CMYK and YCCK 4),
+ * UNKNOWN, non-integral sampling ratios; nothing is written then. The entry points without a model are these with GRAY for
+ * one component and YCBCR for three (so 2 or 4 components stay JPEGGPU_NOT_SUPPORTED there). A NULL `colors`:
+ * JPEGGPU_INVALID_ARGUMENT (jpeggpu_ext_resize_scratch_size_cs: 0). */
+enum jpeggpu_ext_color_space {
+    JPEGGPU_EXT_COLOR_UNKNOWN = 0,
+    JPEGGPU_EXT_COLOR_GRAY    = 1,
+    JPEGGPU_EXT_COLOR_YCBCR   = 2,
+    JPEGGPU_EXT_COLOR_RGB     = 3,
+    JPEGGPU_EXT_COLOR_CMYK    = 4,
+    JPEGGPU_EXT_COLOR_YCCK    = 5
+};
+enum jpeggpu_status jpeggpu_ext_get_color_space(jpeggpu_decoder_t decoder, enum jpeggpu_ext_color_space* color);
+enum jpeggpu_status jpeggpu_ext_planes_to_rgbi_fancy_cs(
+    const struct jpeggpu_img_info* info,
+    enum jpeggpu_ext_color_space color,
+    const struct jpeggpu_img* src,
+    uint8_t* dst,
+    int dst_pitch,
+    int width,
+    int height,
+    jpeggpu_stream_t stream);
+enum jpeggpu_status jpeggpu_ext_planes_to_rgbi_replicate_cs(
+    const struct jpeggpu_img_info* info,
+    enum jpeggpu_ext_color_space color,
+    const struct jpeggpu_img* src,
+    uint8_t* dst,
+    int dst_pitch,
+    int width,
+    int height,
+    jpeggpu_stream_t stream);
+enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_fancy_cs(
+    const struct jpeggpu_img_info* info,
+    enum jpeggpu_ext_color_space color,
+    const struct jpeggpu_ext_crop_info* crop,
+    const struct jpeggpu_img* src,
+    uint8_t* dst,
+    int dst_pitch,
+    jpeggpu_stream_t stream);
+enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_replicate_cs(
+    const struct jpeggpu_img_info* info,
+    enum jpeggpu_ext_color_space color,
+    const struct jpeggpu_ext_crop_info* crop,
+    const struct jpeggpu_img* src,
+    uint8_t* dst,
+    int dst_pitch,
+    jpeggpu_stream_t stream);
+size_t jpeggpu_ext_resize_scratch_size_cs(
+    const struct jpeggpu_ext_resize_item* items,
+    const enum jpeggpu_ext_color_space* colors,
+    int n,
+    int out_w,
+    int out_h,
+    enum jpeggpu_ext_filter filter);
+enum jpeggpu_status jpeggpu_ext_resize_to_rgb_cs(
+    const struct jpeggpu_ext_resize_item* items,
+    const enum jpeggpu_ext_color_space* colors,
+    int n,
+    int out_w,
+    int out_h,
+    enum jpeggpu_ext_filter filter,
+    enum jpeggpu_ext_output_layout layout,
+    uint8_t* dst,
+    void* d_scratch,
+    size_t scratch_size,
+    jpeggpu_stream_t stream);
 
 #ifdef __cplusplus
 }

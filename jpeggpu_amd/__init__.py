@@ -6,6 +6,7 @@ ctypes bindings with the reference's function names, argument meaning and status
 """
 from .api import (  # noqa: F401
     Batch,
+    ColorSpace,
     CropInfo,
     Decoder,
     ImgInfo,

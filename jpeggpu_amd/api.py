@@ -20,6 +20,16 @@ LAYOUTS = {"NHWC": 0, "NCHW": 1}  # enum jpeggpu_ext_output_layout
 SCALE_MODES = {"uniform": 0, "libjpeg": 1}  # enum jpeggpu_ext_scale_mode
 
 
+class ColorSpace(enum.IntEnum):
+    """enum jpeggpu_ext_color_space: what libjpeg and Pillow take a file's components for (Decoder.color_space)."""
+    UNKNOWN = 0
+    GRAY = 1
+    YCBCR = 2
+    RGB = 3
+    CMYK = 4
+    YCCK = 5
+
+
 class Status(enum.IntEnum):
     SUCCESS = 0
     INVALID_ARGUMENT = 1
@@ -174,6 +184,18 @@ def lib():
     L.jpeggpu_ext_resize_scratch_size.argtypes = [C.POINTER(ResizeItem), C.c_int, C.c_int, C.c_int, C.c_int]
     L.jpeggpu_ext_resize_to_rgb.argtypes = [
         C.POINTER(ResizeItem), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.jpeggpu_ext_get_color_space.argtypes = [dec, C.POINTER(C.c_int)]
+    L.jpeggpu_ext_planes_to_rgbi_fancy_cs.argtypes = [
+        C.POINTER(ImgInfo), C.c_int, C.POINTER(Img), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.jpeggpu_ext_planes_to_rgbi_replicate_cs.argtypes = L.jpeggpu_ext_planes_to_rgbi_fancy_cs.argtypes
+    L.jpeggpu_ext_crop_to_rgbi_fancy_cs.argtypes = [
+        C.POINTER(ImgInfo), C.c_int, C.POINTER(CropInfo), C.POINTER(Img), C.c_void_p, C.c_int, C.c_void_p]
+    L.jpeggpu_ext_crop_to_rgbi_replicate_cs.argtypes = L.jpeggpu_ext_crop_to_rgbi_fancy_cs.argtypes
+    L.jpeggpu_ext_resize_scratch_size_cs.restype = C.c_size_t
+    L.jpeggpu_ext_resize_scratch_size_cs.argtypes = [C.POINTER(ResizeItem), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int]
+    L.jpeggpu_ext_resize_to_rgb_cs.argtypes = [
+        C.POINTER(ResizeItem), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+        C.c_void_p]
     L.jpeggpu_ext_resize_weights.argtypes = [
         C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
     _lib = L
@@ -262,6 +284,13 @@ class Decoder:
         si = ScaleInfo()
         _check(lib().jpeggpu_ext_get_scale_info(self._h, C.byref(si)), "jpeggpu_ext_get_scale_info")
         return si
+
+    def color_space(self) -> ColorSpace:
+        """jpeggpu_ext_get_color_space of the last parsed image: GRAY, YCBCR, RGB, CMYK or YCCK by libjpeg's rules (JFIF and
+        Adobe segments, component ids), UNKNOWN for two components."""
+        cs = C.c_int()
+        _check(lib().jpeggpu_ext_get_color_space(self._h, C.byref(cs)), "jpeggpu_ext_get_color_space")
+        return ColorSpace(cs.value)
 
     def set_idct(self, method: str):
         """The full-size IDCT of the next parsed images: "reference" (the default) or "islow", libjpeg-turbo's
@@ -423,14 +452,15 @@ def draft_scale(width, height, requested):
 
 
 def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp=False, device_scan=False, scale=1,
-                     idct="reference", crop=None, scale_mode="uniform"):
+                     idct="reference", crop=None, scale_mode="uniform", return_color=False):
     """Convenience wrapper used by tests: full call sequence on torch's current stream, returns the
     planes as torch uint8 tensors on `device` (torch is only the allocator / stream provider). With
     `device_scan` the restart markers are found on the device and a status it reports there is raised.
     `scale`: 1, 2, 4 or 8 -- planes at 1 / scale (Decoder.set_scale). `idct`: "reference" or "islow" (Decoder.set_idct).
     `crop`: (x, y, w, h) -- only the planes' windows for that rectangle are decoded (Decoder.set_crop), and the CropInfo
     is returned as well: (planes, info, crop_info). `scale_mode`: "uniform" or "libjpeg" (Decoder.set_scale_mode); the
-    returned info then carries the planes' effective sampling factors."""
+    returned info then carries the planes' effective sampling factors. `return_color`: the file's ColorSpace
+    (Decoder.color_space) is appended to what is returned."""
     import torch
 
     dec = Decoder(subseq_bytes)
@@ -457,24 +487,25 @@ def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp
         torch.cuda.synchronize(torch.device(device))
         if device_scan:
             _check(int(dec.device_status(base, stream)), "device-side marker scan")
+        out = (planes, info)
         if crop is not None:
-            crop_info = dec.crop_info()
-            if return_tmp:
-                return planes, info, crop_info, tmp, base, dec.layout()
-            return planes, info, crop_info
+            out += (dec.crop_info(),)
         if return_tmp:
-            return planes, info, tmp, base, dec.layout()
-        return planes, info
+            out += (tmp, base, dec.layout())
+        if return_color:
+            out += (dec.color_space(),)
+        return out
     finally:
         dec.cleanup()
 
 
-def planes_to_rgb(planes, info, fancy=True, device=None, replicate=False):
+def planes_to_rgb(planes, info, fancy=True, device=None, replicate=False, color=None):
     """Planes of a 1- or 3-component image (as decode_to_planes returns them) -> (H, W, 3) uint8 tensor at the full image
     size, on torch's current stream: jpeggpu_ext_planes_to_rgbi_fancy (libjpeg's fancy upsampling and integer colour
     conversion) or, with fancy=False, jpeggpu_ext_planes_to_rgbi (the reference's helper). `replicate`:
     jpeggpu_ext_planes_to_rgbi_replicate -- libjpeg's conversion with replication, its output at 1/8 in the libjpeg scale
-    mode."""
+    mode. `color`: the planes' ColorSpace (Decoder.color_space) -- the _cs form of the fancy or replicating call, which also
+    converts RGB-, CMYK- and YCCK-coded files (four planes); None: grey or YCbCr by the number of components."""
     import torch
 
     n = info.num_components
@@ -489,14 +520,20 @@ def planes_to_rgb(planes, info, fancy=True, device=None, replicate=False):
     out = torch.empty((height, width, 3), dtype=torch.uint8, device=device)
     stream = torch.cuda.current_stream(device).cuda_stream
     name = "jpeggpu_ext_planes_to_rgbi_replicate" if replicate else "jpeggpu_ext_planes_to_rgbi_fancy" if fancy else "jpeggpu_ext_planes_to_rgbi"
+    if color is not None:
+        if not (fancy or replicate):
+            raise ValueError("the reference's helper (fancy=False) takes no colour model")
+        name += "_cs"
+        _check(getattr(lib(), name)(C.byref(info), int(color), C.byref(src), out.data_ptr(), 3 * width, width, height, stream), name)
+        return out
     _check(getattr(lib(), name)(C.byref(info), C.byref(src), out.data_ptr(), 3 * width, width, height, stream), name)
     return out
 
 
-def crop_to_rgb(planes, info, crop_info, device=None, replicate=False):
+def crop_to_rgb(planes, info, crop_info, device=None, replicate=False, color=None):
     """The window planes of a cropped decode (decode_to_planes(..., crop=...)) -> (h, w, 3) uint8 tensor of the rectangle,
     equal to that part of planes_to_rgb's image of the uncropped planes (jpeggpu_ext_crop_to_rgbi_fancy, or with
-    `replicate` jpeggpu_ext_crop_to_rgbi_replicate)."""
+    `replicate` jpeggpu_ext_crop_to_rgbi_replicate). `color`: as in planes_to_rgb."""
     import torch
 
     n = info.num_components
@@ -508,6 +545,10 @@ def crop_to_rgb(planes, info, crop_info, device=None, replicate=False):
     out = torch.empty((h, w, 3), dtype=torch.uint8, device=device)
     stream = torch.cuda.current_stream(device).cuda_stream
     name = "jpeggpu_ext_crop_to_rgbi_replicate" if replicate else "jpeggpu_ext_crop_to_rgbi_fancy"
+    if color is not None:
+        name += "_cs"
+        _check(getattr(lib(), name)(C.byref(info), int(color), C.byref(crop_info), C.byref(src), out.data_ptr(), 3 * w, stream), name)
+        return out
     _check(getattr(lib(), name)(C.byref(info), C.byref(crop_info), C.byref(src), out.data_ptr(), 3 * w, stream), name)
     return out
 
@@ -519,8 +560,9 @@ def _needs_replication(info, scale):
 
 
 def decode_to_rgb(data: bytes, device="cuda:0", device_scan=False, crop=None, scale=1):
-    """Decode a 1- or 3-component JPEG to an (H, W, 3) uint8 tensor on `device` the way libjpeg-turbo does: the ISLOW
-    IDCT at full size, then fancy upsampling and the integer YCbCr -> RGB conversion. Meant to equal
+    """Decode a JPEG to an (H, W, 3) uint8 tensor on `device` the way libjpeg-turbo does: the ISLOW IDCT at full size, then
+    fancy upsampling and the conversion of the file's colour model (Decoder.color_space): grey, YCbCr (jdcolor.c's integer
+    conversion), RGB-coded files as they are, CMYK and YCCK by Pillow's rule for Adobe's inverted samples. Meant to equal
     np.asarray(PIL.Image.open(f).convert("RGB")) (INTEGRATION.md, "Matching Pillow / torchvision"). With `crop` = (x, y,
     w, h) only that rectangle is decoded: an (h, w, 3) tensor equal to decode_to_rgb(data)[y:y + h, x:x + w].
     `scale` = d in 2, 4, 8: the image at 1/d as libjpeg-turbo scales it (the libjpeg scale mode: per-component IDCT sizes,
@@ -528,14 +570,14 @@ def decode_to_rgb(data: bytes, device="cuda:0", device_scan=False, crop=None, sc
     Pillow; `crop` is then in pixels of that image."""
     import torch
 
-    kw = dict(device=device, device_scan=device_scan, idct="islow", scale=scale, scale_mode="libjpeg")
+    kw = dict(device=device, device_scan=device_scan, idct="islow", scale=scale, scale_mode="libjpeg", return_color=True)
     if crop is not None:
-        planes, info, crop_info = decode_to_planes(data, crop=crop, **kw)
-        rgb = crop_to_rgb(planes, info, crop_info, replicate=_needs_replication(info, scale))
+        planes, info, crop_info, color = decode_to_planes(data, crop=crop, **kw)
+        rgb = crop_to_rgb(planes, info, crop_info, replicate=_needs_replication(info, scale), color=color)
         torch.cuda.synchronize(torch.device(device))
         return rgb
-    planes, info = decode_to_planes(data, **kw)
-    rgb = planes_to_rgb(planes, info, fancy=True, replicate=_needs_replication(info, scale))
+    planes, info, color = decode_to_planes(data, **kw)
+    rgb = planes_to_rgb(planes, info, fancy=True, replicate=_needs_replication(info, scale), color=color)
     torch.cuda.synchronize(torch.device(device))
     return rgb
 
@@ -607,18 +649,29 @@ def _resize_items(planes_list, infos, crop_infos):
     return items, keep
 
 
-def resize_scratch_size(planes_list, infos, size, crop_infos=None, filt="bilinear"):
-    """jpeggpu_ext_resize_scratch_size of these items (0 if the call would refuse them)."""
+def _color_array(colors, n):
+    if len(colors) != n:
+        raise ValueError("colors must have one entry per image")
+    return (C.c_int * n)(*[int(c) for c in colors])
+
+
+def resize_scratch_size(planes_list, infos, size, crop_infos=None, filt="bilinear", colors=None):
+    """jpeggpu_ext_resize_scratch_size of these items (0 if the call would refuse them); with `colors` (one ColorSpace
+    per item) jpeggpu_ext_resize_scratch_size_cs."""
     h, w = _size_hw(size)
     items, _keep = _resize_items(planes_list, infos, crop_infos)
+    if colors is not None:
+        return lib().jpeggpu_ext_resize_scratch_size_cs(items, _color_array(colors, len(planes_list)), len(planes_list), w, h, FILTERS[filt])
     return lib().jpeggpu_ext_resize_scratch_size(items, len(planes_list), w, h, FILTERS[filt])
 
 
-def resize_to_rgb(planes_list, infos, size, crop_infos=None, filt="bilinear", layout="NHWC", out=None):
+def resize_to_rgb(planes_list, infos, size, crop_infos=None, filt="bilinear", layout="NHWC", out=None, colors=None):
     """jpeggpu_ext_resize_to_rgb on torch's current stream: every decoded image i
     (planes_list[i], infos[i], and crop_infos[i] from a cropped decode, or None for the whole image) resampled to `size`
     (int: square; (h, w)) with Pillow's BILINEAR or BICUBIC arithmetic. Returns a uint8 tensor of n x h x w x 3 ("NHWC")
-    or n x 3 x h x w ("NCHW"), `out` if given (contiguous, of that shape)."""
+    or n x 3 x h x w ("NCHW"), `out` if given (contiguous, of that shape). `colors`: each image's ColorSpace
+    (Decoder.color_space; jpeggpu_ext_resize_to_rgb_cs -- a call may mix grey, YCbCr, RGB, CMYK and YCCK items); None: grey
+    or YCbCr by the number of components."""
     import torch
 
     if filt not in FILTERS:
@@ -634,9 +687,16 @@ def resize_to_rgb(planes_list, infos, size, crop_infos=None, filt="bilinear", la
         out = torch.empty(shape, dtype=torch.uint8, device=device)
     elif tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous():
         raise ValueError("out must be a contiguous uint8 tensor of shape %s" % (shape,))
+    stream = torch.cuda.current_stream(device).cuda_stream
+    if colors is not None:
+        cs = _color_array(colors, n)
+        need = lib().jpeggpu_ext_resize_scratch_size_cs(items, cs, n, w, h, FILTERS[filt])
+        scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+        _check(lib().jpeggpu_ext_resize_to_rgb_cs(items, cs, n, w, h, FILTERS[filt], LAYOUTS[layout], out.data_ptr(), scratch.data_ptr(),
+                                                  need, stream), "jpeggpu_ext_resize_to_rgb_cs")
+        return out
     need = lib().jpeggpu_ext_resize_scratch_size(items, n, w, h, FILTERS[filt])
     scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
-    stream = torch.cuda.current_stream(device).cuda_stream
     _check(lib().jpeggpu_ext_resize_to_rgb(items, n, w, h, FILTERS[filt], LAYOUTS[layout], out.data_ptr(), scratch.data_ptr(),
                                            need, stream), "jpeggpu_ext_resize_to_rgb")
     # the scratch tensor is freed by torch's caching allocator in stream order: it is not reused before the launches ran
@@ -644,8 +704,8 @@ def resize_to_rgb(planes_list, infos, size, crop_infos=None, filt="bilinear", la
 
 
 def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", device="cuda:0", scales=None):
-    """A training pipeline's decode: every JPEG of `datas` decoded with libjpeg-turbo's arithmetic (ISLOW IDCT, fancy
-    upsampling), only the rectangle crops[i] = (x, y, w, h) of it (None: the whole image), in ONE jpeggpu_ext_decode_batch
+    """A training pipeline's decode: every JPEG of `datas` (of any colour model: decode_to_rgb) decoded with libjpeg-turbo's
+    arithmetic (ISLOW IDCT, fancy upsampling), only the rectangle crops[i] = (x, y, w, h) of it (None: the whole image), in ONE jpeggpu_ext_decode_batch
     call, then resized to `size` (int: square; (h, w)) with Pillow's BILINEAR or BICUBIC arithmetic by one
     jpeggpu_ext_resize_to_rgb call. Returns an n x h x w x 3 ("NHWC") or n x 3 x h x w ("NCHW") uint8 tensor equal to
     Pillow's Image.open(f).convert("RGB").crop((x, y, x + w, y + h)).resize((w_out, h_out), filter) of every image
@@ -665,7 +725,7 @@ def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", devi
     if len(scales) != n or any(s not in (1, 2, 4, 8) for s in scales):
         raise ValueError("scales must have one entry of 1, 2, 4 or 8 per image")
     stream = torch.cuda.current_stream(dev).cuda_stream
-    decs, entries, planes_list, infos, cis, keep = [], [], [], [], [], []
+    decs, entries, planes_list, infos, cis, keep, colors = [], [], [], [], [], [], []
     try:
         scans = 0
         for i, (data, crop, scale) in enumerate(zip(datas, crops, scales)):
@@ -695,11 +755,12 @@ def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", devi
             planes_list.append(planes)
             infos.append(info)
             cis.append(dec.crop_info() if crop is not None else None)
+            colors.append(dec.color_space())
         batch = Batch(scans)
         scratch = torch.empty(batch.scratch_size, dtype=torch.uint8, device=dev)
         batch.set_items(entries)
         batch.decode(scratch.data_ptr(), stream)
-        out = resize_to_rgb(planes_list, infos, size, cis, filt, layout)
+        out = resize_to_rgb(planes_list, infos, size, cis, filt, layout, colors=colors)
         torch.cuda.synchronize(dev)
         batch.destroy()
         return out

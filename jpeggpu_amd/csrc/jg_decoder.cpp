@@ -1124,6 +1124,18 @@ enum jpeggpu_status jpeggpu_ext_get_scale_info(jpeggpu_decoder_t decoder, struct
     return JPEGGPU_SUCCESS;
 }
 
+enum jpeggpu_status jpeggpu_ext_get_color_space(jpeggpu_decoder_t decoder, enum jpeggpu_ext_color_space* color)
+{
+    static_assert(jg::kColorUnknown == int{JPEGGPU_EXT_COLOR_UNKNOWN} && jg::kColorGray == int{JPEGGPU_EXT_COLOR_GRAY} &&
+                      jg::kColorYCbCr == int{JPEGGPU_EXT_COLOR_YCBCR} && jg::kColorRGB == int{JPEGGPU_EXT_COLOR_RGB} &&
+                      jg::kColorCMYK == int{JPEGGPU_EXT_COLOR_CMYK} && jg::kColorYCCK == int{JPEGGPU_EXT_COLOR_YCCK},
+                  "jg::ColorSpace is enum jpeggpu_ext_color_space");
+    if (!decoder || !color) return JPEGGPU_INVALID_ARGUMENT;
+    if (!decoder->d.parsed) return JPEGGPU_INVALID_ARGUMENT;
+    *color = static_cast<jpeggpu_ext_color_space>(decoder->d.reader.s.color_space);
+    return JPEGGPU_SUCCESS;
+}
+
 enum jpeggpu_status jpeggpu_ext_set_idct(jpeggpu_decoder_t decoder, enum jpeggpu_ext_idct method)
 {
     if (!decoder) return JPEGGPU_INVALID_ARGUMENT;

@@ -19,8 +19,19 @@
 namespace jg {
 namespace {
 
+static_assert(kFancyGray == int{JPEGGPU_EXT_COLOR_GRAY} && kFancyYCbCr == int{JPEGGPU_EXT_COLOR_YCBCR} && kFancyRGB == int{JPEGGPU_EXT_COLOR_RGB} &&
+                  kFancyCMYK == int{JPEGGPU_EXT_COLOR_CMYK} && kFancyYCCK == int{JPEGGPU_EXT_COLOR_YCCK},
+              "FancyColor is enum jpeggpu_ext_color_space");
+
+/// The colour model the entry points without one assume: grey for one component, YCbCr for three, none for any other count.
+int color_by_count(const jpeggpu_img_info* info)
+{
+    return !info ? JPEGGPU_EXT_COLOR_UNKNOWN : info->num_components == 1 ? JPEGGPU_EXT_COLOR_GRAY : info->num_components == 3 ? JPEGGPU_EXT_COLOR_YCBCR : JPEGGPU_EXT_COLOR_UNKNOWN;
+}
+
 /// Every check of a libjpeg-exact conversion's source, and its description for the kernels: the planes `src` of `info`,
-/// which are the windows of a cropped decode if `crop` is given and the whole planes otherwise. `replicate`: every
+/// which are the windows of a cropped decode if `crop` is given and the whole planes otherwise, read as the colour model
+/// `color` (enum jpeggpu_ext_color_space; one that does not fit the component count, or UNKNOWN: JPEGGPU_NOT_SUPPORTED). `replicate`: every
 /// component is replicated (libjpeg at 1/8 scale: jdsample.c turns fancy upsampling off when min_DCT_scaled_size is 1);
 /// the colour conversion stays jdcolor.c's. `rect_w` x `rect_h`, if asked for: the rectangle -- the crop's, or else the
 /// image's extent by its planes (callers that convert a whole image bring their own size, and the kernel's clamp is
@@ -28,12 +39,14 @@ namespace {
 /// The statuses and their order are API. One order differs between the callers: jpeggpu_ext_crop_to_rgbi_* refuse a
 /// window outside its plane before non-integral ratios (`window_first`), jpeggpu_ext_resize_to_rgb after them.
 jpeggpu_status fancy_source(
-    const jpeggpu_img_info* info, const jpeggpu_ext_crop_info* crop, const jpeggpu_img* src, bool replicate, bool window_first,
+    const jpeggpu_img_info* info, int color, const jpeggpu_ext_crop_info* crop, const jpeggpu_img* src, bool replicate, bool window_first,
     FancySource& s, int* rect_w = nullptr, int* rect_h = nullptr)
 {
     if (!info || !src) return JPEGGPU_INVALID_ARGUMENT;
     const int nc = info->num_components;
-    if (nc != 1 && nc != 3) return JPEGGPU_NOT_SUPPORTED; // as jpeggpu_ext_planes_to_rgbi
+    const int fits = color == JPEGGPU_EXT_COLOR_GRAY ? 1 : color == JPEGGPU_EXT_COLOR_YCBCR || color == JPEGGPU_EXT_COLOR_RGB ? 3
+                     : color == JPEGGPU_EXT_COLOR_CMYK || color == JPEGGPU_EXT_COLOR_YCCK ? 4 : 0;
+    if (fits == 0 || nc != fits) return JPEGGPU_NOT_SUPPORTED; // without a model: 2 or 4 components, as jpeggpu_ext_planes_to_rgbi
     int sx_max = 0, sy_max = 0;
     bool outside = false; // a window that does not lie inside its plane
     for (int c = 0; c < nc; ++c) {
@@ -61,7 +74,7 @@ jpeggpu_status fancy_source(
         }
     }
     s = FancySource{};
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < 4; ++k) {
         const int cc = k < nc ? k : 0;
         FancyComp& f = s.comp[k];
         f.plane      = src->image[cc];
@@ -77,6 +90,7 @@ jpeggpu_status fancy_source(
     s.x     = crop ? crop->x : 0;
     s.y     = crop ? crop->y : 0;
     s.ncomp = nc;
+    s.color = color;
     if (rect_w && rect_h) {
         if (crop) {
             *rect_w = crop->width;
@@ -182,10 +196,10 @@ size_t resize_table_bytes(int in, int out, int filter)
 }
 
 /// One item's checks and its descriptor, without the table and scratch pointers; `in_w` x `in_h` is the rectangle.
-jpeggpu_status resize_item(const jpeggpu_ext_resize_item& it, ResizeJob& job, int& in_w, int& in_h)
+jpeggpu_status resize_item(const jpeggpu_ext_resize_item& it, int color, ResizeJob& job, int& in_w, int& in_h)
 {
     job = ResizeJob{};
-    return fancy_source(it.info, it.crop, it.src, false, false, job.src, &in_w, &in_h);
+    return fancy_source(it.info, color, it.crop, it.src, false, false, job.src, &in_w, &in_h);
 }
 
 /// Where everything of one call sits in d_scratch: the descriptors, each item's first tile, the tables (together the
@@ -196,10 +210,12 @@ struct ResizePlan {
     std::vector<size_t> off_tab_x, off_tab_y, off_mid;
     size_t off_first = 0, head = 0, total = 0;
     int h_tiles      = 0;
+    bool all_models  = false; // an item that is not grey or YCbCr (fancy_all_models)
 };
 
+/// `colors`: each item's colour model, or null: by its component count (color_by_count).
 jpeggpu_status plan_resize(
-    const jpeggpu_ext_resize_item* items, int n, int out_w, int out_h, int filter, ResizePlan& p)
+    const jpeggpu_ext_resize_item* items, const jpeggpu_ext_color_space* colors, int n, int out_w, int out_h, int filter, ResizePlan& p)
 {
     if (!items || n <= 0 || n > 65535 || out_w <= 0 || out_h <= 0) return JPEGGPU_INVALID_ARGUMENT;
     if (filter != JPEGGPU_EXT_FILTER_BILINEAR && filter != JPEGGPU_EXT_FILTER_BICUBIC) return JPEGGPU_NOT_SUPPORTED;
@@ -220,8 +236,9 @@ jpeggpu_status plan_resize(
     int64_t tiles  = 0;
     const int pitch = static_cast<int>(align_up(3 * static_cast<size_t>(out_w), 16));
     for (int i = 0; i < n; ++i) {
-        const jpeggpu_status st = resize_item(items[i], p.jobs[i], p.in_w[i], p.in_h[i]);
+        const jpeggpu_status st = resize_item(items[i], colors ? static_cast<int>(colors[i]) : color_by_count(items[i].info), p.jobs[i], p.in_w[i], p.in_h[i]);
         if (st != JPEGGPU_SUCCESS) return st;
+        p.all_models = p.all_models || fancy_all_models(p.jobs[i].src);
         p.off_tab_x[i] = off;
         off += align_up(resize_table_bytes(p.in_w[i], out_w, filter), 16);
         p.off_tab_y[i] = off;
@@ -332,62 +349,106 @@ enum jpeggpu_status jpeggpu_ext_planes_to_rgbi(
 
 namespace {
 enum jpeggpu_status planes_to_rgbi_libjpeg(
-    const struct jpeggpu_img_info* info, const struct jpeggpu_img* src, uint8_t* dst, int dst_pitch, int width, int height,
+    const struct jpeggpu_img_info* info, int color, const struct jpeggpu_img* src, uint8_t* dst, int dst_pitch, int width, int height,
     jpeggpu_stream_t stream, bool replicate)
 {
     if (!info || !src || !dst || width <= 0 || height <= 0 || dst_pitch < 3 * width) return JPEGGPU_INVALID_ARGUMENT;
     jg::FancySource s;
-    const jpeggpu_status st = jg::fancy_source(info, nullptr, src, replicate, false, s);
+    const jpeggpu_status st = jg::fancy_source(info, color, nullptr, src, replicate, false, s);
     if (st != JPEGGPU_SUCCESS) return st;
     return jg::launch_rgbi_fancy(s, dst, dst_pitch, width, height, stream) == hipSuccess ? JPEGGPU_SUCCESS : JPEGGPU_INTERNAL_ERROR;
 }
 
 enum jpeggpu_status crop_to_rgbi_libjpeg(
-    const struct jpeggpu_img_info* info, const struct jpeggpu_ext_crop_info* crop, const struct jpeggpu_img* src, uint8_t* dst,
+    const struct jpeggpu_img_info* info, int color, const struct jpeggpu_ext_crop_info* crop, const struct jpeggpu_img* src, uint8_t* dst,
     int dst_pitch, jpeggpu_stream_t stream, bool replicate)
 {
     if (!info || !crop || !src || !dst || crop->width <= 0 || crop->height <= 0 || crop->x < 0 || crop->y < 0 || dst_pitch < 3 * crop->width)
         return JPEGGPU_INVALID_ARGUMENT;
     jg::FancySource s;
-    const jpeggpu_status st = jg::fancy_source(info, crop, src, replicate, true, s);
+    const jpeggpu_status st = jg::fancy_source(info, color, crop, src, replicate, true, s);
     if (st != JPEGGPU_SUCCESS) return st;
     return jg::launch_rgbi_fancy(s, dst, dst_pitch, crop->width, crop->height, stream) == hipSuccess ? JPEGGPU_SUCCESS : JPEGGPU_INTERNAL_ERROR;
 }
 } // namespace
 
+enum jpeggpu_status jpeggpu_ext_planes_to_rgbi_fancy_cs(
+    const struct jpeggpu_img_info* info, enum jpeggpu_ext_color_space color, const struct jpeggpu_img* src, uint8_t* dst, int dst_pitch,
+    int width, int height, jpeggpu_stream_t stream)
+{
+    return planes_to_rgbi_libjpeg(info, color, src, dst, dst_pitch, width, height, stream, false);
+}
+
+enum jpeggpu_status jpeggpu_ext_planes_to_rgbi_replicate_cs(
+    const struct jpeggpu_img_info* info, enum jpeggpu_ext_color_space color, const struct jpeggpu_img* src, uint8_t* dst, int dst_pitch,
+    int width, int height, jpeggpu_stream_t stream)
+{
+    return planes_to_rgbi_libjpeg(info, color, src, dst, dst_pitch, width, height, stream, true);
+}
+
+enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_fancy_cs(
+    const struct jpeggpu_img_info* info, enum jpeggpu_ext_color_space color, const struct jpeggpu_ext_crop_info* crop,
+    const struct jpeggpu_img* src, uint8_t* dst, int dst_pitch, jpeggpu_stream_t stream)
+{
+    return crop_to_rgbi_libjpeg(info, color, crop, src, dst, dst_pitch, stream, false);
+}
+
+enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_replicate_cs(
+    const struct jpeggpu_img_info* info, enum jpeggpu_ext_color_space color, const struct jpeggpu_ext_crop_info* crop,
+    const struct jpeggpu_img* src, uint8_t* dst, int dst_pitch, jpeggpu_stream_t stream)
+{
+    return crop_to_rgbi_libjpeg(info, color, crop, src, dst, dst_pitch, stream, true);
+}
+
+// The entry points without a colour model: grey or YCbCr by the component count.
 enum jpeggpu_status jpeggpu_ext_planes_to_rgbi_fancy(
     const struct jpeggpu_img_info* info, const struct jpeggpu_img* src, uint8_t* dst, int dst_pitch, int width, int height,
     jpeggpu_stream_t stream)
 {
-    return planes_to_rgbi_libjpeg(info, src, dst, dst_pitch, width, height, stream, false);
+    return jpeggpu_ext_planes_to_rgbi_fancy_cs(info, static_cast<jpeggpu_ext_color_space>(jg::color_by_count(info)), src, dst, dst_pitch, width, height, stream);
 }
 
 enum jpeggpu_status jpeggpu_ext_planes_to_rgbi_replicate(
     const struct jpeggpu_img_info* info, const struct jpeggpu_img* src, uint8_t* dst, int dst_pitch, int width, int height,
     jpeggpu_stream_t stream)
 {
-    return planes_to_rgbi_libjpeg(info, src, dst, dst_pitch, width, height, stream, true);
+    return jpeggpu_ext_planes_to_rgbi_replicate_cs(info, static_cast<jpeggpu_ext_color_space>(jg::color_by_count(info)), src, dst, dst_pitch, width, height, stream);
 }
 
 enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_fancy(
     const struct jpeggpu_img_info* info, const struct jpeggpu_ext_crop_info* crop, const struct jpeggpu_img* src, uint8_t* dst,
     int dst_pitch, jpeggpu_stream_t stream)
 {
-    return crop_to_rgbi_libjpeg(info, crop, src, dst, dst_pitch, stream, false);
+    return jpeggpu_ext_crop_to_rgbi_fancy_cs(info, static_cast<jpeggpu_ext_color_space>(jg::color_by_count(info)), crop, src, dst, dst_pitch, stream);
 }
 
 enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_replicate(
     const struct jpeggpu_img_info* info, const struct jpeggpu_ext_crop_info* crop, const struct jpeggpu_img* src, uint8_t* dst,
     int dst_pitch, jpeggpu_stream_t stream)
 {
-    return crop_to_rgbi_libjpeg(info, crop, src, dst, dst_pitch, stream, true);
+    return jpeggpu_ext_crop_to_rgbi_replicate_cs(info, static_cast<jpeggpu_ext_color_space>(jg::color_by_count(info)), crop, src, dst, dst_pitch, stream);
+}
+
+namespace {
+size_t resize_scratch_size(
+    const struct jpeggpu_ext_resize_item* items, const enum jpeggpu_ext_color_space* colors, int n, int out_w, int out_h, enum jpeggpu_ext_filter filter)
+{
+    jg::ResizePlan p;
+    return jg::plan_resize(items, colors, n, out_w, out_h, filter, p) == JPEGGPU_SUCCESS ? p.total : 0;
+}
+} // namespace
+
+size_t jpeggpu_ext_resize_scratch_size_cs(
+    const struct jpeggpu_ext_resize_item* items, const enum jpeggpu_ext_color_space* colors, int n, int out_w, int out_h,
+    enum jpeggpu_ext_filter filter)
+{
+    return colors ? resize_scratch_size(items, colors, n, out_w, out_h, filter) : 0;
 }
 
 size_t jpeggpu_ext_resize_scratch_size(
     const struct jpeggpu_ext_resize_item* items, int n, int out_w, int out_h, enum jpeggpu_ext_filter filter)
 {
-    jg::ResizePlan p;
-    return jg::plan_resize(items, n, out_w, out_h, filter, p) == JPEGGPU_SUCCESS ? p.total : 0;
+    return resize_scratch_size(items, nullptr, n, out_w, out_h, filter);
 }
 
 enum jpeggpu_status jpeggpu_ext_resize_weights(
@@ -405,8 +466,11 @@ enum jpeggpu_status jpeggpu_ext_resize_weights(
     return JPEGGPU_SUCCESS;
 }
 
-enum jpeggpu_status jpeggpu_ext_resize_to_rgb(
+namespace {
+/// `colors` null: each item's model by its component count.
+enum jpeggpu_status resize_to_rgb(
     const struct jpeggpu_ext_resize_item* items,
+    const enum jpeggpu_ext_color_space* colors,
     int n,
     int out_w,
     int out_h,
@@ -418,7 +482,7 @@ enum jpeggpu_status jpeggpu_ext_resize_to_rgb(
     jpeggpu_stream_t stream)
 {
     jg::ResizePlan p;
-    const jpeggpu_status st = jg::plan_resize(items, n, out_w, out_h, filter, p);
+    const jpeggpu_status st = jg::plan_resize(items, colors, n, out_w, out_h, filter, p);
     if (st != JPEGGPU_SUCCESS) return st;
     if (!dst || !d_scratch || (layout != JPEGGPU_EXT_NHWC && layout != JPEGGPU_EXT_NCHW) || scratch_size < p.total)
         return JPEGGPU_INVALID_ARGUMENT;
@@ -463,8 +527,41 @@ enum jpeggpu_status jpeggpu_ext_resize_to_rgb(
     rs.next      = (r + 1) % jg::ResizeStaging::kRing;
     const hipError_t err = jg::launch_resize(
         reinterpret_cast<const jg::ResizeJob*>(base), reinterpret_cast<const int*>(base + p.off_first), n, p.h_tiles, out_w, out_h,
-        layout, dst, stream);
+        layout, p.all_models, dst, stream);
     return err == hipSuccess ? JPEGGPU_SUCCESS : JPEGGPU_INTERNAL_ERROR;
+}
+} // namespace
+
+enum jpeggpu_status jpeggpu_ext_resize_to_rgb_cs(
+    const struct jpeggpu_ext_resize_item* items,
+    const enum jpeggpu_ext_color_space* colors,
+    int n,
+    int out_w,
+    int out_h,
+    enum jpeggpu_ext_filter filter,
+    enum jpeggpu_ext_output_layout layout,
+    uint8_t* dst,
+    void* d_scratch,
+    size_t scratch_size,
+    jpeggpu_stream_t stream)
+{
+    if (!colors) return JPEGGPU_INVALID_ARGUMENT;
+    return resize_to_rgb(items, colors, n, out_w, out_h, filter, layout, dst, d_scratch, scratch_size, stream);
+}
+
+enum jpeggpu_status jpeggpu_ext_resize_to_rgb(
+    const struct jpeggpu_ext_resize_item* items,
+    int n,
+    int out_w,
+    int out_h,
+    enum jpeggpu_ext_filter filter,
+    enum jpeggpu_ext_output_layout layout,
+    uint8_t* dst,
+    void* d_scratch,
+    size_t scratch_size,
+    jpeggpu_stream_t stream)
+{
+    return resize_to_rgb(items, nullptr, n, out_w, out_h, filter, layout, dst, d_scratch, scratch_size, stream);
 }
 
 } // extern "C"

@@ -4,8 +4,10 @@
 //   rgbi_kernel             replication + the JFIF matrix in float -> interleaved RGB (the reference's conv_to_rgbi)
 //   fancy_rgbi_kernel       libjpeg's fancy chroma upsampling + integer YCbCr -> interleaved RGB (jdsample.c, jdcolor.c),
 //                           of a whole image (<false>) or of a rectangle read from the planes' windows (<true>)
+//   fancy_color_kernel      the same for every colour model: RGB-, CMYK- and YCCK-coded files too, as Pillow converts them
 //   resize_h_kernel /       batched resize to one size with Pillow's BILINEAR / BICUBIC arithmetic: the horizontal taps
-//   resize_v_kernel         straight from the planes' windows (fancy RGB in LDS), then the vertical taps (jpeggpu_ext_resize_to_rgb)
+//   resize_v_kernel         straight from the planes' windows (fancy RGB in LDS), then the vertical taps (jpeggpu_ext_resize_to_rgb);
+//                           resize_h_color_kernel: the horizontal pass of a call that holds items of the other models
 //
 // Nothing here is shared with the decode path (jg_kernels.hip): the stage reads finished planes.
 #include "jg_output.hpp"
@@ -104,24 +106,34 @@ __global__ __launch_bounds__(256) void rgbi_kernel(RgbiParams p, uint8_t* __rest
 //
 // Three steps, each written once: fancy_stage puts the samples under a tile of image pixels, with a one-sample halo, in
 // LDS; fancy_pixel makes the RGB of one image pixel from the staged tiles; store_rgb4 writes four of them.
+//
+// `kAllModels`, a compile-time variant of all three and of the kernels built on them. false: grey and YCbCr sources, three
+// tiles (7.8 KB of LDS) -- nearly every file there is. true: every colour model (FancyColor, jg_output.hpp), four tiles:
+// the fourth component of a CMYK or YCCK file is upsampled like the others, by its own FancyMode.
 // ------------------------------------------------------------------------------------------------
 
 constexpr int kFancyTileW = 256, kFancyTileH = 8;
 constexpr int kFancyLdsW = kFancyTileW + 4, kFancyLdsH = kFancyTileH + 2; // samples under a tile at ratio 1, with the halo
-using FancyTile  = uint8_t[kFancyLdsH][kFancyLdsW];
-using FancyTiles = FancyTile[3];
+using FancyTile = uint8_t[kFancyLdsH][kFancyLdsW];
+template <bool kAllModels>
+struct Fancy {
+    static constexpr int kComps = kAllModels ? 4 : 3; // tiles staged, and entries of the tile origins
+    using Tiles = FancyTile[kComps];
+};
 
 /// Stage the samples under the image pixels (ix0, iy0) .. (ix0 + cw - 1, iy0 + ch - 1), cw <= kFancyTileW and ch <=
 /// kFancyTileH: per component, samples floor(ix0 / hr) - 1 .. floor((ix0 + cw - 1) / hr) + 1 and the rows alike, at most
 /// 256 + 2 columns and 8 + 2 rows (ratio 1). (bx, by)[k]: full-plane coordinates of tiles[k][0][0]. The loads are clamped
 /// to the window: that is the edge rule. `kWindowed` false: the windows are the full planes (origin 0), a compile-time
 /// fact. The caller's barrier makes the tiles visible.
-template <bool kWindowed>
-__device__ __forceinline__ void fancy_stage(const FancySource& s, FancyTiles& tiles, int ix0, int iy0, int cw, int ch, int (&bx)[3], int (&by)[3])
+template <bool kWindowed, bool kAllModels>
+__device__ __forceinline__ void fancy_stage(
+    const FancySource& s, typename Fancy<kAllModels>::Tiles& tiles, int ix0, int iy0, int cw, int ch,
+    int (&bx)[Fancy<kAllModels>::kComps], int (&by)[Fancy<kAllModels>::kComps])
 {
     const int t = threadIdx.x;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < Fancy<kAllModels>::kComps; ++k) {
         const FancyComp& c = s.comp[k];
         bx[k] = ix0 / c.hr - 1;
         by[k] = iy0 / c.vr - 1;
@@ -159,16 +171,43 @@ __device__ __forceinline__ int fancy_sample(const FancyComp& c, const FancyTile&
 
 __device__ __forceinline__ uint32_t clamp255(int v) { return static_cast<uint32_t>(min(max(v, 0), 255)); }
 
-/// R, G, B of image pixel (x, y) from the staged tiles: jdcolor.c's ycc_rgb_convert, or the grey sample three times.
-__device__ __forceinline__ void fancy_pixel(const FancySource& s, const FancyTiles& tiles, const int (&bx)[3], const int (&by)[3], int x, int y, uint32_t* rgb)
+/// Pillow's cmyk2rgb (Convert.c) for one channel: K - MULDIV255(ink, K), ink and K in 0..255. The product is below 2^16.
+__device__ __forceinline__ uint32_t cmyk_channel(int ink, int K)
+{
+    const int t = ink * K + 128;
+    return clamp255(K - (((t >> 8) + t) >> 8));
+}
+
+/// R, G, B of image pixel (x, y) from the staged tiles: jdcolor.c's ycc_rgb_convert, or the grey sample three times;
+/// with kAllModels also the samples as they are (RGB) and, of four components, the CMYK rule on top of either: the inks
+/// are 255 - the samples (CMYK) or r, g, b themselves (YCCK).
+template <bool kAllModels>
+__device__ __forceinline__ void fancy_pixel(
+    const FancySource& s, const typename Fancy<kAllModels>::Tiles& tiles, const int (&bx)[Fancy<kAllModels>::kComps],
+    const int (&by)[Fancy<kAllModels>::kComps], int x, int y, uint32_t* rgb)
 {
     const int Y = fancy_sample(s.comp[0], tiles[0], bx[0], by[0], x, y);
-    if (s.ncomp == 3) {
-        const int cb = fancy_sample(s.comp[1], tiles[1], bx[1], by[1], x, y) - 128;
-        const int cr = fancy_sample(s.comp[2], tiles[2], bx[2], by[2], x, y) - 128;
-        rgb[0] = clamp255(Y + ((91881 * cr + (1 << 15)) >> 16));                // FIX(1.40200)
-        rgb[1] = clamp255(Y + ((-22554 * cb - 46802 * cr + (1 << 15)) >> 16)); // FIX(0.34414), FIX(0.71414)
-        rgb[2] = clamp255(Y + ((116130 * cb + (1 << 15)) >> 16));               // FIX(1.77200)
+    if (kAllModels ? s.ncomp >= 3 : s.ncomp == 3) {
+        const int c1 = fancy_sample(s.comp[1], tiles[1], bx[1], by[1], x, y);
+        const int c2 = fancy_sample(s.comp[2], tiles[2], bx[2], by[2], x, y);
+        const bool ycc = !kAllModels || s.color == kFancyYCbCr || s.color == kFancyYCCK;
+        if (ycc) {
+            const int cb = c1 - 128, cr = c2 - 128;
+            rgb[0] = clamp255(Y + ((91881 * cr + (1 << 15)) >> 16));                // FIX(1.40200)
+            rgb[1] = clamp255(Y + ((-22554 * cb - 46802 * cr + (1 << 15)) >> 16)); // FIX(0.34414), FIX(0.71414)
+            rgb[2] = clamp255(Y + ((116130 * cb + (1 << 15)) >> 16));               // FIX(1.77200)
+        } else {
+            rgb[0] = static_cast<uint32_t>(Y);
+            rgb[1] = static_cast<uint32_t>(c1);
+            rgb[2] = static_cast<uint32_t>(c2);
+        }
+        if constexpr (kAllModels) {
+            if (s.ncomp == 4) {
+                const int K = fancy_sample(s.comp[3], tiles[3], bx[3], by[3], x, y);
+#pragma unroll
+                for (int i = 0; i < 3; ++i) rgb[i] = cmyk_channel(ycc ? static_cast<int>(rgb[i]) : 255 - static_cast<int>(rgb[i]), K);
+            }
+        }
     } else {
         rgb[0] = rgb[1] = rgb[2] = static_cast<uint32_t>(Y);
     }
@@ -177,16 +216,17 @@ __device__ __forceinline__ void fancy_pixel(const FancySource& s, const FancyTil
 /// Interleaved 8-bit RGB of the source's rectangle: output pixel (x, y) is image pixel (x + p.x, y + p.y). One
 /// workgroup: an output tile of kFancyTileW x kFancyTileH pixels; each lane converts a 2 x 4 quad -- 4 pixels of 2 rows
 /// -- and stores each row's 12 bytes. `kWindowed` false is the whole image, whose window and rectangle terms are zero
-/// and cost nothing.
-template <bool kWindowed>
-__global__ __launch_bounds__(256) void fancy_rgbi_kernel(FancySource p, uint8_t* __restrict__ dst, int dst_pitch, int width, int height)
+/// and cost nothing. The two kernels below are its instantiations by name: fancy_rgbi_kernel for grey and YCbCr sources,
+/// fancy_color_kernel for every model.
+template <bool kWindowed, bool kAllModels>
+__device__ __forceinline__ void fancy_rgbi_tile(const FancySource& p, uint8_t* dst, int dst_pitch, int width, int height)
 {
-    __shared__ FancyTiles s_t;
+    __shared__ typename Fancy<kAllModels>::Tiles s_t;
     const int t  = threadIdx.x;
     const int x0 = blockIdx.x * kFancyTileW, y0 = blockIdx.y * kFancyTileH;
     const int px = kWindowed ? p.x : 0, py = kWindowed ? p.y : 0;
-    int bx[3], by[3];
-    fancy_stage<kWindowed>(p, s_t, x0 + px, y0 + py, kFancyTileW, kFancyTileH, bx, by);
+    int bx[Fancy<kAllModels>::kComps], by[Fancy<kAllModels>::kComps];
+    fancy_stage<kWindowed, kAllModels>(p, s_t, x0 + px, y0 + py, kFancyTileW, kFancyTileH, bx, by);
     __syncthreads();
     const int x = x0 + 4 * (t & 63);
     if (x >= width) return;
@@ -196,9 +236,21 @@ __global__ __launch_bounds__(256) void fancy_rgbi_kernel(FancySource p, uint8_t*
         if (y >= height) break;
         uint32_t out[12];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) fancy_pixel(p, s_t, bx, by, min(x + i, width - 1) + px, y + py, &out[3 * i]);
+        for (int i = 0; i < 4; ++i) fancy_pixel<kAllModels>(p, s_t, bx, by, min(x + i, width - 1) + px, y + py, &out[3 * i]);
         store_rgb4(dst + static_cast<size_t>(y) * dst_pitch + static_cast<size_t>(x) * 3, out, min(4, width - x));
     }
+}
+
+template <bool kWindowed>
+__global__ __launch_bounds__(256) void fancy_rgbi_kernel(FancySource p, uint8_t* __restrict__ dst, int dst_pitch, int width, int height)
+{
+    fancy_rgbi_tile<kWindowed, false>(p, dst, dst_pitch, width, height);
+}
+
+template <bool kWindowed>
+__global__ __launch_bounds__(256) void fancy_color_kernel(FancySource p, uint8_t* __restrict__ dst, int dst_pitch, int width, int height)
+{
+    fancy_rgbi_tile<kWindowed, true>(p, dst, dst_pitch, width, height);
 }
 
 /// Taps of a horizontal-pass workgroup's columns: int32 weights[columns][taps], from LDS when they fit
@@ -224,11 +276,14 @@ __device__ __forceinline__ void resize_taps_h(const W* w, const uint32_t* px, in
 /// samples under a chunk are staged with their halo (fancy_stage), each pixel gets fancy_pixel into LDS, and each lane
 /// accumulates its output pixel's taps that fall in the chunk. The result is clamped to uint8 (Pillow keeps its
 /// intermediate image in 8 bits) and written to the item's `mid` rows; the crop's full-resolution RGB never leaves LDS.
-__global__ __launch_bounds__(256) void resize_h_kernel(const ResizeJob* __restrict__ jobs, const int* __restrict__ first_tile, int n, int out_w)
+/// `kAllModels` (resize_h_color_kernel): a call with an item that is not grey or YCbCr; its items of those two models are
+/// converted as ever. resize_h_kernel is the instantiation for calls of grey and YCbCr items alone. (The pointers are
+/// __restrict__ on the kernels only: the qualifier repeated here cost resize_h_kernel ten VGPRs once inlined.)
+template <bool kAllModels>
+__device__ __forceinline__ void resize_h_tile(
+    const ResizeJob* jobs, const int* first_tile, int n, int out_w, typename Fancy<kAllModels>::Tiles& s_t,
+    uint32_t (&s_rgb)[kResizeHTileH][kFancyTileW], int (&s_w)[kResizeHTileW * kResizeLdsTaps])
 {
-    __shared__ FancyTiles s_t;
-    __shared__ uint32_t s_rgb[kResizeHTileH][kFancyTileW];
-    __shared__ int s_w[kResizeHTileW * kResizeLdsTaps];
     const int b = blockIdx.x;
     int lo = 0, hi = n - 1; // the last item whose first tile is <= b
     while (lo < hi) {
@@ -261,14 +316,14 @@ __global__ __launch_bounds__(256) void resize_h_kernel(const ResizeJob* __restri
     for (int c0 = a; c0 < e; c0 += kFancyTileW) {
         const int cw  = min(kFancyTileW, e - c0);
         const int ix0 = c0 + src.x, iy0 = r0 + src.y; // the chunk's origin in the image
-        int bx[3], by[3];
-        fancy_stage<true>(src, s_t, ix0, iy0, cw, nr, bx, by);
+        int bx[Fancy<kAllModels>::kComps], by[Fancy<kAllModels>::kComps];
+        fancy_stage<true, kAllModels>(src, s_t, ix0, iy0, cw, nr, bx, by);
         __syncthreads();
         for (int q = t; q < kResizeHTileH * kFancyTileW; q += 256) {
             const int qy = q / kFancyTileW, qx = q % kFancyTileW;
             if (qy >= nr || qx >= cw) continue;
             uint32_t rgb[3];
-            fancy_pixel(src, s_t, bx, by, ix0 + qx, iy0 + qy, rgb);
+            fancy_pixel<kAllModels>(src, s_t, bx, by, ix0 + qx, iy0 + qy, rgb);
             s_rgb[qy][qx] = rgb[0] | rgb[1] << 8 | rgb[2] << 16;
         }
         __syncthreads();
@@ -285,6 +340,22 @@ __global__ __launch_bounds__(256) void resize_h_kernel(const ResizeJob* __restri
 #pragma unroll
         for (int c = 0; c < 3; ++c) o[c] = static_cast<uint8_t>(clamp255((acc[c] + (1 << 21)) >> 22));
     }
+}
+
+__global__ __launch_bounds__(256) void resize_h_kernel(const ResizeJob* __restrict__ jobs, const int* __restrict__ first_tile, int n, int out_w)
+{
+    __shared__ Fancy<false>::Tiles s_t;
+    __shared__ uint32_t s_rgb[kResizeHTileH][kFancyTileW];
+    __shared__ int s_w[kResizeHTileW * kResizeLdsTaps];
+    resize_h_tile<false>(jobs, first_tile, n, out_w, s_t, s_rgb, s_w);
+}
+
+__global__ __launch_bounds__(256) void resize_h_color_kernel(const ResizeJob* __restrict__ jobs, const int* __restrict__ first_tile, int n, int out_w)
+{
+    __shared__ Fancy<true>::Tiles s_t;
+    __shared__ uint32_t s_rgb[kResizeHTileH][kFancyTileW];
+    __shared__ int s_w[kResizeHTileW * kResizeLdsTaps];
+    resize_h_tile<true>(jobs, first_tile, n, out_w, s_t, s_rgb, s_w);
 }
 
 /// Batched resize, pass 2: the vertical taps over the items' `mid` rows, one item per blockIdx.y. Each lane makes 4
@@ -386,17 +457,23 @@ hipError_t launch_rgbi_fancy(const FancySource& src, uint8_t* dst, int dst_pitch
     bool windowed = src.x != 0 || src.y != 0;
     for (const FancyComp& c : src.comp) windowed = windowed || c.ox != 0 || c.oy != 0;
     const dim3 grid((width + kFancyTileW - 1) / kFancyTileW, (height + kFancyTileH - 1) / kFancyTileH);
-    if (windowed) fancy_rgbi_kernel<true><<<grid, 256, 0, stream>>>(src, dst, dst_pitch, width, height);
-    else fancy_rgbi_kernel<false><<<grid, 256, 0, stream>>>(src, dst, dst_pitch, width, height);
+    if (fancy_all_models(src)) {
+        if (windowed) fancy_color_kernel<true><<<grid, 256, 0, stream>>>(src, dst, dst_pitch, width, height);
+        else fancy_color_kernel<false><<<grid, 256, 0, stream>>>(src, dst, dst_pitch, width, height);
+    } else {
+        if (windowed) fancy_rgbi_kernel<true><<<grid, 256, 0, stream>>>(src, dst, dst_pitch, width, height);
+        else fancy_rgbi_kernel<false><<<grid, 256, 0, stream>>>(src, dst, dst_pitch, width, height);
+    }
     return hipGetLastError();
 }
 
 hipError_t launch_resize(
-    const ResizeJob* d_jobs, const int* d_first_tile, int n, int h_tiles, int out_w, int out_h, int layout,
+    const ResizeJob* d_jobs, const int* d_first_tile, int n, int h_tiles, int out_w, int out_h, int layout, bool all_models,
     uint8_t* dst, hipStream_t stream)
 {
     if (n <= 0 || h_tiles <= 0 || out_w <= 0 || out_h <= 0) return hipSuccess;
-    resize_h_kernel<<<h_tiles, 256, 0, stream>>>(d_jobs, d_first_tile, n, out_w);
+    if (all_models) resize_h_color_kernel<<<h_tiles, 256, 0, stream>>>(d_jobs, d_first_tile, n, out_w);
+    else resize_h_kernel<<<h_tiles, 256, 0, stream>>>(d_jobs, d_first_tile, n, out_w);
     const int v_tiles = ((out_w + kResizeVTileW - 1) / kResizeVTileW) * ((out_h + kResizeVTileH - 1) / kResizeVTileH);
     resize_v_kernel<<<dim3(v_tiles, n), 256, 0, stream>>>(d_jobs, out_w, out_h, layout, dst);
     return hipGetLastError();

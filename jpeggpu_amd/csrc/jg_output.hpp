@@ -45,14 +45,28 @@ struct FancyComp {
     int hr, vr;      // output pixels per sample: h_max / h_c, v_max / v_c
     int mode;        // FancyMode
 };
+/// The colour model of a source: what the upsampled samples of a pixel mean (the values of enum jpeggpu_ext_color_space).
+///   grey      the sample three times
+///   YCbCr     jdcolor.c's ycc_rgb_convert
+///   RGB       the three samples as they are
+///   CMYK      Pillow's cmyk2rgb of Adobe's inverted samples s_0..s_3: the inks c_i = 255 - s_i, K = s_3,
+///             out_i = K - MULDIV255(c_i, K), with MULDIV255(a, b) = ((t >> 8) + t) >> 8, t = a b + 128 (exact in 32-bit
+///             integers, no division)
+///   YCCK      ycc_rgb_convert of components 0..2, then the CMYK rule with the inks c_i = r, g, b (libjpeg hands out
+///             255 - r, ... in place of the samples, and Pillow inverts those like any CMYK file's)
+enum FancyColor : int { kFancyGray = 1, kFancyYCbCr = 2, kFancyRGB = 3, kFancyCMYK = 4, kFancyYCCK = 5 };
 struct FancySource {
-    FancyComp comp[3]; // grey: every entry is component 0
+    FancyComp comp[4]; // entries from ncomp on are component 0
     int x, y;
-    int ncomp;         // 1 (grey to R, G, B) or 3
+    int ncomp;         // 1, 3 or 4
+    int color;         // FancyColor; one that fits ncomp (the host checks it)
 };
+/// Grey and YCbCr sources take the kernels' three-tile instantiations; RGB, CMYK and YCCK ones the instantiations that
+/// stage a fourth tile and know every model.
+inline bool fancy_all_models(const FancySource& s) { return s.color != kFancyGray && s.color != kFancyYCbCr; }
 
-/// libjpeg's fancy upsampling + integer YCbCr -> interleaved RGB8 (jdsample.c, jdcolor.c) of the width x height pixels
-/// at the source's rectangle origin.
+/// libjpeg's fancy upsampling + the source's colour conversion -> interleaved RGB8 (jdsample.c, jdcolor.c, Pillow's
+/// Convert.c) of the width x height pixels at the source's rectangle origin.
 hipError_t launch_rgbi_fancy(const FancySource& src, uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream);
 
 /// One item of a batched resize (launch_resize), in device memory: a source rectangle resampled to out_w x out_h RGB by
@@ -77,9 +91,10 @@ inline int resize_h_tiles(int rows, int out_w)
 }
 /// The two passes for `n` items: `d_jobs` ResizeJob[n] and `d_first_tile` int[n] (each item's first horizontal-pass
 /// workgroup; `h_tiles` of them in all) in device memory. `layout` 0: dst is n x out_h x out_w x 3 (NHWC), 1: n x 3 x out_h
-/// x out_w (NCHW).
+/// x out_w (NCHW). `all_models`: some item is not grey or YCbCr (fancy_all_models); the horizontal pass then runs as the
+/// instantiation that knows every model, for all items of the call.
 hipError_t launch_resize(
-    const ResizeJob* d_jobs, const int* d_first_tile, int n, int h_tiles, int out_w, int out_h, int layout,
+    const ResizeJob* d_jobs, const int* d_first_tile, int n, int h_tiles, int out_w, int out_h, int layout, bool all_models,
     uint8_t* dst, hipStream_t stream);
 
 } // namespace jg

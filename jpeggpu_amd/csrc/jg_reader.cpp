@@ -16,7 +16,7 @@ namespace jg {
 
 namespace {
 constexpr uint8_t M_SOF0 = 0xC0, M_SOF1 = 0xC1, M_DHT = 0xC4, M_RST0 = 0xD0, M_RST7 = 0xD7,
-                  M_SOI = 0xD8, M_EOI = 0xD9, M_SOS = 0xDA, M_DQT = 0xDB, M_DRI = 0xDD;
+                  M_SOI = 0xD8, M_EOI = 0xD9, M_SOS = 0xDA, M_DQT = 0xDB, M_DRI = 0xDD, M_APP0 = 0xE0, M_APP14 = 0xEE;
 constexpr int kNatural[64] = JG_ORDER_NATURAL;
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
@@ -382,6 +382,23 @@ jpeggpu_status Reader::skip_segment(const Logger& log)
     log.log("\twarning: skipping this segment\n");
     cur_ += length - 2;
     return JPEGGPU_SUCCESS;
+}
+
+/// What an APP0 or APP14 segment in front of the first scan says about the colour model (jdmarker.c, examine_app0 and
+/// examine_app14): "JFIF\0" in a segment of at least 16 bytes; "Adobe" in one of at least 14, whose transform flag is data
+/// byte 11. cur_ is at the segment's length field and stays there: the caller skips the segment as it skips every APPn,
+/// and a short or malformed one tells nothing.
+void Reader::note_app_segment(uint8_t marker)
+{
+    if (s.num_scans > 0 || remaining() < 2) return;
+    const size_t length = static_cast<size_t>(cur_[0]) << 8 | cur_[1];
+    if (length < 2 || remaining() < length) return;
+    const uint8_t* data = cur_ + 2;
+    if (marker == M_APP0 && length >= 16 && std::memcmp(data, "JFIF\0", 5) == 0) s.saw_jfif = true;
+    if (marker == M_APP14 && length >= 14 && std::memcmp(data, "Adobe", 5) == 0) {
+        s.saw_adobe       = true;
+        s.adobe_transform = data[11];
+    }
 }
 
 jpeggpu_status Reader::read_sos(const Logger& log)
@@ -899,6 +916,7 @@ jpeggpu_status Reader::parse(const uint8_t* data, size_t size, int subseq_bytes,
         } else if (marker == M_SOI || (marker >= M_RST0 && marker <= M_RST7) || marker == 0x01) {
             return JPEGGPU_INVALID_JPEG; // stand-alone markers have no place here
         } else {
+            if (marker == M_APP0 || marker == M_APP14) note_app_segment(marker);
             st = skip_segment(log);
         }
         if (st != JPEGGPU_SUCCESS) return st;
@@ -911,6 +929,14 @@ jpeggpu_status Reader::parse(const uint8_t* data, size_t size, int subseq_bytes,
             return JPEGGPU_INVALID_JPEG;
         }
     }
+    // the colour model (jg_reader.hpp, ColorSpace)
+    const bool ids_rgb = s.num_comp == 3 && s.comp[0].id == 'R' && s.comp[1].id == 'G' && s.comp[2].id == 'B';
+    if (s.num_comp == 1) s.color_space = kColorGray;
+    else if (s.num_comp == 3)
+        s.color_space = s.saw_jfif ? kColorYCbCr : s.saw_adobe ? (s.adobe_transform == 0 ? kColorRGB : kColorYCbCr) : ids_rgb ? kColorRGB : kColorYCbCr;
+    else if (s.num_comp == 4) s.color_space = s.saw_adobe && s.adobe_transform != 0 ? kColorYCCK : kColorCMYK;
+    else s.color_space = kColorUnknown;
+    log.log("colour model %d (jfif %d, adobe %d, transform %d)\n", s.color_space, s.saw_jfif, s.saw_adobe, s.adobe_transform);
     if (shard_world > 1) return apply_segment_shard(shard_rank, shard_world, log);
     return JPEGGPU_SUCCESS;
 }

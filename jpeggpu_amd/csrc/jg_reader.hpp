@@ -4,6 +4,8 @@
 // SOI / SOF0 / SOF1 / DHT / DQT / DRI / SOS / EOI, the same status codes for the same defects, the
 // same geometry rules (plane size ceil(size*ss/ss_max), MCU-rounded data size, single-component
 // frames forced to 1x1 sampling). Differences, each deliberate:
+//   the JFIF APP0 and Adobe APP14 segments are looked at (the reference skips every APPn): with the component ids they
+//   give the frame's colour model (ColorSpace below); nothing else of the decode depends on them;
 //   B-1 Huffman tables persist across scans as T.81 requires (the reference loses them);
 //   B-2 a non-interleaved scan has one data unit per MCU and ceil(size/8) blocks per row;
 //   B-6 length fields and table ids are range-checked;
@@ -80,6 +82,14 @@ struct Scan {
     int max_tail_parts  = 0; // entries of the device's tail_parts array
 };
 
+/// The colour model of a frame's components, by libjpeg's rules (jdapimin.c, default_decompress_parms); the values are
+/// those of enum jpeggpu_ext_color_space (jpeggpu_ext.h).
+///   1 component: grey. 3 components: a JFIF APP0 segment says YCbCr, even beside an Adobe segment; otherwise an Adobe
+///   APP14 segment's transform byte (0: RGB, anything else: YCbCr); otherwise the component ids ('R', 'G', 'B': RGB,
+///   anything else: YCbCr). 4 components: an Adobe segment with transform 0, or none, is CMYK; any other transform YCCK.
+///   2 components: unknown.
+enum ColorSpace : int { kColorUnknown = 0, kColorGray = 1, kColorYCbCr = 2, kColorRGB = 3, kColorCMYK = 4, kColorYCCK = 5 };
+
 struct Stream {
     int size_x = 0, size_y = 0;
     int hs_max = 0, vs_max = 0;
@@ -92,6 +102,10 @@ struct Stream {
     // Transferred byte range of the file: [xfer_begin, xfer_end). Buffer offset = file offset - xfer_begin.
     size_t xfer_begin = 0;
     size_t xfer_end   = 0;
+    // What the application segments in front of the first scan say about the colour model, and the model itself
+    bool saw_jfif = false, saw_adobe = false;
+    uint8_t adobe_transform = 0;
+    int color_space = kColorUnknown; // ColorSpace
 };
 
 /// Requests for a per-image choice (Reader::parse): 0 or -N, N = about how many images share the call (kBatchHintFull:
@@ -184,6 +198,7 @@ struct Reader {
     jpeggpu_status read_sos(const Logger& log);
     jpeggpu_status walk_scan(Scan& scan, const Logger& log);
     jpeggpu_status skip_segment(const Logger& log);
+    void note_app_segment(uint8_t marker);
     jpeggpu_status apply_segment_shard(int rank, int world, const Logger& log);
 };
 
