@@ -30,6 +30,8 @@
  *                                      rules (JFIF and Adobe segments, component ids)
  *   jpeggpu_ext_*_cs                   the libjpeg-exact RGB calls above for a given colour model: the RGB Pillow's
  *                                      Image.convert("RGB") makes of files of all five
+ *   jpeggpu_ext_set_progressive /      progressive JPEGs (SOF2), per decoder and off by default: their scans are decoded
+ *   jpeggpu_ext_get_progressive_info   on the device into coefficient buffers and handed to the IDCT stage
  */
 #ifndef JPEGGPU_JPEGGPU_EXT_H_
 #define JPEGGPU_JPEGGPU_EXT_H_
@@ -268,7 +270,7 @@ enum jpeggpu_ext_stage {
     JPEGGPU_EXT_STAGE_SYNC_INTRA = 2,
     JPEGGPU_EXT_STAGE_SYNC_INTER = 3,
     JPEGGPU_EXT_STAGE_TAILS      = 4,
-    JPEGGPU_EXT_STAGE_WRITE      = 5,
+    JPEGGPU_EXT_STAGE_WRITE      = 5, /* also the progressive launches of a call: zeroing, one launch per level, the hand-over */
     JPEGGPU_EXT_STAGE_IDCT       = 6,
     JPEGGPU_EXT_NUM_STAGES       = 7
 };
@@ -578,6 +580,38 @@ enum jpeggpu_status jpeggpu_ext_resize_to_rgb_cs(
     void* d_scratch,
     size_t scratch_size,
     jpeggpu_stream_t stream);
+
+/* Progressive JPEGs (SOF2; Huffman-coded, 8-bit samples, 1..4 components). OFF by default: a decoder that was not told
+ * otherwise answers JPEGGPU_NOT_SUPPORTED to SOF2, as the reference does. jpeggpu_ext_set_progressive(decoder, 1) takes
+ * effect from the next jpeggpu_decoder_parse_header; SOF3 and SOF5..SOF15 (lossless, hierarchical, arithmetic-coded)
+ * stay JPEGGPU_NOT_SUPPORTED. Up to 64 scans; scan headers that break T.81 G.1.1.1.1 are JPEGGPU_INVALID_JPEG; a scan
+ * that breaks the progression (a first scan of coefficients already coded, a refinement of coefficients that are not at
+ * its bit position, an AC scan before the component's first DC scan) is JPEGGPU_NOT_SUPPORTED, where libjpeg warns and
+ * decodes on. A file may stop early: coefficients no scan coded are 0, bits no scan refined stay 0 (libjpeg would smooth
+ * the blocks of such a file, this decoder does not; files an encoder finished decode to libjpeg's pixels).
+ *
+ * The scans are decoded on the device, one lane per restart segment of a scan and one launch per LEVEL of the scan
+ * script (a scan's level: 0 if no earlier scan touches its coefficients, else one more than the highest level among
+ * those that do), into per-component coefficient buffers inside d_tmp: int16[blocks_y][blocks_x][64], block raster over
+ * the MCU-padded grid, natural order inside a block, zeroed on the stream at the start of every decode. The finished
+ * frame is then presented to the IDCT stage as one non-interleaved baseline scan per component: jpeggpu_ext_get_layout
+ * reports num_components scans without subsequences, and every scale, scale mode, IDCT method, crop (all entropy-coded
+ * data is decoded, only the IDCT is windowed), colour model and the batched calls work as for a baseline file.
+ * jpeggpu_ext_set_device_scan is ignored for a progressive image (its scans are walked on the host);
+ * jpeggpu_ext_set_segment_shard with more than one rank is refused at parse_header with JPEGGPU_NOT_SUPPORTED. Stage
+ * timing counts the progressive launches in JPEGGPU_EXT_STAGE_WRITE. */
+struct jpeggpu_ext_progressive_info {
+    int progressive; /* 1: the last parsed image is a progressive frame (all else 0 otherwise) */
+    int num_scans;   /* scans of the file */
+    int num_levels;
+    size_t off_coefficients[JPEGGPU_MAX_COMP]; /* byte offset of each component's coefficient buffer in d_tmp */
+    int blocks_x[JPEGGPU_MAX_COMP];            /* the buffer's block grid (MCU-padded) */
+    int blocks_y[JPEGGPU_MAX_COMP];
+    int visible_blocks_x[JPEGGPU_MAX_COMP];    /* ceil(plane size / 8): the blocks the IDCT stage is handed */
+    int visible_blocks_y[JPEGGPU_MAX_COMP];
+};
+enum jpeggpu_status jpeggpu_ext_set_progressive(jpeggpu_decoder_t decoder, int enable);
+enum jpeggpu_status jpeggpu_ext_get_progressive_info(jpeggpu_decoder_t decoder, struct jpeggpu_ext_progressive_info* info);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,7 @@ from .api import (  # noqa: F401
     Decoder,
     ImgInfo,
     JpegGpuError,
+    ProgressiveInfo,
     ScaleInfo,
     Status,
     crop_to_rgb,

@@ -67,6 +67,15 @@ class ScaleInfo(C.Structure):
     _fields_ = [("scale_denom", C.c_int), ("mode", C.c_int), ("block_size", C.c_int * MAX_COMP), ("fancy_upsampling", C.c_int)]
 
 
+class ProgressiveInfo(C.Structure):
+    """struct jpeggpu_ext_progressive_info: whether the last parsed image is a progressive frame, its scans and levels, and
+    each component's coefficient buffer in d_tmp: int16 [blocks_y, blocks_x, 64] over the MCU-padded grid, of which the
+    IDCT stage is handed the visible blocks."""
+    _fields_ = [("progressive", C.c_int), ("num_scans", C.c_int), ("num_levels", C.c_int),
+                ("off_coefficients", C.c_size_t * MAX_COMP), ("blocks_x", C.c_int * MAX_COMP), ("blocks_y", C.c_int * MAX_COMP),
+                ("visible_blocks_x", C.c_int * MAX_COMP), ("visible_blocks_y", C.c_int * MAX_COMP)]
+
+
 class ResizeItem(C.Structure):
     """struct jpeggpu_ext_resize_item: a decoded image's info and planes, and its crop (NULL: the whole image)."""
     _fields_ = [("info", C.POINTER(ImgInfo)), ("crop", C.POINTER(CropInfo)), ("src", C.POINTER(Img))]
@@ -196,6 +205,8 @@ def lib():
     L.jpeggpu_ext_resize_to_rgb_cs.argtypes = [
         C.POINTER(ResizeItem), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
         C.c_void_p]
+    L.jpeggpu_ext_set_progressive.argtypes = [dec, C.c_int]
+    L.jpeggpu_ext_get_progressive_info.argtypes = [dec, C.POINTER(ProgressiveInfo)]
     L.jpeggpu_ext_resize_weights.argtypes = [
         C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
     _lib = L
@@ -291,6 +302,17 @@ class Decoder:
         cs = C.c_int()
         _check(lib().jpeggpu_ext_get_color_space(self._h, C.byref(cs)), "jpeggpu_ext_get_color_space")
         return ColorSpace(cs.value)
+
+    def set_progressive(self, on: bool = True):
+        """Read progressive JPEGs (SOF2) from the next parse_header on; off by default, when they are NOT_SUPPORTED
+        (jpeggpu_ext_set_progressive)."""
+        _check(lib().jpeggpu_ext_set_progressive(self._h, int(on)), "jpeggpu_ext_set_progressive")
+
+    def progressive_info(self) -> ProgressiveInfo:
+        """jpeggpu_ext_get_progressive_info of the last parsed image."""
+        pi = ProgressiveInfo()
+        _check(lib().jpeggpu_ext_get_progressive_info(self._h, C.byref(pi)), "jpeggpu_ext_get_progressive_info")
+        return pi
 
     def set_idct(self, method: str):
         """The full-size IDCT of the next parsed images: "reference" (the default) or "islow", libjpeg-turbo's
@@ -452,7 +474,7 @@ def draft_scale(width, height, requested):
 
 
 def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp=False, device_scan=False, scale=1,
-                     idct="reference", crop=None, scale_mode="uniform", return_color=False):
+                     idct="reference", crop=None, scale_mode="uniform", return_color=False, progressive=False):
     """Convenience wrapper used by tests: full call sequence on torch's current stream, returns the
     planes as torch uint8 tensors on `device` (torch is only the allocator / stream provider). With
     `device_scan` the restart markers are found on the device and a status it reports there is raised.
@@ -460,7 +482,8 @@ def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp
     `crop`: (x, y, w, h) -- only the planes' windows for that rectangle are decoded (Decoder.set_crop), and the CropInfo
     is returned as well: (planes, info, crop_info). `scale_mode`: "uniform" or "libjpeg" (Decoder.set_scale_mode); the
     returned info then carries the planes' effective sampling factors. `return_color`: the file's ColorSpace
-    (Decoder.color_space) is appended to what is returned."""
+    (Decoder.color_space) is appended to what is returned. `progressive`: progressive files are decoded
+    (Decoder.set_progressive); with `return_tmp` the ProgressiveInfo follows the layout."""
     import torch
 
     dec = Decoder(subseq_bytes)
@@ -475,6 +498,8 @@ def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp
             dec.set_device_scan(True)
         if crop is not None:
             dec.set_crop(*crop)
+        if progressive:
+            dec.set_progressive(True)
         info = dec.parse_header(data)
         n = dec.get_buffer_size()
         tmp = torch.empty(n + 256, dtype=torch.uint8, device=device)
@@ -492,6 +517,8 @@ def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp
             out += (dec.crop_info(),)
         if return_tmp:
             out += (tmp, base, dec.layout())
+            if progressive:
+                out += (dec.progressive_info(),)
         if return_color:
             out += (dec.color_space(),)
         return out
@@ -567,10 +594,10 @@ def decode_to_rgb(data: bytes, device="cuda:0", device_scan=False, crop=None, sc
     w, h) only that rectangle is decoded: an (h, w, 3) tensor equal to decode_to_rgb(data)[y:y + h, x:x + w].
     `scale` = d in 2, 4, 8: the image at 1/d as libjpeg-turbo scales it (the libjpeg scale mode: per-component IDCT sizes,
     replication instead of fancy upsampling at 1/8), equal to im.draft("RGB", (W // d, H // d)); im.convert("RGB") in
-    Pillow; `crop` is then in pixels of that image."""
+    Pillow; `crop` is then in pixels of that image. Progressive files are decoded too (Decoder.set_progressive)."""
     import torch
 
-    kw = dict(device=device, device_scan=device_scan, idct="islow", scale=scale, scale_mode="libjpeg", return_color=True)
+    kw = dict(device=device, device_scan=device_scan, idct="islow", scale=scale, scale_mode="libjpeg", return_color=True, progressive=True)
     if crop is not None:
         planes, info, crop_info, color = decode_to_planes(data, crop=crop, **kw)
         rgb = crop_to_rgb(planes, info, crop_info, replicate=_needs_replication(info, scale), color=color)
@@ -733,6 +760,7 @@ def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", devi
             decs.append(dec)
             dec.set_batch_hint(n)
             dec.set_idct("islow")
+            dec.set_progressive(True)
             if scale != 1:
                 dec.set_scale(scale)
                 dec.set_scale_mode("libjpeg")

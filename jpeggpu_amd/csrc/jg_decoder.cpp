@@ -10,6 +10,8 @@
 //     pass and no DC pass (decoder.cpp:240-314).
 #include "jg_front.hpp"
 #include "jg_kernels.hpp"
+#include "jg_prog.hpp"
+#include "jg_prog_plan.hpp"
 #include "jg_reader.hpp"
 #include "jg_selftest_data.h"
 #include "jg_staging.hpp"
@@ -55,12 +57,20 @@ struct ScanPlan {
     uint32_t num_windows = 0;
 };
 
+/// A progressive image's part of the plan (jg_prog_core.h): its descriptors in the blob, its coefficient buffers in d_tmp.
+struct ProgPlan {
+    bool on = false;
+    ProgBlobLayout blob;                                        // jg_prog_plan.hpp: offsets inside the blob, the work list
+    size_t coef[kMaxComp] = {}, coef_begin = 0, coef_bytes = 0; // offsets inside d_tmp
+};
+
 struct Plan {
     size_t off_bytes = 0, bytes_len = 0;
     size_t off_blob = 0, blob_size = 0;
     size_t blob_qtables = 0;
     size_t total = 0;
     ScanPlan scan[kMaxScans];
+    ProgPlan prog;
 };
 
 } // namespace
@@ -86,6 +96,7 @@ struct Decoder {
     int subseq_bytes    = 64;
     bool parsed         = false;
     int shard_rank = 0, shard_world = 1; // jpeggpu_ext_set_segment_shard
+    bool progressive    = false; // jpeggpu_ext_set_progressive: SOF2 frames are read, from the next parse_header on
     int device_scan     = 0;     // jpeggpu_ext_set_device_scan: 0 off, 1 on (status via jpeggpu_ext_get_device_status), 2 on and checked by decode
     // jpeggpu_ext_set_scale: planes at 1 / 2^scale_log2. The request takes effect at the next parse_header (`scale_log2`:
     // that of the parsed image); it changes the plane sizes and the IDCT stage only, never the plan or the Huffman path.
@@ -156,7 +167,30 @@ struct Decoder {
 
     void make_plan();
     bool fill_blob();
+    void plan_progressive(Plan& p, size_t& b) const;
+    void fill_progressive();
+    /// Entries of scan i's symbol stream: a region per subsequence, or per data unit for a component of a progressive frame.
+    uint32_t sym_regions(int i) const { return static_cast<uint32_t>(reader.s.progressive ? reader.s.scans[i].prog_regions : reader.s.scans[i].num_subseq); }
+    uint32_t sym_region() const { return reader.s.progressive ? kProgRegionEntries : sym_region_entries(subseq_bytes); }
 };
+
+void Decoder::plan_progressive(Plan& p, size_t& b) const
+{
+    p.prog.on = true;
+    prog_plan_blob(reader.s, p.prog.blob, b);
+}
+
+void Decoder::fill_progressive()
+{
+    const Stream& s    = reader.s;
+    const ProgPlan& pp = plan.prog;
+    ProgPlacement at{};
+    at.blob_in_tmp = plan.off_blob;
+    at.bytes_off = plan.off_bytes, at.bytes_len = plan.bytes_len;
+    at.coef_begin = pp.coef_begin, at.coef_bytes = pp.coef_bytes;
+    for (int c = 0; c < s.num_comp; ++c) at.coef[c] = pp.coef[c], at.sym[c] = plan.scan[c].sym, at.du_tab[c] = plan.scan[c].du_tab;
+    prog_fill_blob(s, pp.blob, at, blob.ptr);
+}
 
 /// Each component's block size for the parsed image. JPEGGPU_EXT_SCALE_LIBJPEG at a scale below 1: jdmaster.c's rule -- from
 /// S_min = 8 / d, a component's size doubles while it stays below 8 and the doubled block still divides what the largest
@@ -310,6 +344,7 @@ void Decoder::make_plan()
             }
         }
     }
+    if (s.progressive) plan_progressive(p, b);
     p.blob_size = b;
 
     // device carve: transferred region first, at fixed places (reference decoder.cpp:116-155)
@@ -404,9 +439,17 @@ void Decoder::make_plan()
     }
     for (int i = 0; i < s.num_scans; ++i) {
         p.scan[i].sym = o; // symbol stream: a fixed region per subsequence
-        o += align_up(sym_buffer_entries(static_cast<uint32_t>(s.scans[i].num_subseq), sym_region_entries(subseq_bytes)) * 2 + 256, 256);
+        o += align_up(sym_buffer_entries(sym_regions(i), sym_region()) * 2 + 256, 256);
         p.scan[i].du_tab = o;
         o += align_up(static_cast<size_t>(s.scans[i].num_du) * sizeof(uint2_t), 256);
+    }
+    if (s.progressive) { // the coefficient buffers, one after the other: one memset zeroes them
+        p.prog.coef_begin = o;
+        for (int c = 0; c < s.num_comp; ++c) {
+            p.prog.coef[c] = o;
+            o += align_up(static_cast<size_t>(s.prog_blocks_x[c]) * static_cast<size_t>(s.prog_blocks_y[c]) * 64 * sizeof(int16_t), 256);
+        }
+        p.prog.coef_bytes = o - p.prog.coef_begin;
     }
     p.total = o;
     plan             = p;
@@ -455,6 +498,7 @@ bool Decoder::fill_blob()
         if (!sp.mh_blocks.empty())
             std::memcpy(blob.ptr + sp.blob_mh_blocks, sp.mh_blocks.data(), sp.mh_blocks.size() * sizeof(MhBlock));
     }
+    if (plan.prog.on) fill_progressive();
     return true;
 }
 
@@ -621,8 +665,8 @@ jpeggpu_status build_jobs(
         job.tails_dc23 = reinterpret_cast<uint32_t*>(base + pl.tails_dc23);
         job.sym         = reinterpret_cast<uint16_t*>(base + pl.sym);
         job.du_tab      = reinterpret_cast<uint2_t*>(base + pl.du_tab);
-        job.sym_region  = sym_region_entries(d.subseq_bytes);
-        job.sym_entries = sym_buffer_entries(static_cast<uint32_t>(sc.num_subseq), job.sym_region);
+        job.sym_region  = d.sym_region();
+        job.sym_entries = sym_buffer_entries(d.sym_regions(i), job.sym_region);
         job.num_chunks = static_cast<int>(sc.chunks.size());
         job.num_seq    = static_cast<int>((static_cast<size_t>(sc.num_subseq) + sp.seq_subseq - 1) / sp.seq_subseq); // <= pl.num_seq, what the arrays are sized for
         if (sc.device_walk) {
@@ -704,6 +748,19 @@ jpeggpu_status read_device_status(Decoder& d, const void* d_tmp, hipStream_t str
     return JPEGGPU_SUCCESS;
 }
 
+/// The progressive part of a lone decode: the coefficient buffers zeroed, the scans level by level, the hand-over.
+jpeggpu_status decode_progressive(Decoder& d, void* d_tmp, hipStream_t stream)
+{
+    using namespace jg;
+    uint8_t* base      = static_cast<uint8_t*>(d_tmp);
+    const ProgPlan& pp = d.plan.prog;
+    JG_CHECK_HIP(hipMemsetAsync(base + pp.coef_begin, 0, pp.coef_bytes, stream));
+    ProgExtent e;
+    extend(e, *reinterpret_cast<const ProgHeader*>(d.blob.ptr + pp.blob.header));
+    JG_CHECK_HIP(launch_prog(ProgImage{base, d.plan.off_blob + pp.blob.header}, e, stream));
+    return JPEGGPU_SUCCESS;
+}
+
 /// `may_block`: the checked mode of the device scan may wait for the stream (jpeggpu_decoder_decode); an item of a batch is
 /// never waited for (jpeggpu_ext.h).
 jpeggpu_status do_decode(Decoder& d, jpeggpu_img* img, void* d_tmp, size_t tmp_size, hipStream_t stream, bool may_block = true)
@@ -759,6 +816,10 @@ jpeggpu_status do_decode(Decoder& d, jpeggpu_img* img, void* d_tmp, size_t tmp_s
             // multi-hypothesis speculation in front of the sequence kernel, which then starts from its table
             for (size_t i = 0; i < d.jobs.size(); ++i)
                 if (d.jobs[i].sp.mh > 1) JG_CHECK_HIP(launch_mh(d.jobs[i], nullptr, d.plan.scan[i].max_seg_subseq, stream));
+        }
+        if (stage == kStageWrite && d.plan.prog.on) { // a progressive frame: its jobs have no other work in front of the IDCT
+            const jpeggpu_status ps = decode_progressive(d, d_tmp, stream);
+            if (ps != JPEGGPU_SUCCESS) return ps;
         }
         JG_CHECK_HIP(launch_stage_scans(static_cast<Stage>(stage), d.jobs.data(), static_cast<int>(d.jobs.size()), stream));
         d.mark(stage, stream);
@@ -857,7 +918,7 @@ enum jpeggpu_status jpeggpu_decoder_parse_header(
     jpeggpu_status st;
     try {
         const int ask = d.subseq_request > 0 ? d.subseq_request : -d.batch_hint; // 0 / -N: chosen per image for N images per call
-        st = d.reader.parse(data, size, ask, d.logger, d.device_scan != 0, d.shard_rank, d.shard_world);
+        st = d.reader.parse(data, size, ask, d.logger, d.device_scan != 0, d.shard_rank, d.shard_world, d.progressive);
         d.subseq_bytes = d.reader.subseq_bytes();
     } catch (const std::bad_alloc&) {
         return JPEGGPU_OUT_OF_HOST_MEMORY;
@@ -895,14 +956,20 @@ enum jpeggpu_status jpeggpu_decoder_parse_header(
     // entry indices (jg_kernels.hip, entry_at / prefetch): a scan whose stream would not fit them (from about
     // 400 MB of entropy-coded data at 64-byte subsequences) is refused here instead of gathering from wrapped offsets.
     for (int i = 0; i < s.num_scans; ++i) {
-        const uint64_t entries = jg::sym_buffer_entries(static_cast<uint32_t>(s.scans[i].num_subseq), jg::sym_region_entries(d.subseq_bytes));
+        const uint64_t entries = jg::sym_buffer_entries(d.sym_regions(i), d.sym_region());
         if (entries * 2u >= (1ull << 32)) {
             d.logger.log("scan %d: %d subsequences of %d bytes need a symbol stream of %llu bytes (32-bit offsets)\n", i,
                          s.scans[i].num_subseq, d.subseq_bytes, static_cast<unsigned long long>(entries * 2u));
             return JPEGGPU_NOT_SUPPORTED;
         }
     }
-    d.make_plan();
+    try {
+        d.make_plan();
+    } catch (const std::bad_alloc&) {
+        return JPEGGPU_OUT_OF_HOST_MEMORY;
+    }
+    // the descriptors of a progressive image hold 32-bit offsets of the blob inside d_tmp
+    if (d.plan.prog.on && d.plan.off_blob + d.plan.blob_size >= (1ull << 32)) return JPEGGPU_NOT_SUPPORTED;
     if (!d.fill_blob()) return JPEGGPU_OUT_OF_HOST_MEMORY;
     d.seq_subseq_used = 0;
     d.parsed = true;
@@ -1136,6 +1203,32 @@ enum jpeggpu_status jpeggpu_ext_get_color_space(jpeggpu_decoder_t decoder, enum 
     return JPEGGPU_SUCCESS;
 }
 
+enum jpeggpu_status jpeggpu_ext_set_progressive(jpeggpu_decoder_t decoder, int enable)
+{
+    if (!decoder) return JPEGGPU_INVALID_ARGUMENT;
+    decoder->d.progressive = enable != 0;
+    return JPEGGPU_SUCCESS;
+}
+
+enum jpeggpu_status jpeggpu_ext_get_progressive_info(jpeggpu_decoder_t decoder, struct jpeggpu_ext_progressive_info* info)
+{
+    if (!decoder || !info) return JPEGGPU_INVALID_ARGUMENT;
+    const Decoder& d = decoder->d;
+    if (!d.parsed) return JPEGGPU_INVALID_ARGUMENT;
+    std::memset(info, 0, sizeof(*info));
+    const jg::Stream& s = d.reader.s;
+    if (!s.progressive) return JPEGGPU_SUCCESS;
+    info->progressive = 1;
+    info->num_scans   = static_cast<int>(s.prog_scans.size());
+    info->num_levels  = s.num_levels;
+    for (int c = 0; c < s.num_comp; ++c) {
+        info->off_coefficients[c] = d.plan.prog.coef[c];
+        info->blocks_x[c] = s.prog_blocks_x[c], info->blocks_y[c] = s.prog_blocks_y[c];
+        info->visible_blocks_x[c] = s.scans[c].mcus_x, info->visible_blocks_y[c] = s.scans[c].mcus_y;
+    }
+    return JPEGGPU_SUCCESS;
+}
+
 enum jpeggpu_status jpeggpu_ext_set_idct(jpeggpu_decoder_t decoder, enum jpeggpu_ext_idct method)
 {
     if (!decoder) return JPEGGPU_INVALID_ARGUMENT;
@@ -1208,6 +1301,9 @@ struct jpeggpu_batch {
     hipEvent_t joined[kMaxOverlap - 1] = {};
     std::vector<jg::ScanJob> jobs;
     std::vector<jg::FrontParams> fronts;
+    std::vector<jg::ProgImage> progs;    // the progressive items of the call (jg_prog.hpp), and their launch extents
+    jg::ProgExtent prog_extent;
+    hipEvent_t prog_done        = nullptr; // overlap > 1: the other streams' IDCT waits for the progressive launches
     std::vector<int> order, group_begin; // scratch of decode_batch: items by subsequence size, job ranges of the sizes
     struct Part {                        // ... and the parts of the job array, one launch per stage each
         int begin, end, way;
@@ -1222,6 +1318,9 @@ struct jpeggpu_batch {
 
 size_t jpeggpu_ext_batch_scratch_size(int max_scans)
 {
+    // (a progressive item's descriptor lies behind the jobs and front-end parameters; such an item has a job per component
+    // and no front-end parameters, so the same bound holds)
+    static_assert(sizeof(jg::ProgImage) <= sizeof(jg::FrontParams), "a progressive item takes the place of front-end parameters");
     return static_cast<size_t>(max_scans > 0 ? max_scans : 0) * (sizeof(jg::ScanJob) + sizeof(jg::FrontParams));
 }
 
@@ -1261,6 +1360,7 @@ enum jpeggpu_status jpeggpu_ext_batch_destroy(jpeggpu_batch_t batch)
         if (batch->staging[r]) (void)hipHostFree(batch->staging[r]);
         if (batch->copied[r]) (void)hipEventDestroy(batch->copied[r]);
     }
+    if (batch->prog_done) (void)hipEventDestroy(batch->prog_done);
     for (auto& set : batch->sets)
         for (hipEvent_t e : set) (void)hipEventDestroy(e);
     delete batch;
@@ -1302,6 +1402,8 @@ static enum jpeggpu_status decode_batch_impl(
     if (num_items == 0) return JPEGGPU_SUCCESS;
     batch->jobs.clear();
     batch->fronts.clear();
+    batch->progs.clear();
+    batch->prog_extent = jg::ProgExtent{};
     jg::ScanJob* d_jobs_rw = static_cast<jg::ScanJob*>(d_scratch);
     uint32_t front_windows = 0;
     // One kernel variant per launch: the items are taken in the order of their subsequence size (chosen per image at
@@ -1357,18 +1459,25 @@ static enum jpeggpu_status decode_batch_impl(
             batch->fronts.push_back(front_params(it.decoder->d, it.d_tmp, d_jobs_rw + first_job + static_cast<size_t>(dk), dk));
             front_windows = std::max(front_windows, batch->fronts.back().num_windows);
         }
+        if (const Decoder& pd = it.decoder->d; pd.plan.prog.on) {
+            batch->progs.push_back(jg::ProgImage{static_cast<uint8_t*>(it.d_tmp), pd.plan.off_blob + pd.plan.prog.blob.header});
+            jg::extend(batch->prog_extent, *reinterpret_cast<const jg::ProgHeader*>(pd.blob.ptr + pd.plan.prog.blob.header));
+        }
     }
     group_begin.push_back(static_cast<int>(batch->jobs.size()));
     const int n         = static_cast<int>(batch->jobs.size());
     const int nf        = static_cast<int>(batch->fronts.size());
+    const int np        = static_cast<int>(batch->progs.size());
     const size_t jbytes = sizeof(jg::ScanJob) * static_cast<size_t>(n), fbytes = sizeof(jg::FrontParams) * static_cast<size_t>(nf);
-    if (n > batch->max_jobs || scratch_size < jbytes + fbytes) return JPEGGPU_INVALID_ARGUMENT;
+    const size_t pbytes = sizeof(jg::ProgImage) * static_cast<size_t>(np);
+    if (n > batch->max_jobs || scratch_size < jbytes + fbytes + pbytes) return JPEGGPU_INVALID_ARGUMENT;
     const int r = batch->next;
     batch->next = (r + 1) % jpeggpu_batch::kRing;
     // the staging buffer may still be the source of a copy enqueued kRing batches ago
     if (batch->in_use[r] && hipEventSynchronize(batch->copied[r]) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
     std::memcpy(batch->staging[r], batch->jobs.data(), jbytes);
     if (nf) std::memcpy(batch->staging[r] + jbytes, batch->fronts.data(), fbytes);
+    if (np) std::memcpy(batch->staging[r] + jbytes + fbytes, batch->progs.data(), pbytes);
     const jg::ScanJob* d_jobs = static_cast<const jg::ScanJob*>(d_scratch);
     std::vector<hipEvent_t>* ev = nullptr;
     if (batch->profiling) {
@@ -1383,7 +1492,7 @@ static enum jpeggpu_status decode_batch_impl(
         }
         (void)hipEventRecord((*ev)[0], stream);
     }
-    if (hipMemcpyAsync(d_scratch, batch->staging[r], jbytes + fbytes, hipMemcpyHostToDevice, stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
+    if (hipMemcpyAsync(d_scratch, batch->staging[r], jbytes + fbytes + pbytes, hipMemcpyHostToDevice, stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
     if (nf && jg::launch_front_batch(reinterpret_cast<const jg::FrontParams*>(static_cast<const uint8_t*>(d_scratch) + jbytes), nf,
                                      front_windows, stream) != hipSuccess) {
         (void)hipGetLastError();
@@ -1422,6 +1531,26 @@ static enum jpeggpu_status decode_batch_impl(
         }
     }
     for (int stage = 0; stage < jg::kNumStages; ++stage) {
+        if (stage == jg::kStageWrite && np) {
+            // The progressive items of the call, once for all of them: their coefficient buffers zeroed, one launch per
+            // level, the hand-over; on the caller's stream, and the IDCT of the other streams' parts waits for it.
+            for (int k = 0; k < num_items; ++k) {
+                const Decoder& pd = items[k].decoder->d;
+                if (pd.plan.prog.on && hipMemsetAsync(static_cast<uint8_t*>(items[k].d_tmp) + pd.plan.prog.coef_begin, 0, pd.plan.prog.coef_bytes, stream) != hipSuccess)
+                    return JPEGGPU_INTERNAL_ERROR;
+            }
+            const jg::ProgImage* d_progs = reinterpret_cast<const jg::ProgImage*>(static_cast<const uint8_t*>(d_scratch) + jbytes + fbytes);
+            if (jg::launch_prog_batch(d_progs, np, batch->prog_extent, stream) != hipSuccess) {
+                (void)hipGetLastError();
+                return JPEGGPU_INTERNAL_ERROR;
+            }
+            if (ways > 1) {
+                if (!batch->prog_done && hipEventCreateWithFlags(&batch->prog_done, hipEventDisableTiming) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
+                if (hipEventRecord(batch->prog_done, stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
+                for (int w = 1; w < ways; ++w)
+                    if (hipStreamWaitEvent(part_stream[w], batch->prog_done, 0) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
+            }
+        }
         for (const Part& p : parts) {
             if (jg::launch_stage_batch(static_cast<jg::Stage>(stage), d_jobs + p.begin, p.end - p.begin, p.extent, part_stream[p.way]) != hipSuccess) {
                 (void)hipGetLastError();

@@ -15,7 +15,7 @@
 namespace jg {
 
 namespace {
-constexpr uint8_t M_SOF0 = 0xC0, M_SOF1 = 0xC1, M_DHT = 0xC4, M_RST0 = 0xD0, M_RST7 = 0xD7,
+constexpr uint8_t M_SOF0 = 0xC0, M_SOF1 = 0xC1, M_SOF2 = 0xC2, M_DHT = 0xC4, M_RST0 = 0xD0, M_RST7 = 0xD7,
                   M_SOI = 0xD8, M_EOI = 0xD9, M_SOS = 0xDA, M_DQT = 0xDB, M_DRI = 0xDD, M_APP0 = 0xE0, M_APP14 = 0xEE;
 constexpr int kNatural[64] = JG_ORDER_NATURAL;
 
@@ -259,6 +259,9 @@ jpeggpu_status Reader::read_sof(const Logger& log)
         Component& comp = s.comp[c];
         comp.size_x     = ceil_div(s.size_x * comp.hs, s.hs_max); // T.81 A.1.1
         comp.size_y     = ceil_div(s.size_y * comp.vs, s.vs_max);
+        // the MCU-padded block grid, the one an interleaved scan of all components covers (a progressive frame's buffer)
+        s.prog_blocks_x[c] = std::max(ceil_div(s.size_x, 8 * s.hs_max) * comp.hs, ceil_div(comp.size_x, 8));
+        s.prog_blocks_y[c] = std::max(ceil_div(s.size_y, 8 * s.vs_max) * comp.vs, ceil_div(comp.size_y, 8));
     }
     return JPEGGPU_SUCCESS;
 }
@@ -364,6 +367,9 @@ jpeggpu_status Reader::read_dri(const Logger& log)
     const uint16_t length = u16();
     if (length != 4 || remaining() < 2) return JPEGGPU_INVALID_JPEG;
     const uint16_t rsti = u16();
+    // A baseline frame's scans share one interval (the kernels index output by segment number). The scans of a progressive
+    // frame each take the interval in force at their SOS: libjpeg writes a new DRI in front of every scan of a file saved
+    // with a restart interval in MCU ROWS, whose length differs between an interleaved scan and a component's own.
     if (s.num_scans > 0 && s.restart_interval != rsti) {
         log.log("\tredefined restart interval\n");
         return JPEGGPU_NOT_SUPPORTED;
@@ -390,7 +396,7 @@ jpeggpu_status Reader::skip_segment(const Logger& log)
 /// and a short or malformed one tells nothing.
 void Reader::note_app_segment(uint8_t marker)
 {
-    if (s.num_scans > 0 || remaining() < 2) return;
+    if (s.num_scans > 0 || !s.prog_scans.empty() || remaining() < 2) return;
     const size_t length = static_cast<size_t>(cur_[0]) << 8 | cur_[1];
     if (length < 2 || remaining() < length) return;
     const uint8_t* data = cur_ + 2;
@@ -404,6 +410,7 @@ void Reader::note_app_segment(uint8_t marker)
 jpeggpu_status Reader::read_sos(const Logger& log)
 {
     if (!found_sof_) return JPEGGPU_INVALID_JPEG;
+    if (s.progressive) return read_sos_progressive(log);
     if (remaining() < 3) {
         log.log("\ttoo few bytes in SOS segment\n");
         return JPEGGPU_INVALID_JPEG;
@@ -592,6 +599,161 @@ jpeggpu_status Reader::read_sos(const Logger& log)
         }
     }
     return walk_scan(scan, log);
+}
+
+/// SOS of a progressive frame (T.81 G.1.1.1.1): a DC scan (Ss = Se = 0; 1..4 components, interleaved like a baseline scan)
+/// or an AC scan (one component, a band Ss..Se), each a first scan (Ah = 0) or a refinement by one bit (Ah = Al + 1).
+/// Header values outside these rules are INVALID_JPEG. A scan that breaks the PROGRESSION -- a first scan of coefficients
+/// already coded, a refinement of coefficients that are not at bit position Ah, an AC scan before its component's first DC
+/// scan -- is NOT_SUPPORTED (libjpeg warns about some of these and decodes on). The walk over the scan's bytes is the
+/// baseline one (walk_scan): it finds the scan's end and checks the restart-marker count against THIS scan's MCUs; only
+/// the byte ranges of the segments are kept of it, since the scan kernel destuffs as it reads.
+jpeggpu_status Reader::read_sos_progressive(const Logger& log)
+{
+    if (remaining() < 3) return JPEGGPU_INVALID_JPEG;
+    const uint16_t length = u16();
+    if (length < 3) return JPEGGPU_INVALID_JPEG;
+    const uint8_t ns = u8();
+    if (ns < 1 || ns > 4) return JPEGGPU_INVALID_JPEG;
+    if (length != 6 + 2 * ns) return JPEGGPU_INVALID_JPEG;
+    if (remaining() < static_cast<size_t>(2 * ns + 3)) return JPEGGPU_INCOMPLETE_BITSTREAM;
+    if (s.prog_scans.size() >= static_cast<size_t>(kMaxProgScans)) {
+        log.log("\tmore than %d scans\n", kMaxProgScans);
+        return JPEGGPU_NOT_SUPPORTED;
+    }
+    ProgScan ps;
+    ps.num_comp           = ns;
+    const bool interleave = ns > 1;
+    for (int a = 0; a < ns; ++a) {
+        ScanComponent& sc = ps.comp[a];
+        const uint8_t sel = u8();
+        const uint8_t tab = u8();
+        int ci            = -1;
+        for (int i = 0; i < s.num_comp; ++i)
+            if (s.comp[i].id == sel) ci = i;
+        if (ci < 0) return JPEGGPU_INVALID_JPEG;
+        if (a > 0 && ci <= ps.comp[a - 1].comp_idx) return JPEGGPU_INVALID_JPEG; // T.81 A.2: frame order
+        if ((tab >> 4) > 3 || (tab & 15) > 3) return JPEGGPU_INVALID_JPEG;
+        const Component& comp = s.comp[ci];
+        if (!qt_defined_[comp.qidx]) return JPEGGPU_INVALID_JPEG;
+        sc.comp_idx = ci;
+        sc.dc_id    = tab >> 4;
+        sc.ac_id    = tab & 15;
+        sc.h        = interleave ? comp.hs : 1;
+        sc.v        = interleave ? comp.vs : 1;
+        sc.data_x   = ceil_div(comp.size_x, 8 * sc.h) * 8 * sc.h;
+        sc.data_y   = ceil_div(comp.size_y, 8 * sc.v) * 8 * sc.v;
+        const int mx = sc.data_x / (8 * sc.h), my = sc.data_y / (8 * sc.v);
+        if (a > 0 && (mx != ps.mcus_x || my != ps.mcus_y)) return JPEGGPU_NOT_SUPPORTED;
+        // an interleaved scan also covers blocks outside the visible grid: they must lie inside the coefficient buffer
+        if (mx * sc.h > s.prog_blocks_x[ci] || my * sc.v > s.prog_blocks_y[ci]) return JPEGGPU_NOT_SUPPORTED;
+        ps.mcus_x = mx;
+        ps.mcus_y = my;
+        ps.du_per_mcu += sc.h * sc.v;
+    }
+    if (ps.du_per_mcu > kMaxDuPerMcu) return JPEGGPU_INVALID_JPEG;
+    ps.ss             = u8();
+    ps.se             = u8();
+    const uint8_t aa  = u8();
+    ps.ah             = aa >> 4;
+    ps.al             = aa & 15;
+    log.log("\tprogressive scan %d: %d components, Ss %d Se %d Ah %d Al %d\n", static_cast<int>(s.prog_scans.size()), ns, ps.ss, ps.se, ps.ah, ps.al);
+    if (ps.ss == 0 ? ps.se != 0 : (ps.se < ps.ss || ps.se > 63 || ns != 1)) return JPEGGPU_INVALID_JPEG;
+    if (ps.al > 13) return JPEGGPU_INVALID_JPEG;
+    if (ps.ah != 0 && ps.ah != ps.al + 1) return JPEGGPU_INVALID_JPEG;
+    const bool dc = ps.ss == 0, first = ps.ah == 0;
+    ps.kind       = dc ? (first ? kProgDcFirst : kProgDcRefine) : (first ? kProgAcFirst : kProgAcRefine);
+    // the progression, and the scan's level
+    int level = 0;
+    for (int a = 0; a < ns; ++a) {
+        const int ci = ps.comp[a].comp_idx;
+        if (!dc && prog_al_[ci][0] < 0) {
+            log.log("\tAC scan of component %d before its first DC scan\n", ci);
+            return JPEGGPU_NOT_SUPPORTED;
+        }
+        for (int k = ps.ss; k <= ps.se; ++k) {
+            if (first ? prog_al_[ci][k] >= 0 : prog_al_[ci][k] != ps.ah) {
+                log.log("\tscan breaks the progression of component %d, coefficient %d\n", ci, k);
+                return JPEGGPU_NOT_SUPPORTED;
+            }
+            level = std::max(level, prog_level_[ci][k] + 1);
+        }
+    }
+    ps.level = level;
+    for (int a = 0; a < ns; ++a) {
+        const int ci = ps.comp[a].comp_idx;
+        for (int k = ps.ss; k <= ps.se; ++k) {
+            prog_al_[ci][k]    = static_cast<int8_t>(ps.al);
+            prog_level_[ci][k] = static_cast<int8_t>(level);
+        }
+        comp_in_scan_[ci] = true; // the quantiser is latched at a component's first scan (read_dqt)
+        // the table in force: a DC refinement scan uses none, an AC scan only its AC table
+        if (ps.kind == kProgDcRefine) continue;
+        const int tc = dc ? 0 : 1, th = dc ? ps.comp[a].dc_id : ps.comp[a].ac_id;
+        if (!(dc ? dc_defined_ : ac_defined_)[th]) return JPEGGPU_INVALID_JPEG;
+        const std::vector<uint8_t>& key = dht_key_[tc][th]; // 16 counts, then the values
+        build_prog_table(ps.table[a], key.data(), key.data() + 16, static_cast<int>(key.size()) - 16);
+    }
+    const int total_mcus = ps.mcus_x * ps.mcus_y;
+    ps.mcus_per_segment  = s.restart_interval ? s.restart_interval : total_mcus;
+    ps.begin             = static_cast<size_t>(cur_ - base_);
+    if (s.prog_scans.empty()) {
+        if (subseq_request_ <= 0) subseq_bytes_ = 64; // (no subsequences: the size only names the kernels of a batch this image is in)
+        s.xfer_begin = (ps.begin - 1) & ~static_cast<size_t>(15);
+    }
+    // the baseline walk, for the scan's end, its restart segments and their count
+    Scan& w = prog_walk_;
+    w.segments.clear();
+    w.chunks.clear();
+    w.num_subseq       = 0;
+    w.mcus_x           = ps.mcus_x;
+    w.mcus_y           = ps.mcus_y;
+    w.mcus_per_segment = ps.mcus_per_segment;
+    const jpeggpu_status st = walk_scan(w, log);
+    if (st != JPEGGPU_SUCCESS) return st;
+    ps.end = w.end;
+    ps.segments.assign(w.segments.size(), uint2_t{0u, 0u});
+    for (const DestuffChunk& c : w.chunks) {
+        uint2_t& g = ps.segments[static_cast<size_t>(c.seg)];
+        if (c.first) g.x = c.begin;
+        g.y = c.end;
+    }
+    s.prog_scans.push_back(ps);
+    return JPEGGPU_SUCCESS;
+}
+
+/// End of a progressive file: every component needs its first DC scan (coefficients no scan coded are 0, bits no scan
+/// refined stay 0); then the frame as the IDCT stage takes it: one non-interleaved scan per component.
+jpeggpu_status Reader::finish_progressive(const Logger& log)
+{
+    if (s.prog_scans.empty()) return JPEGGPU_INVALID_JPEG;
+    s.num_levels = 0;
+    for (const ProgScan& ps : s.prog_scans) s.num_levels = std::max(s.num_levels, ps.level + 1);
+    for (int c = 0; c < s.num_comp; ++c) {
+        if (prog_al_[c][0] < 0) {
+            log.log("\tcomponent %d has no DC scan\n", c);
+            return JPEGGPU_INVALID_JPEG;
+        }
+    }
+    s.num_scans = s.num_comp;
+    for (int c = 0; c < s.num_comp; ++c) {
+        Scan& scan = s.scans[c];
+        scan.table_pack.clear(), scan.table_pack_sync.clear(), scan.segments.clear(), scan.chunks.clear();
+        scan.tail_parts.assign(1, 0);
+        const Component& comp = s.comp[c];
+        scan.num_comp         = 1;
+        ScanComponent& sc     = scan.comp[0];
+        sc.comp_idx = c, sc.dc_id = sc.ac_id = 0, sc.h = sc.v = 1;
+        sc.data_x = ceil_div(comp.size_x, 8) * 8, sc.data_y = ceil_div(comp.size_y, 8) * 8;
+        scan.du_per_mcu = 1;
+        scan.mcus_x = sc.data_x / 8, scan.mcus_y = sc.data_y / 8;
+        scan.mcus_per_segment = scan.mcus_x * scan.mcus_y;
+        scan.num_du           = scan.mcus_x * scan.mcus_y;
+        scan.prog_regions     = scan.num_du;
+        scan.begin = s.prog_scans.front().begin, scan.end = s.prog_scans.back().end;
+    }
+    s.xfer_end = s.prog_scans.back().end;
+    return JPEGGPU_SUCCESS;
 }
 
 /// Walk the entropy-coded bytes of one scan (reference src/reader.cpp:447-489): find restart
@@ -821,8 +983,11 @@ void Reader::cut_segments(int a, int b)
 }
 
 jpeggpu_status Reader::parse(const uint8_t* data, size_t size, int subseq_bytes, const Logger& log, bool device_scan,
-                             int shard_rank, int shard_world)
+                             int shard_rank, int shard_world, bool progressive)
 {
+    progressive_ = progressive;
+    std::memset(prog_al_, -1, sizeof(prog_al_));
+    std::memset(prog_level_, -1, sizeof(prog_level_));
     if (shard_world > 1 && device_scan) {
         // the share is cut out of the host walk's tables (jpeggpu_ext.h says so; the layout shows which walk was used)
         log.log("segment shard %d of %d: host walk, the device scan that was asked for is not used\n", shard_rank, shard_world);
@@ -893,10 +1058,17 @@ jpeggpu_status Reader::parse(const uint8_t* data, size_t size, int subseq_bytes,
         if ((st = read_marker(marker)) != JPEGGPU_SUCCESS) return st;
         log.log("marker 0x%02x\n", marker);
         st = JPEGGPU_SUCCESS;
-        if (marker == M_SOF0 || marker == M_SOF1) {
+        if (marker == M_SOF0 || marker == M_SOF1 || (marker == M_SOF2 && progressive_)) {
             if (found_sof_) return JPEGGPU_INVALID_JPEG;
             found_sof_ = true;
             st         = read_sof(log);
+            if (st == JPEGGPU_SUCCESS && marker == M_SOF2) {
+                s.progressive = true;
+                if (shard_world > 1) {
+                    log.log("\ta segment shard of a progressive frame is not supported\n");
+                    return JPEGGPU_NOT_SUPPORTED;
+                }
+            }
         } else if (
             (marker >= 0xC2 && marker <= 0xCF && marker != M_DHT && marker != 0xC8 &&
              marker != 0xCC)) {
@@ -922,6 +1094,7 @@ jpeggpu_status Reader::parse(const uint8_t* data, size_t size, int subseq_bytes,
         if (st != JPEGGPU_SUCCESS) return st;
     } while (true);
 
+    if (found_sof_ && s.progressive && (st = finish_progressive(log)) != JPEGGPU_SUCCESS) return st;
     if (!found_sof_ || s.num_scans == 0) return JPEGGPU_INVALID_JPEG;
     for (int c = 0; c < s.num_comp; ++c) {
         if (!comp_in_scan_[c]) {

@@ -11,11 +11,13 @@
 //   B-6 length fields and table ids are range-checked;
 //   fill bytes (FF FF .. before a marker) are skipped; a scan whose restart-marker count does not
 //   match the frame geometry is rejected (the kernels index output by segment number);
-//   the walk over the entropy-coded bytes also emits the destuff work list (see jg_defs.h).
+//   the walk over the entropy-coded bytes also emits the destuff work list (see jg_defs.h);
+//   progressive frames (SOF2) are read if the caller asked for them (jpeggpu_ext_set_progressive): ProgScan below.
 #ifndef JG_READER_HPP_
 #define JG_READER_HPP_
 
 #include "jg_defs.h"
+#include "jg_prog_core.h"
 
 #include <jpeggpu/jpeggpu.h>
 
@@ -80,6 +82,26 @@ struct Scan {
     int expect_segments = 0;
     int max_chunks      = 0;
     int max_tail_parts  = 0; // entries of the device's tail_parts array
+    // A component of a progressive frame as the IDCT stage sees it (Stream::progressive): no entropy-coded data of its own
+    // (num_subseq == 0, no segments, no chunks); its symbol stream has one region per data unit (jg_prog_core.h).
+    int prog_regions = 0;
+};
+
+/// One scan of a progressive frame (T.81 Annex G). The scans do not fit Stream::scans: a file has up to kMaxProgScans of
+/// them, several per component, and what they decode into is the coefficient buffer, not a symbol stream.
+struct ProgScan {
+    int kind = 0; // ProgKind
+    int num_comp = 0;
+    ScanComponent comp[kMaxComp];
+    int ss = 0, se = 0, ah = 0, al = 0;
+    // 0 if no earlier scan touches any of its (component, coefficient) pairs, else 1 + the highest level among those that
+    // do: scans of one level write disjoint coefficients and share a launch
+    int level = 0;
+    int du_per_mcu = 0;
+    int mcus_x = 0, mcus_y = 0, mcus_per_segment = 0;
+    size_t begin = 0, end = 0;    // file offsets, as in Scan
+    ProgTable table[kMaxComp];    // per scan component: the DC table (DC first scans) or the AC table (AC scans) in force at SOS
+    std::vector<uint2_t> segments; // byte range of each restart segment in the transferred bytes
 };
 
 /// The colour model of a frame's components, by libjpeg's rules (jdapimin.c, default_decompress_parms); the values are
@@ -106,6 +128,12 @@ struct Stream {
     bool saw_jfif = false, saw_adobe = false;
     uint8_t adobe_transform = 0;
     int color_space = kColorUnknown; // ColorSpace
+    // A progressive frame (SOF2): prog_scans holds the file's scans, and scans[0 .. num_comp) describe the frame as it is
+    // handed to the IDCT stage -- one non-interleaved baseline scan per component (B-2) without entropy-coded data.
+    bool progressive = false;
+    int num_levels   = 0;
+    std::vector<ProgScan> prog_scans;
+    int prog_blocks_x[kMaxComp]{}, prog_blocks_y[kMaxComp]{}; // each component's MCU-padded block grid (the coefficient buffer)
 };
 
 /// Requests for a per-image choice (Reader::parse): 0 or -N, N = about how many images share the call (kBatchHintFull:
@@ -160,8 +188,10 @@ struct Reader {
     /// kSubseqAutoBatched for one that shares its launches with others (jpeggpu_ext_decode_batch). The choice is made
     /// at the first scan header from the bytes left in the file and the restart density (choose_subseq_bytes) and
     /// holds for every scan of the image; subseq_bytes() says what it was.
+    /// `progressive`: SOF2 frames are read (Huffman-coded, 8-bit samples); the device scan and a segment shard do not
+    /// apply to them (the first is ignored, the second refused). Without it they are NOT_SUPPORTED, as in the reference.
     jpeggpu_status parse(const uint8_t* data, size_t size, int subseq_bytes, const Logger& log, bool device_scan = false,
-                         int shard_rank = 0, int shard_world = 1);
+                         int shard_rank = 0, int shard_world = 1, bool progressive = false);
     int subseq_bytes() const { return subseq_bytes_; }
     /// Keep restart segments [a, b) of the parsed image's single, host-walked scan (jg_reader.cpp).
     void cut_segments(int a, int b);
@@ -183,6 +213,12 @@ struct Reader {
     bool comp_in_scan_[kMaxComp]{};
     bool device_scan_ = false;
     bool stop_        = false; // device mode: nothing behind the scan header is parsed on the host
+    bool progressive_ = false; // SOF2 is read
+    // progression of a progressive frame, per (component, coefficient): the successive-approximation bit position the
+    // coefficient has been coded down to (-1: no scan yet), and the level of the last scan that touched it
+    int8_t prog_al_[kMaxComp][64]{};
+    int8_t prog_level_[kMaxComp][64]{};
+    Scan prog_walk_; // scratch of the walk over a progressive scan's bytes
 
     size_t remaining() const { return static_cast<size_t>(end_ - cur_); }
     uint8_t u8() { return *cur_++; }
@@ -196,6 +232,8 @@ struct Reader {
     jpeggpu_status read_dqt(const Logger& log);
     jpeggpu_status read_dri(const Logger& log);
     jpeggpu_status read_sos(const Logger& log);
+    jpeggpu_status read_sos_progressive(const Logger& log);
+    jpeggpu_status finish_progressive(const Logger& log);
     jpeggpu_status walk_scan(Scan& scan, const Logger& log);
     jpeggpu_status skip_segment(const Logger& log);
     void note_app_segment(uint8_t marker);
