@@ -513,7 +513,8 @@ enum jpeggpu_status jpeggpu_ext_resize_weights(
  *          (libjpeg hands out 255 - r ... in place of the samples, and Pillow inverts those like any CMYK file's).
  * On planes of a JPEGGPU_EXT_IDCT_ISLOW decode with the model jpeggpu_ext_get_color_space reported, this is
  * Image.open(f).convert("RGB") for every file Pillow opens as L, RGB or CMYK (in the JPEGGPU_EXT_SCALE_LIBJPEG mode: after
- * draft()). Embedded ICC profiles and EXIF orientation are ignored, as convert("RGB") ignores them.
+ * draft()). Embedded ICC profiles are ignored, as convert("RGB") ignores them; so is EXIF orientation by these calls -- the
+ * oriented calls further down apply it.
  * JPEGGPU_NOT_SUPPORTED: a model that does not fit info's component count (GRAY 1, YCBCR and RGB 3, CMYK and YCCK 4),
  * UNKNOWN, non-integral sampling ratios; nothing is written then. The entry points without a model are these with GRAY for
  * one component and YCBCR for three (so 2 or 4 components stay JPEGGPU_NOT_SUPPORTED there). A NULL `colors`:
@@ -612,6 +613,84 @@ struct jpeggpu_ext_progressive_info {
 };
 enum jpeggpu_status jpeggpu_ext_set_progressive(jpeggpu_decoder_t decoder, int enable);
 enum jpeggpu_status jpeggpu_ext_get_progressive_info(jpeggpu_decoder_t decoder, struct jpeggpu_ext_progressive_info* info);
+
+/* EXIF orientation. jpeggpu_decoder_parse_header reads the Exif APP1 segments in front of the first scan the way Pillow
+ * 12 does and jpeggpu_ext_get_orientation reports the Orientation tag (0x0112) of the last parsed image, 1..8:
+ *   - the data is the first segment's that begins "Exif\0\0", with that of every later such segment (behind its six
+ *     bytes) appended; a TIFF header: "II" with 42 in either byte order, or "MM" with 42 in either order or 43, then the
+ *     offset of IFD0; IFD0's 12-byte entries are read for as long as whole ones lie in the data;
+ *   - an entry of tag 0x0112, a TIFF type 1..13 or 16, a non-empty value that lies in the data: the first of its values
+ *     counts, and a later such entry replaces an earlier. Of types SHORT, LONG, SSHORT, SLONG the values 1..8 are the
+ *     orientation. Everything else is orientation 1: no segment, a truncated or malformed one, an offset outside the data,
+ *     another type, the values 0 and 9..; a bad Exif segment never fails parse_header. One difference from Pillow, on
+ *     purpose: a tag of type RATIONAL, SRATIONAL, FLOAT, DOUBLE, IFD or LONG8 is not converted and is orientation 1,
+ *     where Pillow's exif_transpose would honour a value that compares equal to 2..8 (a DOUBLE 6.0). No camera or
+ *     editor is known to write the tag so; the EXIF standard fixes it as SHORT.
+ *   - Pillow's fallback to an XMP tiff:Orientation attribute when EXIF has none is NOT read: such a file is orientation 1.
+ * Nothing of the decode depends on it: planes, crops and every call above stay in STORED coordinates. With S the stored
+ * image, W x H at the decoder's scale, the DISPLAYED image O (ImageOps.exif_transpose) is
+ *   1  O[y][x] = S[y][x]            5  O[y][x] = S[x][y]           (5..8: O is H x W)
+ *   2  S[y][W-1-x]                  6  S[H-1-x][y]
+ *   3  S[H-1-y][W-1-x]              7  S[H-1-x][W-1-y]
+ *   4  S[H-1-y][x]                  8  S[x][W-1-y]
+ * jpeggpu_ext_orient_size and jpeggpu_ext_orient_rect are host-only and pure: the displayed size of a stored w x h image,
+ * and the stored rectangle (in place, in *x, *y, *rw, *rh) of a rectangle given in displayed coordinates -- pass it to
+ * jpeggpu_ext_set_crop, so a crop in displayed pixels still decodes only its restart segments. An orientation outside
+ * 1..8, sizes below 1 or a rectangle that does not lie in the displayed image: JPEGGPU_INVALID_ARGUMENT.
+ *
+ * jpeggpu_ext_planes_to_rgbi_oriented and jpeggpu_ext_crop_to_rgbi_oriented are the _cs conversions (`replicate` 0: the
+ * _fancy one, else the _replicate one) that write the DISPLAYED image: `width` x `height` and `crop` are stored, `dst`
+ * holds width x height pixels for 1..4 and height x width for 5..8, and `dst_pitch` is at least 3 x the displayed width
+ * (else, or with an orientation outside 1..8: JPEGGPU_INVALID_ARGUMENT). jpeggpu_ext_resize_to_rgb_oriented is
+ * jpeggpu_ext_resize_to_rgb_cs with an orientation per item (NULL: JPEGGPU_INVALID_ARGUMENT; the scratch size call: 0):
+ * each item's crop is the stored rectangle, and the result is what Pillow gives for the displayed rectangle resized to
+ * out_w x out_h -- its horizontal, rounded pass runs along DISPLAYED x. With orientation 1 every one of these launches
+ * exactly what its _cs counterpart launches; a resize call with items of 5..8 takes one launch more. */
+enum jpeggpu_status jpeggpu_ext_get_orientation(jpeggpu_decoder_t decoder, int* orientation);
+enum jpeggpu_status jpeggpu_ext_orient_size(int orientation, int w, int h, int* out_w, int* out_h);
+enum jpeggpu_status jpeggpu_ext_orient_rect(int orientation, int w, int h, int* x, int* y, int* rw, int* rh);
+enum jpeggpu_status jpeggpu_ext_planes_to_rgbi_oriented(
+    const struct jpeggpu_img_info* info,
+    enum jpeggpu_ext_color_space color,
+    int orientation,
+    int replicate,
+    const struct jpeggpu_img* src,
+    uint8_t* dst,
+    int dst_pitch,
+    int width,
+    int height,
+    jpeggpu_stream_t stream);
+enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_oriented(
+    const struct jpeggpu_img_info* info,
+    enum jpeggpu_ext_color_space color,
+    int orientation,
+    int replicate,
+    const struct jpeggpu_ext_crop_info* crop,
+    const struct jpeggpu_img* src,
+    uint8_t* dst,
+    int dst_pitch,
+    jpeggpu_stream_t stream);
+size_t jpeggpu_ext_resize_scratch_size_oriented(
+    const struct jpeggpu_ext_resize_item* items,
+    const enum jpeggpu_ext_color_space* colors,
+    const int* orientations,
+    int n,
+    int out_w,
+    int out_h,
+    enum jpeggpu_ext_filter filter);
+enum jpeggpu_status jpeggpu_ext_resize_to_rgb_oriented(
+    const struct jpeggpu_ext_resize_item* items,
+    const enum jpeggpu_ext_color_space* colors,
+    const int* orientations,
+    int n,
+    int out_w,
+    int out_h,
+    enum jpeggpu_ext_filter filter,
+    enum jpeggpu_ext_output_layout layout,
+    uint8_t* dst,
+    void* d_scratch,
+    size_t scratch_size,
+    jpeggpu_stream_t stream);
 
 #ifdef __cplusplus
 }

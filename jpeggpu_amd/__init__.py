@@ -21,6 +21,8 @@ from .api import (  # noqa: F401
     draft_scale,
     fused_tail_timeouts,
     lib,
+    orient_rect,
+    orient_size,
     parse_headers,
     planes_to_rgb,
     resize_scratch_size,

@@ -207,6 +207,19 @@ def lib():
         C.c_void_p]
     L.jpeggpu_ext_set_progressive.argtypes = [dec, C.c_int]
     L.jpeggpu_ext_get_progressive_info.argtypes = [dec, C.POINTER(ProgressiveInfo)]
+    L.jpeggpu_ext_get_orientation.argtypes = [dec, C.POINTER(C.c_int)]
+    L.jpeggpu_ext_orient_size.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.jpeggpu_ext_orient_rect.argtypes = [C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4
+    L.jpeggpu_ext_planes_to_rgbi_oriented.argtypes = [
+        C.POINTER(ImgInfo), C.c_int, C.c_int, C.c_int, C.POINTER(Img), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.jpeggpu_ext_crop_to_rgbi_oriented.argtypes = [
+        C.POINTER(ImgInfo), C.c_int, C.c_int, C.c_int, C.POINTER(CropInfo), C.POINTER(Img), C.c_void_p, C.c_int, C.c_void_p]
+    L.jpeggpu_ext_resize_scratch_size_oriented.restype = C.c_size_t
+    L.jpeggpu_ext_resize_scratch_size_oriented.argtypes = [
+        C.POINTER(ResizeItem), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int]
+    L.jpeggpu_ext_resize_to_rgb_oriented.argtypes = [
+        C.POINTER(ResizeItem), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+        C.c_void_p, C.c_size_t, C.c_void_p]
     L.jpeggpu_ext_resize_weights.argtypes = [
         C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
     _lib = L
@@ -302,6 +315,12 @@ class Decoder:
         cs = C.c_int()
         _check(lib().jpeggpu_ext_get_color_space(self._h, C.byref(cs)), "jpeggpu_ext_get_color_space")
         return ColorSpace(cs.value)
+
+    def orientation(self) -> int:
+        """jpeggpu_ext_get_orientation of the last parsed image: its EXIF Orientation as Pillow reads it, 1..8 (1: none)."""
+        o = C.c_int()
+        _check(lib().jpeggpu_ext_get_orientation(self._h, C.byref(o)), "jpeggpu_ext_get_orientation")
+        return o.value
 
     def set_progressive(self, on: bool = True):
         """Read progressive JPEGs (SOF2) from the next parse_header on; off by default, when they are NOT_SUPPORTED
@@ -473,8 +492,33 @@ def draft_scale(width, height, requested):
     return 8 if s >= 8 else 4 if s >= 4 else 2 if s >= 2 else 1
 
 
+def orient_size(orientation, w, h):
+    """jpeggpu_ext_orient_size (host only): the displayed (width, height) of a stored w x h image."""
+    ow, oh = C.c_int(), C.c_int()
+    _check(lib().jpeggpu_ext_orient_size(int(orientation), int(w), int(h), C.byref(ow), C.byref(oh)), "jpeggpu_ext_orient_size")
+    return ow.value, oh.value
+
+
+def orient_rect(orientation, w, h, rect):
+    """jpeggpu_ext_orient_rect (host only): the stored rectangle (x, y, w, h) of `rect`, given in displayed coordinates of a
+    stored w x h image -- what Decoder.set_crop takes."""
+    v = [C.c_int(int(a)) for a in rect]
+    _check(lib().jpeggpu_ext_orient_rect(int(orientation), int(w), int(h), *[C.byref(a) for a in v]), "jpeggpu_ext_orient_rect")
+    return tuple(a.value for a in v)
+
+
+def _frame_size(info):
+    """(width, height) of the image an ImgInfo's planes make: img_info has no frame size, but the plane of a component
+    with the largest factor has exactly the frame's extent."""
+    n = info.num_components
+    hmax, vmax = max(info.subsampling.x[:n]), max(info.subsampling.y[:n])
+    return (info.sizes_x[[c for c in range(n) if info.subsampling.x[c] == hmax][0]],
+            info.sizes_y[[c for c in range(n) if info.subsampling.y[c] == vmax][0]])
+
+
 def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp=False, device_scan=False, scale=1,
-                     idct="reference", crop=None, scale_mode="uniform", return_color=False, progressive=False):
+                     idct="reference", crop=None, scale_mode="uniform", return_color=False, progressive=False,
+                     displayed_crop=False, return_orientation=False):
     """Convenience wrapper used by tests: full call sequence on torch's current stream, returns the
     planes as torch uint8 tensors on `device` (torch is only the allocator / stream provider). With
     `device_scan` the restart markers are found on the device and a status it reports there is raised.
@@ -483,7 +527,9 @@ def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp
     is returned as well: (planes, info, crop_info). `scale_mode`: "uniform" or "libjpeg" (Decoder.set_scale_mode); the
     returned info then carries the planes' effective sampling factors. `return_color`: the file's ColorSpace
     (Decoder.color_space) is appended to what is returned. `progressive`: progressive files are decoded
-    (Decoder.set_progressive); with `return_tmp` the ProgressiveInfo follows the layout."""
+    (Decoder.set_progressive); with `return_tmp` the ProgressiveInfo follows the layout. `displayed_crop`: `crop` is in
+    displayed coordinates of the file's EXIF orientation (the header is parsed once more to learn it; orient_rect).
+    `return_orientation`: Decoder.orientation is appended last."""
     import torch
 
     dec = Decoder(subseq_bytes)
@@ -496,10 +542,13 @@ def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp
             dec.set_idct(idct)
         if device_scan:
             dec.set_device_scan(True)
-        if crop is not None:
-            dec.set_crop(*crop)
         if progressive:
             dec.set_progressive(True)
+        if crop is not None and displayed_crop:
+            w, h = _frame_size(dec.parse_header(data))
+            crop = orient_rect(dec.orientation(), w, h, crop)
+        if crop is not None:
+            dec.set_crop(*crop)
         info = dec.parse_header(data)
         n = dec.get_buffer_size()
         tmp = torch.empty(n + 256, dtype=torch.uint8, device=device)
@@ -521,29 +570,40 @@ def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp
                 out += (dec.progressive_info(),)
         if return_color:
             out += (dec.color_space(),)
+        if return_orientation:
+            out += (dec.orientation(),)
         return out
     finally:
         dec.cleanup()
 
 
-def planes_to_rgb(planes, info, fancy=True, device=None, replicate=False, color=None):
+def planes_to_rgb(planes, info, fancy=True, device=None, replicate=False, color=None, orientation=None):
     """Planes of a 1- or 3-component image (as decode_to_planes returns them) -> (H, W, 3) uint8 tensor at the full image
     size, on torch's current stream: jpeggpu_ext_planes_to_rgbi_fancy (libjpeg's fancy upsampling and integer colour
     conversion) or, with fancy=False, jpeggpu_ext_planes_to_rgbi (the reference's helper). `replicate`:
     jpeggpu_ext_planes_to_rgbi_replicate -- libjpeg's conversion with replication, its output at 1/8 in the libjpeg scale
     mode. `color`: the planes' ColorSpace (Decoder.color_space) -- the _cs form of the fancy or replicating call, which also
-    converts RGB-, CMYK- and YCCK-coded files (four planes); None: grey or YCbCr by the number of components."""
+    converts RGB-, CMYK- and YCCK-coded files (four planes); None: grey or YCbCr by the number of components.
+    `orientation`: an EXIF orientation 1..8 (Decoder.orientation) -- jpeggpu_ext_planes_to_rgbi_oriented, the displayed
+    image: (W, H, 3) for 5..8."""
     import torch
 
     n = info.num_components
     device = planes[0].device if device is None else torch.device(device)
-    hmax, vmax = max(info.subsampling.x[:n]), max(info.subsampling.y[:n])
-    # img_info has no frame size; the plane of a component with the largest factor has exactly the frame's extent
-    width = info.sizes_x[[c for c in range(n) if info.subsampling.x[c] == hmax][0]]
-    height = info.sizes_y[[c for c in range(n) if info.subsampling.y[c] == vmax][0]]
+    width, height = _frame_size(info)
     src = Img()
     for c in range(n):
         src.image[c], src.pitch[c] = planes[c].data_ptr(), planes[c].stride(0)
+    if orientation is not None:
+        if not (fancy or replicate):
+            raise ValueError("the reference's helper (fancy=False) takes no orientation")
+        ow, oh = (height, width) if 5 <= int(orientation) <= 8 else (width, height)
+        out = torch.empty((oh, ow, 3), dtype=torch.uint8, device=device)
+        cs = int(color) if color is not None else (int(ColorSpace.GRAY) if n == 1 else int(ColorSpace.YCBCR) if n == 3 else 0)
+        _check(lib().jpeggpu_ext_planes_to_rgbi_oriented(C.byref(info), cs, int(orientation), int(bool(replicate)), C.byref(src), out.data_ptr(),
+                                                         3 * ow, width, height, torch.cuda.current_stream(device).cuda_stream),
+               "jpeggpu_ext_planes_to_rgbi_oriented")
+        return out
     out = torch.empty((height, width, 3), dtype=torch.uint8, device=device)
     stream = torch.cuda.current_stream(device).cuda_stream
     name = "jpeggpu_ext_planes_to_rgbi_replicate" if replicate else "jpeggpu_ext_planes_to_rgbi_fancy" if fancy else "jpeggpu_ext_planes_to_rgbi"
@@ -557,10 +617,11 @@ def planes_to_rgb(planes, info, fancy=True, device=None, replicate=False, color=
     return out
 
 
-def crop_to_rgb(planes, info, crop_info, device=None, replicate=False, color=None):
+def crop_to_rgb(planes, info, crop_info, device=None, replicate=False, color=None, orientation=None):
     """The window planes of a cropped decode (decode_to_planes(..., crop=...)) -> (h, w, 3) uint8 tensor of the rectangle,
     equal to that part of planes_to_rgb's image of the uncropped planes (jpeggpu_ext_crop_to_rgbi_fancy, or with
-    `replicate` jpeggpu_ext_crop_to_rgbi_replicate). `color`: as in planes_to_rgb."""
+    `replicate` jpeggpu_ext_crop_to_rgbi_replicate). `color`: as in planes_to_rgb. `orientation`: as in planes_to_rgb --
+    crop_info is the STORED rectangle (orient_rect), the result the displayed one (jpeggpu_ext_crop_to_rgbi_oriented)."""
     import torch
 
     n = info.num_components
@@ -569,6 +630,14 @@ def crop_to_rgb(planes, info, crop_info, device=None, replicate=False, color=Non
     for c in range(n):
         src.image[c], src.pitch[c] = planes[c].data_ptr(), planes[c].stride(0)
     w, h = crop_info.width, crop_info.height
+    if orientation is not None:
+        ow, oh = (h, w) if 5 <= int(orientation) <= 8 else (w, h)
+        out = torch.empty((oh, ow, 3), dtype=torch.uint8, device=device)
+        cs = int(color) if color is not None else (int(ColorSpace.GRAY) if n == 1 else int(ColorSpace.YCBCR) if n == 3 else 0)
+        _check(lib().jpeggpu_ext_crop_to_rgbi_oriented(C.byref(info), cs, int(orientation), int(bool(replicate)), C.byref(crop_info), C.byref(src),
+                                                       out.data_ptr(), 3 * ow, torch.cuda.current_stream(device).cuda_stream),
+               "jpeggpu_ext_crop_to_rgbi_oriented")
+        return out
     out = torch.empty((h, w, 3), dtype=torch.uint8, device=device)
     stream = torch.cuda.current_stream(device).cuda_stream
     name = "jpeggpu_ext_crop_to_rgbi_replicate" if replicate else "jpeggpu_ext_crop_to_rgbi_fancy"
@@ -586,7 +655,7 @@ def _needs_replication(info, scale):
     return scale == 8 and (len(set(info.subsampling.x[:n])) > 1 or len(set(info.subsampling.y[:n])) > 1)
 
 
-def decode_to_rgb(data: bytes, device="cuda:0", device_scan=False, crop=None, scale=1):
+def decode_to_rgb(data: bytes, device="cuda:0", device_scan=False, crop=None, scale=1, exif_transpose=False):
     """Decode a JPEG to an (H, W, 3) uint8 tensor on `device` the way libjpeg-turbo does: the ISLOW IDCT at full size, then
     fancy upsampling and the conversion of the file's colour model (Decoder.color_space): grey, YCbCr (jdcolor.c's integer
     conversion), RGB-coded files as they are, CMYK and YCCK by Pillow's rule for Adobe's inverted samples. Meant to equal
@@ -594,17 +663,22 @@ def decode_to_rgb(data: bytes, device="cuda:0", device_scan=False, crop=None, sc
     w, h) only that rectangle is decoded: an (h, w, 3) tensor equal to decode_to_rgb(data)[y:y + h, x:x + w].
     `scale` = d in 2, 4, 8: the image at 1/d as libjpeg-turbo scales it (the libjpeg scale mode: per-component IDCT sizes,
     replication instead of fancy upsampling at 1/8), equal to im.draft("RGB", (W // d, H // d)); im.convert("RGB") in
-    Pillow; `crop` is then in pixels of that image. Progressive files are decoded too (Decoder.set_progressive)."""
+    Pillow; `crop` is then in pixels of that image. Progressive files are decoded too (Decoder.set_progressive).
+    `exif_transpose`: the file's EXIF orientation (Decoder.orientation) is applied -- the result is the DISPLAYED image,
+    (W, H, 3) for orientations 5..8, and `crop` is in displayed pixels at the scale: what ImageOps.exif_transpose(im) put
+    after draft() and before convert("RGB") and crop() gives. The XMP orientation Pillow falls back to is not read."""
     import torch
 
     kw = dict(device=device, device_scan=device_scan, idct="islow", scale=scale, scale_mode="libjpeg", return_color=True, progressive=True)
+    if exif_transpose:
+        kw.update(displayed_crop=True, return_orientation=True)
     if crop is not None:
-        planes, info, crop_info, color = decode_to_planes(data, crop=crop, **kw)
-        rgb = crop_to_rgb(planes, info, crop_info, replicate=_needs_replication(info, scale), color=color)
+        planes, info, crop_info, color, *o = decode_to_planes(data, crop=crop, **kw)
+        rgb = crop_to_rgb(planes, info, crop_info, replicate=_needs_replication(info, scale), color=color, orientation=o[0] if o else None)
         torch.cuda.synchronize(torch.device(device))
         return rgb
-    planes, info, color = decode_to_planes(data, **kw)
-    rgb = planes_to_rgb(planes, info, fancy=True, replicate=_needs_replication(info, scale), color=color)
+    planes, info, color, *o = decode_to_planes(data, **kw)
+    rgb = planes_to_rgb(planes, info, fancy=True, replicate=_needs_replication(info, scale), color=color, orientation=o[0] if o else None)
     torch.cuda.synchronize(torch.device(device))
     return rgb
 
@@ -682,23 +756,36 @@ def _color_array(colors, n):
     return (C.c_int * n)(*[int(c) for c in colors])
 
 
-def resize_scratch_size(planes_list, infos, size, crop_infos=None, filt="bilinear", colors=None):
+def _item_colors(colors, infos):
+    """`colors`, or grey / YCbCr by each item's component count (what the calls without a model assume)."""
+    if colors is not None:
+        return colors
+    return [ColorSpace.GRAY if i.num_components == 1 else ColorSpace.YCBCR if i.num_components == 3 else ColorSpace.UNKNOWN for i in infos]
+
+
+def resize_scratch_size(planes_list, infos, size, crop_infos=None, filt="bilinear", colors=None, orientations=None):
     """jpeggpu_ext_resize_scratch_size of these items (0 if the call would refuse them); with `colors` (one ColorSpace
-    per item) jpeggpu_ext_resize_scratch_size_cs."""
+    per item) jpeggpu_ext_resize_scratch_size_cs; with `orientations` jpeggpu_ext_resize_scratch_size_oriented."""
     h, w = _size_hw(size)
     items, _keep = _resize_items(planes_list, infos, crop_infos)
+    if orientations is not None:
+        n = len(planes_list)
+        return lib().jpeggpu_ext_resize_scratch_size_oriented(items, _color_array(_item_colors(colors, infos), n), _color_array(orientations, n),
+                                                              n, w, h, FILTERS[filt])
     if colors is not None:
         return lib().jpeggpu_ext_resize_scratch_size_cs(items, _color_array(colors, len(planes_list)), len(planes_list), w, h, FILTERS[filt])
     return lib().jpeggpu_ext_resize_scratch_size(items, len(planes_list), w, h, FILTERS[filt])
 
 
-def resize_to_rgb(planes_list, infos, size, crop_infos=None, filt="bilinear", layout="NHWC", out=None, colors=None):
+def resize_to_rgb(planes_list, infos, size, crop_infos=None, filt="bilinear", layout="NHWC", out=None, colors=None, orientations=None):
     """jpeggpu_ext_resize_to_rgb on torch's current stream: every decoded image i
     (planes_list[i], infos[i], and crop_infos[i] from a cropped decode, or None for the whole image) resampled to `size`
     (int: square; (h, w)) with Pillow's BILINEAR or BICUBIC arithmetic. Returns a uint8 tensor of n x h x w x 3 ("NHWC")
     or n x 3 x h x w ("NCHW"), `out` if given (contiguous, of that shape). `colors`: each image's ColorSpace
     (Decoder.color_space; jpeggpu_ext_resize_to_rgb_cs -- a call may mix grey, YCbCr, RGB, CMYK and YCCK items); None: grey
-    or YCbCr by the number of components."""
+    or YCbCr by the number of components. `orientations`: each image's EXIF orientation 1..8
+    (jpeggpu_ext_resize_to_rgb_oriented): crop_infos are the STORED rectangles (orient_rect), and the result is the
+    DISPLAYED rectangle resized, as Pillow resizes ImageOps.exif_transpose's image."""
     import torch
 
     if filt not in FILTERS:
@@ -715,6 +802,13 @@ def resize_to_rgb(planes_list, infos, size, crop_infos=None, filt="bilinear", la
     elif tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous():
         raise ValueError("out must be a contiguous uint8 tensor of shape %s" % (shape,))
     stream = torch.cuda.current_stream(device).cuda_stream
+    if orientations is not None:
+        cs, os_ = _color_array(_item_colors(colors, infos), n), _color_array(orientations, n)
+        need = lib().jpeggpu_ext_resize_scratch_size_oriented(items, cs, os_, n, w, h, FILTERS[filt])
+        scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+        _check(lib().jpeggpu_ext_resize_to_rgb_oriented(items, cs, os_, n, w, h, FILTERS[filt], LAYOUTS[layout], out.data_ptr(),
+                                                        scratch.data_ptr(), need, stream), "jpeggpu_ext_resize_to_rgb_oriented")
+        return out
     if colors is not None:
         cs = _color_array(colors, n)
         need = lib().jpeggpu_ext_resize_scratch_size_cs(items, cs, n, w, h, FILTERS[filt])
@@ -730,7 +824,7 @@ def resize_to_rgb(planes_list, infos, size, crop_infos=None, filt="bilinear", la
     return out
 
 
-def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", device="cuda:0", scales=None):
+def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", device="cuda:0", scales=None, exif_transpose=False):
     """A training pipeline's decode: every JPEG of `datas` (of any colour model: decode_to_rgb) decoded with libjpeg-turbo's
     arithmetic (ISLOW IDCT, fancy upsampling), only the rectangle crops[i] = (x, y, w, h) of it (None: the whole image), in ONE jpeggpu_ext_decode_batch
     call, then resized to `size` (int: square; (h, w)) with Pillow's BILINEAR or BICUBIC arithmetic by one
@@ -740,7 +834,9 @@ def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", devi
     decoded at that scale the way libjpeg-turbo does (decode_to_rgb's `scale`; draft_scale gives Pillow's choice), crops[i]
     is in pixels of the image at that scale, and the result equals im.draft("RGB", ...); im.convert("RGB").crop(...)
     .resize(...). A ValueError for an image that libjpeg would upsample by replication (1/8 with subsampling left, e.g.
-    4:2:2): the batched resize does not reproduce that; use scale 4 for it."""
+    4:2:2): the batched resize does not reproduce that; use scale 4 for it. `exif_transpose`: every file's EXIF
+    orientation is applied -- crops[i] is in DISPLAYED pixels at the scale, and the result equals
+    ImageOps.exif_transpose(im) put after draft() and before convert("RGB"), crop() and resize()."""
     import torch
 
     dev = torch.device(device)
@@ -752,7 +848,7 @@ def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", devi
     if len(scales) != n or any(s not in (1, 2, 4, 8) for s in scales):
         raise ValueError("scales must have one entry of 1, 2, 4 or 8 per image")
     stream = torch.cuda.current_stream(dev).cuda_stream
-    decs, entries, planes_list, infos, cis, keep, colors = [], [], [], [], [], [], []
+    decs, entries, planes_list, infos, cis, keep, colors, orients = [], [], [], [], [], [], [], []
     try:
         scans = 0
         for i, (data, crop, scale) in enumerate(zip(datas, crops, scales)):
@@ -764,9 +860,13 @@ def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", devi
             if scale != 1:
                 dec.set_scale(scale)
                 dec.set_scale_mode("libjpeg")
+            if crop is not None and exif_transpose:  # the header once more, for the orientation and the size at the scale
+                w0, h0 = _frame_size(dec.parse_header(data))
+                crop = orient_rect(dec.orientation(), w0, h0, crop)
             if crop is not None:
                 dec.set_crop(*crop)
             info = dec.parse_header(data)
+            orients.append(dec.orientation())
             if _needs_replication(info, scale):
                 raise ValueError("image %d at scale 1/8 has subsampling left (%s x %s): libjpeg replicates there, which the "
                                  "batched resize does not reproduce" % (i, list(info.subsampling.x[:info.num_components]),
@@ -788,7 +888,7 @@ def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", devi
         scratch = torch.empty(batch.scratch_size, dtype=torch.uint8, device=dev)
         batch.set_items(entries)
         batch.decode(scratch.data_ptr(), stream)
-        out = resize_to_rgb(planes_list, infos, size, cis, filt, layout, colors=colors)
+        out = resize_to_rgb(planes_list, infos, size, cis, filt, layout, colors=colors, orientations=orients if exif_transpose else None)
         torch.cuda.synchronize(dev)
         batch.destroy()
         return out

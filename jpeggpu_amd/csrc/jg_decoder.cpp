@@ -1203,6 +1203,14 @@ enum jpeggpu_status jpeggpu_ext_get_color_space(jpeggpu_decoder_t decoder, enum 
     return JPEGGPU_SUCCESS;
 }
 
+enum jpeggpu_status jpeggpu_ext_get_orientation(jpeggpu_decoder_t decoder, int* orientation)
+{
+    if (!decoder || !orientation) return JPEGGPU_INVALID_ARGUMENT;
+    if (!decoder->d.parsed) return JPEGGPU_INVALID_ARGUMENT;
+    *orientation = decoder->d.reader.s.orientation;
+    return JPEGGPU_SUCCESS;
+}
+
 enum jpeggpu_status jpeggpu_ext_set_progressive(jpeggpu_decoder_t decoder, int enable)
 {
     if (!decoder) return JPEGGPU_INVALID_ARGUMENT;

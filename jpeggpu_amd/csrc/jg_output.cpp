@@ -211,15 +211,56 @@ struct ResizePlan {
     size_t off_first = 0, head = 0, total = 0;
     int h_tiles      = 0;
     bool all_models  = false; // an item that is not grey or YCbCr (fancy_all_models)
+    // a call with orientations (jpeggpu_ext_resize_to_rgb_oriented): in_w x in_h is the DISPLAYED rectangle; items of 5..8
+    // have their tiles in first_tile_t (the transposing first pass) and none in first_tile, the others the other way round
+    std::vector<int> orient, first_tile_t;
+    size_t off_first_t = 0;
+    int t_tiles        = 0;
+    bool mirror_store  = false; // an item with kResizeMirrorStore
 };
 
-/// `colors`: each item's colour model, or null: by its component count (color_by_count).
+/// A weight table of `out` coordinates over an axis of `in` samples, turned to run against the axis: coordinate x keeps
+/// its place, its taps are sample in - 1 - s for every s they were, so first becomes in - first - count and the weights
+/// are reversed. The weights themselves are never computed again for the mirrored axis: Pillow's float centres are not
+/// symmetric to the last of the 22 fraction bits. `t`: {first, count}[out], weights[out][taps].
+void mirror_taps(int* t, int in, int out, int taps)
+{
+    for (int x = 0; x < out; ++x) {
+        const int cnt = t[2 * x + 1];
+        t[2 * x]      = in - t[2 * x] - cnt;
+        int* w        = t + 2 * out + static_cast<size_t>(x) * taps;
+        std::reverse(w, w + cnt);
+    }
+}
+
+/// The table's coordinates in reverse order: entry x becomes entry out - 1 - x (mirror_taps + this: the table of a
+/// mirrored axis in stored order, first ascending again).
+void reverse_columns(int* t, int out, int taps)
+{
+    for (int x = 0, y = out - 1; x < y; ++x, --y) {
+        std::swap(t[2 * x], t[2 * y]);
+        std::swap(t[2 * x + 1], t[2 * y + 1]);
+        std::swap_ranges(t + 2 * out + static_cast<size_t>(x) * taps, t + 2 * out + static_cast<size_t>(x + 1) * taps, t + 2 * out + static_cast<size_t>(y) * taps);
+    }
+}
+
+/// `colors`: each item's colour model, or null: by its component count (color_by_count). `orients`: each item's EXIF
+/// orientation, or null: 1 for all -- the plan, the scratch layout and the launches are then what they were without it.
 jpeggpu_status plan_resize(
-    const jpeggpu_ext_resize_item* items, const jpeggpu_ext_color_space* colors, int n, int out_w, int out_h, int filter, ResizePlan& p)
+    const jpeggpu_ext_resize_item* items, const jpeggpu_ext_color_space* colors, const int* orients, int n, int out_w, int out_h, int filter,
+    ResizePlan& p)
 {
     if (!items || n <= 0 || n > 65535 || out_w <= 0 || out_h <= 0) return JPEGGPU_INVALID_ARGUMENT;
     if (filter != JPEGGPU_EXT_FILTER_BILINEAR && filter != JPEGGPU_EXT_FILTER_BICUBIC) return JPEGGPU_NOT_SUPPORTED;
+    bool transposing = false;
+    for (int i = 0; orients && i < n; ++i) {
+        if (!orient_valid(orients[i])) return JPEGGPU_INVALID_ARGUMENT;
+        transposing = transposing || orient_transposes(orients[i]);
+    }
     try {
+        p.orient.assign(n, 1);
+        if (orients) p.orient.assign(orients, orients + n);
+        if (transposing) p.first_tile_t.resize(n);
         p.jobs.resize(n);
         p.first_tile.resize(n);
         p.in_w.resize(n);
@@ -233,12 +274,18 @@ jpeggpu_status plan_resize(
     size_t off     = align_up(sizeof(ResizeJob) * n, 256);
     p.off_first    = off;
     off            = align_up(off + sizeof(int) * n, 256);
-    int64_t tiles  = 0;
+    if (transposing) {
+        p.off_first_t = off;
+        off           = align_up(off + sizeof(int) * n, 256);
+    }
+    int64_t tiles  = 0, tiles_t = 0;
     const int pitch = static_cast<int>(align_up(3 * static_cast<size_t>(out_w), 16));
     for (int i = 0; i < n; ++i) {
         const jpeggpu_status st = resize_item(items[i], colors ? static_cast<int>(colors[i]) : color_by_count(items[i].info), p.jobs[i], p.in_w[i], p.in_h[i]);
         if (st != JPEGGPU_SUCCESS) return st;
         p.all_models = p.all_models || fancy_all_models(p.jobs[i].src);
+        const int o = p.orient[i];
+        if (orient_transposes(o)) std::swap(p.in_w[i], p.in_h[i]); // the displayed rectangle from here on
         p.off_tab_x[i] = off;
         off += align_up(resize_table_bytes(p.in_w[i], out_w, filter), 16);
         p.off_tab_y[i] = off;
@@ -255,15 +302,22 @@ jpeggpu_status plan_resize(
             int f0 = 0, n0 = 0, f1 = 0, n1 = 0;
             resize_bounds(p.in_h[i], out_h, filter, 0, &f0, &n0);
             resize_bounds(p.in_h[i], out_h, filter, out_h - 1, &f1, &n1);
-            j.row0 = f0;
+            j.row0 = orient_mirrors_y(o) ? p.in_h[i] - (f1 + n1) : f0; // rows of `mid` are in stored order (mirror_taps)
             j.rows = f1 + n1 - f0;
         }
+        if (!orient_transposes(o) && orient_mirrors_x(o)) {
+            j.pad_         = kResizeMirrorStore;
+            p.mirror_store = true;
+        }
         p.first_tile[i] = static_cast<int>(tiles);
-        tiles += resize_h_tiles(j.rows, out_w);
-        if (tiles > INT32_MAX) return JPEGGPU_INVALID_ARGUMENT;
+        if (transposing) p.first_tile_t[i] = static_cast<int>(tiles_t);
+        if (orient_transposes(o)) tiles_t += resize_t_tiles(j.rows, out_w);
+        else tiles += resize_h_tiles(j.rows, out_w);
+        if (tiles > INT32_MAX || tiles_t > INT32_MAX) return JPEGGPU_INVALID_ARGUMENT;
     }
     p.head  = off;
     p.h_tiles = static_cast<int>(tiles);
+    p.t_tiles = static_cast<int>(tiles_t);
     for (int i = 0; i < n; ++i) {
         p.off_mid[i] = off;
         off          = align_up(off + static_cast<size_t>(p.jobs[i].rows) * pitch, 256);
@@ -431,10 +485,11 @@ enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_replicate(
 
 namespace {
 size_t resize_scratch_size(
-    const struct jpeggpu_ext_resize_item* items, const enum jpeggpu_ext_color_space* colors, int n, int out_w, int out_h, enum jpeggpu_ext_filter filter)
+    const struct jpeggpu_ext_resize_item* items, const enum jpeggpu_ext_color_space* colors, const int* orients, int n, int out_w, int out_h,
+    enum jpeggpu_ext_filter filter)
 {
     jg::ResizePlan p;
-    return jg::plan_resize(items, colors, n, out_w, out_h, filter, p) == JPEGGPU_SUCCESS ? p.total : 0;
+    return jg::plan_resize(items, colors, orients, n, out_w, out_h, filter, p) == JPEGGPU_SUCCESS ? p.total : 0;
 }
 } // namespace
 
@@ -442,13 +497,13 @@ size_t jpeggpu_ext_resize_scratch_size_cs(
     const struct jpeggpu_ext_resize_item* items, const enum jpeggpu_ext_color_space* colors, int n, int out_w, int out_h,
     enum jpeggpu_ext_filter filter)
 {
-    return colors ? resize_scratch_size(items, colors, n, out_w, out_h, filter) : 0;
+    return colors ? resize_scratch_size(items, colors, nullptr, n, out_w, out_h, filter) : 0;
 }
 
 size_t jpeggpu_ext_resize_scratch_size(
     const struct jpeggpu_ext_resize_item* items, int n, int out_w, int out_h, enum jpeggpu_ext_filter filter)
 {
-    return resize_scratch_size(items, nullptr, n, out_w, out_h, filter);
+    return resize_scratch_size(items, nullptr, nullptr, n, out_w, out_h, filter);
 }
 
 enum jpeggpu_status jpeggpu_ext_resize_weights(
@@ -467,10 +522,11 @@ enum jpeggpu_status jpeggpu_ext_resize_weights(
 }
 
 namespace {
-/// `colors` null: each item's model by its component count.
+/// `colors` null: each item's model by its component count. `orients` null: orientation 1 for all.
 enum jpeggpu_status resize_to_rgb(
     const struct jpeggpu_ext_resize_item* items,
     const enum jpeggpu_ext_color_space* colors,
+    const int* orients,
     int n,
     int out_w,
     int out_h,
@@ -482,7 +538,7 @@ enum jpeggpu_status resize_to_rgb(
     jpeggpu_stream_t stream)
 {
     jg::ResizePlan p;
-    const jpeggpu_status st = jg::plan_resize(items, colors, n, out_w, out_h, filter, p);
+    const jpeggpu_status st = jg::plan_resize(items, colors, orients, n, out_w, out_h, filter, p);
     if (st != JPEGGPU_SUCCESS) return st;
     if (!dst || !d_scratch || (layout != JPEGGPU_EXT_NHWC && layout != JPEGGPU_EXT_NCHW) || scratch_size < p.total)
         return JPEGGPU_INVALID_ARGUMENT;
@@ -513,6 +569,10 @@ enum jpeggpu_status resize_to_rgb(
                     t[2 * x]     = fc[x];
                     t[2 * x + 1] = cnt[x];
                 }
+                // the tables are those of the DISPLAYED axes; a mirrored axis gets them permuted for the stored order
+                const int o = p.orient[i];
+                if (d == 0 ? jg::orient_mirrors_x(o) : jg::orient_mirrors_y(o)) jg::mirror_taps(t, in, out, taps);
+                if (d == 0 && (j.pad_ & jg::kResizeMirrorStore)) jg::reverse_columns(t, out, taps);
             }
         }
     } catch (const std::bad_alloc&) {
@@ -520,14 +580,16 @@ enum jpeggpu_status resize_to_rgb(
     }
     std::memcpy(h, p.jobs.data(), sizeof(jg::ResizeJob) * n);
     std::memcpy(h + p.off_first, p.first_tile.data(), sizeof(int) * n);
+    if (!p.first_tile_t.empty()) std::memcpy(h + p.off_first_t, p.first_tile_t.data(), sizeof(int) * n);
     if (!rs.copied[r] && hipEventCreateWithFlags(&rs.copied[r], hipEventDisableTiming) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
     if (hipMemcpyAsync(base, h, p.head, hipMemcpyHostToDevice, stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
     if (hipEventRecord(rs.copied[r], stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
     rs.in_use[r] = true;
     rs.next      = (r + 1) % jg::ResizeStaging::kRing;
-    const hipError_t err = jg::launch_resize(
-        reinterpret_cast<const jg::ResizeJob*>(base), reinterpret_cast<const int*>(base + p.off_first), n, p.h_tiles, out_w, out_h,
-        layout, p.all_models, dst, stream);
+    const hipError_t err = jg::launch_resize_oriented(
+        reinterpret_cast<const jg::ResizeJob*>(base), reinterpret_cast<const int*>(base + p.off_first),
+        reinterpret_cast<const int*>(base + p.off_first_t), n, p.h_tiles, p.t_tiles, p.mirror_store, out_w, out_h, layout, p.all_models, dst,
+        stream);
     return err == hipSuccess ? JPEGGPU_SUCCESS : JPEGGPU_INTERNAL_ERROR;
 }
 } // namespace
@@ -546,7 +608,7 @@ enum jpeggpu_status jpeggpu_ext_resize_to_rgb_cs(
     jpeggpu_stream_t stream)
 {
     if (!colors) return JPEGGPU_INVALID_ARGUMENT;
-    return resize_to_rgb(items, colors, n, out_w, out_h, filter, layout, dst, d_scratch, scratch_size, stream);
+    return resize_to_rgb(items, colors, nullptr, n, out_w, out_h, filter, layout, dst, d_scratch, scratch_size, stream);
 }
 
 enum jpeggpu_status jpeggpu_ext_resize_to_rgb(
@@ -561,7 +623,91 @@ enum jpeggpu_status jpeggpu_ext_resize_to_rgb(
     size_t scratch_size,
     jpeggpu_stream_t stream)
 {
-    return resize_to_rgb(items, nullptr, n, out_w, out_h, filter, layout, dst, d_scratch, scratch_size, stream);
+    return resize_to_rgb(items, nullptr, nullptr, n, out_w, out_h, filter, layout, dst, d_scratch, scratch_size, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// EXIF orientation: the displayed image of the same conversions (jpeggpu_ext.h)
+// ------------------------------------------------------------------------------------------------
+
+enum jpeggpu_status jpeggpu_ext_orient_size(int orientation, int w, int h, int* out_w, int* out_h)
+{
+    if (!jg::orient_valid(orientation) || w < 1 || h < 1 || !out_w || !out_h) return JPEGGPU_INVALID_ARGUMENT;
+    *out_w = jg::orient_transposes(orientation) ? h : w;
+    *out_h = jg::orient_transposes(orientation) ? w : h;
+    return JPEGGPU_SUCCESS;
+}
+
+enum jpeggpu_status jpeggpu_ext_orient_rect(int orientation, int w, int h, int* x, int* y, int* rw, int* rh)
+{
+    if (!jg::orient_valid(orientation) || w < 1 || h < 1 || !x || !y || !rw || !rh) return JPEGGPU_INVALID_ARGUMENT;
+    const bool tr = jg::orient_transposes(orientation);
+    const int ow = tr ? h : w, oh = tr ? w : h;
+    const int dx = *x, dy = *y, dw = *rw, dh = *rh;
+    if (dx < 0 || dy < 0 || dw < 1 || dh < 1 || dw > ow - dx || dh > oh - dy) return JPEGGPU_INVALID_ARGUMENT;
+    // the displayed x range lies along stored y if the orientation transposes, along stored x otherwise; mirrored or not
+    const int ax = jg::orient_mirrors_x(orientation) ? ow - dx - dw : dx;
+    const int ay = jg::orient_mirrors_y(orientation) ? oh - dy - dh : dy;
+    *x  = tr ? ay : ax;
+    *y  = tr ? ax : ay;
+    *rw = tr ? dh : dw;
+    *rh = tr ? dw : dh;
+    return JPEGGPU_SUCCESS;
+}
+
+enum jpeggpu_status jpeggpu_ext_planes_to_rgbi_oriented(
+    const struct jpeggpu_img_info* info, enum jpeggpu_ext_color_space color, int orientation, int replicate, const struct jpeggpu_img* src,
+    uint8_t* dst, int dst_pitch, int width, int height, jpeggpu_stream_t stream)
+{
+    if (!jg::orient_valid(orientation)) return JPEGGPU_INVALID_ARGUMENT;
+    if (orientation == 1) return planes_to_rgbi_libjpeg(info, color, src, dst, dst_pitch, width, height, stream, replicate != 0);
+    if (!info || !src || !dst || width <= 0 || height <= 0 || dst_pitch < 3 * (jg::orient_transposes(orientation) ? height : width))
+        return JPEGGPU_INVALID_ARGUMENT;
+    jg::FancySource s;
+    const jpeggpu_status st = jg::fancy_source(info, color, nullptr, src, replicate != 0, false, s);
+    if (st != JPEGGPU_SUCCESS) return st;
+    return jg::launch_rgbi_oriented(s, orientation, dst, dst_pitch, width, height, stream) == hipSuccess ? JPEGGPU_SUCCESS : JPEGGPU_INTERNAL_ERROR;
+}
+
+enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_oriented(
+    const struct jpeggpu_img_info* info, enum jpeggpu_ext_color_space color, int orientation, int replicate,
+    const struct jpeggpu_ext_crop_info* crop, const struct jpeggpu_img* src, uint8_t* dst, int dst_pitch, jpeggpu_stream_t stream)
+{
+    if (!jg::orient_valid(orientation)) return JPEGGPU_INVALID_ARGUMENT;
+    if (orientation == 1) return crop_to_rgbi_libjpeg(info, color, crop, src, dst, dst_pitch, stream, replicate != 0);
+    if (!info || !crop || !src || !dst || crop->width <= 0 || crop->height <= 0 || crop->x < 0 || crop->y < 0 ||
+        dst_pitch < 3 * (jg::orient_transposes(orientation) ? crop->height : crop->width))
+        return JPEGGPU_INVALID_ARGUMENT;
+    jg::FancySource s;
+    const jpeggpu_status st = jg::fancy_source(info, color, crop, src, replicate != 0, true, s);
+    if (st != JPEGGPU_SUCCESS) return st;
+    return jg::launch_rgbi_oriented(s, orientation, dst, dst_pitch, crop->width, crop->height, stream) == hipSuccess ? JPEGGPU_SUCCESS
+                                                                                                                  : JPEGGPU_INTERNAL_ERROR;
+}
+
+size_t jpeggpu_ext_resize_scratch_size_oriented(
+    const struct jpeggpu_ext_resize_item* items, const enum jpeggpu_ext_color_space* colors, const int* orientations, int n, int out_w,
+    int out_h, enum jpeggpu_ext_filter filter)
+{
+    return colors && orientations ? resize_scratch_size(items, colors, orientations, n, out_w, out_h, filter) : 0;
+}
+
+enum jpeggpu_status jpeggpu_ext_resize_to_rgb_oriented(
+    const struct jpeggpu_ext_resize_item* items,
+    const enum jpeggpu_ext_color_space* colors,
+    const int* orientations,
+    int n,
+    int out_w,
+    int out_h,
+    enum jpeggpu_ext_filter filter,
+    enum jpeggpu_ext_output_layout layout,
+    uint8_t* dst,
+    void* d_scratch,
+    size_t scratch_size,
+    jpeggpu_stream_t stream)
+{
+    if (!colors || !orientations) return JPEGGPU_INVALID_ARGUMENT;
+    return resize_to_rgb(items, colors, orientations, n, out_w, out_h, filter, layout, dst, d_scratch, scratch_size, stream);
 }
 
 } // extern "C"

@@ -5,9 +5,13 @@
 //   fancy_rgbi_kernel       libjpeg's fancy chroma upsampling + integer YCbCr -> interleaved RGB (jdsample.c, jdcolor.c),
 //                           of a whole image (<false>) or of a rectangle read from the planes' windows (<true>)
 //   fancy_color_kernel      the same for every colour model: RGB-, CMYK- and YCCK-coded files too, as Pillow converts them
+//   fancy_mirrored_kernel / the same pixels written where an EXIF orientation displays them: 2..4 mirror the row kernel's
+//   fancy_transposed_kernel stores, 5..8 turn a square tile through LDS (jpeggpu_ext_planes_to_rgbi_oriented)
 //   resize_h_kernel /       batched resize to one size with Pillow's BILINEAR / BICUBIC arithmetic: the horizontal taps
 //   resize_v_kernel         straight from the planes' windows (fancy RGB in LDS), then the vertical taps (jpeggpu_ext_resize_to_rgb);
-//                           resize_h_color_kernel: the horizontal pass of a call that holds items of the other models
+//                           resize_h_color_kernel: the horizontal pass of a call that holds items of the other models;
+//                           resize_h_oriented_kernel / resize_t_kernel: the first pass of items whose displayed x runs
+//                           against stored x, or down stored columns (jpeggpu_ext_resize_to_rgb_oriented)
 //
 // Nothing here is shared with the decode path (jg_kernels.hip): the stage reads finished planes.
 #include "jg_output.hpp"
@@ -253,6 +257,105 @@ __global__ __launch_bounds__(256) void fancy_color_kernel(FancySource p, uint8_t
     fancy_rgbi_tile<kWindowed, true>(p, dst, dst_pitch, width, height);
 }
 
+// ------------------------------------------------------------------------------------------------
+// The same conversion written where an EXIF orientation displays it (jpeggpu_ext.h has the table). Upsampling and colour
+// conversion stay in stored coordinates -- fancy_stage, fancy_sample and fancy_pixel as they are -- and only the place a
+// pixel is written changes. `flips`: bit 0, displayed x runs against the stored axis it lies along; bit 1, displayed y.
+// ------------------------------------------------------------------------------------------------
+
+/// Orientations 2..4: fancy_rgbi_tile's tile and quads; a lane's four pixels are made in displayed order and stored at
+/// the mirrored position, so a wave still writes one contiguous run per row (dwords if the mirrored start is aligned).
+template <bool kWindowed, bool kAllModels>
+__device__ __forceinline__ void fancy_mirrored_tile(const FancySource& p, uint8_t* dst, int dst_pitch, int width, int height, int flips)
+{
+    __shared__ typename Fancy<kAllModels>::Tiles s_t;
+    const int t  = threadIdx.x;
+    const int x0 = blockIdx.x * kFancyTileW, y0 = blockIdx.y * kFancyTileH;
+    const int px = kWindowed ? p.x : 0, py = kWindowed ? p.y : 0;
+    int bx[Fancy<kAllModels>::kComps], by[Fancy<kAllModels>::kComps];
+    fancy_stage<kWindowed, kAllModels>(p, s_t, x0 + px, y0 + py, kFancyTileW, kFancyTileH, bx, by);
+    __syncthreads();
+    const int x = x0 + 4 * (t & 63);
+    if (x >= width) return;
+    const int np = min(4, width - x);
+    const bool mx = flips & 1, my = flips & 2;
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+        const int y = y0 + 2 * (t >> 6) + dy;
+        if (y >= height) break;
+        uint32_t out[12];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { // displayed pixel i of the lane's run: stored x + np - 1 - i when mirrored
+            const int xs = mx ? max(x + np - 1 - i, x) : min(x + i, width - 1);
+            fancy_pixel<kAllModels>(p, s_t, bx, by, xs + px, y + py, &out[3 * i]);
+        }
+        store_rgb4(dst + static_cast<size_t>(my ? height - 1 - y : y) * dst_pitch + static_cast<size_t>(mx ? width - x - np : x) * 3, out, np);
+    }
+}
+
+template <bool kWindowed, bool kAllModels>
+__global__ __launch_bounds__(256) void fancy_mirrored_kernel(FancySource p, uint8_t* __restrict__ dst, int dst_pitch, int width, int height, int flips)
+{
+    fancy_mirrored_tile<kWindowed, kAllModels>(p, dst, dst_pitch, width, height, flips);
+}
+
+/// Orientations 5..8: stored rows become displayed columns. The row kernel's 256 x 8 tile written transposed would store
+/// 24 bytes per displayed row, so a workgroup takes kOrientTile x kOrientTile stored pixels: eight strips of 64 x 8 are
+/// staged and converted as ever, and their RGB (one dword per pixel) is kept in LDS, s_rgb[stored y][stored x], rows
+/// kOrientTile + 1 dwords apart -- the write-out reads it down a column, 65 dwords from lane to lane, which is one bank on
+/// (64 banks of 4 bytes), so neither side conflicts. Then one wave per displayed row: the row's 3 x 64 = 192 contiguous
+/// bytes as 48 dwords (49 if the row does not start on a dword: the two ends go out as bytes), each put together from
+/// the two pixels it overlaps. LDS per workgroup: 16640 bytes of s_rgb + the staged tiles (7800, or 10400 for all models).
+template <bool kWindowed, bool kAllModels>
+__device__ __forceinline__ void fancy_transposed_tile(const FancySource& p, uint8_t* dst, int dst_pitch, int width, int height, int flips)
+{
+    __shared__ typename Fancy<kAllModels>::Tiles s_t;
+    __shared__ uint32_t s_rgb[kOrientTile][kOrientTile + 1];
+    const int t  = threadIdx.x;
+    const int x0 = blockIdx.x * kOrientTile, y0 = blockIdx.y * kOrientTile;
+    const int nw = min(kOrientTile, width - x0), nh = min(kOrientTile, height - y0);
+    const int px = kWindowed ? p.x : 0, py = kWindowed ? p.y : 0;
+    for (int s0 = 0; s0 < nh; s0 += kFancyTileH) {
+        const int ch = min(kFancyTileH, nh - s0);
+        int bx[Fancy<kAllModels>::kComps], by[Fancy<kAllModels>::kComps];
+        fancy_stage<kWindowed, kAllModels>(p, s_t, x0 + px, y0 + s0 + py, nw, ch, bx, by);
+        __syncthreads();
+        for (int q = t; q < kFancyTileH * kOrientTile; q += 256) {
+            const int qy = q / kOrientTile, qx = q % kOrientTile;
+            if (qy >= ch || qx >= nw) continue;
+            uint32_t rgb[3];
+            fancy_pixel<kAllModels>(p, s_t, bx, by, x0 + qx + px, y0 + s0 + qy + py, rgb);
+            s_rgb[s0 + qy][qx] = rgb[0] | rgb[1] << 8 | rgb[2] << 16;
+        }
+        __syncthreads(); // the next strip's staging overwrites the tiles; the last one: s_rgb is complete
+    }
+    const bool mx = flips & 1, my = flips & 2;
+    const int ox0 = mx ? height - y0 - nh : y0; // the displayed columns of the tile's stored rows, nh of them
+    const int nbytes = 3 * nh, lane = t & 63;
+    for (int row = t >> 6; row < nw; row += 4) { // displayed row: stored column x0 + row
+        const int oy = my ? width - 1 - (x0 + row) : x0 + row;
+        uint8_t* a   = dst + static_cast<size_t>(oy) * dst_pitch + static_cast<size_t>(ox0) * 3;
+        const int b0 = 4 * lane - static_cast<int>(reinterpret_cast<uintptr_t>(a) & 3); // the lane's dword: bytes b0 .. b0 + 3 of the run
+        if (b0 + 4 <= 0 || b0 >= nbytes) continue;
+        if (b0 >= 0 && b0 + 4 <= nbytes) { // pixels b0 / 3 and the next hold its four bytes
+            const int p0 = b0 / 3, r = b0 - 3 * p0;
+            const uint32_t v0 = s_rgb[mx ? nh - 1 - p0 : p0][row], v1 = s_rgb[mx ? nh - 2 - p0 : p0 + 1][row];
+            *reinterpret_cast<uint32_t*>(a + b0) = static_cast<uint32_t>((v0 | static_cast<uint64_t>(v1) << 24) >> (8 * r));
+        } else {
+            for (int b = max(b0, 0); b < min(b0 + 4, nbytes); ++b) {
+                const int pi = b / 3;
+                a[b] = static_cast<uint8_t>(s_rgb[mx ? nh - 1 - pi : pi][row] >> (8 * (b - 3 * pi)));
+            }
+        }
+    }
+}
+
+template <bool kWindowed, bool kAllModels>
+__global__ __launch_bounds__(256) void fancy_transposed_kernel(FancySource p, uint8_t* __restrict__ dst, int dst_pitch, int width, int height, int flips)
+{
+    fancy_transposed_tile<kWindowed, kAllModels>(p, dst, dst_pitch, width, height, flips);
+}
+
 /// Taps of a horizontal-pass workgroup's columns: int32 weights[columns][taps], from LDS when they fit
 /// (kResizeLdsTaps per column) or else straight from the table; RGB of a chunk: one dword (R | G << 8 | B << 16) per pixel.
 /// A product of a weight (|w| < 2^23: normalised weights stay below 1.2) and a sample fits v_mul_i32_i24.
@@ -279,7 +382,9 @@ __device__ __forceinline__ void resize_taps_h(const W* w, const uint32_t* px, in
 /// `kAllModels` (resize_h_color_kernel): a call with an item that is not grey or YCbCr; its items of those two models are
 /// converted as ever. resize_h_kernel is the instantiation for calls of grey and YCbCr items alone. (The pointers are
 /// __restrict__ on the kernels only: the qualifier repeated here cost resize_h_kernel ten VGPRs once inlined.)
-template <bool kAllModels>
+/// `kOriented` (resize_h_oriented_kernel): an item may carry kResizeMirrorStore, and its result then goes to the mirrored
+/// column of `mid`.
+template <bool kAllModels, bool kOriented = false>
 __device__ __forceinline__ void resize_h_tile(
     const ResizeJob* jobs, const int* first_tile, int n, int out_w, typename Fancy<kAllModels>::Tiles& s_t,
     uint32_t (&s_rgb)[kResizeHTileH][kFancyTileW], int (&s_w)[kResizeHTileW * kResizeLdsTaps])
@@ -336,7 +441,9 @@ __device__ __forceinline__ void resize_h_tile(
         __syncthreads();
     }
     if (mine) {
-        uint8_t* o = J.mid + static_cast<size_t>(r0 - J.row0 + r) * J.mid_pitch + 3 * ox;
+        int sx = ox;
+        if constexpr (kOriented) sx = (J.pad_ & kResizeMirrorStore) ? out_w - 1 - ox : ox;
+        uint8_t* o = J.mid + static_cast<size_t>(r0 - J.row0 + r) * J.mid_pitch + 3 * sx;
 #pragma unroll
         for (int c = 0; c < 3; ++c) o[c] = static_cast<uint8_t>(clamp255((acc[c] + (1 << 21)) >> 22));
     }
@@ -356,6 +463,118 @@ __global__ __launch_bounds__(256) void resize_h_color_kernel(const ResizeJob* __
     __shared__ uint32_t s_rgb[kResizeHTileH][kFancyTileW];
     __shared__ int s_w[kResizeHTileW * kResizeLdsTaps];
     resize_h_tile<true>(jobs, first_tile, n, out_w, s_t, s_rgb, s_w);
+}
+
+template <bool kAllModels>
+__global__ __launch_bounds__(256) void resize_h_oriented_kernel(const ResizeJob* __restrict__ jobs, const int* __restrict__ first_tile, int n, int out_w)
+{
+    __shared__ typename Fancy<kAllModels>::Tiles s_t;
+    __shared__ uint32_t s_rgb[kResizeHTileH][kFancyTileW];
+    __shared__ int s_w[kResizeHTileW * kResizeLdsTaps];
+    resize_h_tile<kAllModels, true>(jobs, first_tile, n, out_w, s_t, s_rgb, s_w);
+}
+
+/// The 24-bit multiply (v_mad_i32_i24 with its add) for the kernels added since resize_h_kernel. Not HIP's __mul24: that
+/// is one `static` wrapper for the whole file, and a further call site of it changes how it is inlined into
+/// resize_h_kernel's tap loop, whose code is to stay as it is (the compile check).
+/// Plain C++: the product of two values sign-extended from 24 bits is what the compiler selects that instruction for.
+__device__ __forceinline__ int mul24(int a, int b) { return ((a << 8) >> 8) * ((b << 8) >> 8); }
+
+/// Batched resize, the first pass of an item with orientation 5..8: Pillow's first, rounded pass runs along displayed x,
+/// which is stored y, so the taps (tab_x, permuted by the host for stored rows) run down stored columns, and a row of
+/// `mid` -- a displayed row -- is a stored column of the rectangle (J.row0 / J.rows count those). A workgroup owns up to
+/// kResizeTTileW stored columns, one per lane, and kResizeTTileK output columns: the stored rows their taps read are staged
+/// in strips of kFancyTileH (fancy_stage as ever), each lane converts its column's pixel of a strip row (fancy_pixel) and
+/// adds it to the output columns whose taps hold that row -- the tap ranges and weights are the same for every lane, so
+/// the tests are uniform and the weights broadcast. No RGB goes through LDS or global memory. A lane then writes its 3 x
+/// kResizeTTileK bytes of `mid`. What bounds it: the staging of a strip (one barrier pair per eight stored rows, for 256
+/// columns) and the K uniform tests per pixel; see DESIGN.md, f-9.
+template <bool kAllModels>
+__device__ __forceinline__ void resize_t_tile(
+    const ResizeJob* jobs, const int* first_tile, int n, int out_w, typename Fancy<kAllModels>::Tiles& s_t,
+    int (&s_w)[kResizeTTileK * kResizeLdsTaps])
+{
+    constexpr int K = kResizeTTileK;
+    const int b = blockIdx.x;
+    int lo = 0, hi = n - 1; // the last item whose first tile is <= b (items of the other kind have no tiles)
+    while (lo < hi) {
+        const int m = (lo + hi + 1) >> 1;
+        if (first_tile[m] <= b) lo = m;
+        else hi = m - 1;
+    }
+    const ResizeJob& J = jobs[lo];
+    const int k_tiles = (out_w + K - 1) / K;
+    const int tile = b - first_tile[lo], tc = tile / k_tiles, tk = tile - tc * k_tiles;
+    const int c0 = J.row0 + tc * kResizeTTileW; // the tile's first stored column of the rectangle
+    const int cw = min(kResizeTTileW, J.row0 + J.rows - c0);
+    const int ox0 = tk * K, nk = min(K, out_w - ox0);
+    const int* __restrict__ tab = J.tab_x;
+    const FancySource& src = J.src;
+    const int t = threadIdx.x, taps = J.taps_x;
+    const bool lds_w = taps <= kResizeLdsTaps;
+    const int* __restrict__ wts = tab + 2 * out_w + static_cast<size_t>(ox0) * taps;
+    if (lds_w) // made visible by the strip loop's first barrier
+        for (int q = t; q < nk * taps; q += 256) s_w[q] = wts[q];
+    int f[K], cnt[K], a = 0x7fffffff, e = 0; // stored rows [a, e): what the K columns' taps read (any order of the columns)
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        f[k] = cnt[k] = 0;
+        if (k < nk) {
+            f[k]   = tab[2 * (ox0 + k)];
+            cnt[k] = tab[2 * (ox0 + k) + 1];
+            a      = min(a, f[k]);
+            e      = max(e, f[k] + cnt[k]);
+        }
+    }
+    int acc[K][3];
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc[k][0] = acc[k][1] = acc[k][2] = 0;
+    for (int r = a; r < e; r += kFancyTileH) {
+        const int ch  = min(kFancyTileH, e - r);
+        const int ix0 = c0 + src.x, iy0 = r + src.y; // the strip's origin in the image
+        int bx[Fancy<kAllModels>::kComps], by[Fancy<kAllModels>::kComps];
+        fancy_stage<true, kAllModels>(src, s_t, ix0, iy0, cw, ch, bx, by);
+        __syncthreads();
+        if (t < cw) {
+            for (int rr = 0; rr < ch; ++rr) {
+                uint32_t rgb[3];
+                fancy_pixel<kAllModels>(src, s_t, bx, by, ix0 + t, iy0 + rr, rgb);
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const int j = r + rr - f[k];
+                    if (j < 0 || j >= cnt[k]) continue;
+                    const int wj = lds_w ? s_w[k * taps + j] : wts[static_cast<size_t>(k) * taps + j];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) acc[k][c] += mul24(wj, static_cast<int>(rgb[c]));
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (t >= cw) return;
+    uint32_t v[3 * K];
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[3 * k + c] = clamp255((acc[k][c] + (1 << 21)) >> 22);
+    uint8_t* o = J.mid + static_cast<size_t>(c0 - J.row0 + t) * J.mid_pitch + 3 * ox0; // 8-byte aligned: 3 K = 24 bytes per tile
+    if (nk == K) {
+        uint32_t* o4 = reinterpret_cast<uint32_t*>(o);
+#pragma unroll
+        for (int d = 0; d < 3 * K / 4; ++d) o4[d] = v[4 * d] | v[4 * d + 1] << 8 | v[4 * d + 2] << 16 | v[4 * d + 3] << 24;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3 * K; ++k)
+            if (k < 3 * nk) o[k] = static_cast<uint8_t>(v[k]);
+    }
+}
+
+template <bool kAllModels>
+__global__ __launch_bounds__(256) void resize_t_kernel(const ResizeJob* __restrict__ jobs, const int* __restrict__ first_tile, int n, int out_w)
+{
+    __shared__ typename Fancy<kAllModels>::Tiles s_t;
+    __shared__ int s_w[kResizeTTileK * kResizeLdsTaps];
+    resize_t_tile<kAllModels>(jobs, first_tile, n, out_w, s_t, s_w);
 }
 
 /// Batched resize, pass 2: the vertical taps over the items' `mid` rows, one item per blockIdx.y. Each lane makes 4
@@ -474,6 +693,57 @@ hipError_t launch_resize(
     if (n <= 0 || h_tiles <= 0 || out_w <= 0 || out_h <= 0) return hipSuccess;
     if (all_models) resize_h_color_kernel<<<h_tiles, 256, 0, stream>>>(d_jobs, d_first_tile, n, out_w);
     else resize_h_kernel<<<h_tiles, 256, 0, stream>>>(d_jobs, d_first_tile, n, out_w);
+    const int v_tiles = ((out_w + kResizeVTileW - 1) / kResizeVTileW) * ((out_h + kResizeVTileH - 1) / kResizeVTileH);
+    resize_v_kernel<<<dim3(v_tiles, n), 256, 0, stream>>>(d_jobs, out_w, out_h, layout, dst);
+    return hipGetLastError();
+}
+
+hipError_t launch_rgbi_oriented(const FancySource& src, int orientation, uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream)
+{
+    if (width <= 0 || height <= 0) return hipSuccess;
+    bool windowed = src.x != 0 || src.y != 0;
+    for (const FancyComp& c : src.comp) windowed = windowed || c.ox != 0 || c.oy != 0;
+    const bool all = fancy_all_models(src);
+    const int flips = (orient_mirrors_x(orientation) ? 1 : 0) | (orient_mirrors_y(orientation) ? 2 : 0);
+    if (orient_transposes(orientation)) {
+        const dim3 grid((width + kOrientTile - 1) / kOrientTile, (height + kOrientTile - 1) / kOrientTile);
+        if (all) {
+            if (windowed) fancy_transposed_kernel<true, true><<<grid, 256, 0, stream>>>(src, dst, dst_pitch, width, height, flips);
+            else fancy_transposed_kernel<false, true><<<grid, 256, 0, stream>>>(src, dst, dst_pitch, width, height, flips);
+        } else {
+            if (windowed) fancy_transposed_kernel<true, false><<<grid, 256, 0, stream>>>(src, dst, dst_pitch, width, height, flips);
+            else fancy_transposed_kernel<false, false><<<grid, 256, 0, stream>>>(src, dst, dst_pitch, width, height, flips);
+        }
+    } else {
+        const dim3 grid((width + kFancyTileW - 1) / kFancyTileW, (height + kFancyTileH - 1) / kFancyTileH);
+        if (all) {
+            if (windowed) fancy_mirrored_kernel<true, true><<<grid, 256, 0, stream>>>(src, dst, dst_pitch, width, height, flips);
+            else fancy_mirrored_kernel<false, true><<<grid, 256, 0, stream>>>(src, dst, dst_pitch, width, height, flips);
+        } else {
+            if (windowed) fancy_mirrored_kernel<true, false><<<grid, 256, 0, stream>>>(src, dst, dst_pitch, width, height, flips);
+            else fancy_mirrored_kernel<false, false><<<grid, 256, 0, stream>>>(src, dst, dst_pitch, width, height, flips);
+        }
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_resize_oriented(
+    const ResizeJob* d_jobs, const int* d_first_tile, const int* d_first_tile_t, int n, int h_tiles, int t_tiles, bool mirror_store,
+    int out_w, int out_h, int layout, bool all_models, uint8_t* dst, hipStream_t stream)
+{
+    if (t_tiles <= 0 && !mirror_store) return launch_resize(d_jobs, d_first_tile, n, h_tiles, out_w, out_h, layout, all_models, dst, stream);
+    if (n <= 0 || out_w <= 0 || out_h <= 0) return hipSuccess;
+    if (h_tiles > 0) {
+        if (!mirror_store) {
+            if (all_models) resize_h_color_kernel<<<h_tiles, 256, 0, stream>>>(d_jobs, d_first_tile, n, out_w);
+            else resize_h_kernel<<<h_tiles, 256, 0, stream>>>(d_jobs, d_first_tile, n, out_w);
+        } else if (all_models) resize_h_oriented_kernel<true><<<h_tiles, 256, 0, stream>>>(d_jobs, d_first_tile, n, out_w);
+        else resize_h_oriented_kernel<false><<<h_tiles, 256, 0, stream>>>(d_jobs, d_first_tile, n, out_w);
+    }
+    if (t_tiles > 0) {
+        if (all_models) resize_t_kernel<true><<<t_tiles, 256, 0, stream>>>(d_jobs, d_first_tile_t, n, out_w);
+        else resize_t_kernel<false><<<t_tiles, 256, 0, stream>>>(d_jobs, d_first_tile_t, n, out_w);
+    }
     const int v_tiles = ((out_w + kResizeVTileW - 1) / kResizeVTileW) * ((out_h + kResizeVTileH - 1) / kResizeVTileH);
     resize_v_kernel<<<dim3(v_tiles, n), 256, 0, stream>>>(d_jobs, out_w, out_h, layout, dst);
     return hipGetLastError();

@@ -69,6 +69,21 @@ inline bool fancy_all_models(const FancySource& s) { return s.color != kFancyGra
 /// Convert.c) of the width x height pixels at the source's rectangle origin.
 hipError_t launch_rgbi_fancy(const FancySource& src, uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream);
 
+/// EXIF orientation of an output (jpeggpu_ext.h has the table): what the eight values do to the stored image. Values 5..8
+/// turn rows into columns; `x` / `y`: the DISPLAYED x / y axis runs against the stored axis it lies along.
+inline bool orient_valid(int o) { return o >= 1 && o <= 8; }
+inline bool orient_transposes(int o) { return o >= 5; }
+inline bool orient_mirrors_x(int o) { return o == 2 || o == 3 || o == 6 || o == 7; }
+inline bool orient_mirrors_y(int o) { return o == 3 || o == 4 || o == 7 || o == 8; }
+
+/// launch_rgbi_fancy with the pixels written where `orientation` (2..8) displays them: `width` x `height` is the stored
+/// rectangle, `dst` holds the displayed one. 2..4 keep the row kernel's tile and mirror each lane's store; 5..8 take the
+/// transposing kernel: kOrientTile x kOrientTile stored pixels per workgroup, whose RGB goes through LDS so that a wave
+/// stores 3 x kOrientTile contiguous bytes of one displayed row.
+constexpr int kOrientTile = 64;
+hipError_t launch_rgbi_oriented(
+    const FancySource& src, int orientation, uint8_t* dst, int dst_pitch, int width, int height, hipStream_t stream);
+
 /// One item of a batched resize (launch_resize), in device memory: a source rectangle resampled to out_w x out_h RGB by
 /// two separable passes whose weight tables the host computed (jpeggpu_ext_resize_weights). A table of n output
 /// coordinates with `taps` taps each is int32 {first, count}[n] followed by int32 weights[n][taps] (22 fraction bits).
@@ -80,8 +95,12 @@ struct ResizeJob {
     const int* tab_y;          // out_h rows
     uint8_t* mid;              // rows x out_w RGB of the horizontal pass, rows mid_pitch bytes apart
     int mid_pitch;             // a multiple of 16
-    int pad_;
+    int pad_;                  // oriented calls: kResizeMirrorStore
 };
+/// ResizeJob::pad_ of an item of launch_resize_oriented whose displayed x runs against stored x (orientations 2 and 3):
+/// tab_x is in stored order -- column out_w - 1 - ox of the displayed table, its taps reversed -- and the horizontal pass
+/// writes table column ox' to mid column out_w - 1 - ox'.
+constexpr int kResizeMirrorStore = 1;
 constexpr int kResizeHTileW = 32, kResizeHTileH = 8; // horizontal pass: output columns x rows per workgroup
 constexpr int kResizeVTileW = 256, kResizeVTileH = 4; // vertical pass: output pixels x rows per workgroup
 /// Horizontal-pass workgroups of one item.
@@ -96,6 +115,23 @@ inline int resize_h_tiles(int rows, int out_w)
 hipError_t launch_resize(
     const ResizeJob* d_jobs, const int* d_first_tile, int n, int h_tiles, int out_w, int out_h, int layout, bool all_models,
     uint8_t* dst, hipStream_t stream);
+
+
+/// The transposing first pass of items with orientations 5..8: displayed x lies along stored y, so the rounded pass runs
+/// down stored columns. A workgroup owns kResizeTTileW stored columns (rows of `mid`) and kResizeTTileK output columns.
+constexpr int kResizeTTileW = 256, kResizeTTileK = 8;
+inline int resize_t_tiles(int rows, int out_w)
+{
+    return ((rows + kResizeTTileW - 1) / kResizeTTileW) * ((out_w + kResizeTTileK - 1) / kResizeTTileK);
+}
+/// launch_resize for a call with orientations: items of 1..4 take the horizontal pass (`d_first_tile`, `h_tiles`; one of
+/// them with kResizeMirrorStore: `mirror_store`, the instantiation that knows the flag), items of 5..8 the transposing
+/// pass (`d_first_tile_t`, `t_tiles`; for them ResizeJob::row0 / rows count stored columns and tab_x runs over stored
+/// rows); an item has no tiles in the list of the other kind. The vertical pass is launch_resize's. Without mirrored and
+/// transposed items this launches exactly what launch_resize does.
+hipError_t launch_resize_oriented(
+    const ResizeJob* d_jobs, const int* d_first_tile, const int* d_first_tile_t, int n, int h_tiles, int t_tiles, bool mirror_store,
+    int out_w, int out_h, int layout, bool all_models, uint8_t* dst, hipStream_t stream);
 
 } // namespace jg
 

@@ -16,7 +16,7 @@ namespace jg {
 
 namespace {
 constexpr uint8_t M_SOF0 = 0xC0, M_SOF1 = 0xC1, M_SOF2 = 0xC2, M_DHT = 0xC4, M_RST0 = 0xD0, M_RST7 = 0xD7,
-                  M_SOI = 0xD8, M_EOI = 0xD9, M_SOS = 0xDA, M_DQT = 0xDB, M_DRI = 0xDD, M_APP0 = 0xE0, M_APP14 = 0xEE;
+                  M_SOI = 0xD8, M_EOI = 0xD9, M_SOS = 0xDA, M_DQT = 0xDB, M_DRI = 0xDD, M_APP0 = 0xE0, M_APP1 = 0xE1, M_APP14 = 0xEE;
 constexpr int kNatural[64] = JG_ORDER_NATURAL;
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
@@ -405,6 +405,72 @@ void Reader::note_app_segment(uint8_t marker)
         s.saw_adobe       = true;
         s.adobe_transform = data[11];
     }
+}
+
+/// An APP1 segment in front of the first scan that begins "Exif\0\0" is kept for exif_orientation: Pillow reads the data of
+/// the first such segment with the data of every later one (behind its six bytes) appended. One segment -- every file a
+/// camera wrote -- is not copied. cur_ stays at the length field, as in note_app_segment.
+void Reader::note_exif_segment()
+{
+    if (s.num_scans > 0 || !s.prog_scans.empty() || remaining() < 2) return;
+    const size_t length = static_cast<size_t>(cur_[0]) << 8 | cur_[1];
+    if (length < 8 || remaining() < length || std::memcmp(cur_ + 2, "Exif\0\0", 6) != 0) return;
+    if (!exif_) {
+        exif_     = cur_ + 2;
+        exif_len_ = length - 2;
+        return;
+    }
+    if (exif_cat_.empty()) exif_cat_.assign(exif_, exif_ + exif_len_);
+    exif_cat_.insert(exif_cat_.end(), cur_ + 8, cur_ + length);
+    exif_     = exif_cat_.data();
+    exif_len_ = exif_cat_.size();
+}
+
+/// The EXIF Orientation of the Exif data of `n` bytes at `d`, 1..8, as Pillow 12 reads it (Image.Exif.load, TiffImagePlugin's
+/// ImageFileDirectory_v2.load, ImageOps.exif_transpose); 1 for everything that says nothing. Every read is checked against n.
+///   - leading "Exif\0\0" are dropped; then a TIFF header of 8 bytes: "II" + 2A 00 or 00 2A, or "MM" + 00 2A, 2A 00 or 00 2B
+///     (Pillow's list of prefixes; "II" 2B 00 it takes for BigTIFF and fails), and the offset of IFD0 in that byte order;
+///   - IFD0: a 16-bit count and 12-byte entries, read one by one for as long as whole entries lie in the data;
+///   - an entry of tag 0x0112 and a TIFF type 1..13 or 16 with count x size != 0 whose value lies in the data (inline if it
+///     fits 4 bytes, else at its offset) sets the value, a later one replaces an earlier; the first of `count` values
+///     counts. Of types SHORT, LONG, SSHORT and SLONG that is an integer, and 1..8 are the orientation; of any other type
+///     it is no integer Pillow compares with (BYTE, ASCII, UNDEFINED), or one this parser does not convert (RATIONAL, FLOAT,
+///     DOUBLE, IFD, LONG8: Pillow would take a 6.0 for 6) -- orientation 1.
+int exif_orientation(const uint8_t* d, size_t n)
+{
+    while (n >= 6 && std::memcmp(d, "Exif\0\0", 6) == 0) d += 6, n -= 6;
+    if (n < 8) return 1;
+    bool le;
+    if (d[0] == 'I' && d[1] == 'I' && ((d[2] == 0x2A && d[3] == 0) || (d[2] == 0 && d[3] == 0x2A))) le = true;
+    else if (d[0] == 'M' && d[1] == 'M' && ((d[2] == 0 && (d[3] == 0x2A || d[3] == 0x2B)) || (d[2] == 0x2A && d[3] == 0))) le = false;
+    else return 1;
+    const auto rd16 = [&](size_t o) -> uint32_t { return le ? d[o] | d[o + 1] << 8 : d[o] << 8 | d[o + 1]; };
+    const auto rd32 = [&](size_t o) -> uint32_t { return le ? rd16(o) | rd16(o + 2) << 16 : rd16(o) << 16 | rd16(o + 2); };
+    const size_t ifd = rd32(4);
+    if (ifd > n || n - ifd < 2) return 1;
+    const size_t entries = rd16(ifd);
+    static const uint8_t kUnit[17] = {0, 1, 1, 2, 4, 8, 1, 1, 2, 4, 8, 4, 8, 4, 0, 0, 8}; // TIFF types 1..13 and 16
+    int64_t value = 1;
+    for (size_t i = 0, e = ifd + 2; i < entries && n - e >= 12; ++i, e += 12) {
+        if (rd16(e) != 0x0112) continue;
+        const uint32_t type = rd16(e + 2);
+        if (type > 16 || kUnit[type] == 0) continue;
+        const uint64_t size = static_cast<uint64_t>(rd32(e + 4)) * kUnit[type];
+        if (size == 0) continue;
+        size_t at = e + 8;
+        if (size > 4) {
+            at = rd32(e + 8);
+            if (at > n || n - at < size) continue;
+        }
+        switch (type) {
+        case 3: value = rd16(at); break;
+        case 4: value = rd32(at); break;
+        case 8: value = static_cast<int16_t>(rd16(at)); break;
+        case 9: value = static_cast<int32_t>(rd32(at)); break;
+        default: value = 1;
+        }
+    }
+    return value >= 1 && value <= 8 ? static_cast<int>(value) : 1;
 }
 
 jpeggpu_status Reader::read_sos(const Logger& log)
@@ -1026,6 +1092,9 @@ jpeggpu_status Reader::parse(const uint8_t* data, size_t size, int subseq_bytes,
     subseq_request_ = subseq_bytes;
     subseq_bytes_   = subseq_bytes > 0 ? subseq_bytes : 64; // an automatic choice is made at the first scan header
     found_sof_    = false;
+    exif_         = nullptr;
+    exif_len_     = 0;
+    exif_cat_.clear();
     std::memset(qt_defined_, 0, sizeof(qt_defined_));
     std::memset(dc_defined_, 0, sizeof(dc_defined_));
     std::memset(ac_defined_, 0, sizeof(ac_defined_));
@@ -1089,6 +1158,7 @@ jpeggpu_status Reader::parse(const uint8_t* data, size_t size, int subseq_bytes,
             return JPEGGPU_INVALID_JPEG; // stand-alone markers have no place here
         } else {
             if (marker == M_APP0 || marker == M_APP14) note_app_segment(marker);
+            if (marker == M_APP1) note_exif_segment();
             st = skip_segment(log);
         }
         if (st != JPEGGPU_SUCCESS) return st;
@@ -1109,6 +1179,7 @@ jpeggpu_status Reader::parse(const uint8_t* data, size_t size, int subseq_bytes,
         s.color_space = s.saw_jfif ? kColorYCbCr : s.saw_adobe ? (s.adobe_transform == 0 ? kColorRGB : kColorYCbCr) : ids_rgb ? kColorRGB : kColorYCbCr;
     else if (s.num_comp == 4) s.color_space = s.saw_adobe && s.adobe_transform != 0 ? kColorYCCK : kColorCMYK;
     else s.color_space = kColorUnknown;
+    s.orientation = exif_ ? exif_orientation(exif_, exif_len_) : 1;
     log.log("colour model %d (jfif %d, adobe %d, transform %d)\n", s.color_space, s.saw_jfif, s.saw_adobe, s.adobe_transform);
     if (shard_world > 1) return apply_segment_shard(shard_rank, shard_world, log);
     return JPEGGPU_SUCCESS;

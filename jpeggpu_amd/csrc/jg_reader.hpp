@@ -128,6 +128,7 @@ struct Stream {
     bool saw_jfif = false, saw_adobe = false;
     uint8_t adobe_transform = 0;
     int color_space = kColorUnknown; // ColorSpace
+    int orientation = 1; // the EXIF Orientation of the Exif APP1 data in front of the first scan (exif_orientation): 1..8
     // A progressive frame (SOF2): prog_scans holds the file's scans, and scans[0 .. num_comp) describe the frame as it is
     // handed to the IDCT stage -- one non-interleaved baseline scan per component (B-2) without entropy-coded data.
     bool progressive = false;
@@ -219,6 +220,10 @@ struct Reader {
     int8_t prog_al_[kMaxComp][64]{};
     int8_t prog_level_[kMaxComp][64]{};
     Scan prog_walk_; // scratch of the walk over a progressive scan's bytes
+    // the Exif data in front of the first scan: the first Exif APP1 segment's, in the file; of several, joined in exif_cat_
+    const uint8_t* exif_ = nullptr;
+    size_t exif_len_     = 0;
+    std::vector<uint8_t> exif_cat_;
 
     size_t remaining() const { return static_cast<size_t>(end_ - cur_); }
     uint8_t u8() { return *cur_++; }
@@ -237,8 +242,12 @@ struct Reader {
     jpeggpu_status walk_scan(Scan& scan, const Logger& log);
     jpeggpu_status skip_segment(const Logger& log);
     void note_app_segment(uint8_t marker);
+    void note_exif_segment();
     jpeggpu_status apply_segment_shard(int rank, int world, const Logger& log);
 };
+
+/// The EXIF Orientation, 1..8, that Pillow reads from `n` bytes of Exif data (jg_reader.cpp); 1 for data that says nothing.
+int exif_orientation(const uint8_t* d, size_t n);
 
 /// Build the device form of one Huffman table from a DHT payload
 /// (reference compute_huffman_table, src/reader.cpp:186-224).
