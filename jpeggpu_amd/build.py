@@ -7,7 +7,7 @@ ROOT = os.path.dirname(_HERE)
 CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libjpeggpu.so")
-SOURCES = ["jg_kernels.hip", "jg_output.hip", "jg_front.hip", "jg_prog.hip", "jg_decoder.cpp", "jg_output.cpp", "jg_reader.cpp"]
+SOURCES = ["jg_kernels.hip", "jg_idct.hip", "jg_output.hip", "jg_front.hip", "jg_prog.hip", "jg_decoder.cpp", "jg_output.cpp", "jg_reader.cpp"]
 
 
 def _mode_path(lib_path):
@@ -23,11 +23,7 @@ def _wanted_mode():
 def _stale() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
-    t = os.path.getmtime(LIB_PATH)
-    # every source and header under csrc/ (a header missing from a hand-kept list once left a stale library)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp", ".hip", ".cpp"))]
-    deps += [os.path.join(ROOT, "include", "jpeggpu", h) for h in ("jpeggpu.h", "jpeggpu_ext.h")]
-    if any(os.path.getmtime(d) > t for d in deps):
+    if _newest_source() > os.path.getmtime(LIB_PATH):
         return True
     try:  # built under other settings of the environment: a fast-refill library must not outlive a request for the safe one
         with open(_mode_path(LIB_PATH)) as f:
@@ -54,7 +50,8 @@ def _base_cmd(extra_flags):
 
 def check_refill(extra_flags=(), verbose=False):
     """The write pass refills its bit window from inline assembly and waits for all but the most recent load
-    (jg_kernels.hip, RowWindow: `s_waitcnt vmcnt(1)`). That is only right if the compiler never touches the register the
+    (jg_kernels.hip, RowWindow: `s_waitcnt vmcnt(1)`; that file holds the whole entropy pass and is the only one read here:
+    the IDCT stage is jg_idct.hip's). That is only right if the compiler never touches the register the
     loads target while one is in flight -- which it does not know. So the generated code is checked, for every
     instantiation of huff_write and huff_tail_write: no scratch memory, no spilled registers, and between the loop's first refill block and
     the `s_waitcnt vmcnt(0)` of RowWindow::done() no instruction outside the hand-written assembly blocks names that
@@ -62,8 +59,40 @@ def check_refill(extra_flags=(), verbose=False):
     return check_refill_text(device_assembly(extra_flags, verbose))
 
 
+def _newest_source():
+    """The newest modification time of what a compile reads: every source and header under csrc/ (a header missing from a
+    hand-kept list once left a stale library) and the public headers."""
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp", ".hip", ".cpp"))]
+    deps += [os.path.join(ROOT, "include", "jpeggpu", h) for h in ("jpeggpu.h", "jpeggpu_ext.h")]
+    return max(os.path.getmtime(d) for d in deps)
+
+
+_assembly = {}  # (source, flags, _newest_source()) -> lines: a process that asks again (the tests do) does not compile again
+
+
 def device_assembly(extra_flags=(), verbose=False, source="jg_kernels.hip"):
-    """The gfx950 assembly of one .hip file under csrc/, as lines."""
+    """The gfx950 assembly of one .hip file under csrc/, as lines (not to be modified: kept per process while no source
+    changes). The default is the entropy pass's file; the IDCT kernels are in "jg_idct.hip"."""
+    key = (source, tuple(_base_cmd(extra_flags)), _newest_source())
+    if key not in _assembly:
+        _assembly[key] = _assemble(extra_flags, verbose, source)
+    return _assembly[key]
+
+
+def kernel_metadata(text):
+    """{kernel symbol: {field: int}} from the `.set <symbol>.num_vgpr / .private_seg_size / .uses_dynamic_stack` lines of
+    device_assembly's text: what the assembly tests bound."""
+    import re
+
+    out = {}
+    for line in text:
+        m = re.match(r"\s+\.set (_Z\S+)\.(num_vgpr|private_seg_size|uses_dynamic_stack), (\d+)", line)
+        if m:
+            out.setdefault(m.group(1), {})[m.group(2)] = int(m.group(3))
+    return out
+
+
+def _assemble(extra_flags, verbose, source):
     import tempfile
 
     with tempfile.TemporaryDirectory() as tmp:
@@ -219,25 +248,53 @@ def check_refill_text(text):
     return problems
 
 
+def _jobs():
+    """Compiles at a time: one per source, 16 at the most, MAX_JOBS if that is set (never the machine's CPU count: a shared
+    machine shows more CPUs than a process may use)."""
+    n = min(len(SOURCES), 16)
+    try:
+        n = min(n, max(1, int(os.environ["MAX_JOBS"])))
+    except (KeyError, ValueError):
+        pass
+    return n
+
+
 def _compile(lib_path, verbose, extra_flags):
+    """Every source to an object of its own, side by side, then one link. The check of the write pass's refill runs beside
+    them; only if it fails are the objects built again, with -DJG_SAFE_REFILL."""
+    import sys
+    import tempfile
+    from concurrent.futures import ThreadPoolExecutor
+
     os.makedirs(LIB_DIR, exist_ok=True)
     extra_flags = list(extra_flags)
     if os.environ.get("JPEGGPU_SAFE_REFILL") == "1" and "-DJG_SAFE_REFILL" not in extra_flags:
         extra_flags.append("-DJG_SAFE_REFILL")  # the selectable safe build: the refill waits for every load (vmcnt(0))
-    if "-DJG_SAFE_REFILL" not in extra_flags and os.environ.get("JPEGGPU_SKIP_BUILD_CHECK") != "1":
-        problems = check_refill(extra_flags, verbose)
-        if problems:
-            import sys
+    checked = "-DJG_SAFE_REFILL" not in extra_flags and os.environ.get("JPEGGPU_SKIP_BUILD_CHECK") != "1"
 
+    def run(cmd):
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+
+    with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(_jobs()) as pool:
+
+        def objects(flags):
+            # jg_output.hip and jg_output.cpp are two objects: the name keeps the extension
+            objs = [os.path.join(tmp, s.replace(".", "_") + ".o") for s in SOURCES]
+            for job in [pool.submit(run, _base_cmd(flags) + ["-fPIC", "-c", os.path.join(CSRC, s), "-o", o]) for s, o in zip(SOURCES, objs)]:
+                job.result()
+            return objs
+
+        check = pool.submit(check_refill, extra_flags, verbose) if checked else None
+        objs = objects(extra_flags)
+        problems = check.result() if check else []
+        if problems:
             sys.stderr.write("jpeggpu build: the counted-wait refill of the write pass does not pass its check with this compiler:\n  "
                              + "\n  ".join(problems[:8]) + "\n  -> building with -DJG_SAFE_REFILL (s_waitcnt vmcnt(0): a few per cent slower, always right)\n")
             extra_flags.append("-DJG_SAFE_REFILL")
-    cmd = _base_cmd(extra_flags) + ["-fPIC", "-shared"]
-    cmd += [os.path.join(CSRC, s) for s in SOURCES]
-    cmd += ["-o", lib_path]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
+            objs = objects(extra_flags)
+        run(_base_cmd(extra_flags) + ["-fPIC", "-shared"] + objs + ["-o", lib_path])
     with open(_mode_path(lib_path), "w") as f:  # what the library was built as: `_stale` compares it with the environment
         f.write("%s | refill: %s\n" % (_wanted_mode(), "vmcnt(0), safe" if "-DJG_SAFE_REFILL" in extra_flags else "vmcnt(1), checked"))
     return lib_path

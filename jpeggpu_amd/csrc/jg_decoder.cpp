@@ -953,7 +953,7 @@ enum jpeggpu_status jpeggpu_decoder_parse_header(
     d.data      = data;
     d.data_size = size;
     // The IDCT addresses the 16-bit symbol stream with 32-bit BYTE offsets and the data-unit table holds 32-bit
-    // entry indices (jg_kernels.hip, entry_at / prefetch): a scan whose stream would not fit them (from about
+    // entry indices (jg_idct.hip, entry_at / prefetch): a scan whose stream would not fit them (from about
     // 400 MB of entropy-coded data at 64-byte subsequences) is refused here instead of gathering from wrapped offsets.
     for (int i = 0; i < s.num_scans; ++i) {
         const uint64_t entries = jg::sym_buffer_entries(d.sym_regions(i), d.sym_region());

@@ -40,7 +40,7 @@ constexpr int kSeqSubseqBatch  = kSeqLanes - kSeqOverlapBatch;
 constexpr int kTailPartSubseq = 960;
 // A batched call of fewer subsequences than this does not fill the chip (256 CUs x 5 workgroups of 255 lanes hold
 // 326 000): what it waits for is the chain of dependent flow iterations, as a lone decode does, and its sequence kernel
-// keeps every flow in the workgroup (jg_decoder.cpp, decode_batch_impl; jg_kernels.hip, JobArrayLow). Measured per call of
+// keeps every flow in the workgroup (jg_decoder.cpp, decode_batch_impl; jg_jobs.h, JobArrayLow). Measured per call of
 // cfg-2 images at 256 bytes (11 400 subsequences each; us, flows kept / one iteration + marks + tail kernel, round 5):
 // 2: 530 / 567, 4: 561 / 613, 8: 626 / 678, 16: 828 / 878, 24: 1194 / 1113, 32: 1502 / 1408, 64: 2833 / 2418; the
 // reference's photo 16: 1034 / 1121, 32: 1895 / 1668.

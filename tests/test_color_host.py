@@ -132,9 +132,7 @@ def test_arguments(L, base):
 
 def test_color_kernels_use_no_scratch(L):
     """The all-model instantiations (jg_output.hip) under the bounds of the grey / YCbCr ones, which keep their names."""
-    from tests.test_libjpeg_ref import _kernel_metadata
-
-    meta = _kernel_metadata(jbuild.device_assembly(source="jg_output.hip"))
+    meta = jbuild.kernel_metadata(jbuild.device_assembly(source="jg_output.hip"))
     color = {k: v for k, v in meta.items() if "fancy_color_kernel" in k or "resize_h_color_kernel" in k}
     assert sum("fancy_color_kernelILb0E" in k for k in color) == 1 and sum("fancy_color_kernelILb1E" in k for k in color) == 1
     assert sum("resize_h_color_kernel" in k for k in color) == 1 and len(color) == 3, sorted(meta)

@@ -242,12 +242,10 @@ def test_shard_still_cuts_as_before(L, matrix):
 
 
 def test_crop_kernels_use_no_scratch(L):
-    from tests.test_libjpeg_ref import _kernel_metadata
-
-    meta = _kernel_metadata(jbuild.device_assembly())
+    meta = jbuild.kernel_metadata(jbuild.device_assembly(source="jg_idct.hip"))
     crop = {k: v for k, v in meta.items() if "CropJobs" in k}
     # the cropped colour conversion: the windowed instantiation of fancy_rgbi_kernel (jg_output.hip)
-    crop.update({k: v for k, v in _kernel_metadata(jbuild.device_assembly(source="jg_output.hip")).items() if "fancy_rgbi_kernelILb1E" in k})
+    crop.update({k: v for k, v in jbuild.kernel_metadata(jbuild.device_assembly(source="jg_output.hip")).items() if "fancy_rgbi_kernelILb1E" in k})
     assert sum("fancy_rgbi_kernelILb1E" in k for k in crop) == 1
     assert sum("idct_kernel" in k for k in crop) >= 9 and sum("idct_scaled_kernel" in k for k in crop) >= 12, sorted(crop)
     for k, v in crop.items():

@@ -278,9 +278,7 @@ def test_draft_scale_against_pillow(files, decoded):
 
 
 def test_draft_kernels_use_no_scratch(L):
-    from tests.test_libjpeg_ref import _kernel_metadata
-
-    meta = _kernel_metadata(jbuild.device_assembly())
+    meta = jbuild.kernel_metadata(jbuild.device_assembly(source="jg_idct.hip"))
     draft = {k: v for k, v in meta.items() if "DraftJobs" in k}
     assert sum("idct_kernel" in k for k in draft) == 4 and sum("idct_scaled_kernel" in k for k in draft) == 12, sorted(draft)
     for k, v in draft.items():

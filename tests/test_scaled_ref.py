@@ -141,20 +141,8 @@ def test_shard_rows_scale_with_the_plane(L):
                 assert covered[c] == info.sizes_y[c], (world, d, c)
 
 
-def _kernel_metadata(text):
-    """{kernel symbol: {field: int}} from the code object's metadata of the assembly."""
-    import re
-
-    out, cur = {}, None
-    for line in text:
-        m = re.match(r"\s+\.set (_Z\S+)\.(num_vgpr|private_seg_size|uses_dynamic_stack), (\d+)", line)
-        if m:
-            out.setdefault(m.group(1), {})[m.group(2)] = int(m.group(3))
-    return out
-
-
 def test_scaled_kernels_use_no_scratch():
-    meta = _kernel_metadata(jbuild.device_assembly())
+    meta = jbuild.kernel_metadata(jbuild.device_assembly(source="jg_idct.hip"))
     scaled = {k: v for k, v in meta.items() if "idct_scaled_kernel" in k}
     assert len(scaled) >= 12, sorted(meta)  # three scales x four job sources
     for k, v in scaled.items():
