@@ -40,7 +40,7 @@ constexpr int kSeqSubseqBatch  = kSeqLanes - kSeqOverlapBatch;
 constexpr int kTailPartSubseq = 960;
 // A batched call of fewer subsequences than this does not fill the chip (256 CUs x 5 workgroups of 255 lanes hold
 // 326 000): what it waits for is the chain of dependent flow iterations, as a lone decode does, and its sequence kernel
-// keeps every flow in the workgroup (jg_decoder.cpp, decode_batch_impl; jg_jobs.h, JobArrayLow). Measured per call of
+// keeps every flow in the workgroup (jg_batch.cpp, decode_batch_impl; jg_jobs.h, JobArrayLow). Measured per call of
 // cfg-2 images at 256 bytes (11 400 subsequences each; us, flows kept / one iteration + marks + tail kernel, round 5):
 // 2: 530 / 567, 4: 561 / 613, 8: 626 / 678, 16: 828 / 878, 24: 1194 / 1113, 32: 1502 / 1408, 64: 2833 / 2418; the
 // reference's photo 16: 1034 / 1121, 32: 1895 / 1668.
@@ -479,6 +479,35 @@ struct ScanJob {
     int* bnd_cz;                 //   (-1: nothing to say): a boundary where it equals the stored state needs no flow
     IdctWindow win;              // jpeggpu_ext_set_crop: the MCUs the IDCT transforms (win.mcus_x == 0: every one)
     IdctDraft draft;             // jpeggpu_ext_set_scale_mode: the unit classes of a JPEGGPU_EXT_SCALE_LIBJPEG job (draft.on == 0: none)
+};
+
+/// Everything the kernels of the device-side front end (jg_front.hip) need; all pointers are device memory inside d_tmp.
+struct FrontParams {
+    const uint8_t* bytes;      // transferred bytes; offset 0 is the origin of the 4 KiB window grid
+    uint32_t bytes_len;        // valid bytes
+    uint32_t scan_begin;       // offset of the first entropy-coded byte
+    uint32_t num_windows;
+    uint32_t expect_segments;  // ceil(MCUs / restart interval), from the frame and DRI headers
+    uint32_t subseq_bytes;
+    uint32_t max_subseq;       // capacities computed from the header
+    uint32_t max_chunks;
+    uint32_t max_parts;        // entries of tail_parts (parts + 1)
+    uint32_t* win_data;        // [num_windows]      data bytes per window
+    uint32_t* win_nmark;       // [num_windows]      markers per window
+    uint32_t* win_bad;         // [num_windows]      position of the first FF FF 00 of the window, or 0xFFFFFFFF
+    uint32_t* win_prefix;      // [num_windows + 1]
+    uint32_t* mark_off;        // [num_windows + 1]
+    uint32_t* mk_pos;          // [expect_segments + 1]  position of the i-th marker of the scan
+    uint32_t* mk_g;            // [expect_segments + 1]  data bytes of the scan in front of it
+    uint32_t* seg_cnt;         // [expect_segments + 1]
+    uint32_t* seg_nch;         // [expect_segments + 1]
+    Segment* segments;         // [expect_segments]          out
+    DestuffChunk* chunks;      // [max_chunks]               out
+    int* tail_parts;           // [max_parts]                out
+    MhBlock* mh_blocks;        // [max_mh_blocks] out, or null: blocks of the multi-hypothesis chain walk of a scan WITHOUT restart
+    uint32_t max_mh_blocks;    //   markers (one segment: blocks of kMhMaxSegSubseq subsequences, jg_defs.h)
+    ScanJob* job;              // the scan's job in device memory: counts are filled in
+    uint32_t* status;          // [8]: jpeggpu_status, subsequences, segments, chunks, tail parts, -, first FF FF 00, terminator ordinal
 };
 
 } // namespace jg

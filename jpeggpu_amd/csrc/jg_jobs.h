@@ -119,7 +119,7 @@ struct JobArray {
     static constexpr bool kSpeculateStateOnly = true;
     // The sequence kernel of a batch is bound by how many workgroups a CU holds (LDS: the sync table pack): the 4 KB the
     // re-packing needs cost one in five (538 -> 680 us per 64 images), and follow-up iterations inside that kernel cost
-    // more than the tail kernel's trips they replace (jg_decoder.cpp, sync_iters): batches run huff_sync_intra_batch.
+    // more than the tail kernel's trips they replace (jg_batch.cpp, sync_iters): batches run huff_sync_intra_batch.
     static constexpr bool kRepackFlows = false;
     const ScanJob* jobs;
     __device__ __forceinline__ const ScanJob& get() const { return jobs[blockIdx.y]; }

@@ -254,7 +254,7 @@ __global__ __launch_bounds__(256) void destuff_kernel(JS js)
 /// code), and the write pass stops at the segment's data-unit quota -- so what lies behind the end cannot
 /// change p, c, z, n, the DC sums or an emitted coefficient. On a corrupt stream a lane of the write pass may
 /// run up to one data unit (64 symbols of at most 27 bits: 54 words, plus the window's 3) past its
-/// subsequence: the buffer carries more than one spare tile of rows behind the last one (jg_decoder.cpp),
+/// subsequence: the buffer carries more than one spare tile of rows behind the last one (jg_plan.cpp, make_plan),
 /// whatever they hold.
 template <int W, bool kCrossRows = false>
 struct GlobalFetch {

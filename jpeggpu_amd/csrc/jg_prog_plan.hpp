@@ -1,6 +1,6 @@
 // jg_prog_plan.hpp -- host side of a progressive image's part of the table blob (jg_prog_core.h): where the header, the
 // scan descriptors, their tables, the segment lists and the work list lie, and their content. One routine for the
-// decoder (jg_decoder.cpp) and for the host twin of the kernels (tests/emu), which therefore reads what the device reads.
+// decoder's plan (jg_plan.cpp) and for the host twin of the kernels (tests/emu), which therefore reads what the device reads.
 #ifndef JG_PROG_PLAN_HPP_
 #define JG_PROG_PLAN_HPP_
 

@@ -260,6 +260,39 @@ def test_batch_decode_equals_single(torch_cuda):
         dec.cleanup()
 
 
+def test_batch_stage_timing(torch_cuda):
+    """jpeggpu_ext_batch_get_stage_ms: two 16 x 16 4:2:0 images as a batch with the stage timing on give a time for every
+    stage, and a second read without a decode in between has nothing to report."""
+    import jpeggpu_amd
+    from tools import jpegsynth
+
+    torch = torch_cuda
+    keep, entries = [], []
+    for seed in (1, 2):
+        dec = jpeggpu_amd.Decoder()
+        dec.set_batched(True)
+        info = dec.parse_header(jpegsynth.encode(16, 16, ((2, 2), (1, 1), (1, 1)), seed=seed))
+        n, tmp, base, planes = _alloc(torch, dec, info)
+        dec.transfer(base, n, 0)
+        keep.append((dec, tmp, planes))
+        entries.append((dec, [p.data_ptr() for p in planes], [p.stride(0) for p in planes], base, n))
+    batch = jpeggpu_amd.Batch(2)
+    scratch = torch.empty(batch.scratch_size, dtype=torch.uint8, device="cuda:0")
+    batch.set_items(entries)
+    batch.set_profiling(True)
+    batch.decode(scratch.data_ptr(), 0)
+    torch.cuda.synchronize()
+    ms = batch.stage_ms()
+    assert tuple(ms) == jpeggpu_amd.api.STAGES
+    assert all(v >= 0 for v in ms.values()), ms
+    with pytest.raises(jpeggpu_amd.JpegGpuError) as e:
+        batch.stage_ms()
+    assert e.value.status == jpeggpu_amd.Status.INVALID_ARGUMENT
+    batch.destroy()
+    for dec, _, _ in keep:
+        dec.cleanup()
+
+
 @pytest.mark.parametrize("images", [1, 2, 4, 8, 16])
 def test_small_batches_with_the_plans_the_library_picks(torch_cuda, images, monkeypatch):
     """jpeggpu_ext_set_batch_hint: calls of 1 / 2 / 4 / 8 / 16 images, every decoder told the call's size, decoded with
@@ -802,7 +835,7 @@ def test_block_wise_multi_hypothesis_walk_without_restart_markers(torch_cuda, mo
                 for c in range(ref.ncomp):
                     assert np.array_equal(planes[c].cpu().numpy(), ref.planes[c]), (name, sb, c, "device scan")
     # BASELINE configs[4] -- runs of two data units with the same tables, no restart markers -- synchronises faster without
-    # (measured, jg_decoder.cpp make_plan): the library does not apply the speculation there
+    # (measured, jg_plan.cpp make_plan): the library does not apply the speculation there
     planes, _, _tmp, _base, lay = jpeggpu_amd.decode_to_planes(jpegsynth.config(5, small=True), return_tmp=True)
     assert lay.scans[0].hypotheses == 6 and lay.scans[0].hypothesis_blocks == 0  # (a short scan: one segment, walked whole)
     dec = jpeggpu_amd.Decoder()
