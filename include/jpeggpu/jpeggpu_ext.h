@@ -692,6 +692,55 @@ enum jpeggpu_status jpeggpu_ext_resize_to_rgb_oriented(
     size_t scratch_size,
     jpeggpu_stream_t stream);
 
+/* Batched conversion to RGB (a list of files in, a list of RGB images out, each at its own size -- a validation loader,
+ * or torchvision.io.decode_jpeg on a list): what jpeggpu_ext_crop_to_rgbi_oriented makes of every item with a `crop`, and
+ * jpeggpu_ext_planes_to_rgbi_oriented of every item without one at the image's own extent by its planes (the size of a
+ * plane with the largest sampling factors), each into its own `dst`, with ONE launch for all items of orientations 1..4
+ * and one for all of 5..8 -- at most two per call, not one per image. Planes of one jpeggpu_ext_decode_batch call are the
+ * usual source. Items may mix sizes, scales, IDCT methods, sampling layouts, colour models, orientations, cropped and
+ * whole images.
+ *   - Per item: `info`, `crop` (NULL: the whole image) and `src` as in jpeggpu_ext_resize_item; `color` the planes' model
+ *     (jpeggpu_ext_get_color_space); `orientation` 1..8 (1: stored order); `replicate` 0: fancy upsampling, else
+ *     replication (an image of JPEGGPU_EXT_SCALE_LIBJPEG at 1/8 with subsampling left: jpeggpu_ext_get_scale_info's
+ *     fancy_upsampling == 0) -- this item has room for the flag, so such images are converted here. `crop` and the
+ *     planes are stored; `dst` holds the DISPLAYED rectangle, ow x oh = width x height for 1..4 and height x width for 5..8.
+ *   - JPEGGPU_EXT_HWC: R, G, B of displayed pixel (x, y) at dst + y * dst_pitch + 3 x, dst_pitch >= 3 ow.
+ *     JPEGGPU_EXT_CHW: channel c at dst + c * plane_stride + y * dst_pitch + x, dst_pitch >= ow and plane_stride >=
+ *     dst_pitch * oh (plane_stride is not read for HWC). No alignment is asked of dst or the pitches; rows that start on a
+ *     dword are written in dwords. Outputs that overlap each other are the caller's error and are not checked.
+ *   - `d_scratch`: caller-owned device memory of at least jpeggpu_ext_batch_rgb_scratch_size(n) bytes (the items'
+ *     descriptors and tile lists; host only, 0 for n <= 0 or n > 65535, never smaller for a larger n), private to the
+ *     stream until the call has executed. The host may reuse `items` (and what they point to) as soon as the call
+ *     returns: the descriptors are copied from the page-locked staging ring of the resize calls (of four: the fifth call
+ *     in a row waits until the copy of the first has executed). `stream` must belong to the current device.
+ *   - Each item is checked like the per-image calls, with their statuses in their order (a window outside its plane is
+ *     refused before non-integral ratios): JPEGGPU_NOT_SUPPORTED for a model that does not fit the component count,
+ *     UNKNOWN, non-integral sampling ratios; JPEGGPU_INVALID_ARGUMENT for NULL pointers in an item, windows that do not
+ *     hold the rectangle's samples and their halo. JPEGGPU_INVALID_ARGUMENT as well: NULL `items` or `d_scratch`, n <= 0 or
+ *     n > 65535, a NULL `dst`, an orientation outside 1..8, a dst_pitch or plane_stride too small, an unknown layout,
+ *     scratch_size too small. The first item that fails decides. Every check is made before anything is enqueued and
+ *     without touching the device; on an error nothing is written. */
+enum jpeggpu_ext_image_layout { JPEGGPU_EXT_HWC = 0, JPEGGPU_EXT_CHW = 1 };
+struct jpeggpu_ext_rgb_item {
+    const struct jpeggpu_img_info* info;       /* as parse_header reported it (a cropped decode: the windows) */
+    const struct jpeggpu_ext_crop_info* crop;  /* jpeggpu_ext_get_crop's result; NULL: the whole image */
+    const struct jpeggpu_img* src;             /* the decoded planes */
+    enum jpeggpu_ext_color_space color;
+    int orientation;                           /* 1..8 */
+    int replicate;
+    uint8_t* dst;                              /* the displayed rectangle */
+    int dst_pitch;
+    size_t plane_stride;                       /* JPEGGPU_EXT_CHW only */
+};
+size_t jpeggpu_ext_batch_rgb_scratch_size(int n);
+enum jpeggpu_status jpeggpu_ext_batch_to_rgb(
+    const struct jpeggpu_ext_rgb_item* items,
+    int n,
+    enum jpeggpu_ext_image_layout layout,
+    void* d_scratch,
+    size_t scratch_size,
+    jpeggpu_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

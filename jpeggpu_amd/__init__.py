@@ -5,6 +5,7 @@ hipcc for gfx950). This package is the thin host-side mirror used by the tests a
 ctypes bindings with the reference's function names, argument meaning and status codes.
 """
 from .api import (  # noqa: F401
+    IMAGE_LAYOUTS,
     Batch,
     ColorSpace,
     CropInfo,
@@ -12,9 +13,12 @@ from .api import (  # noqa: F401
     ImgInfo,
     JpegGpuError,
     ProgressiveInfo,
+    RgbItem,
     ScaleInfo,
     Status,
+    batch_to_rgb,
     crop_to_rgb,
+    decode_batch_to_rgb,
     decode_to_planes,
     decode_resized,
     decode_to_rgb,

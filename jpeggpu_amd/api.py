@@ -17,6 +17,7 @@ STAGES = ("front", "destuff", "sync_intra", "sync_inter", "tails", "write", "idc
 IDCT_METHODS = {"reference": 0, "islow": 1}  # enum jpeggpu_ext_idct
 FILTERS = {"bilinear": 0, "bicubic": 1}  # enum jpeggpu_ext_filter
 LAYOUTS = {"NHWC": 0, "NCHW": 1}  # enum jpeggpu_ext_output_layout
+IMAGE_LAYOUTS = {"HWC": 0, "CHW": 1}  # enum jpeggpu_ext_image_layout
 SCALE_MODES = {"uniform": 0, "libjpeg": 1}  # enum jpeggpu_ext_scale_mode
 
 
@@ -79,6 +80,14 @@ class ProgressiveInfo(C.Structure):
 class ResizeItem(C.Structure):
     """struct jpeggpu_ext_resize_item: a decoded image's info and planes, and its crop (NULL: the whole image)."""
     _fields_ = [("info", C.POINTER(ImgInfo)), ("crop", C.POINTER(CropInfo)), ("src", C.POINTER(Img))]
+
+
+class RgbItem(C.Structure):
+    """struct jpeggpu_ext_rgb_item: a decoded image's info, crop (NULL: the whole image) and planes, its colour model, EXIF
+    orientation and whether libjpeg replicates its chroma, and where its displayed RGB goes."""
+    _fields_ = [("info", C.POINTER(ImgInfo)), ("crop", C.POINTER(CropInfo)), ("src", C.POINTER(Img)),
+                ("color", C.c_int), ("orientation", C.c_int), ("replicate", C.c_int),
+                ("dst", C.c_void_p), ("dst_pitch", C.c_int), ("plane_stride", C.c_size_t)]
 
 
 class ExtScanLayout(C.Structure):
@@ -220,6 +229,9 @@ def lib():
     L.jpeggpu_ext_resize_to_rgb_oriented.argtypes = [
         C.POINTER(ResizeItem), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
         C.c_void_p, C.c_size_t, C.c_void_p]
+    L.jpeggpu_ext_batch_rgb_scratch_size.restype = C.c_size_t
+    L.jpeggpu_ext_batch_rgb_scratch_size.argtypes = [C.c_int]
+    L.jpeggpu_ext_batch_to_rgb.argtypes = [C.POINTER(RgbItem), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
     L.jpeggpu_ext_resize_weights.argtypes = [
         C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
     _lib = L
@@ -889,6 +901,134 @@ def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", devi
         batch.set_items(entries)
         batch.decode(scratch.data_ptr(), stream)
         out = resize_to_rgb(planes_list, infos, size, cis, filt, layout, colors=colors, orientations=orients if exif_transpose else None)
+        torch.cuda.synchronize(dev)
+        batch.destroy()
+        return out
+    finally:
+        for dec in decs:
+            dec.cleanup()
+
+
+def _align256(v):
+    return (v + 255) // 256 * 256
+
+
+def batch_to_rgb(planes_list, infos, crop_infos=None, colors=None, orientations=None, replicates=None, layout="HWC"):
+    """jpeggpu_ext_batch_to_rgb on torch's current stream: every decoded image i (planes_list[i], infos[i], and
+    crop_infos[i] from a cropped decode, or None for the whole image) converted to RGB at its own size -- one launch for all
+    images of orientations 1..4 and one for all of 5..8, not one per image. `colors`: each image's ColorSpace (None: grey or
+    YCbCr by the number of components); `orientations`: each image's EXIF orientation 1..8 (None: 1, the stored image;
+    crop_infos are always STORED rectangles, orient_rect); `replicates`: where libjpeg replicates instead of fancy
+    upsampling (None: nowhere). Returns a list of uint8 tensors, (oh, ow, 3) for "HWC" or (3, oh, ow) for "CHW", of the
+    displayed rectangles: views into ONE allocation, each image starting on a multiple of 256 bytes, its rows unpadded."""
+    import torch
+
+    if layout not in IMAGE_LAYOUTS:
+        raise ValueError("layout %r is not one of %s" % (layout, ", ".join(IMAGE_LAYOUTS)))
+    n = len(planes_list)
+    for name, v in (("infos", infos), ("crop_infos", crop_infos), ("colors", colors), ("orientations", orientations), ("replicates", replicates)):
+        if v is not None and len(v) != n:
+            raise ValueError("%s must have one entry per image" % name)
+    if n == 0:
+        return []
+    device = planes_list[0][0].device
+    colors = _item_colors(colors, infos)
+    orientations = [1] * n if orientations is None else [int(o) for o in orientations]
+    if any(not 1 <= o <= 8 for o in orientations):
+        raise ValueError("orientations must be 1..8")
+    items, _keep = _resize_items(planes_list, infos, crop_infos)  # info, crop and src are the resize item's
+    sizes, offsets, total = [], [], 0
+    for i in range(n):
+        ci = crop_infos[i] if crop_infos is not None else None
+        w, h = (ci.width, ci.height) if ci is not None else _frame_size(infos[i])
+        sizes.append((h, w) if orientations[i] >= 5 else (w, h))
+        offsets.append(total)
+        total = _align256(total + 3 * w * h)
+    out = torch.empty(total + 256, dtype=torch.uint8, device=device)
+    start = _align256(out.data_ptr()) - out.data_ptr()  # torch's allocations are aligned far beyond this; kept for any allocator
+    rgb = (RgbItem * n)()
+    for i, (ow, oh) in enumerate(sizes):
+        rgb[i].info, rgb[i].crop, rgb[i].src = items[i].info, items[i].crop, items[i].src
+        rgb[i].color, rgb[i].orientation = int(colors[i]), orientations[i]
+        rgb[i].replicate = int(bool(replicates[i])) if replicates is not None else 0
+        rgb[i].dst = out.data_ptr() + start + offsets[i]
+        rgb[i].dst_pitch = 3 * ow if layout == "HWC" else ow
+        rgb[i].plane_stride = ow * oh
+    need = lib().jpeggpu_ext_batch_rgb_scratch_size(n)
+    scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    _check(lib().jpeggpu_ext_batch_to_rgb(rgb, n, IMAGE_LAYOUTS[layout], scratch.data_ptr(), need, torch.cuda.current_stream(device).cuda_stream),
+           "jpeggpu_ext_batch_to_rgb")
+    # the scratch tensor is freed by torch's caching allocator in stream order: it is not reused before the launches ran
+    views = []
+    for (ow, oh), off in zip(sizes, offsets):
+        flat = out[start + off:start + off + 3 * ow * oh]
+        views.append(flat.view(oh, ow, 3) if layout == "HWC" else flat.view(3, oh, ow))
+    return views
+
+
+def decode_batch_to_rgb(datas, device="cuda:0", crops=None, scales=None, exif_transpose=False, layout="HWC"):
+    """A list of JPEGs in, a list of RGB tensors out, each at its own size (torchvision.io.decode_jpeg on a list; a validation
+    loader): every file of `datas` (of any colour model, baseline or progressive) decoded with libjpeg-turbo's arithmetic
+    in ONE jpeggpu_ext_decode_batch call and converted by ONE jpeggpu_ext_batch_to_rgb call, with one synchronise at the
+    end. Element i equals decode_to_rgb(datas[i], crop=crops[i], scale=scales[i], exif_transpose=exif_transpose) -- (h, w,
+    3) uint8 for "HWC"; for "CHW" that result after .permute(2, 0, 1), (3, h, w). `crops[i]`: (x, y, w, h) or None;
+    `scales[i]` in 1, 2, 4, 8 (default 1), crops in pixels of the image at that scale; images libjpeg upsamples by
+    replication (1/8 with subsampling left) are taken, unlike decode_resized. `exif_transpose`: every file's EXIF
+    orientation is applied, crops[i] is in DISPLAYED pixels. The tensors are views into one allocation (batch_to_rgb). An
+    empty list gives []."""
+    import torch
+
+    if layout not in IMAGE_LAYOUTS:
+        raise ValueError("layout %r is not one of %s" % (layout, ", ".join(IMAGE_LAYOUTS)))
+    dev = torch.device(device)
+    n = len(datas)
+    crops = [None] * n if crops is None else list(crops)
+    if len(crops) != n:
+        raise ValueError("crops must have one entry per image")
+    scales = [1] * n if scales is None else [int(s) for s in scales]
+    if len(scales) != n or any(s not in (1, 2, 4, 8) for s in scales):
+        raise ValueError("scales must have one entry of 1, 2, 4 or 8 per image")
+    if n == 0:
+        return []
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    decs, entries, planes_list, infos, cis, keep, colors, orients, reps = [], [], [], [], [], [], [], [], []
+    try:
+        scans = 0
+        for data, crop, scale in zip(datas, crops, scales):
+            dec = Decoder()
+            decs.append(dec)
+            dec.set_batch_hint(n)
+            dec.set_idct("islow")
+            dec.set_progressive(True)
+            if scale != 1:
+                dec.set_scale(scale)
+                dec.set_scale_mode("libjpeg")
+            if crop is not None and exif_transpose:  # the header once more, for the orientation and the size at the scale
+                w0, h0 = _frame_size(dec.parse_header(data))
+                crop = orient_rect(dec.orientation(), w0, h0, crop)
+            if crop is not None:
+                dec.set_crop(*crop)
+            info = dec.parse_header(data)
+            orients.append(dec.orientation() if exif_transpose else 1)
+            reps.append(_needs_replication(info, scale))
+            scans += dec.layout().num_scans
+            nb = dec.get_buffer_size()
+            tmp = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
+            base = (tmp.data_ptr() + 255) // 256 * 256
+            planes = [torch.empty((info.sizes_y[c], info.sizes_x[c]), dtype=torch.uint8, device=dev)
+                      for c in range(info.num_components)]
+            dec.transfer(base, nb, stream)
+            keep.append(tmp)
+            entries.append((dec, [p.data_ptr() for p in planes], [p.stride(0) for p in planes], base, nb))
+            planes_list.append(planes)
+            infos.append(info)
+            cis.append(dec.crop_info() if crop is not None else None)
+            colors.append(dec.color_space())
+        batch = Batch(scans)
+        scratch = torch.empty(batch.scratch_size, dtype=torch.uint8, device=dev)
+        batch.set_items(entries)
+        batch.decode(scratch.data_ptr(), stream)
+        out = batch_to_rgb(planes_list, infos, cis, colors, orients, reps, layout)
         torch.cuda.synchronize(dev)
         batch.destroy()
         return out

@@ -342,6 +342,94 @@ ResizeStaging& resize_staging()
     return *s;
 }
 
+/// The ring's next buffer with room for `bytes`, once the copy that last read it has executed. Called with rs.mu held.
+jpeggpu_status staging_acquire(ResizeStaging& rs, size_t bytes, uint8_t*& h)
+{
+    const int r = rs.next;
+    // the staging buffer may still be the source of a copy enqueued kRing calls ago
+    if (rs.in_use[r] && hipEventSynchronize(rs.copied[r]) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
+    rs.in_use[r] = false;
+    if (!rs.buf[r].reserve(bytes)) return JPEGGPU_OUT_OF_HOST_MEMORY;
+    h = rs.buf[r].ptr;
+    return JPEGGPU_SUCCESS;
+}
+
+/// The copy of the acquired buffer's first `bytes` to `d_dst` on `stream`; the ring moves on. Called with rs.mu held.
+jpeggpu_status staging_copy(ResizeStaging& rs, void* d_dst, size_t bytes, hipStream_t stream)
+{
+    const int r = rs.next;
+    if (!rs.copied[r] && hipEventCreateWithFlags(&rs.copied[r], hipEventDisableTiming) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
+    if (hipMemcpyAsync(d_dst, rs.buf[r].ptr, bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
+    if (hipEventRecord(rs.copied[r], stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
+    rs.in_use[r] = true;
+    rs.next      = (r + 1) % ResizeStaging::kRing;
+    return JPEGGPU_SUCCESS;
+}
+
+// ------------------------------------------------------------------------------------------------
+// batched conversion (jpeggpu_ext_batch_to_rgb): the items' descriptors and the scratch layout
+// ------------------------------------------------------------------------------------------------
+
+/// Where everything of one call sits in d_scratch: the descriptors, then each item's first tile in the row kernel's list
+/// and in the transposing kernel's. All of it is staged and copied (`total`, without the room to align the pointer).
+struct RgbBatchLayout {
+    size_t off_first = 0, off_first_t = 0, total = 0;
+};
+RgbBatchLayout rgb_batch_layout(int n)
+{
+    RgbBatchLayout l;
+    l.off_first   = align_up(sizeof(RgbJob) * static_cast<size_t>(n), 256);
+    l.off_first_t = align_up(l.off_first + sizeof(int) * static_cast<size_t>(n), 256);
+    l.total       = align_up(l.off_first_t + sizeof(int) * static_cast<size_t>(n), 256);
+    return l;
+}
+
+struct RgbBatchPlan {
+    std::vector<RgbJob> jobs;
+    std::vector<int> first_tile, first_tile_t;
+    int row_tiles = 0, t_tiles = 0;
+    bool all_models = false; // an item that is not grey or YCbCr (fancy_all_models)
+};
+
+/// Every check of a call's items, and their descriptors. Nothing here touches the device.
+jpeggpu_status plan_rgb_batch(const jpeggpu_ext_rgb_item* items, int n, int layout, RgbBatchPlan& p)
+{
+    if (!items || n <= 0 || n > 65535 || (layout != JPEGGPU_EXT_HWC && layout != JPEGGPU_EXT_CHW)) return JPEGGPU_INVALID_ARGUMENT;
+    try {
+        p.jobs.resize(n);
+        p.first_tile.resize(n);
+        p.first_tile_t.resize(n);
+    } catch (const std::bad_alloc&) {
+        return JPEGGPU_OUT_OF_HOST_MEMORY;
+    }
+    int64_t tiles = 0, tiles_t = 0;
+    for (int i = 0; i < n; ++i) {
+        const jpeggpu_ext_rgb_item& it = items[i];
+        if (!it.dst || !orient_valid(it.orientation)) return JPEGGPU_INVALID_ARGUMENT;
+        RgbJob& j = p.jobs[i];
+        j         = RgbJob{};
+        const jpeggpu_status st = fancy_source(it.info, it.color, it.crop, it.src, it.replicate != 0, true, j.src, &j.width, &j.height);
+        if (st != JPEGGPU_SUCCESS) return st;
+        const bool tr = orient_transposes(it.orientation);
+        const int64_t ow = tr ? j.height : j.width, oh = tr ? j.width : j.height; // the displayed rectangle
+        if (layout == JPEGGPU_EXT_HWC ? it.dst_pitch < 3 * ow : it.dst_pitch < ow || it.plane_stride < static_cast<size_t>(it.dst_pitch) * oh)
+            return JPEGGPU_INVALID_ARGUMENT;
+        p.all_models   = p.all_models || fancy_all_models(j.src);
+        j.dst          = it.dst;
+        j.dst_pitch    = it.dst_pitch;
+        j.plane_stride = it.plane_stride;
+        j.flips        = (orient_mirrors_x(it.orientation) ? 1 : 0) | (orient_mirrors_y(it.orientation) ? 2 : 0);
+        j.tiles_x      = rgb_batch_tiles_x(j.width, tr);
+        p.first_tile[i]   = static_cast<int>(tiles);
+        p.first_tile_t[i] = static_cast<int>(tiles_t);
+        (tr ? tiles_t : tiles) += rgb_batch_tiles(j.width, j.height, tr);
+        if (tiles > INT32_MAX || tiles_t > INT32_MAX) return JPEGGPU_INVALID_ARGUMENT;
+    }
+    p.row_tiles = static_cast<int>(tiles);
+    p.t_tiles   = static_cast<int>(tiles_t);
+    return JPEGGPU_SUCCESS;
+}
+
 } // namespace
 } // namespace jg
 
@@ -545,12 +633,9 @@ enum jpeggpu_status resize_to_rgb(
     uint8_t* base = reinterpret_cast<uint8_t*>(jg::align_up(reinterpret_cast<uintptr_t>(d_scratch), 256));
     jg::ResizeStaging& rs = jg::resize_staging();
     std::lock_guard<std::mutex> lock(rs.mu);
-    const int r = rs.next;
-    // the staging buffer may still be the source of a copy enqueued kRing calls ago
-    if (rs.in_use[r] && hipEventSynchronize(rs.copied[r]) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
-    rs.in_use[r] = false;
-    if (!rs.buf[r].reserve(p.head)) return JPEGGPU_OUT_OF_HOST_MEMORY;
-    uint8_t* h = rs.buf[r].ptr;
+    uint8_t* h = nullptr;
+    const jpeggpu_status acquired = jg::staging_acquire(rs, p.head, h);
+    if (acquired != JPEGGPU_SUCCESS) return acquired;
     try {
         for (int i = 0; i < n; ++i) {
             jg::ResizeJob& j = p.jobs[i];
@@ -581,11 +666,8 @@ enum jpeggpu_status resize_to_rgb(
     std::memcpy(h, p.jobs.data(), sizeof(jg::ResizeJob) * n);
     std::memcpy(h + p.off_first, p.first_tile.data(), sizeof(int) * n);
     if (!p.first_tile_t.empty()) std::memcpy(h + p.off_first_t, p.first_tile_t.data(), sizeof(int) * n);
-    if (!rs.copied[r] && hipEventCreateWithFlags(&rs.copied[r], hipEventDisableTiming) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
-    if (hipMemcpyAsync(base, h, p.head, hipMemcpyHostToDevice, stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
-    if (hipEventRecord(rs.copied[r], stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
-    rs.in_use[r] = true;
-    rs.next      = (r + 1) % jg::ResizeStaging::kRing;
+    const jpeggpu_status copied = jg::staging_copy(rs, base, p.head, stream);
+    if (copied != JPEGGPU_SUCCESS) return copied;
     const hipError_t err = jg::launch_resize_oriented(
         reinterpret_cast<const jg::ResizeJob*>(base), reinterpret_cast<const int*>(base + p.off_first),
         reinterpret_cast<const int*>(base + p.off_first_t), n, p.h_tiles, p.t_tiles, p.mirror_store, out_w, out_h, layout, p.all_models, dst,
@@ -708,6 +790,45 @@ enum jpeggpu_status jpeggpu_ext_resize_to_rgb_oriented(
 {
     if (!colors || !orientations) return JPEGGPU_INVALID_ARGUMENT;
     return resize_to_rgb(items, colors, orientations, n, out_w, out_h, filter, layout, dst, d_scratch, scratch_size, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// batched conversion: many images to RGB at their own sizes (jpeggpu_ext.h)
+// ------------------------------------------------------------------------------------------------
+
+size_t jpeggpu_ext_batch_rgb_scratch_size(int n)
+{
+    return n <= 0 || n > 65535 ? 0 : jg::rgb_batch_layout(n).total + 256; // room to align the caller's pointer
+}
+
+enum jpeggpu_status jpeggpu_ext_batch_to_rgb(
+    const struct jpeggpu_ext_rgb_item* items,
+    int n,
+    enum jpeggpu_ext_image_layout layout,
+    void* d_scratch,
+    size_t scratch_size,
+    jpeggpu_stream_t stream)
+{
+    jg::RgbBatchPlan p;
+    const jpeggpu_status st = jg::plan_rgb_batch(items, n, layout, p);
+    if (st != JPEGGPU_SUCCESS) return st;
+    if (!d_scratch || scratch_size < jpeggpu_ext_batch_rgb_scratch_size(n)) return JPEGGPU_INVALID_ARGUMENT;
+    const jg::RgbBatchLayout l = jg::rgb_batch_layout(n);
+    uint8_t* base = reinterpret_cast<uint8_t*>(jg::align_up(reinterpret_cast<uintptr_t>(d_scratch), 256));
+    jg::ResizeStaging& rs = jg::resize_staging();
+    std::lock_guard<std::mutex> lock(rs.mu);
+    uint8_t* h = nullptr;
+    const jpeggpu_status acquired = jg::staging_acquire(rs, l.total, h);
+    if (acquired != JPEGGPU_SUCCESS) return acquired;
+    std::memcpy(h, p.jobs.data(), sizeof(jg::RgbJob) * n);
+    std::memcpy(h + l.off_first, p.first_tile.data(), sizeof(int) * n);
+    std::memcpy(h + l.off_first_t, p.first_tile_t.data(), sizeof(int) * n);
+    const jpeggpu_status copied = jg::staging_copy(rs, base, l.total, stream);
+    if (copied != JPEGGPU_SUCCESS) return copied;
+    const hipError_t err = jg::launch_rgb_batch(
+        reinterpret_cast<const jg::RgbJob*>(base), reinterpret_cast<const int*>(base + l.off_first),
+        reinterpret_cast<const int*>(base + l.off_first_t), n, p.row_tiles, p.t_tiles, layout == JPEGGPU_EXT_CHW, p.all_models, stream);
+    return err == hipSuccess ? JPEGGPU_SUCCESS : JPEGGPU_INTERNAL_ERROR;
 }
 
 } // extern "C"

@@ -12,6 +12,9 @@
 //                           resize_h_color_kernel: the horizontal pass of a call that holds items of the other models;
 //                           resize_h_oriented_kernel / resize_t_kernel: the first pass of items whose displayed x runs
 //                           against stored x, or down stored columns (jpeggpu_ext_resize_to_rgb_oriented)
+//   rgb_batch_kernel /      the conversion of MANY images at their own sizes, any model and orientation, from a device table
+//   rgb_batch_transposed_kernel  of items: one launch for orientations 1..4 and one for 5..8, interleaved (HWC) or planar
+//                           (CHW) output (jpeggpu_ext_batch_to_rgb)
 //
 // Nothing here is shared with the decode path (jg_kernels.hip): the stage reads finished planes.
 #include "jg_output.hpp"
@@ -629,6 +632,162 @@ __global__ __launch_bounds__(256) void resize_v_kernel(const ResizeJob* __restri
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Batched conversion at the items' own sizes (jpeggpu_ext_batch_to_rgb): the tiles of fancy_mirrored_tile and
+// fancy_transposed_tile over a device table of items, the way the resize passes find theirs. The tile bodies are written
+// again here, on fancy_stage / fancy_pixel / store_rgb4, and not shared with the per-image kernels above: those are to come
+// out of the compiler as they were (the compile check). `kPlanar`: the output is three planes (CHW).
+// ------------------------------------------------------------------------------------------------
+
+static_assert(kRgbBatchTileW == kFancyTileW && kRgbBatchTileH == kFancyTileH, "the host counts the row kernel's tiles");
+
+/// The last item whose first tile is <= b: the item of workgroup b (items without tiles in this list share their first
+/// tile with the item behind them and are never found).
+__device__ __forceinline__ int rgb_batch_item(const int* first_tile, int n, int b)
+{
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int m = (lo + hi + 1) >> 1;
+        if (first_tile[m] <= b) lo = m;
+        else hi = m - 1;
+    }
+    return lo;
+}
+
+/// Orientations 1..4 of a batch: one kFancyTileW x kFancyTileH tile of one item per workgroup, each lane a 2 x 4 quad stored
+/// where `flips` displays it (0: fancy_rgbi_tile's store). Only the samples under the tile's part of the rectangle are
+/// staged. Planar: a lane's four pixels are four consecutive bytes of each channel plane -- one dword per channel where
+/// the run is whole and aligned (a wave then writes 256 contiguous bytes per plane), bytes otherwise: store_rgb4's rule.
+template <bool kAllModels, bool kPlanar>
+__global__ __launch_bounds__(256) void rgb_batch_kernel(const RgbJob* __restrict__ jobs, const int* __restrict__ first_tile, int n)
+{
+    __shared__ typename Fancy<kAllModels>::Tiles s_t;
+    const int b = blockIdx.x, item = rgb_batch_item(first_tile, n, b);
+    const RgbJob& J = jobs[item];
+    const FancySource& p = J.src;
+    const int tile = b - first_tile[item], ty = tile / J.tiles_x, tx = tile - ty * J.tiles_x;
+    const int width = J.width, height = J.height;
+    const int t  = threadIdx.x;
+    const int x0 = tx * kFancyTileW, y0 = ty * kFancyTileH;
+    const int px = p.x, py = p.y;
+    int bx[Fancy<kAllModels>::kComps], by[Fancy<kAllModels>::kComps];
+    fancy_stage<true, kAllModels>(p, s_t, x0 + px, y0 + py, min(kFancyTileW, width - x0), min(kFancyTileH, height - y0), bx, by);
+    __syncthreads();
+    const int x = x0 + 4 * (t & 63);
+    if (x >= width) return;
+    const int np = min(4, width - x);
+    const int flips = J.flips;
+    const bool mx = flips & 1, my = flips & 2;
+    uint8_t* dst = J.dst;
+    const int dst_pitch = J.dst_pitch;
+    const size_t xd = static_cast<size_t>(mx ? width - x - np : x);
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+        const int y = y0 + 2 * (t >> 6) + dy;
+        if (y >= height) break;
+        uint32_t out[12];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { // displayed pixel i of the lane's run: stored x + np - 1 - i when mirrored
+            const int xs = mx ? max(x + np - 1 - i, x) : min(x + i, width - 1);
+            fancy_pixel<kAllModels>(p, s_t, bx, by, xs + px, y + py, &out[3 * i]);
+        }
+        uint8_t* drow = dst + static_cast<size_t>(my ? height - 1 - y : y) * dst_pitch;
+        if constexpr (!kPlanar) {
+            store_rgb4(drow + xd * 3, out, np);
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                uint8_t* d = drow + c * J.plane_stride + xd;
+                if (np == 4 && (reinterpret_cast<uintptr_t>(d) & 3) == 0) {
+                    *reinterpret_cast<uint32_t*>(d) = out[c] | out[3 + c] << 8 | out[6 + c] << 16 | out[9 + c] << 24;
+                } else {
+                    for (int i = 0; i < np; ++i) d[i] = static_cast<uint8_t>(out[3 * i + c]);
+                }
+            }
+        }
+    }
+}
+
+/// Orientations 5..8 of a batch: fancy_transposed_tile's body over one kOrientTile x kOrientTile tile of one item. Planar:
+/// a displayed row of the tile is nh <= 64 contiguous bytes in each of the three planes, and ONE wave instruction stores
+/// all three runs: lane 17 c + g writes dword g of channel c's run (17, not 16: a run that does not start on a dword
+/// spills into one more; its two ends go out as bytes), put together from byte c of four pixels of s_rgb. Those four LDS
+/// reads go down a column: pixel q of the row is dword 65 q + row, bank (q + row) mod 32 for ds_read_b32, and a lane's
+/// pixels are 4 g + k, so lanes g and g + 8 of a channel meet on a bank (the three channels read the same dwords, which
+/// broadcast): 2- to 3-way on four reads a row, against a third of the store instructions of a pixel-per-lane write-out.
+template <bool kAllModels, bool kPlanar>
+__global__ __launch_bounds__(256) void rgb_batch_transposed_kernel(const RgbJob* __restrict__ jobs, const int* __restrict__ first_tile, int n)
+{
+    __shared__ typename Fancy<kAllModels>::Tiles s_t;
+    __shared__ uint32_t s_rgb[kOrientTile][kOrientTile + 1];
+    const int b = blockIdx.x, item = rgb_batch_item(first_tile, n, b);
+    const RgbJob& J = jobs[item];
+    const FancySource& p = J.src;
+    const int tile = b - first_tile[item], ty = tile / J.tiles_x, tx = tile - ty * J.tiles_x;
+    const int width = J.width, height = J.height;
+    const int t  = threadIdx.x;
+    const int x0 = tx * kOrientTile, y0 = ty * kOrientTile;
+    const int nw = min(kOrientTile, width - x0), nh = min(kOrientTile, height - y0);
+    const int px = p.x, py = p.y;
+    for (int s0 = 0; s0 < nh; s0 += kFancyTileH) {
+        const int ch = min(kFancyTileH, nh - s0);
+        int bx[Fancy<kAllModels>::kComps], by[Fancy<kAllModels>::kComps];
+        fancy_stage<true, kAllModels>(p, s_t, x0 + px, y0 + s0 + py, nw, ch, bx, by);
+        __syncthreads();
+        for (int q = t; q < kFancyTileH * kOrientTile; q += 256) {
+            const int qy = q / kOrientTile, qx = q % kOrientTile;
+            if (qy >= ch || qx >= nw) continue;
+            uint32_t rgb[3];
+            fancy_pixel<kAllModels>(p, s_t, bx, by, x0 + qx + px, y0 + s0 + qy + py, rgb);
+            s_rgb[s0 + qy][qx] = rgb[0] | rgb[1] << 8 | rgb[2] << 16;
+        }
+        __syncthreads(); // the next strip's staging overwrites the tiles; the last one: s_rgb is complete
+    }
+    const int flips = J.flips;
+    const bool mx = flips & 1, my = flips & 2;
+    const int ox0 = mx ? height - y0 - nh : y0; // the displayed columns of the tile's stored rows, nh of them
+    const int lane = t & 63;
+    uint8_t* dst = J.dst;
+    const int dst_pitch = J.dst_pitch;
+    if constexpr (!kPlanar) {
+        const int nbytes = 3 * nh;
+        for (int row = t >> 6; row < nw; row += 4) { // displayed row: stored column x0 + row
+            const int oy = my ? width - 1 - (x0 + row) : x0 + row;
+            uint8_t* a   = dst + static_cast<size_t>(oy) * dst_pitch + static_cast<size_t>(ox0) * 3;
+            const int b0 = 4 * lane - static_cast<int>(reinterpret_cast<uintptr_t>(a) & 3); // the lane's dword: bytes b0 .. b0 + 3 of the run
+            if (b0 + 4 <= 0 || b0 >= nbytes) continue;
+            if (b0 >= 0 && b0 + 4 <= nbytes) { // pixels b0 / 3 and the next hold its four bytes
+                const int p0 = b0 / 3, r = b0 - 3 * p0;
+                const uint32_t v0 = s_rgb[mx ? nh - 1 - p0 : p0][row], v1 = s_rgb[mx ? nh - 2 - p0 : p0 + 1][row];
+                *reinterpret_cast<uint32_t*>(a + b0) = static_cast<uint32_t>((v0 | static_cast<uint64_t>(v1) << 24) >> (8 * r));
+            } else {
+                for (int k = max(b0, 0); k < min(b0 + 4, nbytes); ++k) {
+                    const int pi = k / 3;
+                    a[k] = static_cast<uint8_t>(s_rgb[mx ? nh - 1 - pi : pi][row] >> (8 * (k - 3 * pi)));
+                }
+            }
+        }
+    } else {
+        const int c = lane / 17, g = lane - 17 * c;
+        if (c >= 3) return;
+        const size_t plane = c * J.plane_stride;
+        for (int row = t >> 6; row < nw; row += 4) {
+            const int oy = my ? width - 1 - (x0 + row) : x0 + row;
+            uint8_t* a   = dst + plane + static_cast<size_t>(oy) * dst_pitch + ox0;
+            const int b0 = 4 * g - static_cast<int>(reinterpret_cast<uintptr_t>(a) & 3); // the lane's dword: pixels b0 .. b0 + 3 of the run
+            if (b0 + 4 <= 0 || b0 >= nh) continue;
+            if (b0 >= 0 && b0 + 4 <= nh) {
+                uint32_t v = 0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v |= ((s_rgb[mx ? nh - 1 - (b0 + k) : b0 + k][row] >> (8 * c)) & 255u) << (8 * k);
+                *reinterpret_cast<uint32_t*>(a + b0) = v;
+            } else {
+                for (int k = max(b0, 0); k < min(b0 + 4, nh); ++k) a[k] = static_cast<uint8_t>(s_rgb[mx ? nh - 1 - k : k][row] >> (8 * c));
+            }
+        }
+    }
+}
+
 } // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -746,6 +905,32 @@ hipError_t launch_resize_oriented(
     }
     const int v_tiles = ((out_w + kResizeVTileW - 1) / kResizeVTileW) * ((out_h + kResizeVTileH - 1) / kResizeVTileH);
     resize_v_kernel<<<dim3(v_tiles, n), 256, 0, stream>>>(d_jobs, out_w, out_h, layout, dst);
+    return hipGetLastError();
+}
+
+hipError_t launch_rgb_batch(
+    const RgbJob* d_jobs, const int* d_first_tile, const int* d_first_tile_t, int n, int row_tiles, int t_tiles, bool planar, bool all_models,
+    hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    if (row_tiles > 0) {
+        if (all_models) {
+            if (planar) rgb_batch_kernel<true, true><<<row_tiles, 256, 0, stream>>>(d_jobs, d_first_tile, n);
+            else rgb_batch_kernel<true, false><<<row_tiles, 256, 0, stream>>>(d_jobs, d_first_tile, n);
+        } else {
+            if (planar) rgb_batch_kernel<false, true><<<row_tiles, 256, 0, stream>>>(d_jobs, d_first_tile, n);
+            else rgb_batch_kernel<false, false><<<row_tiles, 256, 0, stream>>>(d_jobs, d_first_tile, n);
+        }
+    }
+    if (t_tiles > 0) {
+        if (all_models) {
+            if (planar) rgb_batch_transposed_kernel<true, true><<<t_tiles, 256, 0, stream>>>(d_jobs, d_first_tile_t, n);
+            else rgb_batch_transposed_kernel<true, false><<<t_tiles, 256, 0, stream>>>(d_jobs, d_first_tile_t, n);
+        } else {
+            if (planar) rgb_batch_transposed_kernel<false, true><<<t_tiles, 256, 0, stream>>>(d_jobs, d_first_tile_t, n);
+            else rgb_batch_transposed_kernel<false, false><<<t_tiles, 256, 0, stream>>>(d_jobs, d_first_tile_t, n);
+        }
+    }
     return hipGetLastError();
 }
 

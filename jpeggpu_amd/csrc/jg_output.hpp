@@ -133,6 +133,39 @@ hipError_t launch_resize_oriented(
     const ResizeJob* d_jobs, const int* d_first_tile, const int* d_first_tile_t, int n, int h_tiles, int t_tiles, bool mirror_store,
     int out_w, int out_h, int layout, bool all_models, uint8_t* dst, hipStream_t stream);
 
+/// One item of a batched conversion (launch_rgb_batch), in device memory: a source rectangle written at its own size
+/// where `flips` and the kernel that takes it display it. Interleaved (HWC): R, G, B of displayed pixel (x, y) at
+/// dst + y * dst_pitch + 3 * x; planar (CHW): channel c at dst + c * plane_stride + y * dst_pitch + x.
+struct RgbJob {
+    FancySource src;     // as fancy_source builds it (windows, rectangle origin, modes, colour)
+    uint8_t* dst;
+    int dst_pitch;
+    size_t plane_stride; // CHW only
+    int width, height;   // the STORED rectangle
+    int flips;           // bit 0: displayed x runs against the stored axis it lies along; bit 1: displayed y
+    int tiles_x;         // tiles per tile row of this item
+};
+/// Workgroups of one item: kRgbBatchTileW x kRgbBatchTileH tiles (orientations 1..4: the row kernels' tile) or kOrientTile
+/// squares (5..8) of the stored rectangle. rgb_batch_tiles_x: RgbJob::tiles_x.
+constexpr int kRgbBatchTileW = 256, kRgbBatchTileH = 8;
+inline int rgb_batch_tiles_x(int width, bool transposes)
+{
+    return transposes ? (width + kOrientTile - 1) / kOrientTile : (width + kRgbBatchTileW - 1) / kRgbBatchTileW;
+}
+inline int64_t rgb_batch_tiles(int width, int height, bool transposes)
+{
+    const int rows = transposes ? (height + kOrientTile - 1) / kOrientTile : (height + kRgbBatchTileH - 1) / kRgbBatchTileH;
+    return static_cast<int64_t>(rgb_batch_tiles_x(width, transposes)) * rows;
+}
+/// The conversion of `n` items: `d_jobs` RgbJob[n], `d_first_tile` int[n] (each item's first workgroup of the row
+/// kernel; `row_tiles` in all) and `d_first_tile_t` int[n] (the same for the transposing kernel, `t_tiles`) in device
+/// memory. Items of orientations 1..4 have their tiles in the first list, items of 5..8 in the second, none in the other.
+/// At most two launches: none for a list without tiles. `planar`: CHW. `all_models`: some item is not grey or YCbCr
+/// (fancy_all_models); both kernels then run as the instantiation that knows every model, for all items of the call.
+hipError_t launch_rgb_batch(
+    const RgbJob* d_jobs, const int* d_first_tile, const int* d_first_tile_t, int n, int row_tiles, int t_tiles, bool planar, bool all_models,
+    hipStream_t stream);
+
 } // namespace jg
 
 #endif // JG_OUTPUT_HPP_
