@@ -62,7 +62,9 @@ def decode_islow(torch, data, subseq_bytes=None, device_scan=False):
 
 @pytest.mark.parametrize("subseq_bytes,device_scan", [(32, False), (64, True), (256, False), (256, True)])
 def test_matrix_islow_full_size(torch_cuda, matrix, subseq_bytes, device_scan):
-    """Every matrix file, q16_tables and dense_escapes included (their coefficients take the 64-bit pass 1)."""
+    """Every matrix file, q16_tables and dense_escapes included. None of them reaches the 64-bit pass 1: their largest
+    |coefficient * quantiser| is 1,023 (dense_escapes; 534 in q16_tables), far below kIslowPass1Max. That pass is run by
+    tests/test_gpu_idct_cases.py::test_lone_decode[islow-*] on the pass1_*, ycc420* and kats16_* files of tests/idct_cases.py."""
     from oracle import oracle
 
     for name, data in matrix.items():
