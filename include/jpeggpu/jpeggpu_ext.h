@@ -32,6 +32,8 @@
  *                                      Image.convert("RGB") makes of files of all five
  *   jpeggpu_ext_set_progressive /      progressive JPEGs (SOF2), per decoder and off by default: their scans are decoded
  *   jpeggpu_ext_get_progressive_info   on the device into coefficient buffers and handed to the IDCT stage
+ *   jpeggpu_ext_resize_to_tensor       the batched resize written as a model's input: uint8, float32, float16 or bfloat16,
+ *                                      normalised as ToTensor + Normalize do, items flipped left to right where asked
  */
 #ifndef JPEGGPU_JPEGGPU_EXT_H_
 #define JPEGGPU_JPEGGPU_EXT_H_
@@ -688,6 +690,56 @@ enum jpeggpu_status jpeggpu_ext_resize_to_rgb_oriented(
     enum jpeggpu_ext_filter filter,
     enum jpeggpu_ext_output_layout layout,
     uint8_t* dst,
+    void* d_scratch,
+    size_t scratch_size,
+    jpeggpu_stream_t stream);
+
+/* The batched resize written as a model's input: jpeggpu_ext_resize_to_rgb_oriented (RandomResizedCrop equal to torchvision
+ * on Pillow) followed, in the same vertical pass and before anything is stored, by what every training loader does next:
+ * RandomHorizontalFlip, ToTensor and Normalize, and a cast to half precision. `colors` NULL: each item's model by its
+ * component count (jpeggpu_ext_resize_to_rgb); `orientations` NULL: 1 for all. The first-pass launches are exactly those
+ * of the uint8 call on the same arguments; the vertical pass is another kernel: at most three launches, two without items
+ * of orientations 5..8.
+ *   - `dst`: n x out_h x out_w x 3 (JPEGGPU_EXT_NHWC) or n x 3 x out_h x out_w (JPEGGPU_EXT_NCHW) elements of spec->type,
+ *     rows unpadded. It must be aligned to the element (else JPEGGPU_INVALID_ARGUMENT) and need not be aligned further.
+ *   - JPEGGPU_EXT_TENSOR_U8: the bytes of the uint8 call; `mean` and `std` are ignored.
+ *   - The float types, THE CONTRACT: for byte u of channel c (0: R, 1: G, 2: B)
+ *         y = ((float(u) / 255.0f) - mean[c]) / std[c]
+ *     Every operation is an IEEE-754 binary32 operation, rounded to nearest even on its own. It is not contracted into an
+ *     FMA, not computed with a reciprocal multiply and not folded into one scale and bias. This is what ToTensor and
+ *     Normalize compute on the CPU: img.float().div(255), then sub_(mean).div_(std) with float32 tensors. (The reciprocal
+ *     form differs from it in 322 of the 3 x 256 values for the ImageNet constants, the single-FMA form in 522.) mean 0
+ *     and std 1 give ToTensor alone: - 0.0f and / 1.0f are exact. JPEGGPU_EXT_TENSOR_F16 and _BF16 are that float32
+ *     value converted once, round to nearest even; they are NOT arithmetic done in half precision.
+ *   - `flips`: host memory, n entries, read before the call returns; non-zero: item i is flipped left to right -- output
+ *     column x is column out_w - 1 - x of the unflipped result (torch.flip of the resized image over its width, which is
+ *     torchvision's flip AFTER the resize; a resize of the mirrored source differs from it in the last bit). NULL: no item
+ *     is flipped. Flips compose with every orientation and colour model: they touch the vertical pass only.
+ *   - `d_scratch`, `scratch_size`: those of the uint8 call on the same items, colours and orientations --
+ *     jpeggpu_ext_resize_scratch_size_oriented, or jpeggpu_ext_resize_scratch_size_cs / jpeggpu_ext_resize_scratch_size where
+ *     `orientations` / `colors` are NULL. There is no size call of its own.
+ *   - JPEGGPU_INVALID_ARGUMENT: `spec` NULL, a type that is none of the four, and for a float type a std[c] that is zero
+ *     or a mean[c] or std[c] that is not finite -- checked first; then everything the uint8 call refuses, with its statuses
+ *     (n <= 0, an unknown filter: JPEGGPU_NOT_SUPPORTED, an item's checks, NULL dst or scratch, an unknown layout, a
+ *     scratch too small), and a `dst` not aligned to the element. Every check is made before anything is staged or
+ *     enqueued; on an error nothing is written. */
+enum jpeggpu_ext_tensor_type { JPEGGPU_EXT_TENSOR_U8 = 0, JPEGGPU_EXT_TENSOR_F32 = 1, JPEGGPU_EXT_TENSOR_F16 = 2, JPEGGPU_EXT_TENSOR_BF16 = 3 };
+struct jpeggpu_ext_tensor_spec {
+    enum jpeggpu_ext_tensor_type type;
+    float mean[3], std[3];      /* float types only */
+    const unsigned char* flips; /* host, n entries, non-zero: flip item i; NULL: none */
+};
+enum jpeggpu_status jpeggpu_ext_resize_to_tensor(
+    const struct jpeggpu_ext_resize_item* items,
+    const enum jpeggpu_ext_color_space* colors, /* NULL: by the component count */
+    const int* orientations,                    /* NULL: all 1 */
+    int n,
+    int out_w,
+    int out_h,
+    enum jpeggpu_ext_filter filter,
+    enum jpeggpu_ext_output_layout layout,
+    const struct jpeggpu_ext_tensor_spec* spec,
+    void* dst,
     void* d_scratch,
     size_t scratch_size,
     jpeggpu_stream_t stream);

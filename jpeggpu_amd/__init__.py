@@ -6,6 +6,7 @@ ctypes bindings with the reference's function names, argument meaning and status
 """
 from .api import (  # noqa: F401
     IMAGE_LAYOUTS,
+    TENSOR_TYPES,
     Batch,
     ColorSpace,
     CropInfo,
@@ -16,6 +17,7 @@ from .api import (  # noqa: F401
     RgbItem,
     ScaleInfo,
     Status,
+    TensorSpec,
     batch_to_rgb,
     crop_to_rgb,
     decode_batch_to_rgb,
@@ -31,6 +33,7 @@ from .api import (  # noqa: F401
     planes_to_rgb,
     resize_scratch_size,
     resize_to_rgb,
+    resize_to_tensor,
     resize_weights,
     self_test,
     status_string,

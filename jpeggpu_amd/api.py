@@ -19,6 +19,35 @@ FILTERS = {"bilinear": 0, "bicubic": 1}  # enum jpeggpu_ext_filter
 LAYOUTS = {"NHWC": 0, "NCHW": 1}  # enum jpeggpu_ext_output_layout
 IMAGE_LAYOUTS = {"HWC": 0, "CHW": 1}  # enum jpeggpu_ext_image_layout
 SCALE_MODES = {"uniform": 0, "libjpeg": 1}  # enum jpeggpu_ext_scale_mode
+TENSOR_TYPE_NAMES = {"uint8": 0, "float32": 1, "float16": 2, "bfloat16": 3}  # enum jpeggpu_ext_tensor_type, by torch dtype name
+
+
+def _tensor_types():
+    import torch
+
+    return {getattr(torch, name): v for name, v in TENSOR_TYPE_NAMES.items()}
+
+
+class _TensorTypes(dict):
+    """TENSOR_TYPES: torch dtype -> enum jpeggpu_ext_tensor_type. Filled at first use, so importing the binding does not
+    import torch."""
+
+    def _fill(self):
+        if not len(self):
+            self.update(_tensor_types())
+        return self
+
+    def __getitem__(self, k):
+        return dict.__getitem__(self._fill(), k)
+
+    def __contains__(self, k):
+        return dict.__contains__(self._fill(), k)
+
+    def __iter__(self):
+        return dict.__iter__(self._fill())
+
+
+TENSOR_TYPES = _TensorTypes()
 
 
 class ColorSpace(enum.IntEnum):
@@ -80,6 +109,12 @@ class ProgressiveInfo(C.Structure):
 class ResizeItem(C.Structure):
     """struct jpeggpu_ext_resize_item: a decoded image's info and planes, and its crop (NULL: the whole image)."""
     _fields_ = [("info", C.POINTER(ImgInfo)), ("crop", C.POINTER(CropInfo)), ("src", C.POINTER(Img))]
+
+
+class TensorSpec(C.Structure):
+    """struct jpeggpu_ext_tensor_spec: the element type of jpeggpu_ext_resize_to_tensor's output, Normalize's mean and std
+    per channel (float types only) and the items to flip left to right (host bytes, one per item; NULL: none)."""
+    _fields_ = [("type", C.c_int), ("mean", C.c_float * 3), ("std", C.c_float * 3), ("flips", C.POINTER(C.c_ubyte))]
 
 
 class RgbItem(C.Structure):
@@ -229,6 +264,9 @@ def lib():
     L.jpeggpu_ext_resize_to_rgb_oriented.argtypes = [
         C.POINTER(ResizeItem), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
         C.c_void_p, C.c_size_t, C.c_void_p]
+    L.jpeggpu_ext_resize_to_tensor.argtypes = [
+        C.POINTER(ResizeItem), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(TensorSpec),
+        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.jpeggpu_ext_batch_rgb_scratch_size.restype = C.c_size_t
     L.jpeggpu_ext_batch_rgb_scratch_size.argtypes = [C.c_int]
     L.jpeggpu_ext_batch_to_rgb.argtypes = [C.POINTER(RgbItem), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -836,7 +874,77 @@ def resize_to_rgb(planes_list, infos, size, crop_infos=None, filt="bilinear", la
     return out
 
 
-def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", device="cuda:0", scales=None, exif_transpose=False):
+def _channel_triple(v, default, name):
+    """Normalize's per-channel argument as three floats: None (the default), one number for all, or three."""
+    if v is None:
+        return [default] * 3
+    try:
+        v = [float(a) for a in v]
+    except TypeError:
+        v = [float(v)] * 3
+    if len(v) != 3:
+        raise ValueError("%s must be one number or three" % name)
+    return v
+
+
+def resize_to_tensor(planes_list, infos, size, crop_infos=None, filt="bilinear", layout="NHWC", colors=None, orientations=None, dtype=None,
+                     mean=None, std=None, flips=None, out=None):
+    """jpeggpu_ext_resize_to_tensor on torch's current stream: resize_to_rgb's result (same items, `size`, `filt`, `layout`,
+    `colors`, `orientations`) written as a model's input, by the same launches but for the last. `dtype`: torch.float32 (the
+    default), float16, bfloat16 or uint8. For the float types element u of channel c becomes ((float(u) / 255) - mean[c]) /
+    std[c], each operation in float32 on its own -- bit for bit torchvision's ToTensor followed by Normalize(mean, std) on
+    the CPU; `mean` / `std`: three numbers, one, or None (0 and 1: ToTensor alone); float16 and bfloat16 are that float32
+    value converted once. uint8: the bytes (mean and std are ignored). `flips`: one truth value per item -- where true,
+    the item is flipped left to right after the resize (torch.flip over the width, RandomHorizontalFlip with the caller's
+    draws); None: no item. Returns a tensor of `dtype`, n x h x w x 3 ("NHWC") or n x 3 x h x w ("NCHW"); `out` if given
+    (contiguous, of that shape and dtype)."""
+    import torch
+
+    if filt not in FILTERS:
+        raise ValueError("filter %r is not one of %s" % (filt, ", ".join(FILTERS)))
+    if layout not in LAYOUTS:
+        raise ValueError("layout %r is not one of %s" % (layout, ", ".join(LAYOUTS)))
+    dtype = torch.float32 if dtype is None else dtype
+    if dtype not in TENSOR_TYPES:
+        raise ValueError("dtype %r is not one of %s" % (dtype, ", ".join(TENSOR_TYPE_NAMES)))
+    h, w = _size_hw(size)
+    n = len(planes_list)
+    device = planes_list[0][0].device
+    items, _keep = _resize_items(planes_list, infos, crop_infos)
+    spec = TensorSpec()
+    spec.type = TENSOR_TYPES[dtype]
+    spec.mean[:] = _channel_triple(mean, 0.0, "mean")
+    spec.std[:] = _channel_triple(std, 1.0, "std")
+    flip_bytes = None
+    if flips is not None:
+        if len(flips) != n:
+            raise ValueError("flips must have one entry per image")
+        flip_bytes = (C.c_ubyte * n)(*[1 if f else 0 for f in flips])
+        spec.flips = C.cast(flip_bytes, C.POINTER(C.c_ubyte))
+    shape = (n, h, w, 3) if layout == "NHWC" else (n, 3, h, w)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=device)
+    elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous():
+        raise ValueError("out must be a contiguous %s tensor of shape %s" % (dtype, shape))
+    cs = os_ = None
+    if orientations is not None:  # the scratch is the uint8 call's, by the arguments given
+        cs, os_ = _color_array(_item_colors(colors, infos), n), _color_array(orientations, n)
+        need = lib().jpeggpu_ext_resize_scratch_size_oriented(items, cs, os_, n, w, h, FILTERS[filt])
+    elif colors is not None:
+        cs = _color_array(colors, n)
+        need = lib().jpeggpu_ext_resize_scratch_size_cs(items, cs, n, w, h, FILTERS[filt])
+    else:
+        need = lib().jpeggpu_ext_resize_scratch_size(items, n, w, h, FILTERS[filt])
+    scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    _check(lib().jpeggpu_ext_resize_to_tensor(items, cs, os_, n, w, h, FILTERS[filt], LAYOUTS[layout], C.byref(spec), out.data_ptr(),
+                                              scratch.data_ptr(), need, torch.cuda.current_stream(device).cuda_stream),
+           "jpeggpu_ext_resize_to_tensor")
+    # the scratch tensor is freed by torch's caching allocator in stream order: it is not reused before the launches ran
+    return out
+
+
+def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", device="cuda:0", scales=None, exif_transpose=False,
+                   dtype=None, mean=None, std=None, flips=None):
     """A training pipeline's decode: every JPEG of `datas` (of any colour model: decode_to_rgb) decoded with libjpeg-turbo's
     arithmetic (ISLOW IDCT, fancy upsampling), only the rectangle crops[i] = (x, y, w, h) of it (None: the whole image), in ONE jpeggpu_ext_decode_batch
     call, then resized to `size` (int: square; (h, w)) with Pillow's BILINEAR or BICUBIC arithmetic by one
@@ -848,7 +956,12 @@ def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", devi
     .resize(...). A ValueError for an image that libjpeg would upsample by replication (1/8 with subsampling left, e.g.
     4:2:2): the batched resize does not reproduce that; use scale 4 for it. `exif_transpose`: every file's EXIF
     orientation is applied -- crops[i] is in DISPLAYED pixels at the scale, and the result equals
-    ImageOps.exif_transpose(im) put after draft() and before convert("RGB"), crop() and resize()."""
+    ImageOps.exif_transpose(im) put after draft() and before convert("RGB"), crop() and resize().
+    `dtype`, `mean`, `std`, `flips`: with any of them the second step is one jpeggpu_ext_resize_to_tensor call
+    (resize_to_tensor) and the result is a training loader's whole transform -- RandomResizedCrop + RandomHorizontalFlip +
+    ToTensor + Normalize(mean, std), with the draws (crops[i], flips[i]) supplied by the caller -- as a tensor of `dtype`:
+    torch.float32 if `mean` or `std` is given, torch.uint8 (the bytes, flipped where asked) if only `flips` is; float16 and
+    bfloat16 are the float32 result converted once. With all four None the call is what it was, call for call."""
     import torch
 
     dev = torch.device(device)
@@ -900,7 +1013,13 @@ def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", devi
         scratch = torch.empty(batch.scratch_size, dtype=torch.uint8, device=dev)
         batch.set_items(entries)
         batch.decode(scratch.data_ptr(), stream)
-        out = resize_to_rgb(planes_list, infos, size, cis, filt, layout, colors=colors, orientations=orients if exif_transpose else None)
+        if dtype is None and mean is None and std is None and flips is None:
+            out = resize_to_rgb(planes_list, infos, size, cis, filt, layout, colors=colors, orientations=orients if exif_transpose else None)
+        else:
+            if dtype is None:
+                dtype = torch.uint8 if mean is None and std is None else torch.float32
+            out = resize_to_tensor(planes_list, infos, size, cis, filt, layout, colors=colors, orientations=orients if exif_transpose else None,
+                                   dtype=dtype, mean=mean, std=std, flips=flips)
         torch.cuda.synchronize(dev)
         batch.destroy()
         return out

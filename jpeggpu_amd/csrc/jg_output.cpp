@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <mutex>
@@ -610,7 +611,16 @@ enum jpeggpu_status jpeggpu_ext_resize_weights(
 }
 
 namespace {
-/// `colors` null: each item's model by its component count. `orients` null: orientation 1 for all.
+static_assert(jg::kTensorU8 == int{JPEGGPU_EXT_TENSOR_U8} && jg::kTensorF32 == int{JPEGGPU_EXT_TENSOR_F32} &&
+                  jg::kTensorF16 == int{JPEGGPU_EXT_TENSOR_F16} && jg::kTensorBF16 == int{JPEGGPU_EXT_TENSOR_BF16},
+              "TensorType is enum jpeggpu_ext_tensor_type");
+// the layout the ctypes mirror (jpeggpu_amd/api.py, TensorSpec) is written for
+static_assert(offsetof(jpeggpu_ext_tensor_spec, type) == 0 && offsetof(jpeggpu_ext_tensor_spec, mean) == 4 && offsetof(jpeggpu_ext_tensor_spec, std) == 16 &&
+                  offsetof(jpeggpu_ext_tensor_spec, flips) == 32 && sizeof(jpeggpu_ext_tensor_spec) == 40,
+              "struct jpeggpu_ext_tensor_spec");
+
+/// `colors` null: each item's model by its component count. `orients` null: orientation 1 for all. `spec` null: uint8
+/// through resize_v_kernel (the jpeggpu_ext_resize_to_rgb* calls); else, checked by the caller, the tensor pass.
 enum jpeggpu_status resize_to_rgb(
     const struct jpeggpu_ext_resize_item* items,
     const enum jpeggpu_ext_color_space* colors,
@@ -620,16 +630,20 @@ enum jpeggpu_status resize_to_rgb(
     int out_h,
     enum jpeggpu_ext_filter filter,
     enum jpeggpu_ext_output_layout layout,
-    uint8_t* dst,
+    void* dst,
     void* d_scratch,
     size_t scratch_size,
-    jpeggpu_stream_t stream)
+    jpeggpu_stream_t stream,
+    const struct jpeggpu_ext_tensor_spec* spec = nullptr)
 {
     jg::ResizePlan p;
     const jpeggpu_status st = jg::plan_resize(items, colors, orients, n, out_w, out_h, filter, p);
     if (st != JPEGGPU_SUCCESS) return st;
     if (!dst || !d_scratch || (layout != JPEGGPU_EXT_NHWC && layout != JPEGGPU_EXT_NCHW) || scratch_size < p.total)
         return JPEGGPU_INVALID_ARGUMENT;
+    if (spec && reinterpret_cast<uintptr_t>(dst) % jg::tensor_elem_size(spec->type) != 0) return JPEGGPU_INVALID_ARGUMENT;
+    for (int i = 0; spec && spec->flips && i < n; ++i) // the vertical pass alone reads it: plan, tables and `mid` stay as they are
+        if (spec->flips[i]) p.jobs[i].pad_ |= jg::kResizeFlipOutput;
     uint8_t* base = reinterpret_cast<uint8_t*>(jg::align_up(reinterpret_cast<uintptr_t>(d_scratch), 256));
     jg::ResizeStaging& rs = jg::resize_staging();
     std::lock_guard<std::mutex> lock(rs.mu);
@@ -668,10 +682,22 @@ enum jpeggpu_status resize_to_rgb(
     if (!p.first_tile_t.empty()) std::memcpy(h + p.off_first_t, p.first_tile_t.data(), sizeof(int) * n);
     const jpeggpu_status copied = jg::staging_copy(rs, base, p.head, stream);
     if (copied != JPEGGPU_SUCCESS) return copied;
-    const hipError_t err = jg::launch_resize_oriented(
-        reinterpret_cast<const jg::ResizeJob*>(base), reinterpret_cast<const int*>(base + p.off_first),
-        reinterpret_cast<const int*>(base + p.off_first_t), n, p.h_tiles, p.t_tiles, p.mirror_store, out_w, out_h, layout, p.all_models, dst,
-        stream);
+    const jg::ResizeJob* d_jobs = reinterpret_cast<const jg::ResizeJob*>(base);
+    const int* d_first = reinterpret_cast<const int*>(base + p.off_first);
+    const int* d_first_t = reinterpret_cast<const int*>(base + p.off_first_t);
+    hipError_t err;
+    if (spec) {
+        jg::TensorNorm norm;
+        for (int c = 0; c < 3; ++c) {
+            norm.mean[c] = spec->mean[c];
+            norm.std[c]  = spec->std[c];
+        }
+        err = jg::launch_resize_tensor(d_jobs, d_first, d_first_t, n, p.h_tiles, p.t_tiles, p.mirror_store, out_w, out_h, layout, p.all_models,
+                                       spec->type, norm, dst, stream);
+    } else {
+        err = jg::launch_resize_oriented(d_jobs, d_first, d_first_t, n, p.h_tiles, p.t_tiles, p.mirror_store, out_w, out_h, layout, p.all_models,
+                                         static_cast<uint8_t*>(dst), stream);
+    }
     return err == hipSuccess ? JPEGGPU_SUCCESS : JPEGGPU_INTERNAL_ERROR;
 }
 } // namespace
@@ -790,6 +816,41 @@ enum jpeggpu_status jpeggpu_ext_resize_to_rgb_oriented(
 {
     if (!colors || !orientations) return JPEGGPU_INVALID_ARGUMENT;
     return resize_to_rgb(items, colors, orientations, n, out_w, out_h, filter, layout, dst, d_scratch, scratch_size, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the batched resize as a model's input: flip, ToTensor, Normalize and the cast in the vertical pass (jpeggpu_ext.h)
+// ------------------------------------------------------------------------------------------------
+
+enum jpeggpu_status jpeggpu_ext_resize_to_tensor(
+    const struct jpeggpu_ext_resize_item* items,
+    const enum jpeggpu_ext_color_space* colors,
+    const int* orientations,
+    int n,
+    int out_w,
+    int out_h,
+    enum jpeggpu_ext_filter filter,
+    enum jpeggpu_ext_output_layout layout,
+    const struct jpeggpu_ext_tensor_spec* spec,
+    void* dst,
+    void* d_scratch,
+    size_t scratch_size,
+    jpeggpu_stream_t stream)
+{
+    if (!spec) return JPEGGPU_INVALID_ARGUMENT;
+    const int type = spec->type;
+    if (type != JPEGGPU_EXT_TENSOR_U8 && type != JPEGGPU_EXT_TENSOR_F32 && type != JPEGGPU_EXT_TENSOR_F16 && type != JPEGGPU_EXT_TENSOR_BF16)
+        return JPEGGPU_INVALID_ARGUMENT;
+    jpeggpu_ext_tensor_spec s = *spec;
+    for (int c = 0; c < 3; ++c) {
+        if (type == JPEGGPU_EXT_TENSOR_U8) { // ignored: the kernel is handed values that mean nothing
+            s.mean[c] = 0.0f;
+            s.std[c]  = 1.0f;
+        } else if (!std::isfinite(s.mean[c]) || !std::isfinite(s.std[c]) || s.std[c] == 0.0f) {
+            return JPEGGPU_INVALID_ARGUMENT;
+        }
+    }
+    return resize_to_rgb(items, colors, orientations, n, out_w, out_h, filter, layout, dst, d_scratch, scratch_size, stream, &s);
 }
 
 // ------------------------------------------------------------------------------------------------

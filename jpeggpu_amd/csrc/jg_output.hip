@@ -12,6 +12,9 @@
 //                           resize_h_color_kernel: the horizontal pass of a call that holds items of the other models;
 //                           resize_h_oriented_kernel / resize_t_kernel: the first pass of items whose displayed x runs
 //                           against stored x, or down stored columns (jpeggpu_ext_resize_to_rgb_oriented)
+//   resize_v_tensor_kernel  the vertical pass once more, for a model's input: bytes, float, half or bfloat16 elements,
+//                           normalised as ToTensor + Normalize do, items flipped left to right where asked
+//                           (jpeggpu_ext_resize_to_tensor)
 //   rgb_batch_kernel /      the conversion of MANY images at their own sizes, any model and orientation, from a device table
 //   rgb_batch_transposed_kernel  of items: one launch for orientations 1..4 and one for 5..8, interleaved (HWC) or planar
 //                           (CHW) output (jpeggpu_ext_batch_to_rgb)
@@ -19,7 +22,10 @@
 // Nothing here is shared with the decode path (jg_kernels.hip): the stage reads finished planes.
 #include "jg_output.hpp"
 
+#include <hip/hip_bf16.h>
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 namespace jg {
 
@@ -633,6 +639,179 @@ __global__ __launch_bounds__(256) void resize_v_kernel(const ResizeJob* __restri
 }
 
 // ------------------------------------------------------------------------------------------------
+// The vertical pass that writes a model's input (jpeggpu_ext_resize_to_tensor): resize_v_kernel's tile, taps and clamp,
+// then -- with the lane's twelve finished bytes still in registers -- the flip, the normalisation and the cast, so the
+// batch is written once, as the elements the model reads. The tile body is written again here and not shared with
+// resize_v_kernel: that one is to come out of the compiler as it was (the compile check).
+// ------------------------------------------------------------------------------------------------
+
+/// ToTensor + Normalize of byte u: ((float(u) / 255) - mean) / std. Three binary32 operations, each rounded to nearest
+/// even on its own: no FMA, no reciprocal, no folded scale and bias (those differ from the CPU's result in the last bit
+/// of hundreds of the 3 x 256 values). The division is the correctly rounded one (v_div_scale / v_div_fmas / v_div_fixup).
+__device__ __forceinline__ float tensor_norm(uint32_t u, float mean, float std)
+{
+#pragma clang fp contract(off)
+    return __fdiv_rn(__fsub_rn(__fdiv_rn(static_cast<float>(u), 255.0f), mean), std);
+}
+
+/// The bit pattern of the element of type T made of byte u: the byte itself, tensor_norm's float, or that float converted
+/// ONCE, round to nearest even, to half or bfloat16 (never arithmetic in half precision).
+template <class T>
+__device__ __forceinline__ uint32_t tensor_bits(uint32_t u, float mean, float std)
+{
+    if constexpr (sizeof(T) == 1) {
+        return u;
+    } else {
+        const float v = tensor_norm(u, mean, std);
+        if constexpr (sizeof(T) == 4) {
+            return __float_as_uint(v);
+        } else if constexpr (std::is_same<T, _Float16>::value) {
+            return __builtin_bit_cast(uint16_t, static_cast<_Float16>(v)); // v_cvt_f16_f32 in the default rounding mode
+        } else { // bfloat16: the upper half of the float, rounded to nearest even on the lower half
+            const uint32_t b = __float_as_uint(v);
+            if ((b & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;
+            return (b + 0x7fffu + ((b >> 16) & 1u)) >> 16;
+        }
+    }
+}
+
+/// N elements of S bytes (their bit patterns in e[0 .. N - 1]) as N S / 4 dwords in memory order.
+template <int S, int N>
+__device__ __forceinline__ void tensor_pack(const uint32_t (&e)[N], uint32_t (&d)[N * S / 4])
+{
+    constexpr int per = 4 / S;
+#pragma unroll
+    for (int k = 0; k < N / per; ++k) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int j = 0; j < per; ++j) v |= e[per * k + j] << (8 * S * j);
+        d[k] = v;
+    }
+}
+
+template <int S>
+__device__ __forceinline__ void tensor_store_elem(uint8_t* p, uint32_t bits)
+{
+    if constexpr (S == 1) *p = static_cast<uint8_t>(bits);
+    else if constexpr (S == 2) *reinterpret_cast<uint16_t*>(p) = static_cast<uint16_t>(bits);
+    else *reinterpret_cast<uint32_t*>(p) = bits;
+}
+
+/// Two and four dwords as one value that asks for dword alignment only: global_store_dwordx2 / x4 need no more on gfx950.
+typedef uint32_t TensorDwords2 __attribute__((ext_vector_type(2), aligned(4)));
+typedef uint32_t TensorDwords4 __attribute__((ext_vector_type(4), aligned(4)));
+
+/// A lane's run of N contiguous elements of S bytes at p, of which it has the first `count`. The whole run where p lies on
+/// a dword, as 16-byte stores, then an 8-byte one, then dwords (three of them: the compiler joins them, as in store_rgb4).
+/// Written as vectors and not as dword stores in a row, which for float elements the compiler would take apart again: it
+/// sinks the dword the element path below has in common with them. Branches by 8- and 16-byte alignment in front of the
+/// wider stores bought nothing: the target's alignment rule is the dword, and the compiler sank their common dwords too.
+/// Element by element otherwise.
+template <int S, int N>
+__device__ __forceinline__ void tensor_store_run(uint8_t* p, const uint32_t (&e)[N], int count)
+{
+    constexpr int ND = N * S / 4;
+    if (count == N && (reinterpret_cast<uintptr_t>(p) & 3) == 0) {
+        uint32_t d[ND];
+        tensor_pack<S, N>(e, d);
+        uint32_t* q = reinterpret_cast<uint32_t*>(p);
+        int k = 0;
+#pragma unroll
+        for (; k + 4 <= ND; k += 4) *reinterpret_cast<TensorDwords4*>(q + k) = TensorDwords4{d[k], d[k + 1], d[k + 2], d[k + 3]};
+        if (k + 2 == ND) *reinterpret_cast<TensorDwords2*>(q + k) = TensorDwords2{d[k], d[k + 1]};
+        else
+#pragma unroll
+            for (; k < ND; ++k) q[k] = d[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; ++k)
+            if (k < count) tensor_store_elem<S>(p + k * S, e[k]);
+    }
+}
+
+/// Batched resize, pass 2 for a tensor: resize_v_kernel's tile (kResizeVTileW x kResizeVTileH output pixels per workgroup,
+/// 4 consecutive pixels of one row per lane, one item per blockIdx.y), its taps over `mid` and its clamp. What differs:
+///   * an item with kResizeFlipOutput reads `mid` mirrored: output column x is column out_w - 1 - x of the unflipped
+///     result (torch.flip AFTER the resize, not a resize of the mirrored source -- mirror_taps says why those differ).
+///     The lane's 12 bytes then start at 3 (out_w - 4 - x), on a dword only if out_w % 4 == 0: three dword loads then,
+///     and the four pixels change places in registers; for other widths every lane of a flipped item loads bytes, as
+///     the last lane of a row with fewer than four pixels always does.
+///   * the twelve bytes become elements of T (tensor_bits) and go out as whole runs (tensor_store_run): NHWC the lane's 12
+///     contiguous elements (12, 24 or 48 bytes), NCHW (kPlanar) four elements per channel plane (4, 8 or 16 bytes, one
+///     store); per element where the lane has fewer than four pixels or the address is not on a dword. `dst` is aligned
+///     to the element only and rows are unpadded, so for bytes and halves with out_w % 4 != 0 most rows go out per element.
+template <class T, bool kPlanar>
+__global__ __launch_bounds__(256) void resize_v_tensor_kernel(const ResizeJob* __restrict__ jobs, int out_w, int out_h, TensorNorm nm, T* __restrict__ dst)
+{
+    constexpr int S = sizeof(T);
+    const ResizeJob& J = jobs[blockIdx.y];
+    const int col_tiles = (out_w + kResizeVTileW - 1) / kResizeVTileW;
+    const int t = threadIdx.x;
+    const int x = (blockIdx.x % col_tiles) * kResizeVTileW + 4 * (t & 63);
+    const int y = (blockIdx.x / col_tiles) * kResizeVTileH + (t >> 6);
+    if (x >= out_w || y >= out_h) return;
+    const int* __restrict__ tab = J.tab_y;
+    const int f = tab[2 * y] - J.row0, cnt = tab[2 * y + 1];
+    const int* __restrict__ wts = tab + 2 * out_h + static_cast<size_t>(y) * J.taps_y;
+    const int np = min(4, out_w - x); // pixels of this lane
+    const bool flip = (J.pad_ & kResizeFlipOutput) != 0;
+    const bool dwords = np == 4 && (!flip || (out_w & 3) == 0);
+    // dwords: the lane's four mid columns start at c0, ascending; bytes: output pixel i is mid column c0 + i or c0 - i
+    const int c0 = !flip ? x : dwords ? out_w - 4 - x : out_w - 1 - x;
+    const int step = flip ? -3 : 3;
+    int acc[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) acc[k] = 0;
+    for (int j = 0; j < cnt; ++j) {
+        const int w = wts[j];
+        const uint8_t* s = J.mid + static_cast<size_t>(f + j) * J.mid_pitch + 3 * c0; // dwords: 4-byte aligned, mid_pitch % 16 == 0
+        if (dwords) {
+            const uint32_t* s4 = reinterpret_cast<const uint32_t*>(s);
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                const uint32_t v = s4[d];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[4 * d + k] += mul24(w, static_cast<int>((v >> (8 * k)) & 255u));
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (i < np) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) acc[3 * i + c] += mul24(w, static_cast<int>(s[step * i + c]));
+                }
+            }
+        }
+    }
+    if (flip && dwords) { // the dword loads took the pixels in mid's order: 0 <-> 3, 1 <-> 2 (swaps of values: a selected INDEX
+                          // into acc would be a runtime index into registers)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int a0 = acc[c], a1 = acc[3 + c];
+            acc[c]     = acc[9 + c];
+            acc[3 + c] = acc[6 + c];
+            acc[6 + c] = a1;
+            acc[9 + c] = a0;
+        }
+    }
+    uint32_t e[12];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) e[3 * i + c] = tensor_bits<T>(clamp255((acc[3 * i + c] + (1 << 21)) >> 22), nm.mean[c], nm.std[c]);
+    const size_t item = blockIdx.y;
+    if constexpr (!kPlanar) {
+        tensor_store_run<S, 12>(reinterpret_cast<uint8_t*>(dst + ((item * out_h + y) * out_w + x) * 3), e, 3 * np);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const uint32_t ec[4] = {e[c], e[3 + c], e[6 + c], e[9 + c]};
+            tensor_store_run<S, 4>(reinterpret_cast<uint8_t*>(dst + ((item * 3 + c) * out_h + y) * out_w + x), ec, np);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Batched conversion at the items' own sizes (jpeggpu_ext_batch_to_rgb): the tiles of fancy_mirrored_tile and
 // fancy_transposed_tile over a device table of items, the way the resize passes find theirs. The tile bodies are written
 // again here, on fancy_stage / fancy_pixel / store_rgb4, and not shared with the per-image kernels above: those are to come
@@ -886,12 +1065,13 @@ hipError_t launch_rgbi_oriented(const FancySource& src, int orientation, uint8_t
     return hipGetLastError();
 }
 
-hipError_t launch_resize_oriented(
-    const ResizeJob* d_jobs, const int* d_first_tile, const int* d_first_tile_t, int n, int h_tiles, int t_tiles, bool mirror_store,
-    int out_w, int out_h, int layout, bool all_models, uint8_t* dst, hipStream_t stream)
+namespace {
+/// The first pass of a call with orientations: the horizontal pass of its items of 1..4 (the instantiation that knows
+/// kResizeMirrorStore only where an item carries it) and the transposing pass of its items of 5..8.
+void launch_resize_first(
+    const ResizeJob* d_jobs, const int* d_first_tile, const int* d_first_tile_t, int n, int h_tiles, int t_tiles, bool mirror_store, int out_w,
+    bool all_models, hipStream_t stream)
 {
-    if (t_tiles <= 0 && !mirror_store) return launch_resize(d_jobs, d_first_tile, n, h_tiles, out_w, out_h, layout, all_models, dst, stream);
-    if (n <= 0 || out_w <= 0 || out_h <= 0) return hipSuccess;
     if (h_tiles > 0) {
         if (!mirror_store) {
             if (all_models) resize_h_color_kernel<<<h_tiles, 256, 0, stream>>>(d_jobs, d_first_tile, n, out_w);
@@ -903,8 +1083,42 @@ hipError_t launch_resize_oriented(
         if (all_models) resize_t_kernel<true><<<t_tiles, 256, 0, stream>>>(d_jobs, d_first_tile_t, n, out_w);
         else resize_t_kernel<false><<<t_tiles, 256, 0, stream>>>(d_jobs, d_first_tile_t, n, out_w);
     }
+}
+
+template <class T>
+void launch_resize_v_tensor(const ResizeJob* d_jobs, int n, int out_w, int out_h, int layout, const TensorNorm& norm, void* dst, hipStream_t stream)
+{
+    const int v_tiles = ((out_w + kResizeVTileW - 1) / kResizeVTileW) * ((out_h + kResizeVTileH - 1) / kResizeVTileH);
+    if (layout == 0) resize_v_tensor_kernel<T, false><<<dim3(v_tiles, n), 256, 0, stream>>>(d_jobs, out_w, out_h, norm, static_cast<T*>(dst));
+    else resize_v_tensor_kernel<T, true><<<dim3(v_tiles, n), 256, 0, stream>>>(d_jobs, out_w, out_h, norm, static_cast<T*>(dst));
+}
+} // namespace
+
+hipError_t launch_resize_oriented(
+    const ResizeJob* d_jobs, const int* d_first_tile, const int* d_first_tile_t, int n, int h_tiles, int t_tiles, bool mirror_store,
+    int out_w, int out_h, int layout, bool all_models, uint8_t* dst, hipStream_t stream)
+{
+    if (t_tiles <= 0 && !mirror_store) return launch_resize(d_jobs, d_first_tile, n, h_tiles, out_w, out_h, layout, all_models, dst, stream);
+    if (n <= 0 || out_w <= 0 || out_h <= 0) return hipSuccess;
+    launch_resize_first(d_jobs, d_first_tile, d_first_tile_t, n, h_tiles, t_tiles, mirror_store, out_w, all_models, stream);
     const int v_tiles = ((out_w + kResizeVTileW - 1) / kResizeVTileW) * ((out_h + kResizeVTileH - 1) / kResizeVTileH);
     resize_v_kernel<<<dim3(v_tiles, n), 256, 0, stream>>>(d_jobs, out_w, out_h, layout, dst);
+    return hipGetLastError();
+}
+
+hipError_t launch_resize_tensor(
+    const ResizeJob* d_jobs, const int* d_first_tile, const int* d_first_tile_t, int n, int h_tiles, int t_tiles, bool mirror_store,
+    int out_w, int out_h, int layout, bool all_models, int type, const TensorNorm& norm, void* dst, hipStream_t stream)
+{
+    if (n <= 0 || out_w <= 0 || out_h <= 0) return hipSuccess;
+    if (type != kTensorU8 && type != kTensorF32 && type != kTensorF16 && type != kTensorBF16) return hipErrorInvalidValue;
+    launch_resize_first(d_jobs, d_first_tile, d_first_tile_t, n, h_tiles, t_tiles, mirror_store, out_w, all_models, stream);
+    switch (type) {
+    case kTensorU8: launch_resize_v_tensor<uint8_t>(d_jobs, n, out_w, out_h, layout, norm, dst, stream); break;
+    case kTensorF32: launch_resize_v_tensor<float>(d_jobs, n, out_w, out_h, layout, norm, dst, stream); break;
+    case kTensorF16: launch_resize_v_tensor<_Float16>(d_jobs, n, out_w, out_h, layout, norm, dst, stream); break;
+    default: launch_resize_v_tensor<__hip_bfloat16>(d_jobs, n, out_w, out_h, layout, norm, dst, stream); break;
+    }
     return hipGetLastError();
 }
 

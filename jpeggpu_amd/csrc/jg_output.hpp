@@ -95,12 +95,16 @@ struct ResizeJob {
     const int* tab_y;          // out_h rows
     uint8_t* mid;              // rows x out_w RGB of the horizontal pass, rows mid_pitch bytes apart
     int mid_pitch;             // a multiple of 16
-    int pad_;                  // oriented calls: kResizeMirrorStore
+    int pad_;                  // flags: kResizeMirrorStore (oriented calls), kResizeFlipOutput (tensor calls)
 };
 /// ResizeJob::pad_ of an item of launch_resize_oriented whose displayed x runs against stored x (orientations 2 and 3):
 /// tab_x is in stored order -- column out_w - 1 - ox of the displayed table, its taps reversed -- and the horizontal pass
 /// writes table column ox' to mid column out_w - 1 - ox'.
 constexpr int kResizeMirrorStore = 1;
+/// ResizeJob::pad_ of an item of launch_resize_tensor whose RESULT is flipped left to right: output column x is column
+/// out_w - 1 - x of the unflipped result. Only the tensor pass reads it (mirrored columns of `mid`); the first passes
+/// test kResizeMirrorStore alone, so tables, `mid` and orientations are what they are without the flag.
+constexpr int kResizeFlipOutput = 2;
 constexpr int kResizeHTileW = 32, kResizeHTileH = 8; // horizontal pass: output columns x rows per workgroup
 constexpr int kResizeVTileW = 256, kResizeVTileH = 4; // vertical pass: output pixels x rows per workgroup
 /// Horizontal-pass workgroups of one item.
@@ -132,6 +136,21 @@ inline int resize_t_tiles(int rows, int out_w)
 hipError_t launch_resize_oriented(
     const ResizeJob* d_jobs, const int* d_first_tile, const int* d_first_tile_t, int n, int h_tiles, int t_tiles, bool mirror_store,
     int out_w, int out_h, int layout, bool all_models, uint8_t* dst, hipStream_t stream);
+
+/// The element of launch_resize_tensor's output (the values of enum jpeggpu_ext_tensor_type) and its size in bytes.
+enum TensorType : int { kTensorU8 = 0, kTensorF32 = 1, kTensorF16 = 2, kTensorBF16 = 3 };
+inline int tensor_elem_size(int type) { return type == kTensorU8 ? 1 : type == kTensorF32 ? 4 : 2; }
+/// What the tensor pass does to byte u of channel c for the float types: ((float(u) / 255) - mean[c]) / std[c], each
+/// operation a binary32 one rounded to nearest even on its own (jpeggpu_ext.h has the contract). Passed by value.
+struct TensorNorm {
+    float mean[3], std[3];
+};
+/// launch_resize_oriented with another vertical pass: the first-pass launches are exactly that call's, then
+/// resize_v_tensor_kernel writes elements of `type` (a TensorType) to `dst` (aligned to the element), normalised by `norm`
+/// unless they are bytes, items with kResizeFlipOutput flipped left to right. At most three launches, two without items of 5..8.
+hipError_t launch_resize_tensor(
+    const ResizeJob* d_jobs, const int* d_first_tile, const int* d_first_tile_t, int n, int h_tiles, int t_tiles, bool mirror_store,
+    int out_w, int out_h, int layout, bool all_models, int type, const TensorNorm& norm, void* dst, hipStream_t stream);
 
 /// One item of a batched conversion (launch_rgb_batch), in device memory: a source rectangle written at its own size
 /// where `flips` and the kernel that takes it display it. Interleaved (HWC): R, G, B of displayed pixel (x, y) at
