@@ -34,6 +34,8 @@
  *   jpeggpu_ext_get_progressive_info   on the device into coefficient buffers and handed to the IDCT stage
  *   jpeggpu_ext_resize_to_tensor       the batched resize written as a model's input: uint8, float32, float16 or bfloat16,
  *                                      normalised as ToTensor + Normalize do, items flipped left to right where asked
+ *   jpeggpu_ext_resize_view_to_tensor  the evaluation transform: a window of the resize of each item's WHOLE image, zero
+ *                                      outside it -- torchvision's Resize + CenterCrop on Pillow, from a cropped decode
  */
 #ifndef JPEGGPU_JPEGGPU_EXT_H_
 #define JPEGGPU_JPEGGPU_EXT_H_
@@ -432,7 +434,8 @@ enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_replicate(
     int dst_pitch,
     jpeggpu_stream_t stream);
 
-/* Batched resize to one size (a training pipeline's Resize + CenterCrop or RandomResizedCrop): each item's RGB -- what
+/* Batched resize to one size (a training pipeline's RandomResizedCrop, or a Resize of whole images; Resize + CenterCrop
+ * is jpeggpu_ext_resize_view_to_tensor further down): each item's RGB -- what
  * jpeggpu_ext_crop_to_rgbi_fancy makes of a cropped decode's windows, or jpeggpu_ext_planes_to_rgbi_fancy of whole
  * planes -- resampled to out_w x out_h with the arithmetic of Pillow's Image.resize((out_w, out_h), BILINEAR | BICUBIC),
  * into ONE uint8 tensor: n x out_h x out_w x 3 (JPEGGPU_EXT_NHWC) or n x 3 x out_h x out_w (JPEGGPU_EXT_NCHW). On planes
@@ -455,7 +458,8 @@ enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_replicate(
  *     the current device.
  *   - Items of a JPEGGPU_EXT_SCALE_LIBJPEG decode are described by their img_info like any other. The item has no room for
  *     "replicate": an item of that mode at 1/8 with subsampling left gets fancy upsampling here, which is not libjpeg's
- *     output (jpeggpu_ext_get_scale_info: fancy_upsampling == 0); decode such an image at 1/4 instead.
+ *     output (jpeggpu_ext_get_scale_info: fancy_upsampling == 0); decode such an image at 1/4 instead, or use
+ *     jpeggpu_ext_resize_view_to_tensor, whose view has the flag.
  *   - JPEGGPU_NOT_SUPPORTED: a filter other than the two, an item of 2 or 4 components or with non-integral sampling
  *     ratios. JPEGGPU_INVALID_ARGUMENT: NULL pointers, n, out_w or out_h <= 0 (or n > 65535), an unknown layout, an item
  *     whose windows do not hold its rectangle's samples (the checks of jpeggpu_ext_crop_to_rgbi_fancy), scratch_size too
@@ -743,6 +747,96 @@ enum jpeggpu_status jpeggpu_ext_resize_to_tensor(
     void* d_scratch,
     size_t scratch_size,
     jpeggpu_stream_t stream);
+
+/* Resize + CenterCrop (the evaluation transform; torchvision's Resize(s) + CenterCrop(c) on Pillow images): the batched
+ * resize above, generalised from "the item's rectangle resized to out_w x out_h" to "the out_w x out_h window at (x, y) of
+ * the resize of the item's WHOLE image to resized_w x resized_h" -- each item with its own resized size and window, all
+ * in the same two (with items of orientations 5..8: three) launches, by the same kernels: only the weight tables differ.
+ * jpeggpu_ext_resize_view_to_tensor is jpeggpu_ext_resize_to_tensor with views[i] per item: `items`, `colors`,
+ * `orientations` (either may be NULL as there), `spec` (JPEGGPU_EXT_TENSOR_U8 gives the bytes), `dst`, the scratch, the
+ * staging ring and the statuses and their order are that call's. jpeggpu_ext_resize_view_scratch_size is its size call (0
+ * for arguments the call would refuse, a NULL `views` among them).
+ *   - The whole image of item i is the image's extent by its planes when `crop` is NULL, otherwise the full plane size of
+ *     a component with the largest factors (crop->full_x / full_y): the image at the decoder's scale. It is turned for
+ *     orientations 5..8: resized_w, resized_h, x and y are in DISPLAYED pixels.
+ *   - A window pixel inside the resized image is Pillow's Image.resize((resized_w, resized_h), filter) pixel of the whole
+ *     displayed image, by the arithmetic stated at jpeggpu_ext_resize_to_rgb with in = the whole image's size and out =
+ *     the resized size -- the taps are NOT clamped at the item's rectangle. A pixel outside it (x or y negative, or the
+ *     window reaching beyond resized_w / resized_h: CenterCrop's padding of an image smaller than the crop) is byte 0 in
+ *     all three channels, which a float type carries through ((0 / 255) - mean) / std like any other byte.
+ *   - The item's rectangle (the whole image, or the crop of a cropped decode) must hold every source pixel the window's
+ *     taps read, else JPEGGPU_INVALID_ARGUMENT. jpeggpu_ext_resize_view_rect (host only, pure) returns exactly that
+ *     rectangle in STORED coordinates for a stored full_w x full_h image: the union of the column and row tap ranges of
+ *     the window's coordinates, mapped as jpeggpu_ext_orient_rect maps -- pass it to jpeggpu_ext_set_crop and only that part
+ *     of the file is decoded. Any rectangle that contains it will do.
+ *   - `replicate`: libjpeg replicates this item's chroma instead of fancy upsampling (an image of
+ *     JPEGGPU_EXT_SCALE_LIBJPEG at 1/8 with subsampling left: jpeggpu_ext_get_scale_info's fancy_upsampling == 0), so such
+ *     items are taken here and equal Pillow after draft().
+ *   - The view {out_w, out_h, 0, 0, 0} of an item that is a whole image is jpeggpu_ext_resize_to_tensor's result byte for
+ *     byte, from the same plan, scratch layout and launches.
+ *   - JPEGGPU_INVALID_ARGUMENT besides what jpeggpu_ext_resize_to_tensor refuses: `views` NULL, resized_w or resized_h <=
+ *     0, a window that overlaps no pixel of the resized image, a rectangle that does not hold the taps' pixels or does not
+ *     lie in the whole image. The view's checks follow the item's own; every check is made before anything is staged or
+ *     enqueued, and on an error nothing is written.
+ * jpeggpu_ext_resize_view_weights (host only) is the table the kernels get for output coordinates x0 .. x0 + count_out - 1
+ * of `in` -> `resized`: jpeggpu_ext_resize_weights' rows for the coordinates inside [0, resized), `first` minus `origin`
+ * (the rectangle's first sample; it is not checked against any extent); a coordinate outside gets count 0, weights 0 and
+ * a `first` that keeps first and first + count from decreasing along the table, which the horizontal pass relies on: in
+ * front of the image the `first` of the first entry with taps, behind it first + count of the last (0 if no entry has
+ * taps). JPEGGPU_INVALID_ARGUMENT for NULL pointers, in, resized or count_out <= 0 or max_taps below what
+ * jpeggpu_ext_resize_weights asks for in -> resized; JPEGGPU_NOT_SUPPORTED for another filter. */
+struct jpeggpu_ext_resize_view {
+    int resized_w, resized_h;  /* what Image.resize is asked for, of the item's WHOLE displayed image at its scale */
+    int x, y;                  /* the window's top-left corner in that resized image; may be negative (padding) */
+    int replicate;             /* libjpeg replicates this item's chroma (scale_info.fancy_upsampling == 0) */
+};
+size_t jpeggpu_ext_resize_view_scratch_size(
+    const struct jpeggpu_ext_resize_item* items,
+    const enum jpeggpu_ext_color_space* colors, /* NULL: by the component count */
+    const int* orientations,                    /* NULL: all 1 */
+    const struct jpeggpu_ext_resize_view* views,
+    int n,
+    int out_w,
+    int out_h,
+    enum jpeggpu_ext_filter filter);
+enum jpeggpu_status jpeggpu_ext_resize_view_to_tensor(
+    const struct jpeggpu_ext_resize_item* items,
+    const enum jpeggpu_ext_color_space* colors, /* NULL: by the component count */
+    const int* orientations,                    /* NULL: all 1 */
+    const struct jpeggpu_ext_resize_view* views,
+    int n,
+    int out_w,
+    int out_h,
+    enum jpeggpu_ext_filter filter,
+    enum jpeggpu_ext_output_layout layout,
+    const struct jpeggpu_ext_tensor_spec* spec,
+    void* dst,
+    void* d_scratch,
+    size_t scratch_size,
+    jpeggpu_stream_t stream);
+enum jpeggpu_status jpeggpu_ext_resize_view_rect(
+    int full_w, /* the STORED image at its scale */
+    int full_h,
+    int orientation,
+    const struct jpeggpu_ext_resize_view* view,
+    int out_w,
+    int out_h,
+    enum jpeggpu_ext_filter filter,
+    int* x,
+    int* y,
+    int* w,
+    int* h);
+enum jpeggpu_status jpeggpu_ext_resize_view_weights(
+    int in,
+    int resized,
+    int x0,
+    int count_out,
+    int origin,
+    enum jpeggpu_ext_filter filter,
+    int* first,
+    int* count,
+    int* weights,
+    int max_taps);
 
 /* Batched conversion to RGB (a list of files in, a list of RGB images out, each at its own size -- a validation loader,
  * or torchvision.io.decode_jpeg on a list): what jpeggpu_ext_crop_to_rgbi_oriented makes of every item with a `crop`, and

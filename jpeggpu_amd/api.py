@@ -117,6 +117,12 @@ class TensorSpec(C.Structure):
     _fields_ = [("type", C.c_int), ("mean", C.c_float * 3), ("std", C.c_float * 3), ("flips", C.POINTER(C.c_ubyte))]
 
 
+class ResizeView(C.Structure):
+    """struct jpeggpu_ext_resize_view: the size an item's WHOLE displayed image is resized to, the window's corner in that
+    resized image (negative: zero padding), and whether libjpeg replicates the item's chroma."""
+    _fields_ = [("resized_w", C.c_int), ("resized_h", C.c_int), ("x", C.c_int), ("y", C.c_int), ("replicate", C.c_int)]
+
+
 class RgbItem(C.Structure):
     """struct jpeggpu_ext_rgb_item: a decoded image's info, crop (NULL: the whole image) and planes, its colour model, EXIF
     orientation and whether libjpeg replicates its chroma, and where its displayed RGB goes."""
@@ -267,6 +273,15 @@ def lib():
     L.jpeggpu_ext_resize_to_tensor.argtypes = [
         C.POINTER(ResizeItem), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(TensorSpec),
         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.jpeggpu_ext_resize_view_scratch_size.restype = C.c_size_t
+    L.jpeggpu_ext_resize_view_scratch_size.argtypes = [
+        C.POINTER(ResizeItem), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(ResizeView), C.c_int, C.c_int, C.c_int, C.c_int]
+    L.jpeggpu_ext_resize_view_to_tensor.argtypes = [
+        C.POINTER(ResizeItem), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(ResizeView), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+        C.POINTER(TensorSpec), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.jpeggpu_ext_resize_view_rect.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(ResizeView), C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4
+    L.jpeggpu_ext_resize_view_weights.argtypes = [
+        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
     L.jpeggpu_ext_batch_rgb_scratch_size.restype = C.c_size_t
     L.jpeggpu_ext_batch_rgb_scratch_size.argtypes = [C.c_int]
     L.jpeggpu_ext_batch_to_rgb.argtypes = [C.POINTER(RgbItem), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -1020,6 +1035,194 @@ def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", devi
                 dtype = torch.uint8 if mean is None and std is None else torch.float32
             out = resize_to_tensor(planes_list, infos, size, cis, filt, layout, colors=colors, orientations=orients if exif_transpose else None,
                                    dtype=dtype, mean=mean, std=std, flips=flips)
+        torch.cuda.synchronize(dev)
+        batch.destroy()
+        return out
+    finally:
+        for dec in decs:
+            dec.cleanup()
+
+
+def resized_size(w, h, size):
+    """torchvision's Resize(size) of a w x h image, as (resized_w, resized_h): an int makes the shorter side `size` and the
+    longer one int(size * long / short) (true division, truncated); a pair is (height, width) and used as given. Pure
+    Python. (500, 375, 256) -> (341, 256); (640, 227, 256) -> (721, 256)."""
+    if not isinstance(size, int):
+        rh, rw = size
+        return int(rw), int(rh)
+    if w < 1 or h < 1 or size < 1:
+        raise ValueError("sizes must be positive")
+    short, long = (w, h) if w <= h else (h, w)
+    new_long = int(size * long / short)
+    return (size, new_long) if w <= h else (new_long, size)
+
+
+def center_crop_window(rw, rh, crop):
+    """torchvision's CenterCrop(crop) of an rw x rh image, as the window's corner (x, y) in it (`crop`: int, or (height,
+    width)): int(round((rw - cw) / 2.0)) -- Python's round, half to even -- where the image is at least the crop; where it
+    is smaller it is padded with (cw - rw) // 2 zero columns on the left (and (cw - rw + 1) // 2 on the right), so
+    x = -((cw - rw) // 2). The same for y. Pure Python."""
+    ch, cw = _size_hw(crop)
+
+    def corner(r, c):
+        return int(round((r - c) / 2.0)) if c <= r else -((c - r) // 2)
+
+    return corner(rw, cw), corner(rh, ch)
+
+
+def _view_struct(view, replicate=False):
+    rw, rh, x, y = (int(v) for v in view)
+    return ResizeView(rw, rh, x, y, int(bool(replicate)))
+
+
+def resize_view_rect(w, h, view, out_size, filt="bilinear", orientation=1):
+    """jpeggpu_ext_resize_view_rect (host only): the STORED rectangle (x, y, w, h) of a stored w x h image whose pixels the
+    window `view` = (resized_w, resized_h, x, y) of `out_size` (int: square; (h, w)) reads -- the view is in displayed
+    pixels of `orientation`. What Decoder.set_crop takes so that only that part is decoded."""
+    if filt not in FILTERS:
+        raise ValueError("filter %r is not one of %s" % (filt, ", ".join(FILTERS)))
+    oh, ow = _size_hw(out_size)
+    v = [C.c_int() for _ in range(4)]
+    vs = _view_struct(view)
+    _check(lib().jpeggpu_ext_resize_view_rect(int(w), int(h), int(orientation), C.byref(vs), ow, oh, FILTERS[filt], *[C.byref(a) for a in v]),
+           "jpeggpu_ext_resize_view_rect")
+    return tuple(a.value for a in v)
+
+
+def resize_view_weights(in_size, resized, x0, count_out, origin=0, filt="bilinear"):
+    """jpeggpu_ext_resize_view_weights (host only): the table the kernels get for output coordinates x0 .. x0 + count_out - 1
+    of in_size -> resized, `first` relative to `origin`, as numpy int32 (first[count_out], count[count_out],
+    weights[count_out, max_taps]); coordinates outside [0, resized) have count 0."""
+    import numpy as np
+
+    if filt not in FILTERS:
+        raise ValueError("filter %r is not one of %s" % (filt, ", ".join(FILTERS)))
+    k = resize_max_taps(in_size, resized, filt)
+    m = max(int(count_out), 1)
+    first, count, w = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros((m, k), np.int32)
+    ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+    _check(lib().jpeggpu_ext_resize_view_weights(int(in_size), int(resized), int(x0), int(count_out), int(origin), FILTERS[filt], ptr(first),
+                                                 ptr(count), ptr(w), k), "jpeggpu_ext_resize_view_weights")
+    return first, count, w
+
+
+def resize_views_to_tensor(planes_list, infos, views, size, crop_infos=None, filt="bilinear", layout="NHWC", colors=None, orientations=None,
+                           replicates=None, dtype=None, mean=None, std=None, flips=None, out=None):
+    """jpeggpu_ext_resize_view_to_tensor on torch's current stream: resize_to_tensor where image i contributes not its
+    rectangle resized to `size` but the `size` window at (x, y) of the resize of its WHOLE displayed image to resized_w x
+    resized_h -- views[i] = (resized_w, resized_h, x, y), from resized_size and center_crop_window: torchvision's Resize +
+    CenterCrop on Pillow. Pixels of the window outside the resized image are byte 0 (normalised like any byte).
+    crop_infos[i], if given, must hold what resize_view_rect returns for the view. `replicates`: where libjpeg replicates
+    instead of fancy upsampling (1/8 in the libjpeg scale mode with subsampling left); None: nowhere. `dtype` defaults to
+    torch.uint8 unless `mean` or `std` is given (then float32); everything else as in resize_to_tensor."""
+    import torch
+
+    if filt not in FILTERS:
+        raise ValueError("filter %r is not one of %s" % (filt, ", ".join(FILTERS)))
+    if layout not in LAYOUTS:
+        raise ValueError("layout %r is not one of %s" % (layout, ", ".join(LAYOUTS)))
+    if dtype is None:
+        dtype = torch.uint8 if mean is None and std is None else torch.float32
+    if dtype not in TENSOR_TYPES:
+        raise ValueError("dtype %r is not one of %s" % (dtype, ", ".join(TENSOR_TYPE_NAMES)))
+    h, w = _size_hw(size)
+    n = len(planes_list)
+    for name, v in (("infos", infos), ("views", views), ("crop_infos", crop_infos), ("colors", colors), ("orientations", orientations),
+                    ("replicates", replicates), ("flips", flips)):
+        if v is not None and len(v) != n:
+            raise ValueError("%s must have one entry per image" % name)
+    device = planes_list[0][0].device
+    items, _keep = _resize_items(planes_list, infos, crop_infos)
+    vs = (ResizeView * n)(*[_view_struct(views[i], replicates[i] if replicates is not None else False) for i in range(n)])
+    spec = TensorSpec()
+    spec.type = TENSOR_TYPES[dtype]
+    spec.mean[:] = _channel_triple(mean, 0.0, "mean")
+    spec.std[:] = _channel_triple(std, 1.0, "std")
+    flip_bytes = None
+    if flips is not None:
+        flip_bytes = (C.c_ubyte * n)(*[1 if f else 0 for f in flips])
+        spec.flips = C.cast(flip_bytes, C.POINTER(C.c_ubyte))
+    shape = (n, h, w, 3) if layout == "NHWC" else (n, 3, h, w)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=device)
+    elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous():
+        raise ValueError("out must be a contiguous %s tensor of shape %s" % (dtype, shape))
+    cs = _color_array(colors, n) if colors is not None else None
+    os_ = _color_array(orientations, n) if orientations is not None else None
+    need = lib().jpeggpu_ext_resize_view_scratch_size(items, cs, os_, vs, n, w, h, FILTERS[filt])
+    scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    _check(lib().jpeggpu_ext_resize_view_to_tensor(items, cs, os_, vs, n, w, h, FILTERS[filt], LAYOUTS[layout], C.byref(spec), out.data_ptr(),
+                                                   scratch.data_ptr(), need, torch.cuda.current_stream(device).cuda_stream),
+           "jpeggpu_ext_resize_view_to_tensor")
+    # the scratch tensor is freed by torch's caching allocator in stream order: it is not reused before the launches ran
+    return out
+
+
+def decode_center_cropped(datas, resize=256, crop=224, filt="bilinear", layout="NHWC", device="cuda:0", scales=None, exif_transpose=False,
+                          dtype=None, mean=None, std=None):
+    """An evaluation pipeline's decode: torchvision's Resize(resize) + CenterCrop(crop) (+ ToTensor + Normalize with `dtype`,
+    `mean`, `std` as in decode_resized) of every JPEG of `datas`, equal to Pillow's
+    Image.open(f).convert("RGB").resize((rw, rh), filter) cropped (or zero-padded, where the resized image is smaller than
+    the crop) to the centre window, with (rw, rh) = resized_size and the window from center_crop_window -- in ONE
+    jpeggpu_ext_decode_batch call and ONE jpeggpu_ext_resize_view_to_tensor call, however the images' sizes differ. Only the
+    rectangle of each file that the window's taps read is decoded (resize_view_rect). `resize`: int (the shorter side) or
+    (h, w); `crop`: int or (h, w). `scales[i]` in 1, 2, 4, 8: image i is decoded at that scale as libjpeg-turbo does
+    (draft_scale gives Pillow's choice) and the resized size is computed from its size at that scale; 1/8 with subsampling
+    left is taken (libjpeg's replication). `exif_transpose`: the transform runs on the displayed image
+    (ImageOps.exif_transpose after draft()). Files of every colour model and progressive files are taken. Returns n x ch x
+    cw x 3 ("NHWC") or n x 3 x ch x cw ("NCHW"), uint8 unless `dtype`, `mean` or `std` says otherwise."""
+    import torch
+
+    dev = torch.device(device)
+    n = len(datas)
+    scales = [1] * n if scales is None else [int(s) for s in scales]
+    if len(scales) != n or any(s not in (1, 2, 4, 8) for s in scales):
+        raise ValueError("scales must have one entry of 1, 2, 4 or 8 per image")
+    if n == 0:
+        raise ValueError("datas is empty")
+    ch, cw = _size_hw(crop)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    decs, entries, planes_list, infos, cis, keep, colors, orients, views, reps = [], [], [], [], [], [], [], [], [], []
+    try:
+        scans = 0
+        for data, scale in zip(datas, scales):
+            dec = Decoder()
+            decs.append(dec)
+            dec.set_batch_hint(n)
+            dec.set_idct("islow")
+            dec.set_progressive(True)
+            if scale != 1:
+                dec.set_scale(scale)
+                dec.set_scale_mode("libjpeg")
+            w0, h0 = _frame_size(dec.parse_header(data))  # the header once, for the size at the scale and the orientation
+            o = dec.orientation() if exif_transpose else 1
+            dw, dh = orient_size(o, w0, h0)
+            rw, rh = resized_size(dw, dh, resize)
+            view = (rw, rh) + center_crop_window(rw, rh, (ch, cw))
+            dec.set_crop(*resize_view_rect(w0, h0, view, (ch, cw), filt, o))
+            info = dec.parse_header(data)
+            orients.append(o)
+            views.append(view)
+            reps.append(_needs_replication(info, scale))
+            scans += dec.layout().num_scans
+            nb = dec.get_buffer_size()
+            tmp = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
+            base = (tmp.data_ptr() + 255) // 256 * 256
+            planes = [torch.empty((info.sizes_y[c], info.sizes_x[c]), dtype=torch.uint8, device=dev)
+                      for c in range(info.num_components)]
+            dec.transfer(base, nb, stream)
+            keep.append(tmp)
+            entries.append((dec, [p.data_ptr() for p in planes], [p.stride(0) for p in planes], base, nb))
+            planes_list.append(planes)
+            infos.append(info)
+            cis.append(dec.crop_info())
+            colors.append(dec.color_space())
+        batch = Batch(scans)
+        scratch = torch.empty(batch.scratch_size, dtype=torch.uint8, device=dev)
+        batch.set_items(entries)
+        batch.decode(scratch.data_ptr(), stream)
+        out = resize_views_to_tensor(planes_list, infos, views, (ch, cw), cis, filt, layout, colors=colors, orientations=orients,
+                                     replicates=reps, dtype=dtype, mean=mean, std=std)
         torch.cuda.synchronize(dev)
         batch.destroy()
         return out

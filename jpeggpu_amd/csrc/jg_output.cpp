@@ -149,9 +149,10 @@ void resize_bounds(int in, int out, int filter, int x, int* first, int* count)
     *count               = hi - lo;
 }
 
-/// The table of in -> out (in != out) into first / count / w[out][stride], stride >= resize_max_taps; Pillow's
-/// precompute_coeffs + normalize_coeffs_8bpc.
-void resize_table(int in, int out, int filter, int* first, int* count, int* w, int stride)
+/// The table of in -> out (in != out) for output coordinates x0 .. x0 + n_out - 1 into first / count / w[n_out][stride],
+/// stride >= resize_max_taps; Pillow's precompute_coeffs + normalize_coeffs_8bpc. A coordinate outside [0, out) gets no
+/// taps (resize_carry_empty gives its `first` a value). The whole table is x0 = 0, n_out = out.
+void resize_table(int in, int out, int filter, int x0, int n_out, int* first, int* count, int* w, int stride)
 {
 #pragma clang fp contract(off)
     const double scale = static_cast<double>(in) / out;
@@ -159,9 +160,10 @@ void resize_table(int in, int out, int filter, int* first, int* count, int* w, i
     const double ss    = 1.0 / fs;
     const double one   = static_cast<double>(1 << kResizePrecision);
     std::vector<double> k(static_cast<size_t>(stride));
-    for (int x = 0; x < out; ++x) {
+    for (int e = 0; e < n_out; ++e) {
+        const int64_t x = static_cast<int64_t>(x0) + e;
         int lo = 0, n = 0;
-        resize_bounds(in, out, filter, x, &lo, &n);
+        if (x >= 0 && x < out) resize_bounds(in, out, filter, static_cast<int>(x), &lo, &n);
         const double center = (x + 0.5) * scale;
         double sum          = 0.0;
         for (int j = 0; j < n; ++j) {
@@ -170,37 +172,114 @@ void resize_table(int in, int out, int filter, int* first, int* count, int* w, i
         }
         if (sum != 0.0)
             for (int j = 0; j < n; ++j) k[j] /= sum;
-        first[x] = lo;
-        count[x] = n;
-        int* row = w + static_cast<size_t>(x) * stride;
+        first[e] = lo;
+        count[e] = n;
+        int* row = w + static_cast<size_t>(e) * stride;
         for (int j = 0; j < stride; ++j)
             row[j] = j >= n ? 0 : k[j] < 0 ? static_cast<int>(-0.5 + k[j] * one) : static_cast<int>(0.5 + k[j] * one);
     }
 }
 
 /// A direction whose size does not change: one tap of weight 1 (Pillow skips the pass; the result is the same).
-void resize_identity(int size, int* first, int* count, int* w, int stride)
+/// Coordinates x0 .. x0 + n_out - 1 of `size`, those outside [0, size) without a tap.
+void resize_identity(int size, int x0, int n_out, int* first, int* count, int* w, int stride)
 {
-    for (int x = 0; x < size; ++x) {
-        first[x] = x;
-        count[x] = 1;
-        for (int j = 0; j < stride; ++j) w[static_cast<size_t>(x) * stride + j] = j == 0 ? 1 << kResizePrecision : 0;
+    for (int e = 0; e < n_out; ++e) {
+        const int64_t x = static_cast<int64_t>(x0) + e;
+        const bool in = x >= 0 && x < size;
+        first[e] = in ? static_cast<int>(x) : 0;
+        count[e] = in ? 1 : 0;
+        for (int j = 0; j < stride; ++j) w[static_cast<size_t>(e) * stride + j] = in && j == 0 ? 1 << kResizePrecision : 0;
     }
+}
+
+/// Entries without taps (a window's coordinates outside the resized image: padding) keep the kernels' reading of the
+/// table true: resize_h_tile takes a tile's input range from its first entry's `first` and its last entry's
+/// first + count, so an empty entry in front of the image carries the `first` of the first entry with taps, and one
+/// behind it first + count of the last. `first` is then rebased by `origin`. A table without empty entries only has
+/// `origin` subtracted.
+void resize_carry_empty(int* first, const int* count, int n_out, int origin)
+{
+    int a = 0, b = n_out - 1;
+    while (a < n_out && count[a] == 0) ++a;
+    while (b >= 0 && count[b] == 0) --b;
+    for (int e = 0; e < n_out; ++e) {
+        if (a > b) first[e] = 0; // no entry has taps
+        else if (e < a) first[e] = first[a] - origin;
+        else if (e > b) first[e] = first[b] + count[b] - origin;
+    }
+    for (int e = a; e <= b; ++e) first[e] -= origin;
 }
 
 int resize_taps(int in, int out, int filter) { return in == out ? 1 : resize_max_taps(in, out, filter); }
 
 /// Table bytes of one direction: {first, count}[out] + weights[out][taps]
-size_t resize_table_bytes(int in, int out, int filter)
+size_t resize_table_bytes(int out, int taps) { return sizeof(int) * static_cast<size_t>(out) * (2 + static_cast<size_t>(taps)); }
+
+/// One direction of one item, in DISPLAYED pixels: the item's whole image of `full` samples is resized to `resized`, the
+/// output is coordinates x0 .. x0 + out - 1 of that, and the item's rectangle holds samples origin .. origin + extent - 1.
+/// A call without views resizes the rectangle itself: full = extent, resized = out, x0 = origin = 0.
+struct ResizeAxis {
+    int full, resized, x0, origin, extent;
+};
+
+/// Samples [*lo, *hi) of the whole image that the taps of the window's coordinates read; false if no coordinate of the
+/// window lies in the resized image. (first and first + count do not decrease with the coordinate.)
+bool resize_axis_range(const ResizeAxis& a, int out, int filter, int* lo, int* hi)
 {
-    return sizeof(int) * static_cast<size_t>(out) * (2 + static_cast<size_t>(resize_taps(in, out, filter)));
+    const int64_t c0 = std::max<int64_t>(a.x0, 0), c1 = std::min<int64_t>(static_cast<int64_t>(a.x0) + out, a.resized) - 1;
+    if (c0 > c1) return false;
+    if (a.full == a.resized) {
+        *lo = static_cast<int>(c0);
+        *hi = static_cast<int>(c1) + 1;
+        return true;
+    }
+    int f0 = 0, n0 = 0, f1 = 0, n1 = 0;
+    resize_bounds(a.full, a.resized, filter, static_cast<int>(c0), &f0, &n0);
+    resize_bounds(a.full, a.resized, filter, static_cast<int>(c1), &f1, &n1);
+    *lo = f0;
+    *hi = f1 + n1;
+    return true;
+}
+
+/// The table the kernels get for one direction, before any mirroring: {first, count}[out], weights[out][taps] at `t`,
+/// `first` relative to the rectangle.
+void resize_axis_table(const ResizeAxis& a, int out, int taps, int filter, int* t)
+{
+    std::vector<int> first(static_cast<size_t>(out)), cnt(static_cast<size_t>(out));
+    if (a.full == a.resized) resize_identity(a.resized, a.x0, out, first.data(), cnt.data(), t + 2 * out, taps);
+    else resize_table(a.full, a.resized, filter, a.x0, out, first.data(), cnt.data(), t + 2 * out, taps);
+    resize_carry_empty(first.data(), cnt.data(), out, a.origin);
+    for (int x = 0; x < out; ++x) {
+        t[2 * x]     = first[x];
+        t[2 * x + 1] = cnt[x];
+    }
 }
 
 /// One item's checks and its descriptor, without the table and scratch pointers; `in_w` x `in_h` is the rectangle.
-jpeggpu_status resize_item(const jpeggpu_ext_resize_item& it, int color, ResizeJob& job, int& in_w, int& in_h)
+/// `replicate`: libjpeg replicates this item's chroma (a view says so; the calls without views have no room for it).
+jpeggpu_status resize_item(const jpeggpu_ext_resize_item& it, int color, bool replicate, ResizeJob& job, int& in_w, int& in_h)
 {
     job = ResizeJob{};
-    return fancy_source(it.info, color, it.crop, it.src, false, false, job.src, &in_w, &in_h);
+    return fancy_source(it.info, color, it.crop, it.src, replicate, false, job.src, &in_w, &in_h);
+}
+
+/// The item's WHOLE stored image at its scale: the full plane of a component with the largest factors (a cropped decode),
+/// or the rectangle itself, which then is the image. After resize_item has accepted the item.
+void resize_item_full(const jpeggpu_ext_resize_item& it, int in_w, int in_h, int* full_w, int* full_h)
+{
+    *full_w = in_w;
+    *full_h = in_h;
+    if (!it.crop) return;
+    int sx_max = 0, sy_max = 0;
+    for (int c = 0; c < it.info->num_components; ++c) {
+        sx_max = std::max(sx_max, it.info->subsampling.x[c]);
+        sy_max = std::max(sy_max, it.info->subsampling.y[c]);
+    }
+    for (int c = 0; c < it.info->num_components; ++c) {
+        if (it.info->subsampling.x[c] == sx_max) *full_w = it.crop->full_x[c];
+        if (it.info->subsampling.y[c] == sy_max) *full_h = it.crop->full_y[c];
+    }
 }
 
 /// Where everything of one call sits in d_scratch: the descriptors, each item's first tile, the tables (together the
@@ -208,6 +287,7 @@ jpeggpu_status resize_item(const jpeggpu_ext_resize_item& it, int color, ResizeJ
 struct ResizePlan {
     std::vector<ResizeJob> jobs;
     std::vector<int> first_tile, in_w, in_h;
+    std::vector<ResizeAxis> ax, ay; // the two directions of each item, displayed
     std::vector<size_t> off_tab_x, off_tab_y, off_mid;
     size_t off_first = 0, head = 0, total = 0;
     int h_tiles      = 0;
@@ -247,9 +327,11 @@ void reverse_columns(int* t, int out, int taps)
 
 /// `colors`: each item's colour model, or null: by its component count (color_by_count). `orients`: each item's EXIF
 /// orientation, or null: 1 for all -- the plan, the scratch layout and the launches are then what they were without it.
+/// `views`: each item's window of the resize of its whole image (jpeggpu_ext_resize_view_to_tensor), or null: every item's
+/// rectangle is resized to out_w x out_h -- which is the view {out_w, out_h, 0, 0} of an item that is a whole image.
 jpeggpu_status plan_resize(
-    const jpeggpu_ext_resize_item* items, const jpeggpu_ext_color_space* colors, const int* orients, int n, int out_w, int out_h, int filter,
-    ResizePlan& p)
+    const jpeggpu_ext_resize_item* items, const jpeggpu_ext_color_space* colors, const int* orients, const jpeggpu_ext_resize_view* views, int n,
+    int out_w, int out_h, int filter, ResizePlan& p)
 {
     if (!items || n <= 0 || n > 65535 || out_w <= 0 || out_h <= 0) return JPEGGPU_INVALID_ARGUMENT;
     if (filter != JPEGGPU_EXT_FILTER_BILINEAR && filter != JPEGGPU_EXT_FILTER_BICUBIC) return JPEGGPU_NOT_SUPPORTED;
@@ -266,6 +348,8 @@ jpeggpu_status plan_resize(
         p.first_tile.resize(n);
         p.in_w.resize(n);
         p.in_h.resize(n);
+        p.ax.resize(n);
+        p.ay.resize(n);
         p.off_tab_x.resize(n);
         p.off_tab_y.resize(n);
         p.off_mid.resize(n);
@@ -282,30 +366,46 @@ jpeggpu_status plan_resize(
     int64_t tiles  = 0, tiles_t = 0;
     const int pitch = static_cast<int>(align_up(3 * static_cast<size_t>(out_w), 16));
     for (int i = 0; i < n; ++i) {
-        const jpeggpu_status st = resize_item(items[i], colors ? static_cast<int>(colors[i]) : color_by_count(items[i].info), p.jobs[i], p.in_w[i], p.in_h[i]);
+        const jpeggpu_status st = resize_item(items[i], colors ? static_cast<int>(colors[i]) : color_by_count(items[i].info),
+                                              views && views[i].replicate != 0, p.jobs[i], p.in_w[i], p.in_h[i]);
         if (st != JPEGGPU_SUCCESS) return st;
         p.all_models = p.all_models || fancy_all_models(p.jobs[i].src);
         const int o = p.orient[i];
-        if (orient_transposes(o)) std::swap(p.in_w[i], p.in_h[i]); // the displayed rectangle from here on
-        p.off_tab_x[i] = off;
-        off += align_up(resize_table_bytes(p.in_w[i], out_w, filter), 16);
-        p.off_tab_y[i] = off;
-        off += align_up(resize_table_bytes(p.in_h[i], out_h, filter), 16);
-        // the rectangle rows the vertical taps read (all of them when the height does not change)
-        ResizeJob& j = p.jobs[i];
-        j.taps_x     = resize_taps(p.in_w[i], out_w, filter);
-        j.taps_y     = resize_taps(p.in_h[i], out_h, filter);
-        j.mid_pitch  = pitch;
-        if (p.in_h[i] == out_h) {
-            j.row0 = 0;
-            j.rows = out_h;
-        } else {
-            int f0 = 0, n0 = 0, f1 = 0, n1 = 0;
-            resize_bounds(p.in_h[i], out_h, filter, 0, &f0, &n0);
-            resize_bounds(p.in_h[i], out_h, filter, out_h - 1, &f1, &n1);
-            j.row0 = orient_mirrors_y(o) ? p.in_h[i] - (f1 + n1) : f0; // rows of `mid` are in stored order (mirror_taps)
-            j.rows = f1 + n1 - f0;
+        ResizeAxis& ax = p.ax[i];
+        ResizeAxis& ay = p.ay[i];
+        if (views) { // the window of the resize of the whole displayed image; the rectangle lies somewhere in that image
+            const jpeggpu_ext_resize_view& v = views[i];
+            if (v.resized_w <= 0 || v.resized_h <= 0) return JPEGGPU_INVALID_ARGUMENT;
+            int fw = 0, fh = 0, rx = items[i].crop ? items[i].crop->x : 0, ry = items[i].crop ? items[i].crop->y : 0;
+            resize_item_full(items[i], p.in_w[i], p.in_h[i], &fw, &fh);
+            if (static_cast<int64_t>(rx) + p.in_w[i] > fw || static_cast<int64_t>(ry) + p.in_h[i] > fh) return JPEGGPU_INVALID_ARGUMENT;
+            // the stored rectangle in displayed coordinates: jpeggpu_ext_orient_rect's map, the other way
+            const int sx = orient_transposes(o) ? ry : rx, sw = orient_transposes(o) ? p.in_h[i] : p.in_w[i], fx = orient_transposes(o) ? fh : fw;
+            const int sy = orient_transposes(o) ? rx : ry, sh = orient_transposes(o) ? p.in_w[i] : p.in_h[i], fy = orient_transposes(o) ? fw : fh;
+            ax = ResizeAxis{fx, v.resized_w, v.x, orient_mirrors_x(o) ? fx - sx - sw : sx, sw};
+            ay = ResizeAxis{fy, v.resized_h, v.y, orient_mirrors_y(o) ? fy - sy - sh : sy, sh};
         }
+        if (orient_transposes(o)) std::swap(p.in_w[i], p.in_h[i]); // the displayed rectangle from here on
+        if (!views) {
+            ax = ResizeAxis{p.in_w[i], out_w, 0, 0, p.in_w[i]};
+            ay = ResizeAxis{p.in_h[i], out_h, 0, 0, p.in_h[i]};
+        }
+        // the samples the taps read: columns and rows of the displayed image, all of them inside the rectangle
+        int lo_x = 0, hi_x = 0, lo_y = 0, hi_y = 0;
+        if (!resize_axis_range(ax, out_w, filter, &lo_x, &hi_x) || !resize_axis_range(ay, out_h, filter, &lo_y, &hi_y))
+            return JPEGGPU_INVALID_ARGUMENT; // a window beside the resized image
+        if (lo_x < ax.origin || hi_x > ax.origin + ax.extent || lo_y < ay.origin || hi_y > ay.origin + ay.extent) return JPEGGPU_INVALID_ARGUMENT;
+        ResizeJob& j = p.jobs[i];
+        j.taps_x     = resize_taps(ax.full, ax.resized, filter);
+        j.taps_y     = resize_taps(ay.full, ay.resized, filter);
+        j.mid_pitch  = pitch;
+        p.off_tab_x[i] = off;
+        off += align_up(resize_table_bytes(out_w, j.taps_x), 16);
+        p.off_tab_y[i] = off;
+        off += align_up(resize_table_bytes(out_h, j.taps_y), 16);
+        // the rectangle rows the vertical taps read (all of them when the height does not change)
+        j.row0 = orient_mirrors_y(o) ? ay.origin + ay.extent - hi_y : lo_y - ay.origin; // rows of `mid` are in stored order (mirror_taps)
+        j.rows = hi_y - lo_y;
         if (!orient_transposes(o) && orient_mirrors_x(o)) {
             j.pad_         = kResizeMirrorStore;
             p.mirror_store = true;
@@ -575,10 +675,10 @@ enum jpeggpu_status jpeggpu_ext_crop_to_rgbi_replicate(
 namespace {
 size_t resize_scratch_size(
     const struct jpeggpu_ext_resize_item* items, const enum jpeggpu_ext_color_space* colors, const int* orients, int n, int out_w, int out_h,
-    enum jpeggpu_ext_filter filter)
+    enum jpeggpu_ext_filter filter, const struct jpeggpu_ext_resize_view* views = nullptr)
 {
     jg::ResizePlan p;
-    return jg::plan_resize(items, colors, orients, n, out_w, out_h, filter, p) == JPEGGPU_SUCCESS ? p.total : 0;
+    return jg::plan_resize(items, colors, orients, views, n, out_w, out_h, filter, p) == JPEGGPU_SUCCESS ? p.total : 0;
 }
 } // namespace
 
@@ -602,8 +702,8 @@ enum jpeggpu_status jpeggpu_ext_resize_weights(
     if (!first || !count || !weights || in <= 0 || out <= 0 || max_taps < jg::resize_max_taps(in, out, filter))
         return JPEGGPU_INVALID_ARGUMENT;
     try {
-        if (in == out) jg::resize_identity(out, first, count, weights, max_taps);
-        else jg::resize_table(in, out, filter, first, count, weights, max_taps);
+        if (in == out) jg::resize_identity(out, 0, out, first, count, weights, max_taps);
+        else jg::resize_table(in, out, filter, 0, out, first, count, weights, max_taps);
     } catch (const std::bad_alloc&) {
         return JPEGGPU_OUT_OF_HOST_MEMORY;
     }
@@ -620,7 +720,8 @@ static_assert(offsetof(jpeggpu_ext_tensor_spec, type) == 0 && offsetof(jpeggpu_e
               "struct jpeggpu_ext_tensor_spec");
 
 /// `colors` null: each item's model by its component count. `orients` null: orientation 1 for all. `spec` null: uint8
-/// through resize_v_kernel (the jpeggpu_ext_resize_to_rgb* calls); else, checked by the caller, the tensor pass.
+/// through resize_v_kernel (the jpeggpu_ext_resize_to_rgb* calls); else, checked by the caller, the tensor pass. `views`
+/// null: every item's rectangle resized to the output; else each item's window (jpeggpu_ext_resize_view_to_tensor).
 enum jpeggpu_status resize_to_rgb(
     const struct jpeggpu_ext_resize_item* items,
     const enum jpeggpu_ext_color_space* colors,
@@ -634,10 +735,11 @@ enum jpeggpu_status resize_to_rgb(
     void* d_scratch,
     size_t scratch_size,
     jpeggpu_stream_t stream,
-    const struct jpeggpu_ext_tensor_spec* spec = nullptr)
+    const struct jpeggpu_ext_tensor_spec* spec = nullptr,
+    const struct jpeggpu_ext_resize_view* views = nullptr)
 {
     jg::ResizePlan p;
-    const jpeggpu_status st = jg::plan_resize(items, colors, orients, n, out_w, out_h, filter, p);
+    const jpeggpu_status st = jg::plan_resize(items, colors, orients, views, n, out_w, out_h, filter, p);
     if (st != JPEGGPU_SUCCESS) return st;
     if (!dst || !d_scratch || (layout != JPEGGPU_EXT_NHWC && layout != JPEGGPU_EXT_NCHW) || scratch_size < p.total)
         return JPEGGPU_INVALID_ARGUMENT;
@@ -656,18 +758,13 @@ enum jpeggpu_status resize_to_rgb(
             j.tab_x          = reinterpret_cast<const int*>(base + p.off_tab_x[i]);
             j.tab_y          = reinterpret_cast<const int*>(base + p.off_tab_y[i]);
             j.mid            = base + p.off_mid[i];
-            const int dims[2][3] = {{p.in_w[i], out_w, j.taps_x}, {p.in_h[i], out_h, j.taps_y}};
+            const jg::ResizeAxis* axes[2] = {&p.ax[i], &p.ay[i]};
+            const int dims[2][2] = {{out_w, j.taps_x}, {out_h, j.taps_y}};
             const size_t offs[2] = {p.off_tab_x[i], p.off_tab_y[i]};
             for (int d = 0; d < 2; ++d) {
-                const int in = dims[d][0], out = dims[d][1], taps = dims[d][2];
-                std::vector<int> fc(2 * static_cast<size_t>(out)), cnt(out);
+                const int in = axes[d]->extent, out = dims[d][0], taps = dims[d][1]; // `first` counts from the rectangle's edge
                 int* t = reinterpret_cast<int*>(h + offs[d]);
-                if (in == out) jg::resize_identity(out, fc.data(), cnt.data(), t + 2 * out, taps);
-                else jg::resize_table(in, out, filter, fc.data(), cnt.data(), t + 2 * out, taps);
-                for (int x = 0; x < out; ++x) {
-                    t[2 * x]     = fc[x];
-                    t[2 * x + 1] = cnt[x];
-                }
+                jg::resize_axis_table(*axes[d], out, taps, filter, t);
                 // the tables are those of the DISPLAYED axes; a mirrored axis gets them permuted for the stored order
                 const int o = p.orient[i];
                 if (d == 0 ? jg::orient_mirrors_x(o) : jg::orient_mirrors_y(o)) jg::mirror_taps(t, in, out, taps);
@@ -822,6 +919,27 @@ enum jpeggpu_status jpeggpu_ext_resize_to_rgb_oriented(
 // the batched resize as a model's input: flip, ToTensor, Normalize and the cast in the vertical pass (jpeggpu_ext.h)
 // ------------------------------------------------------------------------------------------------
 
+namespace {
+/// The tensor calls' own checks, made first; `s`: the spec handed to the kernels.
+enum jpeggpu_status tensor_spec(const struct jpeggpu_ext_tensor_spec* spec, struct jpeggpu_ext_tensor_spec& s)
+{
+    if (!spec) return JPEGGPU_INVALID_ARGUMENT;
+    const int type = spec->type;
+    if (type != JPEGGPU_EXT_TENSOR_U8 && type != JPEGGPU_EXT_TENSOR_F32 && type != JPEGGPU_EXT_TENSOR_F16 && type != JPEGGPU_EXT_TENSOR_BF16)
+        return JPEGGPU_INVALID_ARGUMENT;
+    s = *spec;
+    for (int c = 0; c < 3; ++c) {
+        if (type == JPEGGPU_EXT_TENSOR_U8) { // ignored: the kernel is handed values that mean nothing
+            s.mean[c] = 0.0f;
+            s.std[c]  = 1.0f;
+        } else if (!std::isfinite(s.mean[c]) || !std::isfinite(s.std[c]) || s.std[c] == 0.0f) {
+            return JPEGGPU_INVALID_ARGUMENT;
+        }
+    }
+    return JPEGGPU_SUCCESS;
+}
+} // namespace
+
 enum jpeggpu_status jpeggpu_ext_resize_to_tensor(
     const struct jpeggpu_ext_resize_item* items,
     const enum jpeggpu_ext_color_space* colors,
@@ -837,20 +955,80 @@ enum jpeggpu_status jpeggpu_ext_resize_to_tensor(
     size_t scratch_size,
     jpeggpu_stream_t stream)
 {
-    if (!spec) return JPEGGPU_INVALID_ARGUMENT;
-    const int type = spec->type;
-    if (type != JPEGGPU_EXT_TENSOR_U8 && type != JPEGGPU_EXT_TENSOR_F32 && type != JPEGGPU_EXT_TENSOR_F16 && type != JPEGGPU_EXT_TENSOR_BF16)
-        return JPEGGPU_INVALID_ARGUMENT;
-    jpeggpu_ext_tensor_spec s = *spec;
-    for (int c = 0; c < 3; ++c) {
-        if (type == JPEGGPU_EXT_TENSOR_U8) { // ignored: the kernel is handed values that mean nothing
-            s.mean[c] = 0.0f;
-            s.std[c]  = 1.0f;
-        } else if (!std::isfinite(s.mean[c]) || !std::isfinite(s.std[c]) || s.std[c] == 0.0f) {
-            return JPEGGPU_INVALID_ARGUMENT;
-        }
-    }
+    jpeggpu_ext_tensor_spec s;
+    const jpeggpu_status st = tensor_spec(spec, s);
+    if (st != JPEGGPU_SUCCESS) return st;
     return resize_to_rgb(items, colors, orientations, n, out_w, out_h, filter, layout, dst, d_scratch, scratch_size, stream, &s);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Resize + CenterCrop: a window of the resize of each item's whole image, zero outside it (jpeggpu_ext.h)
+// ------------------------------------------------------------------------------------------------
+
+size_t jpeggpu_ext_resize_view_scratch_size(
+    const struct jpeggpu_ext_resize_item* items, const enum jpeggpu_ext_color_space* colors, const int* orientations,
+    const struct jpeggpu_ext_resize_view* views, int n, int out_w, int out_h, enum jpeggpu_ext_filter filter)
+{
+    return views ? resize_scratch_size(items, colors, orientations, n, out_w, out_h, filter, views) : 0;
+}
+
+enum jpeggpu_status jpeggpu_ext_resize_view_to_tensor(
+    const struct jpeggpu_ext_resize_item* items,
+    const enum jpeggpu_ext_color_space* colors,
+    const int* orientations,
+    const struct jpeggpu_ext_resize_view* views,
+    int n,
+    int out_w,
+    int out_h,
+    enum jpeggpu_ext_filter filter,
+    enum jpeggpu_ext_output_layout layout,
+    const struct jpeggpu_ext_tensor_spec* spec,
+    void* dst,
+    void* d_scratch,
+    size_t scratch_size,
+    jpeggpu_stream_t stream)
+{
+    jpeggpu_ext_tensor_spec s;
+    const jpeggpu_status st = tensor_spec(spec, s);
+    if (st != JPEGGPU_SUCCESS) return st;
+    if (!views) return JPEGGPU_INVALID_ARGUMENT;
+    return resize_to_rgb(items, colors, orientations, n, out_w, out_h, filter, layout, dst, d_scratch, scratch_size, stream, &s, views);
+}
+
+enum jpeggpu_status jpeggpu_ext_resize_view_rect(
+    int full_w, int full_h, int orientation, const struct jpeggpu_ext_resize_view* view, int out_w, int out_h, enum jpeggpu_ext_filter filter,
+    int* x, int* y, int* w, int* h)
+{
+    if (filter != JPEGGPU_EXT_FILTER_BILINEAR && filter != JPEGGPU_EXT_FILTER_BICUBIC) return JPEGGPU_NOT_SUPPORTED;
+    if (!jg::orient_valid(orientation) || full_w < 1 || full_h < 1 || !view || view->resized_w <= 0 || view->resized_h <= 0 || out_w <= 0 ||
+        out_h <= 0 || !x || !y || !w || !h)
+        return JPEGGPU_INVALID_ARGUMENT;
+    const bool tr = jg::orient_transposes(orientation);
+    const jg::ResizeAxis ax{tr ? full_h : full_w, view->resized_w, view->x, 0, 0}, ay{tr ? full_w : full_h, view->resized_h, view->y, 0, 0};
+    int lo_x = 0, hi_x = 0, lo_y = 0, hi_y = 0;
+    if (!jg::resize_axis_range(ax, out_w, filter, &lo_x, &hi_x) || !jg::resize_axis_range(ay, out_h, filter, &lo_y, &hi_y))
+        return JPEGGPU_INVALID_ARGUMENT;
+    *x = lo_x;
+    *y = lo_y;
+    *w = hi_x - lo_x;
+    *h = hi_y - lo_y;
+    return jpeggpu_ext_orient_rect(orientation, full_w, full_h, x, y, w, h);
+}
+
+enum jpeggpu_status jpeggpu_ext_resize_view_weights(
+    int in, int resized, int x0, int count_out, int origin, enum jpeggpu_ext_filter filter, int* first, int* count, int* weights, int max_taps)
+{
+    if (filter != JPEGGPU_EXT_FILTER_BILINEAR && filter != JPEGGPU_EXT_FILTER_BICUBIC) return JPEGGPU_NOT_SUPPORTED;
+    if (!first || !count || !weights || in <= 0 || resized <= 0 || count_out <= 0 || max_taps < jg::resize_max_taps(in, resized, filter))
+        return JPEGGPU_INVALID_ARGUMENT;
+    try {
+        if (in == resized) jg::resize_identity(resized, x0, count_out, first, count, weights, max_taps);
+        else jg::resize_table(in, resized, filter, x0, count_out, first, count, weights, max_taps);
+    } catch (const std::bad_alloc&) {
+        return JPEGGPU_OUT_OF_HOST_MEMORY;
+    }
+    jg::resize_carry_empty(first, count, count_out, origin);
+    return JPEGGPU_SUCCESS;
 }
 
 // ------------------------------------------------------------------------------------------------
