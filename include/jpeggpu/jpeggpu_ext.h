@@ -332,6 +332,14 @@ enum jpeggpu_status jpeggpu_ext_batch_set_overlap(jpeggpu_batch_t batch, int par
  * the launch under "write" and nothing under "sync_inter". Not taken with a caller's cap of the sequence kernel's
  * iterations (jpeggpu_ext_batch_set_sync_iterations), nor by calls of more than 256 scans. */
 enum jpeggpu_status jpeggpu_ext_batch_set_fused_tail(jpeggpu_batch_t batch, int enable);
+/* Consecutive subsequences a lane of the batched sequence kernel owns: `r` is 1, 2 or 4 (anything else is refused), the
+ * default 2 or the environment's JPEGGPU_SYNC_RUN when the batch is created. With r = 1 a lane speculates its subsequence
+ * and flows into the next one, two state-only decodes per subsequence; with a run of r it speculates only the run's first
+ * subsequence, flows through the others and on into the next lane's run: (r + 1) / r decodes per subsequence. The result
+ * is the same bit for bit; only the sequence kernel's work changes (2: +2.5 % images/s on 12 MP batches; 4: slower than 1). Runs apply where a call fills the chip and runs the
+ * sequence kernel's single iteration: not to a call too small for that (which keeps every flow in its sequence's
+ * workgroup), not with a caller's jpeggpu_ext_batch_set_sync_iterations, never to lone decodes. */
+enum jpeggpu_status jpeggpu_ext_batch_set_sync_run(jpeggpu_batch_t batch, int r);
 /* Writers of huff_tail_write that gave up waiting for a sequence to become ready, since the library was loaded (their
  * wait is bounded so that a defect cannot hang the GPU; 0 on every correct run: tests and the soak assert it). */
 enum jpeggpu_status jpeggpu_ext_fused_tail_timeouts(unsigned int* count);

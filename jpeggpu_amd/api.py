@@ -215,6 +215,8 @@ def lib():
     L.jpeggpu_ext_batch_set_sync_iterations.argtypes = [C.c_void_p, C.c_int]
     L.jpeggpu_ext_batch_set_overlap.argtypes = [C.c_void_p, C.c_int]
     L.jpeggpu_ext_batch_set_fused_tail.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "jpeggpu_ext_batch_set_sync_run"):  # (a library loaded through JPEGGPU_LIB may be older than this file)
+        L.jpeggpu_ext_batch_set_sync_run.argtypes = [C.c_void_p, C.c_int]
     L.jpeggpu_ext_fused_tail_timeouts.argtypes = [C.POINTER(C.c_uint)]
     L.jpeggpu_ext_batch_get_stage_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.jpeggpu_ext_upsample_planes.argtypes = [
@@ -509,6 +511,12 @@ class Batch:
 
     def set_fused_tail(self, enable: bool):
         _check(lib().jpeggpu_ext_batch_set_fused_tail(self._h, 1 if enable else 0), "jpeggpu_ext_batch_set_fused_tail")
+
+    def set_sync_run(self, r: int):
+        """Consecutive subsequences a lane of the batched sequence kernel owns: 1, 2 or 4 (jpeggpu_ext.h)."""
+        if not hasattr(lib(), "jpeggpu_ext_batch_set_sync_run"):
+            raise RuntimeError("this libjpeggpu has no jpeggpu_ext_batch_set_sync_run")
+        _check(lib().jpeggpu_ext_batch_set_sync_run(self._h, int(r)), "jpeggpu_ext_batch_set_sync_run")
 
     def set_sync_iterations(self, n: int):
         _check(lib().jpeggpu_ext_batch_set_sync_iterations(self._h, n), "jpeggpu_ext_batch_set_sync_iterations")

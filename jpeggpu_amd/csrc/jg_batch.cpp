@@ -35,6 +35,11 @@ struct jpeggpu_batch {
     long long keep_flows_below  = jg::kKeepFlowsBelowSubseq;
     // Full batches: the tail kernel's parts and the write pass's sequences as one launch (jg_kernels.hip: huff_tail_write).
     bool fuse_tail_write        = true;
+    // Consecutive subsequences a lane of the batched sequence kernel owns (jg_sync_runs.h): 1, 2 or 4. Runs apply where a
+    // call takes huff_sync_intra_batch with its single iteration: not to calls that keep every flow in the sequence kernel,
+    // not under a caller's jpeggpu_ext_batch_set_sync_iterations. Two: every run of `value` above every run with 1 on the
+    // same card, +2.5 %; four is slower than one (EXPERIMENTS.md: the fetch pattern costs more than the decodes save).
+    int sync_run                = 2;
     // A caller with ONE stream leaves the GPU idle while the latency-bound tail kernel runs (a fifth of a
     // batch's time). With overlap > 1 the jobs are split into that many parts, part 0 on the caller's
     // stream and the others on internal streams forked from and joined back into it with events.
@@ -159,6 +164,7 @@ jpeggpu_status cut_parts(jpeggpu_batch& b, Call& c)
             for (int j = p.begin; j < p.end; ++j) jg::extend(p.extent, b.jobs[static_cast<size_t>(j)]);
             p.extent.repack_flows = c.keep_flows;
             p.extent.fuse_tail_write = b.fuse_tail_write && !b.sync_iters_set;
+            p.extent.sync_run = c.keep_flows || b.sync_iters_set ? 1 : b.sync_run;
             if (p.end > p.begin) b.parts.push_back(p);
         }
     }
@@ -279,6 +285,10 @@ enum jpeggpu_status jpeggpu_ext_batch_create(jpeggpu_batch_t* batch, int max_sca
     b->max_jobs = max_scans;
     if (const char* e = std::getenv("JPEGGPU_EXP_KEEP_FLOWS_BELOW")) b->keep_flows_below = std::atoll(e); // experiments (tools/probe/batch_curve.py)
     if (const char* e = std::getenv("JPEGGPU_FUSE_TAIL_WRITE")) b->fuse_tail_write = std::atoi(e) != 0;
+    if (const char* e = std::getenv("JPEGGPU_SYNC_RUN")) {
+        const int r = std::atoi(e);
+        if (r == 1 || r == 2 || r == 4) b->sync_run = r; // (anything else: the default)
+    }
     for (int r = 0; r < jpeggpu_batch::kRing; ++r) {
         void* p = nullptr;
         if (hipHostMalloc(&p, jpeggpu_ext_batch_scratch_size(max_scans), hipHostMallocDefault) != hipSuccess ||
@@ -352,6 +362,13 @@ enum jpeggpu_status jpeggpu_ext_batch_set_sync_iterations(jpeggpu_batch_t batch,
     if (!batch || iterations < 1) return JPEGGPU_INVALID_ARGUMENT; // the first flow iteration supplies n and the DC sums
     batch->sync_iters     = iterations;
     batch->sync_iters_set = true;
+    return JPEGGPU_SUCCESS;
+}
+
+enum jpeggpu_status jpeggpu_ext_batch_set_sync_run(jpeggpu_batch_t batch, int r)
+{
+    if (!batch || (r != 1 && r != 2 && r != 4)) return JPEGGPU_INVALID_ARGUMENT;
+    batch->sync_run = r;
     return JPEGGPU_SUCCESS;
 }
 

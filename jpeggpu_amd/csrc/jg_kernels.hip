@@ -16,6 +16,7 @@
 #define JG_TABS_IN_LDS 1 // table offsets handed to the symbol loop are absolute LDS addresses (jg_huff_core.h)
 #include "jg_huff_core.h"
 #include "jg_kernels.hpp"
+#include "jg_sync_runs.h"
 
 #include <hip/hip_runtime.h>
 
@@ -754,10 +755,82 @@ __device__ __forceinline__ void fuse_init(const ScanJob* jobs, int job, const Jo
     }
 }
 
-template <int W, class JS>
+/// What run_speculate / run_flow (jg_sync_runs.h) ask of the kernel: the job's segments and state arrays, and the two LDS
+/// words per lane that carry E1 to the lane in front.
+struct RunIo {
+    const JobView& J;
+    int* s_p;
+    int* s_cz;
+    __device__ __forceinline__ Segment segment_of(int sub) const { return ld_global(J.segments + J.seg_idx[sub]); }
+    __device__ __forceinline__ void put_e1(int lane, int p, int cz) const
+    {
+        s_p[lane]  = p;
+        s_cz[lane] = cz;
+    }
+    __device__ __forceinline__ bool e1_is(int lane, int p, int cz) const { return s_p[lane] == p && s_cz[lane] == cz; }
+    __device__ __forceinline__ void store(int sub, const LaneState& st, int cz, bool pending) const
+    {
+        J.pending[sub] = static_cast<uint8_t>(pending ? 1 : 0);
+        J.st_p[sub]    = st.p;
+        J.st_n[sub]    = st.n;
+        J.st_cz[sub]   = cz;
+        J.st_dc01[sub] = st.dc01;
+        J.st_dc23[sub] = st.dc23;
+    }
+};
+
+/// huff_sync_intra_batch<W, JS, R> with R > 1: every lane behind the overlap lane owns a run of R consecutive
+/// subsequences, speculates only the first of them and flows through the rest and into the next lane's run
+/// (jg_sync_runs.h: R + 1 decodes per R subsequences instead of 2 R). A half of the workgroup then covers R write-pass
+/// sequences, SEQ * R subsequences; the state arrays of SeqLdsBatch are not scaled -- only E1 goes through LDS.
+template <int W, class JS, int R>
+__device__ __forceinline__ void sync_intra_batch_runs(const JS& js, uint8_t* smem)
+{
+    const int which = threadIdx.x / T, l = threadIdx.x % T;
+    int* s_p        = reinterpret_cast<int*>(smem + SeqLdsBatch::kState + which * SeqLdsBatch::kOne);
+    int* s_cz       = s_p + 2 * T;
+    uint8_t* s_tab  = smem + SeqLdsBatch::kTabs;
+
+    const JobView J(js.get());
+    if constexpr (std::is_same<JS, JobArray>::value) {
+        if (blockIdx.x == 0) fuse_init(js.jobs, static_cast<int>(blockIdx.y), J, T * kBatchSeqPerWg); // huff_tail_write of the same call
+    }
+    if (static_cast<int>(blockIdx.x) * kBatchSeqPerWg * R >= J.num_seq) return;
+    ScanParams sp = J.sp;
+    sp.use_sync_pack();
+    const int SEQ   = sp.seq_subseq;                                   // 255 in batches: lanes 1 .. SEQ own runs
+    const int group = static_cast<int>(blockIdx.x) * kBatchSeqPerWg + which; // R write-pass sequences
+    RunLane ln;
+    run_plan<R>(ln, l, group * SEQ * R, SEQ, sp.num_subseq);
+    // (the lane's segment: its index asked for before the table pack is copied, the record right behind it)
+    const int lane_seg = J.seg_idx[ln.active ? ln.a : 0];
+
+    load_tables(s_tab, J.tables_sync, sp);
+    const Segment lane_segment = ld_global(J.segments + lane_seg);
+    __syncthreads();
+
+    GlobalFetch<W> fetch{reinterpret_cast<JG_GLOBAL const uint32_t*>(J.destuffed), 0, 0};
+    const RunIo io{J, s_p, s_cz};
+    run_speculate<W>(ln, l, lane_segment, fetch, s_tab, sp, io);
+    __syncthreads();
+    run_flow<W, R>(ln, l, fetch, s_tab, sp, io);
+
+    // (this kernel says nothing about the boundaries, those inside the group included: huff_sync_tail starts a flow at
+    // every one)
+    if (l < R && group * R + l < J.num_seq) {
+        J.bnd_p[group * R + l]  = -1;
+        J.bnd_cz[group * R + l] = -1;
+    }
+}
+
+template <int W, class JS, int R = 1>
 __global__ __launch_bounds__(T * kBatchSeqPerWg) void huff_sync_intra_batch(JS js)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    if constexpr (R > 1) {
+        sync_intra_batch_runs<W, JS, R>(js, smem);
+        return;
+    }
     const int which = threadIdx.x / T;                       // the workgroup's sequence this lane works for
     const int seq   = blockIdx.x * kBatchSeqPerWg + which;
     int* s_p         = reinterpret_cast<int*>(smem + SeqLdsBatch::kState + which * SeqLdsBatch::kOne);
@@ -2012,6 +2085,18 @@ hipError_t launch_huff(Stage stage, const JS& js, const JobExtent& e, int grid_y
             huff_sync_intra<W, JobArrayLow><<<dim3(e.max_seq, grid_y), T, seq_lds, stream>>>(JobArrayLow{js.jobs});
         } else {
             const size_t lds = SeqLdsBatch::kTabs + e.max_tab_bytes_sync;
+            if (e.sync_run == 2 || e.sync_run == 4) { // runs of subsequences per lane: a workgroup covers 2 R sequences
+                const int per_wg = kBatchSeqPerWg * e.sync_run;
+                const dim3 grid((e.max_seq + per_wg - 1) / per_wg, grid_y);
+                if (e.sync_run == 2) {
+                    if ((err = allow_lds(huff_sync_intra_batch<W, JS, 2>, lds)) != hipSuccess) return err;
+                    huff_sync_intra_batch<W, JS, 2><<<grid, T * kBatchSeqPerWg, lds, stream>>>(js);
+                } else {
+                    if ((err = allow_lds(huff_sync_intra_batch<W, JS, 4>, lds)) != hipSuccess) return err;
+                    huff_sync_intra_batch<W, JS, 4><<<grid, T * kBatchSeqPerWg, lds, stream>>>(js);
+                }
+                break;
+            }
             if ((err = allow_lds(huff_sync_intra_batch<W, JS>, lds)) != hipSuccess) return err;
             huff_sync_intra_batch<W, JS><<<dim3((e.max_seq + kBatchSeqPerWg - 1) / kBatchSeqPerWg, grid_y), T * kBatchSeqPerWg, lds, stream>>>(js);
         }

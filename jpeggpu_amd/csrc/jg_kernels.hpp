@@ -39,6 +39,8 @@ struct JobExtent {
     uint32_t max_tab_bytes_sync = 0; // largest sync pack
     bool fuse_tail_write = false;    // batch launches: the tail kernel's parts and the write pass's sequences as ONE launch
                                      // (huff_tail_write), launched at kStageWrite; kStageSyncInter and kStageTails launch nothing
+    int sync_run        = 1;         // batch launches behind huff_sync_intra_batch with its single iteration: consecutive
+                                     // subsequences a lane of that kernel owns (1, 2 or 4; jg_sync_runs.h). Ignored with repack_flows.
     bool repack_flows   = false;     // batch launches: the lone decode's sequence kernel (every flow kept in its workgroup), for
                                      // calls too small to fill the chip; the jobs then carry max_intra_iters = kSeqLanes, tail_marks = 0
 };
