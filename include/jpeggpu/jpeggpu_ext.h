@@ -36,6 +36,8 @@
  *                                      normalised as ToTensor + Normalize do, items flipped left to right where asked
  *   jpeggpu_ext_resize_view_to_tensor  the evaluation transform: a window of the resize of each item's WHOLE image, zero
  *                                      outside it -- torchvision's Resize + CenterCrop on Pillow, from a cropped decode
+ *   jpeggpu_ext_encode_batch           the way back: uint8 images on the device to baseline JPEG files on the device, byte
+ *                                      for byte what Pillow's Image.save writes on libjpeg-turbo
  */
 #ifndef JPEGGPU_JPEGGPU_EXT_H_
 #define JPEGGPU_JPEGGPU_EXT_H_
@@ -893,6 +895,62 @@ enum jpeggpu_status jpeggpu_ext_batch_to_rgb(
     enum jpeggpu_ext_image_layout layout,
     void* d_scratch,
     size_t scratch_size,
+    jpeggpu_stream_t stream);
+
+/* Encoding: grey or RGB uint8 images in device memory to baseline JPEG files in device memory, many per call. The file is
+ * the one Pillow writes on libjpeg-turbo -- Image.fromarray(x).save(f, "JPEG", quality=, subsampling=,
+ * restart_marker_blocks=) -- byte for byte (tests/golden/encode_pins.npz): jccolor.c's fixed-point RGB -> YCbCr, jcsample.c's
+ * h2v1 / h2v2 downsampling without smoothing and its edge rules, jpeg_fdct_islow, the quantiser's rounded division,
+ * jpeg_set_quality's tables, jccoefct.c's dummy blocks, jchuff.c with the Annex K tables, a JFIF header without
+ * density. Not written: optimised Huffman tables, progressive scans, other samplings, four components, EXIF / ICC.
+ *   - An item: `data` the device pointer of sample (0, 0) of channel 0; sample (x, y) of channel c is the byte at
+ *     data + y * row_pitch + x * pixel_stride + c * channel_stride, so an HWC tensor (pixel_stride 3, channel_stride 1), a CHW
+ *     tensor (pixel_stride 1, channel_stride H * W) and any view of either are one struct, without a copy. `channels` 1 (grey)
+ *     or 3 (RGB). `quality` 1..100. `subsampling` of the chroma; a grey file has no chroma, and the value only sets the
+ *     sampling factors its frame header names (as Pillow does). `restart_interval` in MCUs, 0..65535, 0: no restart markers.
+ *     `out`, `capacity`: the item's output slot (out may be NULL with capacity 0: the call then only reports the size).
+ *   - jpeggpu_ext_encode_header (host only, needs no device): SOI up to the end of the scan header. `*size` is the room in
+ *     host_buf on entry and the header's length on return; host_buf NULL only asks for the length.
+ *   - jpeggpu_ext_encode_bound (host only): the size no file of the item's geometry can exceed. A block takes at most 22 bits
+ *     of DC (the longest DC code of the tables, 11 bits, and 11 value bits) and 63 x 26 bits of AC (a 16-bit code and 10 value
+ *     bits per coefficient; a ZRL or EOB is shorter than the coefficients it stands for): 1660 bits. So the stream has at
+ *     most ceil(1660 blocks / 8) + segments bytes with the padding of each restart segment; every byte may be 0xFF and
+ *     doubled by stuffing; then the header, two bytes per restart marker and EOI. 0 for an invalid item.
+ *   - jpeggpu_ext_encode_batch encodes items[0..n) on `stream` with EIGHT launches and one copy of descriptors whatever n and
+ *     the sizes are, and does not synchronise. d_sizes[i] receives the file's length and d_status[i] JPEGGPU_EXT_ENCODE_OK,
+ *     or JPEGGPU_EXT_ENCODE_TOO_SMALL if that length exceeds `capacity`: then d_sizes[i] is the capacity it needs and not one
+ *     byte of its slot is written; the other items are not affected. Sizes are known on the device before anything is written
+ *     to a slot. `d_scratch`: caller-owned device memory of at least jpeggpu_ext_encode_scratch_size(items, n) bytes,
+ *     private to the stream until the call has executed; it holds the coefficients (2 bytes per padded sample) and the
+ *     unstuffed stream at its bound. The host may reuse `items` when the call returns: descriptors and headers travel
+ *     through a page-locked ring of four (the fifth call in a row waits until the copy of the first has executed).
+ *   - JPEGGPU_INVALID_ARGUMENT, before anything is enqueued: NULL items, d_scratch, d_sizes, d_status or data, a NULL out with
+ *     a capacity, n <= 0 or > 65535, width or height outside 1..65535, channels other than 1 or 3, quality outside 1..100, an
+ *     unknown subsampling, a restart interval outside 0..65535, scratch_size too small. JPEGGPU_NOT_SUPPORTED: an item whose
+ *     stream bound reaches 2^32 bits (about 2.5 million blocks: 160 megapixels grey), or a call of 2^31 blocks. */
+enum jpeggpu_ext_subsampling { JPEGGPU_EXT_SUBSAMPLING_444 = 0, JPEGGPU_EXT_SUBSAMPLING_422 = 1, JPEGGPU_EXT_SUBSAMPLING_420 = 2 };
+enum jpeggpu_ext_encode_status { JPEGGPU_EXT_ENCODE_OK = 0, JPEGGPU_EXT_ENCODE_TOO_SMALL = 1 };
+struct jpeggpu_ext_encode_item {
+    const uint8_t* data;
+    int width, height;
+    int channels;
+    int64_t row_pitch, pixel_stride, channel_stride; /* bytes */
+    int quality;
+    int subsampling; /* enum jpeggpu_ext_subsampling */
+    int restart_interval;
+    uint8_t* out;
+    size_t capacity;
+};
+enum jpeggpu_status jpeggpu_ext_encode_header(const struct jpeggpu_ext_encode_item* item, uint8_t* host_buf, size_t* size);
+size_t jpeggpu_ext_encode_bound(const struct jpeggpu_ext_encode_item* item);
+size_t jpeggpu_ext_encode_scratch_size(const struct jpeggpu_ext_encode_item* items, int n);
+enum jpeggpu_status jpeggpu_ext_encode_batch(
+    const struct jpeggpu_ext_encode_item* items,
+    int n,
+    void* d_scratch,
+    size_t scratch_size,
+    size_t* d_sizes,
+    int* d_status,
     jpeggpu_stream_t stream);
 
 #ifdef __cplusplus

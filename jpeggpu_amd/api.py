@@ -19,6 +19,7 @@ FILTERS = {"bilinear": 0, "bicubic": 1}  # enum jpeggpu_ext_filter
 LAYOUTS = {"NHWC": 0, "NCHW": 1}  # enum jpeggpu_ext_output_layout
 IMAGE_LAYOUTS = {"HWC": 0, "CHW": 1}  # enum jpeggpu_ext_image_layout
 SCALE_MODES = {"uniform": 0, "libjpeg": 1}  # enum jpeggpu_ext_scale_mode
+SUBSAMPLINGS = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}  # enum jpeggpu_ext_subsampling (Pillow's numbers)
 TENSOR_TYPE_NAMES = {"uint8": 0, "float32": 1, "float16": 2, "bfloat16": 3}  # enum jpeggpu_ext_tensor_type, by torch dtype name
 
 
@@ -129,6 +130,13 @@ class RgbItem(C.Structure):
     _fields_ = [("info", C.POINTER(ImgInfo)), ("crop", C.POINTER(CropInfo)), ("src", C.POINTER(Img)),
                 ("color", C.c_int), ("orientation", C.c_int), ("replicate", C.c_int),
                 ("dst", C.c_void_p), ("dst_pitch", C.c_int), ("plane_stride", C.c_size_t)]
+
+
+class EncodeItem(C.Structure):
+    """struct jpeggpu_ext_encode_item"""
+    _fields_ = [("data", C.c_void_p), ("width", C.c_int), ("height", C.c_int), ("channels", C.c_int), ("row_pitch", C.c_int64),
+                ("pixel_stride", C.c_int64), ("channel_stride", C.c_int64), ("quality", C.c_int), ("subsampling", C.c_int),
+                ("restart_interval", C.c_int), ("out", C.c_void_p), ("capacity", C.c_size_t)]
 
 
 class ExtScanLayout(C.Structure):
@@ -287,6 +295,13 @@ def lib():
     L.jpeggpu_ext_batch_rgb_scratch_size.restype = C.c_size_t
     L.jpeggpu_ext_batch_rgb_scratch_size.argtypes = [C.c_int]
     L.jpeggpu_ext_batch_to_rgb.argtypes = [C.POINTER(RgbItem), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+    if hasattr(L, "jpeggpu_ext_encode_batch"):  # (a library loaded through JPEGGPU_LIB may be older than this file)
+        L.jpeggpu_ext_encode_header.argtypes = [C.POINTER(EncodeItem), C.c_void_p, C.POINTER(C.c_size_t)]
+        L.jpeggpu_ext_encode_bound.argtypes = [C.POINTER(EncodeItem)]
+        L.jpeggpu_ext_encode_bound.restype = C.c_size_t
+        L.jpeggpu_ext_encode_scratch_size.argtypes = [C.POINTER(EncodeItem), C.c_int]
+        L.jpeggpu_ext_encode_scratch_size.restype = C.c_size_t
+        L.jpeggpu_ext_encode_batch.argtypes = [C.POINTER(EncodeItem), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
     L.jpeggpu_ext_resize_weights.argtypes = [
         C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
     _lib = L
@@ -1365,3 +1380,179 @@ def decode_batch_to_rgb(datas, device="cuda:0", crops=None, scales=None, exif_tr
     finally:
         for dec in decs:
             dec.cleanup()
+
+
+def encode_item(width, height, channels=3, quality=75, subsampling="4:2:0", restart_interval=0):
+    """A struct jpeggpu_ext_encode_item of this geometry without pointers: what encode_header and encode_bound need."""
+    if subsampling not in SUBSAMPLINGS:
+        raise ValueError("subsampling %r is not one of %s" % (subsampling, ", ".join(SUBSAMPLINGS)))
+    it = EncodeItem()
+    it.width, it.height, it.channels = int(width), int(height), int(channels)
+    it.quality, it.subsampling, it.restart_interval = int(quality), SUBSAMPLINGS[subsampling], int(restart_interval)
+    return it
+
+
+def encode_header(width, height, channels=3, quality=75, subsampling="4:2:0", restart_interval=0) -> bytes:
+    """jpeggpu_ext_encode_header (host only): SOI up to the end of the scan header of the file encode_jpeg writes."""
+    it = encode_item(width, height, channels, quality, subsampling, restart_interval)
+    size = C.c_size_t(1024)
+    buf = C.create_string_buffer(1024)
+    _check(lib().jpeggpu_ext_encode_header(C.byref(it), buf, C.byref(size)), "jpeggpu_ext_encode_header")
+    return buf.raw[:size.value]
+
+
+def encode_bound(width, height, channels=3, quality=75, subsampling="4:2:0", restart_interval=0) -> int:
+    """jpeggpu_ext_encode_bound (host only): the size no file of this geometry exceeds."""
+    it = encode_item(width, height, channels, quality, subsampling, restart_interval)
+    n = lib().jpeggpu_ext_encode_bound(C.byref(it))
+    if n == 0:
+        raise JpegGpuError(Status.INVALID_ARGUMENT, "jpeggpu_ext_encode_bound")
+    return n
+
+
+def _per_image(v, n, name):
+    if isinstance(v, (list, tuple)):
+        if len(v) != n:
+            raise ValueError("%s must be one value or one per image" % name)
+        return list(v)
+    return [v] * n
+
+
+def _encode_items(images, quality, subsampling, restart_interval, layout):
+    """The items of a call, without output slots: `images` a list of uint8 device tensors or one 4-D tensor."""
+    import torch
+
+    if layout not in IMAGE_LAYOUTS:
+        raise ValueError("layout %r is not one of %s" % (layout, ", ".join(IMAGE_LAYOUTS)))
+    if isinstance(images, torch.Tensor):
+        if images.dim() != 4:
+            raise ValueError("a batch tensor must have 4 dimensions")
+        images = list(images)
+    images = list(images)
+    n = len(images)
+    qs, ss, rs = _per_image(quality, n, "quality"), _per_image(subsampling, n, "subsampling"), _per_image(restart_interval, n, "restart_interval")
+    items = (EncodeItem * max(n, 1))()
+    for i, x in enumerate(images):
+        if x.dtype != torch.uint8 or not x.is_cuda or x.dim() not in (2, 3):
+            raise ValueError("image %d: a uint8 device tensor of 2 or 3 dimensions is expected" % i)
+        if x.dim() == 2:
+            h, w, ch, ps, cs = x.shape[0], x.shape[1], 1, x.stride(1), 0
+            rp = x.stride(0)
+        elif layout == "HWC":
+            h, w, ch = x.shape
+            rp, ps, cs = x.stride()
+        else:
+            ch, h, w = x.shape
+            cs, rp, ps = x.stride()
+        if ch not in (1, 3):
+            raise ValueError("image %d: 1 or 3 channels are expected, not %d" % (i, ch))
+        it = encode_item(w, h, ch, qs[i], ss[i], rs[i])
+        it.data, it.row_pitch, it.pixel_stride, it.channel_stride = x.data_ptr(), rp, ps, cs
+        items[i] = it
+    return images, items
+
+
+def encode_into(images, outs, quality=75, subsampling="4:2:0", restart_interval=0, layout="HWC"):
+    """jpeggpu_ext_encode_batch on torch's current stream, without synchronising: image i into the slot outs[i] (a contiguous
+    uint8 device tensor whose length is the capacity; None: capacity 0, only the size is reported). Returns the device
+    tensors (sizes int64[n], status int32[n]); status 1 marks a slot that was too small, whose size is the capacity it
+    needs and which was not written."""
+    import torch
+
+    images, items = _encode_items(images, quality, subsampling, restart_interval, layout)
+    n = len(images)
+    if len(outs) != n:
+        raise ValueError("outs must have one entry per image")
+    if n == 0:
+        raise ValueError("no images")
+    device = images[0].device
+    for i, o in enumerate(outs):
+        if o is not None and (o.dtype != torch.uint8 or not o.is_contiguous() or o.device != device):
+            raise ValueError("outs[%d]: a contiguous uint8 tensor on the images' device is expected" % i)
+        items[i].out = o.data_ptr() if o is not None and o.numel() else None
+        items[i].capacity = o.numel() if o is not None else 0
+    need = lib().jpeggpu_ext_encode_scratch_size(items, n)
+    if need == 0:
+        raise JpegGpuError(Status.NOT_SUPPORTED, "jpeggpu_ext_encode_scratch_size")
+    scratch = torch.empty(need, dtype=torch.uint8, device=device)
+    result = torch.empty(12 * n, dtype=torch.uint8, device=device)  # sizes, then status: one copy brings both to the host
+    _check(lib().jpeggpu_ext_encode_batch(items, n, scratch.data_ptr(), need, result.data_ptr(), result.data_ptr() + 8 * n,
+                                          torch.cuda.current_stream(device).cuda_stream), "jpeggpu_ext_encode_batch")
+    # the scratch tensor is freed by torch's caching allocator in stream order: it is not reused before the launches ran
+    return result[:8 * n].view(torch.int64), result[8 * n:].view(torch.int32)
+
+
+def _encode_results(sizes, status):
+    """encode_into's two tensors on the host, with one copy; this synchronises."""
+    import torch
+
+    n = sizes.numel()
+    raw = torch.cat([sizes.view(torch.uint8), status.view(torch.uint8)]).cpu()
+    return raw[:8 * n].view(torch.int64).tolist(), raw[8 * n:].view(torch.int32).tolist()
+
+
+def encode_jpeg_to_device(images, quality=75, subsampling="4:2:0", restart_interval=0, layout="HWC", capacities=None):
+    """Baseline JPEG files of `images`, left on the device: returns (buffer, offsets, sizes) -- file i is
+    buffer[offsets[i]:offsets[i] + sizes[i]], a uint8 device tensor and two lists of ints. Arguments and the files are
+    encode_jpeg's. `capacities`: the slot sizes to start with (default: each image's raw sample count plus its header);
+    items whose file is larger are encoded once more into slots of the size they reported, behind the others. One
+    jpeggpu_ext_encode_batch call (two after an overflow) and one synchronisation per call."""
+    import torch
+
+    images, items = _encode_items(images, quality, subsampling, restart_interval, layout)
+    n = len(images)
+    if n == 0:
+        return None, [], []
+    device = images[0].device
+    if capacities is None:
+        capacities = []
+        for i in range(n):
+            size = C.c_size_t(0)
+            _check(lib().jpeggpu_ext_encode_header(C.byref(items[i]), None, C.byref(size)), "jpeggpu_ext_encode_header")
+            capacities.append(items[i].width * items[i].height * items[i].channels + size.value)
+    capacities = _per_image(capacities, n, "capacities")
+
+    def run(which, caps):
+        offsets, total = [], 0
+        for c in caps:
+            offsets.append(total)
+            total = (total + c + 15) // 16 * 16
+        buf = torch.empty(max(total, 1), dtype=torch.uint8, device=device)
+        outs = [buf[o:o + c] for o, c in zip(offsets, caps)]
+        pick = lambda v: [v[i] for i in which] if isinstance(v, (list, tuple)) else v  # noqa: E731
+        sizes, status = _encode_results(*encode_into([images[i] for i in which], outs, pick(quality), pick(subsampling), pick(restart_interval), layout))
+        return buf, offsets, sizes, status
+
+    buf, offsets, sizes, status = run(list(range(n)), [int(c) for c in capacities])
+    again = [i for i in range(n) if status[i]]
+    if again:
+        buf2, offsets2, sizes2, status2 = run(again, [sizes[i] for i in again])
+        if any(status2):
+            raise JpegGpuError(Status.INTERNAL_ERROR, "jpeggpu_ext_encode_batch (retry)")
+        base = buf.numel()
+        buf = torch.cat([buf, buf2])
+        for k, i in enumerate(again):
+            offsets[i], sizes[i] = base + offsets2[k], sizes2[k]
+    return buf, offsets, sizes
+
+
+def encode_jpeg(images, quality=75, subsampling="4:2:0", restart_interval=0, layout="HWC"):
+    """Baseline JPEG files of uint8 device tensors, as a list of bytes: each file is, byte for byte, what Pillow on
+    libjpeg-turbo writes with Image.fromarray(x).save(f, "JPEG", quality=quality, subsampling=subsampling,
+    restart_marker_blocks=restart_interval) for the same pixels on the host.
+    `images`: a list of tensors of any sizes, or one 4-D batch tensor; an item is H x W x 3 (RGB), H x W x 1 or H x W (grey),
+    or with layout="CHW" 3 x H x W / 1 x H x W. Views (crops, row-padded, permuted) are read through their strides, without a
+    copy. `quality` 1..100, `subsampling` "4:4:4" | "4:2:2" | "4:2:0" (grey has no chroma) and `restart_interval` (MCUs
+    between restart markers, 0: none) are one value or one per image. The whole list is ONE jpeggpu_ext_encode_batch call (a
+    second one for the items whose file is larger than its raw pixels), one synchronisation and one copy to the host."""
+    import torch
+
+    buf, offsets, sizes = encode_jpeg_to_device(images, quality, subsampling, restart_interval, layout)
+    if not sizes:
+        return []
+    host = torch.cat([buf[o:o + s] for o, s in zip(offsets, sizes)]).cpu().numpy().tobytes()  # only the files' bytes travel
+    out, p = [], 0
+    for s in sizes:
+        out.append(host[p:p + s])
+        p += s
+    return out

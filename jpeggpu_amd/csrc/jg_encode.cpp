@@ -1,0 +1,370 @@
+// jg_encode.cpp -- the encoder's part of the exported C ABI (include/jpeggpu/jpeggpu_ext.h): argument checks, the file
+// header, the size bound and the plan of a call for the kernels of jg_encode.hip. It knows nothing of the decoder.
+#include "jg_encode.hpp"
+#include "jg_staging.hpp"
+
+#include <jpeggpu/jpeggpu.h>
+#include <jpeggpu/jpeggpu_ext.h>
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+#include <mutex>
+#include <new>
+#include <vector>
+
+namespace jg {
+namespace enc {
+namespace {
+
+static_assert(sizeof(size_t) == sizeof(unsigned long long), "d_sizes is written as 64-bit words");
+
+// Annex K.1, K.2 (natural order) and K.3 - K.6
+const uint8_t kBaseLuma[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,  69,  56,
+                               14, 17, 22, 29, 51,  87,  80,  62,  18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,
+                               49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+const uint8_t kBaseChroma[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+                                 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+const uint8_t kNatural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
+                              35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+struct HuffSpec {
+    uint8_t bits[16];
+    int count;
+    uint8_t values[162];
+};
+const HuffSpec kDcLuma   = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, 12, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}};
+const HuffSpec kDcChroma = {{0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}, 12, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}};
+const HuffSpec kAcLuma   = {
+    {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7D},
+    162,
+    {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xA1,
+     0x08, 0x23, 0x42, 0xB1, 0xC1, 0x15, 0x52, 0xD1, 0xF0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0A, 0x16, 0x17, 0x18, 0x19, 0x1A, 0x25, 0x26,
+     0x27, 0x28, 0x29, 0x2A, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3A, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4A, 0x53, 0x54, 0x55, 0x56,
+     0x57, 0x58, 0x59, 0x5A, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6A, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7A, 0x83, 0x84, 0x85,
+     0x86, 0x87, 0x88, 0x89, 0x8A, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9A, 0xA2, 0xA3, 0xA4, 0xA5, 0xA6, 0xA7, 0xA8, 0xA9, 0xAA,
+     0xB2, 0xB3, 0xB4, 0xB5, 0xB6, 0xB7, 0xB8, 0xB9, 0xBA, 0xC2, 0xC3, 0xC4, 0xC5, 0xC6, 0xC7, 0xC8, 0xC9, 0xCA, 0xD2, 0xD3, 0xD4, 0xD5, 0xD6,
+     0xD7, 0xD8, 0xD9, 0xDA, 0xE1, 0xE2, 0xE3, 0xE4, 0xE5, 0xE6, 0xE7, 0xE8, 0xE9, 0xEA, 0xF1, 0xF2, 0xF3, 0xF4, 0xF5, 0xF6, 0xF7, 0xF8, 0xF9,
+     0xFA}};
+const HuffSpec kAcChroma = {
+    {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77},
+    162,
+    {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42,
+     0x91, 0xA1, 0xB1, 0xC1, 0x09, 0x23, 0x33, 0x52, 0xF0, 0x15, 0x62, 0x72, 0xD1, 0x0A, 0x16, 0x24, 0x34, 0xE1, 0x25, 0xF1, 0x17, 0x18, 0x19,
+     0x1A, 0x26, 0x27, 0x28, 0x29, 0x2A, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3A, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4A, 0x53, 0x54, 0x55,
+     0x56, 0x57, 0x58, 0x59, 0x5A, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6A, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7A, 0x82, 0x83,
+     0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8A, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9A, 0xA2, 0xA3, 0xA4, 0xA5, 0xA6, 0xA7, 0xA8,
+     0xA9, 0xAA, 0xB2, 0xB3, 0xB4, 0xB5, 0xB6, 0xB7, 0xB8, 0xB9, 0xBA, 0xC2, 0xC3, 0xC4, 0xC5, 0xC6, 0xC7, 0xC8, 0xC9, 0xCA, 0xD2, 0xD3, 0xD4,
+     0xD5, 0xD6, 0xD7, 0xD8, 0xD9, 0xDA, 0xE2, 0xE3, 0xE4, 0xE5, 0xE6, 0xE7, 0xE8, 0xE9, 0xEA, 0xF2, 0xF3, 0xF4, 0xF5, 0xF6, 0xF7, 0xF8, 0xF9,
+     0xFA}};
+
+/// Annex C: code << 8 | length per symbol, and the longest code of the table.
+int derive(const HuffSpec& spec, uint32_t* out)
+{
+    uint32_t code = 0;
+    int k = 0, longest = 0;
+    for (int len = 1; len <= 16; ++len) {
+        for (int i = 0; i < spec.bits[len - 1]; ++i) {
+            out[spec.values[k++]] = code << 8 | uint32_t(len);
+            ++code;
+            longest = len;
+        }
+        code <<= 1;
+    }
+    return longest;
+}
+
+/// The tables once per process, and the check that kMaxBlockBits is what they say.
+const Tables& tables()
+{
+    static const Tables* t = [] {
+        Tables* x = new Tables();
+        int dc    = derive(kDcLuma, x->dc);
+        int d2    = derive(kDcChroma, x->dc + 16);
+        int ac    = derive(kAcLuma, x->ac);
+        int a2    = derive(kAcChroma, x->ac + 256);
+        if ((dc > d2 ? dc : d2) != kMaxDcCode || (ac > a2 ? ac : a2) != kMaxAcCode) std::abort();
+        return x;
+    }();
+    return *t;
+}
+
+/// jpeg_set_quality's table (force_baseline), natural order.
+void quant_table(const uint8_t* base, int quality, uint8_t* q)
+{
+    const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    for (int i = 0; i < 64; ++i) {
+        int v = (base[i] * s + 50) / 100;
+        q[i]  = uint8_t(v < 1 ? 1 : v > 255 ? 255 : v);
+    }
+}
+
+bool valid(const jpeggpu_ext_encode_item* it)
+{
+    return it && it->width >= 1 && it->width <= 65535 && it->height >= 1 && it->height <= 65535 && (it->channels == 1 || it->channels == 3) &&
+           it->quality >= 1 && it->quality <= 100 && it->subsampling >= JPEGGPU_EXT_SUBSAMPLING_444 && it->subsampling <= JPEGGPU_EXT_SUBSAMPLING_420 &&
+           it->restart_interval >= 0 && it->restart_interval <= 65535;
+}
+
+struct Geometry {
+    int hs, vs, mcus_x, mcus_y, blocks_per_mcu;
+    uint64_t blocks, segments, stream_bound;
+};
+Geometry geometry(const jpeggpu_ext_encode_item& it)
+{
+    Geometry g;
+    const bool grey = it.channels == 1;
+    g.hs            = !grey && it.subsampling != JPEGGPU_EXT_SUBSAMPLING_444 ? 2 : 1;
+    g.vs            = !grey && it.subsampling == JPEGGPU_EXT_SUBSAMPLING_420 ? 2 : 1;
+    g.mcus_x        = (it.width + 8 * g.hs - 1) / (8 * g.hs);
+    g.mcus_y        = (it.height + 8 * g.vs - 1) / (8 * g.vs);
+    g.blocks_per_mcu = grey ? 1 : g.hs * g.vs + 2;
+    const uint64_t mcus = uint64_t(g.mcus_x) * g.mcus_y;
+    g.blocks        = mcus * g.blocks_per_mcu;
+    g.segments      = it.restart_interval ? (mcus + it.restart_interval - 1) / it.restart_interval : 1;
+    // every block at kMaxBlockBits, and less than a byte of padding ones per segment
+    g.stream_bound = (g.blocks * kMaxBlockBits + 7) / 8 + g.segments;
+    return g;
+}
+
+void put_segment(std::vector<uint8_t>& out, int marker, const uint8_t* payload, size_t len)
+{
+    out.push_back(0xFF);
+    out.push_back(uint8_t(marker));
+    out.push_back(uint8_t((len + 2) >> 8));
+    out.push_back(uint8_t(len + 2));
+    out.insert(out.end(), payload, payload + len);
+}
+
+/// SOI .. the end of SOS, as libjpeg writes it for Pillow.
+void write_header(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out)
+{
+    const int ncomp = it.channels;
+    // the factors that were asked for go into the frame header of a grey file too (Pillow sets them whatever the mode); with
+    // one component they change nothing else
+    const int hs = it.subsampling != JPEGGPU_EXT_SUBSAMPLING_444 ? 2 : 1, vs = it.subsampling == JPEGGPU_EXT_SUBSAMPLING_420 ? 2 : 1;
+    out.clear();
+    out.push_back(0xFF);
+    out.push_back(0xD8);
+    static const uint8_t jfif[14] = {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+    put_segment(out, 0xE0, jfif, sizeof jfif);
+    for (int t = 0; t < (ncomp == 1 ? 1 : 2); ++t) {
+        uint8_t q[64], seg[65];
+        quant_table(t ? kBaseChroma : kBaseLuma, it.quality, q);
+        seg[0] = uint8_t(t);
+        for (int k = 0; k < 64; ++k) seg[1 + k] = q[kNatural[k]];
+        put_segment(out, 0xDB, seg, sizeof seg);
+    }
+    uint8_t sof[6 + 9] = {8, uint8_t(it.height >> 8), uint8_t(it.height), uint8_t(it.width >> 8), uint8_t(it.width), uint8_t(ncomp)};
+    for (int c = 0; c < ncomp; ++c) {
+        sof[6 + 3 * c] = uint8_t(c + 1);
+        sof[7 + 3 * c] = uint8_t(c == 0 ? hs << 4 | vs : 0x11);
+        sof[8 + 3 * c] = uint8_t(c == 0 ? 0 : 1);
+    }
+    put_segment(out, 0xC0, sof, size_t(6 + 3 * ncomp));
+    const HuffSpec* specs[4] = {&kDcLuma, &kAcLuma, &kDcChroma, &kAcChroma};
+    const uint8_t ids[4]     = {0x00, 0x10, 0x01, 0x11};
+    for (int t = 0; t < (ncomp == 1 ? 2 : 4); ++t) {
+        uint8_t seg[1 + 16 + 162];
+        seg[0] = ids[t];
+        std::memcpy(seg + 1, specs[t]->bits, 16);
+        std::memcpy(seg + 17, specs[t]->values, size_t(specs[t]->count));
+        put_segment(out, 0xC4, seg, size_t(17 + specs[t]->count));
+    }
+    if (it.restart_interval) {
+        const uint8_t dri[2] = {uint8_t(it.restart_interval >> 8), uint8_t(it.restart_interval)};
+        put_segment(out, 0xDD, dri, 2);
+    }
+    uint8_t sos[1 + 6 + 3] = {uint8_t(ncomp)};
+    for (int c = 0; c < ncomp; ++c) {
+        sos[1 + 2 * c] = uint8_t(c + 1);
+        sos[2 + 2 * c] = uint8_t(c == 0 ? 0x00 : 0x11);
+    }
+    sos[1 + 2 * ncomp] = 0x00, sos[2 + 2 * ncomp] = 0x3F, sos[3 + 2 * ncomp] = 0x00;
+    put_segment(out, 0xDA, sos, size_t(4 + 2 * ncomp));
+}
+
+/// The plan of a call: every offset in d_scratch. JPEGGPU_NOT_SUPPORTED for an item or a call beyond the kernels' 32-bit
+/// bit offsets and block indices.
+jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan, std::vector<Item>* out_items, std::vector<std::vector<uint8_t>>* headers)
+{
+    if (!items || n <= 0 || n > 65535) return JPEGGPU_INVALID_ARGUMENT;
+    uint64_t tiles = 0, chunks = 0, header_bytes = 0;
+    std::vector<Geometry> geo(static_cast<size_t>(n));
+    std::vector<uint8_t> header;
+    for (int i = 0; i < n; ++i) {
+        if (!valid(&items[i])) return JPEGGPU_INVALID_ARGUMENT;
+        geo[i] = geometry(items[i]);
+        if (geo[i].stream_bound * 8 >= (uint64_t(1) << 32)) return JPEGGPU_NOT_SUPPORTED;
+        tiles += (geo[i].blocks + kTileBlocks - 1) / kTileBlocks;
+        chunks += (geo[i].stream_bound + kChunkBytes - 1) / kChunkBytes;
+        write_header(items[i], header);
+        header_bytes += align_up(header.size(), 16);
+        if (headers) headers->push_back(header);
+    }
+    if (tiles * kTileBlocks >= (uint64_t(1) << 31) || chunks >= (uint64_t(1) << 31)) return JPEGGPU_NOT_SUPPORTED;
+    plan.n      = n;
+    plan.tiles  = uint32_t(tiles);
+    plan.chunks = uint32_t(chunks);
+    uint64_t off = 0;
+    auto take    = [&off](uint64_t bytes) {
+        const uint64_t at = off;
+        off               = align_up(off + bytes, 256);
+        return at;
+    };
+    plan.tables_off       = take(sizeof(Tables));
+    plan.items_off        = take(sizeof(Item) * (size_t(n) + 1)); // and a sentinel
+    uint64_t header_off   = take(header_bytes);
+    plan.blob_bytes       = off;
+    plan.bits_off         = take(tiles * kTileBlocks * sizeof(uint32_t));
+    plan.tile_sum_off     = take(tiles * sizeof(Cursor));
+    plan.tile_before_off  = take(tiles * sizeof(Cursor));
+    plan.count_off        = take(chunks * sizeof(Count));
+    plan.count_before_off = take(chunks * sizeof(Count));
+    uint32_t tile = 0, chunk = 0;
+    if (out_items) out_items->resize(size_t(n) + 1);
+    for (int i = 0; i < n; ++i) {
+        const Geometry& g       = geo[i];
+        const uint64_t chunks_i = (g.stream_bound + kChunkBytes - 1) / kChunkBytes;
+        const uint64_t coef     = take(g.blocks * 128);
+        const uint64_t stream   = take(chunks_i * kChunkBytes);
+        const uint64_t starts   = take(chunks_i * (kChunkBytes / 8));
+        if (out_items) {
+            const jpeggpu_ext_encode_item& s = items[i];
+            Item& d                          = (*out_items)[i];
+            d                                = Item{};
+            d.src = s.data, d.out = s.out, d.capacity = s.capacity;
+            d.row_pitch = s.row_pitch, d.pixel_stride = s.pixel_stride, d.channel_stride = s.channel_stride;
+            d.coef_off = coef, d.stream_off = stream, d.starts_off = starts;
+            d.width = s.width, d.height = s.height, d.channels = s.channels;
+            d.hs = g.hs, d.vs = g.vs, d.mcus_x = g.mcus_x, d.mcus_y = g.mcus_y;
+            d.blocks_per_mcu = g.blocks_per_mcu, d.blocks = int(g.blocks);
+            d.grid_w = (s.width + 7) / 8, d.grid_h = (s.height + 7) / 8;
+            d.restart_interval = s.restart_interval;
+            d.tile_start = tile, d.chunk_start = chunk;
+            d.header_off = uint32_t(header_off), d.header_len = uint32_t((*headers)[i].size());
+            uint8_t q[64];
+            for (int t = 0; t < 2; ++t) {
+                quant_table(t ? kBaseChroma : kBaseLuma, s.quality, q);
+                for (int k = 0; k < 64; ++k) d.divisor[t][k] = uint16_t(8 * q[kNatural[k]]);
+            }
+            header_off += align_up((*headers)[i].size(), 16);
+        }
+        tile += uint32_t((g.blocks + kTileBlocks - 1) / kTileBlocks);
+        chunk += uint32_t(chunks_i);
+    }
+    if (out_items) {
+        Item& s       = (*out_items)[size_t(n)];
+        s             = Item{};
+        s.tile_start  = tile;
+        s.chunk_start = chunk;
+    }
+    plan.total = off;
+    return JPEGGPU_SUCCESS;
+}
+
+/// Page-locked staging of a call's blob: a ring of four per process, as the resize calls keep theirs. Never destroyed (the
+/// HIP runtime may be gone when static objects are).
+struct Staging {
+    static constexpr int kRing = 4;
+    std::mutex mu;
+    StagingBuffer buf[kRing];
+    hipEvent_t copied[kRing] = {};
+    bool in_use[kRing]       = {};
+    int next                 = 0;
+};
+Staging& staging()
+{
+    static Staging* s = new Staging;
+    return *s;
+}
+
+} // namespace
+} // namespace enc
+} // namespace jg
+
+using namespace jg::enc;
+
+extern "C" {
+
+enum jpeggpu_status jpeggpu_ext_encode_header(const struct jpeggpu_ext_encode_item* item, uint8_t* host_buf, size_t* size)
+{
+    if (!valid(item) || !size) return JPEGGPU_INVALID_ARGUMENT;
+    std::vector<uint8_t> header;
+    try {
+        write_header(*item, header);
+    } catch (const std::bad_alloc&) {
+        return JPEGGPU_OUT_OF_HOST_MEMORY;
+    }
+    const size_t room = *size;
+    *size             = header.size();
+    if (!host_buf) return JPEGGPU_SUCCESS;
+    if (room < header.size()) return JPEGGPU_INVALID_ARGUMENT;
+    std::memcpy(host_buf, header.data(), header.size());
+    return JPEGGPU_SUCCESS;
+}
+
+size_t jpeggpu_ext_encode_bound(const struct jpeggpu_ext_encode_item* item)
+{
+    if (!valid(item)) return 0;
+    (void)tables(); // checks kMaxBlockBits against the tables
+    const Geometry g = geometry(*item);
+    size_t header    = 0;
+    if (jpeggpu_ext_encode_header(item, nullptr, &header) != JPEGGPU_SUCCESS) return 0;
+    // the header; the stream with every byte 0xFF and stuffed; a marker between segments; EOI
+    return header + 2 * size_t(g.stream_bound) + 2 * size_t(g.segments - 1) + 2;
+}
+
+size_t jpeggpu_ext_encode_scratch_size(const struct jpeggpu_ext_encode_item* items, int n)
+{
+    Plan plan;
+    try {
+        if (make_plan(items, n, plan, nullptr, nullptr) != JPEGGPU_SUCCESS) return 0;
+    } catch (const std::bad_alloc&) {
+        return 0;
+    }
+    return size_t(plan.total) + 256; // room to align the caller's pointer
+}
+
+enum jpeggpu_status jpeggpu_ext_encode_batch(
+    const struct jpeggpu_ext_encode_item* items, int n, void* d_scratch, size_t scratch_size, size_t* d_sizes, int* d_status, jpeggpu_stream_t stream)
+{
+    if (!items || n <= 0 || !d_scratch || !d_sizes || !d_status) return JPEGGPU_INVALID_ARGUMENT;
+    for (int i = 0; i < n; ++i)
+        if (!valid(&items[i]) || !items[i].data || (!items[i].out && items[i].capacity)) return JPEGGPU_INVALID_ARGUMENT;
+    Plan plan;
+    std::vector<Item> dev;
+    std::vector<std::vector<uint8_t>> headers;
+    try {
+        const jpeggpu_status st = make_plan(items, n, plan, &dev, &headers);
+        if (st != JPEGGPU_SUCCESS) return st;
+    } catch (const std::bad_alloc&) {
+        return JPEGGPU_OUT_OF_HOST_MEMORY;
+    }
+    uint8_t* base = reinterpret_cast<uint8_t*>(jg::align_up(reinterpret_cast<uintptr_t>(d_scratch), 256));
+    if (size_t(base - static_cast<uint8_t*>(d_scratch)) + plan.total > scratch_size) return JPEGGPU_INVALID_ARGUMENT;
+
+    Staging& rs = staging();
+    std::lock_guard<std::mutex> lock(rs.mu);
+    const int r = rs.next;
+    // the staging buffer may still be the source of a copy enqueued kRing calls ago
+    if (rs.in_use[r] && hipEventSynchronize(rs.copied[r]) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
+    rs.in_use[r] = false;
+    if (!rs.buf[r].reserve(plan.blob_bytes)) return JPEGGPU_OUT_OF_HOST_MEMORY;
+    uint8_t* h = rs.buf[r].ptr;
+    std::memset(h, 0, plan.blob_bytes);
+    std::memcpy(h + plan.tables_off, &tables(), sizeof(Tables));
+    std::memcpy(h + plan.items_off, dev.data(), sizeof(Item) * dev.size());
+    for (int i = 0; i < n; ++i) std::memcpy(h + dev[i].header_off, headers[i].data(), headers[i].size());
+    if (!rs.copied[r] && hipEventCreateWithFlags(&rs.copied[r], hipEventDisableTiming) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
+    if (hipMemcpyAsync(base, h, plan.blob_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
+    if (hipEventRecord(rs.copied[r], stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
+    rs.in_use[r] = true;
+    rs.next      = (r + 1) % Staging::kRing;
+    if (launch_encode(plan, base, reinterpret_cast<unsigned long long*>(d_sizes), d_status, stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
+    return JPEGGPU_SUCCESS;
+}
+
+} // extern "C"

@@ -1,0 +1,89 @@
+// jg_encode.hpp -- the baseline encoder's tables and launch interface (jg_encode.hip; every launch is asynchronous on
+// `stream`). The host (jg_encode.cpp) plans a call into one blob of descriptors that travels to the device in one copy; the
+// kernels index everything by BLOCK (8 x 8 samples), the parallel unit of every stage.
+#ifndef JG_ENCODE_HPP_
+#define JG_ENCODE_HPP_
+
+#include <hip/hip_runtime_api.h>
+
+#include <cstddef>
+#include <cstdint>
+
+namespace jg {
+namespace enc {
+
+/// A workgroup of the block kernels owns a TILE of kTileBlocks consecutive blocks of ONE item's MCU stream (an item's first
+/// tile starts a new tile: `tile_start`). A workgroup of the byte kernels owns a CHUNK of kChunkBytes bytes of one item's
+/// unstuffed stream, kChunkLane bytes per lane. The two scans between the stages are one workgroup of kScanThreads lanes
+/// each, every lane walking a run of consecutive tiles (chunks).
+constexpr int kTileBlocks  = 256;
+constexpr int kChunkLane   = 32;
+constexpr int kChunkBytes  = 256 * kChunkLane;
+constexpr int kScanThreads = 128;
+
+/// The longest a block can get, from the longest codes of the four tables (Annex K.3 - K.6): a DC code of at most 11 bits
+/// (chroma, category 11) with 11 value bits, and 63 AC coefficients of at most a 16-bit code with 10 value bits each. A
+/// ZRL or an EOB replaces coefficients and is shorter than what it replaces (ZRL: 11 bits for 16 coefficients).
+constexpr int kMaxDcCode    = 11;
+constexpr int kMaxAcCode    = 16;
+constexpr int kMaxBlockBits = kMaxDcCode + 11 + 63 * (kMaxAcCode + 10); // 1660
+
+/// Position in the unstuffed stream as a function of the position before: what a run of blocks does to the bit cursor.
+/// A segment's first block starts on a byte, so the functions are  x + a  (kAdd),  roundup8(x + a) + b  (kRound) and the
+/// constant b (kConst: an item's first tile, whatever came before). They are closed under composition, which makes the
+/// segmented scan of the bit counts an ordinary scan.
+enum CursorKind : uint32_t { kAdd = 0, kRound = 1, kConst = 2 };
+struct Cursor {
+    uint32_t kind, a, b;
+};
+/// 0xFF bytes and segment starts of a run of chunks; `reset`: the run begins a new item.
+struct Count {
+    uint32_t reset, ff, starts;
+};
+
+/// One image of a call, as the kernels see it.
+struct Item {
+    const uint8_t* src;
+    uint8_t* out;
+    uint64_t capacity;
+    int64_t row_pitch, pixel_stride, channel_stride;
+    uint64_t coef_off;   // byte offsets in d_scratch: int16[blocks][64], zigzag order, MCU stream order
+    uint64_t stream_off; // the unstuffed stream, chunks * kChunkBytes, zeroed up to its length by the device
+    uint64_t starts_off; // one bit per byte of the unstuffed stream: a restart segment begins here
+    int width, height, channels;
+    int hs, vs;           // luma blocks per MCU, 1 x 1 for grey
+    int mcus_x, mcus_y;
+    int blocks_per_mcu, blocks;
+    int grid_w, grid_h;   // the luma component's real blocks: beyond them a block of an MCU is a dummy
+    int restart_interval; // MCUs, 0: none
+    uint32_t tile_start, chunk_start; // this item's first tile / chunk among the call's
+    uint32_t header_off, header_len;  // in the blob
+    uint16_t divisor[2][64];          // 8 * quantiser, zigzag order: luma, chroma
+};
+
+/// Encoder tables in the blob: code << 8 | length, index = table * 256 + symbol (DC: the category), tables luma, chroma.
+struct Tables {
+    uint32_t dc[2 * 16];
+    uint32_t ac[2 * 256];
+};
+
+/// Where the parts of a call sit in d_scratch (byte offsets; the blob is copied from the host, the rest the device's).
+struct Plan {
+    int n;
+    uint32_t tiles, chunks;
+    uint64_t tables_off, items_off; // in the blob
+    uint64_t blob_bytes;
+    uint64_t bits_off;        // uint32[tiles * kTileBlocks]
+    uint64_t tile_sum_off;    // Cursor[tiles]: each tile's own function
+    uint64_t tile_before_off; // Cursor[tiles]: everything before the tile, composed
+    uint64_t count_off;       // Count[chunks]
+    uint64_t count_before_off;
+    uint64_t total;
+};
+
+hipError_t launch_encode(const Plan& plan, uint8_t* d_scratch, unsigned long long* d_sizes, int* d_status, hipStream_t stream);
+
+} // namespace enc
+} // namespace jg
+
+#endif // JG_ENCODE_HPP_

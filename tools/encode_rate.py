@@ -1,0 +1,155 @@
+"""What encode_jpeg costs against the route a caller takes without it, in one process, the variants alternating inside every
+round (the method of tools/tensor_rate.py). Two workloads:
+
+  * "photos":  64 images of 4032 x 3024 RGB (BASELINE.json configs[2], decoded by this library), quality 75, 4:2:0, no restarts
+  * "resized": 256 images of 224 x 224 (decode_resized's output), quality 90, 4:2:0
+
+  * "device": jpeggpu_amd.encode_jpeg on the device tensors -- one jpeggpu_ext_encode_batch call, one synchronisation, the
+    files copied to the host;
+  * "host": the batch copied to the host and each image saved by Pillow on 16 threads -- what a caller does today. Without
+    Pillow: torchvision.io.encode_jpeg on the CPU tensors; without either the device numbers stand alone and no bar is drawn.
+Both are WALL time per call, the copy to the host included, medians of the rounds with their spread (max - min) in
+milliseconds. The bar: the device route is not slower than the host route by more than the two spreads. Before anything is
+timed the files of both routes are compared (Pillow: byte for byte).
+`--once WORKLOAD` runs a single device call and nothing else: the process to put under a kernel trace.
+Not bench.py: that one measures the flagship workload and stays as it is.
+
+    python tools/encode_rate.py [--rounds 7] [--iters 10] [--out encode_rate.json] [--once photos|resized]
+"""
+import argparse
+import io
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from tools.draft_rate import _spread  # noqa: E402
+
+THREADS = 16
+PILLOW_SUBSAMPLING = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}
+
+
+def _workload(torch, name):
+    import jpeggpu_amd
+    from tools import jpegsynth
+
+    cfg = [jpegsynth.config(2, seed=100 + s) for s in range(8)]
+    if name == "photos":
+        images = jpeggpu_amd.decode_batch_to_rgb([cfg[i % 8] for i in range(64)])
+        return [x.clone() for x in images], dict(quality=75, subsampling="4:2:0", restart_interval=0)
+    small = jpeggpu_amd.decode_resized([cfg[i % 8] for i in range(64)], 224)
+    batch = torch.cat([torch.roll(small, shifts=(7 * k, 11 * k), dims=(1, 2)) for k in range(4)])  # 256 different images
+    return batch.contiguous(), dict(quality=90, subsampling="4:2:0", restart_interval=0)
+
+
+def _host_route(torch, params):
+    """(name, fn(images) -> list of bytes) of the yardstick this machine has, or (None, None)."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    pool = ThreadPoolExecutor(THREADS)
+    try:
+        from PIL import Image
+
+        def save(a):
+            f = io.BytesIO()
+            Image.fromarray(a).save(f, "JPEG", quality=params["quality"], subsampling=PILLOW_SUBSAMPLING[params["subsampling"]],
+                                    restart_marker_blocks=params["restart_interval"])
+            return f.getvalue()
+
+        def fn(images):
+            host = [x.cpu().numpy() for x in images] if isinstance(images, list) else list(images.cpu().numpy())
+            return list(pool.map(save, host))
+
+        return "pillow", fn
+    except ImportError:
+        pass
+    try:
+        import torchvision.io as tio
+
+        def fn(images):
+            host = [x.cpu() for x in images] if isinstance(images, list) else list(images.cpu())
+            return list(pool.map(lambda x: tio.encode_jpeg(x.permute(2, 0, 1).contiguous(), quality=params["quality"]).numpy().tobytes(), host))
+
+        return "torchvision", fn
+    except ImportError:
+        return None, None
+
+
+def _wall(torch, fn, iters):
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t) * 1000 / iters
+
+
+def run(rounds, iters):
+    import torch
+
+    import jpeggpu_amd
+
+    out = []
+    for name in ("photos", "resized"):
+        images, params = _workload(torch, name)
+        n = len(images)
+        device = lambda: jpeggpu_amd.encode_jpeg(images, **params)  # noqa: E731
+        files = device()
+        route, host_fn = _host_route(torch, params)
+        variants = {"device": device}
+        if route:
+            theirs = host_fn(images)
+            if route == "pillow":
+                assert theirs == files, "the device's files are not Pillow's"
+            variants["host_" + route] = lambda: host_fn(images)
+        res = {k: [] for k in variants}
+        for _ in range(rounds):
+            for k, fn in variants.items():  # the variants alternate inside every round
+                res[k].append(_wall(torch, fn, iters))
+        r = {k: _spread(v) for k, v in res.items()}
+        entry = dict(workload=name, images=n, params=params, file_bytes=sum(len(f) for f in files), ms=r, yardstick=route, rounds=rounds, iters=iters)
+        if route:
+            d, h = r["device"], r["host_" + route]
+            entry["bar"] = {"spreads": round(d["spread"] + h["spread"], 4), "device_over_host": round(d["median"] / h["median"], 4),
+                            "holds": bool(d["median"] <= h["median"] + d["spread"] + h["spread"])}
+        out.append(entry)
+        del images, files
+        torch.cuda.empty_cache()
+    return out
+
+
+def once(name):
+    import torch
+
+    import jpeggpu_amd
+
+    images, params = _workload(torch, name)
+    files = jpeggpu_amd.encode_jpeg(images, **params)
+    torch.cuda.synchronize()
+    print(json.dumps(dict(workload=name, images=len(files), file_bytes=sum(len(f) for f in files))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--once", default=None, choices=("photos", "resized"))
+    a = ap.parse_args()
+    if a.once:
+        return once(a.once)
+    res = run(a.rounds, a.iters)
+    for r in res:
+        print(json.dumps(r), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
