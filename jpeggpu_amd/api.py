@@ -222,10 +222,10 @@ def lib():
     L.jpeggpu_ext_batch_set_profiling.argtypes = [C.c_void_p, C.c_int]
     L.jpeggpu_ext_batch_set_sync_iterations.argtypes = [C.c_void_p, C.c_int]
     L.jpeggpu_ext_batch_set_overlap.argtypes = [C.c_void_p, C.c_int]
-    L.jpeggpu_ext_batch_set_fused_tail.argtypes = [C.c_void_p, C.c_int]
-    if hasattr(L, "jpeggpu_ext_batch_set_sync_run"):  # (a library loaded through JPEGGPU_LIB may be older than this file)
-        L.jpeggpu_ext_batch_set_sync_run.argtypes = [C.c_void_p, C.c_int]
-    L.jpeggpu_ext_fused_tail_timeouts.argtypes = [C.POINTER(C.c_uint)]
+    for name, args in (("jpeggpu_ext_batch_set_fused_tail", [C.c_void_p, C.c_int]), ("jpeggpu_ext_batch_set_sync_run", [C.c_void_p, C.c_int]),
+                       ("jpeggpu_ext_fused_tail_timeouts", [C.POINTER(C.c_uint)])):
+        if hasattr(L, name):  # (a library loaded through JPEGGPU_LIB may be older than this file: _newer_symbol)
+            getattr(L, name).argtypes = args
     L.jpeggpu_ext_batch_get_stage_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.jpeggpu_ext_upsample_planes.argtypes = [
         C.POINTER(ImgInfo), C.POINTER(Img), C.POINTER(Img), C.c_int, C.c_int, C.c_void_p]
@@ -315,6 +315,24 @@ def status_string(status) -> str:
 def _check(status, where):
     if status != 0:
         raise JpegGpuError(status, where)
+
+
+def _newer_symbol(name):
+    """lib()'s function `name`, one of those a library loaded through JPEGGPU_LIB may predate: a RuntimeError that names it
+    where it is missing."""
+    if not hasattr(lib(), name):
+        raise RuntimeError("this libjpeggpu has no %s" % name)
+    return getattr(lib(), name)
+
+
+def _img(planes, pitches=None):
+    """An Img of plane pointers and their pitches, or (no pitches) of the planes as 2-D tensors."""
+    if pitches is None:
+        planes, pitches = [p.data_ptr() for p in planes], [p.stride(0) for p in planes]
+    img = Img()
+    for c, (p, pitch) in enumerate(zip(planes, pitches)):
+        img.image[c], img.pitch[c] = p, pitch
+    return img
 
 
 def _host_buffer(data):
@@ -457,11 +475,7 @@ class Decoder:
         _check(lib().jpeggpu_decoder_transfer(self._h, d_tmp, tmp_size, stream), "jpeggpu_decoder_transfer")
 
     def decode(self, planes, pitches, d_tmp: int, tmp_size: int, stream: int = 0):
-        img = Img()
-        for c, (p, pitch) in enumerate(zip(planes, pitches)):
-            img.image[c] = p
-            img.pitch[c] = pitch
-        _check(lib().jpeggpu_decoder_decode(self._h, C.byref(img), d_tmp, tmp_size, stream), "jpeggpu_decoder_decode")
+        _check(lib().jpeggpu_decoder_decode(self._h, C.byref(_img(planes, pitches)), d_tmp, tmp_size, stream), "jpeggpu_decoder_decode")
 
     def set_profiling(self, on: bool):
         _check(lib().jpeggpu_ext_set_profiling(self._h, int(on)), "jpeggpu_ext_set_profiling")
@@ -506,13 +520,9 @@ class Batch:
         arr = (BatchItem * n)()
         imgs = []
         for i, (dec, ptrs, pitches, d_tmp, tmp_size) in enumerate(entries):
-            img = Img()
-            for c, (p, pitch) in enumerate(zip(ptrs, pitches)):
-                img.image[c] = p
-                img.pitch[c] = pitch
-            imgs.append(img)
+            imgs.append(_img(ptrs, pitches))
             arr[i].decoder = dec._h
-            arr[i].img = C.pointer(img)
+            arr[i].img = C.pointer(imgs[i])
             arr[i].d_tmp = d_tmp
             arr[i].tmp_size = tmp_size
         self._items, self._keep = arr, (imgs, entries)
@@ -525,13 +535,11 @@ class Batch:
         _check(lib().jpeggpu_ext_batch_set_overlap(self._h, parts), "jpeggpu_ext_batch_set_overlap")
 
     def set_fused_tail(self, enable: bool):
-        _check(lib().jpeggpu_ext_batch_set_fused_tail(self._h, 1 if enable else 0), "jpeggpu_ext_batch_set_fused_tail")
+        _check(_newer_symbol("jpeggpu_ext_batch_set_fused_tail")(self._h, 1 if enable else 0), "jpeggpu_ext_batch_set_fused_tail")
 
     def set_sync_run(self, r: int):
         """Consecutive subsequences a lane of the batched sequence kernel owns: 1, 2 or 4 (jpeggpu_ext.h)."""
-        if not hasattr(lib(), "jpeggpu_ext_batch_set_sync_run"):
-            raise RuntimeError("this libjpeggpu has no jpeggpu_ext_batch_set_sync_run")
-        _check(lib().jpeggpu_ext_batch_set_sync_run(self._h, int(r)), "jpeggpu_ext_batch_set_sync_run")
+        _check(_newer_symbol("jpeggpu_ext_batch_set_sync_run")(self._h, int(r)), "jpeggpu_ext_batch_set_sync_run")
 
     def set_sync_iterations(self, n: int):
         _check(lib().jpeggpu_ext_batch_set_sync_iterations(self._h, n), "jpeggpu_ext_batch_set_sync_iterations")
@@ -559,7 +567,7 @@ class Batch:
 def fused_tail_timeouts() -> int:
     """Writers of the fused tail + write launch that gave up waiting, since the library was loaded (0 on a correct run)."""
     n = C.c_uint(0)
-    _check(lib().jpeggpu_ext_fused_tail_timeouts(C.byref(n)), "jpeggpu_ext_fused_tail_timeouts")
+    _check(_newer_symbol("jpeggpu_ext_fused_tail_timeouts")(C.byref(n)), "jpeggpu_ext_fused_tail_timeouts")
     return n.value
 
 
@@ -665,6 +673,39 @@ def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp
         dec.cleanup()
 
 
+def _to_rgb(stem, planes, info, crop_info, device, fancy, replicate, color, orientation):
+    """planes_to_rgb's and crop_to_rgb's body. The entry point is `stem` + _oriented with an orientation, else `stem` +
+    _replicate / _fancy / nothing, + _cs with a colour; without `crop_info` it converts the whole image and is told its size."""
+    import torch
+
+    n = info.num_components
+    device = planes[0].device if device is None else torch.device(device)
+    src = _img(planes[:n])
+    w, h = _frame_size(info) if crop_info is None else (crop_info.width, crop_info.height)
+    if not (fancy or replicate) and (orientation is not None or color is not None):
+        raise ValueError("the reference's helper (fancy=False) takes no %s" % ("orientation" if orientation is not None else "colour model"))
+    if orientation is not None:
+        name = stem + "_oriented"
+        cs = int(color) if color is not None else int(_item_colors(None, [info])[0])
+        model = (cs, int(orientation), int(bool(replicate)))
+        ow, oh = (h, w) if 5 <= int(orientation) <= 8 else (w, h)
+    else:
+        name = stem + ("_replicate" if replicate else "_fancy" if fancy else "") + ("_cs" if color is not None else "")
+        model = (int(color),) if color is not None else ()
+        ow, oh = w, h
+    # the C signatures, by what `stem` and `name` select (jpeggpu_ext.h):
+    #   planes_to_rgbi[_fancy|_replicate]     (info,                             src, out, pitch, width, height, stream)
+    #   planes_to_rgbi_{fancy,replicate}_cs   (info, color,                      src, out, pitch, width, height, stream)
+    #   planes_to_rgbi_oriented               (info, color, orientation, repl.,  src, out, pitch, width, height, stream)
+    #   crop_to_rgbi_{fancy,replicate}        (info,                       crop, src, out, pitch, stream)
+    #   crop_to_rgbi_{fancy,replicate}_cs     (info, color,                crop, src, out, pitch, stream)
+    #   crop_to_rgbi_oriented                 (info, color, orientation, repl., crop, src, out, pitch, stream)
+    source, size = ((C.byref(src),), (w, h)) if crop_info is None else ((C.byref(crop_info), C.byref(src)), ())
+    out = torch.empty((oh, ow, 3), dtype=torch.uint8, device=device)
+    _check(getattr(lib(), name)(C.byref(info), *model, *source, out.data_ptr(), 3 * ow, *size, torch.cuda.current_stream(device).cuda_stream), name)
+    return out
+
+
 def planes_to_rgb(planes, info, fancy=True, device=None, replicate=False, color=None, orientation=None):
     """Planes of a 1- or 3-component image (as decode_to_planes returns them) -> (H, W, 3) uint8 tensor at the full image
     size, on torch's current stream: jpeggpu_ext_planes_to_rgbi_fancy (libjpeg's fancy upsampling and integer colour
@@ -674,35 +715,7 @@ def planes_to_rgb(planes, info, fancy=True, device=None, replicate=False, color=
     converts RGB-, CMYK- and YCCK-coded files (four planes); None: grey or YCbCr by the number of components.
     `orientation`: an EXIF orientation 1..8 (Decoder.orientation) -- jpeggpu_ext_planes_to_rgbi_oriented, the displayed
     image: (W, H, 3) for 5..8."""
-    import torch
-
-    n = info.num_components
-    device = planes[0].device if device is None else torch.device(device)
-    width, height = _frame_size(info)
-    src = Img()
-    for c in range(n):
-        src.image[c], src.pitch[c] = planes[c].data_ptr(), planes[c].stride(0)
-    if orientation is not None:
-        if not (fancy or replicate):
-            raise ValueError("the reference's helper (fancy=False) takes no orientation")
-        ow, oh = (height, width) if 5 <= int(orientation) <= 8 else (width, height)
-        out = torch.empty((oh, ow, 3), dtype=torch.uint8, device=device)
-        cs = int(color) if color is not None else (int(ColorSpace.GRAY) if n == 1 else int(ColorSpace.YCBCR) if n == 3 else 0)
-        _check(lib().jpeggpu_ext_planes_to_rgbi_oriented(C.byref(info), cs, int(orientation), int(bool(replicate)), C.byref(src), out.data_ptr(),
-                                                         3 * ow, width, height, torch.cuda.current_stream(device).cuda_stream),
-               "jpeggpu_ext_planes_to_rgbi_oriented")
-        return out
-    out = torch.empty((height, width, 3), dtype=torch.uint8, device=device)
-    stream = torch.cuda.current_stream(device).cuda_stream
-    name = "jpeggpu_ext_planes_to_rgbi_replicate" if replicate else "jpeggpu_ext_planes_to_rgbi_fancy" if fancy else "jpeggpu_ext_planes_to_rgbi"
-    if color is not None:
-        if not (fancy or replicate):
-            raise ValueError("the reference's helper (fancy=False) takes no colour model")
-        name += "_cs"
-        _check(getattr(lib(), name)(C.byref(info), int(color), C.byref(src), out.data_ptr(), 3 * width, width, height, stream), name)
-        return out
-    _check(getattr(lib(), name)(C.byref(info), C.byref(src), out.data_ptr(), 3 * width, width, height, stream), name)
-    return out
+    return _to_rgb("jpeggpu_ext_planes_to_rgbi", planes, info, None, device, fancy, replicate, color, orientation)
 
 
 def crop_to_rgb(planes, info, crop_info, device=None, replicate=False, color=None, orientation=None):
@@ -710,31 +723,7 @@ def crop_to_rgb(planes, info, crop_info, device=None, replicate=False, color=Non
     equal to that part of planes_to_rgb's image of the uncropped planes (jpeggpu_ext_crop_to_rgbi_fancy, or with
     `replicate` jpeggpu_ext_crop_to_rgbi_replicate). `color`: as in planes_to_rgb. `orientation`: as in planes_to_rgb --
     crop_info is the STORED rectangle (orient_rect), the result the displayed one (jpeggpu_ext_crop_to_rgbi_oriented)."""
-    import torch
-
-    n = info.num_components
-    device = planes[0].device if device is None else torch.device(device)
-    src = Img()
-    for c in range(n):
-        src.image[c], src.pitch[c] = planes[c].data_ptr(), planes[c].stride(0)
-    w, h = crop_info.width, crop_info.height
-    if orientation is not None:
-        ow, oh = (h, w) if 5 <= int(orientation) <= 8 else (w, h)
-        out = torch.empty((oh, ow, 3), dtype=torch.uint8, device=device)
-        cs = int(color) if color is not None else (int(ColorSpace.GRAY) if n == 1 else int(ColorSpace.YCBCR) if n == 3 else 0)
-        _check(lib().jpeggpu_ext_crop_to_rgbi_oriented(C.byref(info), cs, int(orientation), int(bool(replicate)), C.byref(crop_info), C.byref(src),
-                                                       out.data_ptr(), 3 * ow, torch.cuda.current_stream(device).cuda_stream),
-               "jpeggpu_ext_crop_to_rgbi_oriented")
-        return out
-    out = torch.empty((h, w, 3), dtype=torch.uint8, device=device)
-    stream = torch.cuda.current_stream(device).cuda_stream
-    name = "jpeggpu_ext_crop_to_rgbi_replicate" if replicate else "jpeggpu_ext_crop_to_rgbi_fancy"
-    if color is not None:
-        name += "_cs"
-        _check(getattr(lib(), name)(C.byref(info), int(color), C.byref(crop_info), C.byref(src), out.data_ptr(), 3 * w, stream), name)
-        return out
-    _check(getattr(lib(), name)(C.byref(info), C.byref(crop_info), C.byref(src), out.data_ptr(), 3 * w, stream), name)
-    return out
+    return _to_rgb("jpeggpu_ext_crop_to_rgbi", planes, info, crop_info, device, True, replicate, color, orientation)
 
 
 def _needs_replication(info, scale):
@@ -827,9 +816,7 @@ def _resize_items(planes_list, infos, crop_infos):
     items = (ResizeItem * n)()
     keep = []
     for i in range(n):
-        src = Img()
-        for c, p in enumerate(planes_list[i]):
-            src.image[c], src.pitch[c] = p.data_ptr(), p.stride(0)
+        src = _img(planes_list[i])
         ci = crop_infos[i] if crop_infos is not None else None
         items[i].info = C.pointer(infos[i])
         items[i].crop = C.pointer(ci) if ci is not None else None
@@ -851,67 +838,6 @@ def _item_colors(colors, infos):
     return [ColorSpace.GRAY if i.num_components == 1 else ColorSpace.YCBCR if i.num_components == 3 else ColorSpace.UNKNOWN for i in infos]
 
 
-def resize_scratch_size(planes_list, infos, size, crop_infos=None, filt="bilinear", colors=None, orientations=None):
-    """jpeggpu_ext_resize_scratch_size of these items (0 if the call would refuse them); with `colors` (one ColorSpace
-    per item) jpeggpu_ext_resize_scratch_size_cs; with `orientations` jpeggpu_ext_resize_scratch_size_oriented."""
-    h, w = _size_hw(size)
-    items, _keep = _resize_items(planes_list, infos, crop_infos)
-    if orientations is not None:
-        n = len(planes_list)
-        return lib().jpeggpu_ext_resize_scratch_size_oriented(items, _color_array(_item_colors(colors, infos), n), _color_array(orientations, n),
-                                                              n, w, h, FILTERS[filt])
-    if colors is not None:
-        return lib().jpeggpu_ext_resize_scratch_size_cs(items, _color_array(colors, len(planes_list)), len(planes_list), w, h, FILTERS[filt])
-    return lib().jpeggpu_ext_resize_scratch_size(items, len(planes_list), w, h, FILTERS[filt])
-
-
-def resize_to_rgb(planes_list, infos, size, crop_infos=None, filt="bilinear", layout="NHWC", out=None, colors=None, orientations=None):
-    """jpeggpu_ext_resize_to_rgb on torch's current stream: every decoded image i
-    (planes_list[i], infos[i], and crop_infos[i] from a cropped decode, or None for the whole image) resampled to `size`
-    (int: square; (h, w)) with Pillow's BILINEAR or BICUBIC arithmetic. Returns a uint8 tensor of n x h x w x 3 ("NHWC")
-    or n x 3 x h x w ("NCHW"), `out` if given (contiguous, of that shape). `colors`: each image's ColorSpace
-    (Decoder.color_space; jpeggpu_ext_resize_to_rgb_cs -- a call may mix grey, YCbCr, RGB, CMYK and YCCK items); None: grey
-    or YCbCr by the number of components. `orientations`: each image's EXIF orientation 1..8
-    (jpeggpu_ext_resize_to_rgb_oriented): crop_infos are the STORED rectangles (orient_rect), and the result is the
-    DISPLAYED rectangle resized, as Pillow resizes ImageOps.exif_transpose's image."""
-    import torch
-
-    if filt not in FILTERS:
-        raise ValueError("filter %r is not one of %s" % (filt, ", ".join(FILTERS)))
-    if layout not in LAYOUTS:
-        raise ValueError("layout %r is not one of %s" % (layout, ", ".join(LAYOUTS)))
-    h, w = _size_hw(size)
-    n = len(planes_list)
-    device = planes_list[0][0].device
-    items, _keep = _resize_items(planes_list, infos, crop_infos)
-    shape = (n, h, w, 3) if layout == "NHWC" else (n, 3, h, w)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=device)
-    elif tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous():
-        raise ValueError("out must be a contiguous uint8 tensor of shape %s" % (shape,))
-    stream = torch.cuda.current_stream(device).cuda_stream
-    if orientations is not None:
-        cs, os_ = _color_array(_item_colors(colors, infos), n), _color_array(orientations, n)
-        need = lib().jpeggpu_ext_resize_scratch_size_oriented(items, cs, os_, n, w, h, FILTERS[filt])
-        scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
-        _check(lib().jpeggpu_ext_resize_to_rgb_oriented(items, cs, os_, n, w, h, FILTERS[filt], LAYOUTS[layout], out.data_ptr(),
-                                                        scratch.data_ptr(), need, stream), "jpeggpu_ext_resize_to_rgb_oriented")
-        return out
-    if colors is not None:
-        cs = _color_array(colors, n)
-        need = lib().jpeggpu_ext_resize_scratch_size_cs(items, cs, n, w, h, FILTERS[filt])
-        scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
-        _check(lib().jpeggpu_ext_resize_to_rgb_cs(items, cs, n, w, h, FILTERS[filt], LAYOUTS[layout], out.data_ptr(), scratch.data_ptr(),
-                                                  need, stream), "jpeggpu_ext_resize_to_rgb_cs")
-        return out
-    need = lib().jpeggpu_ext_resize_scratch_size(items, n, w, h, FILTERS[filt])
-    scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
-    _check(lib().jpeggpu_ext_resize_to_rgb(items, n, w, h, FILTERS[filt], LAYOUTS[layout], out.data_ptr(), scratch.data_ptr(),
-                                           need, stream), "jpeggpu_ext_resize_to_rgb")
-    # the scratch tensor is freed by torch's caching allocator in stream order: it is not reused before the launches ran
-    return out
-
-
 def _channel_triple(v, default, name):
     """Normalize's per-channel argument as three floats: None (the default), one number for all, or three."""
     if v is None:
@@ -923,6 +849,99 @@ def _channel_triple(v, default, name):
     if len(v) != 3:
         raise ValueError("%s must be one number or three" % name)
     return v
+
+
+def _resize_plan(planes_list, infos, size, crop_infos, filt, layout="NHWC", colors=None, orientations=None, views=None, replicates=None,
+                 dtype=None, flips=None):
+    """What the batched resize wrappers share ahead of a launch. The arguments are checked before a device or `infos` is
+    touched: the filter, the layout, the dtype (None: a uint8 RGB call), then that every per-image list has one entry per
+    image. Returns (sizer, call, lead, dims, keep): the scratch-size function and the uint8 entry point paired with it --
+    jpeggpu_ext_resize_scratch_size / jpeggpu_ext_resize_to_rgb, their _cs forms with `colors`, their _oriented forms with
+    `orientations`; with `views` jpeggpu_ext_resize_view_scratch_size / jpeggpu_ext_resize_view_to_tensor --, the arrays both
+    take first, (n, w, h, filter) that follow them, and what must outlive the call."""
+    if filt not in FILTERS:
+        raise ValueError("filter %r is not one of %s" % (filt, ", ".join(FILTERS)))
+    if layout not in LAYOUTS:
+        raise ValueError("layout %r is not one of %s" % (layout, ", ".join(LAYOUTS)))
+    if dtype is not None and dtype not in TENSOR_TYPES:
+        raise ValueError("dtype %r is not one of %s" % (dtype, ", ".join(TENSOR_TYPE_NAMES)))
+    n = len(planes_list)
+    for name, v in (("infos", infos), ("views", views), ("crop_infos", crop_infos), ("colors", colors), ("orientations", orientations),
+                    ("replicates", replicates), ("flips", flips)):
+        if v is not None and len(v) != n:
+            raise ValueError("%s must have one entry per image" % name)
+    h, w = _size_hw(size)
+    items, keep = _resize_items(planes_list, infos, crop_infos)
+    if orientations is not None and views is None:
+        colors = _item_colors(colors, infos)  # (the oriented calls take no NULL for the colours)
+    cs = _color_array(colors, n) if colors is not None else None
+    os_ = _color_array(orientations, n) if orientations is not None else None
+    if views is not None:
+        vs = (ResizeView * n)(*[_view_struct(views[i], replicates[i] if replicates is not None else False) for i in range(n)])
+        sizer, call, lead = "jpeggpu_ext_resize_view_scratch_size", "jpeggpu_ext_resize_view_to_tensor", (items, cs, os_, vs)
+    else:
+        form = "_oriented" if os_ is not None else "_cs" if cs is not None else ""
+        sizer, call = "jpeggpu_ext_resize_scratch_size" + form, "jpeggpu_ext_resize_to_rgb" + form
+        lead = tuple(a for a in (items, cs, os_) if a is not None)  # (each form takes the arrays it is named for)
+    return sizer, call, lead, (n, w, h, FILTERS[filt]), keep
+
+
+def _resize(planes_list, infos, size, crop_infos, filt, layout, colors=None, orientations=None, views=None, replicates=None, tensor=None,
+            out=None):
+    """The one launch path of the batched resize calls, on torch's current stream. `tensor`: None -- the uint8 RGB call
+    _resize_plan names -- or (dtype, mean, std, flips): jpeggpu_ext_resize_to_tensor (with `views`
+    jpeggpu_ext_resize_view_to_tensor), whose scratch is the uint8 call's, by the arguments given."""
+    import torch
+
+    dtype, mean, std, flips = tensor if tensor is not None else (None, None, None, None)
+    sizer, call, lead, dims, _keep = _resize_plan(planes_list, infos, size, crop_infos, filt, layout, colors, orientations, views, replicates,
+                                                  dtype, flips)
+    n, w, h, _ = dims
+    spec, args = (), lead  # (the uint8 and the view calls take the arrays their sizer takes)
+    if tensor is not None:
+        ts = TensorSpec()
+        ts.type = TENSOR_TYPES[dtype]
+        ts.mean[:] = _channel_triple(mean, 0.0, "mean")
+        ts.std[:] = _channel_triple(std, 1.0, "std")
+        if flips is not None:
+            flip_bytes = (C.c_ubyte * n)(*[1 if f else 0 for f in flips])
+            ts.flips = C.cast(flip_bytes, C.POINTER(C.c_ubyte))
+        spec = (C.byref(ts),)
+        if views is None:
+            call, args = "jpeggpu_ext_resize_to_tensor", (lead + (None, None))[:3]  # (items, colours or NULL, orientations or NULL)
+    else:
+        dtype = torch.uint8
+    device = planes_list[0][0].device
+    shape = (n, h, w, 3) if layout == "NHWC" else (n, 3, h, w)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=device)
+    elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous():
+        raise ValueError("out must be a contiguous %s tensor of shape %s" % ("uint8" if tensor is None else dtype, shape))
+    need = getattr(lib(), sizer)(*lead, *dims)
+    scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    _check(getattr(lib(), call)(*args, *dims, LAYOUTS[layout], *spec, out.data_ptr(), scratch.data_ptr(), need,
+                                torch.cuda.current_stream(device).cuda_stream), call)
+    # the scratch tensor is freed by torch's caching allocator in stream order: it is not reused before the launches ran
+    return out
+
+
+def resize_scratch_size(planes_list, infos, size, crop_infos=None, filt="bilinear", colors=None, orientations=None):
+    """jpeggpu_ext_resize_scratch_size of these items (0 if the call would refuse them); with `colors` (one ColorSpace
+    per item) jpeggpu_ext_resize_scratch_size_cs; with `orientations` jpeggpu_ext_resize_scratch_size_oriented."""
+    sizer, _, lead, dims, _keep = _resize_plan(planes_list, infos, size, crop_infos, filt, colors=colors, orientations=orientations)
+    return getattr(lib(), sizer)(*lead, *dims)
+
+
+def resize_to_rgb(planes_list, infos, size, crop_infos=None, filt="bilinear", layout="NHWC", out=None, colors=None, orientations=None):
+    """jpeggpu_ext_resize_to_rgb on torch's current stream: every decoded image i
+    (planes_list[i], infos[i], and crop_infos[i] from a cropped decode, or None for the whole image) resampled to `size`
+    (int: square; (h, w)) with Pillow's BILINEAR or BICUBIC arithmetic. Returns a uint8 tensor of n x h x w x 3 ("NHWC")
+    or n x 3 x h x w ("NCHW"), `out` if given (contiguous, of that shape). `colors`: each image's ColorSpace
+    (Decoder.color_space; jpeggpu_ext_resize_to_rgb_cs -- a call may mix grey, YCbCr, RGB, CMYK and YCCK items); None: grey
+    or YCbCr by the number of components. `orientations`: each image's EXIF orientation 1..8
+    (jpeggpu_ext_resize_to_rgb_oriented): crop_infos are the STORED rectangles (orient_rect), and the result is the
+    DISPLAYED rectangle resized, as Pillow resizes ImageOps.exif_transpose's image."""
+    return _resize(planes_list, infos, size, crop_infos, filt, layout, colors, orientations, out=out)
 
 
 def resize_to_tensor(planes_list, infos, size, crop_infos=None, filt="bilinear", layout="NHWC", colors=None, orientations=None, dtype=None,
@@ -938,47 +957,123 @@ def resize_to_tensor(planes_list, infos, size, crop_infos=None, filt="bilinear",
     (contiguous, of that shape and dtype)."""
     import torch
 
-    if filt not in FILTERS:
-        raise ValueError("filter %r is not one of %s" % (filt, ", ".join(FILTERS)))
-    if layout not in LAYOUTS:
-        raise ValueError("layout %r is not one of %s" % (layout, ", ".join(LAYOUTS)))
-    dtype = torch.float32 if dtype is None else dtype
-    if dtype not in TENSOR_TYPES:
-        raise ValueError("dtype %r is not one of %s" % (dtype, ", ".join(TENSOR_TYPE_NAMES)))
-    h, w = _size_hw(size)
-    n = len(planes_list)
-    device = planes_list[0][0].device
-    items, _keep = _resize_items(planes_list, infos, crop_infos)
-    spec = TensorSpec()
-    spec.type = TENSOR_TYPES[dtype]
-    spec.mean[:] = _channel_triple(mean, 0.0, "mean")
-    spec.std[:] = _channel_triple(std, 1.0, "std")
-    flip_bytes = None
-    if flips is not None:
-        if len(flips) != n:
-            raise ValueError("flips must have one entry per image")
-        flip_bytes = (C.c_ubyte * n)(*[1 if f else 0 for f in flips])
-        spec.flips = C.cast(flip_bytes, C.POINTER(C.c_ubyte))
-    shape = (n, h, w, 3) if layout == "NHWC" else (n, 3, h, w)
-    if out is None:
-        out = torch.empty(shape, dtype=dtype, device=device)
-    elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous():
-        raise ValueError("out must be a contiguous %s tensor of shape %s" % (dtype, shape))
-    cs = os_ = None
-    if orientations is not None:  # the scratch is the uint8 call's, by the arguments given
-        cs, os_ = _color_array(_item_colors(colors, infos), n), _color_array(orientations, n)
-        need = lib().jpeggpu_ext_resize_scratch_size_oriented(items, cs, os_, n, w, h, FILTERS[filt])
-    elif colors is not None:
-        cs = _color_array(colors, n)
-        need = lib().jpeggpu_ext_resize_scratch_size_cs(items, cs, n, w, h, FILTERS[filt])
-    else:
-        need = lib().jpeggpu_ext_resize_scratch_size(items, n, w, h, FILTERS[filt])
-    scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
-    _check(lib().jpeggpu_ext_resize_to_tensor(items, cs, os_, n, w, h, FILTERS[filt], LAYOUTS[layout], C.byref(spec), out.data_ptr(),
-                                              scratch.data_ptr(), need, torch.cuda.current_stream(device).cuda_stream),
-           "jpeggpu_ext_resize_to_tensor")
-    # the scratch tensor is freed by torch's caching allocator in stream order: it is not reused before the launches ran
-    return out
+    return _resize(planes_list, infos, size, crop_infos, filt, layout, colors, orientations,
+                   tensor=(torch.float32 if dtype is None else dtype, mean, std, flips), out=out)
+
+
+class BatchDecode:
+    """The front half of every batched pipeline: a list of JPEGs decoded to planes by ONE jpeggpu_ext_decode_batch call on
+    torch's current stream of `device`. Construction gives every file its Decoder with the settings below, parses its
+    header, allocates its planes and its 256-aligned tmp buffer and enqueues its transfer at once (the copies overlap the
+    parsing of the files behind it); then it creates the Batch for the summed num_scans with its scratch. decode() enqueues
+    the one batch call; transfer() enqueues the copies again, for a caller that decodes repeatedly. Nothing synchronises.
+    close() cleans up the decoders and destroys the batch (again: no effect), after which decode() and transfer() raise a
+    RuntimeError and only the planes and records remain of use; `with` closes, and a construction that fails part-way
+    closes what it made before the exception leaves. An empty `datas` is refused by jpeggpu_ext_batch_create
+    (JpegGpuError, INVALID_ARGUMENT).
+
+    `hint`: Decoder.set_batch_hint (default: the number of files). `idct`: "islow" (libjpeg-turbo's) or "reference".
+    `progressive`: progressive files are taken. `scales[i]` in 1, 2, 4, 8 (default 1) with `scale_mode` ("libjpeg", or
+    "uniform") where the scale is not 1. `crops[i]`: the STORED rectangle (x, y, w, h) at the scale to decode, or None for
+    the whole image. `crop_hooks[i]`: a function for the rectangles that depend on the header -- the file is parsed once
+    for it, hook(i, decoder, stored_w, stored_h) returns the stored rectangle or None (in place of crops[i]), and the
+    header is parsed again with it; None: no first parse.
+
+    Per file, in order: `decoders`, `planes` (lists of uint8 tensors), `infos`, `crop_infos` (None where no rectangle was
+    set), `colors`, `orientations` (the file's own EXIF orientation), `replicates` (where libjpeg replicates instead of
+    fancy upsampling) and `tmps`; `transferred_bytes` is what one round of transfers copies, `batch` the Batch."""
+
+    def __init__(self, datas, device="cuda:0", hint=None, idct="islow", progressive=True, scales=None, scale_mode="libjpeg", crops=None,
+                 crop_hooks=None):
+        import torch
+
+        dev = torch.device(device)
+        self._stream = torch.cuda.current_stream(dev).cuda_stream
+        self.decoders, self.planes, self.infos, self.crop_infos, self.tmps, self._entries = [], [], [], [], [], []
+        self.colors, self.orientations, self.replicates = [], [], []
+        self.transferred_bytes, self.batch = 0, None
+        try:
+            scans = 0
+            for i, data in enumerate(datas):
+                dec = Decoder()
+                self.decoders.append(dec)
+                dec.set_batch_hint(len(datas) if hint is None else hint)
+                dec.set_idct(idct)
+                dec.set_progressive(progressive)
+                scale = 1 if scales is None else scales[i]
+                if scale != 1:
+                    dec.set_scale(scale)
+                    dec.set_scale_mode(scale_mode)
+                crop = crops[i] if crops is not None else None
+                if crop_hooks is not None and crop_hooks[i] is not None:
+                    crop = crop_hooks[i](i, dec, *_frame_size(dec.parse_header(data)))
+                if crop is not None:
+                    dec.set_crop(*crop)
+                info = dec.parse_header(data)
+                lay = dec.layout()
+                scans += lay.num_scans
+                self.transferred_bytes += lay.transferred_bytes
+                nb = dec.get_buffer_size()
+                tmp = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
+                base = _align256(tmp.data_ptr())
+                planes = [torch.empty((info.sizes_y[c], info.sizes_x[c]), dtype=torch.uint8, device=dev)
+                          for c in range(info.num_components)]
+                dec.transfer(base, nb, self._stream)
+                self.tmps.append(tmp)
+                self._entries.append((dec, [p.data_ptr() for p in planes], [p.stride(0) for p in planes], base, nb))
+                self.planes.append(planes)
+                self.infos.append(info)
+                self.crop_infos.append(dec.crop_info() if crop is not None else None)
+                self.colors.append(dec.color_space())
+                self.orientations.append(dec.orientation())
+                self.replicates.append(_needs_replication(info, scale))
+            self.batch = Batch(scans)
+            self._scratch = torch.empty(self.batch.scratch_size, dtype=torch.uint8, device=dev)
+            self.batch.set_items(self._entries)
+        except BaseException:
+            self.close()
+            raise
+
+    def _open(self):
+        if not self.batch._h:
+            raise RuntimeError("this BatchDecode is closed")
+
+    def transfer(self):
+        self._open()
+        for dec, _, _, base, nb in self._entries:
+            dec.transfer(base, nb, self._stream)
+
+    def decode(self):
+        self._open()
+        self.batch.decode(self._scratch.data_ptr(), self._stream)
+
+    def close(self):
+        if self.batch is not None:
+            self.batch.destroy()
+        for dec in self.decoders:
+            dec.cleanup()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _displayed_crops(crops):
+    """BatchDecode's crop_hooks for crops given in DISPLAYED coordinates: orient_rect by the file's orientation."""
+    return [None if crop is None else lambda i, dec, w, h, crop=crop: orient_rect(dec.orientation(), w, h, crop) for crop in crops]
+
+
+def _per_image_args(n, crops, scales):
+    """The pipelines' `crops` and `scales` as lists of n entries."""
+    crops = [None] * n if crops is None else list(crops)
+    if len(crops) != n:
+        raise ValueError("crops must have one entry per image")
+    scales = [1] * n if scales is None else [int(s) for s in scales]
+    if len(scales) != n or any(s not in (1, 2, 4, 8) for s in scales):
+        raise ValueError("scales must have one entry of 1, 2, 4 or 8 per image")
+    return crops, scales
 
 
 def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", device="cuda:0", scales=None, exif_transpose=False,
@@ -992,78 +1087,38 @@ def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", devi
     decoded at that scale the way libjpeg-turbo does (decode_to_rgb's `scale`; draft_scale gives Pillow's choice), crops[i]
     is in pixels of the image at that scale, and the result equals im.draft("RGB", ...); im.convert("RGB").crop(...)
     .resize(...). A ValueError for an image that libjpeg would upsample by replication (1/8 with subsampling left, e.g.
-    4:2:2): the batched resize does not reproduce that; use scale 4 for it. `exif_transpose`: every file's EXIF
+    4:2:2): the batched resize does not reproduce that; use scale 4 for it (raised before the decode call, once every
+    header is parsed and every transfer enqueued). `exif_transpose`: every file's EXIF
     orientation is applied -- crops[i] is in DISPLAYED pixels at the scale, and the result equals
     ImageOps.exif_transpose(im) put after draft() and before convert("RGB"), crop() and resize().
     `dtype`, `mean`, `std`, `flips`: with any of them the second step is one jpeggpu_ext_resize_to_tensor call
     (resize_to_tensor) and the result is a training loader's whole transform -- RandomResizedCrop + RandomHorizontalFlip +
     ToTensor + Normalize(mean, std), with the draws (crops[i], flips[i]) supplied by the caller -- as a tensor of `dtype`:
     torch.float32 if `mean` or `std` is given, torch.uint8 (the bytes, flipped where asked) if only `flips` is; float16 and
-    bfloat16 are the float32 result converted once. With all four None the call is what it was, call for call."""
+    bfloat16 are the float32 result converted once. With all four None the call is what it was, call for call. An empty
+    `datas` is refused where the batch is created: a JpegGpuError from jpeggpu_ext_batch_create (INVALID_ARGUMENT)."""
     import torch
 
-    dev = torch.device(device)
-    n = len(datas)
-    crops = [None] * n if crops is None else list(crops)
-    if len(crops) != n:
-        raise ValueError("crops must have one entry per image")
-    scales = [1] * n if scales is None else [int(s) for s in scales]
-    if len(scales) != n or any(s not in (1, 2, 4, 8) for s in scales):
-        raise ValueError("scales must have one entry of 1, 2, 4 or 8 per image")
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    decs, entries, planes_list, infos, cis, keep, colors, orients = [], [], [], [], [], [], [], []
-    try:
-        scans = 0
-        for i, (data, crop, scale) in enumerate(zip(datas, crops, scales)):
-            dec = Decoder()
-            decs.append(dec)
-            dec.set_batch_hint(n)
-            dec.set_idct("islow")
-            dec.set_progressive(True)
-            if scale != 1:
-                dec.set_scale(scale)
-                dec.set_scale_mode("libjpeg")
-            if crop is not None and exif_transpose:  # the header once more, for the orientation and the size at the scale
-                w0, h0 = _frame_size(dec.parse_header(data))
-                crop = orient_rect(dec.orientation(), w0, h0, crop)
-            if crop is not None:
-                dec.set_crop(*crop)
-            info = dec.parse_header(data)
-            orients.append(dec.orientation())
-            if _needs_replication(info, scale):
-                raise ValueError("image %d at scale 1/8 has subsampling left (%s x %s): libjpeg replicates there, which the "
-                                 "batched resize does not reproduce" % (i, list(info.subsampling.x[:info.num_components]),
-                                                                      list(info.subsampling.y[:info.num_components])))
-            scans += dec.layout().num_scans
-            nb = dec.get_buffer_size()
-            tmp = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
-            base = (tmp.data_ptr() + 255) // 256 * 256
-            planes = [torch.empty((info.sizes_y[c], info.sizes_x[c]), dtype=torch.uint8, device=dev)
-                      for c in range(info.num_components)]
-            dec.transfer(base, nb, stream)
-            keep.append(tmp)
-            entries.append((dec, [p.data_ptr() for p in planes], [p.stride(0) for p in planes], base, nb))
-            planes_list.append(planes)
-            infos.append(info)
-            cis.append(dec.crop_info() if crop is not None else None)
-            colors.append(dec.color_space())
-        batch = Batch(scans)
-        scratch = torch.empty(batch.scratch_size, dtype=torch.uint8, device=dev)
-        batch.set_items(entries)
-        batch.decode(scratch.data_ptr(), stream)
+    crops, scales = _per_image_args(len(datas), crops, scales)
+    crop_args = dict(crop_hooks=_displayed_crops(crops)) if exif_transpose else dict(crops=crops)
+    with BatchDecode(datas, device, scales=scales, **crop_args) as bd:
+        if any(bd.replicates):
+            i = bd.replicates.index(True)
+            info = bd.infos[i]
+            raise ValueError("image %d at scale 1/8 has subsampling left (%s x %s): libjpeg replicates there, which the "
+                             "batched resize does not reproduce" % (i, list(info.subsampling.x[:info.num_components]),
+                                                                  list(info.subsampling.y[:info.num_components])))
+        bd.decode()
+        orients = bd.orientations if exif_transpose else None
         if dtype is None and mean is None and std is None and flips is None:
-            out = resize_to_rgb(planes_list, infos, size, cis, filt, layout, colors=colors, orientations=orients if exif_transpose else None)
+            out = resize_to_rgb(bd.planes, bd.infos, size, bd.crop_infos, filt, layout, colors=bd.colors, orientations=orients)
         else:
             if dtype is None:
                 dtype = torch.uint8 if mean is None and std is None else torch.float32
-            out = resize_to_tensor(planes_list, infos, size, cis, filt, layout, colors=colors, orientations=orients if exif_transpose else None,
+            out = resize_to_tensor(bd.planes, bd.infos, size, bd.crop_infos, filt, layout, colors=bd.colors, orientations=orients,
                                    dtype=dtype, mean=mean, std=std, flips=flips)
-        torch.cuda.synchronize(dev)
-        batch.destroy()
+        torch.cuda.synchronize(torch.device(device))
         return out
-    finally:
-        for dec in decs:
-            dec.cleanup()
 
 
 def resized_size(w, h, size):
@@ -1140,45 +1195,9 @@ def resize_views_to_tensor(planes_list, infos, views, size, crop_infos=None, fil
     torch.uint8 unless `mean` or `std` is given (then float32); everything else as in resize_to_tensor."""
     import torch
 
-    if filt not in FILTERS:
-        raise ValueError("filter %r is not one of %s" % (filt, ", ".join(FILTERS)))
-    if layout not in LAYOUTS:
-        raise ValueError("layout %r is not one of %s" % (layout, ", ".join(LAYOUTS)))
     if dtype is None:
         dtype = torch.uint8 if mean is None and std is None else torch.float32
-    if dtype not in TENSOR_TYPES:
-        raise ValueError("dtype %r is not one of %s" % (dtype, ", ".join(TENSOR_TYPE_NAMES)))
-    h, w = _size_hw(size)
-    n = len(planes_list)
-    for name, v in (("infos", infos), ("views", views), ("crop_infos", crop_infos), ("colors", colors), ("orientations", orientations),
-                    ("replicates", replicates), ("flips", flips)):
-        if v is not None and len(v) != n:
-            raise ValueError("%s must have one entry per image" % name)
-    device = planes_list[0][0].device
-    items, _keep = _resize_items(planes_list, infos, crop_infos)
-    vs = (ResizeView * n)(*[_view_struct(views[i], replicates[i] if replicates is not None else False) for i in range(n)])
-    spec = TensorSpec()
-    spec.type = TENSOR_TYPES[dtype]
-    spec.mean[:] = _channel_triple(mean, 0.0, "mean")
-    spec.std[:] = _channel_triple(std, 1.0, "std")
-    flip_bytes = None
-    if flips is not None:
-        flip_bytes = (C.c_ubyte * n)(*[1 if f else 0 for f in flips])
-        spec.flips = C.cast(flip_bytes, C.POINTER(C.c_ubyte))
-    shape = (n, h, w, 3) if layout == "NHWC" else (n, 3, h, w)
-    if out is None:
-        out = torch.empty(shape, dtype=dtype, device=device)
-    elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous():
-        raise ValueError("out must be a contiguous %s tensor of shape %s" % (dtype, shape))
-    cs = _color_array(colors, n) if colors is not None else None
-    os_ = _color_array(orientations, n) if orientations is not None else None
-    need = lib().jpeggpu_ext_resize_view_scratch_size(items, cs, os_, vs, n, w, h, FILTERS[filt])
-    scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
-    _check(lib().jpeggpu_ext_resize_view_to_tensor(items, cs, os_, vs, n, w, h, FILTERS[filt], LAYOUTS[layout], C.byref(spec), out.data_ptr(),
-                                                   scratch.data_ptr(), need, torch.cuda.current_stream(device).cuda_stream),
-           "jpeggpu_ext_resize_view_to_tensor")
-    # the scratch tensor is freed by torch's caching allocator in stream order: it is not reused before the launches ran
-    return out
+    return _resize(planes_list, infos, size, crop_infos, filt, layout, colors, orientations, views, replicates, (dtype, mean, std, flips), out)
 
 
 def decode_center_cropped(datas, resize=256, crop=224, filt="bilinear", layout="NHWC", device="cuda:0", scales=None, exif_transpose=False,
@@ -1196,62 +1215,26 @@ def decode_center_cropped(datas, resize=256, crop=224, filt="bilinear", layout="
     cw x 3 ("NHWC") or n x 3 x ch x cw ("NCHW"), uint8 unless `dtype`, `mean` or `std` says otherwise."""
     import torch
 
-    dev = torch.device(device)
     n = len(datas)
-    scales = [1] * n if scales is None else [int(s) for s in scales]
-    if len(scales) != n or any(s not in (1, 2, 4, 8) for s in scales):
-        raise ValueError("scales must have one entry of 1, 2, 4 or 8 per image")
+    _, scales = _per_image_args(n, None, scales)
     if n == 0:
         raise ValueError("datas is empty")
     ch, cw = _size_hw(crop)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    decs, entries, planes_list, infos, cis, keep, colors, orients, views, reps = [], [], [], [], [], [], [], [], [], []
-    try:
-        scans = 0
-        for data, scale in zip(datas, scales):
-            dec = Decoder()
-            decs.append(dec)
-            dec.set_batch_hint(n)
-            dec.set_idct("islow")
-            dec.set_progressive(True)
-            if scale != 1:
-                dec.set_scale(scale)
-                dec.set_scale_mode("libjpeg")
-            w0, h0 = _frame_size(dec.parse_header(data))  # the header once, for the size at the scale and the orientation
-            o = dec.orientation() if exif_transpose else 1
-            dw, dh = orient_size(o, w0, h0)
-            rw, rh = resized_size(dw, dh, resize)
-            view = (rw, rh) + center_crop_window(rw, rh, (ch, cw))
-            dec.set_crop(*resize_view_rect(w0, h0, view, (ch, cw), filt, o))
-            info = dec.parse_header(data)
-            orients.append(o)
-            views.append(view)
-            reps.append(_needs_replication(info, scale))
-            scans += dec.layout().num_scans
-            nb = dec.get_buffer_size()
-            tmp = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
-            base = (tmp.data_ptr() + 255) // 256 * 256
-            planes = [torch.empty((info.sizes_y[c], info.sizes_x[c]), dtype=torch.uint8, device=dev)
-                      for c in range(info.num_components)]
-            dec.transfer(base, nb, stream)
-            keep.append(tmp)
-            entries.append((dec, [p.data_ptr() for p in planes], [p.stride(0) for p in planes], base, nb))
-            planes_list.append(planes)
-            infos.append(info)
-            cis.append(dec.crop_info())
-            colors.append(dec.color_space())
-        batch = Batch(scans)
-        scratch = torch.empty(batch.scratch_size, dtype=torch.uint8, device=dev)
-        batch.set_items(entries)
-        batch.decode(scratch.data_ptr(), stream)
-        out = resize_views_to_tensor(planes_list, infos, views, (ch, cw), cis, filt, layout, colors=colors, orientations=orients,
-                                     replicates=reps, dtype=dtype, mean=mean, std=std)
-        torch.cuda.synchronize(dev)
-        batch.destroy()
+    views = []
+
+    def window(i, dec, w0, h0):  # from the first parse: the size at the scale and the orientation
+        o = dec.orientation() if exif_transpose else 1
+        rw, rh = resized_size(*orient_size(o, w0, h0), resize)
+        views.append((rw, rh) + center_crop_window(rw, rh, (ch, cw)))  # (the hooks run in the files' order)
+        return resize_view_rect(w0, h0, views[-1], (ch, cw), filt, o)
+
+    with BatchDecode(datas, device, scales=scales, crop_hooks=[window] * n) as bd:
+        bd.decode()
+        out = resize_views_to_tensor(bd.planes, bd.infos, views, (ch, cw), bd.crop_infos, filt, layout, colors=bd.colors,
+                                     orientations=bd.orientations if exif_transpose else [1] * n, replicates=bd.replicates, dtype=dtype,
+                                     mean=mean, std=std)
+        torch.cuda.synchronize(torch.device(device))
         return out
-    finally:
-        for dec in decs:
-            dec.cleanup()
 
 
 def _align256(v):
@@ -1325,61 +1308,16 @@ def decode_batch_to_rgb(datas, device="cuda:0", crops=None, scales=None, exif_tr
 
     if layout not in IMAGE_LAYOUTS:
         raise ValueError("layout %r is not one of %s" % (layout, ", ".join(IMAGE_LAYOUTS)))
-    dev = torch.device(device)
     n = len(datas)
-    crops = [None] * n if crops is None else list(crops)
-    if len(crops) != n:
-        raise ValueError("crops must have one entry per image")
-    scales = [1] * n if scales is None else [int(s) for s in scales]
-    if len(scales) != n or any(s not in (1, 2, 4, 8) for s in scales):
-        raise ValueError("scales must have one entry of 1, 2, 4 or 8 per image")
+    crops, scales = _per_image_args(n, crops, scales)
     if n == 0:
         return []
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    decs, entries, planes_list, infos, cis, keep, colors, orients, reps = [], [], [], [], [], [], [], [], []
-    try:
-        scans = 0
-        for data, crop, scale in zip(datas, crops, scales):
-            dec = Decoder()
-            decs.append(dec)
-            dec.set_batch_hint(n)
-            dec.set_idct("islow")
-            dec.set_progressive(True)
-            if scale != 1:
-                dec.set_scale(scale)
-                dec.set_scale_mode("libjpeg")
-            if crop is not None and exif_transpose:  # the header once more, for the orientation and the size at the scale
-                w0, h0 = _frame_size(dec.parse_header(data))
-                crop = orient_rect(dec.orientation(), w0, h0, crop)
-            if crop is not None:
-                dec.set_crop(*crop)
-            info = dec.parse_header(data)
-            orients.append(dec.orientation() if exif_transpose else 1)
-            reps.append(_needs_replication(info, scale))
-            scans += dec.layout().num_scans
-            nb = dec.get_buffer_size()
-            tmp = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
-            base = (tmp.data_ptr() + 255) // 256 * 256
-            planes = [torch.empty((info.sizes_y[c], info.sizes_x[c]), dtype=torch.uint8, device=dev)
-                      for c in range(info.num_components)]
-            dec.transfer(base, nb, stream)
-            keep.append(tmp)
-            entries.append((dec, [p.data_ptr() for p in planes], [p.stride(0) for p in planes], base, nb))
-            planes_list.append(planes)
-            infos.append(info)
-            cis.append(dec.crop_info() if crop is not None else None)
-            colors.append(dec.color_space())
-        batch = Batch(scans)
-        scratch = torch.empty(batch.scratch_size, dtype=torch.uint8, device=dev)
-        batch.set_items(entries)
-        batch.decode(scratch.data_ptr(), stream)
-        out = batch_to_rgb(planes_list, infos, cis, colors, orients, reps, layout)
-        torch.cuda.synchronize(dev)
-        batch.destroy()
+    crop_args = dict(crop_hooks=_displayed_crops(crops)) if exif_transpose else dict(crops=crops)
+    with BatchDecode(datas, device, scales=scales, **crop_args) as bd:
+        bd.decode()
+        out = batch_to_rgb(bd.planes, bd.infos, bd.crop_infos, bd.colors, bd.orientations if exif_transpose else [1] * n, bd.replicates, layout)
+        torch.cuda.synchronize(torch.device(device))
         return out
-    finally:
-        for dec in decs:
-            dec.cleanup()
 
 
 def encode_item(width, height, channels=3, quality=75, subsampling="4:2:0", restart_interval=0):

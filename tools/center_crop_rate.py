@@ -44,38 +44,13 @@ def _decoders(torch, datas, scale, rects):
     decode batch needs, and the bytes its transfers copy."""
     import jpeggpu_amd
 
-    keep, entries, planes_list, infos, cis, scans, xfer = [], [], [], [], [], 0, 0
-    for data, rect in zip(datas, rects):
-        dec = jpeggpu_amd.Decoder()
-        dec.set_batch_hint(len(datas))
-        dec.set_idct("islow")
-        if scale != 1:
-            dec.set_scale(scale)
-            dec.set_scale_mode("libjpeg")
-        if rect is not None:
-            dec.set_crop(*rect)
-        info = dec.parse_header(data)
-        scans += dec.layout().num_scans
-        xfer += dec.layout().transferred_bytes
-        nb = dec.get_buffer_size()
-        tmp = torch.empty(nb + 256, dtype=torch.uint8, device="cuda:0")
-        base = (tmp.data_ptr() + 255) // 256 * 256
-        planes = [torch.empty((info.sizes_y[c], info.sizes_x[c]), dtype=torch.uint8, device="cuda:0") for c in range(info.num_components)]
-        keep.append((dec, tmp, base, nb))
-        entries.append((dec, [p.data_ptr() for p in planes], [p.stride(0) for p in planes], base, nb))
-        planes_list.append(planes)
-        infos.append(info)
-        cis.append(dec.crop_info() if rect is not None else None)
-    batch = jpeggpu_amd.Batch(scans)
-    scratch = torch.empty(batch.scratch_size, dtype=torch.uint8, device="cuda:0")
-    batch.set_items(entries)
+    bd = jpeggpu_amd.BatchDecode(datas, progressive=False, scales=[scale] * len(datas), crops=rects)
 
     def decode():
-        for dec, _, base, nb in keep:
-            dec.transfer(base, nb, 0)
-        batch.decode(scratch.data_ptr(), 0)
+        bd.transfer()
+        bd.decode()
 
-    return dict(decode=decode, planes=planes_list, infos=infos, cis=cis, bytes=xfer, keep=(keep, batch, scratch))
+    return dict(decode=decode, planes=bd.planes, infos=bd.infos, cis=bd.crop_infos, bytes=bd.transferred_bytes, keep=bd)
 
 
 def run(rounds, iters, n=64):

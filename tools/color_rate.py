@@ -34,8 +34,7 @@ def _rgb_cs(v, color):
 
     L = lib()
     _planes, infos, cis = v["resize"]
-    outs = v["keep"][2]
-    srcs = v["srcs"]
+    srcs, outs = v["srcs"], v["outs"]
 
     def rgb():
         for info, ci, src, out in zip(infos, cis, srcs, outs):
@@ -43,18 +42,6 @@ def _rgb_cs(v, color):
             assert st == 0
 
     return rgb
-
-
-def _sources(v):
-    from jpeggpu_amd.api import Img
-
-    out = []
-    for planes in v["resize"][0]:
-        src = Img()
-        for c, p in enumerate(planes):
-            src.image[c], src.pitch[c] = p.data_ptr(), p.stride(0)
-        out.append(src)
-    return out
 
 
 def run(rounds, iters, images):
@@ -69,8 +56,6 @@ def run(rounds, iters, images):
     four = [f[:2] + ADOBE_YCCK + f[2:] for f in four]
     a = _setup(torch, [ycc[i % 4] for i in range(images)], 1, "uniform", images)
     b = _setup(torch, [four[i % 4] for i in range(images)], 1, "uniform", images)
-    for v in (a, b):
-        v["srcs"] = _sources(v)
     dec = jpeggpu_amd.Decoder()
     dec.parse_header(four[0])
     assert dec.color_space() == jpeggpu_amd.ColorSpace.YCCK

@@ -70,25 +70,7 @@ def _lone(torch, data, crop):
 def _batch(torch, datas, crops):
     import jpeggpu_amd
 
-    keep, entries, xfer = [], [], 0
-    for data, crop in zip(datas, crops):
-        dec = jpeggpu_amd.Decoder()
-        dec.set_batch_hint(len(datas))
-        if crop is not None:
-            dec.set_crop(*crop)
-        info = dec.parse_header(data)
-        n = dec.get_buffer_size()
-        tmp = torch.empty(n + 256, dtype=torch.uint8, device="cuda:0")
-        base = (tmp.data_ptr() + 255) // 256 * 256
-        planes = [torch.empty((info.sizes_y[c], info.sizes_x[c]), dtype=torch.uint8, device="cuda:0") for c in range(info.num_components)]
-        dec.transfer(base, n, 0)
-        xfer += dec.layout().transferred_bytes
-        keep.append((dec, tmp, planes))
-        entries.append((dec, [p.data_ptr() for p in planes], [p.stride(0) for p in planes], base, n))
-    batch = jpeggpu_amd.Batch(len(datas))
-    scratch = torch.empty(batch.scratch_size, dtype=torch.uint8, device="cuda:0")
-    batch.set_items(entries)
-    return batch, scratch, keep, xfer
+    return jpeggpu_amd.BatchDecode(datas, idct="reference", progressive=False, crops=crops)
 
 
 def _summary(v, digits):
@@ -100,7 +82,7 @@ def run(rounds, iters):
     import torch
 
     import jpeggpu_amd
-    from jpeggpu_amd.api import Img, lib
+    from jpeggpu_amd.api import _img, lib
     from tools import jpegsynth
 
     photo = open(os.path.join(ROOT, "tests", "golden", "IMG_6510.JPG"), "rb").read()
@@ -120,8 +102,8 @@ def run(rounds, iters):
     batches = {"uncropped": _batch(torch, datas, [None] * 64), "random_resized_crop": _batch(torch, datas, rects)}
     for _, fn, _, _ in lone.values():  # warm-up
         fn()
-    for batch, scratch, _, _ in batches.values():
-        batch.decode(scratch.data_ptr(), 0)
+    for bd in batches.values():
+        bd.decode()
     torch.cuda.synchronize()
 
     # RGB: a centre 224 x 224 crop of one 12 MP 4:2:0 image against the whole image
@@ -129,12 +111,7 @@ def run(rounds, iters):
     full_planes, full_info = jpeggpu_amd.decode_to_planes(cfg[0], idct="islow")
     crop_planes, crop_info, ci = jpeggpu_amd.decode_to_planes(cfg[0], idct="islow", crop=(x0, y0, 224, 224))
     stream = torch.cuda.current_stream().cuda_stream
-    srcs = {}
-    for key, planes in (("full", full_planes), ("crop", crop_planes)):
-        src = Img()
-        for c in range(3):
-            src.image[c], src.pitch[c] = planes[c].data_ptr(), planes[c].stride(0)
-        srcs[key] = src
+    srcs = {"full": _img(full_planes), "crop": _img(crop_planes)}
     rgb_full = torch.empty((3024, 4032, 3), dtype=torch.uint8, device="cuda:0")
     rgb_crop = torch.empty((224, 224, 3), dtype=torch.uint8, device="cuda:0")
     rgb_calls = {
@@ -160,15 +137,15 @@ def run(rounds, iters):
             torch.cuda.synchronize()
             res_lone[k]["stages"].append(dec.stage_ms())
             dec.set_profiling(False)
-        for k, (batch, scratch, keep, _) in batches.items():
-            ms = _time(torch, lambda: batch.decode(scratch.data_ptr(), 0), iters)
-            res_batch[k]["img_s"].append(len(keep) * 1000.0 / ms)
-            batch.set_profiling(True)
+        for k, bd in batches.items():
+            ms = _time(torch, bd.decode, iters)
+            res_batch[k]["img_s"].append(len(bd.decoders) * 1000.0 / ms)
+            bd.batch.set_profiling(True)
             for _ in range(3):
-                batch.decode(scratch.data_ptr(), 0)
+                bd.decode()
             torch.cuda.synchronize()
-            res_batch[k]["stages"].append(batch.stage_ms())
-            batch.set_profiling(False)
+            res_batch[k]["stages"].append(bd.batch.stage_ms())
+            bd.batch.set_profiling(False)
         for k, fn in rgb_calls.items():
             res_rgb[k].append(_time(torch, fn, iters * 10))
 
@@ -181,7 +158,7 @@ def run(rounds, iters):
                     "stage_ms_median": stages(v["stages"]), "transferred_bytes": lone[k][3]})
     for k, v in res_batch.items():
         out.append({"workload": "batch64_cfg2", "crop": k, "img_s": _summary(v["img_s"], 1),
-                    "stage_ms_median": stages(v["stages"]), "transferred_bytes": batches[k][3]})
+                    "stage_ms_median": stages(v["stages"]), "transferred_bytes": batches[k].transferred_bytes})
     for k, v in res_rgb.items():
         out.append({"workload": "rgb", "call": k, "ms": _summary(v, 4)})
     out.append({"rounds": rounds, "iters": iters, "rects_area_share": round(sum(w * h for _, _, w, h in rects) / (64 * 4032 * 3024), 4)})

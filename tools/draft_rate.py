@@ -33,48 +33,24 @@ SCALES = (2, 4, 8)
 
 def _setup(torch, datas, scale, mode, hint, crops=None):
     """A batch of decoders at one scale (or one per image) and mode, transferred, with their planes: decode(), rgb() and
-    what the resize takes."""
+    what the resize takes; "srcs" and "outs" are rgb()'s Img and output of every image (tools/color_rate.py)."""
     import jpeggpu_amd
-    from jpeggpu_amd.api import Img, lib
+    from jpeggpu_amd.api import _img, lib
 
-    keep, entries, planes_list, infos, cis, srcs, outs, scans = [], [], [], [], [], [], [], 0
-    for i, data in enumerate(datas):
-        dec = jpeggpu_amd.Decoder()
-        dec.set_batch_hint(hint)
-        dec.set_idct("islow")
-        dec.set_scale(scale[i] if isinstance(scale, (list, tuple)) else scale)
-        dec.set_scale_mode(mode)
-        if crops is not None:
-            dec.set_crop(*crops[i])
-        info = dec.parse_header(data)
-        scans += dec.layout().num_scans
-        n = dec.get_buffer_size()
-        tmp = torch.empty(n + 256, dtype=torch.uint8, device="cuda:0")
-        base = (tmp.data_ptr() + 255) // 256 * 256
-        planes = [torch.empty((info.sizes_y[c], info.sizes_x[c]), dtype=torch.uint8, device="cuda:0") for c in range(info.num_components)]
-        dec.transfer(base, n, 0)
-        ci = dec.crop_info()
-        src = Img()
-        for c in range(info.num_components):
-            src.image[c], src.pitch[c] = planes[c].data_ptr(), planes[c].stride(0)
-        keep.append((dec, tmp))
-        entries.append((dec, [p.data_ptr() for p in planes], [p.stride(0) for p in planes], base, n))
-        planes_list.append(planes), infos.append(info), cis.append(ci), srcs.append(src)
-        outs.append(torch.empty((ci.height, ci.width, 3), dtype=torch.uint8, device="cuda:0") if crops is None else None)
-    batch = jpeggpu_amd.Batch(scans)
-    scratch = torch.empty(batch.scratch_size, dtype=torch.uint8, device="cuda:0")
-    batch.set_items(entries)
+    scales = list(scale) if isinstance(scale, (list, tuple)) else [scale] * len(datas)
+    bd = jpeggpu_amd.BatchDecode(datas, hint=hint, progressive=False, scales=scales, scale_mode=mode, crops=crops)
+    infos, cis = bd.infos, [dec.crop_info() for dec in bd.decoders]  # (without a crop: the whole image at the scale)
+    srcs = [_img(planes) for planes in bd.planes]
+    outs = [torch.empty((ci.height, ci.width, 3), dtype=torch.uint8, device="cuda:0") if crops is None else None for ci in cis]
     L = lib()
-
-    def decode():
-        batch.decode(scratch.data_ptr(), 0)
 
     def rgb():
         for info, ci, src, out in zip(infos, cis, srcs, outs):
             st = L.jpeggpu_ext_planes_to_rgbi_fancy(C.byref(info), C.byref(src), out.data_ptr(), 3 * ci.width, ci.width, ci.height, None)
             assert st == 0
 
-    return {"decode": decode, "rgb": rgb, "batch": batch, "keep": (keep, scratch, outs), "resize": (planes_list, infos, cis), "n": len(datas)}
+    return {"decode": bd.decode, "rgb": rgb, "batch": bd.batch, "keep": bd, "srcs": srcs, "outs": outs, "resize": (bd.planes, infos, cis),
+            "n": len(datas)}
 
 
 def _spread(v, digits=4):

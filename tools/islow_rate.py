@@ -26,23 +26,7 @@ METHODS = ("reference", "islow")
 def _setup(torch, datas, method, hint):
     import jpeggpu_amd
 
-    keep, entries = [], []
-    for data in datas:
-        dec = jpeggpu_amd.Decoder()
-        dec.set_batch_hint(hint)
-        dec.set_idct(method)
-        info = dec.parse_header(data)
-        n = dec.get_buffer_size()
-        tmp = torch.empty(n + 256, dtype=torch.uint8, device="cuda:0")
-        base = (tmp.data_ptr() + 255) // 256 * 256
-        planes = [torch.empty((info.sizes_y[c], info.sizes_x[c]), dtype=torch.uint8, device="cuda:0") for c in range(info.num_components)]
-        dec.transfer(base, n, 0)
-        keep.append((dec, tmp, planes, info))
-        entries.append((dec, [p.data_ptr() for p in planes], [p.stride(0) for p in planes], base, n))
-    batch = jpeggpu_amd.Batch(len(datas) * 3)
-    scratch = torch.empty(batch.scratch_size, dtype=torch.uint8, device="cuda:0")
-    batch.set_items(entries)
-    return batch, scratch, keep
+    return jpeggpu_amd.BatchDecode(datas, hint=hint, idct=method, progressive=False)
 
 
 def _time(torch, fn, iters):
@@ -60,7 +44,7 @@ def run(rounds, iters):
     import torch
 
     import jpeggpu_amd
-    from jpeggpu_amd.api import Img, lib
+    from jpeggpu_amd.api import _img, lib
     from tools import jpegsynth
 
     photo = open(os.path.join(ROOT, "tests", "golden", "IMG_6510.JPG"), "rb").read()
@@ -70,16 +54,14 @@ def run(rounds, iters):
         setups[("photo", m)] = _setup(torch, [photo], m, 0)
         setups[("batch64", m)] = _setup(torch, [cfg[i % 8] for i in range(64)], m, 64)
     results = {k: {"img_s": [], "idct_ms": []} for k in setups}
-    for batch, scratch, keep in setups.values():  # warm-up
-        batch.decode(scratch.data_ptr(), 0)
+    for bd in setups.values():  # warm-up
+        bd.decode()
     torch.cuda.synchronize()
 
     # the RGB kernels on the planes of one 12 MP 4:2:0 image
     planes, info = jpeggpu_amd.decode_to_planes(cfg[0], idct="islow")
     width, height = info.sizes_x[0], info.sizes_y[0]
-    src = Img()
-    for c in range(3):
-        src.image[c], src.pitch[c] = planes[c].data_ptr(), planes[c].stride(0)
+    src = _img(planes)
     rgb = torch.empty((height, width, 3), dtype=torch.uint8, device="cuda:0")
     stream = torch.cuda.current_stream().cuda_stream
     kernels = {"rgbi_kernel": lib().jpeggpu_ext_planes_to_rgbi, "fancy_rgbi_kernel": lib().jpeggpu_ext_planes_to_rgbi_fancy}
@@ -93,21 +75,21 @@ def run(rounds, iters):
     for _ in range(rounds):
         for name in ("photo", "batch64"):
             for m in METHODS:  # the methods alternate inside every round
-                batch, scratch, keep = setups[(name, m)]
-                ms = _time(torch, lambda: batch.decode(scratch.data_ptr(), 0), iters)
-                results[(name, m)]["img_s"].append(len(keep) * 1000.0 / ms)
-                batch.set_profiling(True)  # (a new measurement window)
+                bd = setups[(name, m)]
+                ms = _time(torch, bd.decode, iters)
+                results[(name, m)]["img_s"].append(len(bd.decoders) * 1000.0 / ms)
+                bd.batch.set_profiling(True)  # (a new measurement window)
                 for _ in range(3):
-                    batch.decode(scratch.data_ptr(), 0)
+                    bd.decode()
                 torch.cuda.synchronize()
-                results[(name, m)]["idct_ms"].append(batch.stage_ms()["idct"])
-                batch.set_profiling(False)
+                results[(name, m)]["idct_ms"].append(bd.batch.stage_ms()["idct"])
+                bd.batch.set_profiling(False)
         for k, fn in kernels.items():
             rgb_ms[k].append(_time(torch, rgb_call(fn), iters * 10))
     out = []
     for (name, m), v in results.items():
         out.append({
-            "workload": name, "idct": m, "images": len(setups[(name, m)][2]),
+            "workload": name, "idct": m, "images": len(setups[(name, m)].decoders),
             "img_s_median": round(statistics.median(v["img_s"]), 1), "img_s_min": round(min(v["img_s"]), 1), "img_s_max": round(max(v["img_s"]), 1),
             "idct_ms_median": round(statistics.median(v["idct_ms"]), 4), "idct_ms_min": round(min(v["idct_ms"]), 4), "idct_ms_max": round(max(v["idct_ms"]), 4),
         })

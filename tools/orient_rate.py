@@ -32,15 +32,6 @@ from tools.crop_rate import _time, random_resized_crop  # noqa: E402
 from tools.draft_rate import _spread  # noqa: E402
 
 
-def _img(planes):
-    from jpeggpu_amd.api import Img
-
-    src = Img()
-    for c, p in enumerate(planes):
-        src.image[c], src.pitch[c] = p.data_ptr(), p.stride(0)
-    return src
-
-
 def _rounds(torch, variants, rounds, iters):
     res = {k: [] for k in variants}
     for fn in variants.values():  # warm-up
@@ -61,6 +52,7 @@ def photo(rounds, iters):
     import torch
 
     import jpeggpu_amd
+    from jpeggpu_amd.api import _img
     from tools import jpegsynth
 
     L = jpeggpu_amd.lib()
@@ -113,7 +105,7 @@ def batch(rounds, iters, size=224):
     import torch
 
     import jpeggpu_amd
-    from jpeggpu_amd.api import FILTERS, LAYOUTS, _color_array, _resize_items
+    from jpeggpu_amd.api import FILTERS, LAYOUTS, _color_array, _img, _resize_items
     from tools import jpegsynth
 
     L = jpeggpu_amd.lib()
@@ -122,29 +114,10 @@ def batch(rounds, iters, size=224):
     rng = np.random.default_rng(2024)
     shown = [random_resized_crop(rng, h, w) for _ in range(n)]  # in the displayed image of orientation 6: 3024 x 4032
     rects = [jpeggpu_amd.orient_rect(6, w, h, r) for r in shown]
-    keep, entries, planes_list, infos, cis, scans = [], [], [], [], [], 0
-    for i, rect in enumerate(rects):
-        dec = jpeggpu_amd.Decoder()
-        dec.set_batch_hint(n)
-        dec.set_idct("islow")
-        dec.set_crop(*rect)
-        info = dec.parse_header(cfg[i % 8])
-        scans += dec.layout().num_scans
-        nb = dec.get_buffer_size()
-        tmp = torch.empty(nb + 256, dtype=torch.uint8, device="cuda:0")
-        base = (tmp.data_ptr() + 255) // 256 * 256
-        planes = [torch.empty((info.sizes_y[c], info.sizes_x[c]), dtype=torch.uint8, device="cuda:0") for c in range(info.num_components)]
-        dec.transfer(base, nb, 0)
-        keep.append((dec, tmp))
-        entries.append((dec, [p.data_ptr() for p in planes], [p.stride(0) for p in planes], base, nb))
-        planes_list.append(planes)
-        infos.append(info)
-        cis.append(dec.crop_info())
-    b = jpeggpu_amd.Batch(scans)
-    bscratch = torch.empty(b.scratch_size, dtype=torch.uint8, device="cuda:0")
-    b.set_items(entries)
-    b.decode(bscratch.data_ptr(), 0)
+    bd = jpeggpu_amd.BatchDecode([cfg[i % 8] for i in range(n)], progressive=False, crops=rects)
+    bd.decode()
     torch.cuda.synchronize()
+    planes_list, infos, cis = bd.planes, bd.infos, bd.crop_infos
 
     items, _keep = _resize_items(planes_list, infos, cis)
     colors = _color_array([jpeggpu_amd.ColorSpace.YCBCR] * n, n)

@@ -31,7 +31,7 @@ def run(rounds, iters, size=224):
     import torch
 
     import jpeggpu_amd
-    from jpeggpu_amd.api import FILTERS, LAYOUTS, Img, _resize_items, lib
+    from jpeggpu_amd.api import FILTERS, LAYOUTS, _img, _resize_items, lib
     from tests import pillow_resample_ref as R
     from tools import jpegsynth
 
@@ -41,48 +41,23 @@ def run(rounds, iters, size=224):
     rng = np.random.default_rng(2024)
     rects = [random_resized_crop(rng, 4032, 3024) for _ in range(64)]
 
-    keep, entries, planes_list, infos, cis, scans = [], [], [], [], [], 0
-    for data, rect in zip(datas, rects):
-        dec = jpeggpu_amd.Decoder()
-        dec.set_batch_hint(64)
-        dec.set_idct("islow")
-        dec.set_crop(*rect)
-        info = dec.parse_header(data)
-        scans += dec.layout().num_scans
-        n = dec.get_buffer_size()
-        tmp = torch.empty(n + 256, dtype=torch.uint8, device="cuda:0")
-        base = (tmp.data_ptr() + 255) // 256 * 256
-        planes = [torch.empty((info.sizes_y[c], info.sizes_x[c]), dtype=torch.uint8, device="cuda:0") for c in range(info.num_components)]
-        dec.transfer(base, n, 0)
-        keep.append((dec, tmp))
-        entries.append((dec, [p.data_ptr() for p in planes], [p.stride(0) for p in planes], base, n))
-        planes_list.append(planes)
-        infos.append(info)
-        cis.append(dec.crop_info())
-    batch = jpeggpu_amd.Batch(scans)
-    bscratch = torch.empty(batch.scratch_size, dtype=torch.uint8, device="cuda:0")
-    batch.set_items(entries)
+    bd = jpeggpu_amd.BatchDecode(datas, progressive=False, crops=rects)
+    planes_list, infos, cis = bd.planes, bd.infos, bd.crop_infos
 
     items, _items_keep = _resize_items(planes_list, infos, cis)
     need = L.jpeggpu_ext_resize_scratch_size(items, 64, size, size, FILTERS["bilinear"])
     rscratch = torch.empty(need, dtype=torch.uint8, device="cuda:0")
     out = torch.empty((64, size, size, 3), dtype=torch.uint8, device="cuda:0")
 
-    def decode():
-        batch.decode(bscratch.data_ptr(), 0)
+    decode = bd.decode
 
     def resize():
         st = L.jpeggpu_ext_resize_to_rgb(items, 64, size, size, FILTERS["bilinear"], LAYOUTS["NHWC"], out.data_ptr(),
                                          rscratch.data_ptr(), need, None)
         assert st == 0, jpeggpu_amd.status_string(st)
 
-    srcs, crops_out = [], []
-    for planes, ci in zip(planes_list, cis):
-        src = Img()
-        for c in range(3):
-            src.image[c], src.pitch[c] = planes[c].data_ptr(), planes[c].stride(0)
-        srcs.append(src)
-        crops_out.append(torch.empty((ci.height, ci.width, 3), dtype=torch.uint8, device="cuda:0"))
+    srcs = [_img(planes) for planes in planes_list]
+    crops_out = [torch.empty((ci.height, ci.width, 3), dtype=torch.uint8, device="cuda:0") for ci in cis]
 
     def crop64():
         for i in range(64):

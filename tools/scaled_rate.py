@@ -22,30 +22,14 @@ SCALES = (1, 2, 4, 8)
 def _setup(torch, datas, d, hint):
     import jpeggpu_amd
 
-    keep, entries = [], []
-    for data in datas:
-        dec = jpeggpu_amd.Decoder()
-        dec.set_batch_hint(hint)
-        dec.set_scale(d)
-        info = dec.parse_header(data)
-        n = dec.get_buffer_size()
-        tmp = torch.empty(n + 256, dtype=torch.uint8, device="cuda:0")
-        base = (tmp.data_ptr() + 255) // 256 * 256
-        planes = [torch.empty((info.sizes_y[c], info.sizes_x[c]), dtype=torch.uint8, device="cuda:0") for c in range(info.num_components)]
-        dec.transfer(base, n, 0)
-        keep.append((dec, tmp, planes, info))
-        entries.append((dec, [p.data_ptr() for p in planes], [p.stride(0) for p in planes], base, n))
-    batch = jpeggpu_amd.Batch(len(datas) * 3)
-    scratch = torch.empty(batch.scratch_size, dtype=torch.uint8, device="cuda:0")
-    batch.set_items(entries)
-    return batch, scratch, keep
+    return jpeggpu_amd.BatchDecode(datas, hint=hint, idct="reference", progressive=False, scales=[d] * len(datas), scale_mode="uniform")
 
 
-def _idct_bytes(keep):
+def _idct_bytes(bd):
     """Bytes the IDCT stage moves: data-unit records (8 B), symbol entries (2 B each, all of a unit's at d < 8, the DC one
     at d = 8 -- approximated by the write pass's counts read back) and the plane bytes written."""
     total = 0
-    for dec, tmp, planes, info in keep:
+    for dec, planes in zip(bd.decoders, bd.planes):
         lay = dec.layout()
         for s in range(lay.num_scans):
             sl = lay.scans[s]
@@ -54,20 +38,20 @@ def _idct_bytes(keep):
     return total
 
 
-def _sym_bytes(torch, keep, d):
+def _sym_bytes(torch, bd, d):
     import numpy as np
 
     from tests import gpu_util
 
     total = 0
-    for dec, tmp, planes, info in keep[:1]:
+    for dec, tmp in zip(bd.decoders[:1], bd.tmps):
         lay = dec.layout()
         base = (tmp.data_ptr() + 255) // 256 * 256
         for s in range(lay.num_scans):
             sl = lay.scans[s]
             tab = gpu_util.tmp_view(torch, tmp, base, sl.off_du_table, sl.num_data_units * 2, torch.int32).view(np.uint32).reshape(-1, 2)
             total += 2 * (sl.num_data_units if d == 8 else int((tab[:, 1] & 127).sum()))
-    return total * len(keep)
+    return total * len(bd.decoders)
 
 
 def run(rounds, iters):
@@ -83,35 +67,35 @@ def run(rounds, iters):
         setups[("batch64", d)] = _setup(torch, [cfg[i % 8] for i in range(64)], d, 64)
     results = {k: {"img_s": [], "idct_ms": []} for k in setups}
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for (name, d), (batch, scratch, keep) in setups.items():  # warm-up, and the symbol-stream bytes of each setup
-        batch.decode(scratch.data_ptr(), 0)
+    for bd in setups.values():  # warm-up, and the symbol-stream bytes of each setup
+        bd.decode()
     torch.cuda.synchronize()
-    sym = {k: _sym_bytes(torch, v[2], k[1]) for k, v in setups.items()}
+    sym = {k: _sym_bytes(torch, v, k[1]) for k, v in setups.items()}
     for r in range(rounds):
         for name in ("photo", "batch64"):
             for d in SCALES:  # the scales alternate inside every round
-                batch, scratch, keep = setups[(name, d)]
+                bd = setups[(name, d)]
                 torch.cuda.synchronize()
                 ev0.record()
                 for _ in range(iters):
-                    batch.decode(scratch.data_ptr(), 0)
+                    bd.decode()
                 ev1.record()
                 torch.cuda.synchronize()
                 ms = ev0.elapsed_time(ev1) / iters
-                results[(name, d)]["img_s"].append(len(keep) * 1000.0 / ms)
-                batch.set_profiling(True)  # (a new measurement window)
+                results[(name, d)]["img_s"].append(len(bd.decoders) * 1000.0 / ms)
+                bd.batch.set_profiling(True)  # (a new measurement window)
                 for _ in range(3):
-                    batch.decode(scratch.data_ptr(), 0)
+                    bd.decode()
                 torch.cuda.synchronize()
-                results[(name, d)]["idct_ms"].append(batch.stage_ms()["idct"])
-                batch.set_profiling(False)
+                results[(name, d)]["idct_ms"].append(bd.batch.stage_ms()["idct"])
+                bd.batch.set_profiling(False)
     out = []
     for (name, d), v in results.items():
-        keep = setups[(name, d)][2]
-        nbytes = _idct_bytes(keep) + sym[(name, d)]
+        bd = setups[(name, d)]
+        nbytes = _idct_bytes(bd) + sym[(name, d)]
         idct = statistics.median(v["idct_ms"])
         out.append({
-            "workload": name, "scale": d, "images": len(keep),
+            "workload": name, "scale": d, "images": len(bd.decoders),
             "img_s_median": round(statistics.median(v["img_s"]), 1), "img_s_min": round(min(v["img_s"]), 1), "img_s_max": round(max(v["img_s"]), 1),
             "idct_ms_median": round(idct, 4), "idct_ms_min": round(min(v["idct_ms"]), 4), "idct_ms_max": round(max(v["idct_ms"]), 4),
             "idct_bytes": nbytes, "idct_gb_s": round(nbytes / (idct * 1e6), 1) if idct > 0 else None,

@@ -43,33 +43,10 @@ def _decode(torch, datas, rects):
     """The files' rectangles decoded by one jpeggpu_ext_decode_batch call (ISLOW): (planes_list, infos, crop infos)."""
     import jpeggpu_amd
 
-    keep, entries, planes_list, infos, cis, scans = [], [], [], [], [], 0
-    for data, rect in zip(datas, rects):
-        dec = jpeggpu_amd.Decoder()
-        dec.set_batch_hint(len(datas))
-        dec.set_idct("islow")
-        dec.set_crop(*rect)
-        info = dec.parse_header(data)
-        scans += dec.layout().num_scans
-        nb = dec.get_buffer_size()
-        tmp = torch.empty(nb + 256, dtype=torch.uint8, device="cuda:0")
-        base = (tmp.data_ptr() + 255) // 256 * 256
-        planes = [torch.empty((info.sizes_y[c], info.sizes_x[c]), dtype=torch.uint8, device="cuda:0") for c in range(info.num_components)]
-        dec.transfer(base, nb, 0)
-        keep.append((dec, tmp))
-        entries.append((dec, [p.data_ptr() for p in planes], [p.stride(0) for p in planes], base, nb))
-        planes_list.append(planes)
-        infos.append(info)
-        cis.append(dec.crop_info())
-    b = jpeggpu_amd.Batch(scans)
-    scratch = torch.empty(b.scratch_size, dtype=torch.uint8, device="cuda:0")
-    b.set_items(entries)
-    b.decode(scratch.data_ptr(), 0)
-    torch.cuda.synchronize()
-    b.destroy()
-    for dec, _ in keep:
-        dec.cleanup()
-    return planes_list, infos, cis
+    with jpeggpu_amd.BatchDecode(datas, progressive=False, crops=rects) as bd:
+        bd.decode()
+        torch.cuda.synchronize()
+        return bd.planes, bd.infos, bd.crop_infos
 
 
 def run(rounds, iters, size=224, n=64):
