@@ -63,6 +63,33 @@ def test_bound_covers_every_pinned_file(L):
         assert jpeggpu_amd.encode_bound(*_args(c)) >= pins[c["name"]]["length"], c["name"]
 
 
+def test_header_and_bound_of_every_new_case(L):
+    """The sweep, the edge cases and the items of the big calls (tests/golden/encode_sweep_pins.npz holds lengths and hashes
+    only): the header is the restatement's, the bound covers the pinned length, and the bound is what encode_cases.counts
+    restates -- the tile and chunk counts the structure tests of tests/test_encode_ref.py rest on."""
+    pins = K.sweep_pins()[0]
+    for c in K.new_cases():
+        header = jpeggpu_amd.encode_header(*_args(c))
+        hs, vs = E.SUBSAMPLINGS[c["subsampling"]]
+        assert header == E.header(c["w"], c["h"], 1 if c["grey"] else 3, hs, vs, c["quality"], c["restart_interval"]), c["name"]
+        bound = jpeggpu_amd.encode_bound(*_args(c))
+        assert bound >= pins[c["name"]]["length"], c["name"]
+        n = K.counts(c)
+        assert bound == len(header) + 2 * n["stream_bound"] + 2 * (n["segments"] - 1) + 2, c["name"]
+
+
+def test_scratch_size_follows_the_restated_counts(L):
+    """jpeggpu_ext_encode_scratch_size of the big calls holds at least what the restated tiles and chunks need: the
+    coefficients, the stream and the start bits of every item, and the per-tile and per-chunk arrays."""
+    for items in (K.many_call(), K.grid_call()["items"]):
+        arr = (EncodeItem * len(items))(*[encode_item(*_args(c)) for c in items])
+        need = L.jpeggpu_ext_encode_scratch_size(arr, len(items))
+        tiles, chunks = K.starts(items, "tiles")[-1], K.starts(items, "chunks")[-1]
+        least = sum(K.counts(c)["blocks"] * 128 + K.counts(c)["chunks"] * (K.CHUNK_BYTES + K.CHUNK_BYTES // 8) for c in items)
+        least += tiles * (K.TILE_BLOCKS * 4 + 24) + chunks * 24
+        assert least < need < least + 2048 * len(items) + 8192, "and no more than the descriptors, headers and alignment on top"
+
+
 @pytest.mark.parametrize("w,h,ch,sub,ri", [(1, 1, 1, "4:4:4", 0), (8, 8, 3, "4:2:0", 0), (53, 37, 3, "4:2:0", 1), (53, 37, 3, "4:2:2", 3), (19, 3, 3, "4:4:4", 11),
                                             (40, 24, 1, "4:2:0", 1), (200, 64, 3, "4:2:0", 0)])
 def test_bound_covers_the_worst_stream(L, w, h, ch, sub, ri):
