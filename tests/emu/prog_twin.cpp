@@ -118,4 +118,31 @@ int prog_twin_run(const uint8_t* data, size_t size, int progressive, int shard_w
     return st;
 }
 
+/// The work list of a progressive file as the device reads it: the ProgItem array and level_item, copied out of the blob
+/// that prog_fill_blob wrote (not out of the planner's vectors). items: up to `cap` (scan, segment) pairs; level_item:
+/// kMaxProgScans + 1 entries. Returns the number of items of the list (which may exceed cap), or -1 - status if the
+/// parser refuses the file or it is not progressive.
+int prog_twin_work(const uint8_t* data, size_t size, uint32_t* items, int cap, uint32_t* level_item)
+{
+    Reader r;
+    Logger log;
+    const jpeggpu_status st = r.parse(data, size, 64, log, false, 0, 1, true);
+    if (st != JPEGGPU_SUCCESS) return -1 - static_cast<int>(st);
+    const Stream& s = r.s;
+    if (!s.progressive) return -1;
+    ProgBlobLayout lay;
+    size_t blob_size = 0;
+    prog_plan_blob(s, lay, blob_size);
+    ProgPlacement at{};
+    at.bytes_len = s.xfer_end - s.xfer_begin;
+    std::vector<uint8_t> blob(blob_size, 0);
+    prog_fill_blob(s, lay, at, blob.data());
+    const ProgHeader& H = *reinterpret_cast<const ProgHeader*>(blob.data() + lay.header);
+    std::memcpy(level_item, H.level_item, sizeof(H.level_item));
+    const uint32_t n     = H.level_item[H.num_levels];
+    const ProgItem* list = reinterpret_cast<const ProgItem*>(blob.data() + H.items_off); // (blob_in_tmp is 0 here)
+    for (uint32_t i = 0; i < n && i < static_cast<uint32_t>(cap); ++i) items[2 * i] = list[i].scan, items[2 * i + 1] = list[i].seg;
+    return static_cast<int>(n);
+}
+
 } // extern "C"

@@ -37,7 +37,22 @@ def lib():
             subprocess.check_call(["g++", "-O2", "-shared", "-fPIC"] + compile_args() + sources() + ["-o", _LIB])
         _lib = C.CDLL(_LIB)
         _lib.prog_twin_run.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(Info), C.c_void_p, C.c_void_p]
+        _lib.prog_twin_work.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]
     return _lib
+
+
+IDLE = 0xFFFFFFFF  # the scan number of an idle work item (jg_prog_core.h, kProgNoScan)
+
+
+def work_list(data: bytes):
+    """(items, level_item) as the blob holds them: items uint32 [n, 2] of (scan, segment), IDLE for a padding item;
+    level_item uint32 [MAX_SCANS + 1], the first item of each level (and one past the last level's)."""
+    level_item = np.zeros(MAX_SCANS + 1, np.uint32)
+    n = lib().prog_twin_work(data, len(data), None, 0, level_item.ctypes.data)
+    assert n >= 0, n
+    items = np.zeros((n, 2), np.uint32)
+    assert lib().prog_twin_work(data, len(data), items.ctypes.data, n, level_item.ctypes.data) == n
+    return items, level_item
 
 
 def parse(data: bytes, progressive=True, shard_world=1):

@@ -6,7 +6,9 @@
   * encode(...): a progressive file from quantised coefficients, a scan script and a restart interval, with flat code
     tables -- for the scripts no encoder at hand writes (tests/test_progressive_host.py, tests/test_gpu_progressive.py).
 
-Slow and simple on purpose; the files of the tests are a few blocks large.
+Slow and simple on purpose; most files of the tests are a few blocks large, and the decoder takes a second or two for the
+largest (tests/golden/progressive_large.npz). decode(data, stats) also says what each scan's data exercised: end-of-band
+runs by category, correction bits inside runs, codes longer than 9 bits.
 """
 import numpy as np
 
@@ -32,6 +34,7 @@ class _Bits:
             out.append(raw[i])
             i += 2 if raw[i] == 0xFF else 1  # FF 00 stands for FF
         self.b, self.pos = bytes(out), 0
+        self.symbols = self.long_codes = 0  # Huffman symbols read so far, and those of more than 9 bits (statistics)
 
     def bit(self):
         byte = self.pos >> 3
@@ -63,6 +66,8 @@ def _decode_symbol(br, table):
     for length in range(1, 17):
         code = code << 1 | br.bit()
         if (length, code) in table:
+            br.symbols += 1
+            br.long_codes += length > 9
             return table[(length, code)]
     raise ValueError("no code matches")
 
@@ -75,7 +80,16 @@ class Decoded:
     pass
 
 
-def decode(data: bytes) -> Decoded:
+def decode(data: bytes, stats=None) -> Decoded:
+    """`stats`: a list that gets one dict per scan, in file order -- what the scan's entropy-coded data exercised:
+         eob_categories  [15]: how many end-of-band run symbols of each category r (a run of 2^r .. 2^(r+1) - 1 blocks)
+         runs            [(length, n)]: every run in order, with n the number of the run symbol among the Huffman symbols
+                         of its restart segment (two runs with consecutive n: the second symbol stands right behind the
+                         first one's blocks)
+         longest_run     the longest of them (0: none)
+         correction_bits_in_runs  correction bits read for blocks that an end-of-band run covers (refinement scans)
+         long_codes      Huffman codes of more than 9 bits
+       Nothing else changes with it."""
     i = 2
     assert data[:2] == b"\xff\xd8"
     out = Decoded()
@@ -148,13 +162,17 @@ def decode(data: bytes) -> Decoded:
                     touched[(ci, k)] = level
             out.levels.append(level)
             out.scans.append(dict(comps=[s[0] for s in sel], ss=ss, se=se, ah=ah, al=al, segments=len(parts)))
-            _decode_scan(comps, sel, ss, se, ah, al, restart, parts, dc_tabs, ac_tabs)
+            st = None
+            if stats is not None:
+                st = dict(eob_categories=[0] * 15, runs=[], longest_run=0, correction_bits_in_runs=0, long_codes=0)
+                stats.append(st)
+            _decode_scan(comps, sel, ss, se, ah, al, restart, parts, dc_tabs, ac_tabs, st)
     out.coef = [c["coef"].astype(np.int16) for c in comps]
     out.visible = [(ceil_div(c["ht"], 8), ceil_div(c["w"], 8)) for c in comps]
     return out
 
 
-def _decode_scan(comps, sel, ss, se, ah, al, restart, parts, dc_tabs, ac_tabs):
+def _decode_scan(comps, sel, ss, se, ah, al, restart, parts, dc_tabs, ac_tabs, st=None):
     if len(sel) > 1:  # interleaved: MCUs of h x v blocks per component
         ci0 = sel[0][0]
         mx, my = ceil_div(comps[ci0]["w"], 8 * comps[ci0]["h"]), ceil_div(comps[ci0]["ht"], 8 * comps[ci0]["v"])
@@ -185,12 +203,21 @@ def _decode_scan(comps, sel, ss, se, ah, al, restart, parts, dc_tabs, ac_tabs):
                     elif br.bit():
                         blk[0] |= 1 << al
                 elif ah == 0:
-                    eobrun = _ac_first(br, ac_tabs[ta], blk, ss, se, al, eobrun)
+                    eobrun = _ac_first(br, ac_tabs[ta], blk, ss, se, al, eobrun, st)
                 else:
-                    eobrun = _ac_refine(br, ac_tabs[ta], blk, ss, se, al, eobrun)
+                    eobrun = _ac_refine(br, ac_tabs[ta], blk, ss, se, al, eobrun, st)
+        if st is not None:
+            st["long_codes"] += br.long_codes
 
 
-def _ac_first(br, table, blk, ss, se, al, eobrun):
+def _count_run(st, br, r, length):
+    if st is not None:
+        st["eob_categories"][r] += 1
+        st["runs"].append((length, br.symbols))
+        st["longest_run"] = max(st["longest_run"], length)
+
+
+def _ac_first(br, table, blk, ss, se, al, eobrun, st=None):
     """G.1.2.2: one block of a first AC scan; returns the end-of-band run left for the blocks behind it."""
     if eobrun:
         return eobrun - 1
@@ -202,14 +229,16 @@ def _ac_first(br, table, blk, ss, se, al, eobrun):
             if r == 15:
                 k += 16
                 continue
-            return (1 << r) + br.bits(r) - 1
+            run = (1 << r) + br.bits(r)
+            _count_run(st, br, r, run)
+            return run - 1
         k += r
         blk[ZIGZAG[k]] = _extend(br.bits(s), s) * (1 << al)
         k += 1
     return 0
 
 
-def _ac_refine(br, table, blk, ss, se, al, eobrun):
+def _ac_refine(br, table, blk, ss, se, al, eobrun, st=None):
     """G.1.2.3 (figure G.7): one block of an AC refinement scan."""
     p1 = 1 << al
 
@@ -228,6 +257,7 @@ def _ac_refine(br, table, blk, ss, se, al, eobrun):
                 value = p1 if br.bit() else -p1  # the sign comes in front of the correction bits
             elif r != 15:
                 eobrun = (1 << r) + br.bits(r)
+                _count_run(st, br, r, eobrun)
                 break
             while k <= se:  # pass r zero-history coefficients; the non-zero ones on the way take a correction bit each
                 z = ZIGZAG[k]
@@ -245,6 +275,8 @@ def _ac_refine(br, table, blk, ss, se, al, eobrun):
         while k <= se:
             if blk[ZIGZAG[k]]:
                 correct(ZIGZAG[k])
+                if st is not None:
+                    st["correction_bits_in_runs"] += 1
             k += 1
         eobrun -= 1
     return eobrun

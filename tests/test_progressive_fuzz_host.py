@@ -1,7 +1,8 @@
 """Mutation fuzzing of progressive decoding on the host under AddressSanitizer + UBSan: the product's parser, the scan
 bodies of jg_prog_core.h (through the host twin, tests/emu/prog_twin.cpp) and the hand-over's pack, on mutated copies of
-Pillow's pinned progressive files. A stand-alone program (tests/emu/prog_fuzz_main.cpp): corrupt streams are exercised
-here only, never on the GPU, whose kernels compile the same jg_prog_core.h."""
+Pillow's pinned progressive files, of the two files of long end-of-band runs and of one with a padded work list. A
+stand-alone program (tests/emu/prog_fuzz_main.cpp): corrupt streams are exercised here only, never on the GPU, whose
+kernels compile the same jg_prog_core.h."""
 import os
 import subprocess
 import sys
@@ -23,7 +24,13 @@ def test_mutated_progressive_streams_under_asan_ubsan():
         subprocess.check_call(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
                               + prog_twin.compile_args() + srcs + ["-o", exe])
         files = []
-        for name, (prog, _, _) in sorted(pc.pins().items()):
+        inputs = {name: prog for name, (prog, _, _) in pc.pins().items()}
+        # end-of-band runs of every category and of 0x7FFF blocks (mutated, they meet the clamp of a run to the blocks
+        # left in the segment), and a work list with idle items
+        inputs.update({name: pc.large()[name].prog for name in ("eob_ladder", "eob_cap")})
+        inputs["two_large_444"] = pc.structure()["two_large_444"][0]
+        assert len(inputs) == 10 + 3
+        for name, prog in sorted(inputs.items()):
             p = os.path.join(d, name + ".jpg")
             with open(p, "wb") as f:
                 f.write(prog)
