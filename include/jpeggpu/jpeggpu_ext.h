@@ -37,7 +37,7 @@
  *   jpeggpu_ext_resize_view_to_tensor  the evaluation transform: a window of the resize of each item's WHOLE image, zero
  *                                      outside it -- torchvision's Resize + CenterCrop on Pillow, from a cropped decode
  *   jpeggpu_ext_encode_batch           the way back: uint8 images on the device to baseline JPEG files on the device, byte
- *                                      for byte what Pillow's Image.save writes on libjpeg-turbo
+ *                                      for byte what Pillow's Image.save writes on libjpeg-turbo, optimize=True included
  */
 #ifndef JPEGGPU_JPEGGPU_EXT_H_
 #define JPEGGPU_JPEGGPU_EXT_H_
@@ -902,7 +902,8 @@ enum jpeggpu_status jpeggpu_ext_batch_to_rgb(
  * restart_marker_blocks=) -- byte for byte (tests/golden/encode_pins.npz): jccolor.c's fixed-point RGB -> YCbCr, jcsample.c's
  * h2v1 / h2v2 downsampling without smoothing and its edge rules, jpeg_fdct_islow, the quantiser's rounded division,
  * jpeg_set_quality's tables, jccoefct.c's dummy blocks, jchuff.c with the Annex K tables, a JFIF header without
- * density. Not written: optimised Huffman tables, progressive scans, other samplings, four components, EXIF / ICC.
+ * density; with `optimize` set, jchuff.c's statistics pass and jpeg_gen_optimal_table, the file of save(..., optimize=True)
+ * (tests/golden/encode_opt_pins.npz). Not written: progressive scans, other samplings, four components, EXIF / ICC.
  *   - An item: `data` the device pointer of sample (0, 0) of channel 0; sample (x, y) of channel c is the byte at
  *     data + y * row_pitch + x * pixel_stride + c * channel_stride, so an HWC tensor (pixel_stride 3, channel_stride 1), a CHW
  *     tensor (pixel_stride 1, channel_stride H * W) and any view of either are one struct, without a copy. `channels` 1 (grey)
@@ -916,7 +917,7 @@ enum jpeggpu_status jpeggpu_ext_batch_to_rgb(
  *     bits per coefficient; a ZRL or EOB is shorter than the coefficients it stands for): 1660 bits. So the stream has at
  *     most ceil(1660 blocks / 8) + segments bytes with the padding of each restart segment; every byte may be 0xFF and
  *     doubled by stuffing; then the header, two bytes per restart marker and EOI. 0 for an invalid item.
- *   - jpeggpu_ext_encode_batch encodes items[0..n) on `stream` with EIGHT launches and one copy of descriptors whatever n and
+ *   - jpeggpu_ext_encode_batch encodes items[0..n) on `stream` with EIGHT launches (TEN: `optimize`) and one copy of descriptors whatever n and
  *     the sizes are, and does not synchronise. d_sizes[i] receives the file's length and d_status[i] JPEGGPU_EXT_ENCODE_OK,
  *     or JPEGGPU_EXT_ENCODE_TOO_SMALL if that length exceeds `capacity`: then d_sizes[i] is the capacity it needs and not one
  *     byte of its slot is written; the other items are not affected. Sizes are known on the device before anything is written
@@ -924,12 +925,32 @@ enum jpeggpu_status jpeggpu_ext_batch_to_rgb(
  *     private to the stream until the call has executed; it holds the coefficients (2 bytes per padded sample) and the
  *     unstuffed stream at its bound. The host may reuse `items` when the call returns: descriptors and headers travel
  *     through a page-locked ring of four (the fifth call in a row waits until the copy of the first has executed).
+ *   - `optimize` 1: the item's Huffman tables are made from its own symbol counts, as libjpeg makes them (a call may mix items
+ *     with and without). Its DHT segments, and so its header, depend on the pixels: jpeggpu_ext_encode_header returns
+ *     JPEGGPU_NOT_SUPPORTED for it and sets `*size` to the length of the header with the Annex K tables, which no optimised
+ *     header exceeds (its DHTs list at most the same 12 + 162 symbols, twice). An optimised DC code can take 16 bits, so
+ *     jpeggpu_ext_encode_bound counts 16 + 11 + 63 x 26 = 1665 bits per block for such an item, with that header length, and
+ *     the scratch size follows; for items without the flag both are what they were. A call with at least one such item
+ *     enqueues TEN launches (the symbol counts and the tables, behind the first), still with one copy and no
+ *     synchronisation. d_status[i] JPEGGPU_EXT_ENCODE_TABLE_OVERFLOW: a code of the item would be longer than 32 bits before
+ *     limiting, where libjpeg raises JERR_HUFF_CLEN_OVERFLOW (a table of more than 32 symbols whose counts grow like
+ *     Fibonacci numbers: millions of blocks); d_sizes[i] is 0, the slot is not written, the other items are not affected.
+ *   - jpeggpu_ext_encode_tables_from_counts runs only the table kernel, on `stream`: d_counts holds 256 counts per table,
+ *     d_bits_values receives per table the 16 `bits` bytes and 256 `values` bytes of a DHT segment (values behind the last
+ *     symbol are 0), d_status[t] JPEGGPU_EXT_ENCODE_OK, _TABLE_OVERFLOW, or _EMPTY_TABLE for counts that are all zero (libjpeg
+ *     does not define that table) or beyond what libjpeg's search covers (a count of 2^28, a sum of 10^9); then bits and
+ *     values are zeros. JPEGGPU_INVALID_ARGUMENT for a NULL pointer or n_tables <= 0.
  *   - JPEGGPU_INVALID_ARGUMENT, before anything is enqueued: NULL items, d_scratch, d_sizes, d_status or data, a NULL out with
  *     a capacity, n <= 0 or > 65535, width or height outside 1..65535, channels other than 1 or 3, quality outside 1..100, an
- *     unknown subsampling, a restart interval outside 0..65535, scratch_size too small. JPEGGPU_NOT_SUPPORTED: an item whose
+ *     unknown subsampling, a restart interval outside 0..65535, an `optimize` other than 0 or 1, scratch_size too small. JPEGGPU_NOT_SUPPORTED: an item whose
  *     stream bound reaches 2^32 bits (about 2.5 million blocks: 160 megapixels grey), or a call of 2^31 blocks. */
 enum jpeggpu_ext_subsampling { JPEGGPU_EXT_SUBSAMPLING_444 = 0, JPEGGPU_EXT_SUBSAMPLING_422 = 1, JPEGGPU_EXT_SUBSAMPLING_420 = 2 };
-enum jpeggpu_ext_encode_status { JPEGGPU_EXT_ENCODE_OK = 0, JPEGGPU_EXT_ENCODE_TOO_SMALL = 1 };
+enum jpeggpu_ext_encode_status {
+    JPEGGPU_EXT_ENCODE_OK             = 0,
+    JPEGGPU_EXT_ENCODE_TOO_SMALL      = 1,
+    JPEGGPU_EXT_ENCODE_TABLE_OVERFLOW = 2, /* an optimised code longer than 32 bits before limiting */
+    JPEGGPU_EXT_ENCODE_EMPTY_TABLE    = 3  /* jpeggpu_ext_encode_tables_from_counts only */
+};
 struct jpeggpu_ext_encode_item {
     const uint8_t* data;
     int width, height;
@@ -938,6 +959,7 @@ struct jpeggpu_ext_encode_item {
     int quality;
     int subsampling; /* enum jpeggpu_ext_subsampling */
     int restart_interval;
+    int optimize; /* 0: the Annex K tables, 1: tables made for the image (where LP64 had padding: size and offsets are unchanged) */
     uint8_t* out;
     size_t capacity;
 };
@@ -950,6 +972,12 @@ enum jpeggpu_status jpeggpu_ext_encode_batch(
     void* d_scratch,
     size_t scratch_size,
     size_t* d_sizes,
+    int* d_status,
+    jpeggpu_stream_t stream);
+enum jpeggpu_status jpeggpu_ext_encode_tables_from_counts(
+    const uint32_t* d_counts,
+    int n_tables,
+    uint8_t* d_bits_values,
     int* d_status,
     jpeggpu_stream_t stream);
 

@@ -136,7 +136,7 @@ class EncodeItem(C.Structure):
     """struct jpeggpu_ext_encode_item"""
     _fields_ = [("data", C.c_void_p), ("width", C.c_int), ("height", C.c_int), ("channels", C.c_int), ("row_pitch", C.c_int64),
                 ("pixel_stride", C.c_int64), ("channel_stride", C.c_int64), ("quality", C.c_int), ("subsampling", C.c_int),
-                ("restart_interval", C.c_int), ("out", C.c_void_p), ("capacity", C.c_size_t)]
+                ("restart_interval", C.c_int), ("optimize", C.c_int), ("out", C.c_void_p), ("capacity", C.c_size_t)]
 
 
 class ExtScanLayout(C.Structure):
@@ -302,6 +302,8 @@ def lib():
         L.jpeggpu_ext_encode_scratch_size.argtypes = [C.POINTER(EncodeItem), C.c_int]
         L.jpeggpu_ext_encode_scratch_size.restype = C.c_size_t
         L.jpeggpu_ext_encode_batch.argtypes = [C.POINTER(EncodeItem), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "jpeggpu_ext_encode_tables_from_counts"):
+        L.jpeggpu_ext_encode_tables_from_counts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.jpeggpu_ext_resize_weights.argtypes = [
         C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
     _lib = L
@@ -1320,28 +1322,31 @@ def decode_batch_to_rgb(datas, device="cuda:0", crops=None, scales=None, exif_tr
         return out
 
 
-def encode_item(width, height, channels=3, quality=75, subsampling="4:2:0", restart_interval=0):
-    """A struct jpeggpu_ext_encode_item of this geometry without pointers: what encode_header and encode_bound need."""
+def encode_item(width, height, channels=3, quality=75, subsampling="4:2:0", restart_interval=0, optimize=False):
+    """A struct jpeggpu_ext_encode_item of this geometry without pointers: what encode_header and encode_bound need.
+    `optimize`: Huffman tables made for the image (Pillow's optimize=True) instead of the Annex K tables."""
     if subsampling not in SUBSAMPLINGS:
         raise ValueError("subsampling %r is not one of %s" % (subsampling, ", ".join(SUBSAMPLINGS)))
     it = EncodeItem()
     it.width, it.height, it.channels = int(width), int(height), int(channels)
     it.quality, it.subsampling, it.restart_interval = int(quality), SUBSAMPLINGS[subsampling], int(restart_interval)
+    it.optimize = int(optimize)  # (2 stays 2: the library refuses it)
     return it
 
 
-def encode_header(width, height, channels=3, quality=75, subsampling="4:2:0", restart_interval=0) -> bytes:
-    """jpeggpu_ext_encode_header (host only): SOI up to the end of the scan header of the file encode_jpeg writes."""
-    it = encode_item(width, height, channels, quality, subsampling, restart_interval)
+def encode_header(width, height, channels=3, quality=75, subsampling="4:2:0", restart_interval=0, optimize=False) -> bytes:
+    """jpeggpu_ext_encode_header (host only): SOI up to the end of the scan header of the file encode_jpeg writes. With
+    optimize=True it raises JpegGpuError (NOT_SUPPORTED): that header holds tables made from the pixels."""
+    it = encode_item(width, height, channels, quality, subsampling, restart_interval, optimize)
     size = C.c_size_t(1024)
     buf = C.create_string_buffer(1024)
     _check(lib().jpeggpu_ext_encode_header(C.byref(it), buf, C.byref(size)), "jpeggpu_ext_encode_header")
     return buf.raw[:size.value]
 
 
-def encode_bound(width, height, channels=3, quality=75, subsampling="4:2:0", restart_interval=0) -> int:
+def encode_bound(width, height, channels=3, quality=75, subsampling="4:2:0", restart_interval=0, optimize=False) -> int:
     """jpeggpu_ext_encode_bound (host only): the size no file of this geometry exceeds."""
-    it = encode_item(width, height, channels, quality, subsampling, restart_interval)
+    it = encode_item(width, height, channels, quality, subsampling, restart_interval, optimize)
     n = lib().jpeggpu_ext_encode_bound(C.byref(it))
     if n == 0:
         raise JpegGpuError(Status.INVALID_ARGUMENT, "jpeggpu_ext_encode_bound")
@@ -1356,7 +1361,7 @@ def _per_image(v, n, name):
     return [v] * n
 
 
-def _encode_items(images, quality, subsampling, restart_interval, layout):
+def _encode_items(images, quality, subsampling, restart_interval, layout, optimize=False):
     """The items of a call, without output slots: `images` a list of uint8 device tensors or one 4-D tensor."""
     import torch
 
@@ -1369,6 +1374,7 @@ def _encode_items(images, quality, subsampling, restart_interval, layout):
     images = list(images)
     n = len(images)
     qs, ss, rs = _per_image(quality, n, "quality"), _per_image(subsampling, n, "subsampling"), _per_image(restart_interval, n, "restart_interval")
+    os_ = _per_image(optimize, n, "optimize")
     items = (EncodeItem * max(n, 1))()
     for i, x in enumerate(images):
         if x.dtype != torch.uint8 or not x.is_cuda or x.dim() not in (2, 3):
@@ -1384,20 +1390,21 @@ def _encode_items(images, quality, subsampling, restart_interval, layout):
             cs, rp, ps = x.stride()
         if ch not in (1, 3):
             raise ValueError("image %d: 1 or 3 channels are expected, not %d" % (i, ch))
-        it = encode_item(w, h, ch, qs[i], ss[i], rs[i])
+        it = encode_item(w, h, ch, qs[i], ss[i], rs[i], os_[i])
         it.data, it.row_pitch, it.pixel_stride, it.channel_stride = x.data_ptr(), rp, ps, cs
         items[i] = it
     return images, items
 
 
-def encode_into(images, outs, quality=75, subsampling="4:2:0", restart_interval=0, layout="HWC"):
+def encode_into(images, outs, quality=75, subsampling="4:2:0", restart_interval=0, layout="HWC", optimize=False):
     """jpeggpu_ext_encode_batch on torch's current stream, without synchronising: image i into the slot outs[i] (a contiguous
     uint8 device tensor whose length is the capacity; None: capacity 0, only the size is reported). Returns the device
     tensors (sizes int64[n], status int32[n]); status 1 marks a slot that was too small, whose size is the capacity it
-    needs and which was not written."""
+    needs and which was not written; status 2 (only with `optimize`) an image whose optimised code would be longer than 32
+    bits, which libjpeg refuses too: its size is 0. `optimize`: one value or one per image, like `quality`."""
     import torch
 
-    images, items = _encode_items(images, quality, subsampling, restart_interval, layout)
+    images, items = _encode_items(images, quality, subsampling, restart_interval, layout, optimize)
     n = len(images)
     if len(outs) != n:
         raise ValueError("outs must have one entry per image")
@@ -1429,15 +1436,16 @@ def _encode_results(sizes, status):
     return raw[:8 * n].view(torch.int64).tolist(), raw[8 * n:].view(torch.int32).tolist()
 
 
-def encode_jpeg_to_device(images, quality=75, subsampling="4:2:0", restart_interval=0, layout="HWC", capacities=None):
+def encode_jpeg_to_device(images, quality=75, subsampling="4:2:0", restart_interval=0, layout="HWC", capacities=None, optimize=False):
     """Baseline JPEG files of `images`, left on the device: returns (buffer, offsets, sizes) -- file i is
     buffer[offsets[i]:offsets[i] + sizes[i]], a uint8 device tensor and two lists of ints. Arguments and the files are
     encode_jpeg's. `capacities`: the slot sizes to start with (default: each image's raw sample count plus its header);
     items whose file is larger are encoded once more into slots of the size they reported, behind the others. One
-    jpeggpu_ext_encode_batch call (two after an overflow) and one synchronisation per call."""
+    jpeggpu_ext_encode_batch call (two after an overflow) and one synchronisation per call. `optimize` as in encode_jpeg;
+    the default capacities are those of the same call without it (an optimised file is the shorter one)."""
     import torch
 
-    images, items = _encode_items(images, quality, subsampling, restart_interval, layout)
+    images, items = _encode_items(images, quality, subsampling, restart_interval, layout, optimize)
     n = len(images)
     if n == 0:
         return None, [], []
@@ -1446,7 +1454,9 @@ def encode_jpeg_to_device(images, quality=75, subsampling="4:2:0", restart_inter
         capacities = []
         for i in range(n):
             size = C.c_size_t(0)
-            _check(lib().jpeggpu_ext_encode_header(C.byref(items[i]), None, C.byref(size)), "jpeggpu_ext_encode_header")
+            plain = EncodeItem.from_buffer_copy(items[i])
+            plain.optimize = 0
+            _check(lib().jpeggpu_ext_encode_header(C.byref(plain), None, C.byref(size)), "jpeggpu_ext_encode_header")
             capacities.append(items[i].width * items[i].height * items[i].channels + size.value)
     capacities = _per_image(capacities, n, "capacities")
 
@@ -1458,7 +1468,11 @@ def encode_jpeg_to_device(images, quality=75, subsampling="4:2:0", restart_inter
         buf = torch.empty(max(total, 1), dtype=torch.uint8, device=device)
         outs = [buf[o:o + c] for o, c in zip(offsets, caps)]
         pick = lambda v: [v[i] for i in which] if isinstance(v, (list, tuple)) else v  # noqa: E731
-        sizes, status = _encode_results(*encode_into([images[i] for i in which], outs, pick(quality), pick(subsampling), pick(restart_interval), layout))
+        sizes, status = _encode_results(*encode_into([images[i] for i in which], outs, pick(quality), pick(subsampling), pick(restart_interval), layout,
+                                                     pick(optimize)))
+        for i, st in zip(which, status):
+            if st == 2:
+                raise JpegGpuError(Status.NOT_SUPPORTED, "jpeggpu_ext_encode_batch: image %d needs a Huffman code of more than 32 bits (libjpeg refuses it too)" % i)
         return buf, offsets, sizes, status
 
     buf, offsets, sizes, status = run(list(range(n)), [int(c) for c in capacities])
@@ -1474,18 +1488,19 @@ def encode_jpeg_to_device(images, quality=75, subsampling="4:2:0", restart_inter
     return buf, offsets, sizes
 
 
-def encode_jpeg(images, quality=75, subsampling="4:2:0", restart_interval=0, layout="HWC"):
+def encode_jpeg(images, quality=75, subsampling="4:2:0", restart_interval=0, layout="HWC", optimize=False):
     """Baseline JPEG files of uint8 device tensors, as a list of bytes: each file is, byte for byte, what Pillow on
     libjpeg-turbo writes with Image.fromarray(x).save(f, "JPEG", quality=quality, subsampling=subsampling,
     restart_marker_blocks=restart_interval) for the same pixels on the host.
     `images`: a list of tensors of any sizes, or one 4-D batch tensor; an item is H x W x 3 (RGB), H x W x 1 or H x W (grey),
     or with layout="CHW" 3 x H x W / 1 x H x W. Views (crops, row-padded, permuted) are read through their strides, without a
     copy. `quality` 1..100, `subsampling` "4:4:4" | "4:2:2" | "4:2:0" (grey has no chroma) and `restart_interval` (MCUs
-    between restart markers, 0: none) are one value or one per image. The whole list is ONE jpeggpu_ext_encode_batch call (a
+    between restart markers, 0: none) are one value or one per image, and so is `optimize`: True writes the file of
+    save(..., optimize=True), with Huffman tables made from the image's own symbol counts. The whole list is ONE jpeggpu_ext_encode_batch call (a
     second one for the items whose file is larger than its raw pixels), one synchronisation and one copy to the host."""
     import torch
 
-    buf, offsets, sizes = encode_jpeg_to_device(images, quality, subsampling, restart_interval, layout)
+    buf, offsets, sizes = encode_jpeg_to_device(images, quality, subsampling, restart_interval, layout, optimize=optimize)
     if not sizes:
         return []
     host = torch.cat([buf[o:o + s] for o, s in zip(offsets, sizes)]).cpu().numpy().tobytes()  # only the files' bytes travel
@@ -1494,3 +1509,23 @@ def encode_jpeg(images, quality=75, subsampling="4:2:0", restart_interval=0, lay
         out.append(host[p:p + s])
         p += s
     return out
+
+
+def encode_tables_from_counts(counts):
+    """jpeggpu_ext_encode_tables_from_counts on torch's current stream, without synchronising: jpeg_gen_optimal_table of
+    each row of `counts`, an n x 256 int32 device tensor of symbol counts (a negative one reads as a count beyond the range).
+    Returns the device tensors (bits_values uint8[n, 272]: 16 `bits` bytes, then 256 `values` bytes; status int32[n]: 0,
+    2 for a code longer than 32 bits before limiting, 3 for an empty table or counts beyond libjpeg's range)."""
+    import torch
+
+    if not isinstance(counts, torch.Tensor) or not counts.is_cuda or counts.dtype != torch.int32 or counts.dim() != 2 or counts.shape[1] != 256:
+        raise ValueError("counts: an n x 256 int32 device tensor is expected")
+    if counts.shape[0] == 0:
+        raise ValueError("counts: at least one table is expected")
+    counts = counts.contiguous()
+    n = counts.shape[0]
+    out = torch.empty((n, 272), dtype=torch.uint8, device=counts.device)
+    status = torch.empty(n, dtype=torch.int32, device=counts.device)
+    _check(lib().jpeggpu_ext_encode_tables_from_counts(counts.data_ptr(), n, out.data_ptr(), status.data_ptr(),
+                                                       torch.cuda.current_stream(counts.device).cuda_stream), "jpeggpu_ext_encode_tables_from_counts")
+    return out, status

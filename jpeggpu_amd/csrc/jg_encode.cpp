@@ -20,6 +20,9 @@ namespace enc {
 namespace {
 
 static_assert(sizeof(size_t) == sizeof(unsigned long long), "d_sizes is written as 64-bit words");
+static_assert(sizeof(jpeggpu_ext_encode_item) == 80 && offsetof(jpeggpu_ext_encode_item, out) == 64,
+              "`optimize` took the place of padding: callers built against the struct without it pass a zero there");
+static_assert(sizeof(Item) == 392, "the scratch size of a call without optimised items is part of the interface");
 
 // Annex K.1, K.2 (natural order) and K.3 - K.6
 const uint8_t kBaseLuma[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,  69,  56,
@@ -105,7 +108,7 @@ bool valid(const jpeggpu_ext_encode_item* it)
 {
     return it && it->width >= 1 && it->width <= 65535 && it->height >= 1 && it->height <= 65535 && (it->channels == 1 || it->channels == 3) &&
            it->quality >= 1 && it->quality <= 100 && it->subsampling >= JPEGGPU_EXT_SUBSAMPLING_444 && it->subsampling <= JPEGGPU_EXT_SUBSAMPLING_420 &&
-           it->restart_interval >= 0 && it->restart_interval <= 65535;
+           it->restart_interval >= 0 && it->restart_interval <= 65535 && (it->optimize == 0 || it->optimize == 1);
 }
 
 struct Geometry {
@@ -124,8 +127,8 @@ Geometry geometry(const jpeggpu_ext_encode_item& it)
     const uint64_t mcus = uint64_t(g.mcus_x) * g.mcus_y;
     g.blocks        = mcus * g.blocks_per_mcu;
     g.segments      = it.restart_interval ? (mcus + it.restart_interval - 1) / it.restart_interval : 1;
-    // every block at kMaxBlockBits, and less than a byte of padding ones per segment
-    g.stream_bound = (g.blocks * kMaxBlockBits + 7) / 8 + g.segments;
+    // every block at kMaxBlockBits (optimised tables: a DC code of 16 bits), and less than a byte of padding ones per segment
+    g.stream_bound = (g.blocks * (it.optimize ? kMaxBlockBitsOptimized : kMaxBlockBits) + 7) / 8 + g.segments;
     return g;
 }
 
@@ -138,8 +141,9 @@ void put_segment(std::vector<uint8_t>& out, int marker, const uint8_t* payload, 
     out.insert(out.end(), payload, payload + len);
 }
 
-/// SOI .. the end of SOS, as libjpeg writes it for Pillow.
-void write_header(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out)
+/// The header as libjpeg writes it for Pillow, in the three parts an item with optimised tables needs: SOI .. SOF0 (the
+/// prefix), the DHTs, which for such an item the device writes, and DRI if any and SOS (the suffix).
+void write_prefix(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out)
 {
     const int ncomp = it.channels;
     // the factors that were asked for go into the frame header of a grey file too (Pillow sets them whatever the mode); with
@@ -164,6 +168,11 @@ void write_header(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out)
         sof[8 + 3 * c] = uint8_t(c == 0 ? 0 : 1);
     }
     put_segment(out, 0xC0, sof, size_t(6 + 3 * ncomp));
+}
+
+void write_standard_dhts(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out)
+{
+    const int ncomp          = it.channels;
     const HuffSpec* specs[4] = {&kDcLuma, &kAcLuma, &kDcChroma, &kAcChroma};
     const uint8_t ids[4]     = {0x00, 0x10, 0x01, 0x11};
     for (int t = 0; t < (ncomp == 1 ? 2 : 4); ++t) {
@@ -173,6 +182,11 @@ void write_header(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out)
         std::memcpy(seg + 17, specs[t]->values, size_t(specs[t]->count));
         put_segment(out, 0xC4, seg, size_t(17 + specs[t]->count));
     }
+}
+
+void write_suffix(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out)
+{
+    const int ncomp = it.channels;
     if (it.restart_interval) {
         const uint8_t dri[2] = {uint8_t(it.restart_interval >> 8), uint8_t(it.restart_interval)};
         put_segment(out, 0xDD, dri, 2);
@@ -186,25 +200,55 @@ void write_header(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out)
     put_segment(out, 0xDA, sos, size_t(4 + 2 * ncomp));
 }
 
+/// SOI .. the end of SOS with the Annex K tables: the header of an item without optimised tables, and the longest an
+/// optimised one can get (its DHTs list at most the symbols these list: 12 categories, 162 AC symbols).
+void write_header(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out)
+{
+    write_prefix(it, out);
+    write_standard_dhts(it, out);
+    write_suffix(it, out);
+}
+
 /// The plan of a call: every offset in d_scratch. JPEGGPU_NOT_SUPPORTED for an item or a call beyond the kernels' 32-bit
-/// bit offsets and block indices.
+/// bit offsets and block indices. headers[i]: what goes to the blob at the item's header_off -- its header, or for an item
+/// with optimised tables its OptState with the two parts of the header that the host knows.
 jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan, std::vector<Item>* out_items, std::vector<std::vector<uint8_t>>* headers)
 {
     if (!items || n <= 0 || n > 65535) return JPEGGPU_INVALID_ARGUMENT;
     uint64_t tiles = 0, chunks = 0, header_bytes = 0;
     std::vector<Geometry> geo(static_cast<size_t>(n));
-    std::vector<uint8_t> header;
+    std::vector<uint8_t> header, part;
+    plan.optimized = 0;
     for (int i = 0; i < n; ++i) {
         if (!valid(&items[i])) return JPEGGPU_INVALID_ARGUMENT;
         geo[i] = geometry(items[i]);
         if (geo[i].stream_bound * 8 >= (uint64_t(1) << 32)) return JPEGGPU_NOT_SUPPORTED;
         tiles += (geo[i].blocks + kTileBlocks - 1) / kTileBlocks;
         chunks += (geo[i].stream_bound + kChunkBytes - 1) / kChunkBytes;
-        write_header(items[i], header);
+        if (items[i].optimize) {
+            ++plan.optimized;
+            header.assign(sizeof(OptState), 0);
+            if (headers) {
+                OptState st{}; // (counts, lengths and statuses zero: the device adds to them)
+                write_prefix(items[i], part);
+                if (part.size() > sizeof st.prefix) return JPEGGPU_INTERNAL_ERROR;
+                st.prefix_len = uint32_t(part.size());
+                std::memcpy(st.prefix, part.data(), part.size());
+                part.clear();
+                write_suffix(items[i], part);
+                if (part.size() > sizeof st.suffix) return JPEGGPU_INTERNAL_ERROR;
+                st.suffix_len = uint32_t(part.size());
+                std::memcpy(st.suffix, part.data(), part.size());
+                std::memcpy(header.data(), &st, sizeof st);
+            }
+        } else {
+            write_header(items[i], header);
+        }
         header_bytes += align_up(header.size(), 16);
         if (headers) headers->push_back(header);
     }
     if (tiles * kTileBlocks >= (uint64_t(1) << 31) || chunks >= (uint64_t(1) << 31)) return JPEGGPU_NOT_SUPPORTED;
+    if (header_bytes + sizeof(Tables) + sizeof(Item) * (size_t(n) + 1) + 1024 >= (uint64_t(1) << 32)) return JPEGGPU_NOT_SUPPORTED; // header_off is 32 bits
     plan.n      = n;
     plan.tiles  = uint32_t(tiles);
     plan.chunks = uint32_t(chunks);
@@ -231,6 +275,7 @@ jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan
         const uint64_t coef     = take(g.blocks * 128);
         const uint64_t stream   = take(chunks_i * kChunkBytes);
         const uint64_t starts   = take(chunks_i * (kChunkBytes / 8));
+        const uint64_t work     = items[i].optimize ? take(sizeof(OptWork)) : 0;
         if (out_items) {
             const jpeggpu_ext_encode_item& s = items[i];
             Item& d                          = (*out_items)[i];
@@ -244,7 +289,8 @@ jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan
             d.grid_w = (s.width + 7) / 8, d.grid_h = (s.height + 7) / 8;
             d.restart_interval = s.restart_interval;
             d.tile_start = tile, d.chunk_start = chunk;
-            d.header_off = uint32_t(header_off), d.header_len = uint32_t((*headers)[i].size());
+            d.header_off = uint32_t(header_off), d.header_len = s.optimize ? 0u : uint32_t((*headers)[i].size());
+            if (s.optimize) std::memcpy((*headers)[i].data() + offsetof(OptState, work_off), &work, sizeof work);
             uint8_t q[64];
             for (int t = 0; t < 2; ++t) {
                 quant_table(t ? kBaseChroma : kBaseLuma, s.quality, q);
@@ -300,6 +346,7 @@ enum jpeggpu_status jpeggpu_ext_encode_header(const struct jpeggpu_ext_encode_it
     }
     const size_t room = *size;
     *size             = header.size();
+    if (item->optimize) return JPEGGPU_NOT_SUPPORTED; // its DHTs depend on the pixels; no header is longer than this one
     if (!host_buf) return JPEGGPU_SUCCESS;
     if (room < header.size()) return JPEGGPU_INVALID_ARGUMENT;
     std::memcpy(host_buf, header.data(), header.size());
@@ -312,7 +359,8 @@ size_t jpeggpu_ext_encode_bound(const struct jpeggpu_ext_encode_item* item)
     (void)tables(); // checks kMaxBlockBits against the tables
     const Geometry g = geometry(*item);
     size_t header    = 0;
-    if (jpeggpu_ext_encode_header(item, nullptr, &header) != JPEGGPU_SUCCESS) return 0;
+    const jpeggpu_status st = jpeggpu_ext_encode_header(item, nullptr, &header);
+    if (st != JPEGGPU_SUCCESS && !(item->optimize && st == JPEGGPU_NOT_SUPPORTED)) return 0;
     // the header; the stream with every byte 0xFF and stuffed; a marker between segments; EOI
     return header + 2 * size_t(g.stream_bound) + 2 * size_t(g.segments - 1) + 2;
 }
@@ -364,6 +412,13 @@ enum jpeggpu_status jpeggpu_ext_encode_batch(
     rs.in_use[r] = true;
     rs.next      = (r + 1) % Staging::kRing;
     if (launch_encode(plan, base, reinterpret_cast<unsigned long long*>(d_sizes), d_status, stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
+    return JPEGGPU_SUCCESS;
+}
+
+enum jpeggpu_status jpeggpu_ext_encode_tables_from_counts(const uint32_t* d_counts, int n_tables, uint8_t* d_bits_values, int* d_status, jpeggpu_stream_t stream)
+{
+    if (!d_counts || n_tables <= 0 || !d_bits_values || !d_status) return JPEGGPU_INVALID_ARGUMENT;
+    if (launch_tables_from_counts(d_counts, n_tables, d_bits_values, d_status, stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
     return JPEGGPU_SUCCESS;
 }
 

@@ -1,4 +1,5 @@
-// jg_encode.hip -- baseline JPEG encoding for gfx950: eight launches per call, whatever the number of images and their sizes.
+// jg_encode.hip -- baseline JPEG encoding for gfx950: eight launches per call (ten with optimised Huffman tables), whatever the
+// number of images and their sizes.
 //
 //   1 encode_blocks   one lane per 8 x 8 block: gather through the item's strides (edge rules of jccolor / jcsample),
 //                     colour conversion, chroma downsampling, jpeg_fdct_islow, quantisation; int16 coefficients in zigzag
@@ -13,6 +14,15 @@
 //   7 scan<Count>     ONE workgroup: what lies before each chunk
 //   8 write_files     sizes and the capacity test first; then header, stuffed bytes, restart markers and EOI at their final
 //                     places in the caller's slot
+//
+// A call with at least one item that asks for optimised Huffman tables has two launches more, between 1 and 2:
+//
+//   1a count_symbols  one lane per block of such an item: its DC category and AC symbols into a histogram of the tile in LDS,
+//                     whose non-zero bins are added to the item's counts (integer atomics: the order does not show)
+//   1b build_tables   one wave per item and table: jpeg_gen_optimal_table (jchuff.c) on those counts, the item's own encoder
+//                     tables and its DHT segments
+//
+// Every later stage reads an item's tables through the item (tables_of), so the two kinds of item mix in one call.
 //
 // No kernel waits for another workgroup: every dependency is a launch boundary.
 #include "jg_encode.hpp"
@@ -67,6 +77,16 @@ __device__ inline int item_of_chunk(const Item* items, int n, uint32_t chunk)
         else hi = mid - 1;
     }
     return lo;
+}
+
+/// An item with optimised tables keeps its state where the others keep their header (jg_encode.hpp: Item::header_len).
+__device__ inline bool optimized(const Item& it) { return it.header_len == 0u; }
+__device__ inline OptState* opt_state(const Item& it, uint8_t* scratch) { return reinterpret_cast<OptState*>(scratch + it.header_off); }
+__device__ inline const OptState* opt_state(const Item& it, const uint8_t* scratch) { return reinterpret_cast<const OptState*>(scratch + it.header_off); }
+/// The tables an item's blocks are coded with: the call's Annex K tables, or the item's own.
+__device__ inline const Tables* tables_of(const Item& it, const uint8_t* scratch, const Tables* standard)
+{
+    return optimized(it) ? &reinterpret_cast<const OptWork*>(scratch + opt_state(it, scratch)->work_off)->tables : standard;
 }
 
 /// Bytes of item i's unstuffed stream, padding of the last segment included: where the cursor stands behind its last tile.
@@ -257,8 +277,9 @@ __global__ __launch_bounds__(kTileBlocks) void count_bits(
     const int b       = first + threadIdx.x;
     const int16_t* gc = reinterpret_cast<const int16_t*>(scratch + it.coef_off);
     load_tile(coefs, reinterpret_cast<const uint32_t*>(gc), first, it.blocks);
-    for (int i = threadIdx.x; i < 2 * 256; i += kTileBlocks) ac_len[i] = tables->ac[i] & 0xFF;
-    if (threadIdx.x < 2 * 16) dc_len[threadIdx.x] = tables->dc[threadIdx.x] & 0xFF;
+    const Tables* tab = tables_of(it, scratch, tables);
+    for (int i = threadIdx.x; i < 2 * 256; i += kTileBlocks) ac_len[i] = tab->ac[i] & 0xFF;
+    if (threadIdx.x < 2 * 16) dc_len[threadIdx.x] = tab->dc[threadIdx.x] & 0xFF;
     __syncthreads();
     Cursor mine{kAdd, 0u, 0u};
     if (b < it.blocks) {
@@ -331,8 +352,9 @@ __global__ __launch_bounds__(kTileBlocks) void pack_blocks(
     const int b       = first + threadIdx.x;
     const int16_t* gc = reinterpret_cast<const int16_t*>(scratch + it.coef_off);
     load_tile(coefs, reinterpret_cast<const uint32_t*>(gc), first, it.blocks);
-    for (int i = threadIdx.x; i < 2 * 256; i += kTileBlocks) ac_tab[i] = tables->ac[i];
-    if (threadIdx.x < 2 * 16) dc_tab[threadIdx.x] = tables->dc[threadIdx.x];
+    const Tables* tab = tables_of(it, scratch, tables);
+    for (int i = threadIdx.x; i < 2 * 256; i += kTileBlocks) ac_tab[i] = tab->ac[i];
+    if (threadIdx.x < 2 * 16) dc_tab[threadIdx.x] = tab->dc[threadIdx.x];
     const bool valid = b < it.blocks;
     BlockPlace p{};
     Cursor mine{kAdd, 0u, 0u};
@@ -382,6 +404,218 @@ __global__ __launch_bounds__(kTileBlocks) void pack_blocks(
         if (pad) bw.put((1u << pad) - 1, pad);
     }
     bw.finish();
+}
+
+// ------------------------------------------------------------------------------------------------
+// 1a, 1b: optimised tables -- the symbols of an item, and jpeg_gen_optimal_table on their counts
+// ------------------------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(kTileBlocks) void count_symbols(const Item* __restrict__ items, int n, uint8_t* __restrict__ scratch)
+{
+    __shared__ uint32_t coefs[kTileBlocks * kLdsRow];
+    __shared__ uint32_t hist[2 * kTableCounts];
+    const Item& it = items[item_of_tile(items, n, blockIdx.x)];
+    if (!optimized(it)) return;
+    const int first   = (blockIdx.x - it.tile_start) * kTileBlocks;
+    const int b       = first + threadIdx.x;
+    const int16_t* gc = reinterpret_cast<const int16_t*>(scratch + it.coef_off);
+    load_tile(coefs, reinterpret_cast<const uint32_t*>(gc), first, it.blocks);
+    for (int i = threadIdx.x; i < 2 * kTableCounts; i += kTileBlocks) hist[i] = 0u;
+    __syncthreads();
+    if (b < it.blocks) { // what jchuff.c's htest_one_block counts
+        const BlockPlace p = place_of(it, b);
+        const int16_t* c   = reinterpret_cast<const int16_t*>(coefs + threadIdx.x * kLdsRow);
+        const int diff     = c[0] - (p.pred_block >= 0 ? gc[size_t(p.pred_block) * 64] : 0);
+        uint32_t* h        = hist + p.table * kTableCounts;
+        atomicAdd(h + category(diff), 1u);
+        h += kDcSymbols;
+        int run = 0;
+        for (int k = 1; k < 64; ++k) {
+            const int v = c[k];
+            if (v == 0) {
+                ++run;
+                continue;
+            }
+            if (run > 15) atomicAdd(h + 0xF0, uint32_t(run >> 4));
+            atomicAdd(h + ((run & 15) << 4 | category(v)), 1u);
+            run = 0;
+        }
+        if (run) atomicAdd(h, 1u);
+    }
+    __syncthreads();
+    uint32_t* counts = &opt_state(it, scratch)->counts[0][0];
+    for (int i = threadIdx.x; i < 2 * kTableCounts; i += kTileBlocks)
+        if (hist[i]) atomicAdd(counts + i, hist[i]); // integer sums: the order of the tiles does not show
+}
+
+/// What one wave needs in LDS to build a table.
+struct TableLds {
+    uint32_t all[34];  // symbols per code length 1..32, the pseudo-symbol included: libjpeg's bits[], limited in place
+    uint32_t real[34]; // the same without the pseudo-symbol and before limiting, then its exclusive prefix sums
+    uint32_t first_code[17], first_pos[17];
+    uint32_t n_values;
+};
+
+constexpr int kTableOk = 0, kTableOverflow = 2, kTableEmpty = 3; // jpeggpu_ext_encode_status
+constexpr uint32_t kFreqLimit = 1000000000u;                     // where libjpeg's search for the least count starts
+
+/// jpeg_gen_optimal_table (jchuff.c) by ONE wave of 64 lanes on counts[0 .. n_sym), n_sym <= 256: 16 `bits` bytes, the
+/// `values` in the order of the DHT segment (*n_values of them) and, for codes_out != nullptr, code << 8 | length of every
+/// symbol below n_sym by Annex C from those two (0 for a symbol without a code). Returns kTableOk; kTableOverflow for a code
+/// length above 32 before limiting (libjpeg's JERR_HUFF_CLEN_OVERFLOW); kTableEmpty for counts that are all zero, where
+/// libjpeg's loops leave their arrays, or beyond what its search covers (a count of 2^28, a sum of 10^9). Then bits and
+/// codes are zeros and there are no values.
+///
+/// Lane l owns the symbols l, l + 64, .. l + 256 (symbol 256 is libjpeg's pseudo-symbol of count 1, which keeps the code of
+/// all ones unused). A merge takes the two least non-zero counts, of equal counts the LARGEST index as libjpeg's `<=` does:
+/// both are the least keys count * 512 + (511 - index) of the wave. libjpeg then walks the chains of both trees to lengthen
+/// the code of every member; here every symbol knows the root of its tree, and those of either root do that themselves.
+__device__ int build_table(const uint32_t* counts, int n_sym, TableLds& lds, uint8_t* bits_out, uint8_t* values_out, uint32_t* codes_out, int* n_values)
+{
+    constexpr int kOwn  = 5;
+    constexpr uint64_t kNone = ~uint64_t(0);
+    const int lane = threadIdx.x;
+    uint32_t freq[kOwn];
+    int root[kOwn], size[kOwn], rank[kOwn];
+    uint64_t total = 0;
+    bool beyond    = false;
+#pragma unroll
+    for (int j = 0; j < kOwn; ++j) {
+        const int e = lane + 64 * j;
+        uint32_t f  = e < n_sym ? counts[e] : 0u;
+        beyond |= f >= (1u << 28);
+        total += f;
+        freq[j] = e == 256 ? 1u : f;
+        root[j] = e, size[j] = 0, rank[j] = 0;
+    }
+    for (int off = 32; off; off >>= 1) total += __shfl_xor(total, off, 64);
+    int status = total == 0 || total >= kFreqLimit || __any(beyond) ? kTableEmpty : kTableOk;
+    while (status == kTableOk) { // (uniform: at most 256 merges)
+        uint64_t m1 = kNone, m2 = kNone;
+#pragma unroll
+        for (int j = 0; j < kOwn; ++j) {
+            const uint64_t key = freq[j] ? uint64_t(freq[j]) << 9 | uint32_t(511 - (lane + 64 * j)) : kNone;
+            if (key < m1) m2 = m1, m1 = key;
+            else if (key < m2) m2 = key;
+        }
+        for (int off = 32; off; off >>= 1) { // the two least of the wave: the keys of symbols with a count are distinct
+            const uint64_t o1 = __shfl_xor(m1, off, 64), o2 = __shfl_xor(m2, off, 64);
+            const uint64_t lo = m1 < o1 ? m1 : o1, hi = m1 < o1 ? o1 : m1, second = m2 < o2 ? m2 : o2;
+            m1 = lo, m2 = hi < second ? hi : second;
+        }
+        if (m2 == kNone) break; // one tree is left
+        const int c1 = 511 - int(m1 & 511u), c2 = 511 - int(m2 & 511u);
+#pragma unroll
+        for (int j = 0; j < kOwn; ++j) {
+            const int e = lane + 64 * j;
+            if (root[j] == c1 || root[j] == c2) ++size[j], root[j] = c1;
+            if (e == c1) freq[j] += uint32_t(m2 >> 9);
+            if (e == c2) freq[j] = 0u;
+        }
+    }
+    if (lane < 34) lds.all[lane] = lds.real[lane] = 0u;
+    __syncthreads();
+    bool over = false;
+#pragma unroll
+    for (int j = 0; j < kOwn; ++j) {
+        if (size[j] > 32) over = true;
+        else if (size[j]) {
+            atomicAdd(&lds.all[size[j]], 1u);
+            if (lane + 64 * j < 256) atomicAdd(&lds.real[size[j]], 1u);
+        }
+    }
+    __syncthreads();
+    if (status == kTableOk && __any(over)) status = kTableOverflow;
+    if (status != kTableOk) {
+        if (lane < 16) bits_out[lane] = 0;
+        if (codes_out)
+            for (int e = lane; e < n_sym; e += 64) codes_out[e] = 0u;
+        *n_values = 0;
+        return status;
+    }
+    if (lane == 0) {
+        uint32_t* bits = lds.all;
+        for (int i = 32; i > 16; --i) { // libjpeg's length limiting: a pair of the longest codes moves up by one, a shorter code pays
+            while (bits[i] > 0) {
+                int j = i - 2;
+                while (j > 0 && bits[j] == 0) --j; // (a tree of 257 leaves this deep always has a shorter code)
+                bits[i] -= 2, bits[i - 1] += 1, bits[j + 1] += 2, bits[j] -= 1;
+            }
+        }
+        int i = 16;
+        while (i > 0 && bits[i] == 0) --i;
+        bits[i] -= 1; // the pseudo-symbol leaves the longest length
+        uint32_t code = 0, pos = 0, before = 0;
+        for (int len = 1; len <= 16; ++len) {
+            lds.first_code[len] = code, lds.first_pos[len] = pos;
+            code = (code + bits[len]) << 1;
+            pos += bits[len];
+        }
+        for (int len = 1; len <= 32; ++len) {
+            const uint32_t here = lds.real[len];
+            lds.real[len]       = before;
+            before += here;
+        }
+        lds.n_values = before;
+    }
+    __syncthreads();
+    // huffval lists the symbols by code length BEFORE limiting, then by value: a symbol's place is the symbols of shorter
+    // lengths and those of its own length in front of it
+    for (int s = 1; s <= 32; ++s) {
+        uint32_t at = lds.real[s];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const unsigned long long same = __ballot(size[j] == s);
+            if (size[j] == s) rank[j] = int(at + __popcll(same & ((1ull << lane) - 1ull)));
+            at += uint32_t(__popcll(same));
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int e   = lane + 64 * j;
+        uint32_t code = 0u;
+        if (size[j]) {
+            values_out[rank[j]] = uint8_t(e);
+            for (int len = 1; len <= 16; ++len) // Annex C on (bits, values): after limiting the length is not size[j]
+                if (uint32_t(rank[j]) >= lds.first_pos[len] && uint32_t(rank[j]) - lds.first_pos[len] < lds.all[len])
+                    code = (lds.first_code[len] + uint32_t(rank[j]) - lds.first_pos[len]) << 8 | uint32_t(len);
+        }
+        if (codes_out && e < n_sym) codes_out[e] = code;
+    }
+    if (lane < 16) bits_out[lane] = uint8_t(lds.all[lane + 1]);
+    *n_values = int(lds.n_values);
+    return kTableOk;
+}
+
+__global__ __launch_bounds__(64) void build_tables(const Item* __restrict__ items, int n, uint8_t* __restrict__ scratch)
+{
+    __shared__ TableLds lds;
+    const Item& it = items[blockIdx.x >> 2];
+    const int t    = blockIdx.x & 3; // DC0, AC0, DC1, AC1
+    if (!optimized(it) || (it.channels == 1 && t >= 2)) return;
+    OptState* st    = opt_state(it, scratch);
+    OptWork* work   = reinterpret_cast<OptWork*>(scratch + st->work_off);
+    const int table = t >> 1, ac = t & 1;
+    uint8_t* seg    = work->dht[t];
+    int n_values    = 0;
+    const int status = build_table(st->counts[table] + (ac ? kDcSymbols : 0), ac ? 256 : kDcSymbols, lds, seg + 5, seg + 21,
+                                   ac ? work->tables.ac + 256 * table : work->tables.dc + 16 * table, &n_values);
+    if (threadIdx.x == 0) {
+        const uint32_t len = 2u + 17u + uint32_t(n_values);
+        seg[0] = 0xFF, seg[1] = 0xC4, seg[2] = uint8_t(len >> 8), seg[3] = uint8_t(len), seg[4] = uint8_t(ac << 4 | table);
+        st->dht_len[t]      = len + 2u;
+        st->table_status[t] = uint32_t(status);
+    }
+}
+
+__global__ __launch_bounds__(64) void tables_from_counts(const uint32_t* __restrict__ counts, uint8_t* __restrict__ out, int* __restrict__ status)
+{
+    __shared__ TableLds lds;
+    uint8_t* o   = out + size_t(blockIdx.x) * (16 + 256);
+    int n_values = 0;
+    const int st = build_table(counts + size_t(blockIdx.x) * 256, 256, lds, o, o + 16, nullptr, &n_values);
+    for (int i = n_values + threadIdx.x; i < 256; i += 64) o[16 + i] = 0;
+    if (threadIdx.x == 0) status[blockIdx.x] = st;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -496,16 +730,37 @@ __global__ __launch_bounds__(256) void write_files(
         // the size is known before a byte is written: header, stream, a 0x00 per 0xFF, two bytes per marker, EOI
         const uint32_t last_chunk = items[i + 1].chunk_start - 1;
         const Count all           = compose(count_before[last_chunk], counts[last_chunk]);
-        const uint64_t size       = uint64_t(it.header_len) + bytes + all.ff + 2u * all.starts + 2u;
-        const bool fits           = size <= it.capacity;
+        // an item with optimised tables has its header in parts: what the host wrote around what build_tables made
+        const OptState* st  = optimized(it) ? opt_state(it, blob) : nullptr;
+        uint32_t header_len = it.header_len, table_status = 0u;
+        if (st) {
+            header_len = st->prefix_len + st->suffix_len;
+            for (int t = 0; t < 4; ++t) {
+                header_len += st->dht_len[t];
+                table_status = max(table_status, st->table_status[t]);
+            }
+        }
+        const uint64_t size = table_status ? 0u : uint64_t(header_len) + bytes + all.ff + 2u * all.starts + 2u;
+        const bool fits     = size <= it.capacity;
         if (part == 0 && threadIdx.x == 0) {
             d_sizes[i]  = size;
-            d_status[i] = fits ? 0 : 1;
+            d_status[i] = table_status ? int(table_status) : fits ? 0 : 1;
         }
-        if (!fits || uint64_t(part) * kChunkBytes >= bytes) continue;
+        if (table_status || !fits || uint64_t(part) * kChunkBytes >= bytes) continue;
         uint8_t* out = it.out;
         if (part == 0) {
-            for (uint32_t k = threadIdx.x; k < it.header_len; k += 256) out[k] = blob[it.header_off + k];
+            if (st) {
+                const OptWork* work = reinterpret_cast<const OptWork*>(scratch + st->work_off);
+                uint32_t at         = st->prefix_len;
+                for (uint32_t k = threadIdx.x; k < st->prefix_len; k += 256) out[k] = st->prefix[k];
+                for (int t = 0; t < 4; ++t) {
+                    for (uint32_t k = threadIdx.x; k < st->dht_len[t]; k += 256) out[at + k] = work->dht[t][k];
+                    at += st->dht_len[t];
+                }
+                for (uint32_t k = threadIdx.x; k < st->suffix_len; k += 256) out[at + k] = st->suffix[k];
+            } else {
+                for (uint32_t k = threadIdx.x; k < header_len; k += 256) out[k] = blob[it.header_off + k];
+            }
             if (threadIdx.x == 0) out[size - 2] = 0xFF, out[size - 1] = 0xD9;
         }
         uint32_t dw[8], starts;
@@ -526,7 +781,7 @@ __global__ __launch_bounds__(256) void write_files(
         const Count before = counts[chunk].reset ? Count{1u, 0u, 0u} : count_before[chunk];
         const uint32_t p0  = part * uint32_t(kChunkBytes) + threadIdx.x * kChunkLane;
         uint32_t marker    = before.starts + (before_lane >> 16);
-        uint8_t* o         = out + it.header_len + p0 + before.ff + (before_lane & 0xFFFFu) + 2u * marker;
+        uint8_t* o         = out + header_len + p0 + before.ff + (before_lane & 0xFFFFu) + 2u * marker;
 #pragma unroll
         for (int k = 0; k < kChunkLane; ++k) {
             if (p0 + k < bytes) {
@@ -557,6 +812,10 @@ hipError_t launch_encode(const Plan& plan, uint8_t* d_scratch, unsigned long lon
     Count* count_before   = reinterpret_cast<Count*>(d_scratch + plan.count_before_off);
     const uint32_t chunk_grid = plan.chunks < 4096u ? plan.chunks : 4096u;
     encode_blocks<<<plan.tiles, kTileBlocks, 0, stream>>>(items, plan.n, d_scratch);
+    if (plan.optimized) {
+        count_symbols<<<plan.tiles, kTileBlocks, 0, stream>>>(items, plan.n, d_scratch);
+        build_tables<<<uint32_t(plan.n) * 4u, 64, 0, stream>>>(items, plan.n, d_scratch);
+    }
     count_bits<<<plan.tiles, kTileBlocks, 0, stream>>>(items, plan.n, tables, d_scratch, bits, tile_sum);
     scan_before<Cursor><<<1, kScanThreads, 0, stream>>>(tile_sum, tile_before, plan.tiles);
     clear_streams<<<chunk_grid, 256, 0, stream>>>(items, plan.n, plan.chunks, d_scratch, tile_sum, tile_before);
@@ -564,6 +823,12 @@ hipError_t launch_encode(const Plan& plan, uint8_t* d_scratch, unsigned long lon
     count_bytes<<<chunk_grid, 256, 0, stream>>>(items, plan.n, plan.chunks, d_scratch, tile_sum, tile_before, counts);
     scan_before<Count><<<1, kScanThreads, 0, stream>>>(counts, count_before, plan.chunks);
     write_files<<<chunk_grid, 256, 0, stream>>>(items, plan.n, plan.chunks, d_scratch, d_scratch, tile_sum, tile_before, counts, count_before, d_sizes, d_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_tables_from_counts(const uint32_t* d_counts, int n_tables, uint8_t* d_bits_values, int* d_status, hipStream_t stream)
+{
+    tables_from_counts<<<uint32_t(n_tables), 64, 0, stream>>>(d_counts, d_bits_values, d_status);
     return hipGetLastError();
 }
 

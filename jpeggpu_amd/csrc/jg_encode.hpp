@@ -27,6 +27,8 @@ constexpr int kScanThreads = 128;
 constexpr int kMaxDcCode    = 11;
 constexpr int kMaxAcCode    = 16;
 constexpr int kMaxBlockBits = kMaxDcCode + 11 + 63 * (kMaxAcCode + 10); // 1660
+/// With optimised tables (jpeg_gen_optimal_table limits every code to 16 bits) a DC code can be 16 bits long as well.
+constexpr int kMaxBlockBitsOptimized = 16 + 11 + 63 * (16 + 10); // 1665
 
 /// Position in the unstuffed stream as a function of the position before: what a run of blocks does to the bit cursor.
 /// A segment's first block starts on a byte, so the functions are  x + a  (kAdd),  roundup8(x + a) + b  (kRound) and the
@@ -57,7 +59,7 @@ struct Item {
     int grid_w, grid_h;   // the luma component's real blocks: beyond them a block of an MCU is a dummy
     int restart_interval; // MCUs, 0: none
     uint32_t tile_start, chunk_start; // this item's first tile / chunk among the call's
-    uint32_t header_off, header_len;  // in the blob
+    uint32_t header_off, header_len;  // in the blob. header_len 0: an item with optimised tables, header_off its OptState
     uint16_t divisor[2][64];          // 8 * quantiser, zigzag order: luma, chroma
 };
 
@@ -67,9 +69,34 @@ struct Tables {
     uint32_t ac[2 * 256];
 };
 
+/// Symbol counts of one table as the kernels keep them: 16 DC categories, then 256 AC symbols.
+constexpr int kDcSymbols    = 16;
+constexpr int kTableCounts  = kDcSymbols + 256;
+constexpr int kDhtBytes     = 280; // a DHT segment of 256 values: marker and length (4), class / id, 16 bits, the values: 277
+constexpr int kPrefixBytes  = 192; // SOI, APP0, two DQTs, SOF0 of three components: 177
+constexpr int kSuffixBytes  = 32;  // DRI, SOS of three components: 20
+/// What the device makes for an item with optimised tables, outside the blob: its own Tables and its DHT segments
+/// (DC0, AC0, DC1, AC1; a grey item has the first two), each as it stands in the file.
+struct OptWork {
+    Tables tables;
+    uint8_t dht[4][kDhtBytes];
+};
+/// The state of an item with optimised tables, in the blob: the host zeroes it and writes the two parts of the header
+/// that do not depend on the pixels; count_symbols adds into `counts`, build_tables writes the rest.
+struct OptState {
+    uint32_t counts[2][kTableCounts]; // luma, chroma (Cb and Cr share a table)
+    uint32_t dht_len[4];              // bytes of OptWork::dht[t], 0: no such table
+    uint32_t table_status[4];         // jpeggpu_ext_encode_status of each table: 0, or 2 (a code length above 32)
+    uint32_t prefix_len, suffix_len;
+    uint64_t work_off;                // OptWork, in d_scratch
+    uint8_t prefix[kPrefixBytes];     // SOI .. SOF0
+    uint8_t suffix[kSuffixBytes];     // DRI if any, SOS
+};
+
 /// Where the parts of a call sit in d_scratch (byte offsets; the blob is copied from the host, the rest the device's).
 struct Plan {
     int n;
+    int optimized; // items with optimised tables: none, and the call is the eight launches it always was
     uint32_t tiles, chunks;
     uint64_t tables_off, items_off; // in the blob
     uint64_t blob_bytes;
@@ -82,6 +109,9 @@ struct Plan {
 };
 
 hipError_t launch_encode(const Plan& plan, uint8_t* d_scratch, unsigned long long* d_sizes, int* d_status, hipStream_t stream);
+
+/// jpeg_gen_optimal_table of n_tables x 256 counts: per table 16 `bits` bytes and 256 `values` bytes, and a status.
+hipError_t launch_tables_from_counts(const uint32_t* d_counts, int n_tables, uint8_t* d_bits_values, int* d_status, hipStream_t stream);
 
 } // namespace enc
 } // namespace jg

@@ -12,9 +12,11 @@ Both are WALL time per call, the copy to the host included, medians of the round
 milliseconds. The bar: the device route is not slower than the host route by more than the two spreads. Before anything is
 timed the files of both routes are compared (Pillow: byte for byte).
 `--once WORKLOAD` runs a single device call and nothing else: the process to put under a kernel trace.
+`--optimize` measures optimised Huffman tables instead: encode_jpeg(optimize=True) against Pillow's optimize=True, by the same
+method and with the same bar; each entry also records what the files save against the standard tables.
 Not bench.py: that one measures the flagship workload and stays as it is.
 
-    python tools/encode_rate.py [--rounds 7] [--iters 10] [--out encode_rate.json] [--once photos|resized]
+    python tools/encode_rate.py [--optimize] [--rounds 7] [--iters 10] [--out encode_rate.json] [--once photos|resized]
 """
 import argparse
 import io
@@ -52,12 +54,16 @@ def _host_route(torch, params):
 
     pool = ThreadPoolExecutor(THREADS)
     try:
-        from PIL import Image
+        from PIL import Image, ImageFile
+
+        optimize = bool(params.get("optimize"))
+        if optimize:  # the whole file leaves libjpeg at once then, and Pillow's default buffer is too small for some files
+            ImageFile.MAXBLOCK = max(ImageFile.MAXBLOCK, 1 << 26)
 
         def save(a):
             f = io.BytesIO()
             Image.fromarray(a).save(f, "JPEG", quality=params["quality"], subsampling=PILLOW_SUBSAMPLING[params["subsampling"]],
-                                    restart_marker_blocks=params["restart_interval"])
+                                    restart_marker_blocks=params["restart_interval"], optimize=optimize)
             return f.getvalue()
 
         def fn(images):
@@ -67,6 +73,8 @@ def _host_route(torch, params):
         return "pillow", fn
     except ImportError:
         pass
+    if params.get("optimize"):  # torchvision's encoder has no such switch: no yardstick
+        return None, None
     try:
         import torchvision.io as tio
 
@@ -88,7 +96,7 @@ def _wall(torch, fn, iters):
     return (time.perf_counter() - t) * 1000 / iters
 
 
-def run(rounds, iters):
+def run(rounds, iters, optimize=False):
     import torch
 
     import jpeggpu_amd
@@ -97,6 +105,9 @@ def run(rounds, iters):
     for name in ("photos", "resized"):
         images, params = _workload(torch, name)
         n = len(images)
+        standard_bytes = sum(len(f) for f in jpeggpu_amd.encode_jpeg(images, **params)) if optimize else None
+        if optimize:
+            params["optimize"] = True
         device = lambda: jpeggpu_amd.encode_jpeg(images, **params)  # noqa: E731
         files = device()
         route, host_fn = _host_route(torch, params)
@@ -112,6 +123,9 @@ def run(rounds, iters):
                 res[k].append(_wall(torch, fn, iters))
         r = {k: _spread(v) for k, v in res.items()}
         entry = dict(workload=name, images=n, params=params, file_bytes=sum(len(f) for f in files), ms=r, yardstick=route, rounds=rounds, iters=iters)
+        if optimize:
+            entry["standard_file_bytes"] = standard_bytes
+            entry["saving"] = round(1 - entry["file_bytes"] / standard_bytes, 4)
         if route:
             d, h = r["device"], r["host_" + route]
             entry["bar"] = {"spreads": round(d["spread"] + h["spread"], 4), "device_over_host": round(d["median"] / h["median"], 4),
@@ -122,12 +136,14 @@ def run(rounds, iters):
     return out
 
 
-def once(name):
+def once(name, optimize=False):
     import torch
 
     import jpeggpu_amd
 
     images, params = _workload(torch, name)
+    if optimize:
+        params["optimize"] = True
     files = jpeggpu_amd.encode_jpeg(images, **params)
     torch.cuda.synchronize()
     print(json.dumps(dict(workload=name, images=len(files), file_bytes=sum(len(f) for f in files))))
@@ -139,10 +155,11 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", default=None, choices=("photos", "resized"))
+    ap.add_argument("--optimize", action="store_true")
     a = ap.parse_args()
     if a.once:
-        return once(a.once)
-    res = run(a.rounds, a.iters)
+        return once(a.once, a.optimize)
+    res = run(a.rounds, a.iters, a.optimize)
     for r in res:
         print(json.dumps(r), flush=True)
     if a.out:
