@@ -36,8 +36,9 @@
  *                                      normalised as ToTensor + Normalize do, items flipped left to right where asked
  *   jpeggpu_ext_resize_view_to_tensor  the evaluation transform: a window of the resize of each item's WHOLE image, zero
  *                                      outside it -- torchvision's Resize + CenterCrop on Pillow, from a cropped decode
- *   jpeggpu_ext_encode_batch           the way back: uint8 images on the device to baseline JPEG files on the device, byte
- *                                      for byte what Pillow's Image.save writes on libjpeg-turbo, optimize=True included
+ *   jpeggpu_ext_encode_batch           the way back: uint8 images on the device to baseline or progressive JPEG files on the
+ *                                      device, byte for byte what Pillow's Image.save writes on libjpeg-turbo (optimize=True
+ *                                      and progressive=True included)
  */
 #ifndef JPEGGPU_JPEGGPU_EXT_H_
 #define JPEGGPU_JPEGGPU_EXT_H_
@@ -903,7 +904,9 @@ enum jpeggpu_status jpeggpu_ext_batch_to_rgb(
  * h2v1 / h2v2 downsampling without smoothing and its edge rules, jpeg_fdct_islow, the quantiser's rounded division,
  * jpeg_set_quality's tables, jccoefct.c's dummy blocks, jchuff.c with the Annex K tables, a JFIF header without
  * density; with `optimize` set, jchuff.c's statistics pass and jpeg_gen_optimal_table, the file of save(..., optimize=True)
- * (tests/golden/encode_opt_pins.npz). Not written: progressive scans, other samplings, four components, EXIF / ICC.
+ * (tests/golden/encode_opt_pins.npz); with `progressive` set, jpeg_simple_progression's script coded by jcphuff.c, the file of
+ * save(..., progressive=True) (tests/golden/encode_prog_pins.npz). Not written: other samplings, four components, other scan
+ * scripts, EXIF / ICC.
  *   - An item: `data` the device pointer of sample (0, 0) of channel 0; sample (x, y) of channel c is the byte at
  *     data + y * row_pitch + x * pixel_stride + c * channel_stride, so an HWC tensor (pixel_stride 3, channel_stride 1), a CHW
  *     tensor (pixel_stride 1, channel_stride H * W) and any view of either are one struct, without a copy. `channels` 1 (grey)
@@ -935,6 +938,20 @@ enum jpeggpu_status jpeggpu_ext_batch_to_rgb(
  *     synchronisation. d_status[i] JPEGGPU_EXT_ENCODE_TABLE_OVERFLOW: a code of the item would be longer than 32 bits before
  *     limiting, where libjpeg raises JERR_HUFF_CLEN_OVERFLOW (a table of more than 32 symbols whose counts grow like
  *     Fibonacci numbers: millions of blocks); d_sizes[i] is 0, the slot is not written, the other items are not affected.
+ *   - `progressive` 1 (`optimize` is then ignored: libjpeg always optimises a progressive file, and the bytes are the same
+ *     with either value): a frame header SOF2 and ten scans for RGB, six for grey -- DC first, the low and the high AC band
+ *     of luma, the chroma AC bands, then the refinements --, each scan behind the DHTs of the tables made from its own symbol
+ *     counts (none for a DC refinement), one DRI before the first SOS, restart intervals counted in MCUs of the scan at
+ *     hand (one block in a scan of one component, which walks the component's real blocks only). A call may mix such items
+ *     with the others. They add ELEVEN launches to the call, whatever their number, their sizes and the number of their
+ *     scans; a call without one enqueues what it always did. jpeggpu_ext_encode_header returns JPEGGPU_NOT_SUPPORTED for such
+ *     an item and sets `*size` to a bound on ALL its marker segments: SOI .. SOF2, ten (grey: five) DHTs of 277 bytes, DRI and
+ *     every SOS. jpeggpu_ext_encode_bound counts per block of a scan, every code 16 bits long: DC first 16 + 11 bits, DC
+ *     refinement 1, AC first 26 per coefficient of the band (a code and 10 value bits; a ZRL stands for 16 of them) and 30
+ *     for an EOBn symbol with its 14 bits of run length, AC refinement 17 per coefficient (a code and a sign, or one
+ *     correction bit) and 30; per scan ceil(bits / 8) bytes and one byte of padding per restart segment of that scan; all
+ *     of it doubled by stuffing; two bytes per restart marker of every scan; the marker segments; EOI. The scratch size
+ *     follows. JPEGGPU_EXT_ENCODE_TOO_SMALL and _TABLE_OVERFLOW (any table of any scan) are reported as for `optimize`.
  *   - jpeggpu_ext_encode_tables_from_counts runs only the table kernel, on `stream`: d_counts holds 256 counts per table,
  *     d_bits_values receives per table the 16 `bits` bytes and 256 `values` bytes of a DHT segment (values behind the last
  *     symbol are 0), d_status[t] JPEGGPU_EXT_ENCODE_OK, _TABLE_OVERFLOW, or _EMPTY_TABLE for counts that are all zero (libjpeg
@@ -942,7 +959,7 @@ enum jpeggpu_status jpeggpu_ext_batch_to_rgb(
  *     values are zeros. JPEGGPU_INVALID_ARGUMENT for a NULL pointer or n_tables <= 0.
  *   - JPEGGPU_INVALID_ARGUMENT, before anything is enqueued: NULL items, d_scratch, d_sizes, d_status or data, a NULL out with
  *     a capacity, n <= 0 or > 65535, width or height outside 1..65535, channels other than 1 or 3, quality outside 1..100, an
- *     unknown subsampling, a restart interval outside 0..65535, an `optimize` other than 0 or 1, scratch_size too small. JPEGGPU_NOT_SUPPORTED: an item whose
+ *     unknown subsampling, a restart interval outside 0..65535, an `optimize` or `progressive` other than 0 or 1, scratch_size too small. JPEGGPU_NOT_SUPPORTED: an item whose
  *     stream bound reaches 2^32 bits (about 2.5 million blocks: 160 megapixels grey), or a call of 2^31 blocks. */
 enum jpeggpu_ext_subsampling { JPEGGPU_EXT_SUBSAMPLING_444 = 0, JPEGGPU_EXT_SUBSAMPLING_422 = 1, JPEGGPU_EXT_SUBSAMPLING_420 = 2 };
 enum jpeggpu_ext_encode_status {
@@ -955,6 +972,7 @@ struct jpeggpu_ext_encode_item {
     const uint8_t* data;
     int width, height;
     int channels;
+    int progressive; /* 0: one baseline scan, 1: libjpeg's progressive script (where LP64 had padding: size and offsets are unchanged) */
     int64_t row_pitch, pixel_stride, channel_stride; /* bytes */
     int quality;
     int subsampling; /* enum jpeggpu_ext_subsampling */

@@ -133,8 +133,8 @@ class RgbItem(C.Structure):
 
 
 class EncodeItem(C.Structure):
-    """struct jpeggpu_ext_encode_item"""
-    _fields_ = [("data", C.c_void_p), ("width", C.c_int), ("height", C.c_int), ("channels", C.c_int), ("row_pitch", C.c_int64),
+    """struct jpeggpu_ext_encode_item (`progressive` lies where LP64 had padding behind `channels`)"""
+    _fields_ = [("data", C.c_void_p), ("width", C.c_int), ("height", C.c_int), ("channels", C.c_int), ("progressive", C.c_int), ("row_pitch", C.c_int64),
                 ("pixel_stride", C.c_int64), ("channel_stride", C.c_int64), ("quality", C.c_int), ("subsampling", C.c_int),
                 ("restart_interval", C.c_int), ("optimize", C.c_int), ("out", C.c_void_p), ("capacity", C.c_size_t)]
 
@@ -1322,31 +1322,33 @@ def decode_batch_to_rgb(datas, device="cuda:0", crops=None, scales=None, exif_tr
         return out
 
 
-def encode_item(width, height, channels=3, quality=75, subsampling="4:2:0", restart_interval=0, optimize=False):
+def encode_item(width, height, channels=3, quality=75, subsampling="4:2:0", restart_interval=0, optimize=False, progressive=False):
     """A struct jpeggpu_ext_encode_item of this geometry without pointers: what encode_header and encode_bound need.
-    `optimize`: Huffman tables made for the image (Pillow's optimize=True) instead of the Annex K tables."""
+    `optimize`: Huffman tables made for the image (Pillow's optimize=True) instead of the Annex K tables. `progressive`:
+    libjpeg's progressive script (Pillow's progressive=True), whose tables are always made for the image."""
     if subsampling not in SUBSAMPLINGS:
         raise ValueError("subsampling %r is not one of %s" % (subsampling, ", ".join(SUBSAMPLINGS)))
     it = EncodeItem()
     it.width, it.height, it.channels = int(width), int(height), int(channels)
     it.quality, it.subsampling, it.restart_interval = int(quality), SUBSAMPLINGS[subsampling], int(restart_interval)
     it.optimize = int(optimize)  # (2 stays 2: the library refuses it)
+    it.progressive = int(progressive)
     return it
 
 
-def encode_header(width, height, channels=3, quality=75, subsampling="4:2:0", restart_interval=0, optimize=False) -> bytes:
+def encode_header(width, height, channels=3, quality=75, subsampling="4:2:0", restart_interval=0, optimize=False, progressive=False) -> bytes:
     """jpeggpu_ext_encode_header (host only): SOI up to the end of the scan header of the file encode_jpeg writes. With
-    optimize=True it raises JpegGpuError (NOT_SUPPORTED): that header holds tables made from the pixels."""
-    it = encode_item(width, height, channels, quality, subsampling, restart_interval, optimize)
+    optimize=True or progressive=True it raises JpegGpuError (NOT_SUPPORTED): that header holds tables made from the pixels."""
+    it = encode_item(width, height, channels, quality, subsampling, restart_interval, optimize, progressive)
     size = C.c_size_t(1024)
     buf = C.create_string_buffer(1024)
     _check(lib().jpeggpu_ext_encode_header(C.byref(it), buf, C.byref(size)), "jpeggpu_ext_encode_header")
     return buf.raw[:size.value]
 
 
-def encode_bound(width, height, channels=3, quality=75, subsampling="4:2:0", restart_interval=0, optimize=False) -> int:
+def encode_bound(width, height, channels=3, quality=75, subsampling="4:2:0", restart_interval=0, optimize=False, progressive=False) -> int:
     """jpeggpu_ext_encode_bound (host only): the size no file of this geometry exceeds."""
-    it = encode_item(width, height, channels, quality, subsampling, restart_interval, optimize)
+    it = encode_item(width, height, channels, quality, subsampling, restart_interval, optimize, progressive)
     n = lib().jpeggpu_ext_encode_bound(C.byref(it))
     if n == 0:
         raise JpegGpuError(Status.INVALID_ARGUMENT, "jpeggpu_ext_encode_bound")
@@ -1361,7 +1363,7 @@ def _per_image(v, n, name):
     return [v] * n
 
 
-def _encode_items(images, quality, subsampling, restart_interval, layout, optimize=False):
+def _encode_items(images, quality, subsampling, restart_interval, layout, optimize=False, progressive=False):
     """The items of a call, without output slots: `images` a list of uint8 device tensors or one 4-D tensor."""
     import torch
 
@@ -1375,6 +1377,7 @@ def _encode_items(images, quality, subsampling, restart_interval, layout, optimi
     n = len(images)
     qs, ss, rs = _per_image(quality, n, "quality"), _per_image(subsampling, n, "subsampling"), _per_image(restart_interval, n, "restart_interval")
     os_ = _per_image(optimize, n, "optimize")
+    ps_ = _per_image(progressive, n, "progressive")
     items = (EncodeItem * max(n, 1))()
     for i, x in enumerate(images):
         if x.dtype != torch.uint8 or not x.is_cuda or x.dim() not in (2, 3):
@@ -1390,21 +1393,22 @@ def _encode_items(images, quality, subsampling, restart_interval, layout, optimi
             cs, rp, ps = x.stride()
         if ch not in (1, 3):
             raise ValueError("image %d: 1 or 3 channels are expected, not %d" % (i, ch))
-        it = encode_item(w, h, ch, qs[i], ss[i], rs[i], os_[i])
+        it = encode_item(w, h, ch, qs[i], ss[i], rs[i], os_[i], ps_[i])
         it.data, it.row_pitch, it.pixel_stride, it.channel_stride = x.data_ptr(), rp, ps, cs
         items[i] = it
     return images, items
 
 
-def encode_into(images, outs, quality=75, subsampling="4:2:0", restart_interval=0, layout="HWC", optimize=False):
+def encode_into(images, outs, quality=75, subsampling="4:2:0", restart_interval=0, layout="HWC", optimize=False, progressive=False):
     """jpeggpu_ext_encode_batch on torch's current stream, without synchronising: image i into the slot outs[i] (a contiguous
     uint8 device tensor whose length is the capacity; None: capacity 0, only the size is reported). Returns the device
     tensors (sizes int64[n], status int32[n]); status 1 marks a slot that was too small, whose size is the capacity it
-    needs and which was not written; status 2 (only with `optimize`) an image whose optimised code would be longer than 32
-    bits, which libjpeg refuses too: its size is 0. `optimize`: one value or one per image, like `quality`."""
+    needs and which was not written; status 2 (only with `optimize` or `progressive`) an image whose optimised code would be
+    longer than 32 bits, which libjpeg refuses too: its size is 0. `optimize`, `progressive`: one value or one per image,
+    like `quality`."""
     import torch
 
-    images, items = _encode_items(images, quality, subsampling, restart_interval, layout, optimize)
+    images, items = _encode_items(images, quality, subsampling, restart_interval, layout, optimize, progressive)
     n = len(images)
     if len(outs) != n:
         raise ValueError("outs must have one entry per image")
@@ -1436,16 +1440,16 @@ def _encode_results(sizes, status):
     return raw[:8 * n].view(torch.int64).tolist(), raw[8 * n:].view(torch.int32).tolist()
 
 
-def encode_jpeg_to_device(images, quality=75, subsampling="4:2:0", restart_interval=0, layout="HWC", capacities=None, optimize=False):
+def encode_jpeg_to_device(images, quality=75, subsampling="4:2:0", restart_interval=0, layout="HWC", capacities=None, optimize=False, progressive=False):
     """Baseline JPEG files of `images`, left on the device: returns (buffer, offsets, sizes) -- file i is
     buffer[offsets[i]:offsets[i] + sizes[i]], a uint8 device tensor and two lists of ints. Arguments and the files are
     encode_jpeg's. `capacities`: the slot sizes to start with (default: each image's raw sample count plus its header);
     items whose file is larger are encoded once more into slots of the size they reported, behind the others. One
-    jpeggpu_ext_encode_batch call (two after an overflow) and one synchronisation per call. `optimize` as in encode_jpeg;
-    the default capacities are those of the same call without it (an optimised file is the shorter one)."""
+    jpeggpu_ext_encode_batch call (two after an overflow) and one synchronisation per call. `optimize` and `progressive` as
+    in encode_jpeg; the default capacities are those of the same call without them (a baseline header and the raw samples)."""
     import torch
 
-    images, items = _encode_items(images, quality, subsampling, restart_interval, layout, optimize)
+    images, items = _encode_items(images, quality, subsampling, restart_interval, layout, optimize, progressive)
     n = len(images)
     if n == 0:
         return None, [], []
@@ -1455,7 +1459,7 @@ def encode_jpeg_to_device(images, quality=75, subsampling="4:2:0", restart_inter
         for i in range(n):
             size = C.c_size_t(0)
             plain = EncodeItem.from_buffer_copy(items[i])
-            plain.optimize = 0
+            plain.optimize = plain.progressive = 0
             _check(lib().jpeggpu_ext_encode_header(C.byref(plain), None, C.byref(size)), "jpeggpu_ext_encode_header")
             capacities.append(items[i].width * items[i].height * items[i].channels + size.value)
     capacities = _per_image(capacities, n, "capacities")
@@ -1469,7 +1473,7 @@ def encode_jpeg_to_device(images, quality=75, subsampling="4:2:0", restart_inter
         outs = [buf[o:o + c] for o, c in zip(offsets, caps)]
         pick = lambda v: [v[i] for i in which] if isinstance(v, (list, tuple)) else v  # noqa: E731
         sizes, status = _encode_results(*encode_into([images[i] for i in which], outs, pick(quality), pick(subsampling), pick(restart_interval), layout,
-                                                     pick(optimize)))
+                                                     pick(optimize), pick(progressive)))
         for i, st in zip(which, status):
             if st == 2:
                 raise JpegGpuError(Status.NOT_SUPPORTED, "jpeggpu_ext_encode_batch: image %d needs a Huffman code of more than 32 bits (libjpeg refuses it too)" % i)
@@ -1488,7 +1492,7 @@ def encode_jpeg_to_device(images, quality=75, subsampling="4:2:0", restart_inter
     return buf, offsets, sizes
 
 
-def encode_jpeg(images, quality=75, subsampling="4:2:0", restart_interval=0, layout="HWC", optimize=False):
+def encode_jpeg(images, quality=75, subsampling="4:2:0", restart_interval=0, layout="HWC", optimize=False, progressive=False):
     """Baseline JPEG files of uint8 device tensors, as a list of bytes: each file is, byte for byte, what Pillow on
     libjpeg-turbo writes with Image.fromarray(x).save(f, "JPEG", quality=quality, subsampling=subsampling,
     restart_marker_blocks=restart_interval) for the same pixels on the host.
@@ -1496,11 +1500,13 @@ def encode_jpeg(images, quality=75, subsampling="4:2:0", restart_interval=0, lay
     or with layout="CHW" 3 x H x W / 1 x H x W. Views (crops, row-padded, permuted) are read through their strides, without a
     copy. `quality` 1..100, `subsampling` "4:4:4" | "4:2:2" | "4:2:0" (grey has no chroma) and `restart_interval` (MCUs
     between restart markers, 0: none) are one value or one per image, and so is `optimize`: True writes the file of
-    save(..., optimize=True), with Huffman tables made from the image's own symbol counts. The whole list is ONE jpeggpu_ext_encode_batch call (a
+    save(..., optimize=True), with Huffman tables made from the image's own symbol counts. `progressive` (one value or one
+    per image): True writes the file of save(..., progressive=True), libjpeg's ten scans (six for grey), whatever `optimize`
+    is. The whole list is ONE jpeggpu_ext_encode_batch call (a
     second one for the items whose file is larger than its raw pixels), one synchronisation and one copy to the host."""
     import torch
 
-    buf, offsets, sizes = encode_jpeg_to_device(images, quality, subsampling, restart_interval, layout, optimize=optimize)
+    buf, offsets, sizes = encode_jpeg_to_device(images, quality, subsampling, restart_interval, layout, optimize=optimize, progressive=progressive)
     if not sizes:
         return []
     host = torch.cat([buf[o:o + s] for o, s in zip(offsets, sizes)]).cpu().numpy().tobytes()  # only the files' bytes travel

@@ -1,6 +1,6 @@
 // jg_encode.cpp -- the encoder's part of the exported C ABI (include/jpeggpu/jpeggpu_ext.h): argument checks, the file
 // header, the size bound and the plan of a call for the kernels of jg_encode.hip. It knows nothing of the decoder.
-#include "jg_encode.hpp"
+#include "jg_encode_prog.hpp"
 #include "jg_staging.hpp"
 
 #include <jpeggpu/jpeggpu.h>
@@ -22,6 +22,11 @@ namespace {
 static_assert(sizeof(size_t) == sizeof(unsigned long long), "d_sizes is written as 64-bit words");
 static_assert(sizeof(jpeggpu_ext_encode_item) == 80 && offsetof(jpeggpu_ext_encode_item, out) == 64,
               "`optimize` took the place of padding: callers built against the struct without it pass a zero there");
+static_assert(offsetof(jpeggpu_ext_encode_item, channels) == 16 && offsetof(jpeggpu_ext_encode_item, progressive) == 20 &&
+                  offsetof(jpeggpu_ext_encode_item, row_pitch) == 24 && offsetof(jpeggpu_ext_encode_item, channel_stride) == 40 &&
+                  offsetof(jpeggpu_ext_encode_item, quality) == 48 && offsetof(jpeggpu_ext_encode_item, optimize) == 60 &&
+                  offsetof(jpeggpu_ext_encode_item, capacity) == 72,
+              "`progressive` took the place of the padding behind `channels`: no other member moved");
 static_assert(sizeof(Item) == 392, "the scratch size of a call without optimised items is part of the interface");
 
 // Annex K.1, K.2 (natural order) and K.3 - K.6
@@ -108,13 +113,75 @@ bool valid(const jpeggpu_ext_encode_item* it)
 {
     return it && it->width >= 1 && it->width <= 65535 && it->height >= 1 && it->height <= 65535 && (it->channels == 1 || it->channels == 3) &&
            it->quality >= 1 && it->quality <= 100 && it->subsampling >= JPEGGPU_EXT_SUBSAMPLING_444 && it->subsampling <= JPEGGPU_EXT_SUBSAMPLING_420 &&
-           it->restart_interval >= 0 && it->restart_interval <= 65535 && (it->optimize == 0 || it->optimize == 1);
+           it->restart_interval >= 0 && it->restart_interval <= 65535 && (it->optimize == 0 || it->optimize == 1) &&
+           (it->progressive == 0 || it->progressive == 1);
 }
 
 struct Geometry {
     int hs, vs, mcus_x, mcus_y, blocks_per_mcu;
     uint64_t blocks, segments, stream_bound;
+    uint64_t scan_blocks, markers, marker_bytes; // a progressive item's: the blocks and restart markers of all its scans, DHTs + DRI + SOS at their longest
 };
+
+/// jpeg_simple_progression's script (jcparam.c) as Pillow gets it: component (-1: all, interleaved), Ss, Se, Ah, Al.
+const int kScriptRgb[10][5]  = {{-1, 0, 0, 0, 1}, {0, 1, 5, 0, 2},  {2, 1, 63, 0, 1}, {1, 1, 63, 0, 1}, {0, 6, 63, 0, 2},
+                                {0, 1, 63, 2, 1}, {-1, 0, 0, 1, 0}, {2, 1, 63, 1, 0}, {1, 1, 63, 1, 0}, {0, 1, 63, 1, 0}};
+const int kScriptGrey[6][5] = {{0, 0, 0, 0, 1}, {0, 1, 5, 0, 2}, {0, 6, 63, 0, 2}, {0, 1, 63, 2, 1}, {0, 0, 0, 1, 0}, {0, 1, 63, 1, 0}};
+
+/// The scans of a progressive item, the tables they bring and their headers; returns the bound of its unstuffed stream:
+/// per scan its blocks at their most bits (jg_encode_prog.hpp) and less than a byte of padding ones per restart segment.
+uint64_t prog_script(const jpeggpu_ext_encode_item& it, const Geometry& g, ProgItem& pi, uint64_t* scan_blocks, uint64_t* markers, uint64_t* marker_bytes)
+{
+    const bool grey  = it.channels == 1;
+    const int grid_w = (it.width + 7) / 8, grid_h = (it.height + 7) / 8;
+    const uint64_t mcus = uint64_t(g.mcus_x) * g.mcus_y;
+    pi               = ProgItem{};
+    pi.scans_n       = grey ? 6 : 10;
+    uint64_t first = 0, marks = 0, bound = 0;
+    int slot = 0;
+    *marker_bytes = 0;
+    for (uint32_t s = 0; s < pi.scans_n; ++s) {
+        const int* row = grey ? kScriptGrey[s] : kScriptRgb[s];
+        ProgScan& sc   = pi.scans[s];
+        sc.comp = row[0], sc.ss = row[1], sc.se = row[2], sc.ah = row[3], sc.al = row[4];
+        const uint64_t blocks = sc.comp < 0 ? g.blocks : sc.comp == 0 ? uint64_t(grid_w) * grid_h : mcus;
+        const uint64_t units  = sc.comp < 0 ? mcus : blocks; // what the restart interval counts in this scan
+        const uint64_t segs   = it.restart_interval ? (units + it.restart_interval - 1) / it.restart_interval : 1;
+        sc.blocks       = int(blocks);
+        sc.blocks_x     = sc.comp == 0 ? grid_w : g.mcus_x;
+        sc.first        = uint32_t(first);
+        sc.marks_before = uint32_t(marks);
+        sc.tables       = sc.ss == 0 ? (sc.ah ? 0 : grey ? 1 : 2) : 1;
+        sc.slot         = sc.tables ? slot : -1;
+        for (int t = 0; t < sc.tables; ++t) pi.slot_class_id[slot++] = uint8_t(sc.ss == 0 ? t : 0x10 | (sc.comp > 0));
+        const int band  = sc.se - sc.ss + 1;
+        const int bits  = sc.ss == 0 ? (sc.ah ? kProgDcRefineBits : kProgDcFirstBits) : sc.ah ? prog_ac_refine_bits(band) : prog_ac_first_bits(band);
+        bound += (blocks * uint64_t(bits) + 7) / 8 + segs;
+        first += blocks;
+        marks += segs - 1;
+        // DRI in front of the first SOS; then marker, length, Ns, (Cs, Td Ta) per component, Ss, Se, Ah Al
+        uint32_t n = 0;
+        if (s == 0 && it.restart_interval) {
+            const uint8_t dri[6] = {0xFF, 0xDD, 0, 4, uint8_t(it.restart_interval >> 8), uint8_t(it.restart_interval)};
+            std::memcpy(sc.sos, dri, 6);
+            n = 6;
+        }
+        const int ns = sc.comp < 0 ? 3 : 1;
+        sc.sos[n++] = 0xFF, sc.sos[n++] = 0xDA, sc.sos[n++] = 0, sc.sos[n++] = uint8_t(6 + 2 * ns), sc.sos[n++] = uint8_t(ns);
+        for (int c = 0; c < ns; ++c) {
+            const int comp = sc.comp < 0 ? c : sc.comp;
+            sc.sos[n++]    = uint8_t(comp + 1);
+            sc.sos[n++]    = uint8_t(sc.ss == 0 ? (sc.ah == 0 && comp ? 0x10 : 0x00) : comp > 0);
+        }
+        sc.sos[n++] = uint8_t(sc.ss), sc.sos[n++] = uint8_t(sc.se), sc.sos[n++] = uint8_t(sc.ah << 4 | sc.al);
+        sc.sos_len  = n;
+        *marker_bytes += uint64_t(sc.tables) * 277 + n; // a DHT of 256 values: marker, length, class and id, 16 counts
+    }
+    pi.slots_n   = uint32_t(slot);
+    *scan_blocks = first;
+    *markers     = marks;
+    return bound;
+}
 Geometry geometry(const jpeggpu_ext_encode_item& it)
 {
     Geometry g;
@@ -129,6 +196,11 @@ Geometry geometry(const jpeggpu_ext_encode_item& it)
     g.segments      = it.restart_interval ? (mcus + it.restart_interval - 1) / it.restart_interval : 1;
     // every block at kMaxBlockBits (optimised tables: a DC code of 16 bits), and less than a byte of padding ones per segment
     g.stream_bound = (g.blocks * (it.optimize ? kMaxBlockBitsOptimized : kMaxBlockBits) + 7) / 8 + g.segments;
+    g.scan_blocks = g.markers = g.marker_bytes = 0;
+    if (it.progressive) {
+        ProgItem pi;
+        g.stream_bound = prog_script(it, g, pi, &g.scan_blocks, &g.markers, &g.marker_bytes);
+    }
     return g;
 }
 
@@ -167,7 +239,7 @@ void write_prefix(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out)
         sof[7 + 3 * c] = uint8_t(c == 0 ? hs << 4 | vs : 0x11);
         sof[8 + 3 * c] = uint8_t(c == 0 ? 0 : 1);
     }
-    put_segment(out, 0xC0, sof, size_t(6 + 3 * ncomp));
+    put_segment(out, it.progressive ? 0xC2 : 0xC0, sof, size_t(6 + 3 * ncomp));
 }
 
 void write_standard_dhts(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out)
@@ -212,10 +284,18 @@ void write_header(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out)
 /// The plan of a call: every offset in d_scratch. JPEGGPU_NOT_SUPPORTED for an item or a call beyond the kernels' 32-bit
 /// bit offsets and block indices. headers[i]: what goes to the blob at the item's header_off -- its header, or for an item
 /// with optimised tables its OptState with the two parts of the header that the host knows.
-jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan, std::vector<Item>* out_items, std::vector<std::vector<uint8_t>>* headers)
+/// What a call's progressive items add to the blob.
+struct ProgBlob {
+    std::vector<Item> shadow; // and a sentinel
+    std::vector<ProgItem> items;
+};
+
+jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan, std::vector<Item>* out_items, std::vector<std::vector<uint8_t>>* headers,
+                         ProgBlob* prog)
 {
     if (!items || n <= 0 || n > 65535) return JPEGGPU_INVALID_ARGUMENT;
-    uint64_t tiles = 0, chunks = 0, header_bytes = 0;
+    uint64_t tiles = 0, chunks = 0, header_bytes = 0, prog_tiles = 0, prog_chunks = 0;
+    plan.prog = ProgPlan{};
     std::vector<Geometry> geo(static_cast<size_t>(n));
     std::vector<uint8_t> header, part;
     plan.optimized = 0;
@@ -224,6 +304,14 @@ jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan
         geo[i] = geometry(items[i]);
         if (geo[i].stream_bound * 8 >= (uint64_t(1) << 32)) return JPEGGPU_NOT_SUPPORTED;
         tiles += (geo[i].blocks + kTileBlocks - 1) / kTileBlocks;
+        if (items[i].progressive) { // no header and no chunks among the call's: its stream lies in the progressive spaces
+            ++plan.prog.n;
+            prog_tiles += (geo[i].scan_blocks + kTileBlocks - 1) / kTileBlocks;
+            prog_chunks += (geo[i].stream_bound + kChunkBytes - 1) / kChunkBytes;
+            header.clear();
+            if (headers) headers->push_back(header);
+            continue;
+        }
         chunks += (geo[i].stream_bound + kChunkBytes - 1) / kChunkBytes;
         if (items[i].optimize) {
             ++plan.optimized;
@@ -248,6 +336,7 @@ jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan
         if (headers) headers->push_back(header);
     }
     if (tiles * kTileBlocks >= (uint64_t(1) << 31) || chunks >= (uint64_t(1) << 31)) return JPEGGPU_NOT_SUPPORTED;
+    if (prog_tiles * kTileBlocks >= (uint64_t(1) << 31) || prog_chunks >= (uint64_t(1) << 31)) return JPEGGPU_NOT_SUPPORTED;
     if (header_bytes + sizeof(Tables) + sizeof(Item) * (size_t(n) + 1) + 1024 >= (uint64_t(1) << 32)) return JPEGGPU_NOT_SUPPORTED; // header_off is 32 bits
     plan.n      = n;
     plan.tiles  = uint32_t(tiles);
@@ -261,13 +350,25 @@ jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan
     plan.tables_off       = take(sizeof(Tables));
     plan.items_off        = take(sizeof(Item) * (size_t(n) + 1)); // and a sentinel
     uint64_t header_off   = take(header_bytes);
+    const uint64_t np     = uint64_t(plan.prog.n); // (a take of nothing leaves the offsets of a call without such items as they were)
+    plan.prog.tiles       = uint32_t(prog_tiles);
+    plan.prog.chunks      = uint32_t(prog_chunks);
+    plan.prog.shadow_off  = take(np ? sizeof(Item) * (np + 1) : 0);
+    plan.prog.items_off   = take(sizeof(ProgItem) * np);
     plan.blob_bytes       = off;
     plan.bits_off         = take(tiles * kTileBlocks * sizeof(uint32_t));
     plan.tile_sum_off     = take(tiles * sizeof(Cursor));
     plan.tile_before_off  = take(tiles * sizeof(Cursor));
     plan.count_off        = take(chunks * sizeof(Count));
     plan.count_before_off = take(chunks * sizeof(Count));
-    uint32_t tile = 0, chunk = 0;
+    plan.prog.bits_off         = take(prog_tiles * kTileBlocks * sizeof(uint32_t));
+    plan.prog.facts_off        = take(prog_tiles * kTileBlocks);
+    plan.prog.eobn_off         = take(prog_tiles * kTileBlocks * sizeof(uint16_t));
+    plan.prog.tile_sum_off     = take(prog_tiles * sizeof(Cursor));
+    plan.prog.tile_before_off  = take(prog_tiles * sizeof(Cursor));
+    plan.prog.count_off        = take(prog_chunks * sizeof(Count));
+    plan.prog.count_before_off = take(prog_chunks * sizeof(Count));
+    uint32_t tile = 0, chunk = 0, prog_tile = 0, prog_chunk = 0;
     if (out_items) out_items->resize(size_t(n) + 1);
     for (int i = 0; i < n; ++i) {
         const Geometry& g       = geo[i];
@@ -275,7 +376,8 @@ jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan
         const uint64_t coef     = take(g.blocks * 128);
         const uint64_t stream   = take(chunks_i * kChunkBytes);
         const uint64_t starts   = take(chunks_i * (kChunkBytes / 8));
-        const uint64_t work     = items[i].optimize ? take(sizeof(OptWork)) : 0;
+        const bool progressive  = items[i].progressive != 0;
+        const uint64_t work     = progressive ? take(sizeof(ProgWork)) : items[i].optimize ? take(sizeof(OptWork)) : 0;
         if (out_items) {
             const jpeggpu_ext_encode_item& s = items[i];
             Item& d                          = (*out_items)[i];
@@ -289,16 +391,38 @@ jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan
             d.grid_w = (s.width + 7) / 8, d.grid_h = (s.height + 7) / 8;
             d.restart_interval = s.restart_interval;
             d.tile_start = tile, d.chunk_start = chunk;
-            d.header_off = uint32_t(header_off), d.header_len = s.optimize ? 0u : uint32_t((*headers)[i].size());
-            if (s.optimize) std::memcpy((*headers)[i].data() + offsetof(OptState, work_off), &work, sizeof work);
+            d.header_off = uint32_t(header_off), d.header_len = progressive ? kProgressiveHeader : s.optimize ? 0u : uint32_t((*headers)[i].size());
+            if (s.optimize && !progressive) std::memcpy((*headers)[i].data() + offsetof(OptState, work_off), &work, sizeof work);
             uint8_t q[64];
             for (int t = 0; t < 2; ++t) {
                 quant_table(t ? kBaseChroma : kBaseLuma, s.quality, q);
                 for (int k = 0; k < 64; ++k) d.divisor[t][k] = uint16_t(8 * q[kNatural[k]]);
             }
             header_off += align_up((*headers)[i].size(), 16);
+            if (progressive && prog) {
+                Item sh        = d;
+                sh.tile_start  = prog_tile;
+                sh.chunk_start = prog_chunk;
+                prog->shadow.push_back(sh);
+                ProgItem pi;
+                uint64_t a, b, c;
+                prog_script(s, g, pi, &a, &b, &c);
+                pi.work_off = work;
+                pi.item     = uint32_t(i);
+                std::vector<uint8_t> prefix;
+                write_prefix(s, prefix);
+                if (prefix.size() > sizeof pi.prefix) return JPEGGPU_INTERNAL_ERROR;
+                pi.prefix_len = uint32_t(prefix.size());
+                std::memcpy(pi.prefix, prefix.data(), prefix.size());
+                prog->items.push_back(pi);
+            }
         }
         tile += uint32_t((g.blocks + kTileBlocks - 1) / kTileBlocks);
+        if (progressive) {
+            prog_tile += uint32_t((g.scan_blocks + kTileBlocks - 1) / kTileBlocks);
+            prog_chunk += uint32_t(chunks_i);
+            continue;
+        }
         chunk += uint32_t(chunks_i);
     }
     if (out_items) {
@@ -306,6 +430,13 @@ jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan
         s             = Item{};
         s.tile_start  = tile;
         s.chunk_start = chunk;
+        if (prog && plan.prog.n) {
+            s.tile_start  = prog_tile;
+            s.chunk_start = prog_chunk;
+            prog->shadow.push_back(s);
+            s.tile_start  = tile;
+            s.chunk_start = chunk;
+        }
     }
     plan.total = off;
     return JPEGGPU_SUCCESS;
@@ -346,6 +477,11 @@ enum jpeggpu_status jpeggpu_ext_encode_header(const struct jpeggpu_ext_encode_it
     }
     const size_t room = *size;
     *size             = header.size();
+    if (item->progressive) { // every scan brings its tables: SOI .. SOF2 and what the scans' marker segments can take at most
+        write_prefix(*item, header);
+        *size = header.size() + size_t(geometry(*item).marker_bytes);
+        return JPEGGPU_NOT_SUPPORTED;
+    }
     if (item->optimize) return JPEGGPU_NOT_SUPPORTED; // its DHTs depend on the pixels; no header is longer than this one
     if (!host_buf) return JPEGGPU_SUCCESS;
     if (room < header.size()) return JPEGGPU_INVALID_ARGUMENT;
@@ -360,16 +496,16 @@ size_t jpeggpu_ext_encode_bound(const struct jpeggpu_ext_encode_item* item)
     const Geometry g = geometry(*item);
     size_t header    = 0;
     const jpeggpu_status st = jpeggpu_ext_encode_header(item, nullptr, &header);
-    if (st != JPEGGPU_SUCCESS && !(item->optimize && st == JPEGGPU_NOT_SUPPORTED)) return 0;
-    // the header; the stream with every byte 0xFF and stuffed; a marker between segments; EOI
-    return header + 2 * size_t(g.stream_bound) + 2 * size_t(g.segments - 1) + 2;
+    if (st != JPEGGPU_SUCCESS && !((item->optimize || item->progressive) && st == JPEGGPU_NOT_SUPPORTED)) return 0;
+    // the header; the stream with every byte 0xFF and stuffed; a marker between segments (of every scan); EOI
+    return header + 2 * size_t(g.stream_bound) + 2 * size_t(item->progressive ? g.markers : g.segments - 1) + 2;
 }
 
 size_t jpeggpu_ext_encode_scratch_size(const struct jpeggpu_ext_encode_item* items, int n)
 {
     Plan plan;
     try {
-        if (make_plan(items, n, plan, nullptr, nullptr) != JPEGGPU_SUCCESS) return 0;
+        if (make_plan(items, n, plan, nullptr, nullptr, nullptr) != JPEGGPU_SUCCESS) return 0;
     } catch (const std::bad_alloc&) {
         return 0;
     }
@@ -385,8 +521,9 @@ enum jpeggpu_status jpeggpu_ext_encode_batch(
     Plan plan;
     std::vector<Item> dev;
     std::vector<std::vector<uint8_t>> headers;
+    ProgBlob prog;
     try {
-        const jpeggpu_status st = make_plan(items, n, plan, &dev, &headers);
+        const jpeggpu_status st = make_plan(items, n, plan, &dev, &headers, &prog);
         if (st != JPEGGPU_SUCCESS) return st;
     } catch (const std::bad_alloc&) {
         return JPEGGPU_OUT_OF_HOST_MEMORY;
@@ -406,6 +543,10 @@ enum jpeggpu_status jpeggpu_ext_encode_batch(
     std::memcpy(h + plan.tables_off, &tables(), sizeof(Tables));
     std::memcpy(h + plan.items_off, dev.data(), sizeof(Item) * dev.size());
     for (int i = 0; i < n; ++i) std::memcpy(h + dev[i].header_off, headers[i].data(), headers[i].size());
+    if (plan.prog.n) {
+        std::memcpy(h + plan.prog.shadow_off, prog.shadow.data(), sizeof(Item) * prog.shadow.size());
+        std::memcpy(h + plan.prog.items_off, prog.items.data(), sizeof(ProgItem) * prog.items.size());
+    }
     if (!rs.copied[r] && hipEventCreateWithFlags(&rs.copied[r], hipEventDisableTiming) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
     if (hipMemcpyAsync(base, h, plan.blob_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
     if (hipEventRecord(rs.copied[r], stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;

@@ -24,8 +24,13 @@
 //
 // Every later stage reads an item's tables through the item (tables_of), so the two kinds of item mix in one call.
 //
+// A progressive item (Item::header_len == kProgressiveHeader) takes part in launch 1 only: stages 2 and 5 pass over its
+// tiles, and it has no chunks among those of 4 and 6 - 8. Its scans are coded by the ELEVEN launches of jg_encode_prog.hip,
+// enqueued behind 1b, among them build_prog_tables here (build_table on the counts of each scan) and, on the progressive
+// items' own tiles and chunks, launches 3, 4, 6 and 7 as they are. A call without such an item enqueues none of them.
+//
 // No kernel waits for another workgroup: every dependency is a launch boundary.
-#include "jg_encode.hpp"
+#include "jg_encode_prog.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -81,6 +86,8 @@ __device__ inline int item_of_chunk(const Item* items, int n, uint32_t chunk)
 
 /// An item with optimised tables keeps its state where the others keep their header (jg_encode.hpp: Item::header_len).
 __device__ inline bool optimized(const Item& it) { return it.header_len == 0u; }
+/// A progressive item's blocks are transformed here and coded by jg_encode_prog.hip.
+__device__ inline bool progressive(const Item& it) { return it.header_len == kProgressiveHeader; }
 __device__ inline OptState* opt_state(const Item& it, uint8_t* scratch) { return reinterpret_cast<OptState*>(scratch + it.header_off); }
 __device__ inline const OptState* opt_state(const Item& it, const uint8_t* scratch) { return reinterpret_cast<const OptState*>(scratch + it.header_off); }
 /// The tables an item's blocks are coded with: the call's Annex K tables, or the item's own.
@@ -273,6 +280,10 @@ __global__ __launch_bounds__(kTileBlocks) void count_bits(
     __shared__ uint8_t dc_len[2 * 16], ac_len[2 * 256];
     __shared__ Cursor cursors[kTileBlocks];
     const Item& it    = items[item_of_tile(items, n, blockIdx.x)];
+    if (progressive(it)) { // (the tile scan reads every tile's function)
+        if (threadIdx.x == 0) tile_sum[blockIdx.x] = Cursor{kConst, 0u, 0u};
+        return;
+    }
     const int first   = (blockIdx.x - it.tile_start) * kTileBlocks;
     const int b       = first + threadIdx.x;
     const int16_t* gc = reinterpret_cast<const int16_t*>(scratch + it.coef_off);
@@ -348,6 +359,7 @@ __global__ __launch_bounds__(kTileBlocks) void pack_blocks(
     __shared__ uint32_t dc_tab[2 * 16], ac_tab[2 * 256];
     __shared__ Cursor cursors[kTileBlocks];
     const Item& it    = items[item_of_tile(items, n, blockIdx.x)];
+    if (progressive(it)) return;
     const int first   = (blockIdx.x - it.tile_start) * kTileBlocks;
     const int b       = first + threadIdx.x;
     const int16_t* gc = reinterpret_cast<const int16_t*>(scratch + it.coef_off);
@@ -608,6 +620,26 @@ __global__ __launch_bounds__(64) void build_tables(const Item* __restrict__ item
     }
 }
 
+/// One wave per progressive item and table: the table of a scan from the counts prog_symbols made, its codes and its DHT.
+__global__ __launch_bounds__(64) void build_prog_tables(const ProgItem* __restrict__ pitems, uint8_t* __restrict__ scratch)
+{
+    __shared__ TableLds lds;
+    const ProgItem& pi = pitems[blockIdx.x / kProgSlots];
+    const int slot     = blockIdx.x % kProgSlots;
+    if (slot >= int(pi.slots_n)) return;
+    ProgWork* work   = reinterpret_cast<ProgWork*>(scratch + pi.work_off);
+    const int ac     = pi.slot_class_id[slot] >> 4;
+    uint8_t* seg     = work->dht[slot];
+    int n_values     = 0;
+    const int status = build_table(work->counts[slot], ac ? 256 : kDcSymbols, lds, seg + 5, seg + 21, work->codes[slot], &n_values);
+    if (threadIdx.x == 0) {
+        const uint32_t len = 2u + 17u + uint32_t(n_values);
+        seg[0] = 0xFF, seg[1] = 0xC4, seg[2] = uint8_t(len >> 8), seg[3] = uint8_t(len), seg[4] = pi.slot_class_id[slot];
+        work->dht_len[slot] = len + 2u;
+        work->status[slot]  = uint32_t(status);
+    }
+}
+
 __global__ __launch_bounds__(64) void tables_from_counts(const uint32_t* __restrict__ counts, uint8_t* __restrict__ out, int* __restrict__ status)
 {
     __shared__ TableLds lds;
@@ -816,6 +848,13 @@ hipError_t launch_encode(const Plan& plan, uint8_t* d_scratch, unsigned long lon
         count_symbols<<<plan.tiles, kTileBlocks, 0, stream>>>(items, plan.n, d_scratch);
         build_tables<<<uint32_t(plan.n) * 4u, 64, 0, stream>>>(items, plan.n, d_scratch);
     }
+    if (plan.prog.n) { // the progressive items' own launches; the rest of the call follows as it always did
+        hipError_t e = launch_prog_front(plan, d_scratch, stream);
+        if (e == hipSuccess) e = launch_prog_tables(plan, d_scratch, stream);
+        if (e == hipSuccess) e = launch_prog_back(plan, d_scratch, d_sizes, d_status, stream);
+        if (e != hipSuccess) return e;
+        if (plan.chunks == 0u) return hipGetLastError(); // every item is progressive
+    }
     count_bits<<<plan.tiles, kTileBlocks, 0, stream>>>(items, plan.n, tables, d_scratch, bits, tile_sum);
     scan_before<Cursor><<<1, kScanThreads, 0, stream>>>(tile_sum, tile_before, plan.tiles);
     clear_streams<<<chunk_grid, 256, 0, stream>>>(items, plan.n, plan.chunks, d_scratch, tile_sum, tile_before);
@@ -823,6 +862,32 @@ hipError_t launch_encode(const Plan& plan, uint8_t* d_scratch, unsigned long lon
     count_bytes<<<chunk_grid, 256, 0, stream>>>(items, plan.n, plan.chunks, d_scratch, tile_sum, tile_before, counts);
     scan_before<Count><<<1, kScanThreads, 0, stream>>>(counts, count_before, plan.chunks);
     write_files<<<chunk_grid, 256, 0, stream>>>(items, plan.n, plan.chunks, d_scratch, d_scratch, tile_sum, tile_before, counts, count_before, d_sizes, d_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_prog_tables(const Plan& plan, uint8_t* d_scratch, hipStream_t stream)
+{
+    build_prog_tables<<<uint32_t(plan.prog.n) * uint32_t(kProgSlots), 64, 0, stream>>>(reinterpret_cast<const ProgItem*>(d_scratch + plan.prog.items_off), d_scratch);
+    return hipGetLastError();
+}
+
+hipError_t launch_scan_tiles(const Cursor* tile_sum, Cursor* tile_before, uint32_t tiles, hipStream_t stream)
+{
+    scan_before<Cursor><<<1, kScanThreads, 0, stream>>>(tile_sum, tile_before, tiles);
+    return hipGetLastError();
+}
+
+hipError_t launch_clear_streams(const Item* items, int n, uint32_t chunks, uint8_t* d_scratch, const Cursor* tile_sum, const Cursor* tile_before, hipStream_t stream)
+{
+    clear_streams<<<chunks < 4096u ? chunks : 4096u, 256, 0, stream>>>(items, n, chunks, d_scratch, tile_sum, tile_before);
+    return hipGetLastError();
+}
+
+hipError_t launch_count_bytes(const Item* items, int n, uint32_t chunks, const uint8_t* d_scratch, const Cursor* tile_sum, const Cursor* tile_before, Count* counts,
+                              Count* count_before, hipStream_t stream)
+{
+    count_bytes<<<chunks < 4096u ? chunks : 4096u, 256, 0, stream>>>(items, n, chunks, d_scratch, tile_sum, tile_before, counts);
+    scan_before<Count><<<1, kScanThreads, 0, stream>>>(counts, count_before, chunks);
     return hipGetLastError();
 }
 

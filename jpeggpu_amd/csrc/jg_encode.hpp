@@ -1,4 +1,4 @@
-// jg_encode.hpp -- the baseline encoder's tables and launch interface (jg_encode.hip; every launch is asynchronous on
+// jg_encode.hpp -- the encoder's tables and launch interface (jg_encode.hip; progressive items: jg_encode_prog.hpp; every launch is asynchronous on
 // `stream`). The host (jg_encode.cpp) plans a call into one blob of descriptors that travels to the device in one copy; the
 // kernels index everything by BLOCK (8 x 8 samples), the parallel unit of every stage.
 #ifndef JG_ENCODE_HPP_
@@ -93,10 +93,27 @@ struct OptState {
     uint8_t suffix[kSuffixBytes];     // DRI if any, SOS
 };
 
+/// Item::header_len of a progressive item. The baseline stages pass over it: its tiles hold only its coefficients, it has
+/// no chunks among the call's, and jg_encode_prog.hip codes its scans in tiles and chunks of their own (ProgPlan).
+constexpr uint32_t kProgressiveHeader = 0xFFFFFFFFu;
+
+/// The progressive items of a call (jg_encode_prog.hpp): n of them, the tiles of their scan blocks and the chunks of their
+/// streams, counted apart from the call's, and where their arrays sit in d_scratch. All zero without such an item.
+struct ProgPlan {
+    int n;
+    uint32_t tiles, chunks;
+    uint64_t shadow_off, items_off; // in the blob: Item[n + 1] (tile_start, chunk_start and the stream in these spaces), ProgItem[n]
+    uint64_t bits_off;              // uint32[tiles * kTileBlocks]
+    uint64_t facts_off;             // uint8[tiles * kTileBlocks]
+    uint64_t eobn_off;              // uint16[tiles * kTileBlocks]
+    uint64_t tile_sum_off, tile_before_off, count_off, count_before_off; // as the Plan's
+};
+
 /// Where the parts of a call sit in d_scratch (byte offsets; the blob is copied from the host, the rest the device's).
 struct Plan {
     int n;
     int optimized; // items with optimised tables: none, and the call is the eight launches it always was
+    ProgPlan prog;
     uint32_t tiles, chunks;
     uint64_t tables_off, items_off; // in the blob
     uint64_t blob_bytes;

@@ -14,9 +14,13 @@ timed the files of both routes are compared (Pillow: byte for byte).
 `--once WORKLOAD` runs a single device call and nothing else: the process to put under a kernel trace.
 `--optimize` measures optimised Huffman tables instead: encode_jpeg(optimize=True) against Pillow's optimize=True, by the same
 method and with the same bar; each entry also records what the files save against the standard tables.
+`--progressive` measures progressive files: encode_jpeg(progressive=True) against Pillow's progressive=True, and beside them
+the same call with optimize=True ("device_optimize"), the nearest thing the encoder did before; `--no-host` leaves the host
+route out (Pillow needs seconds per call for the photographs). `--flat` times the one call whose end-of-band runs are the
+longest: a flat 1456 x 1456 grey image, progressive.
 Not bench.py: that one measures the flagship workload and stays as it is.
 
-    python tools/encode_rate.py [--optimize] [--rounds 7] [--iters 10] [--out encode_rate.json] [--once photos|resized]
+    python tools/encode_rate.py [--optimize | --progressive [--no-host] | --flat] [--rounds 7] [--iters 10] [--out encode_rate.json] [--once photos|resized]
 """
 import argparse
 import io
@@ -56,14 +60,14 @@ def _host_route(torch, params):
     try:
         from PIL import Image, ImageFile
 
-        optimize = bool(params.get("optimize"))
-        if optimize:  # the whole file leaves libjpeg at once then, and Pillow's default buffer is too small for some files
+        optimize, progressive = bool(params.get("optimize")), bool(params.get("progressive"))
+        if optimize or progressive:  # the whole file leaves libjpeg at once then, and Pillow's default buffer is too small for some files
             ImageFile.MAXBLOCK = max(ImageFile.MAXBLOCK, 1 << 26)
 
         def save(a):
             f = io.BytesIO()
             Image.fromarray(a).save(f, "JPEG", quality=params["quality"], subsampling=PILLOW_SUBSAMPLING[params["subsampling"]],
-                                    restart_marker_blocks=params["restart_interval"], optimize=optimize)
+                                    restart_marker_blocks=params["restart_interval"], optimize=optimize, progressive=progressive)
             return f.getvalue()
 
         def fn(images):
@@ -73,7 +77,7 @@ def _host_route(torch, params):
         return "pillow", fn
     except ImportError:
         pass
-    if params.get("optimize"):  # torchvision's encoder has no such switch: no yardstick
+    if params.get("optimize") or params.get("progressive"):  # torchvision's encoder has no such switch: no yardstick
         return None, None
     try:
         import torchvision.io as tio
@@ -96,7 +100,7 @@ def _wall(torch, fn, iters):
     return (time.perf_counter() - t) * 1000 / iters
 
 
-def run(rounds, iters, optimize=False):
+def run(rounds, iters, optimize=False, progressive=False, host=True):
     import torch
 
     import jpeggpu_amd
@@ -105,13 +109,18 @@ def run(rounds, iters, optimize=False):
     for name in ("photos", "resized"):
         images, params = _workload(torch, name)
         n = len(images)
-        standard_bytes = sum(len(f) for f in jpeggpu_amd.encode_jpeg(images, **params)) if optimize else None
+        standard_bytes = sum(len(f) for f in jpeggpu_amd.encode_jpeg(images, **params)) if optimize or progressive else None
+        plain = dict(params)
         if optimize:
             params["optimize"] = True
+        if progressive:
+            params["progressive"] = True
         device = lambda: jpeggpu_amd.encode_jpeg(images, **params)  # noqa: E731
         files = device()
-        route, host_fn = _host_route(torch, params)
+        route, host_fn = _host_route(torch, params) if host else (None, None)
         variants = {"device": device}
+        if progressive:
+            variants["device_optimize"] = lambda: jpeggpu_amd.encode_jpeg(images, optimize=True, **plain)
         if route:
             theirs = host_fn(images)
             if route == "pillow":
@@ -123,7 +132,7 @@ def run(rounds, iters, optimize=False):
                 res[k].append(_wall(torch, fn, iters))
         r = {k: _spread(v) for k, v in res.items()}
         entry = dict(workload=name, images=n, params=params, file_bytes=sum(len(f) for f in files), ms=r, yardstick=route, rounds=rounds, iters=iters)
-        if optimize:
+        if optimize or progressive:
             entry["standard_file_bytes"] = standard_bytes
             entry["saving"] = round(1 - entry["file_bytes"] / standard_bytes, 4)
         if route:
@@ -136,7 +145,20 @@ def run(rounds, iters, optimize=False):
     return out
 
 
-def once(name, optimize=False):
+def flat(rounds, iters):
+    """The longest walk of prog_runs: 33 124 blocks of one value, four AC scans, each one lane from end to end."""
+    import torch
+
+    import jpeggpu_amd
+
+    x = torch.full((1456, 1456), 128, dtype=torch.uint8, device="cuda:0")
+    files = jpeggpu_amd.encode_jpeg([x], quality=75, subsampling="4:4:4", progressive=True)
+    res = [_wall(torch, lambda: jpeggpu_amd.encode_jpeg([x], quality=75, subsampling="4:4:4", progressive=True), iters) for _ in range(rounds)]
+    opt = [_wall(torch, lambda: jpeggpu_amd.encode_jpeg([x], quality=75, subsampling="4:4:4", optimize=True), iters) for _ in range(rounds)]
+    return [dict(workload="flat_1456_grey", file_bytes=len(files[0]), ms=dict(device=_spread(res), device_optimize=_spread(opt)), rounds=rounds, iters=iters)]
+
+
+def once(name, optimize=False, progressive=False):
     import torch
 
     import jpeggpu_amd
@@ -144,6 +166,8 @@ def once(name, optimize=False):
     images, params = _workload(torch, name)
     if optimize:
         params["optimize"] = True
+    if progressive:
+        params["progressive"] = True
     files = jpeggpu_amd.encode_jpeg(images, **params)
     torch.cuda.synchronize()
     print(json.dumps(dict(workload=name, images=len(files), file_bytes=sum(len(f) for f in files))))
@@ -156,10 +180,13 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", default=None, choices=("photos", "resized"))
     ap.add_argument("--optimize", action="store_true")
+    ap.add_argument("--progressive", action="store_true")
+    ap.add_argument("--no-host", action="store_true")
+    ap.add_argument("--flat", action="store_true")
     a = ap.parse_args()
     if a.once:
-        return once(a.once, a.optimize)
-    res = run(a.rounds, a.iters, a.optimize)
+        return once(a.once, a.optimize, a.progressive)
+    res = flat(a.rounds, a.iters) if a.flat else run(a.rounds, a.iters, a.optimize, a.progressive, not a.no_host)
     for r in res:
         print(json.dumps(r), flush=True)
     if a.out:
