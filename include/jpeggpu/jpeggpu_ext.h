@@ -39,6 +39,8 @@
  *   jpeggpu_ext_encode_batch           the way back: uint8 images on the device to baseline or progressive JPEG files on the
  *                                      device, byte for byte what Pillow's Image.save writes on libjpeg-turbo (optimize=True
  *                                      and progressive=True included)
+ *   jpeggpu_ext_transcode_batch        jpegtran on the GPU: decoded files' quantised coefficients to new files with optimised
+ *                                      tables, as progressive or baseline, with other restart intervals; no IDCT, no loss
  */
 #ifndef JPEGGPU_JPEGGPU_EXT_H_
 #define JPEGGPU_JPEGGPU_EXT_H_
@@ -966,7 +968,8 @@ enum jpeggpu_ext_encode_status {
     JPEGGPU_EXT_ENCODE_OK             = 0,
     JPEGGPU_EXT_ENCODE_TOO_SMALL      = 1,
     JPEGGPU_EXT_ENCODE_TABLE_OVERFLOW = 2, /* an optimised code longer than 32 bits before limiting */
-    JPEGGPU_EXT_ENCODE_EMPTY_TABLE    = 3  /* jpeggpu_ext_encode_tables_from_counts only */
+    JPEGGPU_EXT_ENCODE_EMPTY_TABLE    = 3, /* jpeggpu_ext_encode_tables_from_counts only */
+    JPEGGPU_EXT_ENCODE_UNCODABLE      = 4  /* jpeggpu_ext_transcode_batch only: a coefficient the target cannot code */
 };
 struct jpeggpu_ext_encode_item {
     const uint8_t* data;
@@ -998,6 +1001,59 @@ enum jpeggpu_status jpeggpu_ext_encode_tables_from_counts(
     uint8_t* d_bits_values,
     int* d_status,
     jpeggpu_stream_t stream);
+
+/* Lossless transcoding: a decoded JPEG's quantised coefficients, as the decoder's entropy stage leaves them in d_tmp, to a
+ * new file with the encoder's entropy stages -- what jpegtran -optimize, -progressive and -restart N do: optimised Huffman
+ * tables, a progressive file from a baseline one or the other way round, other restart intervals. No IDCT, no colour
+ * conversion, no FDCT and no quantiser run; the output holds the source's coefficients exactly, so for a source Pillow wrote
+ * the file is, byte for byte, the one Pillow writes with the other options (tests/golden/transcode_pins.npz).
+ *   - An item: `decoder` has parsed the source (jpeggpu_decoder_parse_header), its bytes were transferred into `d_tmp`
+ *     (jpeggpu_decoder_transfer) and jpeggpu_ext_decode_batch has decoded it there ON THE SAME STREAM, with
+ *     jpeggpu_ext_batch_set_coefficients_only or without; d_tmp is read when the call executes. `progressive`, `optimize`, `out`
+ *     and `capacity` as in jpeggpu_ext_encode_item. `restart_interval` in MCUs, 0: none, -1: the source's (the DRI in force at
+ *     its first scan).
+ *   - The file's layout is the encoder's: SOI, a JFIF APP0 without density, DQT 0 and for colour DQT 1 with the SOURCE's tables,
+ *     SOF0 or SOF2, DHTs, DRI, SOS ... Markers are NOT copied: EXIF, ICC and COM segments are dropped, like jpegtran -copy none.
+ *   - Dummy blocks (blocks of an MCU beyond a component's real grid): where a scan of the source codes them -- an interleaved
+ *     scan, a progressive file's interleaved DC scans -- they keep the source's values; where none does (a component coded in
+ *     a scan of its own) they are 64 zeros, as libjpeg's zeroed coefficient arrays leave them.
+ *   - What can be transcoded is what the encoder writes: 8-bit samples; one component (its frame header keeps the sampling
+ *     byte the source names), or three that jpeggpu_ext_get_color_space calls YCbCr with chroma 1x1 and luma 1x1, 2x1 or 2x2,
+ *     8-bit quantisation tables (Pq = 0), Cb and Cr on one table. JPEGGPU_NOT_SUPPORTED, before anything is enqueued, for
+ *     anything else (4:4:0, 4:1:1, RGB-coded, CMYK, YCCK, Pq = 1, Cb and Cr on different tables), for a decoder with a crop, a
+ *     scale other than 1 or a segment shard, and at the encoder's size limits. JPEGGPU_INVALID_ARGUMENT as for
+ *     jpeggpu_ext_encode_batch, for a decoder that has parsed nothing and a restart interval outside -1..65535.
+ *   - jpeggpu_ext_transcode_header (host only): the header of an item without `optimize` and `progressive`, as
+ *     jpeggpu_ext_encode_header; _bound and _scratch_size reuse the encoder's arithmetic per block.
+ *   - jpeggpu_ext_transcode_batch enqueues what jpeggpu_ext_encode_batch enqueues, with a gather kernel in place of the pixel
+ *     stage and one small launch behind the last: NINE launches (ELEVEN: `optimize`, ELEVEN more: `progressive`), one copy of
+ *     descriptors, no synchronisation; a call may mix the three output kinds. d_status[i] as for encoding, and
+ *     JPEGGPU_EXT_ENCODE_UNCODABLE for a source that holds an AC coefficient of category above 10 or a DC difference of
+ *     category above 11 (a crafted file; nothing an 8-bit encoder writes): d_sizes[i] is 0, the slot is not written, the
+ *     other items are not affected.
+ *   - jpeggpu_ext_batch_set_coefficients_only(batch, 1): jpeggpu_ext_decode_batch stops in front of the IDCT stage (a
+ *     transcode never reads the planes); the plane pointers of its items may then be NULL, and a call planned as lone decodes
+ *     takes the batch's kernels. Default 0: the calls launch what they always did. */
+struct jpeggpu_ext_transcode_item {
+    jpeggpu_decoder_t decoder;
+    void* d_tmp;
+    int progressive, optimize;
+    int restart_interval;
+    uint8_t* out;
+    size_t capacity;
+};
+enum jpeggpu_status jpeggpu_ext_transcode_header(const struct jpeggpu_ext_transcode_item* item, uint8_t* host_buf, size_t* size);
+size_t jpeggpu_ext_transcode_bound(const struct jpeggpu_ext_transcode_item* item);
+size_t jpeggpu_ext_transcode_scratch_size(const struct jpeggpu_ext_transcode_item* items, int n);
+enum jpeggpu_status jpeggpu_ext_transcode_batch(
+    const struct jpeggpu_ext_transcode_item* items,
+    int n,
+    void* d_scratch,
+    size_t scratch_size,
+    size_t* d_sizes,
+    int* d_status,
+    jpeggpu_stream_t stream);
+enum jpeggpu_status jpeggpu_ext_batch_set_coefficients_only(jpeggpu_batch_t batch, int enable);
 
 #ifdef __cplusplus
 }

@@ -139,6 +139,12 @@ class EncodeItem(C.Structure):
                 ("restart_interval", C.c_int), ("optimize", C.c_int), ("out", C.c_void_p), ("capacity", C.c_size_t)]
 
 
+class TranscodeItem(C.Structure):
+    """struct jpeggpu_ext_transcode_item"""
+    _fields_ = [("decoder", C.c_void_p), ("d_tmp", C.c_void_p), ("progressive", C.c_int), ("optimize", C.c_int), ("restart_interval", C.c_int),
+                ("out", C.c_void_p), ("capacity", C.c_size_t)]
+
+
 class ExtScanLayout(C.Structure):
     _fields_ = [
         ("num_components", C.c_int), ("component_idx", C.c_int * MAX_COMP),
@@ -302,6 +308,14 @@ def lib():
         L.jpeggpu_ext_encode_scratch_size.argtypes = [C.POINTER(EncodeItem), C.c_int]
         L.jpeggpu_ext_encode_scratch_size.restype = C.c_size_t
         L.jpeggpu_ext_encode_batch.argtypes = [C.POINTER(EncodeItem), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "jpeggpu_ext_transcode_batch"):
+        L.jpeggpu_ext_transcode_header.argtypes = [C.POINTER(TranscodeItem), C.c_void_p, C.POINTER(C.c_size_t)]
+        L.jpeggpu_ext_transcode_bound.argtypes = [C.POINTER(TranscodeItem)]
+        L.jpeggpu_ext_transcode_bound.restype = C.c_size_t
+        L.jpeggpu_ext_transcode_scratch_size.argtypes = [C.POINTER(TranscodeItem), C.c_int]
+        L.jpeggpu_ext_transcode_scratch_size.restype = C.c_size_t
+        L.jpeggpu_ext_transcode_batch.argtypes = [C.POINTER(TranscodeItem), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.jpeggpu_ext_batch_set_coefficients_only.argtypes = [C.c_void_p, C.c_int]
     if hasattr(L, "jpeggpu_ext_encode_tables_from_counts"):
         L.jpeggpu_ext_encode_tables_from_counts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.jpeggpu_ext_resize_weights.argtypes = [
@@ -542,6 +556,11 @@ class Batch:
     def set_sync_run(self, r: int):
         """Consecutive subsequences a lane of the batched sequence kernel owns: 1, 2 or 4 (jpeggpu_ext.h)."""
         _check(_newer_symbol("jpeggpu_ext_batch_set_sync_run")(self._h, int(r)), "jpeggpu_ext_batch_set_sync_run")
+
+    def set_coefficients_only(self, enable: bool):
+        """The calls stop in front of the IDCT stage, and the items' plane pointers may be NULL (jpeggpu_ext.h): what a
+        transcode needs of a decode."""
+        _check(_newer_symbol("jpeggpu_ext_batch_set_coefficients_only")(self._h, 1 if enable else 0), "jpeggpu_ext_batch_set_coefficients_only")
 
     def set_sync_iterations(self, n: int):
         _check(lib().jpeggpu_ext_batch_set_sync_iterations(self._h, n), "jpeggpu_ext_batch_set_sync_iterations")
@@ -983,10 +1002,12 @@ class BatchDecode:
 
     Per file, in order: `decoders`, `planes` (lists of uint8 tensors), `infos`, `crop_infos` (None where no rectangle was
     set), `colors`, `orientations` (the file's own EXIF orientation), `replicates` (where libjpeg replicates instead of
-    fancy upsampling) and `tmps`; `transferred_bytes` is what one round of transfers copies, `batch` the Batch."""
+    fancy upsampling) and `tmps`; `transferred_bytes` is what one round of transfers copies, `batch` the Batch.
+    `coefficients_only`: no planes are allocated (`planes[i]` is empty) and the batch stops in front of the IDCT stage
+    (Batch.set_coefficients_only): the front half of transcode_jpeg."""
 
     def __init__(self, datas, device="cuda:0", hint=None, idct="islow", progressive=True, scales=None, scale_mode="libjpeg", crops=None,
-                 crop_hooks=None):
+                 crop_hooks=None, coefficients_only=False):
         import torch
 
         dev = torch.device(device)
@@ -1018,8 +1039,8 @@ class BatchDecode:
                 nb = dec.get_buffer_size()
                 tmp = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
                 base = _align256(tmp.data_ptr())
-                planes = [torch.empty((info.sizes_y[c], info.sizes_x[c]), dtype=torch.uint8, device=dev)
-                          for c in range(info.num_components)]
+                planes = [] if coefficients_only else [torch.empty((info.sizes_y[c], info.sizes_x[c]), dtype=torch.uint8, device=dev)
+                                                       for c in range(info.num_components)]
                 dec.transfer(base, nb, self._stream)
                 self.tmps.append(tmp)
                 self._entries.append((dec, [p.data_ptr() for p in planes], [p.stride(0) for p in planes], base, nb))
@@ -1030,6 +1051,8 @@ class BatchDecode:
                 self.orientations.append(dec.orientation())
                 self.replicates.append(_needs_replication(info, scale))
             self.batch = Batch(scans)
+            if coefficients_only:
+                self.batch.set_coefficients_only(True)
             self._scratch = torch.empty(self.batch.scratch_size, dtype=torch.uint8, device=dev)
             self.batch.set_items(self._entries)
         except BaseException:
@@ -1510,6 +1533,117 @@ def encode_jpeg(images, quality=75, subsampling="4:2:0", restart_interval=0, lay
     if not sizes:
         return []
     host = torch.cat([buf[o:o + s] for o, s in zip(offsets, sizes)]).cpu().numpy().tobytes()  # only the files' bytes travel
+    out, p = [], 0
+    for s in sizes:
+        out.append(host[p:p + s])
+        p += s
+    return out
+
+
+def _transcode_items(bd, optimize, progressive, restart_interval):
+    """The items of a transcode call for the decoded files of a BatchDecode, without output slots; a source the writer cannot
+    take raises JpegGpuError naming the item."""
+    n = len(bd.decoders)
+    os_, ps_, rs = _per_image(optimize, n, "optimize"), _per_image(progressive, n, "progressive"), _per_image(restart_interval, n, "restart_interval")
+    items = (TranscodeItem * max(n, 1))()
+    bound = _newer_symbol("jpeggpu_ext_transcode_bound")
+    for i, (dec, _, _, base, _) in enumerate(bd._entries):
+        it = items[i]
+        it.decoder, it.d_tmp = dec._h, base
+        it.optimize, it.progressive = int(os_[i]), int(ps_[i])
+        it.restart_interval = -1 if rs[i] is None else int(rs[i])
+        if bound(C.byref(it)) == 0:  # say why: the header call returns the status
+            size = C.c_size_t(0)
+            st = lib().jpeggpu_ext_transcode_header(C.byref(it), None, C.byref(size))
+            raise JpegGpuError(st if st else Status.NOT_SUPPORTED, "jpeggpu_ext_transcode_batch: item %d cannot be transcoded" % i)
+    return items
+
+
+def transcode_into(bd, outs, optimize=False, progressive=False, restart_interval=None, items=None):
+    """jpeggpu_ext_transcode_batch on torch's current stream, without synchronising, for the files of `bd`, a BatchDecode whose
+    decode() was enqueued on the same stream: file i into the slot outs[i], as encode_into. Returns the device tensors
+    (sizes int64[n], status int32[n]); status 1: the slot was too small, 2: as encode_into, 4: the source holds a
+    coefficient that no Huffman code of the target expresses, and its size is 0. `items`: what _transcode_items made of the
+    same arguments, for a caller that has them already."""
+    import torch
+
+    if items is None:
+        items = _transcode_items(bd, optimize, progressive, restart_interval)
+    n = len(bd.decoders)
+    if len(outs) != n:
+        raise ValueError("outs must have one entry per file")
+    if n == 0:
+        raise ValueError("no files")
+    device = bd.tmps[0].device
+    for i, o in enumerate(outs):
+        if o is not None and (o.dtype != torch.uint8 or not o.is_contiguous() or o.device != device):
+            raise ValueError("outs[%d]: a contiguous uint8 tensor on the decode's device is expected" % i)
+        items[i].out = o.data_ptr() if o is not None and o.numel() else None
+        items[i].capacity = o.numel() if o is not None else 0
+    need = lib().jpeggpu_ext_transcode_scratch_size(items, n)
+    if need == 0:
+        raise JpegGpuError(Status.NOT_SUPPORTED, "jpeggpu_ext_transcode_scratch_size")
+    scratch = torch.empty(need, dtype=torch.uint8, device=device)
+    result = torch.empty(12 * n, dtype=torch.uint8, device=device)
+    _check(lib().jpeggpu_ext_transcode_batch(items, n, scratch.data_ptr(), need, result.data_ptr(), result.data_ptr() + 8 * n,
+                                             torch.cuda.current_stream(device).cuda_stream), "jpeggpu_ext_transcode_batch")
+    return result[:8 * n].view(torch.int64), result[8 * n:].view(torch.int32)
+
+
+def transcode_jpeg_to_device(datas, optimize=False, progressive=False, restart_interval=None, device="cuda:0", capacities=None):
+    """transcode_jpeg's files left on the device: (buffer, offsets, sizes) as encode_jpeg_to_device returns them.
+    `capacities`: the slot sizes to start with (default: twice the source's length, a header and three bytes per block for
+    restart markers and their padding); if a file is larger, the call is repeated once with the sizes it reported."""
+    import torch
+
+    datas = list(datas)
+    if not datas:
+        return None, [], []
+    _newer_symbol("jpeggpu_ext_transcode_batch")
+    with BatchDecode(datas, device, coefficients_only=True) as bd:
+        n = len(datas)
+        items = _transcode_items(bd, optimize, progressive, restart_interval)  # (host only: refuses before anything is enqueued or allocated)
+        bd.decode()
+        if capacities is None:
+            caps = [2 * len(d) + 1024 + 3 * ((_frame_size(info)[0] + 7) // 8) * ((_frame_size(info)[1] + 7) // 8) for d, info in zip(datas, bd.infos)]
+        else:
+            caps = [int(c) for c in _per_image(capacities, n, "capacities")]
+        for attempt in range(2):
+            offsets, total = [], 0
+            for c in caps:
+                offsets.append(total)
+                total = (total + c + 15) // 16 * 16
+            buf = torch.empty(max(total, 1), dtype=torch.uint8, device=bd.tmps[0].device)
+            sizes, status = _encode_results(*transcode_into(bd, [buf[o:o + c] for o, c in zip(offsets, caps)], optimize, progressive, restart_interval,
+                                                            items=items))
+            if 1 not in status:
+                break
+            caps = [max(c, s) for c, s in zip(caps, sizes)]
+    for i, st in enumerate(status):
+        if st == 4:
+            raise JpegGpuError(Status.NOT_SUPPORTED, "jpeggpu_ext_transcode_batch: item %d holds a coefficient that no Huffman code of the target expresses" % i)
+        if st == 2:
+            raise JpegGpuError(Status.NOT_SUPPORTED, "jpeggpu_ext_transcode_batch: item %d needs a Huffman code of more than 32 bits (libjpeg refuses it too)" % i)
+        if st:
+            raise JpegGpuError(Status.INVALID_ARGUMENT, "jpeggpu_ext_transcode_batch: item %d needs %d bytes" % (i, sizes[i]))
+    return buf, offsets, sizes
+
+
+def transcode_jpeg(datas, optimize=False, progressive=False, restart_interval=None, device="cuda:0"):
+    """JPEG files from JPEG files without a pixel in between, as a list of bytes: what jpegtran -optimize, -progressive and
+    -restart N do. Each file holds the source's quantised coefficients exactly, in the layout encode_jpeg writes (the
+    source's quantisation tables; EXIF, ICC and comments are dropped). `optimize`, `progressive` as in encode_jpeg;
+    `restart_interval` in MCUs, 0: none, None: the source's; each one value or one per file. For a source Pillow wrote, the
+    result is the file Pillow writes for the same pixels and parameters with those options. Sources: baseline or progressive,
+    grey or YCbCr 4:4:4, 4:2:2 or 4:2:0 with 8-bit quantisation tables; anything else raises JpegGpuError naming the item.
+    One batched decode that stops in front of the IDCT, one jpeggpu_ext_transcode_batch call, one synchronisation and one
+    copy of the files' bytes to the host."""
+    import torch
+
+    buf, offsets, sizes = transcode_jpeg_to_device(datas, optimize, progressive, restart_interval, device)
+    if not sizes:
+        return []
+    host = torch.cat([buf[o:o + s] for o, s in zip(offsets, sizes)]).cpu().numpy().tobytes()
     out, p = [], 0
     for s in sizes:
         out.append(host[p:p + s])

@@ -40,6 +40,9 @@ struct jpeggpu_batch {
     // not under a caller's jpeggpu_ext_batch_set_sync_iterations. Two: every run of `value` above every run with 1 on the
     // same card, +2.5 %; four is slower than one (EXPERIMENTS.md: the fetch pattern costs more than the decodes save).
     int sync_run                = 2;
+    // jpeggpu_ext_batch_set_coefficients_only: the calls stop in front of the IDCT stage (a transcode reads the entropy
+    // stage's output in d_tmp, never the planes) and their items' plane pointers may be NULL.
+    bool coefficients_only      = false;
     // A caller with ONE stream leaves the GPU idle while the latency-bound tail kernel runs (a fifth of a
     // batch's time). With overlap > 1 the jobs are split into that many parts, part 0 on the caller's
     // stream and the others on internal streams forked from and joined back into it with events.
@@ -96,7 +99,7 @@ jpeggpu_status gather_jobs(jpeggpu_batch& b, Call& c)
             group_begin.push_back(static_cast<int>(b.jobs.size()));
         }
         const size_t first_job = b.jobs.size();
-        const jpeggpu_status st = jg::build_jobs(it.decoder->d, it.img, it.d_tmp, it.tmp_size, b.sync_iters, false, c.keep_flows, b.jobs);
+        const jpeggpu_status st = jg::build_jobs(it.decoder->d, it.img, it.d_tmp, it.tmp_size, b.sync_iters, false, c.keep_flows, b.jobs, !b.coefficients_only);
         if (st != JPEGGPU_SUCCESS) return st;
         if (const int dk = jg::device_scan_index(it.decoder->d); dk >= 0) {
             // device-side front end (jpeggpu_ext_set_device_scan): the counts of this job are filled in on the device
@@ -199,11 +202,13 @@ jpeggpu_status run_stages(jpeggpu_batch& b, const Call& c)
 {
     const jg::ScanJob* d_jobs = reinterpret_cast<const jg::ScanJob*>(c.d_scratch);
     for (int stage = 0; stage < jg::kNumStages; ++stage) {
+        const bool skip = stage == jg::kStageIdct && b.coefficients_only; // a coefficients-only call has no IDCT stage, wherever it stands
         if (stage == jg::kStageWrite && !b.progs.empty()) {
             const jpeggpu_status st = run_progressive(b, c);
             if (st != JPEGGPU_SUCCESS) return st;
         }
         for (const jpeggpu_batch::Part& p : b.parts) {
+            if (skip) break; // (the stage's mark below is kept: the timer counts kNumStages + 1 events per call)
             if (jg::launch_stage_batch(static_cast<jg::Stage>(stage), d_jobs + p.begin, p.end - p.begin, p.extent, c.part_stream[p.way]) != hipSuccess) {
                 (void)hipGetLastError();
                 return JPEGGPU_INTERNAL_ERROR;
@@ -234,7 +239,7 @@ jpeggpu_status decode_batch_impl(
     // decode's kernels, multi-hypothesis speculation included -- the chip is empty either way.
     {
         // (with the batch's stage timing on, the call takes the batch's kernels: its events sit between THOSE launches)
-        bool all_lone = num_items <= jg::kLonePlanImages && !batch->timer.enabled();
+        bool all_lone = num_items <= jg::kLonePlanImages && !batch->timer.enabled() && !batch->coefficients_only;
         for (int i = 0; i < num_items && all_lone; ++i) all_lone = !items[i].decoder->d.batched;
         if (all_lone) {
             for (int i = 0; i < num_items; ++i) {
@@ -362,6 +367,13 @@ enum jpeggpu_status jpeggpu_ext_batch_set_sync_iterations(jpeggpu_batch_t batch,
     if (!batch || iterations < 1) return JPEGGPU_INVALID_ARGUMENT; // the first flow iteration supplies n and the DC sums
     batch->sync_iters     = iterations;
     batch->sync_iters_set = true;
+    return JPEGGPU_SUCCESS;
+}
+
+enum jpeggpu_status jpeggpu_ext_batch_set_coefficients_only(jpeggpu_batch_t batch, int enable)
+{
+    if (!batch) return JPEGGPU_INVALID_ARGUMENT;
+    batch->coefficients_only = enable != 0;
     return JPEGGPU_SUCCESS;
 }
 

@@ -164,9 +164,10 @@ struct Decoder {
 /// `lone`: jpeggpu_decoder_decode (multi-hypothesis tables where the plan has them). `keep_flows`: every flow stays in its
 /// sequence's workgroup (huff_sync_intra with re-packed flows; the tail kernel looks at sequence boundaries only) -- lone
 /// decodes and batches too small to fill the chip; else the sequence kernel runs `max_intra_iters` iterations and marks
-/// the rest for the tail kernel.
+/// the rest for the tail kernel. `planes` false: the jobs stop in front of the IDCT stage, and img's planes are not looked at.
 jpeggpu_status build_jobs(
-    Decoder& d, const jpeggpu_img* img, void* d_tmp, size_t tmp_size, int max_intra_iters, bool lone, bool keep_flows, std::vector<ScanJob>& jobs);
+    Decoder& d, const jpeggpu_img* img, void* d_tmp, size_t tmp_size, int max_intra_iters, bool lone, bool keep_flows, std::vector<ScanJob>& jobs,
+    bool planes = true);
 /// Index of the scan of a parsed image that the device walks (its last one), or -1.
 int device_scan_index(const Decoder& d);
 /// Parameters of the device-side front end for the device-walked scan `k` of a parsed image; `d_job` is the device copy

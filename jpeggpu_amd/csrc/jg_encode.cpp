@@ -1,7 +1,9 @@
 // jg_encode.cpp -- the encoder's part of the exported C ABI (include/jpeggpu/jpeggpu_ext.h): argument checks, the file
-// header, the size bound and the plan of a call for the kernels of jg_encode.hip. It knows nothing of the decoder.
+// header, the size bound and the plan of a call for the kernels of jg_encode.hip. It knows nothing of the decoder: of a
+// transcode item it sees the TranscodeSpec that jg_transcode.cpp made of it (jg_transcode.hpp).
 #include "jg_encode_prog.hpp"
 #include "jg_staging.hpp"
+#include "jg_transcode.hpp"
 
 #include <jpeggpu/jpeggpu.h>
 #include <jpeggpu/jpeggpu_ext.h>
@@ -215,7 +217,8 @@ void put_segment(std::vector<uint8_t>& out, int marker, const uint8_t* payload, 
 
 /// The header as libjpeg writes it for Pillow, in the three parts an item with optimised tables needs: SOI .. SOF0 (the
 /// prefix), the DHTs, which for such an item the device writes, and DRI if any and SOS (the suffix).
-void write_prefix(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out)
+/// `spec`: a transcode item's -- the source's quantisation tables and the sampling byte of its first component.
+void write_prefix(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out, const TranscodeSpec* spec = nullptr)
 {
     const int ncomp = it.channels;
     // the factors that were asked for go into the frame header of a grey file too (Pillow sets them whatever the mode); with
@@ -230,13 +233,13 @@ void write_prefix(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out)
         uint8_t q[64], seg[65];
         quant_table(t ? kBaseChroma : kBaseLuma, it.quality, q);
         seg[0] = uint8_t(t);
-        for (int k = 0; k < 64; ++k) seg[1 + k] = q[kNatural[k]];
+        for (int k = 0; k < 64; ++k) seg[1 + k] = spec ? spec->qtable[t][k] : q[kNatural[k]];
         put_segment(out, 0xDB, seg, sizeof seg);
     }
     uint8_t sof[6 + 9] = {8, uint8_t(it.height >> 8), uint8_t(it.height), uint8_t(it.width >> 8), uint8_t(it.width), uint8_t(ncomp)};
     for (int c = 0; c < ncomp; ++c) {
         sof[6 + 3 * c] = uint8_t(c + 1);
-        sof[7 + 3 * c] = uint8_t(c == 0 ? hs << 4 | vs : 0x11);
+        sof[7 + 3 * c] = uint8_t(c ? 0x11 : spec ? spec->sampling0 : hs << 4 | vs);
         sof[8 + 3 * c] = uint8_t(c == 0 ? 0 : 1);
     }
     put_segment(out, it.progressive ? 0xC2 : 0xC0, sof, size_t(6 + 3 * ncomp));
@@ -274,9 +277,9 @@ void write_suffix(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out)
 
 /// SOI .. the end of SOS with the Annex K tables: the header of an item without optimised tables, and the longest an
 /// optimised one can get (its DHTs list at most the symbols these list: 12 categories, 162 AC symbols).
-void write_header(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out)
+void write_header(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out, const TranscodeSpec* spec = nullptr)
 {
-    write_prefix(it, out);
+    write_prefix(it, out, spec);
     write_standard_dhts(it, out);
     write_suffix(it, out);
 }
@@ -290,8 +293,9 @@ struct ProgBlob {
     std::vector<ProgItem> items;
 };
 
+/// `specs`: the call is a transcode call and items[i] is specs[i].item.
 jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan, std::vector<Item>* out_items, std::vector<std::vector<uint8_t>>* headers,
-                         ProgBlob* prog)
+                         ProgBlob* prog, const TranscodeSpec* specs = nullptr)
 {
     if (!items || n <= 0 || n > 65535) return JPEGGPU_INVALID_ARGUMENT;
     uint64_t tiles = 0, chunks = 0, header_bytes = 0, prog_tiles = 0, prog_chunks = 0;
@@ -318,7 +322,7 @@ jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan
             header.assign(sizeof(OptState), 0);
             if (headers) {
                 OptState st{}; // (counts, lengths and statuses zero: the device adds to them)
-                write_prefix(items[i], part);
+                write_prefix(items[i], part, specs ? specs + i : nullptr);
                 if (part.size() > sizeof st.prefix) return JPEGGPU_INTERNAL_ERROR;
                 st.prefix_len = uint32_t(part.size());
                 std::memcpy(st.prefix, part.data(), part.size());
@@ -330,7 +334,7 @@ jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan
                 std::memcpy(header.data(), &st, sizeof st);
             }
         } else {
-            write_header(items[i], header);
+            write_header(items[i], header, specs ? specs + i : nullptr);
         }
         header_bytes += align_up(header.size(), 16);
         if (headers) headers->push_back(header);
@@ -355,6 +359,7 @@ jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan
     plan.prog.chunks      = uint32_t(prog_chunks);
     plan.prog.shadow_off  = take(np ? sizeof(Item) * (np + 1) : 0);
     plan.prog.items_off   = take(sizeof(ProgItem) * np);
+    plan.gather_off       = take(specs ? sizeof(GatherSrc) * size_t(n) : 0);
     plan.blob_bytes       = off;
     plan.bits_off         = take(tiles * kTileBlocks * sizeof(uint32_t));
     plan.tile_sum_off     = take(tiles * sizeof(Cursor));
@@ -410,7 +415,7 @@ jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan
                 pi.work_off = work;
                 pi.item     = uint32_t(i);
                 std::vector<uint8_t> prefix;
-                write_prefix(s, prefix);
+                write_prefix(s, prefix, specs ? specs + i : nullptr);
                 if (prefix.size() > sizeof pi.prefix) return JPEGGPU_INTERNAL_ERROR;
                 pi.prefix_len = uint32_t(prefix.size());
                 std::memcpy(pi.prefix, prefix.data(), prefix.size());
@@ -466,19 +471,19 @@ using namespace jg::enc;
 
 extern "C" {
 
-enum jpeggpu_status jpeggpu_ext_encode_header(const struct jpeggpu_ext_encode_item* item, uint8_t* host_buf, size_t* size)
+static jpeggpu_status header_of(const jpeggpu_ext_encode_item* item, const TranscodeSpec* spec, uint8_t* host_buf, size_t* size)
 {
     if (!valid(item) || !size) return JPEGGPU_INVALID_ARGUMENT;
     std::vector<uint8_t> header;
     try {
-        write_header(*item, header);
+        write_header(*item, header, spec);
     } catch (const std::bad_alloc&) {
         return JPEGGPU_OUT_OF_HOST_MEMORY;
     }
     const size_t room = *size;
     *size             = header.size();
     if (item->progressive) { // every scan brings its tables: SOI .. SOF2 and what the scans' marker segments can take at most
-        write_prefix(*item, header);
+        write_prefix(*item, header, spec);
         *size = header.size() + size_t(geometry(*item).marker_bytes);
         return JPEGGPU_NOT_SUPPORTED;
     }
@@ -487,6 +492,11 @@ enum jpeggpu_status jpeggpu_ext_encode_header(const struct jpeggpu_ext_encode_it
     if (room < header.size()) return JPEGGPU_INVALID_ARGUMENT;
     std::memcpy(host_buf, header.data(), header.size());
     return JPEGGPU_SUCCESS;
+}
+
+enum jpeggpu_status jpeggpu_ext_encode_header(const struct jpeggpu_ext_encode_item* item, uint8_t* host_buf, size_t* size)
+{
+    return header_of(item, nullptr, host_buf, size);
 }
 
 size_t jpeggpu_ext_encode_bound(const struct jpeggpu_ext_encode_item* item)
@@ -512,18 +522,19 @@ size_t jpeggpu_ext_encode_scratch_size(const struct jpeggpu_ext_encode_item* ite
     return size_t(plan.total) + 256; // room to align the caller's pointer
 }
 
-enum jpeggpu_status jpeggpu_ext_encode_batch(
-    const struct jpeggpu_ext_encode_item* items, int n, void* d_scratch, size_t scratch_size, size_t* d_sizes, int* d_status, jpeggpu_stream_t stream)
+/// jpeggpu_ext_encode_batch, and with `specs` (items[i] is specs[i].item) jpeggpu_ext_transcode_batch.
+static jpeggpu_status batch_of(const jpeggpu_ext_encode_item* items, const TranscodeSpec* specs, int n, void* d_scratch, size_t scratch_size, size_t* d_sizes,
+                               int* d_status, jpeggpu_stream_t stream)
 {
     if (!items || n <= 0 || !d_scratch || !d_sizes || !d_status) return JPEGGPU_INVALID_ARGUMENT;
     for (int i = 0; i < n; ++i)
-        if (!valid(&items[i]) || !items[i].data || (!items[i].out && items[i].capacity)) return JPEGGPU_INVALID_ARGUMENT;
+        if (!valid(&items[i]) || (!specs && !items[i].data) || (!items[i].out && items[i].capacity)) return JPEGGPU_INVALID_ARGUMENT;
     Plan plan;
     std::vector<Item> dev;
     std::vector<std::vector<uint8_t>> headers;
     ProgBlob prog;
     try {
-        const jpeggpu_status st = make_plan(items, n, plan, &dev, &headers, &prog);
+        const jpeggpu_status st = make_plan(items, n, plan, &dev, &headers, &prog, specs);
         if (st != JPEGGPU_SUCCESS) return st;
     } catch (const std::bad_alloc&) {
         return JPEGGPU_OUT_OF_HOST_MEMORY;
@@ -541,6 +552,15 @@ enum jpeggpu_status jpeggpu_ext_encode_batch(
     uint8_t* h = rs.buf[r].ptr;
     std::memset(h, 0, plan.blob_bytes);
     std::memcpy(h + plan.tables_off, &tables(), sizeof(Tables));
+    if (specs) { // each item's source behind the items, and where its capacity is kept a second time
+        GatherSrc* srcs = reinterpret_cast<GatherSrc*>(h + plan.gather_off);
+        for (int i = 0, k = 0; i < n; ++i) {
+            srcs[i]            = specs[i].src;
+            srcs[i].uncodable  = 0u;
+            srcs[i].shadow_off = items[i].progressive ? uint32_t(plan.prog.shadow_off + sizeof(Item) * size_t(k++)) : 0u;
+            dev[i].src         = base + plan.gather_off + sizeof(GatherSrc) * size_t(i);
+        }
+    }
     std::memcpy(h + plan.items_off, dev.data(), sizeof(Item) * dev.size());
     for (int i = 0; i < n; ++i) std::memcpy(h + dev[i].header_off, headers[i].data(), headers[i].size());
     if (plan.prog.n) {
@@ -552,8 +572,73 @@ enum jpeggpu_status jpeggpu_ext_encode_batch(
     if (hipEventRecord(rs.copied[r], stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
     rs.in_use[r] = true;
     rs.next      = (r + 1) % Staging::kRing;
-    if (launch_encode(plan, base, reinterpret_cast<unsigned long long*>(d_sizes), d_status, stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
+    if (launch_encode(plan, base, reinterpret_cast<unsigned long long*>(d_sizes), d_status, stream, specs != nullptr) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
     return JPEGGPU_SUCCESS;
+}
+
+enum jpeggpu_status jpeggpu_ext_encode_batch(
+    const struct jpeggpu_ext_encode_item* items, int n, void* d_scratch, size_t scratch_size, size_t* d_sizes, int* d_status, jpeggpu_stream_t stream)
+{
+    return batch_of(items, nullptr, n, d_scratch, scratch_size, d_sizes, d_status, stream);
+}
+
+/// The specs of a transcode call and their encoder items side by side.
+static jpeggpu_status specs_of(const jpeggpu_ext_transcode_item* items, int n, bool need_device, std::vector<TranscodeSpec>& specs,
+                               std::vector<jpeggpu_ext_encode_item>& enc)
+{
+    if (!items || n <= 0 || n > 65535) return JPEGGPU_INVALID_ARGUMENT;
+    specs.resize(size_t(n));
+    enc.resize(size_t(n));
+    for (int i = 0; i < n; ++i) {
+        const jpeggpu_status st = transcode_spec(items[i], need_device, specs[size_t(i)]);
+        if (st != JPEGGPU_SUCCESS) return st;
+        enc[size_t(i)] = specs[size_t(i)].item;
+    }
+    return JPEGGPU_SUCCESS;
+}
+
+enum jpeggpu_status jpeggpu_ext_transcode_header(const struct jpeggpu_ext_transcode_item* item, uint8_t* host_buf, size_t* size)
+{
+    if (!item || !size) return JPEGGPU_INVALID_ARGUMENT;
+    TranscodeSpec spec;
+    const jpeggpu_status st = transcode_spec(*item, false, spec);
+    return st != JPEGGPU_SUCCESS ? st : header_of(&spec.item, &spec, host_buf, size);
+}
+
+size_t jpeggpu_ext_transcode_bound(const struct jpeggpu_ext_transcode_item* item)
+{
+    TranscodeSpec spec;
+    if (!item || transcode_spec(*item, false, spec) != JPEGGPU_SUCCESS) return 0;
+    return jpeggpu_ext_encode_bound(&spec.item); // (the header's length does not depend on what its tables hold)
+}
+
+size_t jpeggpu_ext_transcode_scratch_size(const struct jpeggpu_ext_transcode_item* items, int n)
+{
+    Plan plan;
+    try {
+        std::vector<TranscodeSpec> specs;
+        std::vector<jpeggpu_ext_encode_item> enc;
+        if (specs_of(items, n, false, specs, enc) != JPEGGPU_SUCCESS) return 0;
+        if (make_plan(enc.data(), n, plan, nullptr, nullptr, nullptr, specs.data()) != JPEGGPU_SUCCESS) return 0;
+    } catch (const std::bad_alloc&) {
+        return 0;
+    }
+    return size_t(plan.total) + 256;
+}
+
+enum jpeggpu_status jpeggpu_ext_transcode_batch(
+    const struct jpeggpu_ext_transcode_item* items, int n, void* d_scratch, size_t scratch_size, size_t* d_sizes, int* d_status, jpeggpu_stream_t stream)
+{
+    if (!d_scratch || !d_sizes || !d_status) return JPEGGPU_INVALID_ARGUMENT;
+    try {
+        std::vector<TranscodeSpec> specs;
+        std::vector<jpeggpu_ext_encode_item> enc;
+        const jpeggpu_status st = specs_of(items, n, true, specs, enc);
+        if (st != JPEGGPU_SUCCESS) return st;
+        return batch_of(enc.data(), specs.data(), n, d_scratch, scratch_size, d_sizes, d_status, stream);
+    } catch (const std::bad_alloc&) {
+        return JPEGGPU_OUT_OF_HOST_MEMORY;
+    }
 }
 
 enum jpeggpu_status jpeggpu_ext_encode_tables_from_counts(const uint32_t* d_counts, int n_tables, uint8_t* d_bits_values, int* d_status, jpeggpu_stream_t stream)

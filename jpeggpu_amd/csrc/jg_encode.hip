@@ -29,8 +29,14 @@
 // enqueued behind 1b, among them build_prog_tables here (build_table on the counts of each scan) and, on the progressive
 // items' own tiles and chunks, launches 3, 4, 6 and 7 as they are. A call without such an item enqueues none of them.
 //
+// A transcode call (jpeggpu_ext_transcode_batch; jg_transcode.hpp) is the same sequence with gather_blocks in place of launch 1
+// -- the items' coefficients come from the decoder's entropy stage, not from pixels -- and finish_transcode behind the last
+// launch, which reports the items whose source holds a coefficient the target cannot code.
+//
 // No kernel waits for another workgroup: every dependency is a launch boundary.
 #include "jg_encode_prog.hpp"
+#include "jg_huff_core.h"
+#include "jg_transcode.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -257,6 +263,9 @@ __device__ inline BlockPlace place_of(const Item& it, int b)
 }
 
 __device__ inline int category(int v) { return 32 - __clz(abs(v)); } // abs(v) < 2^31: __clz(0) is 32
+/// The category of a DC difference, held to what the tables and the bound of a block's bits cover. Pixels never reach the
+/// limit; a transcode item's source can, and then the item is uncodable and its file is never written (gather_blocks).
+__device__ inline int dc_category(int diff) { return min(category(diff), 11); }
 
 /// Inclusive scan of the workgroup's cursors in LDS (Hillis-Steele: kTileBlocks lanes, 8 steps); returns the lane's value.
 __device__ inline Cursor scan_cursors(Cursor* lds, Cursor mine)
@@ -297,7 +306,7 @@ __global__ __launch_bounds__(kTileBlocks) void count_bits(
         const BlockPlace p = place_of(it, b);
         const int16_t* c   = reinterpret_cast<const int16_t*>(coefs + threadIdx.x * kLdsRow);
         const int diff     = c[0] - (p.pred_block >= 0 ? gc[size_t(p.pred_block) * 64] : 0);
-        int s              = category(diff);
+        int s              = dc_category(diff);
         uint32_t total     = dc_len[p.table * 16 + s] + s;
         int run            = 0;
         for (int k = 1; k < 64; ++k) {
@@ -388,7 +397,7 @@ __global__ __launch_bounds__(kTileBlocks) void pack_blocks(
     const int16_t* c = reinterpret_cast<const int16_t*>(coefs + threadIdx.x * kLdsRow);
     {
         const int diff = c[0] - (p.pred_block >= 0 ? gc[size_t(p.pred_block) * 64] : 0);
-        const int s    = category(diff);
+        const int s    = dc_category(diff);
         const uint32_t e = dc_tab[p.table * 16 + s];
         bw.put(e >> 8, e & 0xFF);
         if (s) bw.put(uint32_t(diff < 0 ? diff - 1 : diff) & ((1u << s) - 1), s); // a negative v is sent as v - 1 in s bits
@@ -439,7 +448,7 @@ __global__ __launch_bounds__(kTileBlocks) void count_symbols(const Item* __restr
         const int16_t* c   = reinterpret_cast<const int16_t*>(coefs + threadIdx.x * kLdsRow);
         const int diff     = c[0] - (p.pred_block >= 0 ? gc[size_t(p.pred_block) * 64] : 0);
         uint32_t* h        = hist + p.table * kTableCounts;
-        atomicAdd(h + category(diff), 1u);
+        atomicAdd(h + dc_category(diff), 1u);
         h += kDcSymbols;
         int run = 0;
         for (int k = 1; k < 64; ++k) {
@@ -831,9 +840,144 @@ __global__ __launch_bounds__(256) void write_files(
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// 1 of a transcode call: coefficients from the decoder's entropy stage (jg_transcode.hpp) in place of encode_blocks
+// ------------------------------------------------------------------------------------------------
+
+/// Block b of an item's MCU stream as a block of its component's padded grid.
+struct SrcBlock {
+    int comp, bx, by;
+};
+__device__ inline SrcBlock src_block(const Item& it, int b)
+{
+    const int mcu = b / it.blocks_per_mcu, j = b - mcu * it.blocks_per_mcu;
+    const int my = mcu / it.mcus_x, mx = mcu - my * it.mcus_x;
+    const int luma = it.hs * it.vs;
+    if (j >= luma) return SrcBlock{1 + j - luma, mx, my};
+    const int yo = j / it.hs;
+    return SrcBlock{0, mx * it.hs + j - yo * it.hs, my * it.vs + yo};
+}
+
+/// The data unit of a baseline source that holds the block, -1: no scan codes it (a dummy block of a component's own scan).
+__device__ inline int src_unit(const GatherComp& c, int bx, int by)
+{
+    if (!c.interleaved) return bx < c.vis_x && by < c.vis_y ? by * c.vis_x + bx : -1;
+    const int mx = bx / c.h, my = by / c.v;
+    return (my * c.mcus_x + mx) * c.du_per_mcu + c.k0 + (by - my * c.v) * c.h + (bx - mx * c.h);
+}
+
+/// A unit's record with its first entry held inside the buffer, as idct_scaled_kernel holds it (jg_idct.hip): a record
+/// that a corrupt stream never wrote must not lead out of it.
+__device__ inline uint2_t src_record(const GatherComp& c, int unit)
+{
+    uint2_t rec = static_cast<const uint2_t*>(c.du_tab)[unit];
+    rec.x       = uint32_t(rec.x < c.sym_limit ? rec.x : c.sym_limit);
+    return rec;
+}
+
+/// The source's DC coefficient of block b, absolute.
+__device__ inline int src_dc(const Item& it, const GatherSrc& src, int b)
+{
+    const SrcBlock sb   = src_block(it, b);
+    const GatherComp& c = src.comp[sb.comp];
+    if (c.coef) return c.coef[(int64_t(sb.by) * c.blocks_x + sb.bx) * 64];
+    const int unit = src_unit(c, sb.bx, sb.by);
+    return unit < 0 ? 0 : int16_t(c.sym[src_record(c, unit).x]);
+}
+
+/// One lane per block of the target's MCU stream. The lane fills its row of the tile in LDS -- rows kLdsRow dwords apart,
+/// so the lanes of a wave that store the same zigzag index fall on different banks -- from the unit's entries (escapes as
+/// in the IDCT stage) or from the component's coefficient array, transposed to zigzag order; then the workgroup stores the
+/// tile in whole lines. What the target cannot code -- an AC coefficient of category above 10, a DC difference of category
+/// above 11 -- marks the item: its capacity becomes 0, so that no later stage writes its slot, the coefficient is stored
+/// as 0, so that every table index of the later stages stays in range, and finish_transcode reports it.
+/// A baseline source's unit is walked entry by entry, one 2-byte load in flight ahead of the one in hand, up to 127 of them:
+/// what the kernel takes follows the entries per unit. The measured 1.5 ms per 64 photographs is for
+/// photographic units of a dozen entries or two; a source of dense units (every coefficient coded, every one escaped) takes
+/// several times as long per block. GatherSrc::shadow_off is a 32-bit offset: the blob it points into is below 4 GB.
+__global__ __launch_bounds__(kTileBlocks) void gather_blocks(Item* items, int n, uint8_t* scratch) // (the items lie in the scratch)
+{
+    __shared__ uint32_t tile[kTileBlocks * kLdsRow];
+    Item& it       = items[item_of_tile(items, n, blockIdx.x)];
+    GatherSrc& src = *const_cast<GatherSrc*>(reinterpret_cast<const GatherSrc*>(it.src));
+    const int first = (blockIdx.x - it.tile_start) * kTileBlocks;
+    const int b     = first + threadIdx.x;
+    uint32_t* row   = tile + threadIdx.x * kLdsRow;
+    bool bad        = false;
+    if (b < it.blocks) {
+        const SrcBlock sb   = src_block(it, b);
+        const GatherComp& c = src.comp[sb.comp];
+        int dc              = 0;
+        if (c.coef) {
+            constexpr uint8_t nat[64] = JG_ORDER_NATURAL;
+            const uint4* p            = reinterpret_cast<const uint4*>(c.coef + (int64_t(sb.by) * c.blocks_x + sb.bx) * 64);
+            uint32_t w[32];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const uint4 v = p[q];
+                w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
+            }
+            dc = int16_t(w[0]);
+#pragma unroll
+            for (int k = 0; k < 64; k += 2) {
+                int lo = int16_t(w[nat[k] >> 1] >> (16 * (nat[k] & 1))), hi = int16_t(w[nat[k + 1] >> 1] >> (16 * (nat[k + 1] & 1)));
+                if (k && abs(lo) >= 1024) bad = true, lo = 0;
+                if (abs(hi) >= 1024) bad = true, hi = 0;
+                row[k >> 1] = (uint32_t(lo) & 0xFFFFu) | uint32_t(hi) << 16;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 32; ++k) row[k] = 0u;
+            const int unit = src_unit(c, sb.bx, sb.by);
+            if (unit >= 0) {
+                const uint2_t rec  = src_record(c, unit);
+                const uint32_t cnt = rec.y & 0x7Fu;
+                const bool esc     = (rec.y & kUnitHasEscape) != 0;
+                int16_t* r16       = reinterpret_cast<int16_t*>(row);
+                dc                 = int16_t(c.sym[rec.x]);
+                r16[0]             = int16_t(dc);
+                uint32_t e         = cnt > 1u ? c.sym[sym_advance(rec.x, 1u)] : 0u;
+                for (uint32_t i = 1; i < cnt; ++i) {
+                    const bool more     = i + 1 < cnt;
+                    const uint32_t next = more ? c.sym[sym_advance(rec.x, i + 1)] : 0u;
+                    const uint32_t zz   = sym_entry_index(e);
+                    if (zz) { // index 0 behind the DC: the escape of the coefficient in front
+                        int v = esc && more && sym_entry_index(next) == 0 ? sym_entry_value(e, next) : sym_entry_value(e);
+                        if (abs(v) >= 1024) bad = true, v = 0;
+                        r16[zz] = int16_t(v);
+                    }
+                    e = next;
+                }
+            }
+        }
+        const BlockPlace p = place_of(it, b);
+        if (abs(dc - (p.pred_block >= 0 ? src_dc(it, src, p.pred_block) : 0)) >= 2048) bad = true;
+    }
+    if (__syncthreads_or(bad) && threadIdx.x == 0) { // (every workgroup that finds one stores the same values)
+        src.uncodable = 1u;
+        it.capacity   = 0u;
+        if (src.shadow_off) reinterpret_cast<Item*>(scratch + src.shadow_off)->capacity = 0u;
+    }
+    uint4* out     = reinterpret_cast<uint4*>(scratch + it.coef_off) + size_t(first) * 8;
+    const int rows = min(kTileBlocks, it.blocks - first);
+    for (int i = threadIdx.x; i < rows * 8; i += kTileBlocks) {
+        const uint32_t* s = tile + (i >> 3) * kLdsRow + (i & 7) * 4;
+        out[i]            = make_uint4(s[0], s[1], s[2], s[3]);
+    }
+}
+
+/// The status of the items gather_blocks marked, behind every stage that wrote one.
+__global__ __launch_bounds__(256) void finish_transcode(const Item* __restrict__ items, int n, unsigned long long* __restrict__ d_sizes, int* __restrict__ d_status)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || !reinterpret_cast<const GatherSrc*>(items[i].src)->uncodable) return;
+    d_sizes[i]  = 0u;
+    d_status[i] = JPEGGPU_EXT_ENCODE_UNCODABLE;
+}
+
 } // namespace
 
-hipError_t launch_encode(const Plan& plan, uint8_t* d_scratch, unsigned long long* d_sizes, int* d_status, hipStream_t stream)
+hipError_t launch_encode(const Plan& plan, uint8_t* d_scratch, unsigned long long* d_sizes, int* d_status, hipStream_t stream, bool transcode)
 {
     const Item* items     = reinterpret_cast<const Item*>(d_scratch + plan.items_off);
     const Tables* tables  = reinterpret_cast<const Tables*>(d_scratch + plan.tables_off);
@@ -843,7 +987,12 @@ hipError_t launch_encode(const Plan& plan, uint8_t* d_scratch, unsigned long lon
     Count* counts         = reinterpret_cast<Count*>(d_scratch + plan.count_off);
     Count* count_before   = reinterpret_cast<Count*>(d_scratch + plan.count_before_off);
     const uint32_t chunk_grid = plan.chunks < 4096u ? plan.chunks : 4096u;
-    encode_blocks<<<plan.tiles, kTileBlocks, 0, stream>>>(items, plan.n, d_scratch);
+    if (transcode) gather_blocks<<<plan.tiles, kTileBlocks, 0, stream>>>(reinterpret_cast<Item*>(d_scratch + plan.items_off), plan.n, d_scratch);
+    else encode_blocks<<<plan.tiles, kTileBlocks, 0, stream>>>(items, plan.n, d_scratch);
+    const auto finish = [&] { // a transcode call's last launch
+        if (transcode) finish_transcode<<<(uint32_t(plan.n) + 255u) / 256u, 256, 0, stream>>>(items, plan.n, d_sizes, d_status);
+        return hipGetLastError();
+    };
     if (plan.optimized) {
         count_symbols<<<plan.tiles, kTileBlocks, 0, stream>>>(items, plan.n, d_scratch);
         build_tables<<<uint32_t(plan.n) * 4u, 64, 0, stream>>>(items, plan.n, d_scratch);
@@ -853,7 +1002,7 @@ hipError_t launch_encode(const Plan& plan, uint8_t* d_scratch, unsigned long lon
         if (e == hipSuccess) e = launch_prog_tables(plan, d_scratch, stream);
         if (e == hipSuccess) e = launch_prog_back(plan, d_scratch, d_sizes, d_status, stream);
         if (e != hipSuccess) return e;
-        if (plan.chunks == 0u) return hipGetLastError(); // every item is progressive
+        if (plan.chunks == 0u) return finish(); // every item is progressive
     }
     count_bits<<<plan.tiles, kTileBlocks, 0, stream>>>(items, plan.n, tables, d_scratch, bits, tile_sum);
     scan_before<Cursor><<<1, kScanThreads, 0, stream>>>(tile_sum, tile_before, plan.tiles);
@@ -862,7 +1011,7 @@ hipError_t launch_encode(const Plan& plan, uint8_t* d_scratch, unsigned long lon
     count_bytes<<<chunk_grid, 256, 0, stream>>>(items, plan.n, plan.chunks, d_scratch, tile_sum, tile_before, counts);
     scan_before<Count><<<1, kScanThreads, 0, stream>>>(counts, count_before, plan.chunks);
     write_files<<<chunk_grid, 256, 0, stream>>>(items, plan.n, plan.chunks, d_scratch, d_scratch, tile_sum, tile_before, counts, count_before, d_sizes, d_status);
-    return hipGetLastError();
+    return finish();
 }
 
 hipError_t launch_prog_tables(const Plan& plan, uint8_t* d_scratch, hipStream_t stream)

@@ -116,6 +116,7 @@ struct Plan {
     ProgPlan prog;
     uint32_t tiles, chunks;
     uint64_t tables_off, items_off; // in the blob
+    uint64_t gather_off;            // in the blob: GatherSrc[n] of a transcode call (jg_transcode.hpp), nothing otherwise
     uint64_t blob_bytes;
     uint64_t bits_off;        // uint32[tiles * kTileBlocks]
     uint64_t tile_sum_off;    // Cursor[tiles]: each tile's own function
@@ -125,7 +126,9 @@ struct Plan {
     uint64_t total;
 };
 
-hipError_t launch_encode(const Plan& plan, uint8_t* d_scratch, unsigned long long* d_sizes, int* d_status, hipStream_t stream);
+/// `transcode`: every item's Item::src is its GatherSrc (jg_transcode.hpp); gather_blocks takes the place of encode_blocks and
+/// finish_transcode follows the last launch.
+hipError_t launch_encode(const Plan& plan, uint8_t* d_scratch, unsigned long long* d_sizes, int* d_status, hipStream_t stream, bool transcode = false);
 
 /// jpeg_gen_optimal_table of n_tables x 256 counts: per table 16 `bits` bytes and 256 `values` bytes, and a status.
 hipError_t launch_tables_from_counts(const uint32_t* d_counts, int n_tables, uint8_t* d_bits_values, int* d_status, hipStream_t stream);

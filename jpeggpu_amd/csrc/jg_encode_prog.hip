@@ -229,7 +229,7 @@ __device__ inline void code_block(const Where& w, const int16_t* c, int dc, int 
             return;
         }
         const int diff = (dc >> al) - (dc_pred >> al); // arithmetic shifts
-        const int s    = category(diff);
+        const int s    = min(category(diff), 11); // (beyond 11: an uncodable transcode item, whose file is never written; its bits stay inside the bound)
         out.sym(slot + w.table, s);
         if (s) out.raw(uint32_t(diff < 0 ? diff - 1 : diff) & ((1u << s) - 1u), s);
         return;

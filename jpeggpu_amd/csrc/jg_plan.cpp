@@ -369,11 +369,11 @@ void Decoder::fill_blob(uint8_t* dst) const
 }
 
 jpeggpu_status build_jobs(
-    Decoder& d, const jpeggpu_img* img, void* d_tmp, size_t tmp_size, int max_intra_iters, bool lone, bool keep_flows, std::vector<ScanJob>& jobs)
+    Decoder& d, const jpeggpu_img* img, void* d_tmp, size_t tmp_size, int max_intra_iters, bool lone, bool keep_flows, std::vector<ScanJob>& jobs, bool planes)
 {
     if (!d.parsed) return JPEGGPU_INVALID_ARGUMENT;
     const Stream& s = d.reader.s;
-    for (int c = 0; c < s.num_comp; ++c) {
+    for (int c = 0; c < s.num_comp && planes; ++c) {
         if (!img->image[c] || img->pitch[c] < d.plane_x(c)) return JPEGGPU_INVALID_ARGUMENT;
     }
     if (!d_tmp || (reinterpret_cast<uintptr_t>(d_tmp) & 255)) return JPEGGPU_INVALID_ARGUMENT;

@@ -234,6 +234,7 @@ jpeggpu_status Reader::read_sof(const Logger& log)
         Component& comp  = s.comp[c];
         comp.id          = u8();
         const uint8_t sf = u8();
+        comp.sampling    = sf;
         const int hs = sf >> 4, vs = sf & 15;
         if (hs < 1 || hs > 4 || vs < 1 || vs > 4) {
             log.log("\tinvalid sampling factor (%d, %d)\n", hs, vs);
@@ -355,6 +356,7 @@ jpeggpu_status Reader::read_dqt(const Logger& log)
             const uint16_t q = precision ? u16() : u8();
             if (!in_use) s.qtable[id][kNatural[j]] = q;
         }
+        if (!in_use) s.qtable16[id] = precision != 0;
         qt_defined_[id] = true;
         rem -= bytes;
     }
@@ -608,6 +610,7 @@ jpeggpu_status Reader::read_sos(const Logger& log)
         return JPEGGPU_INTERNAL_ERROR;
     const int total_mcus  = scan.mcus_x * scan.mcus_y;
     scan.mcus_per_segment = s.restart_interval ? s.restart_interval : total_mcus;
+    if (s.num_scans == 0) s.first_restart_interval = s.restart_interval;
     scan.num_du           = total_mcus * scan.du_per_mcu;
     scan.begin            = static_cast<size_t>(cur_ - base_);
     if (s.num_scans == 0 && subseq_request_ <= 0) {
@@ -762,6 +765,7 @@ jpeggpu_status Reader::read_sos_progressive(const Logger& log)
     }
     const int total_mcus = ps.mcus_x * ps.mcus_y;
     ps.mcus_per_segment  = s.restart_interval ? s.restart_interval : total_mcus;
+    if (s.prog_scans.empty()) s.first_restart_interval = s.restart_interval;
     ps.begin             = static_cast<size_t>(cur_ - base_);
     if (s.prog_scans.empty()) {
         if (subseq_request_ <= 0) subseq_bytes_ = 64; // (no subsequences: the size only names the kernels of a batch this image is in)

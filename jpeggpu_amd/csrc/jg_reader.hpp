@@ -43,6 +43,7 @@ struct Component {
     uint8_t id;
     uint8_t qidx;
     int hs, vs;         // sampling factors (1x1 forced for single-component frames)
+    uint8_t sampling;   // the frame header's byte, whatever the frame (a transcode writes it back)
     int size_x, size_y; // plane size
 };
 
@@ -121,6 +122,8 @@ struct Stream {
     int num_scans = 0;
     Scan scans[kMaxScans];
     uint16_t qtable[4][64]; // natural order (reference src/defs.hpp:87-89 keeps 8 bits; 16-bit entries are read too)
+    bool qtable16[4]{};     // the table came with 16-bit entries (Pq = 1)
+    int first_restart_interval = 0; // the DRI in force at the first scan's SOS
     // Transferred byte range of the file: [xfer_begin, xfer_end). Buffer offset = file offset - xfer_begin.
     size_t xfer_begin = 0;
     size_t xfer_end   = 0;

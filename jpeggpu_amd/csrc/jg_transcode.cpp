@@ -1,0 +1,88 @@
+// jg_transcode.cpp -- the decoder's side of the lossless transcode (jpeggpu_ext.h): what a parsed and decoded image is to
+// the encoder -- its geometry as an encoder item, its quantisation tables, and where its coefficients lie in d_tmp for the
+// gather kernel (jg_transcode.hpp). Host only; the calls themselves are jg_encode.cpp's.
+#include "jg_transcode.hpp"
+
+#include "jg_decoder.hpp"
+
+namespace jg {
+namespace enc {
+
+jpeggpu_status transcode_spec(const jpeggpu_ext_transcode_item& it, bool need_device, TranscodeSpec& spec)
+{
+    spec = TranscodeSpec{};
+    if (!it.decoder || !it.decoder->d.parsed) return JPEGGPU_INVALID_ARGUMENT;
+    if (it.restart_interval < -1 || it.restart_interval > 65535 || (it.optimize != 0 && it.optimize != 1) || (it.progressive != 0 && it.progressive != 1) ||
+        (!it.out && it.capacity))
+        return JPEGGPU_INVALID_ARGUMENT;
+    if (need_device && (!it.d_tmp || (reinterpret_cast<uintptr_t>(it.d_tmp) & 255))) return JPEGGPU_INVALID_ARGUMENT;
+    const Decoder& d = it.decoder->d;
+    const Stream& s  = d.reader.s;
+    // the coefficients of the whole frame at its own size: no window, no scale, no share of the restart segments
+    if (d.crop.on || d.scale_log2 != 0 || d.shard_world != 1) return JPEGGPU_NOT_SUPPORTED;
+
+    // what the encoder writes: grey, or YCbCr with chroma 1 x 1 and luma 1 x 1, 2 x 1 or 2 x 2 and one chroma table
+    int subsampling = JPEGGPU_EXT_SUBSAMPLING_444;
+    if (s.num_comp == 3) {
+        const Component& y = s.comp[0];
+        if (s.color_space != kColorYCbCr || s.comp[1].hs != 1 || s.comp[1].vs != 1 || s.comp[2].hs != 1 || s.comp[2].vs != 1 || s.comp[1].qidx != s.comp[2].qidx)
+            return JPEGGPU_NOT_SUPPORTED;
+        if (y.hs == 1 && y.vs == 1) subsampling = JPEGGPU_EXT_SUBSAMPLING_444;
+        else if (y.hs == 2 && y.vs == 1) subsampling = JPEGGPU_EXT_SUBSAMPLING_422;
+        else if (y.hs == 2 && y.vs == 2) subsampling = JPEGGPU_EXT_SUBSAMPLING_420;
+        else return JPEGGPU_NOT_SUPPORTED;
+    } else if (s.num_comp != 1) {
+        return JPEGGPU_NOT_SUPPORTED;
+    }
+    constexpr uint8_t nat[64] = JG_ORDER_NATURAL;
+    for (int t = 0; t < (s.num_comp == 1 ? 1 : 2); ++t) {
+        const int id = s.comp[t].qidx;
+        if (s.qtable16[id]) return JPEGGPU_NOT_SUPPORTED; // Pq = 1
+        for (int k = 0; k < 64; ++k) {
+            if (s.qtable[id][nat[k]] > 255) return JPEGGPU_NOT_SUPPORTED;
+            spec.qtable[t][k] = static_cast<uint8_t>(s.qtable[id][nat[k]]);
+        }
+    }
+    spec.sampling0 = s.comp[0].sampling;
+
+    jpeggpu_ext_encode_item& e = spec.item;
+    e.width = s.size_x, e.height = s.size_y, e.channels = s.num_comp;
+    e.progressive = it.progressive, e.optimize = it.optimize;
+    e.quality          = 75; // (unused: the header holds the source's tables)
+    e.subsampling      = subsampling;
+    e.restart_interval = it.restart_interval < 0 ? s.first_restart_interval : it.restart_interval;
+    e.out = it.out, e.capacity = it.capacity;
+
+    uint8_t* tmp = static_cast<uint8_t*>(it.d_tmp);
+    for (int c = 0; c < s.num_comp; ++c) {
+        GatherComp& g = spec.src.comp[c];
+        g.vis_x = (s.comp[c].size_x + 7) / 8, g.vis_y = (s.comp[c].size_y + 7) / 8;
+        if (s.progressive) {
+            g.coef     = reinterpret_cast<const int16_t*>(tmp + d.plan.prog.coef[c]);
+            g.blocks_x = s.prog_blocks_x[c];
+            continue;
+        }
+        bool found = false;
+        for (int i = 0; i < s.num_scans && !found; ++i) {
+            const Scan& sc = s.scans[i];
+            int k0         = 0;
+            for (int a = 0; a < sc.num_comp && !found; ++a) {
+                if (sc.comp[a].comp_idx == c) {
+                    found         = true;
+                    g.sym         = reinterpret_cast<const uint16_t*>(tmp + d.plan.scan[i].sym);
+                    g.du_tab      = tmp + d.plan.scan[i].du_tab;
+                    g.sym_limit   = sym_buffer_entries(d.sym_regions(i), d.sym_region()) - 10 * kSymSectorStride;
+                    g.interleaved = sc.num_comp > 1;
+                    g.du_per_mcu = sc.du_per_mcu, g.k0 = k0, g.h = sc.comp[a].h, g.v = sc.comp[a].v, g.mcus_x = sc.mcus_x;
+                    if (!g.interleaved) g.vis_x = sc.mcus_x, g.vis_y = sc.mcus_y; // the scan's own grid: the component's real blocks
+                }
+                k0 += sc.comp[a].h * sc.comp[a].v;
+            }
+        }
+        if (!found) return JPEGGPU_NOT_SUPPORTED;
+    }
+    return JPEGGPU_SUCCESS;
+}
+
+} // namespace enc
+} // namespace jg

@@ -1,0 +1,59 @@
+// jg_transcode.hpp -- the lossless transcode's hand-over between the two halves of the library: what jg_transcode.cpp reads
+// out of a decoded image (it knows the decoder) and what jg_encode.cpp and the gather kernel of jg_encode.hip need of it
+// (they do not). A transcode item is an encoder Item whose coefficients come from the decoder's entropy stage instead of
+// encode_blocks: everything behind the gather is the encoder as it is.
+#ifndef JG_TRANSCODE_HPP_
+#define JG_TRANSCODE_HPP_
+
+#include <jpeggpu/jpeggpu.h>
+#include <jpeggpu/jpeggpu_ext.h>
+
+#include <cstdint>
+
+namespace jg {
+namespace enc {
+
+/// Where the blocks of one component of the source lie in the decoder's d_tmp.
+///   baseline source     the symbol stream and data-unit table of the scan that codes the component (jg_defs.h): block
+///                       (bx, by) of the component is data unit  mcu * du_per_mcu + k0 + dy * h + dx  of an interleaved scan
+///                       (mcu over the frame's MCU grid, so dummy blocks are units like any other), and unit
+///                       by * vis_x + bx  of a scan of the component alone, which codes the real blocks only
+///   progressive source  the component's coefficient array: int16[64] per block in natural order, raster over the MCU-padded
+///                       grid `blocks_x` wide (jg_prog_core.h); the blocks no scan wrote are the zeros the decode began with
+struct GatherComp {
+    const uint16_t* sym;
+    const void* du_tab;   // uint2_t[]: {first entry, count | flags}
+    uint64_t sym_limit;   // a record's first entry is clamped to this: 127 + 8 entries from there stay inside the buffer
+    const int16_t* coef;  // progressive source (then sym is NULL)
+    int32_t blocks_x;     // progressive source: the array's row length in blocks
+    int32_t interleaved;  // baseline source: the scan holds other components too
+    int32_t du_per_mcu, k0, h, v, mcus_x;
+    int32_t vis_x, vis_y; // the component's real blocks
+};
+
+/// One item's source, in the call's blob behind the items (Item::src points at it, in d_scratch).
+struct GatherSrc {
+    GatherComp comp[3];
+    // a progressive item's shadow Item in d_scratch (its capacity is what prog_write_files tests), else 0. 32 bits of a 64-bit
+    // plan offset: the shadow items lie in the blob, which make_plan keeps below 4 GB (its test for Item::header_off)
+    uint32_t shadow_off;
+    uint32_t uncodable;  // set by the gather: the source holds a coefficient the target cannot code
+};
+
+/// What jg_transcode.cpp says of one item: the encoder's item (geometry, options, slot; `data` and `quality` unused), the
+/// header's tables and sampling byte, the source.
+struct TranscodeSpec {
+    jpeggpu_ext_encode_item item;
+    uint8_t qtable[2][64]; // zigzag order, as a DQT segment holds them: luma, chroma
+    uint8_t sampling0;     // the frame header's sampling-factor byte of component 0
+    GatherSrc src;
+};
+
+/// The spec of a transcode item: JPEGGPU_INVALID_ARGUMENT / JPEGGPU_NOT_SUPPORTED by the rules of jpeggpu_ext.h.
+/// `need_device`: the pointers into d_tmp are wanted (the batch call), not only the geometry.
+__attribute__((visibility("hidden"))) jpeggpu_status transcode_spec(const jpeggpu_ext_transcode_item& it, bool need_device, TranscodeSpec& spec);
+
+} // namespace enc
+} // namespace jg
+
+#endif // JG_TRANSCODE_HPP_
