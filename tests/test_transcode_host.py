@@ -141,6 +141,37 @@ def test_decoders_with_a_window_a_scale_or_a_shard(L):
         assert s.status(L) == Status.SUCCESS
 
 
+def test_large_sources_on_the_host(L):
+    """What tests/test_gpu_transcode_scale.py takes the large sources for: baseline sources whose symbol stream has several
+    tiles of 64 subsequences (jg_defs.h: kSymTileSubseq), whatever the batch hint; bounds that cover the expected files."""
+    files = T.large()
+    for name, tiles in (("photo_twin", 8), ("photo_rst_twin", 2), ("camera", 64)):
+        for hint in (1, 7, 12):
+            with Source(files[name], setup=lambda d: d.set_batch_hint(hint)) as s:
+                lay = s.dec.layout()
+                assert lay.num_scans == 1 and lay.scans[0].num_subsequences > 64 * tiles, (name, hint, lay.scans[0].num_subsequences)
+                assert lay.scans[0].num_data_units == T.blocks_of(s.info.sizes_x[0], s.info.sizes_y[0], "4:2:0")[0]
+    pins = T.large_pins()[0]
+    for source, label, options, expected in T.LARGE_PAIRS:
+        with Source(files[source], **options) as s:
+            assert s.status(L) == (Status.NOT_SUPPORTED if options.get("optimize") or options.get("progressive") else Status.SUCCESS)
+            size = len(files[expected]) if expected is not None else pins["%s/%s" % (source, label)]["size"]
+            assert L.jpeggpu_ext_transcode_bound(C.byref(s.item)) >= size, (source, label)
+
+
+def test_crafted_and_limit_sources_on_the_host(L):
+    """The four-component file is refused here, before anything is enqueued; a source at or past a coding limit is not: what
+    its coefficients are is known on the device only."""
+    crafted = T.crafted_progressive()
+    for name, (prog, _) in crafted.items():
+        with Source(prog) as s:
+            assert s.status(L) == (Status.NOT_SUPPORTED if name == T.CRAFTED_REFUSED else Status.SUCCESS), name
+    for src in T.limit_sources():
+        for r in src["codable"]:
+            with Source(src["data"], restart_interval=r) as s:
+                assert s.status(L) == Status.SUCCESS, src["name"]
+
+
 def test_invalid_arguments(L):
     a = _colour_pin()
     for r in (-2, 65536, 1 << 20):

@@ -7,7 +7,9 @@ reference for sources Pillow cannot write.
     parse(src) -> what the header says: size, components (sampling byte, table), tables, the DRI at the first scan
     coefficients(src) -> the dict; a dummy block keeps the source's values where a scan of the source codes it (an
                          interleaved scan, a progressive file's interleaved DC scans) and is 64 zeros where none does
-    transcode(src, optimize=False, progressive=False, restart_interval=None) -> bytes"""
+    transcode(src, optimize=False, progressive=False, restart_interval=None) -> bytes; Unsupported for what the library
+                         refuses or marks uncodable: an AC coefficient of magnitude 1024 or more, a DC difference -- in the
+                         TARGET's prediction order, per component, from 0 at every `restart_interval` MCUs -- of 2048 or more"""
 import numpy as np
 
 from oracle import oracle
@@ -103,12 +105,31 @@ def coefficients(src, info=None):
                 mcus_x=mx, mcus_y=my, per_mcu=per_mcu, quality=None)
 
 
+def dc_differences(co, restart_interval):
+    """The DC differences a target with that restart interval codes, per block of the MCU stream: each component predicts
+    from its previous block, and from 0 in the first MCU of the file and of every `restart_interval` MCUs."""
+    dc = co["coefs"][:, 0].astype(np.int64)
+    out = np.zeros_like(dc)
+    for c in range(co["ncomp"]):
+        idx = np.flatnonzero(co["comp"] == c)
+        d = dc[idx].copy()
+        d[1:] -= dc[idx[:-1]]
+        if restart_interval:
+            mcu = co["mcu"][idx]
+            opens = (mcu % restart_interval == 0) & np.r_[True, mcu[1:] != mcu[:-1]]  # the component's first block of such an MCU
+            d[opens] = dc[idx][opens]
+        out[idx] = d
+    return out
+
+
 def transcode(src, optimize=False, progressive=False, restart_interval=None):
     info = _checked(src)
     co = coefficients(src, info)
     if np.abs(co["coefs"][:, 1:].astype(np.int64)).max(initial=0) >= 1024:
         raise Unsupported("an AC coefficient of category above 10")
     r = info["restart"] if restart_interval is None else restart_interval
+    if np.abs(dc_differences(co, r)).max(initial=0) >= 2048:  # whatever the target's first DC scan shifts away: jpeggpu_ext.h
+        raise Unsupported("a DC difference of category above 11")
     inverse = np.argsort(E.ZIGZAG)
     tabs = [np.array(info["qtabs"][c["q"]])[inverse] for c in info["comps"][:2]]  # natural order, as quant_table returns them
     saved = E.coefficients, E.quant_table
