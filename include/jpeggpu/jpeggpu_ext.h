@@ -41,6 +41,8 @@
  *                                      and progressive=True included)
  *   jpeggpu_ext_transcode_batch        jpegtran on the GPU: decoded files' quantised coefficients to new files with optimised
  *                                      tables, as progressive or baseline, with other restart intervals; no IDCT, no loss
+ *   jpeggpu_ext_set_transcode_orientation  ... turned, flipped or transposed on the way (jpegtran -rotate / -flip / -transpose),
+ *                                      still without loss: an EXIF orientation baked into the file
  */
 #ifndef JPEGGPU_JPEGGPU_EXT_H_
 #define JPEGGPU_JPEGGPU_EXT_H_
@@ -1033,7 +1035,33 @@ enum jpeggpu_status jpeggpu_ext_encode_tables_from_counts(
  *     other items are not affected.
  *   - jpeggpu_ext_batch_set_coefficients_only(batch, 1): jpeggpu_ext_decode_batch stops in front of the IDCT stage (a
  *     transcode never reads the planes); the plane pointers of its items may then be NULL, and a call planned as lone decodes
- *     takes the batch's kernels. Default 0: the calls launch what they always did. */
+ *     takes the batch's kernels. Default 0: the calls launch what they always did.
+ *   - jpeggpu_ext_set_transcode_orientation(decoder, orientation, trim): jpegtran -flip / -rotate / -transpose / -transverse.
+ *     The new file's STORED image is the displayed image O of the source's stored image S under `orientation`, 1..8 by the
+ *     table at jpeggpu_ext_get_orientation, made in the coefficient domain without loss. Only the four jpeggpu_ext_transcode_
+ *     calls read the setting, when they are called; it may be set any time after the decoder's creation and holds until it
+ *     is set again; decodes to pixels ignore it. An orientation outside 1..8 or a `trim` other than 0 or 1:
+ *     JPEGGPU_INVALID_ARGUMENT. With orientation 1 (the default) every call is what it was, launch for launch and byte for
+ *     byte, dummy blocks included. Otherwise:
+ *       - a real block of the target is the source's block of the same component under the table, taken on the component's
+ *         own block grid; 5..8 transpose each block (natural index 8 v + u takes the source's 8 u + v); a mirrored displayed
+ *         x (2, 3, 6, 7) negates the coefficients of odd horizontal frequency u, a mirrored displayed y (3, 4, 7, 8) those
+ *         of odd v;
+ *       - for 5..8 the size becomes H x W, both quantisation tables are transposed, and the sampling byte of component 0
+ *         has its nibbles exchanged (a grey file's too, where it changes nothing else). 4:2:2 would become 4:4:0, which the
+ *         encoder does not write: JPEGGPU_NOT_SUPPORTED;
+ *       - a mirror is exact over whole iMCUs of the source only (8 hs x 8 vs pixels; 8 x 8 for grey). The stored x is
+ *         mirrored for 2, 3, 7, 8: W must be a multiple of 8 hs. The stored y is mirrored for 3, 4, 6, 7: H must be a
+ *         multiple of 8 vs. Orientation 5 needs neither. Otherwise, with `trim` 0 (jpegtran -perfect):
+ *         JPEGGPU_NOT_SUPPORTED from all four calls, before anything is enqueued; with `trim` 1 (jpegtran -trim) the stored
+ *         image is first cut at its right and / or bottom edge to the largest such multiple, and an axis shorter than one
+ *         iMCU stays JPEGGPU_NOT_SUPPORTED;
+ *       - the dummy blocks of the target (luma blocks of an MCU beyond the target's real grid) are the encoder's: 63 zeros
+ *         and the DC of the real block in front of them in the MCU's order, as jctrans.c regenerates them. The source's own
+ *         dummy blocks are never read;
+ *       - the coding limits are the target's: the DC-difference rule runs in the target's prediction order.
+ *         `restart_interval` -1 keeps the source's NUMBER of MCUs.
+ *     A call with such an item launches another instantiation of the gather kernel; the number of launches is the same. */
 struct jpeggpu_ext_transcode_item {
     jpeggpu_decoder_t decoder;
     void* d_tmp;
@@ -1054,6 +1082,7 @@ enum jpeggpu_status jpeggpu_ext_transcode_batch(
     int* d_status,
     jpeggpu_stream_t stream);
 enum jpeggpu_status jpeggpu_ext_batch_set_coefficients_only(jpeggpu_batch_t batch, int enable);
+enum jpeggpu_status jpeggpu_ext_set_transcode_orientation(jpeggpu_decoder_t decoder, int orientation, int trim);
 
 #ifdef __cplusplus
 }

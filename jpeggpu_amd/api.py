@@ -316,6 +316,8 @@ def lib():
         L.jpeggpu_ext_transcode_scratch_size.restype = C.c_size_t
         L.jpeggpu_ext_transcode_batch.argtypes = [C.POINTER(TranscodeItem), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         L.jpeggpu_ext_batch_set_coefficients_only.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "jpeggpu_ext_set_transcode_orientation"):
+        L.jpeggpu_ext_set_transcode_orientation.argtypes = [dec, C.c_int, C.c_int]
     if hasattr(L, "jpeggpu_ext_encode_tables_from_counts"):
         L.jpeggpu_ext_encode_tables_from_counts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.jpeggpu_ext_resize_weights.argtypes = [
@@ -437,6 +439,12 @@ class Decoder:
         o = C.c_int()
         _check(lib().jpeggpu_ext_get_orientation(self._h, C.byref(o)), "jpeggpu_ext_get_orientation")
         return o.value
+
+    def set_transcode_orientation(self, orientation: int = 1, trim: bool = False):
+        """jpeggpu_ext_set_transcode_orientation: what the transcode calls make of this decoder's files from now on -- the
+        stored image of the new file is the displayed image under `orientation` (1..8); `trim` cuts partial iMCUs at a
+        mirrored edge instead of refusing them. Decodes to pixels ignore it."""
+        _check(_newer_symbol("jpeggpu_ext_set_transcode_orientation")(self._h, int(orientation), int(trim)), "jpeggpu_ext_set_transcode_orientation")
 
     def set_progressive(self, on: bool = True):
         """Read progressive JPEGs (SOF2) from the next parse_header on; off by default, when they are NOT_SUPPORTED
@@ -1540,11 +1548,30 @@ def encode_jpeg(images, quality=75, subsampling="4:2:0", restart_interval=0, lay
     return out
 
 
-def _transcode_items(bd, optimize, progressive, restart_interval):
+def _transcode_orientations(bd, orientation, exif_transpose, trim):
+    """Per file of a BatchDecode: (orientation 1..8, trim) as jpeggpu_ext_set_transcode_orientation takes them."""
+    n = len(bd.decoders)
+    os_, es, ts = _per_image(orientation, n, "orientation"), _per_image(exif_transpose, n, "exif_transpose"), _per_image(trim, n, "trim")
+    out = []
+    for i in range(n):
+        if es[i] and os_[i] is not None:
+            raise ValueError("item %d: orientation and exif_transpose are both given" % i)
+        o = bd.orientations[i] if es[i] else 1 if os_[i] is None else int(os_[i])
+        if not 1 <= o <= 8:
+            raise ValueError("item %d: orientation must be 1..8" % i)
+        out.append((o, bool(ts[i])))
+    return out
+
+
+def _transcode_items(bd, optimize, progressive, restart_interval, orientation=None, exif_transpose=False, trim=False):
     """The items of a transcode call for the decoded files of a BatchDecode, without output slots; a source the writer cannot
-    take raises JpegGpuError naming the item."""
+    take raises JpegGpuError naming the item. Sets each decoder's transcode orientation (Decoder.set_transcode_orientation),
+    which the calls on the items read."""
     n = len(bd.decoders)
     os_, ps_, rs = _per_image(optimize, n, "optimize"), _per_image(progressive, n, "progressive"), _per_image(restart_interval, n, "restart_interval")
+    for dec, (o, t) in zip(bd.decoders, _transcode_orientations(bd, orientation, exif_transpose, trim)):
+        if o != 1 or t or hasattr(lib(), "jpeggpu_ext_set_transcode_orientation"):
+            dec.set_transcode_orientation(o, t)
     items = (TranscodeItem * max(n, 1))()
     bound = _newer_symbol("jpeggpu_ext_transcode_bound")
     for i, (dec, _, _, base, _) in enumerate(bd._entries):
@@ -1559,16 +1586,16 @@ def _transcode_items(bd, optimize, progressive, restart_interval):
     return items
 
 
-def transcode_into(bd, outs, optimize=False, progressive=False, restart_interval=None, items=None):
+def transcode_into(bd, outs, optimize=False, progressive=False, restart_interval=None, items=None, orientation=None, exif_transpose=False, trim=False):
     """jpeggpu_ext_transcode_batch on torch's current stream, without synchronising, for the files of `bd`, a BatchDecode whose
     decode() was enqueued on the same stream: file i into the slot outs[i], as encode_into. Returns the device tensors
     (sizes int64[n], status int32[n]); status 1: the slot was too small, 2: as encode_into, 4: the source holds a
     coefficient that no Huffman code of the target expresses, and its size is 0. `items`: what _transcode_items made of the
-    same arguments, for a caller that has them already."""
+    same arguments, for a caller that has them already. `orientation`, `exif_transpose`, `trim`: as transcode_jpeg's."""
     import torch
 
     if items is None:
-        items = _transcode_items(bd, optimize, progressive, restart_interval)
+        items = _transcode_items(bd, optimize, progressive, restart_interval, orientation, exif_transpose, trim)
     n = len(bd.decoders)
     if len(outs) != n:
         raise ValueError("outs must have one entry per file")
@@ -1590,10 +1617,11 @@ def transcode_into(bd, outs, optimize=False, progressive=False, restart_interval
     return result[:8 * n].view(torch.int64), result[8 * n:].view(torch.int32)
 
 
-def transcode_jpeg_to_device(datas, optimize=False, progressive=False, restart_interval=None, device="cuda:0", capacities=None):
+def transcode_jpeg_to_device(datas, optimize=False, progressive=False, restart_interval=None, device="cuda:0", capacities=None, orientation=None,
+                             exif_transpose=False, trim=False):
     """transcode_jpeg's files left on the device: (buffer, offsets, sizes) as encode_jpeg_to_device returns them.
-    `capacities`: the slot sizes to start with (default: twice the source's length, a header and three bytes per block for
-    restart markers and their padding); if a file is larger, the call is repeated once with the sizes it reported."""
+    `capacities`: the slot sizes to start with (default: twice the source's length, a header and three bytes per block of the
+    TARGET for restart markers and their padding); if a file is larger, the call is repeated once with the sizes it reported."""
     import torch
 
     datas = list(datas)
@@ -1602,10 +1630,11 @@ def transcode_jpeg_to_device(datas, optimize=False, progressive=False, restart_i
     _newer_symbol("jpeggpu_ext_transcode_batch")
     with BatchDecode(datas, device, coefficients_only=True) as bd:
         n = len(datas)
-        items = _transcode_items(bd, optimize, progressive, restart_interval)  # (host only: refuses before anything is enqueued or allocated)
+        # (host only: refuses before anything is enqueued or allocated)
+        items = _transcode_items(bd, optimize, progressive, restart_interval, orientation, exif_transpose, trim)
         bd.decode()
         if capacities is None:
-            caps = [2 * len(d) + 1024 + 3 * ((_frame_size(info)[0] + 7) // 8) * ((_frame_size(info)[1] + 7) // 8) for d, info in zip(datas, bd.infos)]
+            caps = [2 * len(d) + 1024 + 3 * _transcode_blocks(items[i]) for i, d in enumerate(datas)]
         else:
             caps = [int(c) for c in _per_image(capacities, n, "capacities")]
         for attempt in range(2):
@@ -1614,8 +1643,7 @@ def transcode_jpeg_to_device(datas, optimize=False, progressive=False, restart_i
                 offsets.append(total)
                 total = (total + c + 15) // 16 * 16
             buf = torch.empty(max(total, 1), dtype=torch.uint8, device=bd.tmps[0].device)
-            sizes, status = _encode_results(*transcode_into(bd, [buf[o:o + c] for o, c in zip(offsets, caps)], optimize, progressive, restart_interval,
-                                                            items=items))
+            sizes, status = _encode_results(*transcode_into(bd, [buf[o:o + c] for o, c in zip(offsets, caps)], items=items))
             if 1 not in status:
                 break
             caps = [max(c, s) for c, s in zip(caps, sizes)]
@@ -1629,18 +1657,41 @@ def transcode_jpeg_to_device(datas, optimize=False, progressive=False, restart_i
     return buf, offsets, sizes
 
 
-def transcode_jpeg(datas, optimize=False, progressive=False, restart_interval=None, device="cuda:0"):
+def _transcode_blocks(item):
+    """ceil(w / 8) * ceil(h / 8) of the file an item writes, read from the frame header the library gives it."""
+    size = C.c_size_t(1024)
+    head = (C.c_uint8 * 1024)()
+    one = TranscodeItem()
+    C.pointer(one)[0] = item
+    one.optimize = one.progressive = 0
+    _check(lib().jpeggpu_ext_transcode_header(C.byref(one), head, C.byref(size)), "jpeggpu_ext_transcode_header")
+    head = bytes(head[:size.value])
+    at = 2 + 18  # SOI and APP0; then a DQT of 69 bytes per table, then SOF0: marker, length, precision, height, width
+    while head[at:at + 2] == b"\xff\xdb":
+        at += 69
+    assert head[at:at + 2] == b"\xff\xc0"
+    at += 5
+    return ((head[at] << 8 | head[at + 1]) + 7) // 8 * (((head[at + 2] << 8 | head[at + 3]) + 7) // 8)
+
+
+def transcode_jpeg(datas, optimize=False, progressive=False, restart_interval=None, device="cuda:0", orientation=None, exif_transpose=False, trim=False):
     """JPEG files from JPEG files without a pixel in between, as a list of bytes: what jpegtran -optimize, -progressive and
     -restart N do. Each file holds the source's quantised coefficients exactly, in the layout encode_jpeg writes (the
     source's quantisation tables; EXIF, ICC and comments are dropped). `optimize`, `progressive` as in encode_jpeg;
     `restart_interval` in MCUs, 0: none, None: the source's; each one value or one per file. For a source Pillow wrote, the
     result is the file Pillow writes for the same pixels and parameters with those options. Sources: baseline or progressive,
     grey or YCbCr 4:4:4, 4:2:2 or 4:2:0 with 8-bit quantisation tables; anything else raises JpegGpuError naming the item.
+    `orientation` (1..8, one value or one per file, None: 1) turns, flips or transposes the image without loss, like jpegtran
+    -rotate / -flip / -transpose: the new file's stored image is the displayed image of the source under that EXIF
+    orientation number. `exif_transpose` (one value or one per file): each file's own Orientation tag is the number, which
+    bakes the tag into the file (the result holds no Exif segment); naming both for a file is a ValueError. A mirrored edge
+    must be a whole number of iMCUs of the source: otherwise the item raises JpegGpuError before anything is enqueued, or
+    with `trim` the partial iMCUs at that edge are cut off first, like jpegtran -trim. 4:2:2 takes 1..4 only.
     One batched decode that stops in front of the IDCT, one jpeggpu_ext_transcode_batch call, one synchronisation and one
     copy of the files' bytes to the host."""
     import torch
 
-    buf, offsets, sizes = transcode_jpeg_to_device(datas, optimize, progressive, restart_interval, device)
+    buf, offsets, sizes = transcode_jpeg_to_device(datas, optimize, progressive, restart_interval, device, None, orientation, exif_transpose, trim)
     if not sizes:
         return []
     host = torch.cat([buf[o:o + s] for o, s in zip(offsets, sizes)]).cpu().numpy().tobytes()

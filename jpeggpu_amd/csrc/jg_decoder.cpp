@@ -414,6 +414,14 @@ enum jpeggpu_status jpeggpu_ext_set_scale(jpeggpu_decoder_t decoder, int scale_d
     return JPEGGPU_SUCCESS;
 }
 
+enum jpeggpu_status jpeggpu_ext_set_transcode_orientation(jpeggpu_decoder_t decoder, int orientation, int trim)
+{
+    if (!decoder || orientation < 1 || orientation > 8 || (trim != 0 && trim != 1)) return JPEGGPU_INVALID_ARGUMENT;
+    decoder->d.transcode_orientation = orientation;
+    decoder->d.transcode_trim        = trim != 0;
+    return JPEGGPU_SUCCESS;
+}
+
 enum jpeggpu_status jpeggpu_ext_set_scale_mode(jpeggpu_decoder_t decoder, enum jpeggpu_ext_scale_mode mode)
 {
     if (!decoder) return JPEGGPU_INVALID_ARGUMENT;

@@ -141,6 +141,9 @@ struct Decoder {
         int ox[kMaxComp]{}, oy[kMaxComp]{};   // window origin in the component's plane
         int wx[kMaxComp]{}, wy[kMaxComp]{};   // window size
     } crop;
+    // jpeggpu_ext_set_transcode_orientation: read by the jpeggpu_ext_transcode_* calls only (jg_transcode.cpp), when they run
+    int transcode_orientation = 1;
+    bool transcode_trim       = false;
     int plane_x(int c) const { return crop.on ? crop.wx[c] : full_x(c); } // what decode writes
     int plane_y(int c) const { return crop.on ? crop.wy[c] : full_y(c); }
     JG_LOCAL bool set_crop_window();

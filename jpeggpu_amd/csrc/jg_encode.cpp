@@ -303,7 +303,9 @@ jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan
     std::vector<Geometry> geo(static_cast<size_t>(n));
     std::vector<uint8_t> header, part;
     plan.optimized = 0;
+    plan.oriented  = 0;
     for (int i = 0; i < n; ++i) {
+        if (specs && specs[i].src.oriented) ++plan.oriented;
         if (!valid(&items[i])) return JPEGGPU_INVALID_ARGUMENT;
         geo[i] = geometry(items[i]);
         if (geo[i].stream_bound * 8 >= (uint64_t(1) << 32)) return JPEGGPU_NOT_SUPPORTED;

@@ -31,7 +31,8 @@
 //
 // A transcode call (jpeggpu_ext_transcode_batch; jg_transcode.hpp) is the same sequence with gather_blocks in place of launch 1
 // -- the items' coefficients come from the decoder's entropy stage, not from pixels -- and finish_transcode behind the last
-// launch, which reports the items whose source holds a coefficient the target cannot code.
+// launch, which reports the items whose source holds a coefficient the target cannot code. With an item that has an orientation
+// (jpeggpu_ext_set_transcode_orientation) the call launches gather_blocks<true>, which maps blocks and coefficients on the way.
 //
 // No kernel waits for another workgroup: every dependency is a launch boundary.
 #include "jg_encode_prog.hpp"
@@ -845,17 +846,69 @@ __global__ __launch_bounds__(256) void write_files(
 // ------------------------------------------------------------------------------------------------
 
 /// Block b of an item's MCU stream as a block of its component's padded grid.
+/// kOriented, and the item has an orientation (GatherSrc::oriented): the block of the SOURCE's grid that the target's block
+/// is, and `dummy` for a luma block beyond the target's real grid -- then the block is the real one whose DC the encoder
+/// gives it (encode_blocks), and only that DC is the source's. Such an item never reads the source's own dummy blocks.
 struct SrcBlock {
     int comp, bx, by;
+    bool dummy;
 };
-__device__ inline SrcBlock src_block(const Item& it, int b)
+template <bool kOriented>
+__device__ inline SrcBlock src_block(const Item& it, const GatherSrc& src, int b)
 {
     const int mcu = b / it.blocks_per_mcu, j = b - mcu * it.blocks_per_mcu;
     const int my = mcu / it.mcus_x, mx = mcu - my * it.mcus_x;
     const int luma = it.hs * it.vs;
-    if (j >= luma) return SrcBlock{1 + j - luma, mx, my};
-    const int yo = j / it.hs;
-    return SrcBlock{0, mx * it.hs + j - yo * it.hs, my * it.vs + yo};
+    SrcBlock sb{0, mx, my, false};
+    if (j >= luma) {
+        sb.comp = 1 + j - luma;
+    } else {
+        const int yo = j / it.hs;
+        sb.bx = mx * it.hs + j - yo * it.hs, sb.by = my * it.vs + yo;
+    }
+    if (!kOriented || !src.oriented) return sb;
+    if (sb.comp == 0) {
+        if (sb.by >= it.grid_h) {
+            sb.dummy = true;
+            sb.by -= 1;
+            sb.bx = min(mx * it.hs + it.hs - 1, it.grid_w - 1);
+        } else if (sb.bx >= it.grid_w) {
+            sb.dummy = true;
+            sb.bx    = it.grid_w - 1;
+        }
+    }
+    const GatherComp& c = src.comp[sb.comp];
+    const int x = src.mirror_x ? c.dst_x - 1 - sb.bx : sb.bx, y = src.mirror_y ? c.dst_y - 1 - sb.by : sb.by;
+    sb.bx = src.transpose ? y : x, sb.by = src.transpose ? x : y;
+    return sb;
+}
+
+// An orientation in the coefficient domain, by the source's zigzag index: where the entry goes when the block is transposed
+// (natural 8 v + u to 8 u + v), and which entries a mirror of the source's x (odd u) and of its y (odd v) negates.
+__device__ const uint8_t kZigzagTransposed[64] = {0,  2,  1,  5,  4,  3,  9,  8,  7,  6,  14, 13, 12, 11, 10, 20, 19, 18, 17, 16, 15, 27,
+                                                  26, 25, 24, 23, 22, 21, 35, 34, 33, 32, 31, 30, 29, 28, 42, 41, 40, 39, 38, 37, 36, 48,
+                                                  47, 46, 45, 44, 43, 53, 52, 51, 50, 49, 57, 56, 55, 54, 60, 59, 58, 62, 61, 63};
+constexpr uint64_t kZigzagOddU = 0xB56AAD55554AA952ull, kZigzagOddV = 0xD6AB555AA5552A94ull;
+
+/// A progressive source's block `w` (natural order, two coefficients a dword) to the lane's row, in the target's zigzag order:
+/// kTranspose exchanges u and v, neg_u / neg_v negate the source's odd horizontal / vertical frequencies. Every index of `w`
+/// is a constant once the loop is unrolled, so the array stays in registers. True: a coefficient the target cannot code.
+template <bool kTranspose>
+__device__ inline bool oriented_row(const uint32_t (&w)[32], uint32_t* row, bool neg_u, bool neg_v)
+{
+    constexpr uint8_t nat[64] = JG_ORDER_NATURAL;
+    bool bad                  = false;
+#pragma unroll
+    for (int k = 0; k < 64; k += 2) {
+        const int a = kTranspose ? (nat[k] & 7) << 3 | nat[k] >> 3 : nat[k], b = kTranspose ? (nat[k + 1] & 7) << 3 | nat[k + 1] >> 3 : nat[k + 1];
+        int lo = int16_t(w[a >> 1] >> (16 * (a & 1))), hi = int16_t(w[b >> 1] >> (16 * (b & 1)));
+        if (k && abs(lo) >= 1024) bad = true, lo = 0;
+        if (abs(hi) >= 1024) bad = true, hi = 0;
+        if (((a & 1) && neg_u) != ((a & 8) && neg_v)) lo = -lo; // (k == 0: a == 0, the DC keeps its sign)
+        if (((b & 1) && neg_u) != ((b & 8) && neg_v)) hi = -hi;
+        row[k >> 1] = (uint32_t(lo) & 0xFFFFu) | uint32_t(hi) << 16;
+    }
+    return bad;
 }
 
 /// The data unit of a baseline source that holds the block, -1: no scan codes it (a dummy block of a component's own scan).
@@ -876,9 +929,10 @@ __device__ inline uint2_t src_record(const GatherComp& c, int unit)
 }
 
 /// The source's DC coefficient of block b, absolute.
+template <bool kOriented>
 __device__ inline int src_dc(const Item& it, const GatherSrc& src, int b)
 {
-    const SrcBlock sb   = src_block(it, b);
+    const SrcBlock sb   = src_block<kOriented>(it, src, b);
     const GatherComp& c = src.comp[sb.comp];
     if (c.coef) return c.coef[(int64_t(sb.by) * c.blocks_x + sb.bx) * 64];
     const int unit = src_unit(c, sb.bx, sb.by);
@@ -895,6 +949,11 @@ __device__ inline int src_dc(const Item& it, const GatherSrc& src, int b)
 /// what the kernel takes follows the entries per unit. The measured 1.5 ms per 64 photographs is for
 /// photographic units of a dozen entries or two; a source of dense units (every coefficient coded, every one escaped) takes
 /// several times as long per block. GatherSrc::shadow_off is a 32-bit offset: the blob it points into is below 4 GB.
+/// kOriented: the instantiation of a call with an item of orientation 2..8 (jpeggpu_ext_set_transcode_orientation). The lane
+/// reads the source block that src_block names and stores each coefficient at the transposed zigzag index with its mirror's
+/// sign; a dummy block of such an item takes one DC from the source and nothing else. An item of orientation 1 in such a
+/// call goes the same way with an identity mapping and gets the values the other instantiation gives it.
+template <bool kOriented>
 __global__ __launch_bounds__(kTileBlocks) void gather_blocks(Item* items, int n, uint8_t* scratch) // (the items lie in the scratch)
 {
     __shared__ uint32_t tile[kTileBlocks * kLdsRow];
@@ -905,10 +964,18 @@ __global__ __launch_bounds__(kTileBlocks) void gather_blocks(Item* items, int n,
     uint32_t* row   = tile + threadIdx.x * kLdsRow;
     bool bad        = false;
     if (b < it.blocks) {
-        const SrcBlock sb   = src_block(it, b);
+        const SrcBlock sb   = src_block<kOriented>(it, src, b);
         const GatherComp& c = src.comp[sb.comp];
         int dc              = 0;
-        if (c.coef) {
+        // what the orientation does to the SOURCE's frequencies: its stored x is mirrored (odd u change sign), its stored y
+        const bool transpose = kOriented && src.transpose;
+        const bool neg_u = kOriented && (transpose ? src.mirror_y : src.mirror_x), neg_v = kOriented && (transpose ? src.mirror_x : src.mirror_y);
+        if (kOriented && sb.dummy) {
+#pragma unroll
+            for (int k = 0; k < 32; ++k) row[k] = 0u;
+            dc     = src_dc<kOriented>(it, src, b);
+            row[0] = uint32_t(dc) & 0xFFFFu;
+        } else if (c.coef) {
             constexpr uint8_t nat[64] = JG_ORDER_NATURAL;
             const uint4* p            = reinterpret_cast<const uint4*>(c.coef + (int64_t(sb.by) * c.blocks_x + sb.bx) * 64);
             uint32_t w[32];
@@ -918,12 +985,16 @@ __global__ __launch_bounds__(kTileBlocks) void gather_blocks(Item* items, int n,
                 w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
             }
             dc = int16_t(w[0]);
+            if (kOriented) {
+                bad = transpose ? oriented_row<true>(w, row, neg_u, neg_v) : oriented_row<false>(w, row, neg_u, neg_v);
+            } else {
 #pragma unroll
-            for (int k = 0; k < 64; k += 2) {
-                int lo = int16_t(w[nat[k] >> 1] >> (16 * (nat[k] & 1))), hi = int16_t(w[nat[k + 1] >> 1] >> (16 * (nat[k + 1] & 1)));
-                if (k && abs(lo) >= 1024) bad = true, lo = 0;
-                if (abs(hi) >= 1024) bad = true, hi = 0;
-                row[k >> 1] = (uint32_t(lo) & 0xFFFFu) | uint32_t(hi) << 16;
+                for (int k = 0; k < 64; k += 2) {
+                    int lo = int16_t(w[nat[k] >> 1] >> (16 * (nat[k] & 1))), hi = int16_t(w[nat[k + 1] >> 1] >> (16 * (nat[k + 1] & 1)));
+                    if (k && abs(lo) >= 1024) bad = true, lo = 0;
+                    if (abs(hi) >= 1024) bad = true, hi = 0;
+                    row[k >> 1] = (uint32_t(lo) & 0xFFFFu) | uint32_t(hi) << 16;
+                }
             }
         } else {
 #pragma unroll
@@ -934,6 +1005,7 @@ __global__ __launch_bounds__(kTileBlocks) void gather_blocks(Item* items, int n,
                 const uint32_t cnt = rec.y & 0x7Fu;
                 const bool esc     = (rec.y & kUnitHasEscape) != 0;
                 int16_t* r16       = reinterpret_cast<int16_t*>(row);
+                const uint64_t neg = kOriented ? (neg_u ? kZigzagOddU : 0ull) ^ (neg_v ? kZigzagOddV : 0ull) : 0ull;
                 dc                 = int16_t(c.sym[rec.x]);
                 r16[0]             = int16_t(dc);
                 uint32_t e         = cnt > 1u ? c.sym[sym_advance(rec.x, 1u)] : 0u;
@@ -944,14 +1016,15 @@ __global__ __launch_bounds__(kTileBlocks) void gather_blocks(Item* items, int n,
                     if (zz) { // index 0 behind the DC: the escape of the coefficient in front
                         int v = esc && more && sym_entry_index(next) == 0 ? sym_entry_value(e, next) : sym_entry_value(e);
                         if (abs(v) >= 1024) bad = true, v = 0;
-                        r16[zz] = int16_t(v);
+                        if (kOriented) r16[transpose ? kZigzagTransposed[zz] : zz] = int16_t(neg >> zz & 1u ? -v : v);
+                        else r16[zz] = int16_t(v);
                     }
                     e = next;
                 }
             }
         }
         const BlockPlace p = place_of(it, b);
-        if (abs(dc - (p.pred_block >= 0 ? src_dc(it, src, p.pred_block) : 0)) >= 2048) bad = true;
+        if (abs(dc - (p.pred_block >= 0 ? src_dc<kOriented>(it, src, p.pred_block) : 0)) >= 2048) bad = true;
     }
     if (__syncthreads_or(bad) && threadIdx.x == 0) { // (every workgroup that finds one stores the same values)
         src.uncodable = 1u;
@@ -987,7 +1060,8 @@ hipError_t launch_encode(const Plan& plan, uint8_t* d_scratch, unsigned long lon
     Count* counts         = reinterpret_cast<Count*>(d_scratch + plan.count_off);
     Count* count_before   = reinterpret_cast<Count*>(d_scratch + plan.count_before_off);
     const uint32_t chunk_grid = plan.chunks < 4096u ? plan.chunks : 4096u;
-    if (transcode) gather_blocks<<<plan.tiles, kTileBlocks, 0, stream>>>(reinterpret_cast<Item*>(d_scratch + plan.items_off), plan.n, d_scratch);
+    if (transcode && plan.oriented) gather_blocks<true><<<plan.tiles, kTileBlocks, 0, stream>>>(reinterpret_cast<Item*>(d_scratch + plan.items_off), plan.n, d_scratch);
+    else if (transcode) gather_blocks<false><<<plan.tiles, kTileBlocks, 0, stream>>>(reinterpret_cast<Item*>(d_scratch + plan.items_off), plan.n, d_scratch);
     else encode_blocks<<<plan.tiles, kTileBlocks, 0, stream>>>(items, plan.n, d_scratch);
     const auto finish = [&] { // a transcode call's last launch
         if (transcode) finish_transcode<<<(uint32_t(plan.n) + 255u) / 256u, 256, 0, stream>>>(items, plan.n, d_sizes, d_status);

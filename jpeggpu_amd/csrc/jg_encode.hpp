@@ -113,6 +113,7 @@ struct ProgPlan {
 struct Plan {
     int n;
     int optimized; // items with optimised tables: none, and the call is the eight launches it always was
+    int oriented;  // a transcode call's items with an orientation (GatherSrc::oriented): none, and the gather is the one it always was
     ProgPlan prog;
     uint32_t tiles, chunks;
     uint64_t tables_off, items_off; // in the blob

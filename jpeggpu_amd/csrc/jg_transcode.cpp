@@ -45,8 +45,34 @@ jpeggpu_status transcode_spec(const jpeggpu_ext_transcode_item& it, bool need_de
     }
     spec.sampling0 = s.comp[0].sampling;
 
+    // jpeggpu_ext_set_transcode_orientation: the stored image the new file holds is the displayed image of the source's.
+    // A mirror is exact over whole iMCUs of the source only, so the mirrored STORED axes are such multiples or are cut to one
+    const int o          = d.transcode_orientation;
+    const bool transpose = o >= 5, mirror_x = o == 2 || o == 3 || o == 6 || o == 7, mirror_y = o == 3 || o == 4 || o == 7 || o == 8;
+    const bool stored_x = transpose ? mirror_y : mirror_x, stored_y = transpose ? mirror_x : mirror_y;
+    const int hs = s.num_comp == 1 ? 1 : s.comp[0].hs, vs = s.num_comp == 1 ? 1 : s.comp[0].vs;
+    int w = s.size_x, h = s.size_y; // the source, trimmed
+    if (stored_x && w % (8 * hs)) {
+        if (!d.transcode_trim || w < 8 * hs) return JPEGGPU_NOT_SUPPORTED;
+        w -= w % (8 * hs);
+    }
+    if (stored_y && h % (8 * vs)) {
+        if (!d.transcode_trim || h < 8 * vs) return JPEGGPU_NOT_SUPPORTED;
+        h -= h % (8 * vs);
+    }
+    if (transpose) {
+        if (subsampling == JPEGGPU_EXT_SUBSAMPLING_422) return JPEGGPU_NOT_SUPPORTED; // it would be 4:4:0
+        for (int t = 0; t < 2; ++t) { // entry (v, u) is the source's (u, v)
+            uint8_t q[64];
+            for (int k = 0; k < 64; ++k) q[(nat[k] & 7) << 3 | nat[k] >> 3] = spec.qtable[t][k];
+            for (int k = 0; k < 64; ++k) spec.qtable[t][k] = q[nat[k]];
+        }
+        spec.sampling0 = uint8_t(spec.sampling0 << 4 | spec.sampling0 >> 4); // (a grey file's byte too: jpegtran's transpose_critical_parameters)
+    }
+    spec.src.oriented = o != 1, spec.src.transpose = transpose, spec.src.mirror_x = mirror_x, spec.src.mirror_y = mirror_y;
+
     jpeggpu_ext_encode_item& e = spec.item;
-    e.width = s.size_x, e.height = s.size_y, e.channels = s.num_comp;
+    e.width = transpose ? h : w, e.height = transpose ? w : h, e.channels = s.num_comp;
     e.progressive = it.progressive, e.optimize = it.optimize;
     e.quality          = 75; // (unused: the header holds the source's tables)
     e.subsampling      = subsampling;
@@ -57,6 +83,8 @@ jpeggpu_status transcode_spec(const jpeggpu_ext_transcode_item& it, bool need_de
     for (int c = 0; c < s.num_comp; ++c) {
         GatherComp& g = spec.src.comp[c];
         g.vis_x = (s.comp[c].size_x + 7) / 8, g.vis_y = (s.comp[c].size_y + 7) / 8;
+        const int cut_x = ((c ? (w + hs - 1) / hs : w) + 7) / 8, cut_y = ((c ? (h + vs - 1) / vs : h) + 7) / 8; // of the trimmed source
+        g.dst_x = transpose ? cut_y : cut_x, g.dst_y = transpose ? cut_x : cut_y;
         if (s.progressive) {
             g.coef     = reinterpret_cast<const int16_t*>(tmp + d.plan.prog.coef[c]);
             g.blocks_x = s.prog_blocks_x[c];

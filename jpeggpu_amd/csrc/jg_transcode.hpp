@@ -29,6 +29,7 @@ struct GatherComp {
     int32_t interleaved;  // baseline source: the scan holds other components too
     int32_t du_per_mcu, k0, h, v, mcus_x;
     int32_t vis_x, vis_y; // the component's real blocks
+    int32_t dst_x, dst_y; // the TARGET's real blocks of the component (an oriented item: the mirrors run over them)
 };
 
 /// One item's source, in the call's blob behind the items (Item::src points at it, in d_scratch).
@@ -38,6 +39,11 @@ struct GatherSrc {
     // plan offset: the shadow items lie in the blob, which make_plan keeps below 4 GB (its test for Item::header_off)
     uint32_t shadow_off;
     uint32_t uncodable;  // set by the gather: the source holds a coefficient the target cannot code
+    // jpeggpu_ext_set_transcode_orientation other than 1 (`oriented`): block (bx, by) of the target's component grid is the
+    // source's block at  x = mirror_x ? dst_x - 1 - bx : bx,  y = mirror_y ? dst_y - 1 - by : by  (the DISPLAYED axes of
+    // jpeggpu_ext.h's table), x and y exchanged with `transpose`; the coefficients follow (gather_blocks). The target's
+    // dummy blocks are then the encoder's (encode_blocks), whatever the source holds beyond its grid.
+    uint8_t oriented, transpose, mirror_x, mirror_y;
 };
 
 /// What jg_transcode.cpp says of one item: the encoder's item (geometry, options, slot; `data` and `quality` unused), the

@@ -13,9 +13,11 @@ RESIDENT ("resident_*"): the files parsed and transferred once, the output slots
 decode batch plus jpeggpu_ext_transcode_batch, or the decode batch, jpeggpu_ext_batch_to_rgb and jpeggpu_ext_encode_batch,
 up to the synchronisation -- what the device does for either route.
 `--once optimize|progressive` runs a single transcode call and nothing else: the process to put under a kernel trace, which
-gives gather_blocks its own time (it writes 36 MB of coefficients per image).
+gives gather_blocks its own time (it writes 36 MB of coefficients per image); `--orientation N` turns every file of that
+call (transcode_jpeg's `orientation`), which launches the gather's other instantiation.
 
-    python tools/transcode_rate.py [--rounds 7] [--iters 3] [--images 64] [--out transcode_rate.json] [--once optimize|progressive]
+    python tools/transcode_rate.py [--rounds 7] [--iters 3] [--images 64] [--out transcode_rate.json]
+                                   [--once optimize|progressive [--orientation N]]
 """
 import argparse
 import json
@@ -105,12 +107,13 @@ def _resident(torch, jpeggpu_amd, datas, rounds, iters):
     return res
 
 
-def once(flag, n):
+def once(flag, n, orientation=None):
     import torch
 
     import jpeggpu_amd
 
-    files = jpeggpu_amd.transcode_jpeg(_sources(n), **{flag: True})
+    more = dict(orientation=orientation) if orientation else {}  # (4032 x 3024 is whole iMCUs both ways: every orientation is exact)
+    files = jpeggpu_amd.transcode_jpeg(_sources(n), **{flag: True}, **more)
     torch.cuda.synchronize()
     print(json.dumps(dict(images=len(files), file_bytes=sum(len(f) for f in files))))
 
@@ -122,9 +125,10 @@ def main():
     ap.add_argument("--images", type=int, default=64)
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", default=None, choices=("optimize", "progressive"))
+    ap.add_argument("--orientation", type=int, default=None, help="with --once: transcode_jpeg's orientation, 1..8")
     a = ap.parse_args()
     if a.once:
-        return once(a.once, a.images)
+        return once(a.once, a.images, a.orientation)
     res = run(a.rounds, a.iters, a.images)
     print(json.dumps(res), flush=True)
     if a.out:
