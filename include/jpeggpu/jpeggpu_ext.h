@@ -43,6 +43,7 @@
  *                                      tables, as progressive or baseline, with other restart intervals; no IDCT, no loss
  *   jpeggpu_ext_set_transcode_orientation  ... turned, flipped or transposed on the way (jpegtran -rotate / -flip / -transpose),
  *                                      still without loss: an EXIF orientation baked into the file
+ *   jpeggpu_ext_set_transcode_crop     ... or cut to a rectangle (jpegtran -crop), decoding only the restart segments it needs
  */
 #ifndef JPEGGPU_JPEGGPU_EXT_H_
 #define JPEGGPU_JPEGGPU_EXT_H_
@@ -1022,8 +1023,8 @@ enum jpeggpu_status jpeggpu_ext_encode_tables_from_counts(
  *   - What can be transcoded is what the encoder writes: 8-bit samples; one component (its frame header keeps the sampling
  *     byte the source names), or three that jpeggpu_ext_get_color_space calls YCbCr with chroma 1x1 and luma 1x1, 2x1 or 2x2,
  *     8-bit quantisation tables (Pq = 0), Cb and Cr on one table. JPEGGPU_NOT_SUPPORTED, before anything is enqueued, for
- *     anything else (4:4:0, 4:1:1, RGB-coded, CMYK, YCCK, Pq = 1, Cb and Cr on different tables), for a decoder with a crop, a
- *     scale other than 1 or a segment shard, and at the encoder's size limits. JPEGGPU_INVALID_ARGUMENT as for
+ *     anything else (4:4:0, 4:1:1, RGB-coded, CMYK, YCCK, Pq = 1, Cb and Cr on different tables), for a decoder with a crop
+ *     (unless jpeggpu_ext_set_transcode_crop is set too, below), a scale other than 1 or a segment shard, and at the encoder's size limits. JPEGGPU_INVALID_ARGUMENT as for
  *     jpeggpu_ext_encode_batch, for a decoder that has parsed nothing and a restart interval outside -1..65535.
  *   - jpeggpu_ext_transcode_header (host only): the header of an item without `optimize` and `progressive`, as
  *     jpeggpu_ext_encode_header; _bound and _scratch_size reuse the encoder's arithmetic per block.
@@ -1061,7 +1062,35 @@ enum jpeggpu_status jpeggpu_ext_encode_tables_from_counts(
  *         dummy blocks are never read;
  *       - the coding limits are the target's: the DC-difference rule runs in the target's prediction order.
  *         `restart_interval` -1 keeps the source's NUMBER of MCUs.
- *     A call with such an item launches another instantiation of the gather kernel; the number of launches is the same. */
+ *     A call with such an item launches another instantiation of the gather kernel; the number of launches is the same.
+ *   - jpeggpu_ext_set_transcode_crop(decoder, x, y, width, height): jpegtran -crop. The new file holds the rectangle of the
+ *     image the transcode would write without it -- the image AFTER the orientation and its trim, so with an orientation
+ *     the rectangle is in displayed pixels, as jpegtran applies -crop to its transformed output. Read by the four
+ *     jpeggpu_ext_transcode_ calls only, when they are called, and held until it is set again, like the orientation.
+ *     (0, 0, 0, 0), the default, switches it off: every call is then what it was, launch for launch and byte for byte. A
+ *     negative value, or a `width` or `height` of 0 beside any other value: JPEGGPU_INVALID_ARGUMENT at once. Checked by all
+ *     four calls before anything is enqueued, on the uncropped target W' x H' with luma factors hs' x vs' (exchanged for
+ *     5..8; 1 x 1 for grey):
+ *       - x + width <= W' and y + height <= H', else JPEGGPU_INVALID_ARGUMENT;
+ *       - x a multiple of 8 hs' and y of 8 vs', else JPEGGPU_NOT_SUPPORTED (jpegtran -perfect; round down and grow the size
+ *         for jpegtran's own behaviour, as transcode_jpeg(expand=True) does). `width` and `height` may be anything from 1 up;
+ *       - the orientation's edge and trim rules stay on the WHOLE source, as they are.
+ *     The target is width x height. Its real blocks are the uncropped target's from block (x / 8, y / 8) of luma and
+ *     (x / (8 hs'), y / (8 vs')) of chroma on; the mirrors run over the UNCROPPED target's grid (written block -> plus
+ *     offset -> mirror -> exchange -> source block). Its dummy blocks are the encoder's, as for an orientation, also for a
+ *     crop of the whole image (a cropped item, not "off"). Tables, sampling byte, restart interval (-1: the source's number
+ *     of MCUs) and the coding limits in the target's prediction order are as without a crop -- the left edge of a crop is
+ *     predicted from the right edge of its row above; header, bound and scratch size are the encoder's arithmetic on
+ *     width x height. Where the rectangle starts on an iMCU boundary and each extent is a multiple of the iMCU or reaches
+ *     the image's edge, the file of a source Pillow wrote is the file Pillow writes for the cropped pixels; an extent that
+ *     ends inside the image keeps the source's real samples beyond it in its last blocks (Pillow would replicate the edge).
+ *     A call with such an item launches the mapped instantiation of the gather kernel, also at orientation 1.
+ *     With a transcode crop the decoder may carry a decode window (jpeggpu_ext_set_crop), so that only the restart segments
+ *     that hold the window are transferred and entropy-decoded (a single scan with restart markers; any other file is
+ *     decoded whole, a progressive one into whole coefficient arrays, and transcodes all the same): the window's frame MCUs
+ *     must hold every source block the target reads, the DC sources of its dummy blocks included, else
+ *     JPEGGPU_NOT_SUPPORTED. A rectangle of pixels that covers the source pixels of the target does (the window adds a
+ *     sample of halo). A decode window WITHOUT a transcode crop, a scale and a segment shard stay JPEGGPU_NOT_SUPPORTED. */
 struct jpeggpu_ext_transcode_item {
     jpeggpu_decoder_t decoder;
     void* d_tmp;
@@ -1083,6 +1112,7 @@ enum jpeggpu_status jpeggpu_ext_transcode_batch(
     jpeggpu_stream_t stream);
 enum jpeggpu_status jpeggpu_ext_batch_set_coefficients_only(jpeggpu_batch_t batch, int enable);
 enum jpeggpu_status jpeggpu_ext_set_transcode_orientation(jpeggpu_decoder_t decoder, int orientation, int trim);
+enum jpeggpu_status jpeggpu_ext_set_transcode_crop(jpeggpu_decoder_t decoder, int x, int y, int width, int height);
 
 #ifdef __cplusplus
 }

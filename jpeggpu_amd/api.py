@@ -318,6 +318,8 @@ def lib():
         L.jpeggpu_ext_batch_set_coefficients_only.argtypes = [C.c_void_p, C.c_int]
     if hasattr(L, "jpeggpu_ext_set_transcode_orientation"):
         L.jpeggpu_ext_set_transcode_orientation.argtypes = [dec, C.c_int, C.c_int]
+    if hasattr(L, "jpeggpu_ext_set_transcode_crop"):
+        L.jpeggpu_ext_set_transcode_crop.argtypes = [dec, C.c_int, C.c_int, C.c_int, C.c_int]
     if hasattr(L, "jpeggpu_ext_encode_tables_from_counts"):
         L.jpeggpu_ext_encode_tables_from_counts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.jpeggpu_ext_resize_weights.argtypes = [
@@ -402,6 +404,7 @@ class Decoder:
             ptr = data.ctypes.data if hasattr(data, "ctypes") else data.data_ptr()
             n = data.nbytes if hasattr(data, "nbytes") else data.numel()
         _check(lib().jpeggpu_decoder_parse_header(self._h, C.byref(info), ptr, n), "jpeggpu_decoder_parse_header")
+        self.info = info  # of the last parsed image
         return info
 
     def set_device_scan(self, on=True):
@@ -445,6 +448,12 @@ class Decoder:
         stored image of the new file is the displayed image under `orientation` (1..8); `trim` cuts partial iMCUs at a
         mirrored edge instead of refusing them. Decodes to pixels ignore it."""
         _check(_newer_symbol("jpeggpu_ext_set_transcode_orientation")(self._h, int(orientation), int(trim)), "jpeggpu_ext_set_transcode_orientation")
+
+    def set_transcode_crop(self, x: int = 0, y: int = 0, w: int = 0, h: int = 0):
+        """jpeggpu_ext_set_transcode_crop: the transcode calls write only the rectangle (x, y, w, h) of the image they would
+        write without it (after the orientation and its trim) from now on; (0, 0, 0, 0): the whole image again. x and y are
+        multiples of the target's iMCU. Decodes to pixels ignore it."""
+        _check(_newer_symbol("jpeggpu_ext_set_transcode_crop")(self._h, int(x), int(y), int(w), int(h)), "jpeggpu_ext_set_transcode_crop")
 
     def set_progressive(self, on: bool = True):
         """Read progressive JPEGs (SOF2) from the next parse_header on; off by default, when they are NOT_SUPPORTED
@@ -1563,15 +1572,84 @@ def _transcode_orientations(bd, orientation, exif_transpose, trim):
     return out
 
 
-def _transcode_items(bd, optimize, progressive, restart_interval, orientation=None, exif_transpose=False, trim=False):
+def _expanded(rect, ths, tvs):
+    """jpegtran's rule for a crop that does not start on an iMCU boundary: the origin moves up and left to one and the size
+    grows by what that adds."""
+    x, y, w, h = rect
+    return x - x % (8 * ths), y - y % (8 * tvs), w + x % (8 * ths), h + y % (8 * tvs)
+
+
+def transcode_crop_rects(width, height, hs, vs, rect, orientation=1, trim=False, expand=False):
+    """The arithmetic of a cropped transcode (host only, no library call): for a stored width x height source whose luma has
+    the factors hs x vs (1, 1 for grey) and a rectangle (x, y, w, h) in pixels of the image the transcode would write without
+    a crop -- the displayed image under `orientation`, cut by `trim` where the orientation's edge rules need it -- returns
+    (target, source): `target` the rectangle the library gets (with `expand`, x and y rounded down to the target's iMCU and w
+    and h grown by what was cut, jpegtran's rule), `source` the rectangle of stored source pixels it holds, what
+    Decoder.set_crop takes to decode no more than that. ValueError: the orientation refuses the source, or the rectangle is
+    empty or does not lie inside the uncropped target. The alignment of x and y is the library's to judge."""
+    o = int(orientation)
+    if not 1 <= o <= 8:
+        raise ValueError("orientation must be 1..8")
+    w, h = int(width), int(height)
+    if o in (2, 3, 7, 8) and w % (8 * hs):  # the stored x is mirrored
+        if not trim or w < 8 * hs:
+            raise ValueError("a mirrored edge with a partial iMCU")
+        w -= w % (8 * hs)
+    if o in (3, 4, 6, 7) and h % (8 * vs):
+        if not trim or h < 8 * vs:
+            raise ValueError("a mirrored edge with a partial iMCU")
+        h -= h % (8 * vs)
+    tw, th, ths, tvs = (h, w, vs, hs) if o >= 5 else (w, h, hs, vs)
+    x, y, cw, ch = (int(v) for v in rect)
+    if expand:
+        x, y, cw, ch = _expanded((x, y, cw, ch), ths, tvs)
+    if x < 0 or y < 0 or cw < 1 or ch < 1 or x + cw > tw or y + ch > th:
+        raise ValueError("the rectangle does not lie inside the %d x %d image" % (tw, th))
+    x0 = tw - x - cw if o in (2, 3, 6, 7) else x  # the displayed axes' mirrors, then the exchange
+    y0 = th - y - ch if o in (3, 4, 7, 8) else y
+    return (x, y, cw, ch), ((y0, x0, ch, cw) if o >= 5 else (x0, y0, cw, ch))
+
+
+def _luma_factors(info):
+    """(hs, vs) as the transcode counts iMCUs: luma's factors of a colour file, (1, 1) for grey."""
+    return (1, 1) if info.num_components == 1 else (info.subsampling.x[0], info.subsampling.y[0])
+
+
+def _transcode_crops(n, crops):
+    """`crops` of the transcode calls as a list of n entries: None or (x, y, w, h)."""
+    if crops is None:
+        return [None] * n
+    if len(crops) == 4 and not any(c is None or hasattr(c, "__len__") for c in crops):
+        return [tuple(int(v) for v in crops)] * n
+    crops = list(crops)
+    if len(crops) != n:
+        raise ValueError("crops must be one rectangle or one entry per file")
+    for i, c in enumerate(crops):
+        if c is not None and len(c) != 4:
+            raise ValueError("crops[%d]: (x, y, w, h) is expected" % i)
+    return [None if c is None else tuple(int(v) for v in c) for c in crops]
+
+
+def _transcode_items(bd, optimize, progressive, restart_interval, orientation=None, exif_transpose=False, trim=False, crops=None, expand=False):
     """The items of a transcode call for the decoded files of a BatchDecode, without output slots; a source the writer cannot
-    take raises JpegGpuError naming the item. Sets each decoder's transcode orientation (Decoder.set_transcode_orientation),
-    which the calls on the items read."""
+    take raises JpegGpuError naming the item. Sets each decoder's transcode orientation (Decoder.set_transcode_orientation)
+    and crop (Decoder.set_transcode_crop), which the calls on the items read."""
     n = len(bd.decoders)
     os_, ps_, rs = _per_image(optimize, n, "optimize"), _per_image(progressive, n, "progressive"), _per_image(restart_interval, n, "restart_interval")
-    for dec, (o, t) in zip(bd.decoders, _transcode_orientations(bd, orientation, exif_transpose, trim)):
+    crops, expands = _transcode_crops(n, crops), _per_image(expand, n, "expand")
+    for i, (dec, (o, t)) in enumerate(zip(bd.decoders, _transcode_orientations(bd, orientation, exif_transpose, trim))):
         if o != 1 or t or hasattr(lib(), "jpeggpu_ext_set_transcode_orientation"):
             dec.set_transcode_orientation(o, t)
+        rect = crops[i]
+        if rect is not None and expands[i]:
+            hs, vs = _luma_factors(bd.infos[i])
+            ths, tvs = (vs, hs) if o >= 5 else (hs, vs)
+            rect = _expanded(rect, ths, tvs)
+        if rect is not None or hasattr(lib(), "jpeggpu_ext_set_transcode_crop"):
+            try:
+                dec.set_transcode_crop(*(rect or (0, 0, 0, 0)))
+            except JpegGpuError as e:
+                raise JpegGpuError(e.status, "jpeggpu_ext_set_transcode_crop: item %d: crop %r" % (i, rect))
     items = (TranscodeItem * max(n, 1))()
     bound = _newer_symbol("jpeggpu_ext_transcode_bound")
     for i, (dec, _, _, base, _) in enumerate(bd._entries):
@@ -1586,16 +1664,19 @@ def _transcode_items(bd, optimize, progressive, restart_interval, orientation=No
     return items
 
 
-def transcode_into(bd, outs, optimize=False, progressive=False, restart_interval=None, items=None, orientation=None, exif_transpose=False, trim=False):
+def transcode_into(bd, outs, optimize=False, progressive=False, restart_interval=None, items=None, orientation=None, exif_transpose=False, trim=False,
+                   crops=None, expand=False):
     """jpeggpu_ext_transcode_batch on torch's current stream, without synchronising, for the files of `bd`, a BatchDecode whose
     decode() was enqueued on the same stream: file i into the slot outs[i], as encode_into. Returns the device tensors
     (sizes int64[n], status int32[n]); status 1: the slot was too small, 2: as encode_into, 4: the source holds a
     coefficient that no Huffman code of the target expresses, and its size is 0. `items`: what _transcode_items made of the
-    same arguments, for a caller that has them already. `orientation`, `exif_transpose`, `trim`: as transcode_jpeg's."""
+    same arguments, for a caller that has them already. `orientation`, `exif_transpose`, `trim`, `crops`, `expand`: as
+    transcode_jpeg's; `bd` decodes what its maker asked for -- whole files, or with BatchDecode(crops=) the source rectangles
+    of transcode_crop_rects, which must hold what the items read."""
     import torch
 
     if items is None:
-        items = _transcode_items(bd, optimize, progressive, restart_interval, orientation, exif_transpose, trim)
+        items = _transcode_items(bd, optimize, progressive, restart_interval, orientation, exif_transpose, trim, crops, expand)
     n = len(bd.decoders)
     if len(outs) != n:
         raise ValueError("outs must have one entry per file")
@@ -1617,8 +1698,26 @@ def transcode_into(bd, outs, optimize=False, progressive=False, restart_interval
     return result[:8 * n].view(torch.int64), result[8 * n:].view(torch.int32)
 
 
+def _transcode_windows(n, orientation, exif_transpose, trim, crops, expand):
+    """BatchDecode's crop_hooks for a cropped transcode: each cropped file decodes only the source rectangle of its crop
+    (transcode_crop_rects). A rectangle the rules refuse sets no window: the item is then refused by the library, by name."""
+    crops = _transcode_crops(n, crops)
+    if not any(c is not None for c in crops):
+        return None
+    os_, es, ts, xs = _per_image(orientation, n, "orientation"), _per_image(exif_transpose, n, "exif_transpose"), _per_image(trim, n, "trim"), _per_image(expand, n, "expand")
+
+    def hook(i, dec, w, h):
+        o = dec.orientation() if es[i] else 1 if os_[i] is None else int(os_[i])
+        try:
+            return transcode_crop_rects(w, h, *_luma_factors(dec.info), crops[i], o, bool(ts[i]), bool(xs[i]))[1]
+        except ValueError:
+            return None
+
+    return [None if c is None else hook for c in crops]
+
+
 def transcode_jpeg_to_device(datas, optimize=False, progressive=False, restart_interval=None, device="cuda:0", capacities=None, orientation=None,
-                             exif_transpose=False, trim=False):
+                             exif_transpose=False, trim=False, crops=None, expand=False):
     """transcode_jpeg's files left on the device: (buffer, offsets, sizes) as encode_jpeg_to_device returns them.
     `capacities`: the slot sizes to start with (default: twice the source's length, a header and three bytes per block of the
     TARGET for restart markers and their padding); if a file is larger, the call is repeated once with the sizes it reported."""
@@ -1628,10 +1727,10 @@ def transcode_jpeg_to_device(datas, optimize=False, progressive=False, restart_i
     if not datas:
         return None, [], []
     _newer_symbol("jpeggpu_ext_transcode_batch")
-    with BatchDecode(datas, device, coefficients_only=True) as bd:
-        n = len(datas)
+    n = len(datas)
+    with BatchDecode(datas, device, coefficients_only=True, crop_hooks=_transcode_windows(n, orientation, exif_transpose, trim, crops, expand)) as bd:
         # (host only: refuses before anything is enqueued or allocated)
-        items = _transcode_items(bd, optimize, progressive, restart_interval, orientation, exif_transpose, trim)
+        items = _transcode_items(bd, optimize, progressive, restart_interval, orientation, exif_transpose, trim, crops, expand)
         bd.decode()
         if capacities is None:
             caps = [2 * len(d) + 1024 + 3 * _transcode_blocks(items[i]) for i, d in enumerate(datas)]
@@ -1674,7 +1773,8 @@ def _transcode_blocks(item):
     return ((head[at] << 8 | head[at + 1]) + 7) // 8 * (((head[at + 2] << 8 | head[at + 3]) + 7) // 8)
 
 
-def transcode_jpeg(datas, optimize=False, progressive=False, restart_interval=None, device="cuda:0", orientation=None, exif_transpose=False, trim=False):
+def transcode_jpeg(datas, optimize=False, progressive=False, restart_interval=None, device="cuda:0", orientation=None, exif_transpose=False, trim=False,
+                   crops=None, expand=False):
     """JPEG files from JPEG files without a pixel in between, as a list of bytes: what jpegtran -optimize, -progressive and
     -restart N do. Each file holds the source's quantised coefficients exactly, in the layout encode_jpeg writes (the
     source's quantisation tables; EXIF, ICC and comments are dropped). `optimize`, `progressive` as in encode_jpeg;
@@ -1687,11 +1787,19 @@ def transcode_jpeg(datas, optimize=False, progressive=False, restart_interval=No
     bakes the tag into the file (the result holds no Exif segment); naming both for a file is a ValueError. A mirrored edge
     must be a whole number of iMCUs of the source: otherwise the item raises JpegGpuError before anything is enqueued, or
     with `trim` the partial iMCUs at that edge are cut off first, like jpegtran -trim. 4:2:2 takes 1..4 only.
+    `crops`: one rectangle (x, y, w, h) or one per file (None: the whole image), cut out without loss like jpegtran -crop, in
+    pixels of the image the call would write without it -- after `orientation` and `trim`, so in displayed pixels. x and y
+    must be multiples of the target's iMCU (8 hs x 8 vs of luma's factors, exchanged for 5..8; 8 x 8 for grey), or with
+    `expand` (one value or one per file) they are rounded down to one and w and h grow by what that adds, which is what
+    jpegtran does; w and h may be anything. Where w and h are multiples of the iMCU too or reach the image's edge, the file is
+    the one Pillow writes for the cropped pixels. Each cropped file is decoded only as far as its rectangle needs
+    (transcode_crop_rects, Decoder.set_crop: the restart segments that hold it, where the file has restart markers).
     One batched decode that stops in front of the IDCT, one jpeggpu_ext_transcode_batch call, one synchronisation and one
     copy of the files' bytes to the host."""
     import torch
 
-    buf, offsets, sizes = transcode_jpeg_to_device(datas, optimize, progressive, restart_interval, device, None, orientation, exif_transpose, trim)
+    buf, offsets, sizes = transcode_jpeg_to_device(datas, optimize, progressive, restart_interval, device, None, orientation, exif_transpose, trim, crops,
+                                                   expand)
     if not sizes:
         return []
     host = torch.cat([buf[o:o + s] for o, s in zip(offsets, sizes)]).cpu().numpy().tobytes()

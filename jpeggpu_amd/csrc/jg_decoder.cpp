@@ -422,6 +422,15 @@ enum jpeggpu_status jpeggpu_ext_set_transcode_orientation(jpeggpu_decoder_t deco
     return JPEGGPU_SUCCESS;
 }
 
+enum jpeggpu_status jpeggpu_ext_set_transcode_crop(jpeggpu_decoder_t decoder, int x, int y, int width, int height)
+{
+    if (!decoder || x < 0 || y < 0 || width < 0 || height < 0) return JPEGGPU_INVALID_ARGUMENT;
+    if ((width == 0 || height == 0) && (x || y || width || height)) return JPEGGPU_INVALID_ARGUMENT; // all zero: no crop
+    int* r = decoder->d.transcode_crop;
+    r[0] = x, r[1] = y, r[2] = width, r[3] = height;
+    return JPEGGPU_SUCCESS;
+}
+
 enum jpeggpu_status jpeggpu_ext_set_scale_mode(jpeggpu_decoder_t decoder, enum jpeggpu_ext_scale_mode mode)
 {
     if (!decoder) return JPEGGPU_INVALID_ARGUMENT;

@@ -144,6 +144,9 @@ struct Decoder {
     // jpeggpu_ext_set_transcode_orientation: read by the jpeggpu_ext_transcode_* calls only (jg_transcode.cpp), when they run
     int transcode_orientation = 1;
     bool transcode_trim       = false;
+    // jpeggpu_ext_set_transcode_crop: {x, y, width, height} in pixels of the image the transcode would write without it
+    // (width 0: none), read by the same calls
+    int transcode_crop[4] = {0, 0, 0, 0};
     int plane_x(int c) const { return crop.on ? crop.wx[c] : full_x(c); } // what decode writes
     int plane_y(int c) const { return crop.on ? crop.wy[c] : full_y(c); }
     JG_LOCAL bool set_crop_window();

@@ -32,7 +32,8 @@
 // A transcode call (jpeggpu_ext_transcode_batch; jg_transcode.hpp) is the same sequence with gather_blocks in place of launch 1
 // -- the items' coefficients come from the decoder's entropy stage, not from pixels -- and finish_transcode behind the last
 // launch, which reports the items whose source holds a coefficient the target cannot code. With an item that has an orientation
-// (jpeggpu_ext_set_transcode_orientation) the call launches gather_blocks<true>, which maps blocks and coefficients on the way.
+// (jpeggpu_ext_set_transcode_orientation) or a crop (jpeggpu_ext_set_transcode_crop) the call launches gather_blocks<true>,
+// which maps blocks and coefficients on the way.
 //
 // No kernel waits for another workgroup: every dependency is a launch boundary.
 #include "jg_encode_prog.hpp"
@@ -846,9 +847,11 @@ __global__ __launch_bounds__(256) void write_files(
 // ------------------------------------------------------------------------------------------------
 
 /// Block b of an item's MCU stream as a block of its component's padded grid.
-/// kOriented, and the item has an orientation (GatherSrc::oriented): the block of the SOURCE's grid that the target's block
-/// is, and `dummy` for a luma block beyond the target's real grid -- then the block is the real one whose DC the encoder
-/// gives it (encode_blocks), and only that DC is the source's. Such an item never reads the source's own dummy blocks.
+/// kOriented, and the item has an orientation or a crop (GatherSrc::oriented): the block of the SOURCE's grid that the
+/// target's block is, and `dummy` for a luma block beyond the target's real grid -- then the block is the real one whose DC
+/// the encoder gives it (encode_blocks), and only that DC is the source's. Such an item never reads the source's own dummy
+/// blocks. In order: the written grid's block, plus the crop's offset in the uncropped target's grid, mirrored there,
+/// exchanged.
 struct SrcBlock {
     int comp, bx, by;
     bool dummy;
@@ -878,6 +881,7 @@ __device__ inline SrcBlock src_block(const Item& it, const GatherSrc& src, int b
         }
     }
     const GatherComp& c = src.comp[sb.comp];
+    sb.bx += c.off_x, sb.by += c.off_y;
     const int x = src.mirror_x ? c.dst_x - 1 - sb.bx : sb.bx, y = src.mirror_y ? c.dst_y - 1 - sb.by : sb.by;
     sb.bx = src.transpose ? y : x, sb.by = src.transpose ? x : y;
     return sb;
@@ -912,11 +916,20 @@ __device__ inline bool oriented_row(const uint32_t (&w)[32], uint32_t* row, bool
 }
 
 /// The data unit of a baseline source that holds the block, -1: no scan codes it (a dummy block of a component's own scan).
-__device__ inline int src_unit(const GatherComp& c, int bx, int by)
+/// kOriented: counted from GatherSrc::first_unit, as the IDCT stage counts from its first_mcu (jg_idct.hip); a unit in front
+/// of it was not decoded and is -1 (transcode_spec refuses an item that would read one, on either side of what was kept).
+template <bool kOriented>
+__device__ inline int src_unit(const GatherSrc& src, const GatherComp& c, int bx, int by)
 {
-    if (!c.interleaved) return bx < c.vis_x && by < c.vis_y ? by * c.vis_x + bx : -1;
-    const int mx = bx / c.h, my = by / c.v;
-    return (my * c.mcus_x + mx) * c.du_per_mcu + c.k0 + (by - my * c.v) * c.h + (bx - mx * c.h);
+    int unit;
+    if (!c.interleaved) {
+        unit = bx < c.vis_x && by < c.vis_y ? by * c.vis_x + bx : -1;
+    } else {
+        const int mx = bx / c.h, my = by / c.v;
+        unit         = (my * c.mcus_x + mx) * c.du_per_mcu + c.k0 + (by - my * c.v) * c.h + (bx - mx * c.h);
+    }
+    if (kOriented) unit = unit >= src.first_unit ? unit - src.first_unit : -1;
+    return unit;
 }
 
 /// A unit's record with its first entry held inside the buffer, as idct_scaled_kernel holds it (jg_idct.hip): a record
@@ -935,7 +948,7 @@ __device__ inline int src_dc(const Item& it, const GatherSrc& src, int b)
     const SrcBlock sb   = src_block<kOriented>(it, src, b);
     const GatherComp& c = src.comp[sb.comp];
     if (c.coef) return c.coef[(int64_t(sb.by) * c.blocks_x + sb.bx) * 64];
-    const int unit = src_unit(c, sb.bx, sb.by);
+    const int unit = src_unit<kOriented>(src, c, sb.bx, sb.by);
     return unit < 0 ? 0 : int16_t(c.sym[src_record(c, unit).x]);
 }
 
@@ -949,7 +962,8 @@ __device__ inline int src_dc(const Item& it, const GatherSrc& src, int b)
 /// what the kernel takes follows the entries per unit. The measured 1.5 ms per 64 photographs is for
 /// photographic units of a dozen entries or two; a source of dense units (every coefficient coded, every one escaped) takes
 /// several times as long per block. GatherSrc::shadow_off is a 32-bit offset: the blob it points into is below 4 GB.
-/// kOriented: the instantiation of a call with an item of orientation 2..8 (jpeggpu_ext_set_transcode_orientation). The lane
+/// kOriented: the instantiation of a call with a mapped item: of orientation 2..8 (jpeggpu_ext_set_transcode_orientation) or
+/// with a crop (jpeggpu_ext_set_transcode_crop), which is the identity orientation behind an offset. The lane
 /// reads the source block that src_block names and stores each coefficient at the transposed zigzag index with its mirror's
 /// sign; a dummy block of such an item takes one DC from the source and nothing else. An item of orientation 1 in such a
 /// call goes the same way with an identity mapping and gets the values the other instantiation gives it.
@@ -999,7 +1013,7 @@ __global__ __launch_bounds__(kTileBlocks) void gather_blocks(Item* items, int n,
         } else {
 #pragma unroll
             for (int k = 0; k < 32; ++k) row[k] = 0u;
-            const int unit = src_unit(c, sb.bx, sb.by);
+            const int unit = src_unit<kOriented>(src, c, sb.bx, sb.by);
             if (unit >= 0) {
                 const uint2_t rec  = src_record(c, unit);
                 const uint32_t cnt = rec.y & 0x7Fu;

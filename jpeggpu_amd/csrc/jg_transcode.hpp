@@ -17,7 +17,8 @@ namespace enc {
 ///   baseline source     the symbol stream and data-unit table of the scan that codes the component (jg_defs.h): block
 ///                       (bx, by) of the component is data unit  mcu * du_per_mcu + k0 + dy * h + dx  of an interleaved scan
 ///                       (mcu over the frame's MCU grid, so dummy blocks are units like any other), and unit
-///                       by * vis_x + bx  of a scan of the component alone, which codes the real blocks only
+///                       by * vis_x + bx  of a scan of the component alone, which codes the real blocks only; a mapped item
+///                       counts both from GatherSrc::first_unit (a decode that kept only some restart segments)
 ///   progressive source  the component's coefficient array: int16[64] per block in natural order, raster over the MCU-padded
 ///                       grid `blocks_x` wide (jg_prog_core.h); the blocks no scan wrote are the zeros the decode began with
 struct GatherComp {
@@ -29,8 +30,12 @@ struct GatherComp {
     int32_t interleaved;  // baseline source: the scan holds other components too
     int32_t du_per_mcu, k0, h, v, mcus_x;
     int32_t vis_x, vis_y; // the component's real blocks
-    int32_t dst_x, dst_y; // the TARGET's real blocks of the component (an oriented item: the mirrors run over them)
+    int32_t dst_x, dst_y; // the TARGET's real blocks of the component (a mapped item: the mirrors run over them)
+    // jpeggpu_ext_set_transcode_crop: the block of that grid where the written file's grid begins (in what was padding: the
+    // struct keeps its size, and a frame of 65535 pixels has 8192 blocks)
+    int16_t off_x, off_y;
 };
+static_assert(sizeof(GatherComp) == 80, "GatherComp: the crop's offsets lie in its padding");
 
 /// One item's source, in the call's blob behind the items (Item::src points at it, in d_scratch).
 struct GatherSrc {
@@ -39,12 +44,17 @@ struct GatherSrc {
     // plan offset: the shadow items lie in the blob, which make_plan keeps below 4 GB (its test for Item::header_off)
     uint32_t shadow_off;
     uint32_t uncodable;  // set by the gather: the source holds a coefficient the target cannot code
-    // jpeggpu_ext_set_transcode_orientation other than 1 (`oriented`): block (bx, by) of the target's component grid is the
-    // source's block at  x = mirror_x ? dst_x - 1 - bx : bx,  y = mirror_y ? dst_y - 1 - by : by  (the DISPLAYED axes of
+    // jpeggpu_ext_set_transcode_orientation other than 1 or jpeggpu_ext_set_transcode_crop (`oriented`: the item is mapped):
+    // block (bx, by) of the written component grid is block (bx + off_x, by + off_y) of the uncropped target's, and that is
+    // the source's block at  x = mirror_x ? dst_x - 1 - bx : bx,  y = mirror_y ? dst_y - 1 - by : by  (the DISPLAYED axes of
     // jpeggpu_ext.h's table), x and y exchanged with `transpose`; the coefficients follow (gather_blocks). The target's
     // dummy blocks are then the encoder's (encode_blocks), whatever the source holds beyond its grid.
     uint8_t oriented, transpose, mirror_x, mirror_y;
+    // a mapped item of a baseline source whose decode kept only some restart segments (jpeggpu_ext_set_crop; Scan::first_mcu):
+    // the frame's data unit that is unit 0 of du_tab. Such a file has one scan, so one number serves its components.
+    int32_t first_unit;
 };
+static_assert(sizeof(GatherSrc) == 256, "GatherSrc: first_unit lies in its padding");
 
 /// What jg_transcode.cpp says of one item: the encoder's item (geometry, options, slot; `data` and `quality` unused), the
 /// header's tables and sampling byte, the source.
