@@ -44,6 +44,7 @@
  *   jpeggpu_ext_set_transcode_orientation  ... turned, flipped or transposed on the way (jpegtran -rotate / -flip / -transpose),
  *                                      still without loss: an EXIF orientation baked into the file
  *   jpeggpu_ext_set_transcode_crop     ... or cut to a rectangle (jpegtran -crop), decoding only the restart segments it needs
+ *   jpeggpu_ext_set_transcode_frame    ... keeping the source's own frame layout: any sampling, up to four components and tables
  */
 #ifndef JPEGGPU_JPEGGPU_EXT_H_
 #define JPEGGPU_JPEGGPU_EXT_H_
@@ -1090,7 +1091,38 @@ enum jpeggpu_status jpeggpu_ext_encode_tables_from_counts(
  *     decoded whole, a progressive one into whole coefficient arrays, and transcodes all the same): the window's frame MCUs
  *     must hold every source block the target reads, the DC sources of its dummy blocks included, else
  *     JPEGGPU_NOT_SUPPORTED. A rectangle of pixels that covers the source pixels of the target does (the window adds a
- *     sample of halo). A decode window WITHOUT a transcode crop, a scale and a segment shard stay JPEGGPU_NOT_SUPPORTED. */
+ *     sample of halo). A decode window WITHOUT a transcode crop, a scale and a segment shard stay JPEGGPU_NOT_SUPPORTED.
+ *   - jpeggpu_ext_set_transcode_frame(decoder, mode): which frame layout the new file has. Read by the four
+ *     jpeggpu_ext_transcode_ calls only, when they are called, and held until it is set again, like the orientation and the
+ *     crop. A value other than the two below: JPEGGPU_INVALID_ARGUMENT, and the setting stays as it was.
+ *       JPEGGPU_EXT_TRANSCODE_FRAME_ENCODER (0, the default): the layout the pixel encoder writes, and every refusal above.
+ *       JPEGGPU_EXT_TRANSCODE_FRAME_SOURCE (1): the new file keeps the SOURCE's frame layout, as the file libjpeg writes
+ *         after jpeg_copy_critical_parameters (jpegtran). Accepted: every file the parser accepts with one to four
+ *         components -- any sampling factors (at most 10 blocks per MCU), up to four quantisation tables with 8- or 16-bit
+ *         entries, every colour model jpeggpu_ext_get_color_space tells apart and two components; baseline, multi-scan and
+ *         progressive sources. A scale, a segment shard, a decode window without a transcode crop, the encoder's size
+ *         limits and the coding limits are refused as in the other mode. A file the other mode accepts gives the same
+ *         bytes with every option (so such a file's tables are numbered 0 and 1 as there, whatever the source calls them).
+ *         The file written, for every other source:
+ *           - colour space: the source's. Component ids 1, 2, 3 (YCbCr), 'R' 'G' 'B', 'C' 'M' 'Y' 'K', 1..4 (YCCK), 0..n-1
+ *             (unknown); APP0 for YCbCr only, in the other mode's bytes; an Adobe APP14 segment (version 100, flags 0,
+ *             transform 0 / 0 / 2) for RGB, CMYK and YCCK; Huffman tables 1 for components 1 and 2 of YCbCr and YCCK,
+ *             tables 0 for everything else (jpeg_set_colorspace);
+ *           - each component keeps its sampling factors and its quantisation-table number: one DQT segment per table a
+ *             component names, in component order, Pq = 1 for a table with an entry above 255, and then SOF1 for SOF0;
+ *           - without `optimize` the Annex K tables the selectors name (DC 0 and AC 0 alone where no component selects
+ *             tables 1); with `optimize` one optimised table per class and selector in use;
+ *           - a dummy block (a block of an MCU beyond its component's real grid, in any component whose factors exceed 1)
+ *             of an item without orientation and crop keeps the source's values where a scan of the source codes it and
+ *             is zero where none does; of a mapped item it is the encoder's: 63 zeros and the DC of the block in front of
+ *             it among its component's blocks of the MCU;
+ *           - orientations 5..8 exchange the factors of EVERY component (4:2:2 becomes 4:4:0). The edge, trim and crop-origin
+ *             rules use the iMCU of the target, 8 h_max x 8 v_max, in place of luma's factors; 4:2:2 takes every orientation.
+ *           - `progressive`: SOF2. Three-component YCbCr keeps the ten scans of the other mode; every other case gets
+ *             jpeg_simple_progression's all-purpose script of 2 + 4 n scans: the DC of all components interleaved (Al 1); per
+ *             component AC 1-5 (Al 2), then AC 6-63 (Al 2), then AC 1-63 (Ah 2, Al 1); the DC refinement; per component
+ *             AC 1-63 (Ah 1, Al 0). A component's own scan runs over its real blocks; the first scan brings the DC tables
+ *             its components select, every AC scan one table under its component's selector. */
 struct jpeggpu_ext_transcode_item {
     jpeggpu_decoder_t decoder;
     void* d_tmp;
@@ -1113,6 +1145,11 @@ enum jpeggpu_status jpeggpu_ext_transcode_batch(
 enum jpeggpu_status jpeggpu_ext_batch_set_coefficients_only(jpeggpu_batch_t batch, int enable);
 enum jpeggpu_status jpeggpu_ext_set_transcode_orientation(jpeggpu_decoder_t decoder, int orientation, int trim);
 enum jpeggpu_status jpeggpu_ext_set_transcode_crop(jpeggpu_decoder_t decoder, int x, int y, int width, int height);
+enum jpeggpu_ext_transcode_frame {
+    JPEGGPU_EXT_TRANSCODE_FRAME_ENCODER = 0,
+    JPEGGPU_EXT_TRANSCODE_FRAME_SOURCE  = 1
+};
+enum jpeggpu_status jpeggpu_ext_set_transcode_frame(jpeggpu_decoder_t decoder, int mode);
 
 #ifdef __cplusplus
 }

@@ -320,6 +320,8 @@ def lib():
         L.jpeggpu_ext_set_transcode_orientation.argtypes = [dec, C.c_int, C.c_int]
     if hasattr(L, "jpeggpu_ext_set_transcode_crop"):
         L.jpeggpu_ext_set_transcode_crop.argtypes = [dec, C.c_int, C.c_int, C.c_int, C.c_int]
+    if hasattr(L, "jpeggpu_ext_set_transcode_frame"):
+        L.jpeggpu_ext_set_transcode_frame.argtypes = [dec, C.c_int]
     if hasattr(L, "jpeggpu_ext_encode_tables_from_counts"):
         L.jpeggpu_ext_encode_tables_from_counts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.jpeggpu_ext_resize_weights.argtypes = [
@@ -448,6 +450,11 @@ class Decoder:
         stored image of the new file is the displayed image under `orientation` (1..8); `trim` cuts partial iMCUs at a
         mirrored edge instead of refusing them. Decodes to pixels ignore it."""
         _check(_newer_symbol("jpeggpu_ext_set_transcode_orientation")(self._h, int(orientation), int(trim)), "jpeggpu_ext_set_transcode_orientation")
+
+    def set_transcode_frame(self, mode: int = 0):
+        """jpeggpu_ext_set_transcode_frame: 0 -- the transcode calls write the encoder's frame layouts and refuse every other
+        source; 1 -- the new file keeps the source's own layout (any sampling, up to four components and tables)."""
+        _check(_newer_symbol("jpeggpu_ext_set_transcode_frame")(self._h, int(mode)), "jpeggpu_ext_set_transcode_frame")
 
     def set_transcode_crop(self, x: int = 0, y: int = 0, w: int = 0, h: int = 0):
         """jpeggpu_ext_set_transcode_crop: the transcode calls write only the rectangle (x, y, w, h) of the image they would
@@ -1610,9 +1617,26 @@ def transcode_crop_rects(width, height, hs, vs, rect, orientation=1, trim=False,
     return (x, y, cw, ch), ((y0, x0, ch, cw) if o >= 5 else (x0, y0, cw, ch))
 
 
-def _luma_factors(info):
-    """(hs, vs) as the transcode counts iMCUs: luma's factors of a colour file, (1, 1) for grey."""
-    return (1, 1) if info.num_components == 1 else (info.subsampling.x[0], info.subsampling.y[0])
+def _luma_factors(info, frame="encoder"):
+    """(hs, vs) as the transcode counts iMCUs: luma's factors of a colour file, (1, 1) for grey; with frame="source" the
+    largest factors of the file's components."""
+    n = info.num_components
+    if n == 1:
+        return (1, 1)
+    if frame == "source":
+        return (max(info.subsampling.x[:n]), max(info.subsampling.y[:n]))
+    return (info.subsampling.x[0], info.subsampling.y[0])
+
+
+TRANSCODE_FRAMES = {"encoder": 0, "source": 1}
+
+
+def _transcode_frames(n, frame):
+    frames = _per_image(frame, n, "frame")
+    for f in frames:
+        if f not in TRANSCODE_FRAMES:
+            raise ValueError('frame must be "encoder" or "source"')
+    return frames
 
 
 def _transcode_crops(n, crops):
@@ -1630,19 +1654,22 @@ def _transcode_crops(n, crops):
     return [None if c is None else tuple(int(v) for v in c) for c in crops]
 
 
-def _transcode_items(bd, optimize, progressive, restart_interval, orientation=None, exif_transpose=False, trim=False, crops=None, expand=False):
+def _transcode_items(bd, optimize, progressive, restart_interval, orientation=None, exif_transpose=False, trim=False, crops=None, expand=False,
+                     frame="encoder"):
     """The items of a transcode call for the decoded files of a BatchDecode, without output slots; a source the writer cannot
     take raises JpegGpuError naming the item. Sets each decoder's transcode orientation (Decoder.set_transcode_orientation)
     and crop (Decoder.set_transcode_crop), which the calls on the items read."""
     n = len(bd.decoders)
     os_, ps_, rs = _per_image(optimize, n, "optimize"), _per_image(progressive, n, "progressive"), _per_image(restart_interval, n, "restart_interval")
-    crops, expands = _transcode_crops(n, crops), _per_image(expand, n, "expand")
+    crops, expands, frames = _transcode_crops(n, crops), _per_image(expand, n, "expand"), _transcode_frames(n, frame)
     for i, (dec, (o, t)) in enumerate(zip(bd.decoders, _transcode_orientations(bd, orientation, exif_transpose, trim))):
+        if frames[i] != "encoder" or hasattr(lib(), "jpeggpu_ext_set_transcode_frame"):
+            dec.set_transcode_frame(TRANSCODE_FRAMES[frames[i]])
         if o != 1 or t or hasattr(lib(), "jpeggpu_ext_set_transcode_orientation"):
             dec.set_transcode_orientation(o, t)
         rect = crops[i]
         if rect is not None and expands[i]:
-            hs, vs = _luma_factors(bd.infos[i])
+            hs, vs = _luma_factors(bd.infos[i], frames[i])
             ths, tvs = (vs, hs) if o >= 5 else (hs, vs)
             rect = _expanded(rect, ths, tvs)
         if rect is not None or hasattr(lib(), "jpeggpu_ext_set_transcode_crop"):
@@ -1665,18 +1692,18 @@ def _transcode_items(bd, optimize, progressive, restart_interval, orientation=No
 
 
 def transcode_into(bd, outs, optimize=False, progressive=False, restart_interval=None, items=None, orientation=None, exif_transpose=False, trim=False,
-                   crops=None, expand=False):
+                   crops=None, expand=False, frame="encoder"):
     """jpeggpu_ext_transcode_batch on torch's current stream, without synchronising, for the files of `bd`, a BatchDecode whose
     decode() was enqueued on the same stream: file i into the slot outs[i], as encode_into. Returns the device tensors
     (sizes int64[n], status int32[n]); status 1: the slot was too small, 2: as encode_into, 4: the source holds a
     coefficient that no Huffman code of the target expresses, and its size is 0. `items`: what _transcode_items made of the
-    same arguments, for a caller that has them already. `orientation`, `exif_transpose`, `trim`, `crops`, `expand`: as
+    same arguments, for a caller that has them already. `orientation`, `exif_transpose`, `trim`, `crops`, `expand`, `frame`: as
     transcode_jpeg's; `bd` decodes what its maker asked for -- whole files, or with BatchDecode(crops=) the source rectangles
     of transcode_crop_rects, which must hold what the items read."""
     import torch
 
     if items is None:
-        items = _transcode_items(bd, optimize, progressive, restart_interval, orientation, exif_transpose, trim, crops, expand)
+        items = _transcode_items(bd, optimize, progressive, restart_interval, orientation, exif_transpose, trim, crops, expand, frame)
     n = len(bd.decoders)
     if len(outs) != n:
         raise ValueError("outs must have one entry per file")
@@ -1698,18 +1725,19 @@ def transcode_into(bd, outs, optimize=False, progressive=False, restart_interval
     return result[:8 * n].view(torch.int64), result[8 * n:].view(torch.int32)
 
 
-def _transcode_windows(n, orientation, exif_transpose, trim, crops, expand):
+def _transcode_windows(n, orientation, exif_transpose, trim, crops, expand, frame="encoder"):
     """BatchDecode's crop_hooks for a cropped transcode: each cropped file decodes only the source rectangle of its crop
     (transcode_crop_rects). A rectangle the rules refuse sets no window: the item is then refused by the library, by name."""
     crops = _transcode_crops(n, crops)
     if not any(c is not None for c in crops):
         return None
     os_, es, ts, xs = _per_image(orientation, n, "orientation"), _per_image(exif_transpose, n, "exif_transpose"), _per_image(trim, n, "trim"), _per_image(expand, n, "expand")
+    frames = _transcode_frames(n, frame)
 
     def hook(i, dec, w, h):
         o = dec.orientation() if es[i] else 1 if os_[i] is None else int(os_[i])
         try:
-            return transcode_crop_rects(w, h, *_luma_factors(dec.info), crops[i], o, bool(ts[i]), bool(xs[i]))[1]
+            return transcode_crop_rects(w, h, *_luma_factors(dec.info, frames[i]), crops[i], o, bool(ts[i]), bool(xs[i]))[1]
         except ValueError:
             return None
 
@@ -1717,10 +1745,11 @@ def _transcode_windows(n, orientation, exif_transpose, trim, crops, expand):
 
 
 def transcode_jpeg_to_device(datas, optimize=False, progressive=False, restart_interval=None, device="cuda:0", capacities=None, orientation=None,
-                             exif_transpose=False, trim=False, crops=None, expand=False):
+                             exif_transpose=False, trim=False, crops=None, expand=False, frame="encoder"):
     """transcode_jpeg's files left on the device: (buffer, offsets, sizes) as encode_jpeg_to_device returns them.
     `capacities`: the slot sizes to start with (default: twice the source's length, a header and three bytes per block of the
-    TARGET for restart markers and their padding); if a file is larger, the call is repeated once with the sizes it reported."""
+    TARGET's MCUs for restart markers and their padding); if a file is larger, the call is repeated once with the sizes it
+    reported."""
     import torch
 
     datas = list(datas)
@@ -1728,9 +1757,10 @@ def transcode_jpeg_to_device(datas, optimize=False, progressive=False, restart_i
         return None, [], []
     _newer_symbol("jpeggpu_ext_transcode_batch")
     n = len(datas)
-    with BatchDecode(datas, device, coefficients_only=True, crop_hooks=_transcode_windows(n, orientation, exif_transpose, trim, crops, expand)) as bd:
+    with BatchDecode(datas, device, coefficients_only=True,
+                     crop_hooks=_transcode_windows(n, orientation, exif_transpose, trim, crops, expand, frame)) as bd:
         # (host only: refuses before anything is enqueued or allocated)
-        items = _transcode_items(bd, optimize, progressive, restart_interval, orientation, exif_transpose, trim, crops, expand)
+        items = _transcode_items(bd, optimize, progressive, restart_interval, orientation, exif_transpose, trim, crops, expand, frame)
         bd.decode()
         if capacities is None:
             caps = [2 * len(d) + 1024 + 3 * _transcode_blocks(items[i]) for i, d in enumerate(datas)]
@@ -1757,24 +1787,29 @@ def transcode_jpeg_to_device(datas, optimize=False, progressive=False, restart_i
 
 
 def _transcode_blocks(item):
-    """ceil(w / 8) * ceil(h / 8) of the file an item writes, read from the frame header the library gives it."""
-    size = C.c_size_t(1024)
-    head = (C.c_uint8 * 1024)()
+    """The blocks of the file an item writes, dummy ones included, read from the frame header the library gives it: per
+    component its blocks of an MCU times the MCUs (an encoder layout's luma: about ceil(w / 8) * ceil(h / 8) as before)."""
+    size = C.c_size_t(2048)  # (four DQTs of 16-bit entries and four DHTs: 1028 bytes)
+    head = (C.c_uint8 * 2048)()
     one = TranscodeItem()
     C.pointer(one)[0] = item
     one.optimize = one.progressive = 0
     _check(lib().jpeggpu_ext_transcode_header(C.byref(one), head, C.byref(size)), "jpeggpu_ext_transcode_header")
     head = bytes(head[:size.value])
-    at = 2 + 18  # SOI and APP0; then a DQT of 69 bytes per table, then SOF0: marker, length, precision, height, width
-    while head[at:at + 2] == b"\xff\xdb":
-        at += 69
-    assert head[at:at + 2] == b"\xff\xc0"
+    at = 2  # SOI; then APP0 or APP14 and the DQTs, then SOF0 or SOF1: marker, length, precision, height, width, components
+    while head[at + 1] not in (0xC0, 0xC1):
+        at += 2 + (head[at + 2] << 8 | head[at + 3])
     at += 5
-    return ((head[at] << 8 | head[at + 1]) + 7) // 8 * (((head[at + 2] << 8 | head[at + 3]) + 7) // 8)
+    height, width, ncomp = head[at] << 8 | head[at + 1], head[at + 2] << 8 | head[at + 3], head[at + 4]
+    if ncomp == 1 or (ncomp == 3 and head[at + 6] in (0x11, 0x21, 0x22) and head[at + 9] == head[at + 12] == 0x11):
+        return (height + 7) // 8 * ((width + 7) // 8)  # an encoder layout: luma's real blocks, as before
+    fs = [(head[at + 6 + 3 * c] >> 4, head[at + 6 + 3 * c] & 15) for c in range(ncomp)]
+    hmax, vmax = max(f[0] for f in fs), max(f[1] for f in fs)
+    return -(-width // (8 * hmax)) * -(-height // (8 * vmax)) * sum(f[0] * f[1] for f in fs)
 
 
 def transcode_jpeg(datas, optimize=False, progressive=False, restart_interval=None, device="cuda:0", orientation=None, exif_transpose=False, trim=False,
-                   crops=None, expand=False):
+                   crops=None, expand=False, frame="encoder"):
     """JPEG files from JPEG files without a pixel in between, as a list of bytes: what jpegtran -optimize, -progressive and
     -restart N do. Each file holds the source's quantised coefficients exactly, in the layout encode_jpeg writes (the
     source's quantisation tables; EXIF, ICC and comments are dropped). `optimize`, `progressive` as in encode_jpeg;
@@ -1786,7 +1821,14 @@ def transcode_jpeg(datas, optimize=False, progressive=False, restart_interval=No
     orientation number. `exif_transpose` (one value or one per file): each file's own Orientation tag is the number, which
     bakes the tag into the file (the result holds no Exif segment); naming both for a file is a ValueError. A mirrored edge
     must be a whole number of iMCUs of the source: otherwise the item raises JpegGpuError before anything is enqueued, or
-    with `trim` the partial iMCUs at that edge are cut off first, like jpegtran -trim. 4:2:2 takes 1..4 only.
+    with `trim` the partial iMCUs at that edge are cut off first, like jpegtran -trim. 4:2:2 takes 1..4 only, unless
+    frame="source".
+    `frame` ("encoder" | "source", one value or one per file): "source" keeps each source's own frame layout, as jpegtran
+    does, and so takes every file the decoder reads: any sampling factors (4:4:0, 4:1:1 ..), separate Cb and Cr tables, 16-bit
+    tables, RGB-coded, CMYK, YCCK and two-component files. The file then has the source's colour model, sampling factors and
+    table numbers; orientations 5..8 exchange the factors of every component (4:2:2 becomes 4:4:0), and the iMCU of the edge
+    and crop rules is 8 h_max x 8 v_max. A file the default takes gives the same bytes. `progressive` writes libjpeg's ten
+    scans for three-component YCbCr and its all-purpose script of 2 + 4 n scans for everything else (18 for CMYK).
     `crops`: one rectangle (x, y, w, h) or one per file (None: the whole image), cut out without loss like jpegtran -crop, in
     pixels of the image the call would write without it -- after `orientation` and `trim`, so in displayed pixels. x and y
     must be multiples of the target's iMCU (8 hs x 8 vs of luma's factors, exchanged for 5..8; 8 x 8 for grey), or with
@@ -1799,7 +1841,7 @@ def transcode_jpeg(datas, optimize=False, progressive=False, restart_interval=No
     import torch
 
     buf, offsets, sizes = transcode_jpeg_to_device(datas, optimize, progressive, restart_interval, device, None, orientation, exif_transpose, trim, crops,
-                                                   expand)
+                                                   expand, frame)
     if not sizes:
         return []
     host = torch.cat([buf[o:o + s] for o, s in zip(offsets, sizes)]).cpu().numpy().tobytes()

@@ -431,6 +431,13 @@ enum jpeggpu_status jpeggpu_ext_set_transcode_crop(jpeggpu_decoder_t decoder, in
     return JPEGGPU_SUCCESS;
 }
 
+enum jpeggpu_status jpeggpu_ext_set_transcode_frame(jpeggpu_decoder_t decoder, int mode)
+{
+    if (!decoder || (mode != JPEGGPU_EXT_TRANSCODE_FRAME_ENCODER && mode != JPEGGPU_EXT_TRANSCODE_FRAME_SOURCE)) return JPEGGPU_INVALID_ARGUMENT;
+    decoder->d.transcode_frame = mode;
+    return JPEGGPU_SUCCESS;
+}
+
 enum jpeggpu_status jpeggpu_ext_set_scale_mode(jpeggpu_decoder_t decoder, enum jpeggpu_ext_scale_mode mode)
 {
     if (!decoder) return JPEGGPU_INVALID_ARGUMENT;

@@ -147,6 +147,8 @@ struct Decoder {
     // jpeggpu_ext_set_transcode_crop: {x, y, width, height} in pixels of the image the transcode would write without it
     // (width 0: none), read by the same calls
     int transcode_crop[4] = {0, 0, 0, 0};
+    // jpeggpu_ext_set_transcode_frame: the new file keeps the source's frame layout (1) or must have the encoder's (0)
+    int transcode_frame = 0;
     int plane_x(int c) const { return crop.on ? crop.wx[c] : full_x(c); } // what decode writes
     int plane_y(int c) const { return crop.on ? crop.wy[c] : full_y(c); }
     JG_LOCAL bool set_crop_window();

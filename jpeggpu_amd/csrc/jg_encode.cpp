@@ -111,9 +111,12 @@ void quant_table(const uint8_t* base, int quality, uint8_t* q)
     }
 }
 
-bool valid(const jpeggpu_ext_encode_item* it)
+/// `spec`: a transcode item's, which may keep a frame of its own (TranscodeSpec::general) of up to four components.
+bool valid(const jpeggpu_ext_encode_item* it, const TranscodeSpec* spec = nullptr)
 {
-    return it && it->width >= 1 && it->width <= 65535 && it->height >= 1 && it->height <= 65535 && (it->channels == 1 || it->channels == 3) &&
+    const bool general = spec && spec->general;
+    return it && it->width >= 1 && it->width <= 65535 && it->height >= 1 && it->height <= 65535 &&
+           (general ? it->channels >= 1 && it->channels <= 4 : it->channels == 1 || it->channels == 3) &&
            it->quality >= 1 && it->quality <= 100 && it->subsampling >= JPEGGPU_EXT_SUBSAMPLING_444 && it->subsampling <= JPEGGPU_EXT_SUBSAMPLING_420 &&
            it->restart_interval >= 0 && it->restart_interval <= 65535 && (it->optimize == 0 || it->optimize == 1) &&
            (it->progressive == 0 || it->progressive == 1);
@@ -122,6 +125,7 @@ bool valid(const jpeggpu_ext_encode_item* it)
 struct Geometry {
     int hs, vs, mcus_x, mcus_y, blocks_per_mcu;
     uint64_t blocks, segments, stream_bound;
+    int slots;                                   // a progressive item's Huffman tables
     uint64_t scan_blocks, markers, marker_bytes; // a progressive item's: the blocks and restart markers of all its scans, DHTs + DRI + SOS at their longest
 };
 
@@ -130,10 +134,94 @@ const int kScriptRgb[10][5]  = {{-1, 0, 0, 0, 1}, {0, 1, 5, 0, 2},  {2, 1, 63, 0
                                 {0, 1, 63, 2, 1}, {-1, 0, 0, 1, 0}, {2, 1, 63, 1, 0}, {1, 1, 63, 1, 0}, {0, 1, 63, 1, 0}};
 const int kScriptGrey[6][5] = {{0, 0, 0, 0, 1}, {0, 1, 5, 0, 2}, {0, 6, 63, 0, 2}, {0, 1, 63, 2, 1}, {0, 0, 0, 1, 0}, {0, 1, 63, 1, 0}};
 
+/// prog_script for a transcode item that keeps its source's frame: three-component YCbCr keeps the ten scans, a single
+/// component the six, everything else gets jpeg_simple_progression's all-purpose script -- DC of all components interleaved
+/// (Al 1); per component AC 1-5 (Al 2), AC 6-63 (Al 2), AC 1-63 (Ah 2, Al 1); the DC refinement; per component AC 1-63
+/// (Ah 1, Al 0). A component's scan runs over its real grid, its tables follow its selector.
+uint64_t general_prog_script(const jpeggpu_ext_encode_item& it, const Geometry& g, ProgItem& pi, uint64_t* scan_blocks, uint64_t* markers, uint64_t* marker_bytes,
+                             const TranscodeSpec& spec)
+{
+    const Frame& f  = spec.frame;
+    const int ncomp = it.channels;
+    int script[kProgScans][5], n_scans = 0;
+    const auto add = [&](int comp, int ss, int se, int ah, int al) {
+        const int row[5] = {comp, ss, se, ah, al};
+        std::memcpy(script[n_scans++], row, sizeof row);
+    };
+    if (ncomp == 1) {
+        std::memcpy(script, kScriptGrey, sizeof kScriptGrey), n_scans = 6;
+    } else if (ncomp == 3 && spec.color_space == JPEGGPU_EXT_COLOR_YCBCR) {
+        std::memcpy(script, kScriptRgb, sizeof kScriptRgb), n_scans = 10;
+    } else {
+        add(-1, 0, 0, 0, 1);
+        for (int c = 0; c < ncomp; ++c) add(c, 1, 5, 0, 2);
+        for (int c = 0; c < ncomp; ++c) add(c, 6, 63, 0, 2);
+        for (int c = 0; c < ncomp; ++c) add(c, 1, 63, 2, 1);
+        add(-1, 0, 0, 1, 0);
+        for (int c = 0; c < ncomp; ++c) add(c, 1, 63, 1, 0);
+    }
+    int k0[4] = {0, 0, 0, 0}, ch[4], cv[4];
+    for (int c = 0, at = 0; c < ncomp; ++c) {
+        ch[c] = f.hv >> (8 * c) & 15, cv[c] = f.hv >> (8 * c + 4) & 15;
+        k0[c] = at;
+        at += ch[c] * cv[c];
+    }
+    const uint64_t mcus = uint64_t(g.mcus_x) * g.mcus_y;
+    pi         = ProgItem{};
+    pi.scans_n = uint32_t(n_scans);
+    uint64_t first = 0, marks = 0, bound = 0;
+    int slot = 0;
+    *marker_bytes = 0;
+    for (int s = 0; s < n_scans; ++s) {
+        const int* row = script[s];
+        ProgScan& sc   = pi.scans[s];
+        sc.comp = row[0], sc.ss = row[1], sc.se = row[2], sc.ah = row[3], sc.al = row[4];
+        const int c           = sc.comp < 0 ? 0 : sc.comp;
+        const uint64_t blocks = sc.comp < 0 ? g.blocks : uint64_t(f.grid_w[c]) * f.grid_h[c];
+        const uint64_t units  = sc.comp < 0 ? mcus : blocks;
+        const uint64_t segs   = it.restart_interval ? (units + it.restart_interval - 1) / it.restart_interval : 1;
+        sc.blocks = int(blocks), sc.blocks_x = f.grid_w[c];
+        sc.h = ch[c], sc.v = cv[c], sc.k0 = k0[c];
+        sc.first = uint32_t(first), sc.marks_before = uint32_t(marks);
+        const bool two = f.select != 0; // the DC scan brings the tables its components select
+        sc.tables = sc.ss == 0 ? (sc.ah ? 0 : sc.comp < 0 && two ? 2 : 1) : 1;
+        sc.slot   = sc.tables ? slot : -1;
+        for (int t = 0; t < sc.tables; ++t) pi.slot_class_id[slot++] = uint8_t(sc.ss == 0 ? t : 0x10 | spec.comp[c].select);
+        const int band = sc.se - sc.ss + 1;
+        const int bits = sc.ss == 0 ? (sc.ah ? kProgDcRefineBits : kProgDcFirstBits) : sc.ah ? prog_ac_refine_bits(band) : prog_ac_first_bits(band);
+        bound += (blocks * uint64_t(bits) + 7) / 8 + segs;
+        first += blocks;
+        marks += segs - 1;
+        uint32_t n = 0;
+        if (s == 0 && it.restart_interval) {
+            const uint8_t dri[6] = {0xFF, 0xDD, 0, 4, uint8_t(it.restart_interval >> 8), uint8_t(it.restart_interval)};
+            std::memcpy(sc.sos, dri, 6);
+            n = 6;
+        }
+        const int ns = sc.comp < 0 ? ncomp : 1;
+        sc.sos[n++] = 0xFF, sc.sos[n++] = 0xDA, sc.sos[n++] = 0, sc.sos[n++] = uint8_t(6 + 2 * ns), sc.sos[n++] = uint8_t(ns);
+        for (int a = 0; a < ns; ++a) {
+            const int comp = sc.comp < 0 ? a : sc.comp;
+            const int sel  = spec.comp[comp].select;
+            sc.sos[n++]    = spec.comp[comp].id;
+            sc.sos[n++]    = uint8_t(sc.ss == 0 ? (sc.ah == 0 ? sel << 4 : 0x00) : sel);
+        }
+        sc.sos[n++] = uint8_t(sc.ss), sc.sos[n++] = uint8_t(sc.se), sc.sos[n++] = uint8_t(sc.ah << 4 | sc.al);
+        sc.sos_len  = n;
+        *marker_bytes += uint64_t(sc.tables) * 277 + n;
+    }
+    pi.slots_n   = uint32_t(slot);
+    *scan_blocks = first;
+    *markers     = marks;
+    return bound;
+}
+
 /// The scans of a progressive item, the tables they bring and their headers; returns the bound of its unstuffed stream:
 /// per scan its blocks at their most bits (jg_encode_prog.hpp) and less than a byte of padding ones per restart segment.
-uint64_t prog_script(const jpeggpu_ext_encode_item& it, const Geometry& g, ProgItem& pi, uint64_t* scan_blocks, uint64_t* markers, uint64_t* marker_bytes)
+uint64_t prog_script(const jpeggpu_ext_encode_item& it, const Geometry& g, ProgItem& pi, uint64_t* scan_blocks, uint64_t* markers, uint64_t* marker_bytes,
+                     const TranscodeSpec* spec = nullptr)
 {
+    if (spec && spec->general) return general_prog_script(it, g, pi, scan_blocks, markers, marker_bytes, *spec);
     const bool grey  = it.channels == 1;
     const int grid_w = (it.width + 7) / 8, grid_h = (it.height + 7) / 8;
     const uint64_t mcus = uint64_t(g.mcus_x) * g.mcus_y;
@@ -184,7 +272,7 @@ uint64_t prog_script(const jpeggpu_ext_encode_item& it, const Geometry& g, ProgI
     *markers     = marks;
     return bound;
 }
-Geometry geometry(const jpeggpu_ext_encode_item& it)
+Geometry geometry(const jpeggpu_ext_encode_item& it, const TranscodeSpec* spec = nullptr)
 {
     Geometry g;
     const bool grey = it.channels == 1;
@@ -193,15 +281,29 @@ Geometry geometry(const jpeggpu_ext_encode_item& it)
     g.mcus_x        = (it.width + 8 * g.hs - 1) / (8 * g.hs);
     g.mcus_y        = (it.height + 8 * g.vs - 1) / (8 * g.vs);
     g.blocks_per_mcu = grey ? 1 : g.hs * g.vs + 2;
+    if (spec && spec->general) { // the iMCU of the largest factors (a single component's MCU is one block); hs 0 marks the item
+        int hmax = 1, vmax = 1;
+        g.blocks_per_mcu = 0;
+        for (int c = 0; c < it.channels; ++c) {
+            const int h = spec->frame.hv >> (8 * c) & 15, v = spec->frame.hv >> (8 * c + 4) & 15;
+            hmax = h > hmax ? h : hmax, vmax = v > vmax ? v : vmax;
+            g.blocks_per_mcu += h * v;
+        }
+        g.mcus_x = (it.width + 8 * hmax - 1) / (8 * hmax);
+        g.mcus_y = (it.height + 8 * vmax - 1) / (8 * vmax);
+        g.hs = g.vs = 0;
+    }
     const uint64_t mcus = uint64_t(g.mcus_x) * g.mcus_y;
     g.blocks        = mcus * g.blocks_per_mcu;
     g.segments      = it.restart_interval ? (mcus + it.restart_interval - 1) / it.restart_interval : 1;
     // every block at kMaxBlockBits (optimised tables: a DC code of 16 bits), and less than a byte of padding ones per segment
     g.stream_bound = (g.blocks * (it.optimize ? kMaxBlockBitsOptimized : kMaxBlockBits) + 7) / 8 + g.segments;
     g.scan_blocks = g.markers = g.marker_bytes = 0;
+    g.slots       = 0;
     if (it.progressive) {
         ProgItem pi;
-        g.stream_bound = prog_script(it, g, pi, &g.scan_blocks, &g.markers, &g.marker_bytes);
+        g.stream_bound = prog_script(it, g, pi, &g.scan_blocks, &g.markers, &g.marker_bytes, spec);
+        g.slots        = int(pi.slots_n);
     }
     return g;
 }
@@ -215,11 +317,48 @@ void put_segment(std::vector<uint8_t>& out, int marker, const uint8_t* payload, 
     out.insert(out.end(), payload, payload + len);
 }
 
+/// SOI .. SOFn of a transcode item that keeps its source's frame (jpeggpu_ext.h: jpeggpu_ext_set_transcode_frame).
+void write_general_prefix(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out, const TranscodeSpec& spec)
+{
+    out.clear();
+    out.push_back(0xFF);
+    out.push_back(0xD8);
+    const int cs = spec.color_space;
+    if (cs == JPEGGPU_EXT_COLOR_GRAY || cs == JPEGGPU_EXT_COLOR_YCBCR) {
+        static const uint8_t jfif[14] = {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+        put_segment(out, 0xE0, jfif, sizeof jfif);
+    } else if (cs == JPEGGPU_EXT_COLOR_RGB || cs == JPEGGPU_EXT_COLOR_CMYK || cs == JPEGGPU_EXT_COLOR_YCCK) {
+        const uint8_t adobe[12] = {'A', 'd', 'o', 'b', 'e', 0, 100, 0, 0, 0, 0, uint8_t(cs == JPEGGPU_EXT_COLOR_YCCK ? 2 : 0)};
+        put_segment(out, 0xEE, adobe, sizeof adobe);
+    }
+    bool sof1 = false;
+    for (int t = 0; t < spec.tables_n; ++t) {
+        uint8_t seg[1 + 128];
+        size_t n = 0;
+        seg[n++] = uint8_t((spec.table16[t] ? 0x10 : 0) | spec.table_id[t]);
+        for (int k = 0; k < 64; ++k) {
+            if (spec.table16[t]) seg[n++] = uint8_t(spec.table[t][k] >> 8);
+            seg[n++] = uint8_t(spec.table[t][k]);
+        }
+        put_segment(out, 0xDB, seg, n);
+        sof1 |= spec.table16[t];
+    }
+    const int ncomp     = it.channels;
+    uint8_t sof[6 + 12] = {8, uint8_t(it.height >> 8), uint8_t(it.height), uint8_t(it.width >> 8), uint8_t(it.width), uint8_t(ncomp)};
+    for (int c = 0; c < ncomp; ++c) {
+        sof[6 + 3 * c] = spec.comp[c].id;
+        sof[7 + 3 * c] = uint8_t(spec.comp[c].h << 4 | spec.comp[c].v);
+        sof[8 + 3 * c] = spec.comp[c].tq;
+    }
+    put_segment(out, it.progressive ? 0xC2 : sof1 ? 0xC1 : 0xC0, sof, size_t(6 + 3 * ncomp));
+}
+
 /// The header as libjpeg writes it for Pillow, in the three parts an item with optimised tables needs: SOI .. SOF0 (the
 /// prefix), the DHTs, which for such an item the device writes, and DRI if any and SOS (the suffix).
 /// `spec`: a transcode item's -- the source's quantisation tables and the sampling byte of its first component.
 void write_prefix(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out, const TranscodeSpec* spec = nullptr)
 {
+    if (spec && spec->general) return write_general_prefix(it, out, *spec);
     const int ncomp = it.channels;
     // the factors that were asked for go into the frame header of a grey file too (Pillow sets them whatever the mode); with
     // one component they change nothing else
@@ -245,12 +384,13 @@ void write_prefix(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out, 
     put_segment(out, it.progressive ? 0xC2 : 0xC0, sof, size_t(6 + 3 * ncomp));
 }
 
-void write_standard_dhts(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out)
+void write_standard_dhts(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out, const TranscodeSpec* spec = nullptr)
 {
     const int ncomp          = it.channels;
     const HuffSpec* specs[4] = {&kDcLuma, &kAcLuma, &kDcChroma, &kAcChroma};
     const uint8_t ids[4]     = {0x00, 0x10, 0x01, 0x11};
-    for (int t = 0; t < (ncomp == 1 ? 2 : 4); ++t) {
+    const bool one           = spec && spec->general ? spec->frame.select == 0 : ncomp == 1; // no component selects tables 1
+    for (int t = 0; t < (one ? 2 : 4); ++t) {
         uint8_t seg[1 + 16 + 162];
         seg[0] = ids[t];
         std::memcpy(seg + 1, specs[t]->bits, 16);
@@ -259,17 +399,18 @@ void write_standard_dhts(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>
     }
 }
 
-void write_suffix(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out)
+void write_suffix(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out, const TranscodeSpec* spec = nullptr)
 {
     const int ncomp = it.channels;
     if (it.restart_interval) {
         const uint8_t dri[2] = {uint8_t(it.restart_interval >> 8), uint8_t(it.restart_interval)};
         put_segment(out, 0xDD, dri, 2);
     }
-    uint8_t sos[1 + 6 + 3] = {uint8_t(ncomp)};
+    uint8_t sos[1 + 8 + 3] = {uint8_t(ncomp)};
     for (int c = 0; c < ncomp; ++c) {
         sos[1 + 2 * c] = uint8_t(c + 1);
         sos[2 + 2 * c] = uint8_t(c == 0 ? 0x00 : 0x11);
+        if (spec && spec->general) sos[1 + 2 * c] = spec->comp[c].id, sos[2 + 2 * c] = uint8_t(spec->comp[c].select ? 0x11 : 0x00);
     }
     sos[1 + 2 * ncomp] = 0x00, sos[2 + 2 * ncomp] = 0x3F, sos[3 + 2 * ncomp] = 0x00;
     put_segment(out, 0xDA, sos, size_t(4 + 2 * ncomp));
@@ -280,8 +421,8 @@ void write_suffix(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out)
 void write_header(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out, const TranscodeSpec* spec = nullptr)
 {
     write_prefix(it, out, spec);
-    write_standard_dhts(it, out);
-    write_suffix(it, out);
+    write_standard_dhts(it, out, spec);
+    write_suffix(it, out, spec);
 }
 
 /// The plan of a call: every offset in d_scratch. JPEGGPU_NOT_SUPPORTED for an item or a call beyond the kernels' 32-bit
@@ -306,12 +447,13 @@ jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan
     plan.oriented  = 0;
     for (int i = 0; i < n; ++i) {
         if (specs && specs[i].src.oriented) ++plan.oriented;
-        if (!valid(&items[i])) return JPEGGPU_INVALID_ARGUMENT;
-        geo[i] = geometry(items[i]);
+        if (!valid(&items[i], specs ? specs + i : nullptr)) return JPEGGPU_INVALID_ARGUMENT;
+        geo[i] = geometry(items[i], specs ? specs + i : nullptr);
         if (geo[i].stream_bound * 8 >= (uint64_t(1) << 32)) return JPEGGPU_NOT_SUPPORTED;
         tiles += (geo[i].blocks + kTileBlocks - 1) / kTileBlocks;
         if (items[i].progressive) { // no header and no chunks among the call's: its stream lies in the progressive spaces
             ++plan.prog.n;
+            plan.prog.slots = geo[i].slots > plan.prog.slots ? geo[i].slots : plan.prog.slots;
             prog_tiles += (geo[i].scan_blocks + kTileBlocks - 1) / kTileBlocks;
             prog_chunks += (geo[i].stream_bound + kChunkBytes - 1) / kChunkBytes;
             header.clear();
@@ -322,18 +464,22 @@ jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan
         if (items[i].optimize) {
             ++plan.optimized;
             header.assign(sizeof(OptState), 0);
+            if (specs && specs[i].general) header.resize(sizeof(OptState) + size_t(kLongPrefixBytes)); // (planned at its longest)
             if (headers) {
+                header.resize(sizeof(OptState));
                 OptState st{}; // (counts, lengths and statuses zero: the device adds to them)
                 write_prefix(items[i], part, specs ? specs + i : nullptr);
-                if (part.size() > sizeof st.prefix) return JPEGGPU_INTERNAL_ERROR;
+                if (part.size() > size_t(kLongPrefixBytes)) return JPEGGPU_INTERNAL_ERROR;
                 st.prefix_len = uint32_t(part.size());
-                std::memcpy(st.prefix, part.data(), part.size());
+                if (long_prefix(st.prefix_len)) header.insert(header.end(), part.begin(), part.end()); // behind the state
+                else std::memcpy(st.prefix, part.data(), part.size());
                 part.clear();
-                write_suffix(items[i], part);
+                write_suffix(items[i], part, specs ? specs + i : nullptr);
                 if (part.size() > sizeof st.suffix) return JPEGGPU_INTERNAL_ERROR;
                 st.suffix_len = uint32_t(part.size());
                 std::memcpy(st.suffix, part.data(), part.size());
                 std::memcpy(header.data(), &st, sizeof st);
+                if (specs && specs[i].general) header.resize(sizeof(OptState) + size_t(kLongPrefixBytes));
             }
         } else {
             write_header(items[i], header, specs ? specs + i : nullptr);
@@ -405,6 +551,11 @@ jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan
                 quant_table(t ? kBaseChroma : kBaseLuma, s.quality, q);
                 for (int k = 0; k < 64; ++k) d.divisor[t][k] = uint16_t(8 * q[kNatural[k]]);
             }
+            if (specs && specs[i].general) { // nothing is quantised: the frame lies in the divisors' place
+                std::memset(d.divisor, 0, sizeof d.divisor);
+                d.frame  = specs[i].frame;
+                d.grid_w = d.frame.grid_w[0], d.grid_h = d.frame.grid_h[0];
+            }
             header_off += align_up((*headers)[i].size(), 16);
             if (progressive && prog) {
                 Item sh        = d;
@@ -413,7 +564,7 @@ jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan
                 prog->shadow.push_back(sh);
                 ProgItem pi;
                 uint64_t a, b, c;
-                prog_script(s, g, pi, &a, &b, &c);
+                prog_script(s, g, pi, &a, &b, &c, specs ? specs + i : nullptr);
                 pi.work_off = work;
                 pi.item     = uint32_t(i);
                 std::vector<uint8_t> prefix;
@@ -475,7 +626,7 @@ extern "C" {
 
 static jpeggpu_status header_of(const jpeggpu_ext_encode_item* item, const TranscodeSpec* spec, uint8_t* host_buf, size_t* size)
 {
-    if (!valid(item) || !size) return JPEGGPU_INVALID_ARGUMENT;
+    if (!valid(item, spec) || !size) return JPEGGPU_INVALID_ARGUMENT;
     std::vector<uint8_t> header;
     try {
         write_header(*item, header, spec);
@@ -486,7 +637,7 @@ static jpeggpu_status header_of(const jpeggpu_ext_encode_item* item, const Trans
     *size             = header.size();
     if (item->progressive) { // every scan brings its tables: SOI .. SOF2 and what the scans' marker segments can take at most
         write_prefix(*item, header, spec);
-        *size = header.size() + size_t(geometry(*item).marker_bytes);
+        *size = header.size() + size_t(geometry(*item, spec).marker_bytes);
         return JPEGGPU_NOT_SUPPORTED;
     }
     if (item->optimize) return JPEGGPU_NOT_SUPPORTED; // its DHTs depend on the pixels; no header is longer than this one
@@ -501,17 +652,19 @@ enum jpeggpu_status jpeggpu_ext_encode_header(const struct jpeggpu_ext_encode_it
     return header_of(item, nullptr, host_buf, size);
 }
 
-size_t jpeggpu_ext_encode_bound(const struct jpeggpu_ext_encode_item* item)
+static size_t bound_of(const jpeggpu_ext_encode_item* item, const TranscodeSpec* spec)
 {
-    if (!valid(item)) return 0;
+    if (!valid(item, spec)) return 0;
     (void)tables(); // checks kMaxBlockBits against the tables
-    const Geometry g = geometry(*item);
+    const Geometry g = geometry(*item, spec);
     size_t header    = 0;
-    const jpeggpu_status st = jpeggpu_ext_encode_header(item, nullptr, &header);
+    const jpeggpu_status st = header_of(item, spec, nullptr, &header);
     if (st != JPEGGPU_SUCCESS && !((item->optimize || item->progressive) && st == JPEGGPU_NOT_SUPPORTED)) return 0;
     // the header; the stream with every byte 0xFF and stuffed; a marker between segments (of every scan); EOI
     return header + 2 * size_t(g.stream_bound) + 2 * size_t(item->progressive ? g.markers : g.segments - 1) + 2;
 }
+
+size_t jpeggpu_ext_encode_bound(const struct jpeggpu_ext_encode_item* item) { return bound_of(item, nullptr); }
 
 size_t jpeggpu_ext_encode_scratch_size(const struct jpeggpu_ext_encode_item* items, int n)
 {
@@ -530,7 +683,7 @@ static jpeggpu_status batch_of(const jpeggpu_ext_encode_item* items, const Trans
 {
     if (!items || n <= 0 || !d_scratch || !d_sizes || !d_status) return JPEGGPU_INVALID_ARGUMENT;
     for (int i = 0; i < n; ++i)
-        if (!valid(&items[i]) || (!specs && !items[i].data) || (!items[i].out && items[i].capacity)) return JPEGGPU_INVALID_ARGUMENT;
+        if (!valid(&items[i], specs ? specs + i : nullptr) || (!specs && !items[i].data) || (!items[i].out && items[i].capacity)) return JPEGGPU_INVALID_ARGUMENT;
     Plan plan;
     std::vector<Item> dev;
     std::vector<std::vector<uint8_t>> headers;
@@ -611,7 +764,7 @@ size_t jpeggpu_ext_transcode_bound(const struct jpeggpu_ext_transcode_item* item
 {
     TranscodeSpec spec;
     if (!item || transcode_spec(*item, false, spec) != JPEGGPU_SUCCESS) return 0;
-    return jpeggpu_ext_encode_bound(&spec.item); // (the header's length does not depend on what its tables hold)
+    return bound_of(&spec.item, spec.general ? &spec : nullptr); // (an encoder layout's header is as long whatever its tables hold)
 }
 
 size_t jpeggpu_ext_transcode_scratch_size(const struct jpeggpu_ext_transcode_item* items, int n)

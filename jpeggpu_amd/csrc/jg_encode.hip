@@ -257,6 +257,14 @@ __device__ inline BlockPlace place_of(const Item& it, int b)
     const int luma       = it.hs * it.vs;
     p.segment_first      = first_mcu && p.j == 0;
     p.segment_last       = b == it.blocks - 1 || (ri && p.j == it.blocks_per_mcu - 1 && (p.mcu + 1) % ri == 0);
+    if (it.hs == 0) { // the item's own frame (jg_encode.hpp: Frame): the block's entry of the two maps, shifted out of uniform words
+        const uint32_t m = uint32_t(it.frame.map >> (6 * p.j)) & 63u;
+        p.table          = it.frame.select >> (m & 3u) & 1;
+        // behind the first block of its component in the MCU the block in front is the component's; the first one follows
+        // the component's last block of the MCU in front
+        p.pred_block = m >> 2 ? b - 1 : first_mcu ? -1 : b - it.blocks_per_mcu + (int(it.frame.last >> (4 * p.j)) & 15);
+        return p;
+    }
     p.table              = p.j >= luma;
     if (p.j < luma && p.j > 0) p.pred_block = b - 1;
     else if (first_mcu) p.pred_block = -1;
@@ -615,7 +623,7 @@ __global__ __launch_bounds__(64) void build_tables(const Item* __restrict__ item
     __shared__ TableLds lds;
     const Item& it = items[blockIdx.x >> 2];
     const int t    = blockIdx.x & 3; // DC0, AC0, DC1, AC1
-    if (!optimized(it) || (it.channels == 1 && t >= 2)) return;
+    if (!optimized(it) || ((it.hs ? it.channels == 1 : it.frame.select == 0) && t >= 2)) return; // no block is coded with tables 1
     OptState* st    = opt_state(it, scratch);
     OptWork* work   = reinterpret_cast<OptWork*>(scratch + st->work_off);
     const int table = t >> 1, ac = t & 1;
@@ -632,11 +640,11 @@ __global__ __launch_bounds__(64) void build_tables(const Item* __restrict__ item
 }
 
 /// One wave per progressive item and table: the table of a scan from the counts prog_symbols made, its codes and its DHT.
-__global__ __launch_bounds__(64) void build_prog_tables(const ProgItem* __restrict__ pitems, uint8_t* __restrict__ scratch)
+__global__ __launch_bounds__(64) void build_prog_tables(const ProgItem* __restrict__ pitems, uint8_t* __restrict__ scratch, int slots)
 {
     __shared__ TableLds lds;
-    const ProgItem& pi = pitems[blockIdx.x / kProgSlots];
-    const int slot     = blockIdx.x % kProgSlots;
+    const ProgItem& pi = pitems[blockIdx.x / slots]; // `slots`: the most tables an item of the call has (ProgPlan::slots)
+    const int slot     = blockIdx.x % slots;
     if (slot >= int(pi.slots_n)) return;
     ProgWork* work   = reinterpret_cast<ProgWork*>(scratch + pi.work_off);
     const int ac     = pi.slot_class_id[slot] >> 4;
@@ -795,7 +803,8 @@ __global__ __launch_bounds__(256) void write_files(
             if (st) {
                 const OptWork* work = reinterpret_cast<const OptWork*>(scratch + st->work_off);
                 uint32_t at         = st->prefix_len;
-                for (uint32_t k = threadIdx.x; k < st->prefix_len; k += 256) out[k] = st->prefix[k];
+                const uint8_t* prefix = long_prefix(st->prefix_len) ? reinterpret_cast<const uint8_t*>(st + 1) : st->prefix; // (a long one: behind the state)
+                for (uint32_t k = threadIdx.x; k < st->prefix_len; k += 256) out[k] = prefix[k];
                 for (int t = 0; t < 4; ++t) {
                     for (uint32_t k = threadIdx.x; k < st->dht_len[t]; k += 256) out[at + k] = work->dht[t][k];
                     at += st->dht_len[t];
@@ -863,14 +872,28 @@ __device__ inline SrcBlock src_block(const Item& it, const GatherSrc& src, int b
     const int my = mcu / it.mcus_x, mx = mcu - my * it.mcus_x;
     const int luma = it.hs * it.vs;
     SrcBlock sb{0, mx, my, false};
-    if (j >= luma) {
+    if (it.hs == 0) { // the item's own frame: every component has h x v blocks in the MCU, and dummy blocks where they exceed 1
+        const uint32_t m = uint32_t(it.frame.map >> (6 * j)) & 63u;
+        const int xo = m >> 2 & 3u, yo = m >> 4;
+        sb.comp     = m & 3u;
+        const int h = it.frame.hv >> (8 * sb.comp) & 15u, v = it.frame.hv >> (8 * sb.comp + 4) & 15u;
+        sb.bx = mx * h + xo, sb.by = my * v + yo;
+        if (!kOriented || !src.oriented) return sb;
+        // the MCU's real blocks of the component are rx x ry from its first one on; the block in front of a dummy one, and
+        // of that one, in the MCU's order ends at the last real block of the row, or of the last real row
+        const int rx = min(h, it.frame.grid_w[sb.comp] - mx * h), ry = min(v, it.frame.grid_h[sb.comp] - my * v);
+        if (xo >= rx || yo >= ry) {
+            sb.dummy = true;
+            sb.bx = mx * h + rx - 1, sb.by = my * v + min(yo, ry - 1);
+        }
+    } else if (j >= luma) {
         sb.comp = 1 + j - luma;
     } else {
         const int yo = j / it.hs;
         sb.bx = mx * it.hs + j - yo * it.hs, sb.by = my * it.vs + yo;
     }
     if (!kOriented || !src.oriented) return sb;
-    if (sb.comp == 0) {
+    if (sb.comp == 0 && it.hs) {
         if (sb.by >= it.grid_h) {
             sb.dummy = true;
             sb.by -= 1;
@@ -1104,7 +1127,8 @@ hipError_t launch_encode(const Plan& plan, uint8_t* d_scratch, unsigned long lon
 
 hipError_t launch_prog_tables(const Plan& plan, uint8_t* d_scratch, hipStream_t stream)
 {
-    build_prog_tables<<<uint32_t(plan.prog.n) * uint32_t(kProgSlots), 64, 0, stream>>>(reinterpret_cast<const ProgItem*>(d_scratch + plan.prog.items_off), d_scratch);
+    build_prog_tables<<<uint32_t(plan.prog.n) * uint32_t(plan.prog.slots), 64, 0, stream>>>(reinterpret_cast<const ProgItem*>(d_scratch + plan.prog.items_off), d_scratch,
+                                                                                           plan.prog.slots);
     return hipGetLastError();
 }
 

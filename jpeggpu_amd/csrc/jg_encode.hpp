@@ -43,6 +43,21 @@ struct Count {
     uint32_t reset, ff, starts;
 };
 
+/// The frame of a transcode item that keeps its source's layout (jpeggpu_ext_set_transcode_frame), where the pixel encoder's
+/// three layouts do not describe it: Item::hs == 0 marks such an item, and the description lies where a pixel item keeps its
+/// divisors, so sizeof(Item) stays what it is. Components' blocks follow each other in the MCU, each component's row by row.
+/// The two maps are whole 64-bit words: a uniform load reaches them, and a lane shifts out the entry of its block.
+struct Frame {
+    uint64_t map;        // 6 bits per block of the MCU: component | xo << 2 | yo << 4 (the block's place among its component's)
+    uint64_t last;       // 4 bits per block of the MCU: the blocks of its component in an MCU, less one
+    uint32_t hv;         // 8 bits per component: h | v << 4
+    uint8_t ncomp;
+    uint8_t select;      // bit c: component c is coded with Huffman tables 1 (else tables 0)
+    uint8_t pad[2];
+    int32_t grid_w[4], grid_h[4]; // each component's real blocks: beyond them a block of an MCU is a dummy
+};
+constexpr int kMaxMcuBlocks = 10;
+
 /// One image of a call, as the kernels see it.
 struct Item {
     const uint8_t* src;
@@ -53,14 +68,17 @@ struct Item {
     uint64_t stream_off; // the unstuffed stream, chunks * kChunkBytes, zeroed up to its length by the device
     uint64_t starts_off; // one bit per byte of the unstuffed stream: a restart segment begins here
     int width, height, channels;
-    int hs, vs;           // luma blocks per MCU, 1 x 1 for grey
+    int hs, vs;           // luma blocks per MCU, 1 x 1 for grey; 0, 0: the layout is `frame`'s
     int mcus_x, mcus_y;
     int blocks_per_mcu, blocks;
     int grid_w, grid_h;   // the luma component's real blocks: beyond them a block of an MCU is a dummy
     int restart_interval; // MCUs, 0: none
     uint32_t tile_start, chunk_start; // this item's first tile / chunk among the call's
     uint32_t header_off, header_len;  // in the blob. header_len 0: an item with optimised tables, header_off its OptState
-    uint16_t divisor[2][64];          // 8 * quantiser, zigzag order: luma, chroma
+    union {
+        uint16_t divisor[2][64];      // 8 * quantiser, zigzag order: luma, chroma
+        Frame frame;                  // hs == 0 (a transcode item: nothing is quantised)
+    };
 };
 
 /// Encoder tables in the blob: code << 8 | length, index = table * 256 + symbol (DC: the category), tables luma, chroma.
@@ -74,7 +92,7 @@ constexpr int kDcSymbols    = 16;
 constexpr int kTableCounts  = kDcSymbols + 256;
 constexpr int kDhtBytes     = 280; // a DHT segment of 256 values: marker and length (4), class / id, 16 bits, the values: 277
 constexpr int kPrefixBytes  = 192; // SOI, APP0, two DQTs, SOF0 of three components: 177
-constexpr int kSuffixBytes  = 32;  // DRI, SOS of three components: 20
+constexpr int kSuffixBytes  = 32;  // DRI, SOS of three components: 20; of four: 22
 /// What the device makes for an item with optimised tables, outside the blob: its own Tables and its DHT segments
 /// (DC0, AC0, DC1, AC1; a grey item has the first two), each as it stands in the file.
 struct OptWork {
@@ -89,9 +107,15 @@ struct OptState {
     uint32_t table_status[4];         // jpeggpu_ext_encode_status of each table: 0, or 2 (a code length above 32)
     uint32_t prefix_len, suffix_len;
     uint64_t work_off;                // OptWork, in d_scratch
-    uint8_t prefix[kPrefixBytes];     // SOI .. SOF0
+    uint8_t prefix[kPrefixBytes];     // SOI .. SOF0; a prefix_len above kPrefixBytes (a `frame` item: up to four DQTs of
+                                      // 16-bit entries) lies in the blob behind this struct instead
     uint8_t suffix[kSuffixBytes];     // DRI if any, SOS
 };
+/// The longest SOI .. SOFn: APP0, four DQTs of 16-bit entries, four components.
+constexpr int kLongPrefixBytes = 2 + 18 + 4 * 133 + 22;
+/// Where an item's prefix lies: host (make_plan) and device (write_files) go through this one rule.
+constexpr bool long_prefix(uint32_t prefix_len) { return prefix_len > uint32_t(kPrefixBytes); }
+static_assert(kLongPrefixBytes > kPrefixBytes && kSuffixBytes >= 6 + 16, "a long prefix exists, and DRI with an SOS of four components fits the suffix");
 
 /// Item::header_len of a progressive item. The baseline stages pass over it: its tiles hold only its coefficients, it has
 /// no chunks among the call's, and jg_encode_prog.hip codes its scans in tiles and chunks of their own (ProgPlan).
@@ -101,6 +125,7 @@ constexpr uint32_t kProgressiveHeader = 0xFFFFFFFFu;
 /// streams, counted apart from the call's, and where their arrays sit in d_scratch. All zero without such an item.
 struct ProgPlan {
     int n;
+    int slots;              // the most Huffman tables an item has: what the scan-block kernels keep in LDS
     uint32_t tiles, chunks;
     uint64_t shadow_off, items_off; // in the blob: Item[n + 1] (tile_start, chunk_start and the stream in these spaces), ProgItem[n]
     uint64_t bits_off;              // uint32[tiles * kTileBlocks]

@@ -157,6 +157,12 @@ __device__ inline Where where_of(const ProgItem& pi, const Item& it, int p)
         w.b             = w.q;
         w.segment_first = first_mcu && j == 0;
         w.segment_last  = w.q == sc.blocks - 1 || (ri && j == bpm - 1 && (mcu + 1) % ri == 0);
+        if (it.hs == 0) { // the item's own frame (jg_encode.hpp: Frame), as place_of reads it
+            const uint32_t m = uint32_t(it.frame.map >> (6 * j)) & 63u;
+            w.table          = it.frame.select >> (m & 3u) & 1;
+            w.pred           = m >> 2 ? w.b - 1 : first_mcu ? -1 : w.b - bpm + (int(it.frame.last >> (4 * j)) & 15);
+            return w;
+        }
         w.table         = j >= luma;
         if (j < luma && j > 0) w.pred = w.b - 1;
         else if (first_mcu) w.pred = -1;
@@ -167,7 +173,12 @@ __device__ inline Where where_of(const ProgItem& pi, const Item& it, int p)
     w.segment_first = ri ? w.q % ri == 0 : w.q == 0;
     w.segment_last  = w.q == sc.blocks - 1 || (ri && (w.q + 1) % ri == 0);
     w.table         = sc.comp > 0;
-    if (sc.comp == 0) {
+    if (it.hs == 0) { // the component's h x v blocks of an MCU begin at k0 (a single component's DC scans: b is q)
+        const int by = w.q / sc.blocks_x, bx = w.q - by * sc.blocks_x;
+        const int my = by / sc.v, mx = bx / sc.h;
+        w.b     = (my * it.mcus_x + mx) * bpm + sc.k0 + (by - my * sc.v) * sc.h + (bx - mx * sc.h);
+        w.table = it.frame.select >> sc.comp & 1;
+    } else if (sc.comp == 0) {
         const int by = w.q / sc.blocks_x, bx = w.q - by * sc.blocks_x;
         w.b = ((by / it.vs) * it.mcus_x + bx / it.hs) * bpm + (by % it.vs) * it.hs + bx % it.hs;
     } else {
@@ -334,7 +345,7 @@ __global__ __launch_bounds__(kTileBlocks) void prog_facts(const Item* __restrict
     const Lane l = lane_of(shadow, pitems, n);
     if (blockIdx.x == l.it->tile_start) {
         uint32_t* counts = &reinterpret_cast<ProgWork*>(scratch + l.pi->work_off)->counts[0][0];
-        for (int i = threadIdx.x; i < kProgSlots * 256; i += kTileBlocks) counts[i] = 0u;
+        for (int i = threadIdx.x; i < int(l.pi->slots_n) * 256; i += kTileBlocks) counts[i] = 0u; // (the tables the item has)
     }
     if (!l.valid) return;
     const Where w      = where_of(*l.pi, *l.it, l.p);
@@ -399,12 +410,12 @@ __global__ __launch_bounds__(kTileBlocks) void prog_runs(const Item* __restrict_
 }
 
 __global__ __launch_bounds__(kTileBlocks) void prog_symbols(const Item* __restrict__ shadow, const ProgItem* __restrict__ pitems, int n, uint8_t* __restrict__ scratch,
-                                                            const uint16_t* __restrict__ eobn)
+                                                            const uint16_t* __restrict__ eobn, int slots)
 {
     __shared__ uint32_t coefs[kTileBlocks * kLdsRow];
-    __shared__ uint32_t hist[kProgSlots * 256];
+    extern __shared__ uint32_t hist[]; // [slots][256]
     const Lane l = lane_of(shadow, pitems, n);
-    for (int i = threadIdx.x; i < kProgSlots * 256; i += kTileBlocks) hist[i] = 0u;
+    for (int i = threadIdx.x; i < slots * 256; i += kTileBlocks) hist[i] = 0u;
     __syncthreads();
     if (l.valid) {
         const Where w = where_of(*l.pi, *l.it, l.p);
@@ -417,7 +428,7 @@ __global__ __launch_bounds__(kTileBlocks) void prog_symbols(const Item* __restri
     }
     __syncthreads();
     uint32_t* counts = &reinterpret_cast<ProgWork*>(scratch + l.pi->work_off)->counts[0][0];
-    for (int i = threadIdx.x; i < kProgSlots * 256; i += kTileBlocks)
+    for (int i = threadIdx.x; i < slots * 256; i += kTileBlocks)
         if (hist[i]) atomicAdd(counts + i, hist[i]); // integer sums: the order of the tiles does not show
 }
 
@@ -435,7 +446,7 @@ __global__ __launch_bounds__(kTileBlocks) void prog_count_bits(const Item* __res
                                                                const uint16_t* __restrict__ eobn, uint32_t* __restrict__ bits, Cursor* __restrict__ tile_sum)
 {
     __shared__ uint32_t coefs[kTileBlocks * kLdsRow];
-    __shared__ uint32_t tab[kProgSlots * 256];
+    extern __shared__ uint32_t tab[]; // [the call's most slots][256]: ProgPlan::slots
     __shared__ Cursor cursors[kTileBlocks];
     const Lane l = lane_of(shadow, pitems, n);
     load_codes(tab, *l.pi, scratch);
@@ -461,7 +472,7 @@ __global__ __launch_bounds__(kTileBlocks) void prog_pack(const Item* __restrict_
                                                          const uint16_t* __restrict__ eobn, const uint32_t* __restrict__ bits, const Cursor* __restrict__ tile_before)
 {
     __shared__ uint32_t coefs[kTileBlocks * kLdsRow];
-    __shared__ uint32_t tab[kProgSlots * 256];
+    extern __shared__ uint32_t tab[]; // [the call's most slots][256]: ProgPlan::slots
     __shared__ Cursor cursors[kTileBlocks];
     const Lane l = lane_of(shadow, pitems, n);
     load_codes(tab, *l.pi, scratch);
@@ -623,9 +634,10 @@ hipError_t launch_prog_front(const Plan& plan, uint8_t* d_scratch, hipStream_t s
     const ProgItem* pitems = reinterpret_cast<const ProgItem*>(d_scratch + pp.items_off);
     uint8_t* facts         = d_scratch + pp.facts_off;
     uint16_t* eobn         = reinterpret_cast<uint16_t*>(d_scratch + pp.eobn_off);
+    const size_t lds       = size_t(pp.slots) * 256 * sizeof(uint32_t); // the tables of the item that has the most
     prog_facts<<<pp.tiles, kTileBlocks, 0, stream>>>(shadow, pitems, pp.n, d_scratch, facts, eobn);
     prog_runs<<<pp.tiles, kTileBlocks, 0, stream>>>(shadow, pitems, pp.n, facts, eobn);
-    prog_symbols<<<pp.tiles, kTileBlocks, 0, stream>>>(shadow, pitems, pp.n, d_scratch, eobn);
+    prog_symbols<<<pp.tiles, kTileBlocks, lds, stream>>>(shadow, pitems, pp.n, d_scratch, eobn, pp.slots);
     return hipGetLastError();
 }
 
@@ -640,11 +652,12 @@ hipError_t launch_prog_back(const Plan& plan, uint8_t* d_scratch, unsigned long 
     Cursor* tile_before    = reinterpret_cast<Cursor*>(d_scratch + pp.tile_before_off);
     Count* counts          = reinterpret_cast<Count*>(d_scratch + pp.count_off);
     Count* count_before    = reinterpret_cast<Count*>(d_scratch + pp.count_before_off);
-    prog_count_bits<<<pp.tiles, kTileBlocks, 0, stream>>>(shadow, pitems, pp.n, d_scratch, eobn, bits, tile_sum);
+    const size_t lds       = size_t(pp.slots) * 256 * sizeof(uint32_t);
+    prog_count_bits<<<pp.tiles, kTileBlocks, lds, stream>>>(shadow, pitems, pp.n, d_scratch, eobn, bits, tile_sum);
     hipError_t e = launch_scan_tiles(tile_sum, tile_before, pp.tiles, stream);
     if (e == hipSuccess) e = launch_clear_streams(shadow, pp.n, pp.chunks, d_scratch, tile_sum, tile_before, stream);
     if (e != hipSuccess) return e;
-    prog_pack<<<pp.tiles, kTileBlocks, 0, stream>>>(shadow, pitems, pp.n, d_scratch, eobn, bits, tile_before);
+    prog_pack<<<pp.tiles, kTileBlocks, lds, stream>>>(shadow, pitems, pp.n, d_scratch, eobn, bits, tile_before);
     e = launch_count_bytes(shadow, pp.n, pp.chunks, d_scratch, tile_sum, tile_before, counts, count_before, stream);
     if (e != hipSuccess) return e;
     prog_write_files<<<pp.chunks < 4096u ? pp.chunks : 4096u, 256, 0, stream>>>(shadow, pitems, pp.n, pp.chunks, d_scratch, tile_sum, tile_before, counts, count_before,

@@ -1,6 +1,7 @@
 // jg_encode_prog.hpp -- what the host plans for a progressive item and what the kernels of jg_encode_prog.hip keep for it.
-// The file is libjpeg's jpeg_simple_progression script coded by jcphuff.c's rules: ten scans for RGB, six for grey, every
-// scan with Huffman tables made from its own symbol counts.
+// The file is libjpeg's jpeg_simple_progression script coded by jcphuff.c's rules: ten scans for three-component YCbCr, six
+// for grey, and for a transcode item that keeps another frame (jg_encode.hpp: Frame) the all-purpose script of 2 + 4 n scans;
+// every scan with Huffman tables made from its own symbol counts.
 //
 // The parallel unit is the SCAN BLOCK: one block of one scan. An item's scan blocks are numbered scan after scan, each scan
 // in its own order -- MCU order over the padded grid for the two interleaved DC scans, the component's real blocks row by
@@ -15,8 +16,9 @@
 namespace jg {
 namespace enc {
 
-constexpr int kProgScans = 10;
-constexpr int kProgSlots = 10; // Huffman tables of a file: two DC tables of the first scan, one AC table per AC scan
+constexpr int kProgScans = 18; // four components: 2 + 4 * 4
+constexpr int kProgSlots = 18; // Huffman tables of a file: up to two DC tables of the first scan, one AC table per AC scan
+constexpr int kProgSlotsEncoder = 10; // what the pixel encoder's scripts need: the kernels' LDS follows the call's items (ProgPlan::slots)
 /// jcphuff.c: an end-of-band run is sent when it reaches kMaxEobRun blocks, and in a refinement scan when more than
 /// kMaxPendingBits correction bits wait behind it (MAX_CORR_BITS - DCTSIZE2 + 1).
 constexpr uint32_t kMaxEobRun      = 0x7FFF;
@@ -38,6 +40,7 @@ struct ProgScan {
     int comp;              // the scan's component, -1: all of them, interleaved
     int ss, se, ah, al;
     int blocks, blocks_x;  // the scan's blocks and, for a scan of one component, the width of its grid
+    int h, v, k0;          // a `Frame` item's scan of one component: its blocks in an MCU, and the first one's place there
     uint32_t first;        // its first scan block among the item's
     int slot, tables;      // its first table and how many it brings: 2 (the first scan of RGB: luma, chroma), 1 or 0
     uint32_t marks_before; // restart markers of the scans in front of it
@@ -53,8 +56,8 @@ struct ProgItem {
     uint32_t scans_n, slots_n;
     uint32_t prefix_len;
     uint8_t slot_class_id[kProgSlots + 2]; // the DHT's Tc << 4 | Th
-    uint8_t prefix[kPrefixBytes];          // SOI .. SOF2
-    ProgScan scans[kProgScans];
+    ProgScan scans[kProgScans];            // (in front of the prefix: what every lane reads stays within the struct's first lines)
+    uint8_t prefix[kLongPrefixBytes + 2];  // SOI .. SOF2
 };
 
 /// What the device makes for a progressive item.

@@ -24,28 +24,34 @@ jpeggpu_status transcode_spec(const jpeggpu_ext_transcode_item& it, bool need_de
     const bool cropped = tc[2] > 0;
     if ((d.crop.on && !cropped) || d.scale_log2 != 0 || d.shard_world != 1) return JPEGGPU_NOT_SUPPORTED;
 
-    // what the encoder writes: grey, or YCbCr with chroma 1 x 1 and luma 1 x 1, 2 x 1 or 2 x 2 and one chroma table
+    // what the encoder writes: grey, or YCbCr with chroma 1 x 1 and luma 1 x 1, 2 x 1 or 2 x 2 and one chroma table, 8-bit
+    // tables. In SOURCE mode (jpeggpu_ext_set_transcode_frame) such a file goes the same way to the same bytes (its tables
+    // numbered 0 and 1, whatever the source calls them); every other file keeps its own frame (`general`)
+    const bool keep = d.transcode_frame == JPEGGPU_EXT_TRANSCODE_FRAME_SOURCE;
     int subsampling = JPEGGPU_EXT_SUBSAMPLING_444;
+    bool encoders   = true;
     if (s.num_comp == 3) {
         const Component& y = s.comp[0];
         if (s.color_space != kColorYCbCr || s.comp[1].hs != 1 || s.comp[1].vs != 1 || s.comp[2].hs != 1 || s.comp[2].vs != 1 || s.comp[1].qidx != s.comp[2].qidx)
-            return JPEGGPU_NOT_SUPPORTED;
-        if (y.hs == 1 && y.vs == 1) subsampling = JPEGGPU_EXT_SUBSAMPLING_444;
+            encoders = false;
+        else if (y.hs == 1 && y.vs == 1) subsampling = JPEGGPU_EXT_SUBSAMPLING_444;
         else if (y.hs == 2 && y.vs == 1) subsampling = JPEGGPU_EXT_SUBSAMPLING_422;
         else if (y.hs == 2 && y.vs == 2) subsampling = JPEGGPU_EXT_SUBSAMPLING_420;
-        else return JPEGGPU_NOT_SUPPORTED;
+        else encoders = false;
     } else if (s.num_comp != 1) {
-        return JPEGGPU_NOT_SUPPORTED;
+        encoders = false;
     }
     constexpr uint8_t nat[64] = JG_ORDER_NATURAL;
-    for (int t = 0; t < (s.num_comp == 1 ? 1 : 2); ++t) {
+    for (int t = 0; encoders && t < (s.num_comp == 1 ? 1 : 2); ++t) {
         const int id = s.comp[t].qidx;
-        if (s.qtable16[id]) return JPEGGPU_NOT_SUPPORTED; // Pq = 1
-        for (int k = 0; k < 64; ++k) {
-            if (s.qtable[id][nat[k]] > 255) return JPEGGPU_NOT_SUPPORTED;
+        if (s.qtable16[id]) encoders = false; // Pq = 1
+        for (int k = 0; encoders && k < 64; ++k) {
+            if (s.qtable[id][nat[k]] > 255) encoders = false;
             spec.qtable[t][k] = static_cast<uint8_t>(s.qtable[id][nat[k]]);
         }
     }
+    if (!encoders && !keep) return JPEGGPU_NOT_SUPPORTED;
+    if (s.num_comp < 1 || s.num_comp > 4) return JPEGGPU_NOT_SUPPORTED;
     spec.sampling0 = s.comp[0].sampling;
 
     // jpeggpu_ext_set_transcode_orientation: the stored image the new file holds is the displayed image of the source's.
@@ -53,7 +59,14 @@ jpeggpu_status transcode_spec(const jpeggpu_ext_transcode_item& it, bool need_de
     const int o          = d.transcode_orientation;
     const bool transpose = o >= 5, mirror_x = o == 2 || o == 3 || o == 6 || o == 7, mirror_y = o == 3 || o == 4 || o == 7 || o == 8;
     const bool stored_x = transpose ? mirror_y : mirror_x, stored_y = transpose ? mirror_x : mirror_y;
-    const int hs = s.num_comp == 1 ? 1 : s.comp[0].hs, vs = s.num_comp == 1 ? 1 : s.comp[0].vs;
+    // the source's factors per component (1 x 1 for a single component) and the iMCU's
+    int ch[4] = {1, 1, 1, 1}, cv[4] = {1, 1, 1, 1}, hs = 1, vs = 1, per_mcu = 0;
+    for (int c = 0; c < s.num_comp; ++c) {
+        if (s.num_comp > 1) ch[c] = s.comp[c].hs, cv[c] = s.comp[c].vs;
+        hs = ch[c] > hs ? ch[c] : hs, vs = cv[c] > vs ? cv[c] : vs;
+        per_mcu += ch[c] * cv[c];
+    }
+    if (per_mcu > kMaxMcuBlocks) return JPEGGPU_NOT_SUPPORTED;
     int w = s.size_x, h = s.size_y; // the source, trimmed
     if (stored_x && w % (8 * hs)) {
         if (!d.transcode_trim || w < 8 * hs) return JPEGGPU_NOT_SUPPORTED;
@@ -64,7 +77,10 @@ jpeggpu_status transcode_spec(const jpeggpu_ext_transcode_item& it, bool need_de
         h -= h % (8 * vs);
     }
     if (transpose) {
-        if (subsampling == JPEGGPU_EXT_SUBSAMPLING_422) return JPEGGPU_NOT_SUPPORTED; // it would be 4:4:0
+        if (subsampling == JPEGGPU_EXT_SUBSAMPLING_422) {
+            if (!keep) return JPEGGPU_NOT_SUPPORTED; // it would be 4:4:0
+            encoders = false;
+        }
         for (int t = 0; t < 2; ++t) { // entry (v, u) is the source's (u, v)
             uint8_t q[64];
             for (int k = 0; k < 64; ++k) q[(nat[k] & 7) << 3 | nat[k] >> 3] = spec.qtable[t][k];
@@ -73,21 +89,66 @@ jpeggpu_status transcode_spec(const jpeggpu_ext_transcode_item& it, bool need_de
         spec.sampling0 = uint8_t(spec.sampling0 << 4 | spec.sampling0 >> 4); // (a grey file's byte too: jpegtran's transpose_critical_parameters)
     }
     spec.src.oriented = o != 1 || cropped, spec.src.transpose = transpose, spec.src.mirror_x = mirror_x, spec.src.mirror_y = mirror_y;
+    spec.general      = !encoders;
 
     // jpeggpu_ext_set_transcode_crop: a rectangle of that image, from an iMCU boundary of the target on
-    const int ths = transpose ? vs : hs, tvs = transpose ? hs : vs; // the target's luma factors
+    const int ths = transpose ? vs : hs, tvs = transpose ? hs : vs; // the target's iMCU
     int out_w = transpose ? h : w, out_h = transpose ? w : h;
     if (cropped) {
         if (tc[0] > out_w - tc[2] || tc[1] > out_h - tc[3]) return JPEGGPU_INVALID_ARGUMENT;
         if (tc[0] % (8 * ths) || tc[1] % (8 * tvs)) return JPEGGPU_NOT_SUPPORTED;
         out_w = tc[2], out_h = tc[3];
     }
+    const auto blocks_of = [](int pixels, int f, int fmax) { return ((pixels * f + fmax - 1) / fmax + 7) / 8; }; // of a component
+
+    if (spec.general) { // the header of libjpeg after jpeg_copy_critical_parameters and jpeg_set_colorspace
+        const int cs     = s.color_space;
+        spec.color_space = cs;
+        static const char rgb[] = "RGB", cmyk[] = "CMYK";
+        Frame& f = spec.frame;
+        f        = Frame{};
+        f.ncomp  = uint8_t(s.num_comp);
+        int j    = 0;
+        for (int c = 0; c < s.num_comp; ++c) {
+            TranscodeSpec::Comp& tcmp = spec.comp[c];
+            tcmp.id     = cs == kColorGray || cs == kColorYCbCr || cs == kColorYCCK ? uint8_t(c + 1) : cs == kColorRGB ? uint8_t(rgb[c]) : cs == kColorCMYK ? uint8_t(cmyk[c]) : uint8_t(c);
+            tcmp.h      = uint8_t(transpose ? cv[c] : ch[c]);
+            tcmp.v      = uint8_t(transpose ? ch[c] : cv[c]);
+            if (s.num_comp == 1) tcmp.h = spec.sampling0 >> 4, tcmp.v = spec.sampling0 & 15; // written back as it came
+            tcmp.tq     = s.comp[c].qidx;
+            tcmp.select = (cs == kColorYCbCr || cs == kColorYCCK) && (c == 1 || c == 2);
+            int t       = 0;
+            while (t < spec.tables_n && spec.table_id[t] != tcmp.tq) ++t;
+            if (t == spec.tables_n) {
+                spec.table_id[t] = tcmp.tq;
+                uint16_t q[64];
+                for (int k = 0; k < 64; ++k) {
+                    const uint16_t v = s.qtable[tcmp.tq][nat[k]];
+                    if (v > 255) spec.table16[t] = true;
+                    spec.table[t][k] = v;
+                    q[transpose ? (nat[k] & 7) << 3 | nat[k] >> 3 : nat[k]] = v;
+                }
+                if (transpose)
+                    for (int k = 0; k < 64; ++k) spec.table[t][k] = q[nat[k]];
+                ++spec.tables_n;
+            }
+            const int th = transpose ? cv[c] : ch[c], tv = transpose ? ch[c] : cv[c]; // the blocks of an MCU
+            for (int yo = 0; yo < tv; ++yo)
+                for (int xo = 0; xo < th; ++xo, ++j) {
+                    f.map |= uint64_t(c | xo << 2 | yo << 4) << (6 * j);
+                    f.last |= uint64_t(th * tv - 1) << (4 * j);
+                }
+            f.hv |= uint32_t(th | tv << 4) << (8 * c);
+            f.select |= uint8_t(tcmp.select << c);
+            f.grid_w[c] = blocks_of(out_w, th, ths), f.grid_h[c] = blocks_of(out_h, tv, tvs);
+        }
+    }
 
     jpeggpu_ext_encode_item& e = spec.item;
     e.width = out_w, e.height = out_h, e.channels = s.num_comp;
     e.progressive = it.progressive, e.optimize = it.optimize;
     e.quality          = 75; // (unused: the header holds the source's tables)
-    e.subsampling      = subsampling;
+    e.subsampling      = spec.general ? JPEGGPU_EXT_SUBSAMPLING_444 : subsampling;
     e.restart_interval = it.restart_interval < 0 ? s.first_restart_interval : it.restart_interval;
     e.out = it.out, e.capacity = it.capacity;
 
@@ -95,14 +156,15 @@ jpeggpu_status transcode_spec(const jpeggpu_ext_transcode_item& it, bool need_de
     for (int c = 0; c < s.num_comp; ++c) {
         GatherComp& g = spec.src.comp[c];
         g.vis_x = (s.comp[c].size_x + 7) / 8, g.vis_y = (s.comp[c].size_y + 7) / 8;
-        const int cut_x = ((c ? (w + hs - 1) / hs : w) + 7) / 8, cut_y = ((c ? (h + vs - 1) / vs : h) + 7) / 8; // of the trimmed source
+        const int cut_x = blocks_of(w, ch[c], hs), cut_y = blocks_of(h, cv[c], vs); // of the trimmed source
+        const int th = transpose ? cv[c] : ch[c], tv = transpose ? ch[c] : cv[c];    // the component's factors in the target
         g.dst_x = transpose ? cut_y : cut_x, g.dst_y = transpose ? cut_x : cut_y;
         // the source's blocks a cropped item reads, [sx0, sx1) x [sy0, sy1): its real blocks (the DC of a dummy block is one
         // of them) from the offset on, mirrored over the uncropped target's grid, exchanged
         int sx0 = 0, sy0 = 0, sx1 = 0, sy1 = 0;
         if (cropped) {
-            g.off_x = int16_t(tc[0] / (c ? 8 * ths : 8)), g.off_y = int16_t(tc[1] / (c ? 8 * tvs : 8));
-            const int nx = ((c ? (out_w + ths - 1) / ths : out_w) + 7) / 8, ny = ((c ? (out_h + tvs - 1) / tvs : out_h) + 7) / 8;
+            g.off_x = int16_t(tc[0] / (8 * ths) * th), g.off_y = int16_t(tc[1] / (8 * tvs) * tv);
+            const int nx = blocks_of(out_w, th, ths), ny = blocks_of(out_h, tv, tvs);
             const int x0 = mirror_x ? g.dst_x - g.off_x - nx : g.off_x, y0 = mirror_y ? g.dst_y - g.off_y - ny : g.off_y;
             sx0 = transpose ? y0 : x0, sy0 = transpose ? x0 : y0;
             sx1 = sx0 + (transpose ? ny : nx), sy1 = sy0 + (transpose ? nx : ny);

@@ -10,6 +10,8 @@
 
 #include <cstdint>
 
+#include "jg_encode.hpp"
+
 namespace jg {
 namespace enc {
 
@@ -39,7 +41,7 @@ static_assert(sizeof(GatherComp) == 80, "GatherComp: the crop's offsets lie in i
 
 /// One item's source, in the call's blob behind the items (Item::src points at it, in d_scratch).
 struct GatherSrc {
-    GatherComp comp[3];
+    GatherComp comp[4];
     // a progressive item's shadow Item in d_scratch (its capacity is what prog_write_files tests), else 0. 32 bits of a 64-bit
     // plan offset: the shadow items lie in the blob, which make_plan keeps below 4 GB (its test for Item::header_off)
     uint32_t shadow_off;
@@ -54,7 +56,7 @@ struct GatherSrc {
     // the frame's data unit that is unit 0 of du_tab. Such a file has one scan, so one number serves its components.
     int32_t first_unit;
 };
-static_assert(sizeof(GatherSrc) == 256, "GatherSrc: first_unit lies in its padding");
+static_assert(sizeof(GatherSrc) == 4 * sizeof(GatherComp) + 16, "GatherSrc: four components and four words");
 
 /// What jg_transcode.cpp says of one item: the encoder's item (geometry, options, slot; `data` and `quality` unused), the
 /// header's tables and sampling byte, the source.
@@ -63,6 +65,18 @@ struct TranscodeSpec {
     uint8_t qtable[2][64]; // zigzag order, as a DQT segment holds them: luma, chroma
     uint8_t sampling0;     // the frame header's sampling-factor byte of component 0
     GatherSrc src;
+    // jpeggpu_ext_set_transcode_frame(SOURCE) on a source outside the encoder's layouts: the file keeps the source's frame.
+    // `item` then carries the component count in `channels`, and the header and the geometry are made of what follows.
+    bool general;
+    int color_space;       // enum jpeggpu_ext_color_space
+    struct Comp {
+        uint8_t id, h, v, tq, select; // as written: the factors exchanged by a transposing orientation
+    } comp[4];
+    int tables_n;          // the DQT segments, in the order written
+    uint8_t table_id[4];
+    bool table16[4];       // Pq = 1: an entry above 255
+    uint16_t table[4][64]; // zigzag order (transposed by a transposing orientation)
+    Frame frame;           // what the kernels get (jg_encode.hpp), over the TARGET's grids
 };
 
 /// The spec of a transcode item: JPEGGPU_INVALID_ARGUMENT / JPEGGPU_NOT_SUPPORTED by the rules of jpeggpu_ext.h.
