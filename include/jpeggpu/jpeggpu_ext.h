@@ -855,6 +855,92 @@ enum jpeggpu_status jpeggpu_ext_resize_view_weights(
     int* weights,
     int max_taps);
 
+/* Thumbnails (a resize service, a thumbnail cache): Pillow's im.thumbnail((req_w, req_h), BILINEAR | BICUBIC, reducing_gap)
+ * of many JPEG files at once, each with its own result size. That chain is not Image.resize: it has a size rule of its
+ * own, decodes at a reduced scale (draft), averages integer boxes (Image.reduce) in front of the convolution, and resizes
+ * from a box that may end inside a sample.
+ *
+ * jpeggpu_ext_thumbnail_plan (host only, pure) says what the chain does to a width x height file. `reducing_gap` <= 0 is
+ * Pillow's None; otherwise it must be at least 1.
+ *   1. The final size out_w x out_h: if req_w >= width and req_h >= height nothing happens -- the thumbnail is the
+ *      full-scale decode (identity = 1, scale 1). Otherwise, in doubles, with aspect = width / height: if req_w / req_h >=
+ *      aspect the width becomes round_aspect(req_h * aspect), else the height round_aspect(req_w / aspect), where
+ *      round_aspect takes of floor and ceil the one whose ratio to the other side is nearer `aspect` (the floor on a tie;
+ *      a height of 0 counts as exact) and then at least 1.
+ *   2. With a gap: draft() for (int(req_w g), int(req_h g)): s = min(width / that, height / that) in integers, rounded down
+ *      to 8, 4, 2 or 1 = `scale`. The decode -- JPEGGPU_EXT_SCALE_LIBJPEG at that scale -- has dec_w x dec_h = ceil(width /
+ *      s) x ceil(height / s) pixels, and the box is width / s x height / s in doubles.
+ *   3. If the decode has the final size it is the thumbnail (identity = 1), whatever the box.
+ *   4. With a gap: fx = int(box_w / out_w / g) or 1, fy alike. If either exceeds 1 the decode is reduced by (fx, fy) to
+ *      red_w x red_h = ceil(dec_w / fx) x ceil(dec_h / fy) and the box is divided by the factors; else red = dec.
+ *   5. box_w, box_h: the box rounded to binary32, as it passes through Pillow's C code. The resize is of red_w x red_h
+ *      pixels to out_w x out_h from the box (0, 0, box_w, box_h).
+ *   6. JPEGGPU_NOT_SUPPORTED if red_h > 100 red_w and out_h < red_h: Pillow runs the vertical pass first on such an image.
+ * `replicate` is set to 0; the caller sets it for an image whose chroma libjpeg replicates at `scale`
+ * (jpeggpu_ext_get_scale_info: fancy_upsampling == 0). JPEGGPU_INVALID_ARGUMENT: a NULL plan, width or height outside
+ * 1..65535, req_w or req_h < 1, a gap in (0, 1), not a number, or above 65536. JPEGGPU_NOT_SUPPORTED: another filter.
+ *
+ * jpeggpu_ext_resize_box_weights (host only) is jpeggpu_ext_resize_weights for `in` samples of which the resize covers
+ * `extent`: scale = extent / out in double, everything else as stated there, the taps clamped at `in`; max_taps at least 2
+ * ceil(support) + 1 with fs = max(extent / out, 1). extent == in gives jpeggpu_ext_resize_weights' table bit for bit.
+ *
+ * jpeggpu_ext_thumbnail_to_rgb makes the thumbnails of n decoded images: items[i] are the whole planes of a decode at
+ * plans[i].scale (`crop` NULL), colors[i] their model (NULL: by the component count). `dst` is n x canvas_h x canvas_w x 3
+ * uint8; item i's thumbnail, out_h x out_w, lies in the top-left corner of slot i, zeros elsewhere in the slot. A grey
+ * file's thumbnail is its one channel three times. On planes of a JPEGGPU_EXT_IDCT_ISLOW, JPEGGPU_EXT_SCALE_LIBJPEG decode
+ * the thumbnail equals np.asarray(im) after im.thumbnail(...) (for a grey file: each channel does).
+ *   - The reduction: an output pixel over nx x ny source pixels (fx x fy, fewer in the last column and row) is, per
+ *     channel, ((sum + n / 2) * m) >> 24 in 32-bit unsigned arithmetic with n = nx ny and m = (uint32)((float)(1 << 24) /
+ *     (float)n) -- not a rounded mean. One launch for all items that reduce; it reads the planes as every conversion here
+ *     does (fancy upsampling or replication, the colour model), so the decoded-size RGB is never written, and leaves
+ *     reduced planes in `d_scratch` that the resize passes read as an RGB-coded (or grey) image.
+ *   - The resize: jpeggpu_ext_resize_view_to_tensor's two launches with the view {out_w, out_h, 0, 0} of the canvas and the
+ *     tables of jpeggpu_ext_resize_box_weights; an item with identity = 1 gets one tap of weight 1 per coordinate. At most
+ *     three launches per call, two if no item reduces.
+ *   - `d_scratch`: at least jpeggpu_ext_thumbnail_scratch_size bytes (0 for arguments the call would refuse; it only grows
+ *     with n for the same items), private to the stream until the call has executed; the staging ring is the resize calls'.
+ *   - JPEGGPU_NOT_SUPPORTED: another filter, a model that does not fit the component count, non-integral sampling ratios,
+ *     a CMYK or YCCK item (Pillow's thumbnail of those is CMYK), a box of more than 2^23 pixels, a plan that 6. refuses.
+ *     JPEGGPU_INVALID_ARGUMENT: NULL pointers, n, canvas_w or canvas_h <= 0 (or n > 65535), an item with a `crop`, a plan
+ *     that does not fit its item (dec_w x dec_h is not the image's extent by its planes; red_w, red_h not the ceilings; fx
+ *     or fy < 1; out_w or out_h < 1 or beyond the canvas; a box that is not positive and finite; identity with factors or
+ *     with another final size), scratch_size too small. Every check is made before anything is staged or enqueued; on an
+ *     error nothing is written. */
+struct jpeggpu_ext_thumbnail {
+    int scale;             /* 1, 2, 4 or 8: what to decode at (JPEGGPU_EXT_SCALE_LIBJPEG) */
+    int dec_w, dec_h;      /* the decoded size */
+    int fx, fy;            /* Image.reduce's factors; 1, 1: no reduction */
+    int red_w, red_h;      /* the size after the reduction */
+    float box_w, box_h;    /* how much of red_w x red_h the resize covers */
+    int out_w, out_h;      /* the thumbnail's size */
+    int identity;          /* the decode is the thumbnail */
+    int replicate;         /* libjpeg replicates this item's chroma (set by the caller) */
+};
+enum jpeggpu_status jpeggpu_ext_thumbnail_plan(
+    int width, int height, int req_w, int req_h, enum jpeggpu_ext_filter filter, double reducing_gap, struct jpeggpu_ext_thumbnail* plan);
+enum jpeggpu_status jpeggpu_ext_resize_box_weights(
+    int in, float extent, int out, enum jpeggpu_ext_filter filter, int* first, int* count, int* weights, int max_taps);
+size_t jpeggpu_ext_thumbnail_scratch_size(
+    const struct jpeggpu_ext_resize_item* items,
+    const enum jpeggpu_ext_color_space* colors, /* NULL: by the component count */
+    const struct jpeggpu_ext_thumbnail* plans,
+    int n,
+    int canvas_w,
+    int canvas_h,
+    enum jpeggpu_ext_filter filter);
+enum jpeggpu_status jpeggpu_ext_thumbnail_to_rgb(
+    const struct jpeggpu_ext_resize_item* items,
+    const enum jpeggpu_ext_color_space* colors, /* NULL: by the component count */
+    const struct jpeggpu_ext_thumbnail* plans,
+    int n,
+    int canvas_w,
+    int canvas_h,
+    enum jpeggpu_ext_filter filter,
+    uint8_t* dst,
+    void* d_scratch,
+    size_t scratch_size,
+    jpeggpu_stream_t stream);
+
 /* Batched conversion to RGB (a list of files in, a list of RGB images out, each at its own size -- a validation loader,
  * or torchvision.io.decode_jpeg on a list): what jpeggpu_ext_crop_to_rgbi_oriented makes of every item with a `crop`, and
  * jpeggpu_ext_planes_to_rgbi_oriented of every item without one at the image's own extent by its planes (the size of a

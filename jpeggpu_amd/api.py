@@ -124,6 +124,18 @@ class ResizeView(C.Structure):
     _fields_ = [("resized_w", C.c_int), ("resized_h", C.c_int), ("x", C.c_int), ("y", C.c_int), ("replicate", C.c_int)]
 
 
+class Thumbnail(C.Structure):
+    """struct jpeggpu_ext_thumbnail: what Pillow's Image.thumbnail does to one file (thumbnail_plan)."""
+    _fields_ = [("scale", C.c_int), ("dec_w", C.c_int), ("dec_h", C.c_int), ("fx", C.c_int), ("fy", C.c_int), ("red_w", C.c_int),
+                ("red_h", C.c_int), ("box_w", C.c_float), ("box_h", C.c_float), ("out_w", C.c_int), ("out_h", C.c_int), ("identity", C.c_int),
+                ("replicate", C.c_int)]
+
+    def astuple(self):
+        """(scale, dec_w, dec_h, fx, fy, red_w, red_h, box_w, box_h, out_w, out_h, identity)"""
+        return (self.scale, self.dec_w, self.dec_h, self.fx, self.fy, self.red_w, self.red_h, self.box_w, self.box_h, self.out_w, self.out_h,
+                self.identity)
+
+
 class RgbItem(C.Structure):
     """struct jpeggpu_ext_rgb_item: a decoded image's info, crop (NULL: the whole image) and planes, its colour model, EXIF
     orientation and whether libjpeg replicates its chroma, and where its displayed RGB goes."""
@@ -326,6 +338,16 @@ def lib():
         L.jpeggpu_ext_encode_tables_from_counts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.jpeggpu_ext_resize_weights.argtypes = [
         C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
+    if hasattr(L, "jpeggpu_ext_thumbnail_to_rgb"):
+        L.jpeggpu_ext_thumbnail_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(Thumbnail)]
+        L.jpeggpu_ext_resize_box_weights.argtypes = [
+            C.c_int, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
+        L.jpeggpu_ext_thumbnail_scratch_size.restype = C.c_size_t
+        L.jpeggpu_ext_thumbnail_scratch_size.argtypes = [
+            C.POINTER(ResizeItem), C.POINTER(C.c_int), C.POINTER(Thumbnail), C.c_int, C.c_int, C.c_int, C.c_int]
+        L.jpeggpu_ext_thumbnail_to_rgb.argtypes = [
+            C.POINTER(ResizeItem), C.POINTER(C.c_int), C.POINTER(Thumbnail), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+            C.c_size_t, C.c_void_p]
     _lib = L
     return L
 
@@ -1284,6 +1306,168 @@ def decode_center_cropped(datas, resize=256, crop=224, filt="bilinear", layout="
                                      mean=mean, std=std)
         torch.cuda.synchronize(torch.device(device))
         return out
+
+
+def _thumbnail_request(size):
+    """Pillow's (width, height) request after math.floor, each at least 1."""
+    import math
+
+    rw, rh = (int(math.floor(v)) for v in size)
+    if rw < 1 or rh < 1:
+        raise ValueError("a thumbnail's requested width and height must be at least 1")
+    return rw, rh
+
+
+def thumbnail_plan(width, height, size, resample="bicubic", reducing_gap=2.0) -> Thumbnail:
+    """jpeggpu_ext_thumbnail_plan (host only, pure): what Pillow's im.thumbnail(size, resample, reducing_gap) does to a
+    width x height JPEG -- the scale to decode at, the decoded size, Image.reduce's factors and the reduced size, the box
+    the resize covers (as binary32), the thumbnail's size, and whether the decode already is the thumbnail. `size`: Pillow's
+    (width, height) request; `reducing_gap`: None, or at least 1. A JpegGpuError (NOT_SUPPORTED) for an image more than 100
+    times taller than wide at the resize, which Pillow resizes in the other order."""
+    if resample not in FILTERS:
+        raise ValueError("filter %r is not one of %s" % (resample, ", ".join(FILTERS)))
+    rw, rh = _thumbnail_request(size)
+    plan = Thumbnail()
+    _check(_newer_symbol("jpeggpu_ext_thumbnail_plan")(int(width), int(height), rw, rh, FILTERS[resample],
+                                                       0.0 if reducing_gap is None else float(reducing_gap), C.byref(plan)),
+           "jpeggpu_ext_thumbnail_plan")
+    return plan
+
+
+def resize_box_weights(in_size, extent, out_size, filt="bilinear"):
+    """jpeggpu_ext_resize_box_weights (host only): resize_weights for `in_size` samples of which the resize covers `extent`
+    (rounded to binary32), as numpy int32 (first[out], count[out], weights[out, max_taps])."""
+    import math
+
+    import numpy as np
+
+    if filt not in FILTERS:
+        raise ValueError("filter %r is not one of %s" % (filt, ", ".join(FILTERS)))
+    extent = C.c_float(extent).value
+    k = 2 * int(math.ceil({"bilinear": 1.0, "bicubic": 2.0}[filt] * max(extent / out_size, 1.0))) + 1 if extent > 0 and out_size > 0 else 1
+    first, count = np.zeros(max(out_size, 1), np.int32), np.zeros(max(out_size, 1), np.int32)
+    w = np.zeros((max(out_size, 1), k), np.int32)
+    ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+    _check(_newer_symbol("jpeggpu_ext_resize_box_weights")(int(in_size), extent, int(out_size), FILTERS[filt], ptr(first), ptr(count), ptr(w), k),
+           "jpeggpu_ext_resize_box_weights")
+    return first, count, w
+
+
+def thumbnails_to_rgb(planes_list, infos, plans, canvas, filt="bicubic", colors=None, out=None):
+    """jpeggpu_ext_thumbnail_to_rgb on torch's current stream: the thumbnails of decoded images -- planes_list[i] and infos[i]
+    of a whole-image decode at plans[i].scale, plans[i] from thumbnail_plan (with `replicate` set where libjpeg replicates
+    the chroma), colors[i] the ColorSpace (None: by the component count). `canvas`: (height, width), at least every plan's
+    out_h x out_w. Returns the n x height x width x 3 uint8 canvas (`out` if given): thumbnail i in the top-left corner of
+    slot i, zeros around it."""
+    import torch
+
+    if filt not in FILTERS:
+        raise ValueError("filter %r is not one of %s" % (filt, ", ".join(FILTERS)))
+    n = len(planes_list)
+    for name, v in (("infos", infos), ("plans", plans), ("colors", colors)):
+        if v is not None and len(v) != n:
+            raise ValueError("%s must have one entry per image" % name)
+    ch, cw = _size_hw(canvas)
+    items, _keep = _resize_items(planes_list, infos, None)
+    cs = _color_array(colors, n) if colors is not None else None
+    ps = (Thumbnail * n)(*plans)
+    device = planes_list[0][0].device
+    shape = (n, ch, cw, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=device)
+    elif tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous uint8 tensor of shape %s" % (shape,))
+    need = _newer_symbol("jpeggpu_ext_thumbnail_scratch_size")(items, cs, ps, n, cw, ch, FILTERS[filt])
+    scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    _check(lib().jpeggpu_ext_thumbnail_to_rgb(items, cs, ps, n, cw, ch, FILTERS[filt], out.data_ptr(), scratch.data_ptr(), need,
+                                              torch.cuda.current_stream(device).cuda_stream), "jpeggpu_ext_thumbnail_to_rgb")
+    # the scratch tensor is freed by torch's caching allocator in stream order: it is not reused before the launches ran
+    return out
+
+
+def _exif_transposed(view, orientation):
+    """ImageOps.exif_transpose of a small (h, w[, 3]) tensor, with torch: the eight orientations as flips and a transpose."""
+    o = int(orientation)
+    if o >= 5:  # 5: transpose, 6: rotate 270, 7: transverse, 8: rotate 90 -- a transpose, then the flips of 1, 2, 3, 4
+        view = view.transpose(0, 1)
+    flips = {1: (), 2: (1,), 3: (0, 1), 4: (0,), 5: (), 6: (1,), 7: (0, 1), 8: (0,)}[o]
+    return view.flip(flips) if flips else view
+
+
+def _header_frame_size(data):
+    """(width, height) of a JPEG from its frame header, without parsing anything else: the thumbnail plans come before the
+    decoders are set up, because the scale to decode at depends on the size. Bytes are walked marker by marker up to the
+    frame header; any other buffer, and a file this walk does not understand, goes through a Decoder's parse_header, which
+    raises what the file deserves."""
+    if isinstance(data, (bytes, bytearray)) and data[:2] == b"\xff\xd8":
+        i, n = 2, len(data)
+        while i + 4 <= n and data[i] == 0xFF:
+            m = data[i + 1]
+            if m == 0xFF:  # a fill byte
+                i += 1
+            elif m == 0x01 or 0xD0 <= m <= 0xD8:  # markers without a segment
+                i += 2
+            elif m == 0xDA or m == 0xD9:
+                break
+            else:
+                if m in (0xC0, 0xC1, 0xC2) and i + 9 <= n:
+                    w, h = data[i + 7] << 8 | data[i + 8], data[i + 5] << 8 | data[i + 6]
+                    if w and h:
+                        return w, h
+                    break
+                i += 2 + (data[i + 2] << 8 | data[i + 3])
+    probe = Decoder()
+    try:
+        probe.set_progressive(True)
+        return _frame_size(probe.parse_header(data))
+    finally:
+        probe.cleanup()
+
+
+def decode_thumbnails(datas, size, resample="bicubic", reducing_gap=2.0, exif_transpose=False, device="cuda:0"):
+    """Pillow's im.thumbnail(size, resample, reducing_gap) of every JPEG of `datas`, on the GPU: one BatchDecode at the
+    scales draft() would pick (thumbnail_plan), then ONE jpeggpu_ext_thumbnail_to_rgb call -- Image.reduce's box averages and
+    the resize from Pillow's fractional box -- with nothing on the host in between. `size`: Pillow's (width, height) request;
+    `resample`: "bilinear" or "bicubic"; `reducing_gap`: None, or at least 1. Returns a list of uint8 tensors, views of one
+    canvas: h x w x 3, or h x w for a grey file, each equal to np.asarray(im) after im.thumbnail(...). `exif_transpose`: each
+    view is turned as ImageOps.exif_transpose turns the thumbnail (applied AFTER the thumbnail, with torch, on the small
+    tensor). CMYK and YCCK files, and images more than 100 times taller than wide at the resize, raise a JpegGpuError
+    (NOT_SUPPORTED)."""
+    import torch
+
+    if resample not in FILTERS:
+        raise ValueError("filter %r is not one of %s" % (resample, ", ".join(FILTERS)))
+    _thumbnail_request(size)
+    n = len(datas)
+    if n == 0:
+        raise ValueError("datas is empty")
+    plans = [thumbnail_plan(*_header_frame_size(data), size, resample, reducing_gap) for data in datas]
+    with BatchDecode(datas, device, scales=[p.scale for p in plans]) as bd:
+        for p, rep in zip(plans, bd.replicates):
+            p.replicate = int(bool(rep))
+        bd.decode()
+        canvas = thumbnails_to_rgb(bd.planes, bd.infos, plans, (max(p.out_h for p in plans), max(p.out_w for p in plans)), resample, bd.colors)
+        torch.cuda.synchronize(torch.device(device))
+        views = []
+        for i, p in enumerate(plans):
+            v = canvas[i, :p.out_h, :p.out_w] if bd.infos[i].num_components != 1 else canvas[i, :p.out_h, :p.out_w, 0]
+            views.append(_exif_transposed(v, bd.orientations[i]) if exif_transpose else v)
+        return views
+
+
+def thumbnail_jpeg(datas, size, resample="bicubic", reducing_gap=2.0, exif_transpose=False, device="cuda:0", quality=75, subsampling=None,
+                   optimize=False, progressive=False, restart_interval=0):
+    """JPEG in, smaller JPEG out: decode_thumbnails' views encoded by encode_jpeg (one decode batch, one thumbnail call, one
+    encode call; the pixels never visit the host). Returns a list of bytes: encode_jpeg's file of each thumbnail, which for a
+    source without a COM segment is byte for byte what im.save(f, "JPEG", quality=..., ...) writes after
+    im.thumbnail(size, resample, reducing_gap) (Pillow copies only the comment across). `subsampling` None is save()'s
+    default: "4:2:0" for a colour file, and factors 1 x 1 in a grey file's frame header (which an explicit subsampling
+    would change, in Pillow as here)."""
+    views = decode_thumbnails(datas, size, resample, reducing_gap, exif_transpose, device)
+    if subsampling is None:
+        subsampling = ["4:4:4" if v.dim() == 2 else "4:2:0" for v in views]
+    return encode_jpeg(views, quality=quality, subsampling=subsampling, restart_interval=restart_interval, optimize=optimize,
+                       progressive=progressive)
 
 
 def _align256(v):

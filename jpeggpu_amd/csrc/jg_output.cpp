@@ -126,20 +126,21 @@ double resize_filter(int filter, double x)
     return 0.0;
 }
 
-/// Pillow's ksize: the most taps an output coordinate of in -> out can get.
-int resize_max_taps(int in, int out, int filter)
+/// Pillow's ksize: the most taps an output coordinate of a resize of `extent` input samples to `out` can get. `extent` is
+/// the input size of every resize but a thumbnail's, whose box may end inside a sample (jpeggpu_ext_resize_box_weights).
+int resize_max_taps(double extent, int out, int filter)
 {
 #pragma clang fp contract(off)
-    const double scale = static_cast<double>(in) / out;
+    const double scale = extent / out;
     const double fs    = scale < 1.0 ? 1.0 : scale;
     return static_cast<int>(std::ceil(resize_support(filter) * fs)) * 2 + 1;
 }
 
-/// Taps first .. first + count - 1 of output coordinate x.
-void resize_bounds(int in, int out, int filter, int x, int* first, int* count)
+/// Taps first .. first + count - 1 of output coordinate x: `in` samples, of which the resize covers `extent`.
+void resize_bounds(int in, double extent, int out, int filter, int x, int* first, int* count)
 {
 #pragma clang fp contract(off)
-    const double scale   = static_cast<double>(in) / out;
+    const double scale   = extent / out;
     const double fs      = scale < 1.0 ? 1.0 : scale;
     const double support = resize_support(filter) * fs;
     const double center  = (x + 0.5) * scale;
@@ -149,13 +150,14 @@ void resize_bounds(int in, int out, int filter, int x, int* first, int* count)
     *count               = hi - lo;
 }
 
-/// The table of in -> out (in != out) for output coordinates x0 .. x0 + n_out - 1 into first / count / w[n_out][stride],
-/// stride >= resize_max_taps; Pillow's precompute_coeffs + normalize_coeffs_8bpc. A coordinate outside [0, out) gets no
-/// taps (resize_carry_empty gives its `first` a value). The whole table is x0 = 0, n_out = out.
-void resize_table(int in, int out, int filter, int x0, int n_out, int* first, int* count, int* w, int stride)
+/// The table of in -> out (in != out, or an extent that is not `in`) for output coordinates x0 .. x0 + n_out - 1 into
+/// first / count / w[n_out][stride], stride >= resize_max_taps; Pillow's precompute_coeffs + normalize_coeffs_8bpc. A
+/// coordinate outside [0, out) gets no taps (resize_carry_empty gives its `first` a value). The whole table is x0 = 0,
+/// n_out = out.
+void resize_table(int in, double extent, int out, int filter, int x0, int n_out, int* first, int* count, int* w, int stride)
 {
 #pragma clang fp contract(off)
-    const double scale = static_cast<double>(in) / out;
+    const double scale = extent / out;
     const double fs    = scale < 1.0 ? 1.0 : scale;
     const double ss    = 1.0 / fs;
     const double one   = static_cast<double>(1 << kResizePrecision);
@@ -163,7 +165,7 @@ void resize_table(int in, int out, int filter, int x0, int n_out, int* first, in
     for (int e = 0; e < n_out; ++e) {
         const int64_t x = static_cast<int64_t>(x0) + e;
         int lo = 0, n = 0;
-        if (x >= 0 && x < out) resize_bounds(in, out, filter, static_cast<int>(x), &lo, &n);
+        if (x >= 0 && x < out) resize_bounds(in, extent, out, filter, static_cast<int>(x), &lo, &n);
         const double center = (x + 0.5) * scale;
         double sum          = 0.0;
         for (int j = 0; j < n; ++j) {
@@ -211,16 +213,22 @@ void resize_carry_empty(int* first, const int* count, int n_out, int origin)
     for (int e = a; e <= b; ++e) first[e] -= origin;
 }
 
-int resize_taps(int in, int out, int filter) { return in == out ? 1 : resize_max_taps(in, out, filter); }
+/// One item's axis is skipped (resize_identity) when nothing changes along it: the size stays and the extent is the size.
+bool resize_axis_same(int in, double extent, int out) { return in == out && extent == static_cast<double>(in); }
+
+int resize_taps(int in, double extent, int out, int filter) { return resize_axis_same(in, extent, out) ? 1 : resize_max_taps(extent, out, filter); }
 
 /// Table bytes of one direction: {first, count}[out] + weights[out][taps]
 size_t resize_table_bytes(int out, int taps) { return sizeof(int) * static_cast<size_t>(out) * (2 + static_cast<size_t>(taps)); }
 
 /// One direction of one item, in DISPLAYED pixels: the item's whole image of `full` samples is resized to `resized`, the
 /// output is coordinates x0 .. x0 + out - 1 of that, and the item's rectangle holds samples origin .. origin + extent - 1.
-/// A call without views resizes the rectangle itself: full = extent, resized = out, x0 = origin = 0.
+/// A call without views resizes the rectangle itself: full = extent, resized = out, x0 = origin = 0. `box`: how much of
+/// `full` the resize covers, which is `full` itself for every call but a thumbnail's (Pillow's box: it may end inside a
+/// sample, and the scale is box / resized).
 struct ResizeAxis {
     int full, resized, x0, origin, extent;
+    double box;
 };
 
 /// Samples [*lo, *hi) of the whole image that the taps of the window's coordinates read; false if no coordinate of the
@@ -229,14 +237,14 @@ bool resize_axis_range(const ResizeAxis& a, int out, int filter, int* lo, int* h
 {
     const int64_t c0 = std::max<int64_t>(a.x0, 0), c1 = std::min<int64_t>(static_cast<int64_t>(a.x0) + out, a.resized) - 1;
     if (c0 > c1) return false;
-    if (a.full == a.resized) {
+    if (resize_axis_same(a.full, a.box, a.resized)) {
         *lo = static_cast<int>(c0);
         *hi = static_cast<int>(c1) + 1;
         return true;
     }
     int f0 = 0, n0 = 0, f1 = 0, n1 = 0;
-    resize_bounds(a.full, a.resized, filter, static_cast<int>(c0), &f0, &n0);
-    resize_bounds(a.full, a.resized, filter, static_cast<int>(c1), &f1, &n1);
+    resize_bounds(a.full, a.box, a.resized, filter, static_cast<int>(c0), &f0, &n0);
+    resize_bounds(a.full, a.box, a.resized, filter, static_cast<int>(c1), &f1, &n1);
     *lo = f0;
     *hi = f1 + n1;
     return true;
@@ -247,8 +255,8 @@ bool resize_axis_range(const ResizeAxis& a, int out, int filter, int* lo, int* h
 void resize_axis_table(const ResizeAxis& a, int out, int taps, int filter, int* t)
 {
     std::vector<int> first(static_cast<size_t>(out)), cnt(static_cast<size_t>(out));
-    if (a.full == a.resized) resize_identity(a.resized, a.x0, out, first.data(), cnt.data(), t + 2 * out, taps);
-    else resize_table(a.full, a.resized, filter, a.x0, out, first.data(), cnt.data(), t + 2 * out, taps);
+    if (resize_axis_same(a.full, a.box, a.resized)) resize_identity(a.resized, a.x0, out, first.data(), cnt.data(), t + 2 * out, taps);
+    else resize_table(a.full, a.box, a.resized, filter, a.x0, out, first.data(), cnt.data(), t + 2 * out, taps);
     resize_carry_empty(first.data(), cnt.data(), out, a.origin);
     for (int x = 0; x < out; ++x) {
         t[2 * x]     = first[x];
@@ -329,9 +337,11 @@ void reverse_columns(int* t, int out, int taps)
 /// orientation, or null: 1 for all -- the plan, the scratch layout and the launches are then what they were without it.
 /// `views`: each item's window of the resize of its whole image (jpeggpu_ext_resize_view_to_tensor), or null: every item's
 /// rectangle is resized to out_w x out_h -- which is the view {out_w, out_h, 0, 0} of an item that is a whole image.
+/// `boxes` (with views only; jpeggpu_ext_thumbnail_to_rgb): item i's resize covers boxes[2 i] x boxes[2 i + 1] of its whole
+/// image, or null: all of it, as in every other call.
 jpeggpu_status plan_resize(
     const jpeggpu_ext_resize_item* items, const jpeggpu_ext_color_space* colors, const int* orients, const jpeggpu_ext_resize_view* views, int n,
-    int out_w, int out_h, int filter, ResizePlan& p)
+    int out_w, int out_h, int filter, ResizePlan& p, const float* boxes = nullptr)
 {
     if (!items || n <= 0 || n > 65535 || out_w <= 0 || out_h <= 0) return JPEGGPU_INVALID_ARGUMENT;
     if (filter != JPEGGPU_EXT_FILTER_BILINEAR && filter != JPEGGPU_EXT_FILTER_BICUBIC) return JPEGGPU_NOT_SUPPORTED;
@@ -382,13 +392,13 @@ jpeggpu_status plan_resize(
             // the stored rectangle in displayed coordinates: jpeggpu_ext_orient_rect's map, the other way
             const int sx = orient_transposes(o) ? ry : rx, sw = orient_transposes(o) ? p.in_h[i] : p.in_w[i], fx = orient_transposes(o) ? fh : fw;
             const int sy = orient_transposes(o) ? rx : ry, sh = orient_transposes(o) ? p.in_w[i] : p.in_h[i], fy = orient_transposes(o) ? fw : fh;
-            ax = ResizeAxis{fx, v.resized_w, v.x, orient_mirrors_x(o) ? fx - sx - sw : sx, sw};
-            ay = ResizeAxis{fy, v.resized_h, v.y, orient_mirrors_y(o) ? fy - sy - sh : sy, sh};
+            ax = ResizeAxis{fx, v.resized_w, v.x, orient_mirrors_x(o) ? fx - sx - sw : sx, sw, boxes ? static_cast<double>(boxes[2 * i]) : fx};
+            ay = ResizeAxis{fy, v.resized_h, v.y, orient_mirrors_y(o) ? fy - sy - sh : sy, sh, boxes ? static_cast<double>(boxes[2 * i + 1]) : fy};
         }
         if (orient_transposes(o)) std::swap(p.in_w[i], p.in_h[i]); // the displayed rectangle from here on
         if (!views) {
-            ax = ResizeAxis{p.in_w[i], out_w, 0, 0, p.in_w[i]};
-            ay = ResizeAxis{p.in_h[i], out_h, 0, 0, p.in_h[i]};
+            ax = ResizeAxis{p.in_w[i], out_w, 0, 0, p.in_w[i], static_cast<double>(p.in_w[i])};
+            ay = ResizeAxis{p.in_h[i], out_h, 0, 0, p.in_h[i], static_cast<double>(p.in_h[i])};
         }
         // the samples the taps read: columns and rows of the displayed image, all of them inside the rectangle
         int lo_x = 0, hi_x = 0, lo_y = 0, hi_y = 0;
@@ -396,8 +406,8 @@ jpeggpu_status plan_resize(
             return JPEGGPU_INVALID_ARGUMENT; // a window beside the resized image
         if (lo_x < ax.origin || hi_x > ax.origin + ax.extent || lo_y < ay.origin || hi_y > ay.origin + ay.extent) return JPEGGPU_INVALID_ARGUMENT;
         ResizeJob& j = p.jobs[i];
-        j.taps_x     = resize_taps(ax.full, ax.resized, filter);
-        j.taps_y     = resize_taps(ay.full, ay.resized, filter);
+        j.taps_x     = resize_taps(ax.full, ax.box, ax.resized, filter);
+        j.taps_y     = resize_taps(ay.full, ay.box, ay.resized, filter);
         j.mid_pitch  = pitch;
         p.off_tab_x[i] = off;
         off += align_up(resize_table_bytes(out_w, j.taps_x), 16);
@@ -528,6 +538,143 @@ jpeggpu_status plan_rgb_batch(const jpeggpu_ext_rgb_item* items, int n, int layo
     }
     p.row_tiles = static_cast<int>(tiles);
     p.t_tiles   = static_cast<int>(tiles_t);
+    return JPEGGPU_SUCCESS;
+}
+
+// ------------------------------------------------------------------------------------------------
+// thumbnails (jpeggpu_ext_thumbnail_plan, jpeggpu_ext_thumbnail_to_rgb): Pillow's size rule, and the call's layout
+// ------------------------------------------------------------------------------------------------
+
+/// Image.thumbnail's round_aspect: of floor(number) and ceil(number) the one whose aspect ratio is nearer the image's, the
+/// floor on a tie, and 1 at least. `along_x`: the result is a width beside the height `other`, else a height beside the
+/// width `other` (a height of 0 counts as a perfect fit, and then becomes 1).
+int round_aspect(double number, double aspect, int other, bool along_x)
+{
+#pragma clang fp contract(off)
+    const double lo = std::floor(number), hi = std::ceil(number);
+    const auto key = [&](double v) { return along_x ? std::fabs(aspect - v / other) : v == 0.0 ? 0.0 : std::fabs(aspect - other / v); };
+    const double pick = key(hi) < key(lo) ? hi : lo;
+    return std::max(static_cast<int>(pick), 1);
+}
+
+/// Where everything of one thumbnail call sits in d_scratch, and what the resize passes are told: the reduction's
+/// descriptors and tile list (`head` bytes, staged and copied), the reduced planes of the items that reduce, then the whole
+/// layout of a resize call with views (ResizePlan) at `off_resize`. An item that reduces enters the resize as a made-up
+/// whole image of its reduced planes -- one grey component or three RGB-coded ones, factors 1 --; any other item as itself.
+struct ThumbnailPlan {
+    ResizePlan resize;
+    std::vector<ReduceJob> jobs; // of the items that reduce, in their order
+    std::vector<int> first_tile;
+    std::vector<jpeggpu_img_info> infos;
+    std::vector<jpeggpu_img> imgs;
+    std::vector<jpeggpu_ext_resize_item> items;
+    std::vector<jpeggpu_ext_color_space> colors;
+    std::vector<jpeggpu_ext_resize_view> views;
+    std::vector<float> boxes;
+    size_t off_first = 0, head = 0, off_resize = 0, total = 0;
+    int tiles        = 0;
+    bool all_models  = false; // an item that reduces and is RGB-coded
+};
+
+/// Every check of a call's items, and its plan. `base`: the 256-aligned start of the scratch (the reduced planes' addresses
+/// go into the descriptors; the size call passes an address that nothing dereferences). Nothing here touches the device.
+jpeggpu_status plan_thumbnails(
+    const jpeggpu_ext_resize_item* items, const jpeggpu_ext_color_space* colors, const jpeggpu_ext_thumbnail* plans, int n, int canvas_w,
+    int canvas_h, int filter, uint8_t* base, ThumbnailPlan& t)
+{
+    if (!items || !plans || n <= 0 || n > 65535 || canvas_w <= 0 || canvas_h <= 0) return JPEGGPU_INVALID_ARGUMENT;
+    if (filter != JPEGGPU_EXT_FILTER_BILINEAR && filter != JPEGGPU_EXT_FILTER_BICUBIC) return JPEGGPU_NOT_SUPPORTED;
+    int nr = 0;
+    for (int i = 0; i < n; ++i) nr += plans[i].fx > 1 || plans[i].fy > 1 ? 1 : 0;
+    try {
+        t.jobs.resize(nr);
+        t.first_tile.resize(nr);
+        t.infos.resize(n);
+        t.imgs.resize(n);
+        t.items.resize(n);
+        t.colors.resize(n);
+        t.views.resize(n);
+        t.boxes.resize(2 * static_cast<size_t>(n));
+    } catch (const std::bad_alloc&) {
+        return JPEGGPU_OUT_OF_HOST_MEMORY;
+    }
+    size_t off  = align_up(sizeof(ReduceJob) * nr, 256);
+    t.off_first = off;
+    off         = align_up(off + sizeof(int) * nr, 256);
+    t.head      = off;
+    int64_t tiles = 0;
+    for (int i = 0, r = 0; i < n; ++i) {
+        const jpeggpu_ext_thumbnail& pl = plans[i];
+        const int color = colors ? static_cast<int>(colors[i]) : color_by_count(items[i].info);
+        if (items[i].crop) return JPEGGPU_INVALID_ARGUMENT; // a thumbnail is of a whole image
+        FancySource src;
+        int w = 0, h = 0;
+        const jpeggpu_status st = fancy_source(items[i].info, color, nullptr, items[i].src, pl.replicate != 0, false, src, &w, &h);
+        if (st != JPEGGPU_SUCCESS) return st;
+        if (color == JPEGGPU_EXT_COLOR_CMYK || color == JPEGGPU_EXT_COLOR_YCCK) return JPEGGPU_NOT_SUPPORTED; // Pillow's thumbnail of those is CMYK
+        if (pl.dec_w != w || pl.dec_h != h || pl.fx < 1 || pl.fy < 1 || pl.red_w != (w + pl.fx - 1) / pl.fx || pl.red_h != (h + pl.fy - 1) / pl.fy ||
+            pl.out_w < 1 || pl.out_h < 1 || pl.out_w > canvas_w || pl.out_h > canvas_h || !(pl.box_w > 0.0f) || !(pl.box_h > 0.0f) ||
+            !std::isfinite(pl.box_w) || !std::isfinite(pl.box_h))
+            return JPEGGPU_INVALID_ARGUMENT;
+        const bool reduces = pl.fx > 1 || pl.fy > 1;
+        if (pl.identity && (reduces || pl.out_w != w || pl.out_h != h)) return JPEGGPU_INVALID_ARGUMENT;
+        if (static_cast<int64_t>(pl.fx) * pl.fy > (1 << 23)) return JPEGGPU_NOT_SUPPORTED; // a box's sum must fit 32 bits
+        if (!pl.identity && pl.red_h > static_cast<int64_t>(pl.red_w) * 100 && pl.out_h < pl.red_h) return JPEGGPU_NOT_SUPPORTED; // Pillow: vertical pass first
+        t.items[i]  = items[i];
+        t.colors[i] = static_cast<jpeggpu_ext_color_space>(color);
+        t.views[i]  = jpeggpu_ext_resize_view{pl.out_w, pl.out_h, 0, 0, reduces ? 0 : pl.replicate};
+        t.boxes[2 * i]     = pl.identity ? static_cast<float>(w) : pl.box_w;
+        t.boxes[2 * i + 1] = pl.identity ? static_cast<float>(h) : pl.box_h;
+        if (!reduces) continue;
+        const int nc       = src.ncomp == 1 ? 1 : 3;
+        const int pitch    = static_cast<int>(align_up(static_cast<size_t>(pl.red_w), 16));
+        const size_t plane = static_cast<size_t>(pitch) * pl.red_h;
+        ReduceJob& j   = t.jobs[r];
+        j              = ReduceJob{};
+        j.src          = src;
+        j.width        = w;
+        j.height       = h;
+        j.fx           = pl.fx;
+        j.fy           = pl.fy;
+        j.red_w        = pl.red_w;
+        j.red_h        = pl.red_h;
+        j.dst          = base + off;
+        j.pitch        = pitch;
+        j.plane_stride = plane;
+        const int last_x = w - (pl.red_w - 1) * pl.fx, last_y = h - (pl.red_h - 1) * pl.fy; // pixels of the last column's and row's boxes
+        j.mult[0]      = reduce_multiplier(pl.fx * pl.fy);
+        j.mult[1]      = reduce_multiplier(last_x * pl.fy);
+        j.mult[2]      = reduce_multiplier(pl.fx * last_y);
+        j.mult[3]      = reduce_multiplier(last_x * last_y);
+        j.rows_per_tile = reduce_rows_per_tile(pl.fy);
+        j.tiles_x      = reduce_tiles_x(pl.red_w);
+        t.all_models   = t.all_models || fancy_all_models(src);
+        t.first_tile[r] = static_cast<int>(tiles);
+        tiles += reduce_tiles(pl.red_w, pl.red_h, pl.fy);
+        if (tiles > INT32_MAX) return JPEGGPU_INVALID_ARGUMENT;
+        jpeggpu_img_info& info = t.infos[i];
+        jpeggpu_img& img       = t.imgs[i];
+        info                   = jpeggpu_img_info{};
+        img                    = jpeggpu_img{};
+        info.num_components    = nc;
+        for (int c = 0; c < nc; ++c) {
+            info.sizes_x[c]       = pl.red_w;
+            info.sizes_y[c]       = pl.red_h;
+            info.subsampling.x[c] = 1;
+            info.subsampling.y[c] = 1;
+            img.image[c]          = j.dst + c * plane;
+            img.pitch[c]          = pitch;
+        }
+        t.items[i]  = jpeggpu_ext_resize_item{&info, nullptr, &img};
+        t.colors[i] = nc == 1 ? JPEGGPU_EXT_COLOR_GRAY : JPEGGPU_EXT_COLOR_RGB;
+        off         = align_up(off + nc * plane, 256);
+        ++r;
+    }
+    t.tiles      = static_cast<int>(tiles);
+    t.off_resize = off;
+    const jpeggpu_status st = plan_resize(t.items.data(), t.colors.data(), nullptr, t.views.data(), n, canvas_w, canvas_h, filter, t.resize, t.boxes.data());
+    if (st != JPEGGPU_SUCCESS) return st;
+    t.total = t.off_resize + t.resize.total + 256; // room to align the caller's pointer
     return JPEGGPU_SUCCESS;
 }
 
@@ -703,7 +850,7 @@ enum jpeggpu_status jpeggpu_ext_resize_weights(
         return JPEGGPU_INVALID_ARGUMENT;
     try {
         if (in == out) jg::resize_identity(out, 0, out, first, count, weights, max_taps);
-        else jg::resize_table(in, out, filter, 0, out, first, count, weights, max_taps);
+        else jg::resize_table(in, in, out, filter, 0, out, first, count, weights, max_taps);
     } catch (const std::bad_alloc&) {
         return JPEGGPU_OUT_OF_HOST_MEMORY;
     }
@@ -736,11 +883,17 @@ enum jpeggpu_status resize_to_rgb(
     size_t scratch_size,
     jpeggpu_stream_t stream,
     const struct jpeggpu_ext_tensor_spec* spec = nullptr,
-    const struct jpeggpu_ext_resize_view* views = nullptr)
+    const struct jpeggpu_ext_resize_view* views = nullptr,
+    jg::ResizePlan* planned = nullptr)
 {
-    jg::ResizePlan p;
-    const jpeggpu_status st = jg::plan_resize(items, colors, orients, views, n, out_w, out_h, filter, p);
-    if (st != JPEGGPU_SUCCESS) return st;
+    // `planned`: the caller has made the plan of these arguments and every check below already (jpeggpu_ext_thumbnail_to_rgb,
+    // which enqueues its reduction between the checks and this call's copy and launches)
+    jg::ResizePlan own;
+    jg::ResizePlan& p = planned ? *planned : own;
+    if (!planned) {
+        const jpeggpu_status st = jg::plan_resize(items, colors, orients, views, n, out_w, out_h, filter, p);
+        if (st != JPEGGPU_SUCCESS) return st;
+    }
     if (!dst || !d_scratch || (layout != JPEGGPU_EXT_NHWC && layout != JPEGGPU_EXT_NCHW) || scratch_size < p.total)
         return JPEGGPU_INVALID_ARGUMENT;
     if (spec && reinterpret_cast<uintptr_t>(dst) % jg::tensor_elem_size(spec->type) != 0) return JPEGGPU_INVALID_ARGUMENT;
@@ -1004,7 +1157,8 @@ enum jpeggpu_status jpeggpu_ext_resize_view_rect(
         out_h <= 0 || !x || !y || !w || !h)
         return JPEGGPU_INVALID_ARGUMENT;
     const bool tr = jg::orient_transposes(orientation);
-    const jg::ResizeAxis ax{tr ? full_h : full_w, view->resized_w, view->x, 0, 0}, ay{tr ? full_w : full_h, view->resized_h, view->y, 0, 0};
+    const jg::ResizeAxis ax{tr ? full_h : full_w, view->resized_w, view->x, 0, 0, static_cast<double>(tr ? full_h : full_w)};
+    const jg::ResizeAxis ay{tr ? full_w : full_h, view->resized_h, view->y, 0, 0, static_cast<double>(tr ? full_w : full_h)};
     int lo_x = 0, hi_x = 0, lo_y = 0, hi_y = 0;
     if (!jg::resize_axis_range(ax, out_w, filter, &lo_x, &hi_x) || !jg::resize_axis_range(ay, out_h, filter, &lo_y, &hi_y))
         return JPEGGPU_INVALID_ARGUMENT;
@@ -1023,7 +1177,7 @@ enum jpeggpu_status jpeggpu_ext_resize_view_weights(
         return JPEGGPU_INVALID_ARGUMENT;
     try {
         if (in == resized) jg::resize_identity(resized, x0, count_out, first, count, weights, max_taps);
-        else jg::resize_table(in, resized, filter, x0, count_out, first, count, weights, max_taps);
+        else jg::resize_table(in, in, resized, filter, x0, count_out, first, count, weights, max_taps);
     } catch (const std::bad_alloc&) {
         return JPEGGPU_OUT_OF_HOST_MEMORY;
     }
@@ -1068,6 +1222,138 @@ enum jpeggpu_status jpeggpu_ext_batch_to_rgb(
         reinterpret_cast<const jg::RgbJob*>(base), reinterpret_cast<const int*>(base + l.off_first),
         reinterpret_cast<const int*>(base + l.off_first_t), n, p.row_tiles, p.t_tiles, layout == JPEGGPU_EXT_CHW, p.all_models, stream);
     return err == hipSuccess ? JPEGGPU_SUCCESS : JPEGGPU_INTERNAL_ERROR;
+}
+
+// ------------------------------------------------------------------------------------------------
+// thumbnails: Pillow's Image.thumbnail of a batch -- draft, reduce, resize (jpeggpu_ext.h)
+// ------------------------------------------------------------------------------------------------
+
+enum jpeggpu_status jpeggpu_ext_thumbnail_plan(
+    int width, int height, int req_w, int req_h, enum jpeggpu_ext_filter filter, double reducing_gap, struct jpeggpu_ext_thumbnail* plan)
+{
+#pragma clang fp contract(off)
+    if (!plan || width < 1 || height < 1 || width > 65535 || height > 65535 || req_w < 1 || req_h < 1 || reducing_gap != reducing_gap ||
+        (reducing_gap > 0.0 && reducing_gap < 1.0) || reducing_gap > 65536.0)
+        return JPEGGPU_INVALID_ARGUMENT;
+    if (filter != JPEGGPU_EXT_FILTER_BILINEAR && filter != JPEGGPU_EXT_FILTER_BICUBIC) return JPEGGPU_NOT_SUPPORTED;
+    const bool gap = reducing_gap > 0.0;
+    jpeggpu_ext_thumbnail p{};
+    p.scale = p.fx = p.fy = 1;
+    p.dec_w = p.red_w = p.out_w = width;
+    p.dec_h = p.red_h = p.out_h = height;
+    p.box_w = static_cast<float>(width);
+    p.box_h = static_cast<float>(height);
+    p.identity = 1;
+    if (req_w >= width && req_h >= height) { // nothing happens: the full-scale decode
+        *plan = p;
+        return JPEGGPU_SUCCESS;
+    }
+    // 1. the final size (preserve_aspect_ratio)
+    int x = req_w, y = req_h;
+    const double aspect = static_cast<double>(width) / height;
+    if (static_cast<double>(x) / y >= aspect) x = jg::round_aspect(y * aspect, aspect, y, true);
+    else y = jg::round_aspect(x / aspect, aspect, x, false);
+    p.out_w = x;
+    p.out_h = y;
+    // 2. draft() for the request times the gap
+    if (gap) {
+        const double dw = req_w * reducing_gap, dh = req_h * reducing_gap;
+        const int rw = dw >= 2147483647.0 ? INT32_MAX : static_cast<int>(dw), rh = dh >= 2147483647.0 ? INT32_MAX : static_cast<int>(dh);
+        const int s = std::min(width / rw, height / rh);
+        p.scale = s >= 8 ? 8 : s >= 4 ? 4 : s >= 2 ? 2 : 1;
+    }
+    p.dec_w = p.red_w = (width + p.scale - 1) / p.scale;
+    p.dec_h = p.red_h = (height + p.scale - 1) / p.scale;
+    double bx = static_cast<double>(width) / p.scale, by = static_cast<double>(height) / p.scale;
+    // 3. the draft already hit the size
+    if (p.dec_w == x && p.dec_h == y) {
+        p.box_w = static_cast<float>(p.dec_w);
+        p.box_h = static_cast<float>(p.dec_h);
+        *plan = p;
+        return JPEGGPU_SUCCESS;
+    }
+    p.identity = 0;
+    // 4. reduce
+    if (gap) {
+        p.fx = std::max(static_cast<int>(bx / x / reducing_gap), 1);
+        p.fy = std::max(static_cast<int>(by / y / reducing_gap), 1);
+        if (p.fx > 1 || p.fy > 1) {
+            p.red_w = (p.dec_w + p.fx - 1) / p.fx;
+            p.red_h = (p.dec_h + p.fy - 1) / p.fy;
+            bx /= p.fx;
+            by /= p.fy;
+        }
+    }
+    // 5. the box passes through C as binary32
+    p.box_w = static_cast<float>(bx);
+    p.box_h = static_cast<float>(by);
+    // 6. Pillow resizes such an image vertically first
+    if (p.red_h > static_cast<int64_t>(p.red_w) * 100 && y < p.red_h) return JPEGGPU_NOT_SUPPORTED;
+    *plan = p;
+    return JPEGGPU_SUCCESS;
+}
+
+enum jpeggpu_status jpeggpu_ext_resize_box_weights(
+    int in, float extent, int out, enum jpeggpu_ext_filter filter, int* first, int* count, int* weights, int max_taps)
+{
+    if (filter != JPEGGPU_EXT_FILTER_BILINEAR && filter != JPEGGPU_EXT_FILTER_BICUBIC) return JPEGGPU_NOT_SUPPORTED;
+    if (!first || !count || !weights || in <= 0 || out <= 0 || !(extent > 0.0f) || !std::isfinite(extent) ||
+        max_taps < jg::resize_max_taps(extent, out, filter))
+        return JPEGGPU_INVALID_ARGUMENT;
+    try {
+        if (jg::resize_axis_same(in, extent, out)) jg::resize_identity(out, 0, out, first, count, weights, max_taps);
+        else jg::resize_table(in, extent, out, filter, 0, out, first, count, weights, max_taps);
+    } catch (const std::bad_alloc&) {
+        return JPEGGPU_OUT_OF_HOST_MEMORY;
+    }
+    return JPEGGPU_SUCCESS;
+}
+
+size_t jpeggpu_ext_thumbnail_scratch_size(
+    const struct jpeggpu_ext_resize_item* items, const enum jpeggpu_ext_color_space* colors, const struct jpeggpu_ext_thumbnail* plans, int n,
+    int canvas_w, int canvas_h, enum jpeggpu_ext_filter filter)
+{
+    jg::ThumbnailPlan t;
+    uint8_t* const nowhere = reinterpret_cast<uint8_t*>(uintptr_t{256}); // the planes' addresses are computed, never read
+    return jg::plan_thumbnails(items, colors, plans, n, canvas_w, canvas_h, filter, nowhere, t) == JPEGGPU_SUCCESS ? t.total : 0;
+}
+
+enum jpeggpu_status jpeggpu_ext_thumbnail_to_rgb(
+    const struct jpeggpu_ext_resize_item* items,
+    const enum jpeggpu_ext_color_space* colors,
+    const struct jpeggpu_ext_thumbnail* plans,
+    int n,
+    int canvas_w,
+    int canvas_h,
+    enum jpeggpu_ext_filter filter,
+    uint8_t* dst,
+    void* d_scratch,
+    size_t scratch_size,
+    jpeggpu_stream_t stream)
+{
+    jg::ThumbnailPlan t;
+    uint8_t* base = reinterpret_cast<uint8_t*>(jg::align_up(d_scratch ? reinterpret_cast<uintptr_t>(d_scratch) : uintptr_t{256}, 256));
+    const jpeggpu_status st = jg::plan_thumbnails(items, colors, plans, n, canvas_w, canvas_h, filter, base, t);
+    if (st != JPEGGPU_SUCCESS) return st;
+    if (!dst || !d_scratch || scratch_size < t.total) return JPEGGPU_INVALID_ARGUMENT;
+    if (t.tiles > 0) { // the reduction of the items that have factors: one launch
+        jg::ResizeStaging& rs = jg::resize_staging();
+        std::lock_guard<std::mutex> lock(rs.mu);
+        uint8_t* h = nullptr;
+        const jpeggpu_status acquired = jg::staging_acquire(rs, t.head, h);
+        if (acquired != JPEGGPU_SUCCESS) return acquired;
+        std::memcpy(h, t.jobs.data(), sizeof(jg::ReduceJob) * t.jobs.size());
+        std::memcpy(h + t.off_first, t.first_tile.data(), sizeof(int) * t.first_tile.size());
+        const jpeggpu_status copied = jg::staging_copy(rs, base, t.head, stream);
+        if (copied != JPEGGPU_SUCCESS) return copied;
+        const hipError_t err = jg::launch_reduce(reinterpret_cast<const jg::ReduceJob*>(base), reinterpret_cast<const int*>(base + t.off_first),
+                                                 static_cast<int>(t.jobs.size()), t.tiles, t.all_models, stream);
+        if (err != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
+    }
+    // the two resize passes over the canvas: a view larger than the resized image leaves zeros around it
+    const size_t used = static_cast<size_t>(base - static_cast<uint8_t*>(d_scratch)) + t.off_resize;
+    return resize_to_rgb(t.items.data(), t.colors.data(), nullptr, n, canvas_w, canvas_h, filter, JPEGGPU_EXT_NHWC, dst, base + t.off_resize,
+                         scratch_size - used, stream, nullptr, t.views.data(), &t.resize);
 }
 
 } // extern "C"

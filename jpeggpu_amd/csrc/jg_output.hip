@@ -18,6 +18,9 @@
 //   rgb_batch_kernel /      the conversion of MANY images at their own sizes, any model and orientation, from a device table
 //   rgb_batch_transposed_kernel  of items: one launch for orientations 1..4 and one for 5..8, interleaved (HWC) or planar
 //                           (CHW) output (jpeggpu_ext_batch_to_rgb)
+//   reduce_kernel           Pillow's Image.reduce of many images in one launch: integer box averages of the items' RGB into
+//                           planes the resize passes read, the stage in front of a thumbnail's resize
+//                           (jpeggpu_ext_thumbnail_to_rgb)
 //
 // Nothing here is shared with the decode path (jg_kernels.hip): the stage reads finished planes.
 #include "jg_output.hpp"
@@ -967,6 +970,75 @@ __global__ __launch_bounds__(256) void rgb_batch_transposed_kernel(const RgbJob*
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Box reduction in front of a thumbnail's resize (jpeggpu_ext_thumbnail_to_rgb): Pillow's Image.reduce((fx, fy)) of every
+// item that has factors, from a device table of items and a tile list like the batched conversion's. The source is read
+// as everywhere else -- fancy_stage, fancy_pixel -- so an item's full RGB at its decoded size is never written: only the
+// reduced planes are, which the resize passes then read as an RGB-coded (or grey) source with factors 1.
+// ------------------------------------------------------------------------------------------------
+
+/// One workgroup: kReduceTileW reduced columns of J.rows_per_tile reduced rows of one item. The source pixels under them
+/// are taken in chunks of kFancyTileW columns, and a chunk in rounds of kFancyTileH rows: a lane owns one source column of
+/// the chunk, converts its pixel of every staged row and keeps the column's sum in registers until a box ends (its last
+/// row, or the image's), then adds it to the box's sum in LDS -- fx lanes meet there, once per box and column. The sums are
+/// exact in 32 bits (the host refuses boxes of more than 2^23 pixels), and so is (sum + n / 2) * m: m <= 2^24 / n.
+/// A grey source has one plane: only its first channel is summed and written.
+template <bool kAllModels>
+__global__ __launch_bounds__(256) void reduce_kernel(const ReduceJob* __restrict__ jobs, const int* __restrict__ first_tile, int n)
+{
+    __shared__ typename Fancy<kAllModels>::Tiles s_t;
+    __shared__ uint32_t s_sum[kReduceTileH][kReduceTileW][3];
+    const int b = blockIdx.x, item = rgb_batch_item(first_tile, n, b);
+    const ReduceJob& J = jobs[item];
+    const FancySource& p = J.src;
+    const int tile = b - first_tile[item], ty = tile / J.tiles_x, tx = tile - ty * J.tiles_x;
+    const int t = threadIdx.x;
+    const int fx = J.fx, fy = J.fy;
+    const int rx0 = tx * kReduceTileW, ry0 = ty * J.rows_per_tile; // the tile's first reduced column and row
+    const int nrx = min(kReduceTileW, J.red_w - rx0), nry = min(J.rows_per_tile, J.red_h - ry0);
+    const int sx0 = rx0 * fx, sx1 = min((rx0 + nrx) * fx, J.width);  // the source columns and rows under the tile
+    const int sy0 = ry0 * fy, sy1 = min((ry0 + nry) * fy, J.height);
+    const int chans = p.ncomp == 1 ? 1 : 3;
+    for (int q = t; q < kReduceTileH * kReduceTileW * 3; q += 256) (&s_sum[0][0][0])[q] = 0; // before the first barrier below
+    for (int c0 = sx0; c0 < sx1; c0 += kFancyTileW) {
+        const int cw = min(kFancyTileW, sx1 - c0);
+        const int rx = (c0 + t) / fx - rx0; // the lane's reduced column in the tile (t < cw)
+        uint32_t acc[3] = {0, 0, 0};
+        for (int r = sy0; r < sy1; r += kFancyTileH) {
+            const int ch = min(kFancyTileH, sy1 - r);
+            int bx[Fancy<kAllModels>::kComps], by[Fancy<kAllModels>::kComps];
+            fancy_stage<true, kAllModels>(p, s_t, c0 + p.x, r + p.y, cw, ch, bx, by);
+            __syncthreads();
+            if (t < cw) {
+                for (int rr = 0; rr < ch; ++rr) {
+                    uint32_t rgb[3];
+                    fancy_pixel<kAllModels>(p, s_t, bx, by, c0 + t + p.x, r + rr + p.y, rgb);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) acc[c] += rgb[c];
+                    const int done = r + rr + 1; // source rows summed so far: a box ends on a multiple of fy, or with the image
+                    if (done % fy == 0 || done == sy1) {
+                        const int ry = (done - 1) / fy - ry0;
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            if (c < chans) atomicAdd(&s_sum[ry][rx][c], acc[c]);
+                            acc[c] = 0;
+                        }
+                    }
+                }
+            }
+            __syncthreads(); // the next round's staging overwrites the tiles; the last one: the sums are complete
+        }
+    }
+    for (int q = t; q < nry * nrx; q += 256) {
+        const int ry = q / nrx, rx = q - ry * nrx;
+        const int gx = rx0 + rx, gy = ry0 + ry;
+        const int nx = min(fx, J.width - gx * fx), ny = min(fy, J.height - gy * fy); // the box's pixels: fewer at the edges
+        const uint32_t half = static_cast<uint32_t>(nx * ny) >> 1, m = J.mult[(nx != fx ? 1 : 0) | (ny != fy ? 2 : 0)];
+        uint8_t* o = J.dst + static_cast<size_t>(gy) * J.pitch + gx;
+        for (int c = 0; c < chans; ++c) o[c * J.plane_stride] = static_cast<uint8_t>(((s_sum[ry][rx][c] + half) * m) >> 24);
+    }
+}
+
 } // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -1145,6 +1217,14 @@ hipError_t launch_rgb_batch(
             else rgb_batch_transposed_kernel<false, false><<<t_tiles, 256, 0, stream>>>(d_jobs, d_first_tile_t, n);
         }
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_reduce(const ReduceJob* d_jobs, const int* d_first_tile, int n, int tiles, bool all_models, hipStream_t stream)
+{
+    if (n <= 0 || tiles <= 0) return hipSuccess;
+    if (all_models) reduce_kernel<true><<<tiles, 256, 0, stream>>>(d_jobs, d_first_tile, n);
+    else reduce_kernel<false><<<tiles, 256, 0, stream>>>(d_jobs, d_first_tile, n);
     return hipGetLastError();
 }
 

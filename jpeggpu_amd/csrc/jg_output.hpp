@@ -185,6 +185,39 @@ hipError_t launch_rgb_batch(
     const RgbJob* d_jobs, const int* d_first_tile, const int* d_first_tile_t, int n, int row_tiles, int t_tiles, bool planar, bool all_models,
     hipStream_t stream);
 
+/// One item of a batched box reduction (launch_reduce), in device memory: the source's width x height RGB (grey: its one
+/// channel) averaged over boxes of fx x fy pixels -- fewer in the last column and row when the size is no multiple --
+/// into red_w x red_h planes, ceil(width / fx) x ceil(height / fy): Pillow's Image.reduce((fx, fy)) of the whole image.
+/// A result is ((sum + n / 2) * m) >> 24 in 32-bit unsigned arithmetic, n the pixels of its box; m =
+/// uint32(float(1 << 24) / float(n)), a binary32 division that the HOST makes (reduce_multiplier), for the four boxes an
+/// item can have: mult[0] whole, [1] last column, [2] last row, [3] both.
+struct ReduceJob {
+    FancySource src;
+    int width, height;   // the source rectangle
+    int fx, fy;
+    int red_w, red_h;
+    uint8_t* dst;        // plane c at dst + c * plane_stride, rows `pitch` apart; one plane for a grey source, else three
+    int pitch;
+    size_t plane_stride;
+    uint32_t mult[4];
+    int rows_per_tile;   // reduced rows a workgroup owns (reduce_rows_per_tile)
+    int tiles_x;         // tiles per tile row of this item
+};
+inline uint32_t reduce_multiplier(int n) { return static_cast<uint32_t>(static_cast<float>(1 << 24) / static_cast<float>(n)); }
+/// A workgroup owns kReduceTileW reduced columns and as many reduced rows, kReduceTileH at most, as fit the eight source
+/// rows that are staged at once (one row where fy exceeds four: its source rows then take several rounds).
+constexpr int kReduceTileW = 64, kReduceTileH = 8;
+inline int reduce_rows_per_tile(int fy) { return fy >= kReduceTileH ? 1 : kReduceTileH / fy; }
+inline int reduce_tiles_x(int red_w) { return (red_w + kReduceTileW - 1) / kReduceTileW; }
+inline int64_t reduce_tiles(int red_w, int red_h, int fy)
+{
+    const int rows = reduce_rows_per_tile(fy);
+    return static_cast<int64_t>(reduce_tiles_x(red_w)) * ((red_h + rows - 1) / rows);
+}
+/// The reduction of `n` items in one launch: `d_jobs` ReduceJob[n] and `d_first_tile` int[n] (each item's first workgroup;
+/// `tiles` in all) in device memory. `all_models`: some item is not grey or YCbCr (fancy_all_models).
+hipError_t launch_reduce(const ReduceJob* d_jobs, const int* d_first_tile, int n, int tiles, bool all_models, hipStream_t stream);
+
 } // namespace jg
 
 #endif // JG_OUTPUT_HPP_
