@@ -273,6 +273,24 @@ struct jpeggpu_ext_crop_info {
 enum jpeggpu_status jpeggpu_ext_set_crop(jpeggpu_decoder_t decoder, int x, int y, int width, int height);
 enum jpeggpu_status jpeggpu_ext_get_crop(jpeggpu_decoder_t decoder, struct jpeggpu_ext_crop_info* info);
 
+/* Luma-only decoding: libjpeg's out_color_space = JCS_GRAYSCALE, what Pillow's im.draft("L", size) asks for. Set before
+ * jpeggpu_decoder_parse_header and held like the scale (enable 0 or 1, else JPEGGPU_INVALID_ARGUMENT); 0, the default, leaves
+ * every call as it was: the same launches, the same bytes. With 1, by the colour model jpeggpu_ext_get_color_space reports:
+ *   - GRAY: nothing changes.
+ *   - YCBCR: the IDCT stage transforms the data units of component 0 only -- in an interleaved scan the units of each MCU
+ *     that belong to it, of a scan that codes only other components none at all (non-interleaved baseline files, the
+ *     finished coefficients of a progressive file) -- with every transform: the reference's, ISLOW, the reduced ones in
+ *     both scale modes (in JPEGGPU_EXT_SCALE_LIBJPEG component 0 keeps the block size jpeggpu_ext_get_scale_info reports).
+ *     Plane 0 holds what it holds without the setting, crops and scales included. The planes of the other components are
+ *     never written, and their pointers in jpeggpu_img are not looked at: they may be NULL. parse_header's sizes, the
+ *     buffer size and jpeggpu_ext_get_layout are unchanged; entropy decoding is unchanged (every scan is still decoded).
+ *   - RGB (an RGB-coded file): its grey needs all three components; the decode is unchanged and the grey output calls
+ *     below apply jdcolor.c's rgb_gray_convert.
+ *   - CMYK, YCCK, UNKNOWN: parse_header returns JPEGGPU_NOT_SUPPORTED (Pillow's draft("L") leaves such files as they are).
+ * A jpeggpu_ext_decode_batch call may mix luma-only and other decoders; a call without a luma-only one launches exactly
+ * the kernels it launched before. */
+enum jpeggpu_status jpeggpu_ext_set_luma_only(jpeggpu_decoder_t decoder, int enable);
+
 /* Stage timing: when enabled, jpeggpu_decoder_decode records HIP events on the caller's stream
  * between its launches; after the stream has been synchronised jpeggpu_ext_get_stage_ms returns the
  * mean milliseconds per stage (summed over scans) of the decodes since the previous call (at most the
@@ -986,6 +1004,74 @@ enum jpeggpu_status jpeggpu_ext_batch_to_rgb(
     const struct jpeggpu_ext_rgb_item* items,
     int n,
     enum jpeggpu_ext_image_layout layout,
+    void* d_scratch,
+    size_t scratch_size,
+    jpeggpu_stream_t stream);
+
+/* Grey output: one 8-bit channel, what libjpeg hands a caller of out_color_space = JCS_GRAYSCALE and Pillow's
+ * np.asarray(im) shows after im.draft("L", size). The grey of a pixel: for GRAY and YCBCR sources component 0, upsampled
+ * only where its sampling factors are below the frame's largest (by the fancy or the replicating rule of the RGB calls);
+ * for RGB sources (RGB-coded files) (19595 R + 38470 G + 7471 B + 32768) >> 16 of the three upsampled samples, jdcolor.c's
+ * rgb_gray_convert. CMYK, YCCK and UNKNOWN: JPEGGPU_NOT_SUPPORTED. Of a GRAY or YCBCR source only component 0's plane is read:
+ * src->image[1..] may be NULL, as after a decode with jpeggpu_ext_set_luma_only; `info` (and `crop`) are parse_header's
+ * (jpeggpu_ext_get_crop's) as they are, all components of them. Three calls, the grey forms of three RGB calls, with their
+ * validation rules, statuses and the same contract that nothing is written on an error:
+ *   - jpeggpu_ext_crop_to_gray_oriented: jpeggpu_ext_crop_to_rgbi_oriented for one channel, displayed pixel (x, y) at
+ *     dst + y * dst_pitch + x, dst_pitch >= the displayed width. `crop` NULL: the whole image, at its extent by its planes
+ *     (jpeggpu_ext_planes_to_rgbi_oriented). One launch.
+ *   - jpeggpu_ext_batch_to_gray: jpeggpu_ext_batch_to_rgb for one channel; the items are jpeggpu_ext_rgb_item, of which
+ *     plane_stride is not read and dst_pitch >= the displayed width. Scratch: jpeggpu_ext_batch_gray_scratch_size(n), with
+ *     that call's rules. At most two launches. An item of orientation 1 whose component 0 has the largest factors is a
+ *     pitched copy of a window of plane 0: it is made by the same launch, in 16-byte pieces.
+ *   - jpeggpu_ext_resize_view_to_gray_tensor: jpeggpu_ext_resize_view_to_tensor for one channel -- views, orientations,
+ *     per-item flips, the four element types -- with `views` NULL meaning whole rectangles resized to out_w x out_h, which
+ *     makes it the grey form of jpeggpu_ext_resize_to_rgb and jpeggpu_ext_resize_to_tensor too. The arithmetic is Pillow's
+ *     ImagingResample on one 8-bit band: the weights of jpeggpu_ext_resize_weights, the rounding and the clamp to 8 bits
+ *     after the first pass are those of the RGB calls. Normalisation uses spec->mean[0] and spec->std[0] alone. `dst` is n
+ *     x out_h x out_w x 1 (NHWC) or n x 1 x out_h x out_w (NCHW): the same bytes. Scratch:
+ *     jpeggpu_ext_resize_view_to_gray_scratch_size of the same arguments (0 for arguments the call would refuse); the rows
+ *     between the passes hold one byte per pixel, out_w padded to 16, a third of the RGB call's. Two launches, three
+ *     when items of orientations 5..8 stand beside others.
+ * Thumbnails stay RGB-only: jpeggpu_ext_thumbnail_plan, jpeggpu_ext_thumbnail_to_rgb and the Python thumbnail calls have no
+ * grey form. */
+enum jpeggpu_status jpeggpu_ext_crop_to_gray_oriented(
+    const struct jpeggpu_img_info* info,
+    enum jpeggpu_ext_color_space color,
+    int orientation,
+    int replicate,
+    const struct jpeggpu_ext_crop_info* crop,
+    const struct jpeggpu_img* src,
+    uint8_t* dst,
+    int dst_pitch,
+    jpeggpu_stream_t stream);
+size_t jpeggpu_ext_batch_gray_scratch_size(int n);
+enum jpeggpu_status jpeggpu_ext_batch_to_gray(
+    const struct jpeggpu_ext_rgb_item* items,
+    int n,
+    void* d_scratch,
+    size_t scratch_size,
+    jpeggpu_stream_t stream);
+size_t jpeggpu_ext_resize_view_to_gray_scratch_size(
+    const struct jpeggpu_ext_resize_item* items,
+    const enum jpeggpu_ext_color_space* colors,
+    const int* orientations,
+    const struct jpeggpu_ext_resize_view* views,
+    int n,
+    int out_w,
+    int out_h,
+    enum jpeggpu_ext_filter filter);
+enum jpeggpu_status jpeggpu_ext_resize_view_to_gray_tensor(
+    const struct jpeggpu_ext_resize_item* items,
+    const enum jpeggpu_ext_color_space* colors,
+    const int* orientations,
+    const struct jpeggpu_ext_resize_view* views,
+    int n,
+    int out_w,
+    int out_h,
+    enum jpeggpu_ext_filter filter,
+    enum jpeggpu_ext_output_layout layout,
+    const struct jpeggpu_ext_tensor_spec* spec,
+    void* dst,
     void* d_scratch,
     size_t scratch_size,
     jpeggpu_stream_t stream);

@@ -348,6 +348,15 @@ def lib():
         L.jpeggpu_ext_thumbnail_to_rgb.argtypes = [
             C.POINTER(ResizeItem), C.POINTER(C.c_int), C.POINTER(Thumbnail), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
             C.c_size_t, C.c_void_p]
+    if hasattr(L, "jpeggpu_ext_set_luma_only"):  # grey output (_newer_symbol)
+        L.jpeggpu_ext_set_luma_only.argtypes = [dec, C.c_int]
+        L.jpeggpu_ext_crop_to_gray_oriented.argtypes = L.jpeggpu_ext_crop_to_rgbi_oriented.argtypes
+        L.jpeggpu_ext_batch_gray_scratch_size.restype = C.c_size_t
+        L.jpeggpu_ext_batch_gray_scratch_size.argtypes = [C.c_int]
+        L.jpeggpu_ext_batch_to_gray.argtypes = [C.POINTER(RgbItem), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.jpeggpu_ext_resize_view_to_gray_scratch_size.restype = C.c_size_t
+        L.jpeggpu_ext_resize_view_to_gray_scratch_size.argtypes = L.jpeggpu_ext_resize_view_scratch_size.argtypes
+        L.jpeggpu_ext_resize_view_to_gray_tensor.argtypes = L.jpeggpu_ext_resize_view_to_tensor.argtypes
     _lib = L
     return L
 
@@ -501,6 +510,12 @@ class Decoder:
         if method not in IDCT_METHODS:
             raise ValueError("idct method %r is not one of %s" % (method, ", ".join(IDCT_METHODS)))
         _check(lib().jpeggpu_ext_set_idct(self._h, IDCT_METHODS[method]), "jpeggpu_ext_set_idct")
+
+    def set_luma_only(self, on: bool = True):
+        """jpeggpu_ext_set_luma_only: from the next parse_header on, only component 0 of a YCbCr file is transformed and
+        written (libjpeg's JCS_GRAYSCALE; the other planes' pointers may be 0); grey and RGB-coded files are decoded as
+        ever, CMYK and YCCK ones refused by parse_header (NOT_SUPPORTED)."""
+        _check(_newer_symbol("jpeggpu_ext_set_luma_only")(self._h, 1 if on else 0), "jpeggpu_ext_set_luma_only")
 
     def set_crop(self, x: int, y: int, w: int, h: int):
         """Decode only the rectangle (x, y, w, h) of the image at the decoder's scale from the next parse_header on
@@ -681,7 +696,7 @@ def _frame_size(info):
 
 def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp=False, device_scan=False, scale=1,
                      idct="reference", crop=None, scale_mode="uniform", return_color=False, progressive=False,
-                     displayed_crop=False, return_orientation=False):
+                     displayed_crop=False, return_orientation=False, luma_only=False):
     """Convenience wrapper used by tests: full call sequence on torch's current stream, returns the
     planes as torch uint8 tensors on `device` (torch is only the allocator / stream provider). With
     `device_scan` the restart markers are found on the device and a status it reports there is raised.
@@ -692,11 +707,14 @@ def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp
     (Decoder.color_space) is appended to what is returned. `progressive`: progressive files are decoded
     (Decoder.set_progressive); with `return_tmp` the ProgressiveInfo follows the layout. `displayed_crop`: `crop` is in
     displayed coordinates of the file's EXIF orientation (the header is parsed once more to learn it; orient_rect).
-    `return_orientation`: Decoder.orientation is appended last."""
+    `return_orientation`: Decoder.orientation is appended last. `luma_only`: Decoder.set_luma_only -- of a YCbCr file only
+    plane 0 is allocated, decoded and returned (`planes` has one entry; `info` still describes all components)."""
     import torch
 
     dec = Decoder(subseq_bytes)
     try:
+        if luma_only:
+            dec.set_luma_only(True)
         if scale != 1:
             dec.set_scale(scale)
         if scale_mode != "uniform":
@@ -718,7 +736,7 @@ def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp
         base = (tmp.data_ptr() + 255) // 256 * 256
         stream = torch.cuda.current_stream(torch.device(device)).cuda_stream
         planes = [torch.empty((info.sizes_y[c], info.sizes_x[c]), dtype=torch.uint8, device=device)
-                  for c in range(info.num_components)]
+                  for c in range(1 if luma_only and dec.color_space() == ColorSpace.YCBCR else info.num_components)]
         dec.transfer(base, n, stream)
         dec.decode([p.data_ptr() for p in planes], [p.stride(0) for p in planes], base, n, stream)
         torch.cuda.synchronize(torch.device(device))
@@ -793,6 +811,11 @@ def crop_to_rgb(planes, info, crop_info, device=None, replicate=False, color=Non
     return _to_rgb("jpeggpu_ext_crop_to_rgbi", planes, info, crop_info, device, True, replicate, color, orientation)
 
 
+def _max_factors(info):
+    n = info.num_components
+    return max(info.subsampling.x[:n]), max(info.subsampling.y[:n])
+
+
 def _needs_replication(info, scale):
     """libjpeg replicates instead of fancy upsampling at 1/8 (jdsample.c); it matters where subsampling is left."""
     n = info.num_components
@@ -825,6 +848,47 @@ def decode_to_rgb(data: bytes, device="cuda:0", device_scan=False, crop=None, sc
     rgb = planes_to_rgb(planes, info, fancy=True, replicate=_needs_replication(info, scale), color=color, orientation=o[0] if o else None)
     torch.cuda.synchronize(torch.device(device))
     return rgb
+
+
+def planes_to_gray(planes, info, crop_info=None, device=None, replicate=False, color=None, orientation=1):
+    """jpeggpu_ext_crop_to_gray_oriented on torch's current stream: the planes of a decode (the windows of a cropped one, with
+    its `crop_info`; of a luma-only decode plane 0 alone) -> the (h, w) uint8 grey of the image or rectangle as `orientation`
+    displays it, (w, h) for 5..8. The grey is component 0 of grey and YCbCr files, upsampled where its sampling factors are
+    below the largest, and jdcolor.c's rgb_gray_convert of RGB-coded ones. `color`: the planes' ColorSpace; None: grey or
+    YCbCr by the number of components. `replicate`: as in planes_to_rgb."""
+    import torch
+
+    device = planes[0].device if device is None else torch.device(device)
+    src = _img(planes[:info.num_components])
+    w, h = _frame_size(info) if crop_info is None else (crop_info.width, crop_info.height)
+    ow, oh = (h, w) if 5 <= int(orientation) <= 8 else (w, h)
+    cs = int(color) if color is not None else int(_item_colors(None, [info])[0])
+    out = torch.empty((oh, ow), dtype=torch.uint8, device=device)
+    name = "jpeggpu_ext_crop_to_gray_oriented"
+    _check(_newer_symbol(name)(C.byref(info), cs, int(orientation), int(bool(replicate)), C.byref(crop_info) if crop_info is not None else None,
+                               C.byref(src), out.data_ptr(), ow, torch.cuda.current_stream(device).cuda_stream), name)
+    return out
+
+
+def decode_to_gray(data: bytes, device="cuda:0", crop=None, scale=1, exif_transpose=False):
+    """Decode a JPEG to an (H, W) uint8 grey tensor on `device` the way libjpeg-turbo does for out_color_space =
+    JCS_GRAYSCALE: of a YCbCr file only the luma component goes through the IDCT (Decoder.set_luma_only: ISLOW at full size,
+    the reduced IDCTs at `scale` = d in 2, 4, 8 in the libjpeg scale mode), a grey file is its one component, an RGB-coded
+    file is decoded whole and converted by jdcolor.c's rgb_gray_convert. Meant to equal np.asarray(im) after
+    im.draft("L", (W // d, H // d)) in Pillow; CMYK and YCCK files, which Pillow's draft("L") leaves as they are, raise
+    JpegGpuError (NOT_SUPPORTED). `crop` = (x, y, w, h) in pixels of the image at the scale and `exif_transpose` as in
+    decode_to_rgb: ImageOps.exif_transpose(im) and im.crop applied after the draft."""
+    import torch
+
+    kw = dict(device=device, idct="islow", scale=scale, scale_mode="libjpeg", return_color=True, progressive=True, luma_only=True,
+              return_orientation=True, displayed_crop=bool(exif_transpose))
+    if crop is not None:
+        planes, info, crop_info, color, o = decode_to_planes(data, crop=crop, **kw)
+    else:
+        (planes, info, color, o), crop_info = decode_to_planes(data, **kw), None
+    gray = planes_to_gray(planes, info, crop_info, replicate=_needs_replication(info, scale), color=color, orientation=o if exif_transpose else 1)
+    torch.cuda.synchronize(torch.device(device))
+    return gray
 
 
 def parse_headers(decoders, buffers, num_threads=4):
@@ -918,6 +982,17 @@ def _channel_triple(v, default, name):
     return v
 
 
+def _channel_single(v, name):
+    """A grey call's `mean` or `std`: one number, or a sequence of one."""
+    try:
+        v = list(v)
+    except TypeError:
+        return float(v)
+    if len(v) != 1:
+        raise ValueError("%s must be one number for mode \"L\"" % name)
+    return float(v[0])
+
+
 def _resize_plan(planes_list, infos, size, crop_infos, filt, layout="NHWC", colors=None, orientations=None, views=None, replicates=None,
                  dtype=None, flips=None):
     """What the batched resize wrappers share ahead of a launch. The arguments are checked before a device or `infos` is
@@ -954,13 +1029,16 @@ def _resize_plan(planes_list, infos, size, crop_infos, filt, layout="NHWC", colo
 
 
 def _resize(planes_list, infos, size, crop_infos, filt, layout, colors=None, orientations=None, views=None, replicates=None, tensor=None,
-            out=None):
+            out=None, gray=False):
     """The one launch path of the batched resize calls, on torch's current stream. `tensor`: None -- the uint8 RGB call
     _resize_plan names -- or (dtype, mean, std, flips): jpeggpu_ext_resize_to_tensor (with `views`
-    jpeggpu_ext_resize_view_to_tensor), whose scratch is the uint8 call's, by the arguments given."""
+    jpeggpu_ext_resize_view_to_tensor), whose scratch is the uint8 call's, by the arguments given. `gray` (with `tensor`): one
+    channel -- jpeggpu_ext_resize_view_to_gray_tensor and its own scratch size, `views` or not; `mean` and `std` are one number."""
     import torch
 
     dtype, mean, std, flips = tensor if tensor is not None else (None, None, None, None)
+    if gray:
+        mean, std = (None if v is None else _channel_single(v, name) for v, name in ((mean, "mean"), (std, "std")))
     sizer, call, lead, dims, _keep = _resize_plan(planes_list, infos, size, crop_infos, filt, layout, colors, orientations, views, replicates,
                                                   dtype, flips)
     n, w, h, _ = dims
@@ -974,12 +1052,17 @@ def _resize(planes_list, infos, size, crop_infos, filt, layout, colors=None, ori
             flip_bytes = (C.c_ubyte * n)(*[1 if f else 0 for f in flips])
             ts.flips = C.cast(flip_bytes, C.POINTER(C.c_ubyte))
         spec = (C.byref(ts),)
-        if views is None:
+        if gray:  # (items, colours or NULL, orientations or NULL, views or NULL) for the call and its sizer alike
+            sizer, call = "jpeggpu_ext_resize_view_to_gray_scratch_size", "jpeggpu_ext_resize_view_to_gray_tensor"
+            _newer_symbol(call)
+            lead = args = lead if views is not None else (lead + (None, None))[:3] + (None,)
+        elif views is None:
             call, args = "jpeggpu_ext_resize_to_tensor", (lead + (None, None))[:3]  # (items, colours or NULL, orientations or NULL)
     else:
         dtype = torch.uint8
     device = planes_list[0][0].device
-    shape = (n, h, w, 3) if layout == "NHWC" else (n, 3, h, w)
+    chans = 1 if gray else 3
+    shape = (n, h, w, chans) if layout == "NHWC" else (n, chans, h, w)
     if out is None:
         out = torch.empty(shape, dtype=dtype, device=device)
     elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous():
@@ -1028,6 +1111,20 @@ def resize_to_tensor(planes_list, infos, size, crop_infos=None, filt="bilinear",
                    tensor=(torch.float32 if dtype is None else dtype, mean, std, flips), out=out)
 
 
+def resize_to_gray(planes_list, infos, size, crop_infos=None, filt="bilinear", layout="NHWC", colors=None, orientations=None, views=None,
+                   replicates=None, dtype=None, mean=None, std=None, flips=None, out=None):
+    """jpeggpu_ext_resize_view_to_gray_tensor on torch's current stream: resize_to_tensor (or, with `views`,
+    resize_views_to_tensor) for ONE channel -- the grey of every item (planes_to_gray; of a luma-only decode plane 0 alone)
+    resampled with Pillow's arithmetic on an "L" image. Returns n x h x w x 1 ("NHWC") or n x 1 x h x w ("NCHW") of `dtype`
+    (uint8 unless `dtype`, `mean` or `std` says otherwise); `mean` and `std` are one number each."""
+    import torch
+
+    if dtype is None:
+        dtype = torch.uint8 if mean is None and std is None else torch.float32
+    return _resize(planes_list, infos, size, crop_infos, filt, layout, colors, orientations, views, replicates, (dtype, mean, std, flips), out,
+                   gray=True)
+
+
 class BatchDecode:
     """The front half of every batched pipeline: a list of JPEGs decoded to planes by ONE jpeggpu_ext_decode_batch call on
     torch's current stream of `device`. Construction gives every file its Decoder with the settings below, parses its
@@ -1050,10 +1147,11 @@ class BatchDecode:
     set), `colors`, `orientations` (the file's own EXIF orientation), `replicates` (where libjpeg replicates instead of
     fancy upsampling) and `tmps`; `transferred_bytes` is what one round of transfers copies, `batch` the Batch.
     `coefficients_only`: no planes are allocated (`planes[i]` is empty) and the batch stops in front of the IDCT stage
-    (Batch.set_coefficients_only): the front half of transcode_jpeg."""
+    (Batch.set_coefficients_only): the front half of transcode_jpeg. `luma_only`: a truth value for all files or one per
+    file -- Decoder.set_luma_only; of a YCbCr file only plane 0 is allocated and decoded (`planes[i]` has one entry)."""
 
     def __init__(self, datas, device="cuda:0", hint=None, idct="islow", progressive=True, scales=None, scale_mode="libjpeg", crops=None,
-                 crop_hooks=None, coefficients_only=False):
+                 crop_hooks=None, coefficients_only=False, luma_only=False):
         import torch
 
         dev = torch.device(device)
@@ -1069,6 +1167,9 @@ class BatchDecode:
                 dec.set_batch_hint(len(datas) if hint is None else hint)
                 dec.set_idct(idct)
                 dec.set_progressive(progressive)
+                luma = bool(luma_only[i] if isinstance(luma_only, (list, tuple)) else luma_only)
+                if luma:
+                    dec.set_luma_only(True)
                 scale = 1 if scales is None else scales[i]
                 if scale != 1:
                     dec.set_scale(scale)
@@ -1085,8 +1186,9 @@ class BatchDecode:
                 nb = dec.get_buffer_size()
                 tmp = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
                 base = _align256(tmp.data_ptr())
+                ncomp = 1 if luma and dec.color_space() == ColorSpace.YCBCR else info.num_components
                 planes = [] if coefficients_only else [torch.empty((info.sizes_y[c], info.sizes_x[c]), dtype=torch.uint8, device=dev)
-                                                       for c in range(info.num_components)]
+                                                       for c in range(ncomp)]
                 dec.transfer(base, nb, self._stream)
                 self.tmps.append(tmp)
                 self._entries.append((dec, [p.data_ptr() for p in planes], [p.stride(0) for p in planes], base, nb))
@@ -1148,7 +1250,7 @@ def _per_image_args(n, crops, scales):
 
 
 def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", device="cuda:0", scales=None, exif_transpose=False,
-                   dtype=None, mean=None, std=None, flips=None):
+                   dtype=None, mean=None, std=None, flips=None, mode="RGB"):
     """A training pipeline's decode: every JPEG of `datas` (of any colour model: decode_to_rgb) decoded with libjpeg-turbo's
     arithmetic (ISLOW IDCT, fancy upsampling), only the rectangle crops[i] = (x, y, w, h) of it (None: the whole image), in ONE jpeggpu_ext_decode_batch
     call, then resized to `size` (int: square; (h, w)) with Pillow's BILINEAR or BICUBIC arithmetic by one
@@ -1167,21 +1269,32 @@ def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", devi
     ToTensor + Normalize(mean, std), with the draws (crops[i], flips[i]) supplied by the caller -- as a tensor of `dtype`:
     torch.float32 if `mean` or `std` is given, torch.uint8 (the bytes, flipped where asked) if only `flips` is; float16 and
     bfloat16 are the float32 result converted once. With all four None the call is what it was, call for call. An empty
-    `datas` is refused where the batch is created: a JpegGpuError from jpeggpu_ext_batch_create (INVALID_ARGUMENT)."""
+    `datas` is refused where the batch is created: a JpegGpuError from jpeggpu_ext_batch_create (INVALID_ARGUMENT).
+    `mode`: "RGB", or "L" -- one channel, n x h x w x 1 or n x 1 x h x w: the files are decoded luma-only (decode_to_gray)
+    and resized by one jpeggpu_ext_resize_view_to_gray_tensor call, equal to im.draft("L", ...) in place of draft("RGB") and
+    convert("RGB") above; `mean` and `std` are then one number each (or 1-tuples)."""
     import torch
 
+    if mode not in ("RGB", "L"):
+        raise ValueError("mode %r is not one of RGB, L" % (mode,))
     crops, scales = _per_image_args(len(datas), crops, scales)
     crop_args = dict(crop_hooks=_displayed_crops(crops)) if exif_transpose else dict(crops=crops)
-    with BatchDecode(datas, device, scales=scales, **crop_args) as bd:
-        if any(bd.replicates):
-            i = bd.replicates.index(True)
+    with BatchDecode(datas, device, scales=scales, luma_only=mode == "L", **crop_args) as bd:
+        replicates = bd.replicates
+        if mode == "L":  # only component 0 is upsampled, and nearly always it has the largest factors: nothing to replicate
+            replicates = [r and (i.subsampling.x[0], i.subsampling.y[0]) != _max_factors(i) for r, i in zip(replicates, bd.infos)]
+        if any(replicates):
+            i = replicates.index(True)
             info = bd.infos[i]
             raise ValueError("image %d at scale 1/8 has subsampling left (%s x %s): libjpeg replicates there, which the "
                              "batched resize does not reproduce" % (i, list(info.subsampling.x[:info.num_components]),
                                                                   list(info.subsampling.y[:info.num_components])))
         bd.decode()
         orients = bd.orientations if exif_transpose else None
-        if dtype is None and mean is None and std is None and flips is None:
+        if mode == "L":
+            out = resize_to_gray(bd.planes, bd.infos, size, bd.crop_infos, filt, layout, colors=bd.colors, orientations=orients, dtype=dtype,
+                                 mean=mean, std=std, flips=flips)
+        elif dtype is None and mean is None and std is None and flips is None:
             out = resize_to_rgb(bd.planes, bd.infos, size, bd.crop_infos, filt, layout, colors=bd.colors, orientations=orients)
         else:
             if dtype is None:
@@ -1272,7 +1385,7 @@ def resize_views_to_tensor(planes_list, infos, views, size, crop_infos=None, fil
 
 
 def decode_center_cropped(datas, resize=256, crop=224, filt="bilinear", layout="NHWC", device="cuda:0", scales=None, exif_transpose=False,
-                          dtype=None, mean=None, std=None):
+                          dtype=None, mean=None, std=None, mode="RGB"):
     """An evaluation pipeline's decode: torchvision's Resize(resize) + CenterCrop(crop) (+ ToTensor + Normalize with `dtype`,
     `mean`, `std` as in decode_resized) of every JPEG of `datas`, equal to Pillow's
     Image.open(f).convert("RGB").resize((rw, rh), filter) cropped (or zero-padded, where the resized image is smaller than
@@ -1283,9 +1396,12 @@ def decode_center_cropped(datas, resize=256, crop=224, filt="bilinear", layout="
     (draft_scale gives Pillow's choice) and the resized size is computed from its size at that scale; 1/8 with subsampling
     left is taken (libjpeg's replication). `exif_transpose`: the transform runs on the displayed image
     (ImageOps.exif_transpose after draft()). Files of every colour model and progressive files are taken. Returns n x ch x
-    cw x 3 ("NHWC") or n x 3 x ch x cw ("NCHW"), uint8 unless `dtype`, `mean` or `std` says otherwise."""
+    cw x 3 ("NHWC") or n x 3 x ch x cw ("NCHW"), uint8 unless `dtype`, `mean` or `std` says otherwise. `mode`: "RGB", or "L" as in
+    decode_resized: one channel of luma-only decodes, `mean` and `std` one number each."""
     import torch
 
+    if mode not in ("RGB", "L"):
+        raise ValueError("mode %r is not one of RGB, L" % (mode,))
     n = len(datas)
     _, scales = _per_image_args(n, None, scales)
     if n == 0:
@@ -1299,11 +1415,14 @@ def decode_center_cropped(datas, resize=256, crop=224, filt="bilinear", layout="
         views.append((rw, rh) + center_crop_window(rw, rh, (ch, cw)))  # (the hooks run in the files' order)
         return resize_view_rect(w0, h0, views[-1], (ch, cw), filt, o)
 
-    with BatchDecode(datas, device, scales=scales, crop_hooks=[window] * n) as bd:
+    with BatchDecode(datas, device, scales=scales, crop_hooks=[window] * n, luma_only=mode == "L") as bd:
         bd.decode()
-        out = resize_views_to_tensor(bd.planes, bd.infos, views, (ch, cw), bd.crop_infos, filt, layout, colors=bd.colors,
-                                     orientations=bd.orientations if exif_transpose else [1] * n, replicates=bd.replicates, dtype=dtype,
-                                     mean=mean, std=std)
+        kw = dict(colors=bd.colors, orientations=bd.orientations if exif_transpose else [1] * n, replicates=bd.replicates, dtype=dtype,
+                  mean=mean, std=std)
+        if mode == "L":
+            out = resize_to_gray(bd.planes, bd.infos, (ch, cw), bd.crop_infos, filt, layout, views=views, **kw)
+        else:
+            out = resize_views_to_tensor(bd.planes, bd.infos, views, (ch, cw), bd.crop_infos, filt, layout, **kw)
         torch.cuda.synchronize(torch.device(device))
         return out
 
@@ -1549,6 +1668,67 @@ def decode_batch_to_rgb(datas, device="cuda:0", crops=None, scales=None, exif_tr
     with BatchDecode(datas, device, scales=scales, **crop_args) as bd:
         bd.decode()
         out = batch_to_rgb(bd.planes, bd.infos, bd.crop_infos, bd.colors, bd.orientations if exif_transpose else [1] * n, bd.replicates, layout)
+        torch.cuda.synchronize(torch.device(device))
+        return out
+
+
+def batch_to_gray(planes_list, infos, crop_infos=None, colors=None, orientations=None, replicates=None):
+    """jpeggpu_ext_batch_to_gray on torch's current stream: batch_to_rgb for one channel -- every decoded image i (of a
+    luma-only decode plane 0 alone) as its (oh, ow) uint8 grey (planes_to_gray), at most two launches for the list. The
+    tensors are views into ONE allocation, each image starting on a multiple of 256 bytes, its rows unpadded."""
+    import torch
+
+    n = len(planes_list)
+    for name, v in (("infos", infos), ("crop_infos", crop_infos), ("colors", colors), ("orientations", orientations), ("replicates", replicates)):
+        if v is not None and len(v) != n:
+            raise ValueError("%s must have one entry per image" % name)
+    if n == 0:
+        return []
+    device = planes_list[0][0].device
+    colors = _item_colors(colors, infos)
+    orientations = [1] * n if orientations is None else [int(o) for o in orientations]
+    if any(not 1 <= o <= 8 for o in orientations):
+        raise ValueError("orientations must be 1..8")
+    items, _keep = _resize_items(planes_list, infos, crop_infos)  # info, crop and src are the resize item's
+    sizes, offsets, total = [], [], 0
+    for i in range(n):
+        ci = crop_infos[i] if crop_infos is not None else None
+        w, h = (ci.width, ci.height) if ci is not None else _frame_size(infos[i])
+        sizes.append((h, w) if orientations[i] >= 5 else (w, h))
+        offsets.append(total)
+        total = _align256(total + w * h)
+    out = torch.empty(total + 256, dtype=torch.uint8, device=device)
+    start = _align256(out.data_ptr()) - out.data_ptr()
+    it = (RgbItem * n)()
+    for i, (ow, oh) in enumerate(sizes):
+        it[i].info, it[i].crop, it[i].src = items[i].info, items[i].crop, items[i].src
+        it[i].color, it[i].orientation = int(colors[i]), orientations[i]
+        it[i].replicate = int(bool(replicates[i])) if replicates is not None else 0
+        it[i].dst = out.data_ptr() + start + offsets[i]
+        it[i].dst_pitch = ow
+    need = _newer_symbol("jpeggpu_ext_batch_gray_scratch_size")(n)
+    scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    _check(_newer_symbol("jpeggpu_ext_batch_to_gray")(it, n, scratch.data_ptr(), need, torch.cuda.current_stream(device).cuda_stream),
+           "jpeggpu_ext_batch_to_gray")
+    # the scratch tensor is freed by torch's caching allocator in stream order: it is not reused before the launches ran
+    return [out[start + off:start + off + ow * oh].view(oh, ow) for (ow, oh), off in zip(sizes, offsets)]
+
+
+def decode_batch_to_gray(datas, device="cuda:0", crops=None, scales=None, exif_transpose=False):
+    """A list of JPEGs in, a list of (h, w) uint8 grey tensors out, each at its own size: every file decoded luma-only in ONE
+    jpeggpu_ext_decode_batch call and written by ONE jpeggpu_ext_batch_to_gray call, with one synchronise at the end. Element
+    i equals decode_to_gray(datas[i], crop=crops[i], scale=scales[i], exif_transpose=exif_transpose); the arguments are
+    decode_batch_to_rgb's. A CMYK or YCCK file raises JpegGpuError (NOT_SUPPORTED). An empty list gives []."""
+    import torch
+
+    n = len(datas)
+    crops, scales = _per_image_args(n, crops, scales)
+    if n == 0:
+        return []
+    crop_args = dict(crop_hooks=_displayed_crops(crops)) if exif_transpose else dict(crops=crops)
+    with BatchDecode(datas, device, scales=scales, luma_only=True, **crop_args) as bd:
+        bd.decode()
+        out = batch_to_gray(bd.planes, bd.infos, bd.crop_infos, bd.colors, bd.orientations if exif_transpose else [1] * n, bd.replicates)
         torch.cuda.synchronize(torch.device(device))
         return out
 

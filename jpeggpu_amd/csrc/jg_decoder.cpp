@@ -447,6 +447,13 @@ enum jpeggpu_status jpeggpu_ext_set_scale_mode(jpeggpu_decoder_t decoder, enum j
     return JPEGGPU_SUCCESS;
 }
 
+enum jpeggpu_status jpeggpu_ext_set_luma_only(jpeggpu_decoder_t decoder, int enable)
+{
+    if (!decoder || (enable != 0 && enable != 1)) return JPEGGPU_INVALID_ARGUMENT;
+    decoder->d.luma_only_request = enable != 0;
+    return JPEGGPU_SUCCESS;
+}
+
 enum jpeggpu_status jpeggpu_ext_get_scale_info(jpeggpu_decoder_t decoder, struct jpeggpu_ext_scale_info* info)
 {
     if (!decoder || !info) return JPEGGPU_INVALID_ARGUMENT;

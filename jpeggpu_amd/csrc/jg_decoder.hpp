@@ -149,6 +149,11 @@ struct Decoder {
     int transcode_crop[4] = {0, 0, 0, 0};
     // jpeggpu_ext_set_transcode_frame: the new file keeps the source's frame layout (1) or must have the encoder's (0)
     int transcode_frame = 0;
+    // jpeggpu_ext_set_luma_only, taking effect at the next parse_header like the scale. `luma_only`: the parsed image is a
+    // YCbCr one whose IDCT stage transforms component 0 alone (build_jobs lists only its units, IdctDraft); the planes of the
+    // other components are neither asked for nor written. Grey and RGB-coded images are decoded as ever.
+    bool luma_only_request = false;
+    bool luma_only         = false;
     int plane_x(int c) const { return crop.on ? crop.wx[c] : full_x(c); } // what decode writes
     int plane_y(int c) const { return crop.on ? crop.wy[c] : full_y(c); }
     JG_LOCAL bool set_crop_window();

@@ -402,9 +402,15 @@ struct IdctWindow {
 /// units k[lg][0 .. n[lg]) of it, and unit w of the class is unit k[lg][w % n[lg]] of MCU w / n[lg] of the job (of its
 /// window, for a cropped one). Such a job carries IdctParams::scale_log2 = kDraftScale | log2 d, which every kernel of
 /// the other jobs reads as "not mine"; `on` is what the draft instantiations ask.
+///
+/// Luma-only decoding (jpeggpu_ext_set_luma_only) uses the same lists in every scale mode: the classes hold the units of
+/// component 0 alone, so the units of the other components are never transformed (a scan without component 0: no unit at
+/// all). `on` is kDraftOn for such a job too, except at full size with the reference IDCT, whose 8x8 units are not ISLOW
+/// ones: kDraftLumaReference, the jobs of idct_kernel<LumaJobs<JS>>.
 constexpr uint8_t kDraftScale = 4;
+constexpr uint8_t kDraftOn = 1, kDraftLumaReference = 2;
 struct IdctDraft {
-    uint8_t on;
+    uint8_t on; // 0, kDraftOn or kDraftLumaReference
     uint8_t n[4];
     uint8_t k[4][kMaxDuPerMcu];
     uint8_t comp_lg[kMaxComp]; // per scan component

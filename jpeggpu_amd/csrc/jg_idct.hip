@@ -7,7 +7,9 @@
 //   idct_kernel<IslowJobs<..>>  full size with libjpeg-turbo's jpeg_idct_islow (jidctint.c; jpeggpu_ext_set_idct)
 //   ..<CropJobs<..>>        the units of a job's MCU window only (jpeggpu_ext_set_crop)
 //   ..<DraftJobs<..>>       the units of one block size of a job in libjpeg's scale mode, whose components differ in size
-//                                                                    (jdmaster.c; jpeggpu_ext_set_scale_mode)
+//                                                                    (jdmaster.c; jpeggpu_ext_set_scale_mode), and of a
+//                                                                    luma-only job: component 0's (jpeggpu_ext_set_luma_only)
+//   ..<LumaJobs<..>>        component 0's units of a full-size luma-only job with the reference transform
 //
 // Integer arithmetic throughout: no MFMA. Every kernel takes a job source (jg_jobs.h), as the kernels of the entropy pass
 // do; the sources that only this stage knows (an array's full-size jobs, the jobs of one IDCT method) are defined here.
@@ -246,12 +248,35 @@ struct IsDraft<DraftJobs<JS>> : std::true_type {
 template <class JS>
 struct IsDraft<IslowJobs<JS>> : IsDraft<JS> {
 };
+/// Luma-only decoding (jpeggpu_ext_set_luma_only) needs no kernel of its own: build_jobs lists the units of component 0
+/// alone in the job's classes, and the DraftJobs instantiations transform what is listed -- fewer units, no branch per
+/// unit. One case they do not cover: 8x8 units with the REFERENCE transform (theirs are ISLOW). LumaJobs<JS> is that
+/// instantiation of idct_kernel: class 0 of the jobs marked kDraftLumaReference, which the DraftJobs ones count no units
+/// of. The launch picks it only when a call holds such a job.
+template <class JS>
+struct LumaJobs {
+    JS js;
+    __device__ __forceinline__ const ScanJob& get() const { return js.get(); }
+};
+template <class JS>
+struct IsDraft<LumaJobs<JS>> : std::true_type {
+};
+/// IdctDraft::on of the jobs whose classes a job source takes.
+template <class JS>
+struct DraftOn : std::integral_constant<uint8_t, kDraftOn> {
+};
+template <class JS>
+struct DraftOn<LumaJobs<JS>> : std::integral_constant<uint8_t, kDraftLumaReference> {
+};
+template <class JS>
+struct DraftOn<IslowJobs<JS>> : DraftOn<JS> {
+};
 /// Units of class kLg in the job: its MCUs (the window's, for a cropped job: IdctParams::num_du counts those) times the
 /// class's units per MCU. 0 for a job of another kind and for one the device front end refused (num_du == 0).
-template <int kLg>
+template <int kLg, uint8_t kOn = kDraftOn>
 __device__ __forceinline__ int draft_num_du(const ScanJob& j)
 {
-    if (!j.draft.on) return 0;
+    if (j.draft.on != kOn) return 0;
     return static_cast<int>(magic_quot(static_cast<uint32_t>(j.ip.num_du), j.ip.du_per_mcu_mul, j.ip.du_per_mcu_shift)) * j.draft.n[kLg];
 }
 /// Unit w of class kLg: window_unit's answer for data unit k[kLg][w % n] of MCU w / n.
@@ -339,7 +364,7 @@ __global__ __launch_bounds__(256) void idct_kernel(JS js)
     using X = typename IdctOf<JS>::type;
     constexpr bool kCrop = IsCropped<JS>::value;
     constexpr bool kDraft = IsDraft<JS>::value; // the 8x8 units of a JPEGGPU_EXT_SCALE_LIBJPEG job (draft_unit)
-    static_assert(!kDraft || X::kIslow, "blocks of size 8 of that mode take the ISLOW arithmetic");
+    static_assert(!kDraft || X::kIslow == (DraftOn<JS>::value == kDraftOn), "blocks of size 8 of that mode take the ISLOW arithmetic; LumaJobs: the reference's");
     __shared__ __attribute__((aligned(16))) int16_t s_blk[kIdctDuPerBlock][kIdctDuStride]; // [unit][col * 8 + row]
     // ISLOW: the int workspace between the passes, [unit][row * 8 + col] (+8: as s_blk)
     __shared__ __attribute__((aligned(16))) int s_ws[X::kIslow ? kIdctDuPerBlock : 1][X::kIslow ? kIdctDuStride : 4];
@@ -368,7 +393,7 @@ __global__ __launch_bounds__(256) void idct_kernel(JS js)
     const IdctParams& ip = J.ip;
     const int du0        = blockIdx.x * kIdctDuPerWg;
     const int num_du     = [&] {
-        if constexpr (kDraft) return draft_num_du<0>(js.get());
+        if constexpr (kDraft) return draft_num_du<0, DraftOn<JS>::value>(js.get());
         else return ip.num_du;
     }();
     if (du0 >= num_du) return;
@@ -909,6 +934,7 @@ hipError_t launch_idct(const JS& js, const JobExtent& e, int grid_y, hipStream_t
     if (e.draft_sizes & 2u) launch(idct_scaled_kernel<D, 1>, D{js});
     if (e.draft_sizes & 4u) launch(idct_scaled_kernel<D, 2>, D{js});
     if (e.draft_sizes & 8u) launch(idct_scaled_kernel<D, 3>, D{js});
+    if (e.luma_reference) launch(idct_kernel<LumaJobs<JS>>, LumaJobs<JS>{js});
     return hipGetLastError();
 }
 

@@ -2189,7 +2189,8 @@ void extend(JobExtent& e, const ScanJob& job)
     e.max_idct_blocks = blocks > e.max_idct_blocks ? blocks : e.max_idct_blocks;
     e.scales |= 1u << job.ip.scale_log2;
     if (job.ip.scale_log2 == 0) e.methods |= 1u << job.ip.idct_method;
-    if (job.draft.on)
+    if (job.draft.on == kDraftLumaReference) e.luma_reference = e.luma_reference || job.draft.n[0] != 0;
+    else if (job.draft.on)
         for (int lg = 0; lg < 4; ++lg)
             if (job.draft.n[lg]) e.draft_sizes |= 1u << lg;
     if (job.win.mcus_x != 0) e.crop = true;

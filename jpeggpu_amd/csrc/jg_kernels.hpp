@@ -33,6 +33,7 @@ struct JobExtent {
     int subseq_words    = 0; // identical for every job of a launch
     uint32_t scales     = 0; // bit s: a job decodes at 1 / 2^s (IdctParams::scale_log2; bits kDraftScale + 1 ..: jobs of the next line)
     uint32_t draft_sizes = 0; // bit lg: a JPEGGPU_EXT_SCALE_LIBJPEG job has components of block size 8 >> lg (IdctDraft)
+    bool luma_reference = false; // a full-size luma-only job of the reference IDCT (kDraftLumaReference): idct_kernel<LumaJobs<..>>
     uint32_t methods    = 0; // bit m: a full-size job takes IDCT method m (IdctParams::idct_method)
     bool crop           = false; // a job has an MCU window (jpeggpu_ext_set_crop, ScanJob::win): the IDCT's CropJobs instantiations
     uint32_t max_tab_bytes = 0;      // largest write-pass table pack

@@ -343,6 +343,75 @@ enum jpeggpu_status jpeggpu_ext_batch_to_rgb(
         reinterpret_cast<const int*>(base + p.at.off_first_t), n, p.row_tiles, p.t_tiles, layout == JPEGGPU_EXT_CHW, p.all_models, stream));
 }
 
+// Grey output (jg_output_gray.hip): one image, a batch at the items' own sizes, a batch resized to one 1-channel tensor.
+enum jpeggpu_status jpeggpu_ext_crop_to_gray_oriented(
+    const struct jpeggpu_img_info* info, enum jpeggpu_ext_color_space color, int orientation, int replicate,
+    const struct jpeggpu_ext_crop_info* crop, const struct jpeggpu_img* src, uint8_t* dst, int dst_pitch, jpeggpu_stream_t stream)
+{
+    if (!jg::orient_valid(orientation)) return JPEGGPU_INVALID_ARGUMENT;
+    if (!info || !src || !dst || (crop && (crop->width <= 0 || crop->height <= 0 || crop->x < 0 || crop->y < 0))) return JPEGGPU_INVALID_ARGUMENT;
+    jg::RgbJob j{};
+    const jpeggpu_status st = jg::fancy_source(info, color, crop, src, replicate != 0, true, j.src, &j.width, &j.height, true);
+    if (st != JPEGGPU_SUCCESS) return st;
+    const bool tr = jg::orient_transposes(orientation);
+    if (j.width <= 0 || j.height <= 0 || dst_pitch < (tr ? j.height : j.width)) return JPEGGPU_INVALID_ARGUMENT;
+    j.dst       = dst;
+    j.dst_pitch = dst_pitch;
+    j.flips     = (jg::orient_mirrors_x(orientation) ? 1 : 0) | (jg::orient_mirrors_y(orientation) ? 2 : 0);
+    j.tiles_x   = jg::rgb_batch_tiles_x(j.width, tr);
+    return launched(jg::launch_gray_image(j, tr, stream));
+}
+
+enum jpeggpu_status jpeggpu_ext_batch_to_gray(
+    const struct jpeggpu_ext_rgb_item* items, int n, void* d_scratch, size_t scratch_size, jpeggpu_stream_t stream)
+{
+    jg::RgbBatchPlan p;
+    const jpeggpu_status st = jg::plan_rgb_batch(items, n, JPEGGPU_EXT_HWC, p, true);
+    if (st != JPEGGPU_SUCCESS) return st;
+    if (!d_scratch || scratch_size < jpeggpu_ext_batch_gray_scratch_size(n)) return JPEGGPU_INVALID_ARGUMENT;
+    uint8_t* base = scratch_base(d_scratch);
+    std::lock_guard<std::mutex> lock(staging().mu);
+    const jpeggpu_status staged = stage_and_copy(
+        p.at.total,
+        [&](uint8_t* h) {
+            jg::fill_rgb_batch(p, h);
+            return JPEGGPU_SUCCESS;
+        },
+        base, stream);
+    if (staged != JPEGGPU_SUCCESS) return staged;
+    return launched(jg::launch_gray_batch(
+        reinterpret_cast<const jg::RgbJob*>(base), reinterpret_cast<const int*>(base + p.at.off_first),
+        reinterpret_cast<const int*>(base + p.at.off_first_t), n, p.row_tiles, p.t_tiles, p.all_models, stream));
+}
+
+enum jpeggpu_status jpeggpu_ext_resize_view_to_gray_tensor(
+    const struct jpeggpu_ext_resize_item* items, const enum jpeggpu_ext_color_space* colors, const int* orientations,
+    const struct jpeggpu_ext_resize_view* views, int n, int out_w, int out_h, enum jpeggpu_ext_filter filter,
+    enum jpeggpu_ext_output_layout layout, const struct jpeggpu_ext_tensor_spec* spec, void* dst, void* d_scratch, size_t scratch_size,
+    jpeggpu_stream_t stream)
+{
+    jpeggpu_ext_tensor_spec s;
+    if (spec) { // one mean and one std: the tensor calls' checks on three copies of them
+        s = *spec;
+        s.mean[1] = s.mean[2] = s.mean[0];
+        s.std[1] = s.std[2] = s.std[0];
+    }
+    jpeggpu_status st = jg::tensor_spec(spec ? &s : nullptr, s);
+    if (st != JPEGGPU_SUCCESS) return st;
+    jg::ResizePlan p;
+    st = jg::plan_resize(items, colors, orientations, views, n, out_w, out_h, filter, p, nullptr, true);
+    if (st != JPEGGPU_SUCCESS) return st;
+    if (!dst || !d_scratch || (layout != JPEGGPU_EXT_NHWC && layout != JPEGGPU_EXT_NCHW) || scratch_size < p.total) return JPEGGPU_INVALID_ARGUMENT;
+    if (reinterpret_cast<uintptr_t>(dst) % jg::tensor_elem_size(s.type) != 0) return JPEGGPU_INVALID_ARGUMENT;
+    uint8_t* base = scratch_base(d_scratch);
+    std::lock_guard<std::mutex> lock(staging().mu);
+    const jpeggpu_status staged = stage_and_copy(p.head, [&](uint8_t* h) { return jg::fill_resize(p, s.flips, base, h); }, base, stream);
+    if (staged != JPEGGPU_SUCCESS) return staged;
+    return launched(jg::launch_gray_resize(
+        reinterpret_cast<const jg::ResizeJob*>(base), reinterpret_cast<const int*>(base + p.off_first), reinterpret_cast<const int*>(base + p.off_first_t), n,
+        p.h_tiles, p.t_tiles, p.out_w, p.out_h, p.all_models, s.type, s.mean[0], s.std[0], dst, stream));
+}
+
 // Thumbnails: Pillow's Image.thumbnail of a batch -- draft, reduce, resize.
 enum jpeggpu_status jpeggpu_ext_thumbnail_to_rgb(
     const struct jpeggpu_ext_resize_item* items, const enum jpeggpu_ext_color_space* colors, const struct jpeggpu_ext_thumbnail* plans, int n,

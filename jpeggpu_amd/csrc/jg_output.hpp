@@ -72,6 +72,26 @@ hipError_t launch_rgb_batch(
 /// `tiles` in all) in device memory. `all_models`: some item is not grey or YCbCr (fancy_all_models).
 hipError_t launch_reduce(const ReduceJob* d_jobs, const int* d_first_tile, int n, int tiles, bool all_models, hipStream_t stream);
 
+// The grey output stage (jg_output_gray.hip). Its sources are fancy_source's with `gray` set: one component (grey and
+// YCbCr files: component 0) or three (RGB-coded files: jdcolor.c's rgb_gray_convert); `rgb`: some item of the call is of
+// the second kind, and every kernel of the call then runs as the instantiation that stages three tiles.
+
+/// One image to grey where job.flips and `transposes` display it: the tiles of launch_gray_batch for a descriptor that
+/// travels as a kernel argument. One launch.
+hipError_t launch_gray_image(const RgbJob& job, bool transposes, hipStream_t stream);
+
+/// launch_rgb_batch for one 8-bit channel: displayed pixel (x, y) of an item at dst + y * dst_pitch + x. At most two
+/// launches. An item of orientation 1 whose component 0 is at full resolution is copied, in the row kernel's launch.
+hipError_t launch_gray_batch(
+    const RgbJob* d_jobs, const int* d_first_tile, const int* d_first_tile_t, int n, int row_tiles, int t_tiles, bool rgb, hipStream_t stream);
+
+/// launch_resize_tensor for one channel: ResizeJob::mid holds one byte per pixel, `dst` is n x out_h x out_w elements of
+/// `type`, normalised by the one `mean` and `std` unless they are bytes. Two launches, three with items of 5..8 beside
+/// others.
+hipError_t launch_gray_resize(
+    const ResizeJob* d_jobs, const int* d_first_tile, const int* d_first_tile_t, int n, int h_tiles, int t_tiles, int out_w, int out_h, bool rgb,
+    int type, float mean, float std, void* dst, hipStream_t stream);
+
 } // namespace jg
 
 #endif // JG_OUTPUT_HPP_

@@ -37,31 +37,36 @@ int color_by_count(const jpeggpu_img_info* info)
 
 jpeggpu_status fancy_source(
     const jpeggpu_img_info* info, int color, const jpeggpu_ext_crop_info* crop, const jpeggpu_img* src, bool replicate, bool window_first,
-    FancySource& s, int* rect_w, int* rect_h)
+    FancySource& s, int* rect_w, int* rect_h, bool gray)
 {
     if (!info || !src) return JPEGGPU_INVALID_ARGUMENT;
     const int nc = info->num_components;
     const int fits = color == JPEGGPU_EXT_COLOR_GRAY ? 1 : color == JPEGGPU_EXT_COLOR_YCBCR || color == JPEGGPU_EXT_COLOR_RGB ? 3
                      : color == JPEGGPU_EXT_COLOR_CMYK || color == JPEGGPU_EXT_COLOR_YCCK ? 4 : 0;
     if (fits == 0 || nc != fits) return JPEGGPU_NOT_SUPPORTED; // without a model: 2 or 4 components, as jpeggpu_ext_planes_to_rgbi
+    if (gray && fits == 4) return JPEGGPU_NOT_SUPPORTED;       // libjpeg has no grey of CMYK and YCCK
+    // the components the output reads: all of them, or for a grey of a YCbCr source component 0 alone (the others' planes
+    // are not looked at: a luma-only decode has none); the sampling maxima are the frame's either way
+    const int used = gray && color != JPEGGPU_EXT_COLOR_RGB ? 1 : nc;
     int sx_max = 0, sy_max = 0;
     bool outside = false; // a window that does not lie inside its plane
     for (int c = 0; c < nc; ++c) {
         if (info->subsampling.x[c] < 1 || info->subsampling.y[c] < 1) return JPEGGPU_INVALID_ARGUMENT;
+        sx_max = std::max(sx_max, info->subsampling.x[c]);
+        sy_max = std::max(sy_max, info->subsampling.y[c]);
+        if (c >= used) continue;
         if (!src->image[c] || src->pitch[c] < info->sizes_x[c] || info->sizes_x[c] < 1 || info->sizes_y[c] < 1)
             return JPEGGPU_INVALID_ARGUMENT;
         if (crop)
             outside = outside || crop->origin_x[c] < 0 || crop->origin_y[c] < 0 || crop->origin_x[c] + info->sizes_x[c] > crop->full_x[c] ||
                       crop->origin_y[c] + info->sizes_y[c] > crop->full_y[c];
-        sx_max = std::max(sx_max, info->subsampling.x[c]);
-        sy_max = std::max(sy_max, info->subsampling.y[c]);
     }
     if (outside && window_first) return JPEGGPU_INVALID_ARGUMENT;
     for (int c = 0; c < nc; ++c) // libjpeg upsamples by integral ratios only (jdsample.c)
         if (sx_max % info->subsampling.x[c] != 0 || sy_max % info->subsampling.y[c] != 0) return JPEGGPU_NOT_SUPPORTED;
     if (crop) {
         if (crop->width <= 0 || crop->height <= 0 || crop->x < 0 || crop->y < 0 || outside) return JPEGGPU_INVALID_ARGUMENT;
-        for (int c = 0; c < nc; ++c) { // every sample the rectangle reads, and its halo, clipped to the plane, is in the window
+        for (int c = 0; c < used; ++c) { // every sample the rectangle reads, and its halo, clipped to the plane, is in the window
             const int hr = sx_max / info->subsampling.x[c], vr = sy_max / info->subsampling.y[c];
             const int lo_x = std::max(crop->x / hr - 1, 0), hi_x = std::min((crop->x + crop->width - 1) / hr + 1, crop->full_x[c] - 1);
             const int lo_y = std::max(crop->y / vr - 1, 0), hi_y = std::min((crop->y + crop->height - 1) / vr + 1, crop->full_y[c] - 1);
@@ -72,7 +77,7 @@ jpeggpu_status fancy_source(
     }
     s = FancySource{};
     for (int k = 0; k < 4; ++k) {
-        const int cc = k < nc ? k : 0;
+        const int cc = k < used ? k : 0;
         FancyComp& f = s.comp[k];
         f.plane      = src->image[cc];
         f.pitch      = src->pitch[cc];
@@ -86,8 +91,8 @@ jpeggpu_status fancy_source(
     }
     s.x     = crop ? crop->x : 0;
     s.y     = crop ? crop->y : 0;
-    s.ncomp = nc;
-    s.color = color;
+    s.ncomp = used;
+    s.color = used == nc ? color : JPEGGPU_EXT_COLOR_GRAY;
     if (rect_w && rect_h) {
         if (crop) {
             *rect_w = crop->width;
@@ -299,7 +304,7 @@ void reverse_columns(int* t, int out, int taps)
 
 jpeggpu_status plan_resize(
     const jpeggpu_ext_resize_item* items, const jpeggpu_ext_color_space* colors, const int* orients, const jpeggpu_ext_resize_view* views, int n,
-    int out_w, int out_h, int filter, ResizePlan& p, const float* boxes)
+    int out_w, int out_h, int filter, ResizePlan& p, const float* boxes, bool gray)
 {
     if (!items || n <= 0 || n > 65535 || out_w <= 0 || out_h <= 0) return JPEGGPU_INVALID_ARGUMENT;
     if (!filter_known(filter)) return JPEGGPU_NOT_SUPPORTED;
@@ -335,12 +340,12 @@ jpeggpu_status plan_resize(
         off           = align_up(off + sizeof(int) * n, 256);
     }
     int64_t tiles  = 0, tiles_t = 0;
-    const int pitch = static_cast<int>(align_up(3 * static_cast<size_t>(out_w), 16));
+    const int pitch = static_cast<int>(align_up((gray ? 1 : 3) * static_cast<size_t>(out_w), 16)); // a grey call keeps one byte per pixel
     for (int i = 0; i < n; ++i) {
         // the item's checks and its descriptor, without the table and scratch pointers; in_w x in_h is the rectangle
         p.jobs[i] = ResizeJob{};
         const jpeggpu_status st = fancy_source(items[i].info, colors ? static_cast<int>(colors[i]) : color_by_count(items[i].info), items[i].crop,
-                                               items[i].src, views && views[i].replicate != 0, false, p.jobs[i].src, &p.in_w[i], &p.in_h[i]);
+                                               items[i].src, views && views[i].replicate != 0, false, p.jobs[i].src, &p.in_w[i], &p.in_h[i], gray);
         if (st != JPEGGPU_SUCCESS) return st;
         p.all_models = p.all_models || fancy_all_models(p.jobs[i].src);
         const int o = p.orient[i];
@@ -445,7 +450,7 @@ RgbBatchLayout rgb_batch_layout(int n)
     return l;
 }
 
-jpeggpu_status plan_rgb_batch(const jpeggpu_ext_rgb_item* items, int n, int layout, RgbBatchPlan& p)
+jpeggpu_status plan_rgb_batch(const jpeggpu_ext_rgb_item* items, int n, int layout, RgbBatchPlan& p, bool gray)
 {
     if (!items || n <= 0 || n > 65535 || (layout != JPEGGPU_EXT_HWC && layout != JPEGGPU_EXT_CHW)) return JPEGGPU_INVALID_ARGUMENT;
     try {
@@ -462,11 +467,12 @@ jpeggpu_status plan_rgb_batch(const jpeggpu_ext_rgb_item* items, int n, int layo
         if (!it.dst || !orient_valid(it.orientation)) return JPEGGPU_INVALID_ARGUMENT;
         RgbJob& j = p.jobs[i];
         j         = RgbJob{};
-        const jpeggpu_status st = fancy_source(it.info, it.color, it.crop, it.src, it.replicate != 0, true, j.src, &j.width, &j.height);
+        const jpeggpu_status st = fancy_source(it.info, it.color, it.crop, it.src, it.replicate != 0, true, j.src, &j.width, &j.height, gray);
         if (st != JPEGGPU_SUCCESS) return st;
         const bool tr = orient_transposes(it.orientation);
         const int64_t ow = tr ? j.height : j.width, oh = tr ? j.width : j.height; // the displayed rectangle
-        if (layout == JPEGGPU_EXT_HWC ? it.dst_pitch < 3 * ow : it.dst_pitch < ow || it.plane_stride < static_cast<size_t>(it.dst_pitch) * oh)
+        if (gray ? it.dst_pitch < ow
+                 : layout == JPEGGPU_EXT_HWC ? it.dst_pitch < 3 * ow : it.dst_pitch < ow || it.plane_stride < static_cast<size_t>(it.dst_pitch) * oh)
             return JPEGGPU_INVALID_ARGUMENT;
         p.all_models   = p.all_models || fancy_all_models(j.src);
         j.dst          = it.dst;
@@ -708,10 +714,10 @@ namespace {
 
 size_t resize_scratch_size(
     const jpeggpu_ext_resize_item* items, const jpeggpu_ext_color_space* colors, const int* orients, int n, int out_w, int out_h, int filter,
-    const jpeggpu_ext_resize_view* views = nullptr)
+    const jpeggpu_ext_resize_view* views = nullptr, bool gray = false)
 {
     jg::ResizePlan p;
-    return jg::plan_resize(items, colors, orients, views, n, out_w, out_h, filter, p) == JPEGGPU_SUCCESS ? p.total : 0;
+    return jg::plan_resize(items, colors, orients, views, n, out_w, out_h, filter, p, nullptr, gray) == JPEGGPU_SUCCESS ? p.total : 0;
 }
 
 /// The whole table of `in` samples, of which the resize covers `extent`, to `out`, or its coordinates x0 .. x0 + n_out - 1
@@ -761,6 +767,15 @@ size_t jpeggpu_ext_resize_view_scratch_size(
 {
     return views ? resize_scratch_size(items, colors, orientations, n, out_w, out_h, filter, views) : 0;
 }
+
+size_t jpeggpu_ext_resize_view_to_gray_scratch_size(
+    const struct jpeggpu_ext_resize_item* items, const enum jpeggpu_ext_color_space* colors, const int* orientations,
+    const struct jpeggpu_ext_resize_view* views, int n, int out_w, int out_h, enum jpeggpu_ext_filter filter)
+{
+    return resize_scratch_size(items, colors, orientations, n, out_w, out_h, filter, views, true);
+}
+
+size_t jpeggpu_ext_batch_gray_scratch_size(int n) { return jpeggpu_ext_batch_rgb_scratch_size(n); }
 
 size_t jpeggpu_ext_batch_rgb_scratch_size(int n)
 {

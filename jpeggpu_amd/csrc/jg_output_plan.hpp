@@ -25,11 +25,14 @@ int color_by_count(const jpeggpu_img_info* info);
 /// the colour conversion stays jdcolor.c's. `rect_w` x `rect_h`, if asked for: the rectangle -- the crop's, or else the
 /// image's extent by its planes (callers that convert a whole image bring their own size, and the kernel's clamp is
 /// their edge rule).
+/// `gray`: the source of a GREY output (jg_output_gray.hip): CMYK and YCCK are JPEGGPU_NOT_SUPPORTED; of a grey or YCbCr
+/// image only component 0 is described (ncomp 1, colour GRAY, its ratios still those to the frame's largest factors) and
+/// only its plane and window are looked at -- the other planes may be NULL --; an RGB-coded image keeps its three.
 /// The statuses and their order are API. One order differs between the callers: jpeggpu_ext_crop_to_rgbi_* refuse a
 /// window outside its plane before non-integral ratios (`window_first`), jpeggpu_ext_resize_to_rgb after them.
 jpeggpu_status fancy_source(
     const jpeggpu_img_info* info, int color, const jpeggpu_ext_crop_info* crop, const jpeggpu_img* src, bool replicate, bool window_first,
-    FancySource& s, int* rect_w = nullptr, int* rect_h = nullptr);
+    FancySource& s, int* rect_w = nullptr, int* rect_h = nullptr, bool gray = false);
 
 /// Pillow's ksize: the most taps an output coordinate of a resize of `extent` input samples to `out` can get. `extent` is
 /// the input size of every resize but a thumbnail's, whose box may end inside a sample (jpeggpu_ext_resize_box_weights).
@@ -70,10 +73,11 @@ struct ResizePlan {
 /// `views`: each item's window of the resize of its whole image (jpeggpu_ext_resize_view_to_tensor), or null: every item's
 /// rectangle is resized to out_w x out_h -- which is the view {out_w, out_h, 0, 0} of an item that is a whole image.
 /// `boxes` (with views only; jpeggpu_ext_thumbnail_to_rgb): item i's resize covers boxes[2 i] x boxes[2 i + 1] of its whole
-/// image, or null: all of it, as in every other call.
+/// image, or null: all of it, as in every other call. `gray`: a call of the grey stage -- the items' sources are grey ones
+/// (fancy_source), a row of `mid` holds one byte per pixel, and `all_models` says that an item is RGB-coded.
 jpeggpu_status plan_resize(
     const jpeggpu_ext_resize_item* items, const jpeggpu_ext_color_space* colors, const int* orients, const jpeggpu_ext_resize_view* views, int n,
-    int out_w, int out_h, int filter, ResizePlan& p, const float* boxes = nullptr);
+    int out_w, int out_h, int filter, ResizePlan& p, const float* boxes = nullptr, bool gray = false);
 
 /// The staged part of a planned call, written to the `p.head` bytes at `h`: the descriptors, bound to the 256-aligned
 /// device address `base` of the scratch, the first-tile lists, and each item's two tables -- those of the DISPLAYED axes,
@@ -97,8 +101,10 @@ struct RgbBatchPlan {
     bool all_models = false; // an item that is not grey or YCbCr (fancy_all_models)
 };
 
-/// Every check of a call's items, and their descriptors.
-jpeggpu_status plan_rgb_batch(const jpeggpu_ext_rgb_item* items, int n, int layout, RgbBatchPlan& p);
+/// Every check of a call's items, and their descriptors. `gray`: a call of the grey stage (jpeggpu_ext_batch_to_gray) --
+/// grey sources, one byte per pixel (dst_pitch >= the displayed width; `layout` and plane_stride are not read), and
+/// `all_models` says that an item is RGB-coded.
+jpeggpu_status plan_rgb_batch(const jpeggpu_ext_rgb_item* items, int n, int layout, RgbBatchPlan& p, bool gray = false);
 /// The plan's staged bytes, written to the `p.at.total` bytes at `h`.
 void fill_rgb_batch(const RgbBatchPlan& p, uint8_t* h);
 

@@ -295,6 +295,14 @@ jpeggpu_status Decoder::plan_image(jpeggpu_img_info* img_info, const uint8_t* da
     }
     if (st != JPEGGPU_SUCCESS) return st;
     const Stream& s = reader.s;
+    luma_only = false;
+    if (luma_only_request) { // libjpeg's out_color_space = JCS_GRAYSCALE: grey and RGB-coded files need every component
+        if (s.color_space != kColorGray && s.color_space != kColorYCbCr && s.color_space != kColorRGB) {
+            logger.log("luma-only decoding: colour model %d has no grey\n", s.color_space);
+            return JPEGGPU_NOT_SUPPORTED;
+        }
+        luma_only = s.color_space == kColorYCbCr;
+    }
     set_block_sizes();
     if (want_crop) {
         if (!set_crop_window()) {
@@ -374,6 +382,7 @@ jpeggpu_status build_jobs(
     if (!d.parsed) return JPEGGPU_INVALID_ARGUMENT;
     const Stream& s = d.reader.s;
     for (int c = 0; c < s.num_comp && planes; ++c) {
+        if (c > 0 && d.luma_only) break; // never written: the pointers may be NULL
         if (!img->image[c] || img->pitch[c] < d.plane_x(c)) return JPEGGPU_INVALID_ARGUMENT;
     }
     if (!d_tmp || (reinterpret_cast<uintptr_t>(d_tmp) & 255)) return JPEGGPU_INVALID_ARGUMENT;
@@ -423,7 +432,8 @@ jpeggpu_status build_jobs(
         ip.du_per_mcu  = sc.du_per_mcu;
         ip.mcus_x      = sc.mcus_x;
         ip.first_mcu   = sc.first_mcu;
-        ip.scale_log2  = static_cast<uint8_t>(d.draft ? kDraftScale | d.scale_log2 : d.scale_log2);
+        // a luma-only job lists its units by block size as a draft job does: no kernel of the other jobs takes it
+        ip.scale_log2  = static_cast<uint8_t>(d.draft || d.luma_only ? kDraftScale | d.scale_log2 : d.scale_log2);
         ip.idct_method = d.scale_log2 == 0 ? d.idct_method : kIdctReference;
         {
             const MagicDiv a = magic_div(static_cast<uint32_t>(sc.du_per_mcu)), b = magic_div(static_cast<uint32_t>(sc.mcus_x));
@@ -450,12 +460,16 @@ jpeggpu_status build_jobs(
             ip.qidx[a]          = fc.qidx;
             ip.plane[a]         = img->image[c.comp_idx];
         }
-        if (d.draft) { // the units of the MCU by block size (IdctDraft)
+        if (d.draft || d.luma_only) { // the units of the MCU by block size (IdctDraft); luma only: those of component 0
             IdctDraft& dr = job.draft;
-            dr.on         = 1;
+            // 8x8 blocks of kDraftOn jobs take the ISLOW arithmetic; a full-size luma-only job of the reference IDCT is a
+            // class of its own
+            dr.on = d.luma_only && !d.draft && d.scale_log2 == 0 && d.idct_method == kIdctReference ? kDraftLumaReference : kDraftOn;
             for (int k = 0; k < sc.du_per_mcu; ++k) {
-                const int lg                   = d.blk_lg[sc.comp[ip.du_comp[k]].comp_idx];
+                const int comp_idx             = sc.comp[ip.du_comp[k]].comp_idx;
+                const int lg                   = d.blk_lg[comp_idx];
                 dr.comp_lg[ip.du_comp[k]]      = static_cast<uint8_t>(lg);
+                if (d.luma_only && comp_idx != 0) continue; // component_needed = FALSE (jdmaster.c): no IDCT
                 dr.k[lg][dr.n[lg]++]           = static_cast<uint8_t>(k);
             }
             for (int lg = 0; lg < 4; ++lg) {
