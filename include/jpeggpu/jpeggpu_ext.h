@@ -45,6 +45,8 @@
  *                                      still without loss: an EXIF orientation baked into the file
  *   jpeggpu_ext_set_transcode_crop     ... or cut to a rectangle (jpegtran -crop), decoding only the restart segments it needs
  *   jpeggpu_ext_set_transcode_frame    ... keeping the source's own frame layout: any sampling, up to four components and tables
+ *   jpeggpu_ext_roundtrip_batch        JPEG compression as an augmentation: the pixels of Pillow's save at quality q, then open,
+ *                                      in two launches per call and without a file
  */
 #ifndef JPEGGPU_JPEGGPU_EXT_H_
 #define JPEGGPU_JPEGGPU_EXT_H_
@@ -1322,6 +1324,58 @@ enum jpeggpu_ext_transcode_frame {
     JPEGGPU_EXT_TRANSCODE_FRAME_SOURCE  = 1
 };
 enum jpeggpu_status jpeggpu_ext_set_transcode_frame(jpeggpu_decoder_t decoder, int mode);
+
+/* JPEG round trip (JPEG compression as an augmentation or degradation: torchvision.transforms.v2.JPEG, albumentations'
+ * ImageCompression, DALI's jpeg_compression_distortion): the pixels an image has after it was saved as a baseline JPEG of
+ * quality q and opened again, on the device, without the file. For an H x W (grey) or H x W x 3 (RGB) uint8 array `a` the
+ * result is, byte for byte (tests/golden/roundtrip_pins.npz),
+ *     buf = BytesIO(); Image.fromarray(a).save(buf, "JPEG", quality=q, subsampling=s); np.asarray(Image.open(buf))
+ * of Pillow on libjpeg-turbo. Entropy coding is lossless, so none is done: one launch takes every block of the call from
+ * pixels through jpeggpu_ext_encode_batch's first stage (jccolor.c, jcsample.c, jpeg_fdct_islow, the quantiser with
+ * jpeg_set_quality's tables) and, on the quantised values still in registers, the decoder's ISLOW transform (dequantisation,
+ * jpeg_idct_islow, the range limit); a second launch, jpeggpu_ext_batch_to_rgb's, makes RGB of the component planes (fancy
+ * upsampling, YCbCr -> RGB). Optimised or progressive coding and restart intervals change no pixel and have no field here.
+ * The range limit is jidctint.c's table lookup, as in the decoder: a sample that overshoots the 8-bit range by more than 384
+ * wraps, where libjpeg-turbo's SIMD IDCT saturates. No input gets there with quantisers up to 100, and none of the pinned
+ * ones at any quality; tests/roundtrip_ref.py holds a block built to (WRAP_BLOCK, quality 1).
+ *   - An item: `data`, `width`, `height`, `channels` (1 or 3), the three strides, `quality` 1..100 and `subsampling` as in
+ *     jpeggpu_ext_encode_item (`subsampling` is not read for a grey item). `dst`, `dst_pitch` and `plane_stride` as in
+ *     jpeggpu_ext_rgb_item with `layout`: an RGB item's R, G, B of pixel (x, y) at dst + y * dst_pitch + 3 x (HWC) or channel c
+ *     at dst + c * plane_stride + y * dst_pitch + x (CHW); a grey item's sample at dst + y * dst_pitch + x whatever the
+ *     layout, dst_pitch >= width, plane_stride not read. No alignment is asked of any pointer or pitch.
+ *   - `dst` may be the very view `data` describes (same pointer, same strides): an RGB item's source is read completely by
+ *     the first launch before the second writes, and a grey block is read only by the lane that then stores it. Any other
+ *     overlap of an output with an input or another output is the caller's error and is not checked.
+ *   - A call may mix grey and RGB items, sizes, qualities and subsamplings. With an RGB item it is TWO launches whatever n
+ *     is, of grey items only ONE; one copy of descriptors through the page-locked staging ring of the resize calls (of four:
+ *     the fifth call in a row waits until the copy of the first has executed), and nothing synchronises. The host may reuse
+ *     `items` as soon as the call returns.
+ *   - `d_scratch`: caller-owned device memory of at least jpeggpu_ext_roundtrip_scratch_size(items, n) bytes (host only; 0
+ *     for items the call would refuse for their geometry, never smaller for a longer list), private to the stream until the
+ *     call has executed: the descriptors and, per RGB item, its three component planes padded to whole blocks.
+ *   - JPEGGPU_INVALID_ARGUMENT, before anything is enqueued and without touching the device: NULL items, d_scratch, data or
+ *     dst, n <= 0 or > 65535, width or height outside 1..65535, channels other than 1 or 3, quality outside 1..100, an
+ *     unknown subsampling (RGB items) or layout, a dst_pitch or plane_stride too small, scratch_size too small.
+ *     JPEGGPU_NOT_SUPPORTED: a call of 2^31 blocks. On an error nothing is written. */
+struct jpeggpu_ext_roundtrip_item {
+    const uint8_t* data;
+    int width, height;
+    int channels;    /* 1 or 3 */
+    int64_t row_pitch, pixel_stride, channel_stride; /* bytes, as jpeggpu_ext_encode_item */
+    int quality;     /* 1..100 */
+    int subsampling; /* enum jpeggpu_ext_subsampling; not read for grey */
+    uint8_t* dst;
+    int dst_pitch;
+    size_t plane_stride; /* RGB items of JPEGGPU_EXT_CHW only */
+};
+size_t jpeggpu_ext_roundtrip_scratch_size(const struct jpeggpu_ext_roundtrip_item* items, int n);
+enum jpeggpu_status jpeggpu_ext_roundtrip_batch(
+    const struct jpeggpu_ext_roundtrip_item* items,
+    int n,
+    enum jpeggpu_ext_image_layout layout,
+    void* d_scratch,
+    size_t scratch_size,
+    jpeggpu_stream_t stream);
 
 #ifdef __cplusplus
 }

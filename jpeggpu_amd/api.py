@@ -151,6 +151,13 @@ class EncodeItem(C.Structure):
                 ("restart_interval", C.c_int), ("optimize", C.c_int), ("out", C.c_void_p), ("capacity", C.c_size_t)]
 
 
+class RoundtripItem(C.Structure):
+    """struct jpeggpu_ext_roundtrip_item"""
+    _fields_ = [("data", C.c_void_p), ("width", C.c_int), ("height", C.c_int), ("channels", C.c_int), ("row_pitch", C.c_int64),
+                ("pixel_stride", C.c_int64), ("channel_stride", C.c_int64), ("quality", C.c_int), ("subsampling", C.c_int),
+                ("dst", C.c_void_p), ("dst_pitch", C.c_int), ("plane_stride", C.c_size_t)]
+
+
 class TranscodeItem(C.Structure):
     """struct jpeggpu_ext_transcode_item"""
     _fields_ = [("decoder", C.c_void_p), ("d_tmp", C.c_void_p), ("progressive", C.c_int), ("optimize", C.c_int), ("restart_interval", C.c_int),
@@ -320,6 +327,10 @@ def lib():
         L.jpeggpu_ext_encode_scratch_size.argtypes = [C.POINTER(EncodeItem), C.c_int]
         L.jpeggpu_ext_encode_scratch_size.restype = C.c_size_t
         L.jpeggpu_ext_encode_batch.argtypes = [C.POINTER(EncodeItem), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "jpeggpu_ext_roundtrip_batch"):
+        L.jpeggpu_ext_roundtrip_scratch_size.argtypes = [C.POINTER(RoundtripItem), C.c_int]
+        L.jpeggpu_ext_roundtrip_scratch_size.restype = C.c_size_t
+        L.jpeggpu_ext_roundtrip_batch.argtypes = [C.POINTER(RoundtripItem), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
     if hasattr(L, "jpeggpu_ext_transcode_batch"):
         L.jpeggpu_ext_transcode_header.argtypes = [C.POINTER(TranscodeItem), C.c_void_p, C.POINTER(C.c_size_t)]
         L.jpeggpu_ext_transcode_bound.argtypes = [C.POINTER(TranscodeItem)]
@@ -1925,6 +1936,57 @@ def encode_jpeg(images, quality=75, subsampling="4:2:0", restart_interval=0, lay
     for s in sizes:
         out.append(host[p:p + s])
         p += s
+    return out
+
+
+def jpeg_roundtrip(images, quality=75, subsampling="4:2:0", layout="HWC", out=None):
+    """JPEG compression as an augmentation: for each uint8 device tensor the pixels it has after it was saved as a baseline
+    JPEG and opened again -- byte for byte np.asarray(Image.open(buf)) after Image.fromarray(x).save(buf, "JPEG",
+    quality=quality, subsampling=subsampling) of Pillow on libjpeg-turbo --, without a file, an entropy coder or the host.
+    `images`: a list of tensors of any sizes (or one 4-D batch tensor); an item is H x W (grey) or, by `layout`, H x W x 3 /
+    3 x H x W. Any strided view is read through its strides, without a copy. `quality` 1..100 and `subsampling` "4:4:4" |
+    "4:2:2" | "4:2:0" (not used for grey) are one value or one per image. Returns a list of new tensors of the inputs'
+    shapes; with `out` (one tensor per image, of its shape, whose rows are dense: stride 1 along x, or 3 and 1 for HWC) the
+    result is written there, and out[i] may be images[i] itself. ONE jpeggpu_ext_roundtrip_batch call on torch's current
+    stream -- two launches, one with grey images only -- and no synchronisation."""
+    import torch
+
+    images, enc = _encode_items(images, quality, subsampling, 0, layout)
+    n = len(images)
+    if n == 0:
+        return []
+    device = images[0].device
+    if out is None:
+        out = [torch.empty(x.shape, dtype=torch.uint8, device=device) for x in images]
+    out = list(out)
+    if len(out) != n:
+        raise ValueError("out must have one tensor per image")
+    items = (RoundtripItem * n)()
+    for i, (x, o, e) in enumerate(zip(images, out, enc)):
+        if x.dim() != 2 and e.channels != 3:
+            raise ValueError("image %d: H x W or three channels are expected" % i)
+        if o.dtype != torch.uint8 or o.device != device or o.shape != x.shape:
+            raise ValueError("out[%d]: a uint8 tensor of the image's shape on its device is expected" % i)
+        if x.dim() == 2:
+            pitch, plane, dense = o.stride(0), 0, o.stride(1) == 1
+        elif layout == "HWC":
+            pitch, plane, dense = o.stride(0), 0, o.stride(1) == 3 and o.stride(2) == 1
+        else:
+            pitch, plane, dense = o.stride(1), o.stride(0), o.stride(2) == 1
+        if not dense:
+            raise ValueError("out[%d]: rows of adjacent pixels are expected" % i)
+        it = items[i]
+        it.data, it.width, it.height, it.channels = e.data, e.width, e.height, e.channels
+        it.row_pitch, it.pixel_stride, it.channel_stride = e.row_pitch, e.pixel_stride, e.channel_stride
+        it.quality, it.subsampling = e.quality, e.subsampling
+        it.dst, it.dst_pitch, it.plane_stride = o.data_ptr(), pitch, plane
+    need = lib().jpeggpu_ext_roundtrip_scratch_size(items, n)
+    if need == 0:
+        raise JpegGpuError(Status.INVALID_ARGUMENT, "jpeggpu_ext_roundtrip_scratch_size")
+    scratch = torch.empty(need, dtype=torch.uint8, device=device)
+    _check(lib().jpeggpu_ext_roundtrip_batch(items, n, IMAGE_LAYOUTS[layout], scratch.data_ptr(), need, torch.cuda.current_stream(device).cuda_stream),
+           "jpeggpu_ext_roundtrip_batch")
+    # the scratch tensor is freed by torch's caching allocator in stream order: it is not reused before the launches ran
     return out
 
 

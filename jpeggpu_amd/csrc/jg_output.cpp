@@ -1,8 +1,10 @@
 // jg_output.cpp -- the RGB output stage's entry points of the exported C ABI (include/jpeggpu/jpeggpu_ext.h) that touch
 // the device: they have jg_output_plan.cpp check and plan a call, stage and copy what the plan fills, and launch the
-// kernels of jg_output.hip. The stage reads finished planes and knows nothing of the decoder.
+// kernels of jg_output.hip. The stage reads finished planes and knows nothing of the decoder. The JPEG round trip
+// (jg_roundtrip.hip) is launched from here too: its second half is this stage, and it shares the staging ring.
 #include "jg_output.hpp"
 #include "jg_output_plan.hpp"
+#include "jg_roundtrip.hpp"
 #include "jg_staging.hpp"
 
 #include <hip/hip_runtime.h>
@@ -410,6 +412,34 @@ enum jpeggpu_status jpeggpu_ext_resize_view_to_gray_tensor(
     return launched(jg::launch_gray_resize(
         reinterpret_cast<const jg::ResizeJob*>(base), reinterpret_cast<const int*>(base + p.off_first), reinterpret_cast<const int*>(base + p.off_first_t), n,
         p.h_tiles, p.t_tiles, p.out_w, p.out_h, p.all_models, s.type, s.mean[0], s.std[0], dst, stream));
+}
+
+// JPEG round trip (jg_roundtrip.hip): the encoder's first stage and the ISLOW transform in one launch, then the batched
+// conversion above on the planes of the RGB items.
+enum jpeggpu_status jpeggpu_ext_roundtrip_batch(
+    const struct jpeggpu_ext_roundtrip_item* items, int n, enum jpeggpu_ext_image_layout layout, void* d_scratch, size_t scratch_size,
+    jpeggpu_stream_t stream)
+{
+    jg::rt::Plan p;
+    uint8_t* base = scratch_base(d_scratch ? d_scratch : reinterpret_cast<void*>(uintptr_t{256}));
+    const jpeggpu_status st = jg::rt::plan_roundtrip(items, n, layout, base, p);
+    if (st != JPEGGPU_SUCCESS) return st;
+    if (!d_scratch || scratch_size < p.total + 256) return JPEGGPU_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(staging().mu);
+    const jpeggpu_status staged = stage_and_copy(
+        p.head,
+        [&](uint8_t* h) {
+            jg::rt::fill_roundtrip(p, h);
+            return JPEGGPU_SUCCESS;
+        },
+        base, stream);
+    if (staged != JPEGGPU_SUCCESS) return staged;
+    const hipError_t err = jg::rt::launch_roundtrip_blocks(reinterpret_cast<const jg::rt::Item*>(base + p.off_items), n, p.tiles, base, stream);
+    if (err != hipSuccess || p.n_rgb == 0) return launched(err);
+    return launched(jg::launch_rgb_batch(
+        reinterpret_cast<const jg::RgbJob*>(base), reinterpret_cast<const int*>(base + p.rgb.at.off_first),
+        reinterpret_cast<const int*>(base + p.rgb.at.off_first_t), p.n_rgb, p.rgb.row_tiles, p.rgb.t_tiles, layout == JPEGGPU_EXT_CHW, p.rgb.all_models,
+        stream));
 }
 
 // Thumbnails: Pillow's Image.thumbnail of a batch -- draft, reduce, resize.
