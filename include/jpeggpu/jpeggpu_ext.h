@@ -47,6 +47,8 @@
  *   jpeggpu_ext_set_transcode_frame    ... keeping the source's own frame layout: any sampling, up to four components and tables
  *   jpeggpu_ext_roundtrip_batch        JPEG compression as an augmentation: the pixels of Pillow's save at quality q, then open,
  *                                      in two launches per call and without a file
+ *   jpeggpu_ext_read_coefficients_batch   DCT-domain access (libjpeg's jpeg_read_coefficients / jpeg_write_coefficients): the
+ *   jpeggpu_ext_write_coefficients_batch  quantised coefficients of decoded files as tensors, and files from such tensors
  */
 #ifndef JPEGGPU_JPEGGPU_EXT_H_
 #define JPEGGPU_JPEGGPU_EXT_H_
@@ -1375,6 +1377,119 @@ enum jpeggpu_status jpeggpu_ext_roundtrip_batch(
     enum jpeggpu_ext_image_layout layout,
     void* d_scratch,
     size_t scratch_size,
+    jpeggpu_stream_t stream);
+
+/* DCT-domain access: libjpeg's jpeg_read_coefficients and jpeg_write_coefficients (what jpegio.read,
+ * torchjpeg.codec.read_coefficients / write_coefficients and jpeglib wrap on the CPU), batched and on the device.
+ *
+ * READING. A component's coefficients are a tensor [blocks_y][blocks_x][64] over its REAL block grid -- libjpeg's
+ * width_in_blocks x height_in_blocks, blocks_x = ceil(ceil(width * h_c / h_max) / 8) and likewise for y (one component: h_c /
+ * h_max is 1 whatever its frame header says), not the MCU-padded grid -- with natural order inside a block (8 v + u), so
+ * that it views as [by][bx][8][8]. The DC is absolute.
+ *   - jpeggpu_ext_get_coefficient_info (host only; after jpeggpu_decoder_parse_header, else JPEGGPU_INVALID_ARGUMENT): the
+ *     frame's size and component count, its colour model (jpeggpu_ext_get_color_space) and whether it is progressive; per
+ *     component the grid, the sampling factors of the frame header, the quantisation table in natural order and whether
+ *     one of its entries is above 255. Entries of components the frame does not have are zero.
+ *   - jpeggpu_ext_read_coefficients_batch: an item is a decoder, its d_tmp and one destination per component, with a
+ *     transcode item's precondition: parsed, transferred and decoded by jpeggpu_ext_decode_batch on the same stream, with
+ *     jpeggpu_ext_batch_set_coefficients_only or without; d_tmp is read when the call executes. dst[c]: caller-owned device
+ *     memory of blocks_y * blocks_x * 64 elements, aligned to 16 bytes; entries beyond the component count are not read.
+ *     Every file the decoder reads: baseline (interleaved scans, and a component's own scan, whose units are its real
+ *     blocks) and progressive (out of the padded coefficient array, its rows cut to the real grid), 1..4 components, any
+ *     sampling, 8- and 16-bit tables, restart markers, device scan or not. A real block that no scan codes is 64 zeros.
+ *   - spec->type: JPEGGPU_EXT_COEF_I16 gives the quantised values exactly. JPEGGPU_EXT_COEF_F32 / _F16 give float(value),
+ *     and with spec->dequantize = 1 that times float(table entry): ONE IEEE-754 binary32 multiply, rounded to nearest even,
+ *     and for _F16 then one conversion, rounded to nearest even -- never arithmetic in half precision (as
+ *     jpeggpu_ext_resize_to_tensor converts). Dequantised _I16 is JPEGGPU_INVALID_ARGUMENT: a 16-bit table overflows it.
+ *   - One copy of descriptors (the encoder's page-locked staging ring), ONE launch whatever the call holds -- a workgroup
+ *     owns 256 consecutive blocks of one component's raster, so its stores are whole 128-byte lines of one tensor -- and
+ *     nothing synchronises. The host may reuse `items` as soon as the call returns.
+ *   - d_scratch: caller-owned, at least jpeggpu_ext_read_coefficients_scratch_size(n) bytes (host only, never smaller for
+ *     a larger n; 0 for n <= 0 or n > 65535), private to the stream until the call has executed.
+ *   - JPEGGPU_INVALID_ARGUMENT, before anything is enqueued: NULL items, spec or d_scratch, n <= 0 or > 65535, a NULL or
+ *     unparsed decoder, a d_tmp that is NULL or not aligned to 256 bytes, a dst[c] that is NULL or not aligned to 16 bytes, an
+ *     unknown type, a dequantize other than 0 or 1, a scratch too small. JPEGGPU_NOT_SUPPORTED, as a transcode refuses them:
+ *     a decoder with a scale other than 1 or a segment shard, and one with a decode window (jpeggpu_ext_set_crop) --
+ *     windowed reading is not offered --, and a call of 2^31 blocks. On an error nothing is written.
+ *
+ * WRITING. An item describes a frame and names one int16 tensor per component, laid out as above over the REAL grids:
+ * `width`, `height`, `components` 1..4, sampling factors h[c], v[c] in 1..4 (of a single component they go into the frame
+ * header as they are and change nothing else), qtable[c]: the component's table in natural order, entries 1..65535,
+ * `color_space` (enum jpeggpu_ext_color_space; GRAY 1 component, YCBCR and RGB 3, CMYK and YCCK 4, UNKNOWN any count),
+ * coef[c]: contiguous device memory aligned to 16 bytes, read when the call executes; `progressive`, `optimize`,
+ * `restart_interval` 0..65535 (MCUs), `out`, `capacity` as in jpeggpu_ext_encode_item. Everything behind the first launch
+ * is jpeggpu_ext_transcode_batch: the item is a transcode item whose source is the caller's tensors.
+ *   - The file. A layout the pixel encoder writes -- one component, or YCbCr with chroma 1 x 1, luma 1 x 1, 2 x 1 or 2 x 2,
+ *     equal tables for Cb and Cr and no entry above 255 -- gets the encoder's header (tables 0 and 1, APP0), and is then byte
+ *     for byte what jpeggpu_ext_transcode_batch makes of a source with these coefficients. Everything else gets the header
+ *     of jpeggpu_ext_set_transcode_frame(SOURCE) by the rules stated there (ids and APP0 / APP14 by the colour model,
+ *     Huffman tables 1 for components 1 and 2 of YCbCr and YCCK, SOF1 where a table has an entry above 255, the all-purpose
+ *     progressive script), with the quantisation tables numbered by first appearance: components whose tables are equal
+ *     share one DQT segment.
+ *   - Dummy blocks (blocks of an MCU beyond a component's real grid) are not in the tensors. They are the encoder's
+ *     (jctrans.c): AC zero and the DC of the block in front of them among the component's blocks of the MCU.
+ *   - d_status as jpeggpu_ext_transcode_batch: JPEGGPU_EXT_ENCODE_UNCODABLE for an item alone that holds an AC coefficient
+ *     of magnitude 1024 or more, or a DC difference of 2048 or more in the file's prediction order (per component, from 0
+ *     at every restart): its size is 0 and its slot is not written; the other items are not touched by it.
+ *   - The launches are those of jpeggpu_ext_transcode_batch for the same mix of output kinds (its mapped gather first), one
+ *     copy of descriptors, nothing synchronises. d_scratch: jpeggpu_ext_write_coefficients_scratch_size(items, n) (host
+ *     only; 0 for items the call refuses; never smaller for a longer list).
+ *   - jpeggpu_ext_write_coefficients_header / _bound (host only; `coef`, `out` and `capacity` are not read): as
+ *     jpeggpu_ext_encode_header / jpeggpu_ext_encode_bound serve the pixel encoder.
+ *   - JPEGGPU_INVALID_ARGUMENT, before anything is enqueued: width or height outside 1..65535, components outside 1..4, a
+ *     factor outside 1..4, an MCU of more than 10 blocks, a table entry of 0, a colour model that does not fit the component
+ *     count, a coef[c] that is NULL or not aligned to 16 bytes (the batch call), options out of range, `out` NULL with a
+ *     capacity. (A grid that does not fit the frame cannot be expressed: the grids follow from the frame. The Python
+ *     wrapper checks each tensor's shape against them.) JPEGGPU_NOT_SUPPORTED: the encoder's size limits. */
+struct jpeggpu_ext_coefficient_info {
+    int width, height, num_components;
+    int color_space; /* enum jpeggpu_ext_color_space */
+    int progressive;
+    int blocks_x[JPEGGPU_MAX_COMP], blocks_y[JPEGGPU_MAX_COMP];
+    int h[JPEGGPU_MAX_COMP], v[JPEGGPU_MAX_COMP];
+    int table16[JPEGGPU_MAX_COMP];         /* the component's table has an entry above 255 */
+    uint16_t qtable[JPEGGPU_MAX_COMP][64]; /* natural order */
+};
+enum jpeggpu_status jpeggpu_ext_get_coefficient_info(jpeggpu_decoder_t decoder, struct jpeggpu_ext_coefficient_info* info);
+enum jpeggpu_ext_coefficient_type { JPEGGPU_EXT_COEF_I16 = 0, JPEGGPU_EXT_COEF_F32 = 1, JPEGGPU_EXT_COEF_F16 = 2 };
+struct jpeggpu_ext_coefficient_spec {
+    enum jpeggpu_ext_coefficient_type type;
+    int dequantize; /* float types only */
+};
+struct jpeggpu_ext_coefficient_read_item {
+    jpeggpu_decoder_t decoder;
+    void* d_tmp;
+    void* dst[JPEGGPU_MAX_COMP];
+};
+size_t jpeggpu_ext_read_coefficients_scratch_size(int n);
+enum jpeggpu_status jpeggpu_ext_read_coefficients_batch(
+    const struct jpeggpu_ext_coefficient_read_item* items,
+    int n,
+    const struct jpeggpu_ext_coefficient_spec* spec,
+    void* d_scratch,
+    size_t scratch_size,
+    jpeggpu_stream_t stream);
+struct jpeggpu_ext_coefficient_item {
+    int width, height, components;
+    int h[JPEGGPU_MAX_COMP], v[JPEGGPU_MAX_COMP];
+    uint16_t qtable[JPEGGPU_MAX_COMP][64]; /* natural order, entries 1..65535 */
+    int color_space;                       /* enum jpeggpu_ext_color_space */
+    const int16_t* coef[JPEGGPU_MAX_COMP];
+    int progressive, optimize;
+    int restart_interval;
+    uint8_t* out;
+    size_t capacity;
+};
+enum jpeggpu_status jpeggpu_ext_write_coefficients_header(const struct jpeggpu_ext_coefficient_item* item, uint8_t* host_buf, size_t* size);
+size_t jpeggpu_ext_write_coefficients_bound(const struct jpeggpu_ext_coefficient_item* item);
+size_t jpeggpu_ext_write_coefficients_scratch_size(const struct jpeggpu_ext_coefficient_item* items, int n);
+enum jpeggpu_status jpeggpu_ext_write_coefficients_batch(
+    const struct jpeggpu_ext_coefficient_item* items,
+    int n,
+    void* d_scratch,
+    size_t scratch_size,
+    size_t* d_sizes,
+    int* d_status,
     jpeggpu_stream_t stream);
 
 #ifdef __cplusplus

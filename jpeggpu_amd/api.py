@@ -164,6 +164,30 @@ class TranscodeItem(C.Structure):
                 ("out", C.c_void_p), ("capacity", C.c_size_t)]
 
 
+class CoefficientInfo(C.Structure):
+    """struct jpeggpu_ext_coefficient_info"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("num_components", C.c_int), ("color_space", C.c_int), ("progressive", C.c_int),
+                ("blocks_x", C.c_int * MAX_COMP), ("blocks_y", C.c_int * MAX_COMP), ("h", C.c_int * MAX_COMP), ("v", C.c_int * MAX_COMP),
+                ("table16", C.c_int * MAX_COMP), ("qtable", (C.c_uint16 * 64) * MAX_COMP)]
+
+
+class CoefficientSpec(C.Structure):
+    """struct jpeggpu_ext_coefficient_spec"""
+    _fields_ = [("type", C.c_int), ("dequantize", C.c_int)]
+
+
+class CoefficientReadItem(C.Structure):
+    """struct jpeggpu_ext_coefficient_read_item"""
+    _fields_ = [("decoder", C.c_void_p), ("d_tmp", C.c_void_p), ("dst", C.c_void_p * MAX_COMP)]
+
+
+class CoefficientItem(C.Structure):
+    """struct jpeggpu_ext_coefficient_item"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("components", C.c_int), ("h", C.c_int * MAX_COMP), ("v", C.c_int * MAX_COMP),
+                ("qtable", (C.c_uint16 * 64) * MAX_COMP), ("color_space", C.c_int), ("coef", C.c_void_p * MAX_COMP),
+                ("progressive", C.c_int), ("optimize", C.c_int), ("restart_interval", C.c_int), ("out", C.c_void_p), ("capacity", C.c_size_t)]
+
+
 class ExtScanLayout(C.Structure):
     _fields_ = [
         ("num_components", C.c_int), ("component_idx", C.c_int * MAX_COMP),
@@ -339,6 +363,17 @@ def lib():
         L.jpeggpu_ext_transcode_scratch_size.restype = C.c_size_t
         L.jpeggpu_ext_transcode_batch.argtypes = [C.POINTER(TranscodeItem), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         L.jpeggpu_ext_batch_set_coefficients_only.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "jpeggpu_ext_read_coefficients_batch"):  # DCT-domain access (_newer_symbol)
+        L.jpeggpu_ext_get_coefficient_info.argtypes = [dec, C.POINTER(CoefficientInfo)]
+        L.jpeggpu_ext_read_coefficients_scratch_size.argtypes = [C.c_int]
+        L.jpeggpu_ext_read_coefficients_scratch_size.restype = C.c_size_t
+        L.jpeggpu_ext_read_coefficients_batch.argtypes = [C.POINTER(CoefficientReadItem), C.c_int, C.POINTER(CoefficientSpec), C.c_void_p, C.c_size_t, C.c_void_p]
+        L.jpeggpu_ext_write_coefficients_header.argtypes = [C.POINTER(CoefficientItem), C.c_void_p, C.POINTER(C.c_size_t)]
+        L.jpeggpu_ext_write_coefficients_bound.argtypes = [C.POINTER(CoefficientItem)]
+        L.jpeggpu_ext_write_coefficients_bound.restype = C.c_size_t
+        L.jpeggpu_ext_write_coefficients_scratch_size.argtypes = [C.POINTER(CoefficientItem), C.c_int]
+        L.jpeggpu_ext_write_coefficients_scratch_size.restype = C.c_size_t
+        L.jpeggpu_ext_write_coefficients_batch.argtypes = [C.POINTER(CoefficientItem), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(L, "jpeggpu_ext_set_transcode_orientation"):
         L.jpeggpu_ext_set_transcode_orientation.argtypes = [dec, C.c_int, C.c_int]
     if hasattr(L, "jpeggpu_ext_set_transcode_crop"):
@@ -503,6 +538,12 @@ class Decoder:
         write without it (after the orientation and its trim) from now on; (0, 0, 0, 0): the whole image again. x and y are
         multiples of the target's iMCU. Decodes to pixels ignore it."""
         _check(_newer_symbol("jpeggpu_ext_set_transcode_crop")(self._h, int(x), int(y), int(w), int(h)), "jpeggpu_ext_set_transcode_crop")
+
+    def coefficient_info(self) -> CoefficientInfo:
+        """jpeggpu_ext_get_coefficient_info of the last parsed image: the real block grids, factors and tables."""
+        ci = CoefficientInfo()
+        _check(_newer_symbol("jpeggpu_ext_get_coefficient_info")(self._h, C.byref(ci)), "jpeggpu_ext_get_coefficient_info")
+        return ci
 
     def set_progressive(self, on: bool = True):
         """Read progressive JPEGs (SOF2) from the next parse_header on; off by default, when they are NOT_SUPPORTED
@@ -1159,10 +1200,12 @@ class BatchDecode:
     fancy upsampling) and `tmps`; `transferred_bytes` is what one round of transfers copies, `batch` the Batch.
     `coefficients_only`: no planes are allocated (`planes[i]` is empty) and the batch stops in front of the IDCT stage
     (Batch.set_coefficients_only): the front half of transcode_jpeg. `luma_only`: a truth value for all files or one per
-    file -- Decoder.set_luma_only; of a YCbCr file only plane 0 is allocated and decoded (`planes[i]` has one entry)."""
+    file -- Decoder.set_luma_only; of a YCbCr file only plane 0 is allocated and decoded (`planes[i]` has one entry).
+    `device_scan`: a truth value for all files or one per file -- Decoder.set_device_scan(True): the device finds the
+    file's restart markers."""
 
     def __init__(self, datas, device="cuda:0", hint=None, idct="islow", progressive=True, scales=None, scale_mode="libjpeg", crops=None,
-                 crop_hooks=None, coefficients_only=False, luma_only=False):
+                 crop_hooks=None, coefficients_only=False, luma_only=False, device_scan=False):
         import torch
 
         dev = torch.device(device)
@@ -1181,6 +1224,8 @@ class BatchDecode:
                 luma = bool(luma_only[i] if isinstance(luma_only, (list, tuple)) else luma_only)
                 if luma:
                     dec.set_luma_only(True)
+                if device_scan[i] if isinstance(device_scan, (list, tuple)) else device_scan:
+                    dec.set_device_scan(True)
                 scale = 1 if scales is None else scales[i]
                 if scale != 1:
                     dec.set_scale(scale)
@@ -2268,6 +2313,222 @@ def transcode_jpeg(datas, optimize=False, progressive=False, restart_interval=No
 
     buf, offsets, sizes = transcode_jpeg_to_device(datas, optimize, progressive, restart_interval, device, None, orientation, exif_transpose, trim, crops,
                                                    expand, frame)
+    if not sizes:
+        return []
+    host = torch.cat([buf[o:o + s] for o, s in zip(offsets, sizes)]).cpu().numpy().tobytes()
+    out, p = [], 0
+    for s in sizes:
+        out.append(host[p:p + s])
+        p += s
+    return out
+
+
+COEFFICIENT_TYPE_NAMES = {"int16": 0, "float32": 1, "float16": 2}  # enum jpeggpu_ext_coefficient_type, by torch dtype name
+
+
+class Coefficients:
+    """The DCT-domain form of one JPEG (read_coefficients returns these; write_coefficients takes these or any object with
+    the same fields): `coefficients[c]` a tensor [blocks_y, blocks_x, 8, 8] over component c's real block grid, the DC
+    absolute; `qtables[c]` a uint16 numpy array [8, 8]; `width`, `height`; `sampling` [(h, v), ...] as in the frame header;
+    `color_space` (ColorSpace); `progressive`: whether the source was (read only)."""
+
+    def __init__(self, coefficients, qtables, width, height, sampling, color_space, progressive=False):
+        self.coefficients, self.qtables, self.width, self.height = list(coefficients), list(qtables), int(width), int(height)
+        self.sampling, self.color_space, self.progressive = [tuple(f) for f in sampling], ColorSpace(color_space), bool(progressive)
+
+
+def coefficient_grid(width, height, sampling):
+    """[(blocks_y, blocks_x), ...]: each component's real block grid -- libjpeg's height_in_blocks x width_in_blocks."""
+    if len(sampling) == 1:
+        return [(-(-height // 8), -(-width // 8))]
+    hmax, vmax = max(f[0] for f in sampling), max(f[1] for f in sampling)
+    return [(-(-(-(-height * v // vmax)) // 8), -(-(-(-width * h // hmax)) // 8)) for h, v in sampling]
+
+
+def read_coefficients_into(bd, dtype=None, dequantize=False):
+    """jpeggpu_ext_read_coefficients_batch on torch's current stream, without synchronising, for the files of `bd`, a
+    BatchDecode whose decode() was enqueued on the same stream (with coefficients_only or without): a list of Coefficients.
+    All tensors of the call are views of ONE allocation, each aligned to 256 bytes."""
+    import numpy as np
+    import torch
+
+    dtype = torch.int16 if dtype is None else dtype
+    names = {getattr(torch, k): v for k, v in COEFFICIENT_TYPE_NAMES.items()}
+    if dtype not in names:
+        raise ValueError("dtype must be torch.int16, torch.float32 or torch.float16")
+    call = _newer_symbol("jpeggpu_ext_read_coefficients_batch")
+    n = len(bd.decoders)
+    if n == 0:
+        return []
+    device = bd.tmps[0].device
+    esize = torch.empty(0, dtype=dtype).element_size()
+    infos, offsets, total = [dec.coefficient_info() for dec in bd.decoders], [], 0
+    for ci in infos:
+        for c in range(ci.num_components):
+            offsets.append(total)
+            total = _align256(total + ci.blocks_y[c] * ci.blocks_x[c] * 64 * esize)
+    buf = torch.empty(total + 256, dtype=torch.uint8, device=device)
+    pad = _align256(buf.data_ptr()) - buf.data_ptr()
+    items, out, k = (CoefficientReadItem * n)(), [], 0
+    for i, (ci, (dec, _, _, base, _)) in enumerate(zip(infos, bd._entries)):
+        items[i].decoder, items[i].d_tmp = dec._h, base
+        tensors = []
+        for c in range(ci.num_components):
+            by, bx = ci.blocks_y[c], ci.blocks_x[c]
+            t = buf[pad + offsets[k]:pad + offsets[k] + by * bx * 64 * esize].view(dtype).view(by, bx, 8, 8)
+            items[i].dst[c] = t.data_ptr()
+            tensors.append(t)
+            k += 1
+        tables = [np.ctypeslib.as_array(ci.qtable[c]).reshape(8, 8).copy() for c in range(ci.num_components)]
+        out.append(Coefficients(tensors, tables, ci.width, ci.height, [(ci.h[c], ci.v[c]) for c in range(ci.num_components)], ci.color_space,
+                                ci.progressive))
+    spec = CoefficientSpec(names[dtype], int(bool(dequantize)))
+    need = lib().jpeggpu_ext_read_coefficients_scratch_size(n)
+    scratch = torch.empty(need, dtype=torch.uint8, device=device)
+    _check(call(items, n, C.byref(spec), scratch.data_ptr(), need, torch.cuda.current_stream(device).cuda_stream), "jpeggpu_ext_read_coefficients_batch")
+    return out
+
+
+def read_coefficients(datas, device="cuda:0", dtype=None, dequantize=False):
+    """The quantised DCT coefficients of JPEG files, on the device: what jpeg_read_coefficients (jpegio.read,
+    torchjpeg.codec.read_coefficients) gives on the CPU. Returns one Coefficients per file; `dtype` torch.int16 (default:
+    the values exactly), or torch.float32 / torch.float16, which with `dequantize` hold value * table entry (one float32
+    multiply; for float16 that product converted once). Dequantised int16 is refused. Every file the decoder reads:
+    baseline and progressive, 1..4 components, any sampling, 16-bit tables. One batched decode that stops in front of the
+    IDCT, ONE allocation for all tensors, one read call; nothing synchronises."""
+    import torch
+
+    datas = list(datas)
+    if not datas:
+        return []
+    _newer_symbol("jpeggpu_ext_read_coefficients_batch")
+    if dequantize and (dtype is None or dtype == torch.int16):
+        raise JpegGpuError(Status.INVALID_ARGUMENT, "read_coefficients: dequantised int16 (a 16-bit table overflows it)")
+    with BatchDecode(datas, device, coefficients_only=True) as bd:
+        bd.decode()
+        return read_coefficients_into(bd, dtype, dequantize)
+
+
+def _coefficient_items(cs, optimize, progressive, restart_interval):
+    """The items of a write call without output slots, and the tensors they point into (kept alive by the caller)."""
+    import numpy as np
+    import torch
+
+    cs = list(cs)
+    n = len(cs)
+    os_, ps_, rs = _per_image(optimize, n, "optimize"), _per_image(progressive, n, "progressive"), _per_image(restart_interval, n, "restart_interval")
+    items, keep = (CoefficientItem * max(n, 1))(), []
+    for i, x in enumerate(cs):
+        nc = len(x.coefficients)
+        if not 1 <= nc <= MAX_COMP or len(x.qtables) != nc or len(x.sampling) != nc:
+            raise ValueError("item %d: 1..4 components with one table and one (h, v) each are expected" % i)
+        it = items[i]
+        it.width, it.height, it.components, it.color_space = int(x.width), int(x.height), nc, int(x.color_space)
+        it.optimize, it.progressive, it.restart_interval = int(os_[i]), int(ps_[i]), int(rs[i])
+        grids = coefficient_grid(it.width, it.height, [tuple(f) for f in x.sampling]) if it.width > 0 and it.height > 0 else [None] * nc
+        for c in range(nc):
+            t = x.coefficients[c]
+            if t.dtype != torch.int16 or not t.is_cuda or not t.is_contiguous() or t.data_ptr() % 16:
+                raise JpegGpuError(Status.INVALID_ARGUMENT,
+                                   "write_coefficients: item %d component %d: a contiguous int16 device tensor aligned to 16 bytes is expected" % (i, c))
+            if grids[c] is not None and tuple(t.shape) not in (grids[c] + (8, 8), grids[c] + (64,)):
+                raise JpegGpuError(Status.INVALID_ARGUMENT,
+                                   "write_coefficients: item %d component %d: shape %r does not fit the frame's grid %r" % (i, c, tuple(t.shape), grids[c]))
+            it.h[c], it.v[c] = int(x.sampling[c][0]), int(x.sampling[c][1])
+            q = np.asarray(x.qtables[c]).reshape(64)
+            if q.min() < 1 or q.max() > 65535:
+                raise JpegGpuError(Status.INVALID_ARGUMENT, "write_coefficients: item %d component %d: table entries must be 1..65535" % (i, c))
+            for k in range(64):
+                it.qtable[c][k] = int(q[k])
+            it.coef[c] = t.data_ptr()
+            keep.append(t)
+        if lib().jpeggpu_ext_write_coefficients_bound(C.byref(it)) == 0:  # say why: the header call returns the status
+            size = C.c_size_t(0)
+            st = lib().jpeggpu_ext_write_coefficients_header(C.byref(it), None, C.byref(size))
+            raise JpegGpuError(st if st else Status.NOT_SUPPORTED, "jpeggpu_ext_write_coefficients_batch: item %d cannot be written" % i)
+    return items, keep
+
+
+def write_coefficients_into(cs, outs, optimize=False, progressive=False, restart_interval=0, items=None):
+    """jpeggpu_ext_write_coefficients_batch on torch's current stream, without synchronising: item i into the slot outs[i], as
+    encode_into. Returns the device tensors (sizes int64[n], status int32[n]) with transcode_into's statuses."""
+    import torch
+
+    _newer_symbol("jpeggpu_ext_write_coefficients_batch")
+    cs = list(cs)
+    if items is None:
+        items, _ = _coefficient_items(cs, optimize, progressive, restart_interval)
+    n = len(cs)
+    if len(outs) != n:
+        raise ValueError("outs must have one entry per item")
+    if n == 0:
+        raise ValueError("no items")
+    device = cs[0].coefficients[0].device
+    for i, o in enumerate(outs):
+        if o is not None and (o.dtype != torch.uint8 or not o.is_contiguous() or o.device != device):
+            raise ValueError("outs[%d]: a contiguous uint8 tensor on the coefficients' device is expected" % i)
+        items[i].out = o.data_ptr() if o is not None and o.numel() else None
+        items[i].capacity = o.numel() if o is not None else 0
+    need = lib().jpeggpu_ext_write_coefficients_scratch_size(items, n)
+    if need == 0:
+        raise JpegGpuError(Status.NOT_SUPPORTED, "jpeggpu_ext_write_coefficients_scratch_size")
+    scratch = torch.empty(need, dtype=torch.uint8, device=device)
+    result = torch.empty(12 * n, dtype=torch.uint8, device=device)
+    _check(lib().jpeggpu_ext_write_coefficients_batch(items, n, scratch.data_ptr(), need, result.data_ptr(), result.data_ptr() + 8 * n,
+                                                      torch.cuda.current_stream(device).cuda_stream), "jpeggpu_ext_write_coefficients_batch")
+    return result[:8 * n].view(torch.int64), result[8 * n:].view(torch.int32)
+
+
+def write_coefficients_to_device(cs, optimize=False, progressive=False, restart_interval=0, capacities=None):
+    """write_coefficients' files left on the device: (buffer, offsets, sizes) as encode_jpeg_to_device returns them.
+    `capacities`: the slot sizes to start with (default: a header and four bytes per coefficient block, restart markers
+    included); if a file is larger, the call is repeated once with the sizes it reported."""
+    import torch
+
+    cs = list(cs)
+    if not cs:
+        return None, [], []
+    _newer_symbol("jpeggpu_ext_write_coefficients_batch")
+    n = len(cs)
+    items, _keep = _coefficient_items(cs, optimize, progressive, restart_interval)
+    if capacities is None:
+        caps = [2048 + sum(48 * t.numel() // 64 for t in x.coefficients) for x in cs]
+    else:
+        caps = [int(c) for c in _per_image(capacities, n, "capacities")]
+    for attempt in range(2):
+        offsets, total = [], 0
+        for c in caps:
+            offsets.append(total)
+            total = (total + c + 15) // 16 * 16
+        buf = torch.empty(max(total, 1), dtype=torch.uint8, device=cs[0].coefficients[0].device)
+        sizes, status = _encode_results(*write_coefficients_into(cs, [buf[o:o + c] for o, c in zip(offsets, caps)], items=items))
+        if 1 not in status:
+            break
+        caps = [max(c, s) for c, s in zip(caps, sizes)]
+    for i, st in enumerate(status):
+        if st == 4:
+            raise JpegGpuError(Status.NOT_SUPPORTED, "jpeggpu_ext_write_coefficients_batch: item %d holds a coefficient that no Huffman code expresses" % i)
+        if st == 2:
+            raise JpegGpuError(Status.NOT_SUPPORTED, "jpeggpu_ext_write_coefficients_batch: item %d needs a Huffman code of more than 32 bits (libjpeg refuses it too)" % i)
+        if st:
+            raise JpegGpuError(Status.INVALID_ARGUMENT, "jpeggpu_ext_write_coefficients_batch: item %d needs %d bytes" % (i, sizes[i]))
+    return buf, offsets, sizes
+
+
+def write_coefficients(cs, optimize=False, progressive=False, restart_interval=0):
+    """JPEG files that hold exactly the given quantised coefficients, as a list of bytes: what jpeg_write_coefficients
+    (jpegio.write, torchjpeg.codec.write_coefficients) does on the CPU. `cs`: Coefficients, as read_coefficients returns
+    them (changed on the device or not) or built from scratch -- any object with `coefficients` (int16 device tensors
+    [blocks_y, blocks_x, 8, 8] over each component's real grid, coefficient_grid), `qtables`, `width`, `height`, `sampling`
+    and `color_space`. `optimize`, `progressive`, `restart_interval` (MCUs, 0: none): one value or one per item. A layout
+    encode_jpeg writes gets its header, and the file is transcode_jpeg's for a source with these coefficients; every other
+    layout is written as transcode_jpeg(frame="source") writes it. An item with an AC coefficient of magnitude 1024 or
+    more, or a DC step of 2048 or more, raises JpegGpuError (write_coefficients_into reports it per item instead).
+    One jpeggpu_ext_write_coefficients_batch call (a second for files larger than the default slots), one synchronisation
+    and one copy of the files' bytes to the host."""
+    import torch
+
+    buf, offsets, sizes = write_coefficients_to_device(cs, optimize, progressive, restart_interval)
     if not sizes:
         return []
     host = torch.cat([buf[o:o + s] for o, s in zip(offsets, sizes)]).cpu().numpy().tobytes()

@@ -617,6 +617,29 @@ Staging& staging()
 }
 
 } // namespace
+
+/// jpeggpu_ext_read_coefficients_batch behind its checks: the items through the staging ring, one launch.
+jpeggpu_status read_coefficients(const ReadItem* items, int n, int type, void* d_scratch, size_t scratch_size, hipStream_t stream)
+{
+    const size_t bytes = sizeof(ReadItem) * (size_t(n) + 1);
+    uint8_t* base      = reinterpret_cast<uint8_t*>(jg::align_up(reinterpret_cast<uintptr_t>(d_scratch), 256));
+    if (size_t(base - static_cast<uint8_t*>(d_scratch)) + bytes > scratch_size) return JPEGGPU_INVALID_ARGUMENT;
+    Staging& rs = staging();
+    std::lock_guard<std::mutex> lock(rs.mu);
+    const int r = rs.next;
+    if (rs.in_use[r] && hipEventSynchronize(rs.copied[r]) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
+    rs.in_use[r] = false;
+    if (!rs.buf[r].reserve(bytes)) return JPEGGPU_OUT_OF_HOST_MEMORY;
+    std::memcpy(rs.buf[r].ptr, items, bytes);
+    if (!rs.copied[r] && hipEventCreateWithFlags(&rs.copied[r], hipEventDisableTiming) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
+    if (hipMemcpyAsync(base, rs.buf[r].ptr, bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
+    if (hipEventRecord(rs.copied[r], stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
+    rs.in_use[r] = true;
+    rs.next      = (r + 1) % Staging::kRing;
+    if (launch_read_blocks(reinterpret_cast<const ReadItem*>(base), n, items[n].tile_start[0], type, stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
+    return JPEGGPU_SUCCESS;
+}
+
 } // namespace enc
 } // namespace jg
 
@@ -789,6 +812,65 @@ enum jpeggpu_status jpeggpu_ext_transcode_batch(
         std::vector<TranscodeSpec> specs;
         std::vector<jpeggpu_ext_encode_item> enc;
         const jpeggpu_status st = specs_of(items, n, true, specs, enc);
+        if (st != JPEGGPU_SUCCESS) return st;
+        return batch_of(enc.data(), specs.data(), n, d_scratch, scratch_size, d_sizes, d_status, stream);
+    } catch (const std::bad_alloc&) {
+        return JPEGGPU_OUT_OF_HOST_MEMORY;
+    }
+}
+
+/// The specs of a jpeggpu_ext_write_coefficients_ call and their encoder items side by side (jg_coefficients.cpp: coefficient_spec).
+static jpeggpu_status coefficient_specs_of(const jpeggpu_ext_coefficient_item* items, int n, bool need_device, std::vector<TranscodeSpec>& specs,
+                                           std::vector<jpeggpu_ext_encode_item>& enc)
+{
+    if (!items || n <= 0 || n > 65535) return JPEGGPU_INVALID_ARGUMENT;
+    specs.resize(size_t(n));
+    enc.resize(size_t(n));
+    for (int i = 0; i < n; ++i) {
+        const jpeggpu_status st = coefficient_spec(items[i], need_device, specs[size_t(i)]);
+        if (st != JPEGGPU_SUCCESS) return st;
+        enc[size_t(i)] = specs[size_t(i)].item;
+    }
+    return JPEGGPU_SUCCESS;
+}
+
+enum jpeggpu_status jpeggpu_ext_write_coefficients_header(const struct jpeggpu_ext_coefficient_item* item, uint8_t* host_buf, size_t* size)
+{
+    if (!item || !size) return JPEGGPU_INVALID_ARGUMENT;
+    TranscodeSpec spec;
+    const jpeggpu_status st = coefficient_spec(*item, false, spec);
+    return st != JPEGGPU_SUCCESS ? st : header_of(&spec.item, &spec, host_buf, size);
+}
+
+size_t jpeggpu_ext_write_coefficients_bound(const struct jpeggpu_ext_coefficient_item* item)
+{
+    TranscodeSpec spec;
+    if (!item || coefficient_spec(*item, false, spec) != JPEGGPU_SUCCESS) return 0;
+    return bound_of(&spec.item, spec.general ? &spec : nullptr);
+}
+
+size_t jpeggpu_ext_write_coefficients_scratch_size(const struct jpeggpu_ext_coefficient_item* items, int n)
+{
+    Plan plan;
+    try {
+        std::vector<TranscodeSpec> specs;
+        std::vector<jpeggpu_ext_encode_item> enc;
+        if (coefficient_specs_of(items, n, false, specs, enc) != JPEGGPU_SUCCESS) return 0;
+        if (make_plan(enc.data(), n, plan, nullptr, nullptr, nullptr, specs.data()) != JPEGGPU_SUCCESS) return 0;
+    } catch (const std::bad_alloc&) {
+        return 0;
+    }
+    return size_t(plan.total) + 256;
+}
+
+enum jpeggpu_status jpeggpu_ext_write_coefficients_batch(
+    const struct jpeggpu_ext_coefficient_item* items, int n, void* d_scratch, size_t scratch_size, size_t* d_sizes, int* d_status, jpeggpu_stream_t stream)
+{
+    if (!d_scratch || !d_sizes || !d_status) return JPEGGPU_INVALID_ARGUMENT;
+    try {
+        std::vector<TranscodeSpec> specs;
+        std::vector<jpeggpu_ext_encode_item> enc;
+        const jpeggpu_status st = coefficient_specs_of(items, n, true, specs, enc);
         if (st != JPEGGPU_SUCCESS) return st;
         return batch_of(enc.data(), specs.data(), n, d_scratch, scratch_size, d_sizes, d_status, stream);
     } catch (const std::bad_alloc&) {

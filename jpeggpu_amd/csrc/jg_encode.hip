@@ -35,9 +35,14 @@
 // (jpeggpu_ext_set_transcode_orientation) or a crop (jpeggpu_ext_set_transcode_crop) the call launches gather_blocks<true>,
 // which maps blocks and coefficients on the way.
 //
+// jpeggpu_ext_write_coefficients_batch is a transcode call whose sources are the caller's tensors, every item mapped with the
+// identity (jg_coefficients.cpp), so it launches gather_blocks<true> and what follows it. jpeggpu_ext_read_coefficients_batch
+// is the one launch of read_blocks at the end of this file: the gather's walk of the decoder's entries, stored as tensors.
+//
 // No kernel waits for another workgroup: every dependency is a launch boundary.
 #include "jg_encode_prog.hpp"
 #include "jg_huff_core.h"
+#include "jg_output_device.h"
 #include "jg_transcode.hpp"
 
 #include <hip/hip_runtime.h>
@@ -964,6 +969,25 @@ __device__ inline uint2_t src_record(const GatherComp& c, int unit)
     return rec;
 }
 
+/// The AC coefficients of a baseline source's unit: put(zigzag index, value) for each entry behind the DC, an escaped value
+/// joined with its escape entry as in the IDCT stage. One 2-byte load is in flight ahead of the entry in hand; a unit has
+/// at most 127 entries, which src_record's clamp keeps inside the buffer.
+template <class F>
+__device__ __forceinline__ void walk_entries(const GatherComp& c, uint2_t rec, F&& put)
+{
+    const uint32_t cnt = rec.y & 0x7Fu;
+    const bool esc     = (rec.y & kUnitHasEscape) != 0;
+    uint32_t e         = cnt > 1u ? c.sym[sym_advance(rec.x, 1u)] : 0u;
+    for (uint32_t i = 1; i < cnt; ++i) {
+        const bool more     = i + 1 < cnt;
+        const uint32_t next = more ? c.sym[sym_advance(rec.x, i + 1)] : 0u;
+        const uint32_t zz   = sym_entry_index(e);
+        if (zz) // index 0 behind the DC: the escape of the coefficient in front
+            put(zz, esc && more && sym_entry_index(next) == 0 ? sym_entry_value(e, next) : sym_entry_value(e));
+        e = next;
+    }
+}
+
 /// The source's DC coefficient of block b, absolute.
 template <bool kOriented>
 __device__ inline int src_dc(const Item& it, const GatherSrc& src, int b)
@@ -1039,25 +1063,15 @@ __global__ __launch_bounds__(kTileBlocks) void gather_blocks(Item* items, int n,
             const int unit = src_unit<kOriented>(src, c, sb.bx, sb.by);
             if (unit >= 0) {
                 const uint2_t rec  = src_record(c, unit);
-                const uint32_t cnt = rec.y & 0x7Fu;
-                const bool esc     = (rec.y & kUnitHasEscape) != 0;
                 int16_t* r16       = reinterpret_cast<int16_t*>(row);
                 const uint64_t neg = kOriented ? (neg_u ? kZigzagOddU : 0ull) ^ (neg_v ? kZigzagOddV : 0ull) : 0ull;
                 dc                 = int16_t(c.sym[rec.x]);
                 r16[0]             = int16_t(dc);
-                uint32_t e         = cnt > 1u ? c.sym[sym_advance(rec.x, 1u)] : 0u;
-                for (uint32_t i = 1; i < cnt; ++i) {
-                    const bool more     = i + 1 < cnt;
-                    const uint32_t next = more ? c.sym[sym_advance(rec.x, i + 1)] : 0u;
-                    const uint32_t zz   = sym_entry_index(e);
-                    if (zz) { // index 0 behind the DC: the escape of the coefficient in front
-                        int v = esc && more && sym_entry_index(next) == 0 ? sym_entry_value(e, next) : sym_entry_value(e);
-                        if (abs(v) >= 1024) bad = true, v = 0;
-                        if (kOriented) r16[transpose ? kZigzagTransposed[zz] : zz] = int16_t(neg >> zz & 1u ? -v : v);
-                        else r16[zz] = int16_t(v);
-                    }
-                    e = next;
-                }
+                walk_entries(c, rec, [&](uint32_t zz, int v) {
+                    if (abs(v) >= 1024) bad = true, v = 0;
+                    if (kOriented) r16[transpose ? kZigzagTransposed[zz] : zz] = int16_t(neg >> zz & 1u ? -v : v);
+                    else r16[zz] = int16_t(v);
+                });
             }
         }
         const BlockPlace p = place_of(it, b);
@@ -1085,7 +1099,98 @@ __global__ __launch_bounds__(256) void finish_transcode(const Item* __restrict__
     d_status[i] = JPEGGPU_EXT_ENCODE_UNCODABLE;
 }
 
+// ------------------------------------------------------------------------------------------------
+// jpeggpu_ext_read_coefficients_batch: the decoder's coefficients as the caller's tensors (jg_transcode.hpp: ReadItem)
+// ------------------------------------------------------------------------------------------------
+
+/// The item that owns a tile of a read call: the last whose first tile is not behind it. items[n] is a sentinel.
+__device__ inline int read_item_of_tile(const ReadItem* items, int n, uint32_t tile)
+{
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (items[mid].tile_start[0] <= tile) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+/// One lane per block of the TARGET: a workgroup owns kReadTile consecutive blocks of one component's raster over its real
+/// grid, so what it stores is one contiguous run of the component's tensor, in whole 128-byte lines. The lane fills its row
+/// of the tile in LDS in NATURAL order -- rows kLdsRow dwords apart, as gather_blocks keeps them: lanes that write the same
+/// index fall on different banks, and the 16-byte pieces the lanes then read back (8 lanes a row of int16, 16 a row of
+/// float) are conflict-free in each half of the wave -- from the unit's entries, walked as gather_blocks walks them, or, for
+/// a progressive source, from its block of the padded coefficient array. A block no scan codes stays 64 zeros.
+/// T int16_t: the values. T float / _Float16: float(value) * float(factor), one binary32 multiply, then float_bits<T>.
+template <class T>
+__global__ __launch_bounds__(kReadTile) void read_blocks(const ReadItem* __restrict__ items, int n)
+{
+    __shared__ uint32_t tile[kReadTile * kLdsRow];
+    const ReadItem& it = items[read_item_of_tile(items, n, blockIdx.x)];
+    int comp           = 0;
+    for (int c = 1; c < 4; ++c) comp += it.tile_start[c] <= blockIdx.x; // (a component the frame lacks starts at the item's end)
+    const GatherComp& c = it.src.comp[comp];
+    const int grid_w = it.grid_w[comp], blocks = grid_w * it.grid_h[comp];
+    const int first = (blockIdx.x - it.tile_start[comp]) * kReadTile;
+    const int b     = first + threadIdx.x;
+    uint32_t* row   = tile + threadIdx.x * kLdsRow;
+    if (b < blocks) {
+        const int by = b / grid_w, bx = b - by * grid_w;
+        if (c.coef) {
+            const uint4* p = reinterpret_cast<const uint4*>(c.coef + (int64_t(by) * c.blocks_x + bx) * 64);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const uint4 v = p[q];
+                row[4 * q] = v.x, row[4 * q + 1] = v.y, row[4 * q + 2] = v.z, row[4 * q + 3] = v.w;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 32; ++k) row[k] = 0u;
+            const int unit = c.sym ? src_unit<false>(it.src, c, bx, by) : -1;
+            if (unit >= 0) {
+                const uint2_t rec = src_record(c, unit);
+                int16_t* r16      = reinterpret_cast<int16_t*>(row);
+                r16[0]            = int16_t(c.sym[rec.x]);
+                walk_entries(c, rec, [&](uint32_t zz, int v) { r16[kNatural[zz]] = int16_t(v); });
+            }
+        }
+    }
+    __syncthreads();
+    const int rows = min(kReadTile, blocks - first);
+    if constexpr (sizeof(T) == 2 && !std::is_same<T, _Float16>::value) {
+        uint4* out = reinterpret_cast<uint4*>(it.dst[comp]) + size_t(first) * 8;
+        for (int i = threadIdx.x; i < rows * 8; i += kReadTile) {
+            const uint32_t* s = tile + (i >> 3) * kLdsRow + (i & 7) * 4;
+            out[i]            = make_uint4(s[0], s[1], s[2], s[3]);
+        }
+    } else {
+        constexpr int kPer = 16 / int(sizeof(T)), kParts = 64 / kPer; // elements a lane stores, lanes a block
+        const uint16_t* factor = it.factor[comp];
+        uint4* out             = reinterpret_cast<uint4*>(it.dst[comp]) + size_t(first) * kParts;
+        for (int i = threadIdx.x; i < rows * kParts; i += kReadTile) {
+            const int part    = i % kParts;
+            const uint32_t* s = tile + (i / kParts) * kLdsRow + part * (kPer / 2);
+            uint32_t e[kPer], d[4];
+#pragma unroll
+            for (int k = 0; k < kPer; ++k) {
+                const int v = int16_t(s[k >> 1] >> (16 * (k & 1)));
+                e[k]        = float_bits<T>(__fmul_rn(float(v), float(factor[part * kPer + k])));
+            }
+            tensor_pack<int(sizeof(T)), kPer>(e, d);
+            out[i] = make_uint4(d[0], d[1], d[2], d[3]);
+        }
+    }
+}
+
 } // namespace
+
+hipError_t launch_read_blocks(const ReadItem* d_items, int n, uint32_t tiles, int type, hipStream_t stream)
+{
+    if (type == JPEGGPU_EXT_COEF_F32) read_blocks<float><<<tiles, kReadTile, 0, stream>>>(d_items, n);
+    else if (type == JPEGGPU_EXT_COEF_F16) read_blocks<_Float16><<<tiles, kReadTile, 0, stream>>>(d_items, n);
+    else read_blocks<int16_t><<<tiles, kReadTile, 0, stream>>>(d_items, n);
+    return hipGetLastError();
+}
 
 hipError_t launch_encode(const Plan& plan, uint8_t* d_scratch, unsigned long long* d_sizes, int* d_status, hipStream_t stream, bool transcode)
 {

@@ -59,25 +59,28 @@ __device__ __forceinline__ float tensor_norm(uint32_t u, float mean, float std)
     return __fdiv_rn(__fsub_rn(__fdiv_rn(static_cast<float>(u), 255.0f), mean), std);
 }
 
-/// The bit pattern of the element of type T made of byte u: the byte itself, tensor_norm's float, or that float converted
-/// ONCE, round to nearest even, to half or bfloat16 (never arithmetic in half precision).
+/// The bit pattern of float v as an element of the float type T: itself, or converted ONCE, round to nearest even, to half
+/// or bfloat16 (never arithmetic in half precision). Also the coefficient reader's conversion (jg_encode.hip: read_blocks).
+template <class T>
+__device__ __forceinline__ uint32_t float_bits(float v)
+{
+    if constexpr (sizeof(T) == 4) {
+        return __float_as_uint(v);
+    } else if constexpr (std::is_same<T, _Float16>::value) {
+        return __builtin_bit_cast(uint16_t, static_cast<_Float16>(v)); // v_cvt_f16_f32 in the default rounding mode
+    } else { // bfloat16: the upper half of the float, rounded to nearest even on the lower half
+        const uint32_t b = __float_as_uint(v);
+        if ((b & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;
+        return (b + 0x7fffu + ((b >> 16) & 1u)) >> 16;
+    }
+}
+
+/// The bit pattern of the element of type T made of byte u: the byte itself, or float_bits of tensor_norm's float.
 template <class T>
 __device__ __forceinline__ uint32_t tensor_bits(uint32_t u, float mean, float std)
 {
-    if constexpr (sizeof(T) == 1) {
-        return u;
-    } else {
-        const float v = tensor_norm(u, mean, std);
-        if constexpr (sizeof(T) == 4) {
-            return __float_as_uint(v);
-        } else if constexpr (std::is_same<T, _Float16>::value) {
-            return __builtin_bit_cast(uint16_t, static_cast<_Float16>(v)); // v_cvt_f16_f32 in the default rounding mode
-        } else { // bfloat16: the upper half of the float, rounded to nearest even on the lower half
-            const uint32_t b = __float_as_uint(v);
-            if ((b & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;
-            return (b + 0x7fffu + ((b >> 16) & 1u)) >> 16;
-        }
-    }
+    if constexpr (sizeof(T) == 1) return u;
+    else return float_bits<T>(tensor_norm(u, mean, std));
 }
 
 /// N elements of S bytes (their bit patterns in e[0 .. N - 1]) as N S / 4 dwords in memory order.

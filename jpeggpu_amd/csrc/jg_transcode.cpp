@@ -8,6 +8,38 @@
 namespace jg {
 namespace enc {
 
+/// Where component c of a parsed image lies in `tmp`, its d_tmp (jg_transcode.hpp: GatherComp; the fields that depend on an
+/// item's target stay the caller's). *scan: the scan that codes a baseline source's component, nullptr for a progressive
+/// source. False: no scan codes the component.
+bool source_comp(const Decoder& d, uint8_t* tmp, int c, GatherComp& g, const Scan** scan)
+{
+    const Stream& s = d.reader.s;
+    *scan           = nullptr;
+    if (s.progressive) {
+        g.coef     = reinterpret_cast<const int16_t*>(tmp + d.plan.prog.coef[c]);
+        g.blocks_x = s.prog_blocks_x[c];
+        return true;
+    }
+    for (int i = 0; i < s.num_scans; ++i) {
+        const Scan& sc = s.scans[i];
+        int k0         = 0;
+        for (int a = 0; a < sc.num_comp; ++a) {
+            if (sc.comp[a].comp_idx == c) {
+                g.sym         = reinterpret_cast<const uint16_t*>(tmp + d.plan.scan[i].sym);
+                g.du_tab      = tmp + d.plan.scan[i].du_tab;
+                g.sym_limit   = sym_buffer_entries(d.sym_regions(i), d.sym_region()) - 10 * kSymSectorStride;
+                g.interleaved = sc.num_comp > 1;
+                g.du_per_mcu = sc.du_per_mcu, g.k0 = k0, g.h = sc.comp[a].h, g.v = sc.comp[a].v, g.mcus_x = sc.mcus_x;
+                if (!g.interleaved) g.vis_x = sc.mcus_x, g.vis_y = sc.mcus_y; // the scan's own grid: the component's real blocks
+                *scan = &sc;
+                return true;
+            }
+            k0 += sc.comp[a].h * sc.comp[a].v;
+        }
+    }
+    return false;
+}
+
 jpeggpu_status transcode_spec(const jpeggpu_ext_transcode_item& it, bool need_device, TranscodeSpec& spec)
 {
     spec = TranscodeSpec{};
@@ -175,37 +207,16 @@ jpeggpu_status transcode_spec(const jpeggpu_ext_transcode_item& it, bool need_de
         if (d.crop.on && (sx0 < d.crop.mx0 * s.comp[c].hs || sx1 > d.crop.mx1 * s.comp[c].hs || sy0 < d.crop.my0 * s.comp[c].vs ||
                           sy1 > d.crop.my1 * s.comp[c].vs))
             return JPEGGPU_NOT_SUPPORTED;
-        if (s.progressive) {
-            g.coef     = reinterpret_cast<const int16_t*>(tmp + d.plan.prog.coef[c]);
-            g.blocks_x = s.prog_blocks_x[c];
-            continue;
+        const Scan* sc = nullptr;
+        if (!source_comp(d, tmp, c, g, &sc)) return JPEGGPU_NOT_SUPPORTED;
+        if (sc && cropped && sc->shard_mcus) {
+            // the scan was cut to the restart segments that hold the window (Reader::cut_segments): its units count
+            // from MCU first_mcu on, and every MCU of the scan that is read must lie in the kept run
+            const int bh = g.interleaved ? g.h : 1, bv = g.interleaved ? g.v : 1;
+            const int first = (sy0 / bv) * sc->mcus_x + sx0 / bh, last = ((sy1 - 1) / bv) * sc->mcus_x + (sx1 - 1) / bh;
+            if (first < sc->first_mcu || last >= sc->first_mcu + sc->shard_mcus) return JPEGGPU_NOT_SUPPORTED;
+            spec.src.first_unit = sc->first_mcu * sc->du_per_mcu;
         }
-        bool found = false;
-        for (int i = 0; i < s.num_scans && !found; ++i) {
-            const Scan& sc = s.scans[i];
-            int k0         = 0;
-            for (int a = 0; a < sc.num_comp && !found; ++a) {
-                if (sc.comp[a].comp_idx == c) {
-                    found         = true;
-                    g.sym         = reinterpret_cast<const uint16_t*>(tmp + d.plan.scan[i].sym);
-                    g.du_tab      = tmp + d.plan.scan[i].du_tab;
-                    g.sym_limit   = sym_buffer_entries(d.sym_regions(i), d.sym_region()) - 10 * kSymSectorStride;
-                    g.interleaved = sc.num_comp > 1;
-                    g.du_per_mcu = sc.du_per_mcu, g.k0 = k0, g.h = sc.comp[a].h, g.v = sc.comp[a].v, g.mcus_x = sc.mcus_x;
-                    if (!g.interleaved) g.vis_x = sc.mcus_x, g.vis_y = sc.mcus_y; // the scan's own grid: the component's real blocks
-                    if (cropped && sc.shard_mcus) {
-                        // the scan was cut to the restart segments that hold the window (Reader::cut_segments): its units count
-                        // from MCU first_mcu on, and every MCU of the scan that is read must lie in the kept run
-                        const int bh = g.interleaved ? g.h : 1, bv = g.interleaved ? g.v : 1;
-                        const int first = (sy0 / bv) * sc.mcus_x + sx0 / bh, last = ((sy1 - 1) / bv) * sc.mcus_x + (sx1 - 1) / bh;
-                        if (first < sc.first_mcu || last >= sc.first_mcu + sc.shard_mcus) return JPEGGPU_NOT_SUPPORTED;
-                        spec.src.first_unit = sc.first_mcu * sc.du_per_mcu;
-                    }
-                }
-                k0 += sc.comp[a].h * sc.comp[a].v;
-            }
-        }
-        if (!found) return JPEGGPU_NOT_SUPPORTED;
     }
     return JPEGGPU_SUCCESS;
 }

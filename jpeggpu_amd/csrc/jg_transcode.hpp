@@ -13,6 +13,8 @@
 #include "jg_encode.hpp"
 
 namespace jg {
+struct Decoder;
+struct Scan;
 namespace enc {
 
 /// Where the blocks of one component of the source lie in the decoder's d_tmp.
@@ -82,6 +84,35 @@ struct TranscodeSpec {
 /// The spec of a transcode item: JPEGGPU_INVALID_ARGUMENT / JPEGGPU_NOT_SUPPORTED by the rules of jpeggpu_ext.h.
 /// `need_device`: the pointers into d_tmp are wanted (the batch call), not only the geometry.
 __attribute__((visibility("hidden"))) jpeggpu_status transcode_spec(const jpeggpu_ext_transcode_item& it, bool need_device, TranscodeSpec& spec);
+
+/// jg_transcode.cpp: where component c of a parsed image lies in its d_tmp, for transcode_spec and the coefficient reader.
+__attribute__((visibility("hidden"))) bool source_comp(const Decoder& d, uint8_t* tmp, int c, GatherComp& g, const Scan** scan);
+
+/// The spec of a jpeggpu_ext_write_coefficients_ item (jg_coefficients.cpp): a transcode item whose source is the caller's
+/// tensors -- GatherComp::coef over the REAL grids, blocks_x the real grid's width -- mapped with the identity, so that
+/// gather_blocks<true> makes the dummy blocks the tensors do not hold.
+__attribute__((visibility("hidden"))) jpeggpu_status coefficient_spec(const jpeggpu_ext_coefficient_item& it, bool need_device, TranscodeSpec& spec);
+
+/// One item of jpeggpu_ext_read_coefficients_batch as read_blocks sees it: the source as a transcode item's, and per
+/// component the caller's tensor over the real grid grid_w x grid_h, the component's first tile among the call's (a tile:
+/// kReadTile consecutive blocks of ONE component's raster; tile_start[c] of a component the frame lacks, and [4], is the
+/// item's end) and the factor of each coefficient in natural order: the quantisation table, or ones.
+constexpr int kReadTile = kTileBlocks; // (64-block tiles were measured 4 % slower on 64 photographs: DESIGN.md section 7)
+struct ReadItem {
+    GatherSrc src;
+    void* dst[4];
+    uint32_t tile_start[5];
+    int32_t grid_w[4], grid_h[4];
+    uint32_t pad;
+    uint16_t factor[4][64];
+};
+static_assert(sizeof(ReadItem) % 8 == 0, "ReadItem: an array of them keeps its pointers aligned");
+
+/// jg_coefficients.cpp (it knows the decoder) makes the items, items[n] a sentinel whose tile_start[0] is the call's tile
+/// count; jg_encode.cpp stages them through the encoder's ring and launches read_blocks (jg_encode.hip). `type`: enum
+/// jpeggpu_ext_coefficient_type.
+__attribute__((visibility("hidden"))) jpeggpu_status read_coefficients(const ReadItem* items, int n, int type, void* d_scratch, size_t scratch_size, hipStream_t stream);
+hipError_t launch_read_blocks(const ReadItem* d_items, int n, uint32_t tiles, int type, hipStream_t stream);
 
 } // namespace enc
 } // namespace jg
