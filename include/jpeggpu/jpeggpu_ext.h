@@ -1149,7 +1149,8 @@ enum jpeggpu_ext_encode_status {
     JPEGGPU_EXT_ENCODE_TOO_SMALL      = 1,
     JPEGGPU_EXT_ENCODE_TABLE_OVERFLOW = 2, /* an optimised code longer than 32 bits before limiting */
     JPEGGPU_EXT_ENCODE_EMPTY_TABLE    = 3, /* jpeggpu_ext_encode_tables_from_counts only */
-    JPEGGPU_EXT_ENCODE_UNCODABLE      = 4  /* jpeggpu_ext_transcode_batch only: a coefficient the target cannot code */
+    JPEGGPU_EXT_ENCODE_UNCODABLE      = 4, /* jpeggpu_ext_transcode_batch only: a coefficient the target cannot code */
+    JPEGGPU_EXT_ENCODE_OVER_BUDGET    = 5  /* jpeggpu_ext_encode_fit_batch only: even quality_min exceeds max_bytes */
 };
 struct jpeggpu_ext_encode_item {
     const uint8_t* data;
@@ -1180,6 +1181,61 @@ enum jpeggpu_status jpeggpu_ext_encode_tables_from_counts(
     int n_tables,
     uint8_t* d_bits_values,
     int* d_status,
+    jpeggpu_stream_t stream);
+
+/* Encoding to a byte budget: for every item the best quality of a range whose file is no longer than `max_bytes`, found on
+ * the device, and that file -- byte for byte the one jpeggpu_ext_encode_batch writes for the item at the chosen quality.
+ *   - The chosen quality, exactly. Let size(q) be the length of jpeggpu_ext_encode_batch's file of the item at quality q (its
+ *     subsampling, restart interval and `optimize` flag are the item's own; with `optimize` 1 every q has its own tables and
+ *     size(q) counts their DHTs). With lo = quality_min, hi = quality_max, B = max_bytes:
+ *         if size(hi) <= B:     chosen = hi
+ *         else if size(lo) > B: JPEGGPU_EXT_ENCODE_OVER_BUDGET
+ *         else: best = lo, a = lo + 1, b = hi - 1; while a <= b: m = (a + b) / 2;
+ *               if size(m) <= B: best = m, a = m + 1; else b = m - 1;     chosen = best
+ *     size(q) is NOT monotone in q (on small images a step down by a byte or two from q to q + 1 is common), so this rule, not
+ *     "the largest quality that fits", is the contract: the file always fits, and the chosen quality is the largest fitting
+ *     one wherever size grows with quality.
+ *   - An item: `item` as for jpeggpu_ext_encode_batch, except that item.quality is ignored and item.progressive must be 0;
+ *     1 <= quality_min <= quality_max <= 100. `out`, `capacity`: the slot of the chosen file; `max_bytes` limits the file, not
+ *     the slot (out may be NULL with capacity 0: the call then only reports quality and size).
+ *   - d_quality[i] receives the chosen quality, for an item over budget quality_min. d_status[i]: JPEGGPU_EXT_ENCODE_OK;
+ *     JPEGGPU_EXT_ENCODE_TOO_SMALL as for jpeggpu_ext_encode_batch -- `capacity` is smaller than the chosen file, d_sizes[i] is
+ *     what it needs, the slot is untouched; JPEGGPU_EXT_ENCODE_OVER_BUDGET -- even quality_min is larger than max_bytes,
+ *     d_sizes[i] is size(quality_min), the slot is untouched; _TABLE_OVERFLOW as for `optimize` (a probe whose tables
+ *     overflow has no file and counts as size 0). An item's status never affects its neighbours.
+ *   - The pixel stage (colour conversion, downsampling, FDCT) runs once per call and keeps the unquantised transform; each
+ *     evaluation of size() requantises it with a quality that lives in device memory and runs the encoder's size stages. The
+ *     items of a call search in lockstep; the host derives the number of evaluations P from the widest range of the call
+ *     (w = quality_max - quality_min + 1: P = 1 for w = 1, 2 for w = 2, else 3 + floor(log2(w - 2)); 9 for 1..100) and
+ *     enqueues everything at once: the call does not synchronise, no evaluation makes the host wait for the device, and
+ *     descriptors and headers travel through the encoder's page-locked ring in one copy. An item whose search has ended
+ *     sits out the remaining evaluations (its tiles and chunks leave every kernel at their first test).
+ *   - Launches: 10 + 8 P, and 12 + 10 P for a call with at least one `optimize` item -- one for the transform, per
+ *     evaluation the requantiser, launches 2 - 7 of jpeggpu_ext_encode_batch (with `optimize`: 1a, 1b as well) and the
+ *     decision, then the final pass at the chosen qualities: requantiser, the eight (ten) launches less the first, and the
+ *     report. Whatever n and the image sizes are; jpeggpu_ext_encode_fit_launches (host only) returns the number for a
+ *     call's items, 0 for invalid ones. 82 launches for the range 1..100.
+ *   - `d_scratch`: at least jpeggpu_ext_encode_fit_scratch_size(items, n) bytes: what jpeggpu_ext_encode_scratch_size counts
+ *     for the same items, and beyond it the unquantised transform (int16, 2 bytes per padded sample: jpeg_fdct_islow's
+ *     output stays within +-8192 and a few units of rounding) and 64 bytes of search state per item. 0 for invalid items.
+ *   - JPEGGPU_INVALID_ARGUMENT as for jpeggpu_ext_encode_batch, and for quality_min > quality_max, either outside 1..100, or a
+ *     NULL d_quality. JPEGGPU_NOT_SUPPORTED, before anything is enqueued: an item with `progressive` 1 (a progressive search
+ *     is not offered), and the limits of jpeggpu_ext_encode_batch. */
+struct jpeggpu_ext_encode_fit_item {
+    struct jpeggpu_ext_encode_item item; /* item.quality is ignored; item.progressive must be 0 */
+    size_t max_bytes;
+    int quality_min, quality_max;
+};
+size_t jpeggpu_ext_encode_fit_scratch_size(const struct jpeggpu_ext_encode_fit_item* items, int n);
+int jpeggpu_ext_encode_fit_launches(const struct jpeggpu_ext_encode_fit_item* items, int n);
+enum jpeggpu_status jpeggpu_ext_encode_fit_batch(
+    const struct jpeggpu_ext_encode_fit_item* items,
+    int n,
+    void* d_scratch,
+    size_t scratch_size,
+    size_t* d_sizes,
+    int* d_status,
+    int* d_quality,
     jpeggpu_stream_t stream);
 
 /* Lossless transcoding: a decoded JPEG's quantised coefficients, as the decoder's entropy stage leaves them in d_tmp, to a

@@ -151,6 +151,21 @@ class EncodeItem(C.Structure):
                 ("restart_interval", C.c_int), ("optimize", C.c_int), ("out", C.c_void_p), ("capacity", C.c_size_t)]
 
 
+class EncodeFitItem(C.Structure):
+    """struct jpeggpu_ext_encode_fit_item"""
+    _fields_ = [("item", EncodeItem), ("max_bytes", C.c_size_t), ("quality_min", C.c_int), ("quality_max", C.c_int)]
+
+
+class EncodeStatus(enum.IntEnum):
+    """enum jpeggpu_ext_encode_status: what the encoder's calls leave per item in their status tensor."""
+    OK = 0
+    TOO_SMALL = 1
+    TABLE_OVERFLOW = 2
+    EMPTY_TABLE = 3
+    UNCODABLE = 4
+    OVER_BUDGET = 5
+
+
 class RoundtripItem(C.Structure):
     """struct jpeggpu_ext_roundtrip_item"""
     _fields_ = [("data", C.c_void_p), ("width", C.c_int), ("height", C.c_int), ("channels", C.c_int), ("row_pitch", C.c_int64),
@@ -351,6 +366,11 @@ def lib():
         L.jpeggpu_ext_encode_scratch_size.argtypes = [C.POINTER(EncodeItem), C.c_int]
         L.jpeggpu_ext_encode_scratch_size.restype = C.c_size_t
         L.jpeggpu_ext_encode_batch.argtypes = [C.POINTER(EncodeItem), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "jpeggpu_ext_encode_fit_batch"):  # encoding to a byte budget (_newer_symbol)
+        L.jpeggpu_ext_encode_fit_scratch_size.argtypes = [C.POINTER(EncodeFitItem), C.c_int]
+        L.jpeggpu_ext_encode_fit_scratch_size.restype = C.c_size_t
+        L.jpeggpu_ext_encode_fit_launches.argtypes = [C.POINTER(EncodeFitItem), C.c_int]
+        L.jpeggpu_ext_encode_fit_batch.argtypes = [C.POINTER(EncodeFitItem), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(L, "jpeggpu_ext_roundtrip_batch"):
         L.jpeggpu_ext_roundtrip_scratch_size.argtypes = [C.POINTER(RoundtripItem), C.c_int]
         L.jpeggpu_ext_roundtrip_scratch_size.restype = C.c_size_t
@@ -1631,16 +1651,23 @@ def decode_thumbnails(datas, size, resample="bicubic", reducing_gap=2.0, exif_tr
 
 
 def thumbnail_jpeg(datas, size, resample="bicubic", reducing_gap=2.0, exif_transpose=False, device="cuda:0", quality=75, subsampling=None,
-                   optimize=False, progressive=False, restart_interval=0):
+                   optimize=False, progressive=False, restart_interval=0, max_bytes=None, min_quality=1):
     """JPEG in, smaller JPEG out: decode_thumbnails' views encoded by encode_jpeg (one decode batch, one thumbnail call, one
     encode call; the pixels never visit the host). Returns a list of bytes: encode_jpeg's file of each thumbnail, which for a
     source without a COM segment is byte for byte what im.save(f, "JPEG", quality=..., ...) writes after
     im.thumbnail(size, resample, reducing_gap) (Pillow copies only the comment across). `subsampling` None is save()'s
     default: "4:2:0" for a colour file, and factors 1 x 1 in a grey file's frame header (which an explicit subsampling
-    would change, in Pillow as here)."""
+    would change, in Pillow as here). `max_bytes` (one value or one per file): a size limit -- the encode step is then
+    encode_jpeg_fit's search over min_quality..quality, and the function returns (files, qualities); progressive=True is
+    not offered with it."""
     views = decode_thumbnails(datas, size, resample, reducing_gap, exif_transpose, device)
     if subsampling is None:
         subsampling = ["4:4:4" if v.dim() == 2 else "4:2:0" for v in views]
+    if max_bytes is not None:
+        if progressive:
+            raise JpegGpuError(Status.NOT_SUPPORTED, "thumbnail_jpeg: max_bytes with progressive=True")
+        return encode_jpeg_fit(views, max_bytes, quality=quality, min_quality=min_quality, subsampling=subsampling, restart_interval=restart_interval,
+                               optimize=optimize)
     return encode_jpeg(views, quality=quality, subsampling=subsampling, restart_interval=restart_interval, optimize=optimize,
                        progressive=progressive)
 
@@ -1982,6 +2009,116 @@ def encode_jpeg(images, quality=75, subsampling="4:2:0", restart_interval=0, lay
         out.append(host[p:p + s])
         p += s
     return out
+
+
+def _fit_items(images, max_bytes, quality, min_quality, subsampling, restart_interval, layout, optimize):
+    """The items of a budget call, without output slots: _encode_items' with each image's budget and range of qualities."""
+    images, plain = _encode_items(images, 75, subsampling, restart_interval, layout, optimize)
+    n = len(images)
+    bs, his, los = _per_image(max_bytes, n, "max_bytes"), _per_image(quality, n, "quality"), _per_image(min_quality, n, "min_quality")
+    items = (EncodeFitItem * max(n, 1))()
+    for i in range(n):
+        if int(bs[i]) < 0:
+            raise ValueError("image %d: max_bytes must not be negative" % i)
+        items[i].item = plain[i]
+        items[i].max_bytes, items[i].quality_min, items[i].quality_max = int(bs[i]), int(los[i]), int(his[i])
+    return images, items
+
+
+def encode_fit_launches(width, height, channels=3, max_bytes=0, quality=75, min_quality=1, subsampling="4:2:0", restart_interval=0, optimize=False) -> int:
+    """jpeggpu_ext_encode_fit_launches (host only) for one item of this geometry: the kernel launches a budget call over the
+    range min_quality..quality enqueues -- 10 + 8 P, with optimize 12 + 10 P, P the evaluations the range needs. Raises
+    JpegGpuError (INVALID_ARGUMENT) for an item the library refuses."""
+    items = (EncodeFitItem * 1)()
+    items[0].item = encode_item(width, height, channels, 75, subsampling, restart_interval, optimize)
+    items[0].max_bytes, items[0].quality_min, items[0].quality_max = int(max_bytes), int(min_quality), int(quality)
+    n = _newer_symbol("jpeggpu_ext_encode_fit_launches")(items, 1)
+    if n == 0:
+        raise JpegGpuError(Status.INVALID_ARGUMENT, "jpeggpu_ext_encode_fit_launches")
+    return n
+
+
+def encode_fit_into(images, outs, max_bytes, quality=75, min_quality=1, subsampling="4:2:0", restart_interval=0, layout="HWC", optimize=False):
+    """jpeggpu_ext_encode_fit_batch on torch's current stream, without synchronising: for image i the best quality of
+    min_quality..quality whose file is at most max_bytes long, and that file -- encode_into's at that quality, byte for byte
+    -- in the slot outs[i] (None: only quality and size are reported). The search runs on the device: the pixel stage once,
+    then one requantisation and the size stages per evaluation, with nothing on the host in between. `max_bytes`, `quality`,
+    `min_quality` and the encoder's arguments are one value or one per image. Returns the device tensors (sizes int64[n],
+    status int32[n], qualities int32[n]); status as encode_into, and EncodeStatus.OVER_BUDGET (5) for an image whose file
+    exceeds max_bytes even at min_quality: its size is that file's, its quality min_quality, its slot untouched.
+    The chosen quality is the answer of a bisection (include/jpeggpu/jpeggpu_ext.h states it exactly): the file always fits,
+    and the quality is the largest that fits wherever the size grows with the quality, which on small images it sometimes
+    does not."""
+    import torch
+
+    images, items = _fit_items(images, max_bytes, quality, min_quality, subsampling, restart_interval, layout, optimize)
+    n = len(images)
+    if len(outs) != n:
+        raise ValueError("outs must have one entry per image")
+    if n == 0:
+        raise ValueError("no images")
+    device = images[0].device
+    for i, o in enumerate(outs):
+        if o is not None and (o.dtype != torch.uint8 or not o.is_contiguous() or o.device != device):
+            raise ValueError("outs[%d]: a contiguous uint8 tensor on the images' device is expected" % i)
+        items[i].item.out = o.data_ptr() if o is not None and o.numel() else None
+        items[i].item.capacity = o.numel() if o is not None else 0
+    fit_batch = _newer_symbol("jpeggpu_ext_encode_fit_batch")
+    need = lib().jpeggpu_ext_encode_fit_scratch_size(items, n)
+    if need == 0:  # a range the library refuses, or (as in encode_into) a size beyond the kernels' limits
+        bad_range = any(not 1 <= items[i].quality_min <= items[i].quality_max <= 100 for i in range(n))
+        raise JpegGpuError(Status.INVALID_ARGUMENT if bad_range else Status.NOT_SUPPORTED, "jpeggpu_ext_encode_fit_scratch_size")
+    scratch = torch.empty(need, dtype=torch.uint8, device=device)
+    result = torch.empty(16 * n, dtype=torch.uint8, device=device)  # sizes, status, qualities: one copy brings all to the host
+    _check(fit_batch(items, n, scratch.data_ptr(), need, result.data_ptr(), result.data_ptr() + 8 * n, result.data_ptr() + 12 * n,
+                     torch.cuda.current_stream(device).cuda_stream), "jpeggpu_ext_encode_fit_batch")
+    # the scratch tensor is freed by torch's caching allocator in stream order: it is not reused before the launches ran
+    return result[:8 * n].view(torch.int64), result[8 * n:12 * n].view(torch.int32), result[12 * n:].view(torch.int32)
+
+
+def encode_jpeg_fit(images, max_bytes, quality=75, min_quality=1, subsampling="4:2:0", restart_interval=0, layout="HWC", optimize=False, strict=True):
+    """JPEG files of uint8 device tensors under a size limit: returns (files, qualities), file i the one encode_jpeg writes
+    for image i at qualities[i], the best quality of min_quality..quality whose file is at most max_bytes long (encode_fit_into
+    says which that is, exactly). `quality` is the upper end: the file of plain encode_jpeg if it fits, a lower quality only
+    if it must be. `max_bytes`, `quality`, `min_quality` and the encoder's arguments are one value or one per image. An
+    image that exceeds its limit even at min_quality raises a JpegGpuError naming it; with strict=False its file is None and
+    its quality min_quality. One jpeggpu_ext_encode_fit_batch call, one synchronisation and one copy to the host."""
+    import torch
+
+    images, items = _fit_items(images, max_bytes, quality, min_quality, subsampling, restart_interval, layout, optimize)
+    n = len(images)
+    if n == 0:
+        return [], []
+    device = images[0].device
+    # no file is longer than its budget, nor than the bound of its geometry
+    caps = [min(int(items[i].max_bytes), lib().jpeggpu_ext_encode_bound(C.byref(items[i].item))) for i in range(n)]
+    offsets, total = [], 0
+    for c in caps:
+        offsets.append(total)
+        total = (total + c + 15) // 16 * 16
+    buf = torch.empty(max(total, 1), dtype=torch.uint8, device=device)
+    sizes, status, qualities = encode_fit_into(images, [buf[o:o + c] for o, c in zip(offsets, caps)], max_bytes, quality, min_quality, subsampling,
+                                               restart_interval, layout, optimize)
+    raw = torch.cat([sizes.view(torch.uint8), status.view(torch.uint8), qualities.view(torch.uint8)]).cpu()
+    sizes, status = raw[:8 * n].view(torch.int64).tolist(), raw[8 * n:12 * n].view(torch.int32).tolist()
+    qualities = raw[12 * n:].view(torch.int32).tolist()
+    for i, st in enumerate(status):
+        if st == EncodeStatus.OVER_BUDGET and strict:
+            raise JpegGpuError(Status.INVALID_ARGUMENT, "jpeggpu_ext_encode_fit_batch: image %d takes %d bytes at quality %d, more than its max_bytes of %d"
+                               % (i, sizes[i], qualities[i], int(items[i].max_bytes)))
+        if st == EncodeStatus.TABLE_OVERFLOW:
+            raise JpegGpuError(Status.NOT_SUPPORTED, "jpeggpu_ext_encode_fit_batch: image %d needs a Huffman code of more than 32 bits (libjpeg refuses it too)" % i)
+        if st not in (EncodeStatus.OK, EncodeStatus.OVER_BUDGET):
+            raise JpegGpuError(Status.INTERNAL_ERROR, "jpeggpu_ext_encode_fit_batch: image %d, status %d" % (i, st))
+    keep = [i for i in range(n) if status[i] == EncodeStatus.OK]
+    files = [None] * n
+    if keep:
+        host = torch.cat([buf[offsets[i]:offsets[i] + sizes[i]] for i in keep]).cpu().numpy().tobytes()  # only the files' bytes travel
+        p = 0
+        for i in keep:
+            files[i] = host[p:p + sizes[i]]
+            p += sizes[i]
+    return files, qualities
 
 
 def jpeg_roundtrip(images, quality=75, subsampling="4:2:0", layout="HWC", out=None):

@@ -1,7 +1,9 @@
 // jg_encode.cpp -- the encoder's part of the exported C ABI (include/jpeggpu/jpeggpu_ext.h): argument checks, the file
 // header, the size bound and the plan of a call for the kernels of jg_encode.hip. It knows nothing of the decoder: of a
 // transcode item it sees the TranscodeSpec that jg_transcode.cpp made of it (jg_transcode.hpp).
+#include "jg_encode_fit.hpp"
 #include "jg_encode_prog.hpp"
+#include "jg_quant.h"
 #include "jg_staging.hpp"
 #include "jg_transcode.hpp"
 
@@ -31,12 +33,7 @@ static_assert(offsetof(jpeggpu_ext_encode_item, channels) == 16 && offsetof(jpeg
               "`progressive` took the place of the padding behind `channels`: no other member moved");
 static_assert(sizeof(Item) == 392, "the scratch size of a call without optimised items is part of the interface");
 
-// Annex K.1, K.2 (natural order) and K.3 - K.6
-const uint8_t kBaseLuma[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,  69,  56,
-                               14, 17, 22, 29, 51,  87,  80,  62,  18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,
-                               49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
-const uint8_t kBaseChroma[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
-                                 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+// The zigzag order, and Annex K.3 - K.6 (K.1 and K.2: jg_quant.h)
 const uint8_t kNatural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
                               35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
@@ -102,13 +99,10 @@ const Tables& tables()
 }
 
 /// jpeg_set_quality's table (force_baseline), natural order.
-void quant_table(const uint8_t* base, int quality, uint8_t* q)
+/// `table` 0: luma, 1: chroma. The arithmetic is jg_quant.h's, which the device shares.
+void quant_table(int table, int quality, uint8_t* q)
 {
-    const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
-    for (int i = 0; i < 64; ++i) {
-        int v = (base[i] * s + 50) / 100;
-        q[i]  = uint8_t(v < 1 ? 1 : v > 255 ? 255 : v);
-    }
+    for (int i = 0; i < 64; ++i) q[i] = uint8_t(quantizer(table, quality, i));
 }
 
 /// `spec`: a transcode item's, which may keep a frame of its own (TranscodeSpec::general) of up to four components.
@@ -370,7 +364,7 @@ void write_prefix(const jpeggpu_ext_encode_item& it, std::vector<uint8_t>& out, 
     put_segment(out, 0xE0, jfif, sizeof jfif);
     for (int t = 0; t < (ncomp == 1 ? 1 : 2); ++t) {
         uint8_t q[64], seg[65];
-        quant_table(t ? kBaseChroma : kBaseLuma, it.quality, q);
+        quant_table(t, it.quality, q);
         seg[0] = uint8_t(t);
         for (int k = 0; k < 64; ++k) seg[1 + k] = spec ? spec->qtable[t][k] : q[kNatural[k]];
         put_segment(out, 0xDB, seg, sizeof seg);
@@ -435,8 +429,10 @@ struct ProgBlob {
 };
 
 /// `specs`: the call is a transcode call and items[i] is specs[i].item.
+/// `fit`: the call is a budget call (jg_encode_fit.hpp) -- its FitItem[n] in the blob and each item's unquantised transform
+/// behind the item's other arrays; `fit_items`, if not null, receives where those lie and each item's blocks.
 jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan, std::vector<Item>* out_items, std::vector<std::vector<uint8_t>>* headers,
-                         ProgBlob* prog, const TranscodeSpec* specs = nullptr)
+                         ProgBlob* prog, const TranscodeSpec* specs = nullptr, bool fit = false, std::vector<FitItem>* fit_items = nullptr)
 {
     if (!items || n <= 0 || n > 65535) return JPEGGPU_INVALID_ARGUMENT;
     uint64_t tiles = 0, chunks = 0, header_bytes = 0, prog_tiles = 0, prog_chunks = 0;
@@ -508,6 +504,7 @@ jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan
     plan.prog.shadow_off  = take(np ? sizeof(Item) * (np + 1) : 0);
     plan.prog.items_off   = take(sizeof(ProgItem) * np);
     plan.gather_off       = take(specs ? sizeof(GatherSrc) * size_t(n) : 0);
+    plan.fit_off          = take(fit ? sizeof(FitItem) * size_t(n) : 0);
     plan.blob_bytes       = off;
     plan.bits_off         = take(tiles * kTileBlocks * sizeof(uint32_t));
     plan.tile_sum_off     = take(tiles * sizeof(Cursor));
@@ -523,6 +520,7 @@ jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan
     plan.prog.count_before_off = take(prog_chunks * sizeof(Count));
     uint32_t tile = 0, chunk = 0, prog_tile = 0, prog_chunk = 0;
     if (out_items) out_items->resize(size_t(n) + 1);
+    if (fit_items) fit_items->assign(size_t(n), FitItem{});
     for (int i = 0; i < n; ++i) {
         const Geometry& g       = geo[i];
         const uint64_t chunks_i = (g.stream_bound + kChunkBytes - 1) / kChunkBytes;
@@ -531,6 +529,8 @@ jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan
         const uint64_t starts   = take(chunks_i * (kChunkBytes / 8));
         const bool progressive  = items[i].progressive != 0;
         const uint64_t work     = progressive ? take(sizeof(ProgWork)) : items[i].optimize ? take(sizeof(OptWork)) : 0;
+        const uint64_t raw      = take(fit ? g.blocks * 128 : 0);
+        if (fit_items) (*fit_items)[size_t(i)].raw_off = raw, (*fit_items)[size_t(i)].blocks = int32_t(g.blocks);
         if (out_items) {
             const jpeggpu_ext_encode_item& s = items[i];
             Item& d                          = (*out_items)[i];
@@ -548,7 +548,7 @@ jpeggpu_status make_plan(const jpeggpu_ext_encode_item* items, int n, Plan& plan
             if (s.optimize && !progressive) std::memcpy((*headers)[i].data() + offsetof(OptState, work_off), &work, sizeof work);
             uint8_t q[64];
             for (int t = 0; t < 2; ++t) {
-                quant_table(t ? kBaseChroma : kBaseLuma, s.quality, q);
+                quant_table(t, s.quality, q);
                 for (int k = 0; k < 64; ++k) d.divisor[t][k] = uint16_t(8 * q[kNatural[k]]);
             }
             if (specs && specs[i].general) { // nothing is quantised: the frame lies in the divisors' place
@@ -700,9 +700,20 @@ size_t jpeggpu_ext_encode_scratch_size(const struct jpeggpu_ext_encode_item* ite
     return size_t(plan.total) + 256; // room to align the caller's pointer
 }
 
-/// jpeggpu_ext_encode_batch, and with `specs` (items[i] is specs[i].item) jpeggpu_ext_transcode_batch.
+/// Where the 64 bytes of an item's DQT payloads lie in SOI .. SOF0 as write_prefix made it, 0: no such table.
+static void dqt_payloads(const uint8_t* prefix, size_t len, uint32_t at[2])
+{
+    at[0] = at[1] = 0u;
+    for (size_t p = 2; p + 4 <= len && prefix[p] == 0xFF;) { // marker, length, and for a DQT the precision / id byte
+        if (prefix[p + 1] == 0xDB && prefix[p + 4] < 2) at[prefix[p + 4]] = uint32_t(p + 5);
+        p += 2 + (size_t(prefix[p + 2]) << 8 | prefix[p + 3]);
+    }
+}
+
+/// jpeggpu_ext_encode_batch, and with `specs` (items[i] is specs[i].item) jpeggpu_ext_transcode_batch; with `fit`
+/// (items[i] is fit[i].item at quality_max) jpeggpu_ext_encode_fit_batch.
 static jpeggpu_status batch_of(const jpeggpu_ext_encode_item* items, const TranscodeSpec* specs, int n, void* d_scratch, size_t scratch_size, size_t* d_sizes,
-                               int* d_status, jpeggpu_stream_t stream)
+                               int* d_status, jpeggpu_stream_t stream, const jpeggpu_ext_encode_fit_item* fit = nullptr, int* d_quality = nullptr)
 {
     if (!items || n <= 0 || !d_scratch || !d_sizes || !d_status) return JPEGGPU_INVALID_ARGUMENT;
     for (int i = 0; i < n; ++i)
@@ -711,8 +722,9 @@ static jpeggpu_status batch_of(const jpeggpu_ext_encode_item* items, const Trans
     std::vector<Item> dev;
     std::vector<std::vector<uint8_t>> headers;
     ProgBlob prog;
+    std::vector<FitItem> fits;
     try {
-        const jpeggpu_status st = make_plan(items, n, plan, &dev, &headers, &prog, specs);
+        const jpeggpu_status st = make_plan(items, n, plan, &dev, &headers, &prog, specs, fit != nullptr, fit ? &fits : nullptr);
         if (st != JPEGGPU_SUCCESS) return st;
     } catch (const std::bad_alloc&) {
         return JPEGGPU_OUT_OF_HOST_MEMORY;
@@ -745,11 +757,37 @@ static jpeggpu_status batch_of(const jpeggpu_ext_encode_item* items, const Trans
         std::memcpy(h + plan.prog.shadow_off, prog.shadow.data(), sizeof(Item) * prog.shadow.size());
         std::memcpy(h + plan.prog.items_off, prog.items.data(), sizeof(ProgItem) * prog.items.size());
     }
+    int probes = 0;
+    if (fit) { // every search starts at quality_max, whose tables the items and headers above hold
+        int widest = 1;
+        for (int i = 0; i < n; ++i) {
+            FitItem& f  = fits[size_t(i)];
+            f.max_bytes = fit[i].max_bytes;
+            f.lo = fit[i].quality_min, f.hi = f.q = fit[i].quality_max;
+            f.phase = kFitHigh;
+            // the header a standard item has in the blob begins with the prefix; an optimised one keeps it in its state
+            const size_t prefix_at = items[i].optimize ? offsetof(OptState, prefix) : 0;
+            const size_t prefix_n  = items[i].optimize ? size_t(kPrefixBytes) : headers[size_t(i)].size();
+            dqt_payloads(headers[size_t(i)].data() + prefix_at, prefix_n, f.dqt_off);
+            for (int t = 0; t < 2; ++t)
+                if (f.dqt_off[t]) f.dqt_off[t] += dev[size_t(i)].header_off + uint32_t(prefix_at);
+            widest = f.hi - f.lo + 1 > widest ? f.hi - f.lo + 1 : widest;
+        }
+        probes = fit_probes(widest);
+        std::memcpy(h + plan.fit_off, fits.data(), sizeof(FitItem) * fits.size());
+    }
     if (!rs.copied[r] && hipEventCreateWithFlags(&rs.copied[r], hipEventDisableTiming) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
     if (hipMemcpyAsync(base, h, plan.blob_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
     if (hipEventRecord(rs.copied[r], stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
     rs.in_use[r] = true;
     rs.next      = (r + 1) % Staging::kRing;
+    if (fit) {
+        int launched = 0;
+        if (launch_encode_fit(plan, probes, base, reinterpret_cast<unsigned long long*>(d_sizes), d_status, d_quality, stream, &launched) != hipSuccess ||
+            launched != fit_launches(probes, plan.optimized != 0))
+            return JPEGGPU_INTERNAL_ERROR;
+        return JPEGGPU_SUCCESS;
+    }
     if (launch_encode(plan, base, reinterpret_cast<unsigned long long*>(d_sizes), d_status, stream, specs != nullptr) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
     return JPEGGPU_SUCCESS;
 }
@@ -759,6 +797,33 @@ enum jpeggpu_status jpeggpu_ext_encode_batch(
 {
     return batch_of(items, nullptr, n, d_scratch, scratch_size, d_sizes, d_status, stream);
 }
+
+} // extern "C"
+
+namespace jg {
+namespace enc {
+
+size_t encode_fit_scratch(const jpeggpu_ext_encode_item* items, int n)
+{
+    Plan plan;
+    try {
+        if (make_plan(items, n, plan, nullptr, nullptr, nullptr, nullptr, true) != JPEGGPU_SUCCESS) return 0;
+    } catch (const std::bad_alloc&) {
+        return 0;
+    }
+    return size_t(plan.total) + 256; // room to align the caller's pointer
+}
+
+jpeggpu_status encode_fit_batch(const jpeggpu_ext_encode_item* items, const jpeggpu_ext_encode_fit_item* fit, int n, void* d_scratch, size_t scratch_size,
+                                size_t* d_sizes, int* d_status, int* d_quality, hipStream_t stream)
+{
+    return batch_of(items, nullptr, n, d_scratch, scratch_size, d_sizes, d_status, stream, fit, d_quality);
+}
+
+} // namespace enc
+} // namespace jg
+
+extern "C" {
 
 /// The specs of a transcode call and their encoder items side by side.
 static jpeggpu_status specs_of(const jpeggpu_ext_transcode_item* items, int n, bool need_device, std::vector<TranscodeSpec>& specs,

@@ -39,7 +39,13 @@
 // identity (jg_coefficients.cpp), so it launches gather_blocks<true> and what follows it. jpeggpu_ext_read_coefficients_batch
 // is the one launch of read_blocks at the end of this file: the gather's walk of the decoder's entries, stored as tensors.
 //
+// jpeggpu_ext_encode_fit_batch (jg_encode_fit.hip) searches the quality that fits a byte budget: its own pixel stage keeps the
+// unquantised transform, and every evaluation enqueues launches (1a, 1b,) 2 - 7 from here as they are (launch_table_stages,
+// launch_size_stages), the final pass launch 8 as well (launch_write_files). What the two files share on the device -- the
+// cursor algebra, the pixel stage up to the transform, the quantiser's division, a file's length -- is jg_encode_device.h.
+//
 // No kernel waits for another workgroup: every dependency is a launch boundary.
+#include "jg_encode_device.h"
 #include "jg_encode_prog.hpp"
 #include "jg_huff_core.h"
 #include "jg_output_device.h"
@@ -51,178 +57,25 @@ namespace jg {
 namespace enc {
 namespace {
 
-__device__ const uint8_t kNatural[64] = { // natural index of zigzag position k
-    0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
-    35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-__device__ inline uint32_t roundup8(uint32_t x) { return (x + 7u) & ~7u; }
-
-__device__ inline uint32_t apply(Cursor f, uint32_t x)
-{
-    return f.kind == kAdd ? x + f.a : f.kind == kRound ? roundup8(x + f.a) + f.b : f.b;
-}
-/// f first, then g.
-__device__ inline Cursor compose(Cursor f, Cursor g)
-{
-    if (g.kind == kConst) return g;
-    if (f.kind == kConst) return Cursor{kConst, 0u, apply(g, f.b)};
-    if (g.kind == kAdd) return f.kind == kAdd ? Cursor{kAdd, f.a + g.a, 0u} : Cursor{kRound, f.a, f.b + g.a};
-    if (f.kind == kAdd) return Cursor{kRound, f.a + g.a, g.b};
-    return Cursor{kRound, f.a, roundup8(f.b + g.a) + g.b};
-}
-__device__ inline Count compose(Count f, Count g)
-{
-    return g.reset ? g : Count{f.reset, f.ff + g.ff, f.starts + g.starts};
-}
-
-/// The item that owns a tile (a chunk): the last whose first tile (chunk) is not behind it. items[n] is a sentinel.
-__device__ inline int item_of_tile(const Item* items, int n, uint32_t tile)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (items[mid].tile_start <= tile) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-__device__ inline int item_of_chunk(const Item* items, int n, uint32_t chunk)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (items[mid].chunk_start <= chunk) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
-/// An item with optimised tables keeps its state where the others keep their header (jg_encode.hpp: Item::header_len).
-__device__ inline bool optimized(const Item& it) { return it.header_len == 0u; }
-/// A progressive item's blocks are transformed here and coded by jg_encode_prog.hip.
-__device__ inline bool progressive(const Item& it) { return it.header_len == kProgressiveHeader; }
-__device__ inline OptState* opt_state(const Item& it, uint8_t* scratch) { return reinterpret_cast<OptState*>(scratch + it.header_off); }
-__device__ inline const OptState* opt_state(const Item& it, const uint8_t* scratch) { return reinterpret_cast<const OptState*>(scratch + it.header_off); }
-/// The tables an item's blocks are coded with: the call's Annex K tables, or the item's own.
-__device__ inline const Tables* tables_of(const Item& it, const uint8_t* scratch, const Tables* standard)
-{
-    return optimized(it) ? &reinterpret_cast<const OptWork*>(scratch + opt_state(it, scratch)->work_off)->tables : standard;
-}
-
-/// Bytes of item i's unstuffed stream, padding of the last segment included: where the cursor stands behind its last tile.
-__device__ inline uint32_t stream_bytes(const Item* items, int i, const Cursor* tile_sum, const Cursor* tile_before)
-{
-    const uint32_t last = items[i + 1].tile_start - 1;
-    return (apply(compose(tile_before[last], tile_sum[last]), 0u) + 7u) >> 3;
-}
-
 // ------------------------------------------------------------------------------------------------
 // 1: pixels to coefficients
 // ------------------------------------------------------------------------------------------------
-
-__device__ inline int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
-
-/// One pass of jpeg_fdct_islow (jfdctint.c) over d[0], d[S], .. d[7 S]. FIRST: the row pass (results scaled by 4).
-template <int S, bool FIRST>
-__device__ inline void fdct_pass(int* d)
-{
-    constexpr int N = FIRST ? 11 : 15;
-    const int t0 = d[0] + d[7 * S], t7 = d[0] - d[7 * S], t1 = d[S] + d[6 * S], t6 = d[S] - d[6 * S];
-    const int t2 = d[2 * S] + d[5 * S], t5 = d[2 * S] - d[5 * S], t3 = d[3 * S] + d[4 * S], t4 = d[3 * S] - d[4 * S];
-    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
-    d[0]     = FIRST ? (t10 + t11) << 2 : descale(t10 + t11, 2);
-    d[4 * S] = FIRST ? (t10 - t11) << 2 : descale(t10 - t11, 2);
-    int z1   = (t12 + t13) * 4433;
-    d[2 * S] = descale(z1 + t13 * 6270, N);
-    d[6 * S] = descale(z1 - t12 * 15137, N);
-    z1       = t4 + t7;
-    int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
-    const int z5 = (z3 + z4) * 9633;
-    const int u4 = t4 * 2446, u5 = t5 * 16819, u6 = t6 * 25172, u7 = t7 * 12299;
-    z1 *= -7373;
-    z2 *= -20995;
-    z3 = z3 * -16069 + z5;
-    z4 = z4 * -3196 + z5;
-    d[7 * S] = descale(u4 + z1 + z3, N);
-    d[5 * S] = descale(u5 + z2 + z4, N);
-    d[3 * S] = descale(u6 + z2 + z3, N);
-    d[S]     = descale(u7 + z1 + z4, N);
-}
 
 __global__ __launch_bounds__(kTileBlocks) void encode_blocks(const Item* __restrict__ items, int n, uint8_t* __restrict__ scratch)
 {
     const Item& it = items[item_of_tile(items, n, blockIdx.x)];
     const int b    = (blockIdx.x - it.tile_start) * kTileBlocks + threadIdx.x;
     if (b >= it.blocks) return;
-    const int mcu = b / it.blocks_per_mcu, j = b - mcu * it.blocks_per_mcu;
-    const int my = mcu / it.mcus_x, mx = mcu - my * it.mcus_x;
-    const int luma_blocks = it.hs * it.vs;
-    const int w = it.width, h = it.height;
-    // the block of its component's plane that this lane transforms, and the input samples per sample of that plane
-    int bx, by, fx = 1, fy = 1, comp = 0;
-    bool dummy = false;
-    if (j < luma_blocks) {
-        const int yo = j / it.hs, xo = j - yo * it.hs;
-        bx = mx * it.hs + xo;
-        by = my * it.vs + yo;
-        // jccoefct.c: a block of the MCU beyond the component's grid is 63 zeros and the DC of the block before it in the MCU's
-        // order -- at the right edge the last real block of its row, below the grid the last block of the row above
-        if (by >= it.grid_h) {
-            dummy = true;
-            by -= 1;
-            bx = min(mx * it.hs + it.hs - 1, it.grid_w - 1);
-        } else if (bx >= it.grid_w) {
-            dummy = true;
-            bx    = it.grid_w - 1;
-        }
-    } else {
-        comp = 1 + j - luma_blocks;
-        bx = mx, by = my, fx = it.hs, fy = it.vs;
-    }
-    // jccolor.c's fixed point; grey input is the sample itself
-    int kr = 19595, kg = 38470, kb = 7471, rnd = 32768;
-    if (comp == 1) kr = -11059, kg = -21709, kb = 32768, rnd = (128 << 16) + 32767;
-    if (comp == 2) kr = 32768, kg = -27439, kb = -5329, rnd = (128 << 16) + 32767;
-    const bool grey    = it.channels == 1;
-    const int shift    = (fx == 2) + (fy == 2);
-    const int plane_h  = (h + fy - 1) / fy; // rows: the input repeats its last row to a multiple of fy only, then the LAST DOWNSAMPLED row repeats
-    const uint8_t* src = it.src;
-    const int64_t cs   = it.channel_stride;
-
-    int d[64];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const int cy = min(by * 8 + r, plane_h - 1);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const int cx = bx * 8 + c;
-            int sum      = 0;
-            for (int dy = 0; dy < fy; ++dy) {
-                const uint8_t* row = src + int64_t(min(cy * fy + dy, h - 1)) * it.row_pitch;
-                for (int dx = 0; dx < fx; ++dx) {
-                    const uint8_t* p = row + int64_t(min(cx * fx + dx, w - 1)) * it.pixel_stride; // columns: the last sample repeats
-                    sum += grey ? int(p[0]) : (kr * int(p[0]) + kg * int(p[cs]) + kb * int(p[2 * cs]) + rnd) >> 16;
-                }
-            }
-            // jcsample.c: h2v1 bias 0, 1, 0, 1 .., h2v2 bias 1, 2, 1, 2 .. along the output row
-            const int bias = fx == 2 ? (fy == 2 ? 1 + (cx & 1) : (cx & 1)) : 0;
-            d[r * 8 + c]   = ((sum + bias) >> shift) - 128;
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 8; ++r) fdct_pass<1, true>(d + 8 * r);
-#pragma unroll
-    for (int c = 0; c < 8; ++c) fdct_pass<8, false>(d + c);
+    int d[64], comp;
+    bool dummy;
+    transform_block(it, b, d, comp, dummy);
 
     const uint16_t* divisor = it.divisor[comp > 0];
     uint4* out              = reinterpret_cast<uint4*>(scratch + it.coef_off) + size_t(b) * 8;
     uint32_t packed[32];
 #pragma unroll
     for (int k = 0; k < 64; ++k) {
-        const int c       = d[kNatural[k]];
-        const uint32_t dv = divisor[k];
-        int t             = int((uint32_t(abs(c)) + (dv >> 1)) / dv);
-        t                 = c < 0 ? -t : t;
+        int t = quantize(d[kNatural[k]], divisor[k]);
         if (dummy && k) t = 0;
         if (k & 1) packed[k >> 1] |= uint32_t(t) << 16;
         else packed[k >> 1] = uint32_t(t) & 0xFFFFu;
@@ -782,22 +635,12 @@ __global__ __launch_bounds__(256) void write_files(
         const int i          = item_of_chunk(items, n, chunk);
         const Item& it       = items[i];
         const uint32_t part  = chunk - it.chunk_start;
-        const uint32_t bytes = stream_bytes(items, i, tile_sum, tile_before);
-        // the size is known before a byte is written: header, stream, a 0x00 per 0xFF, two bytes per marker, EOI
-        const uint32_t last_chunk = items[i + 1].chunk_start - 1;
-        const Count all           = compose(count_before[last_chunk], counts[last_chunk]);
-        // an item with optimised tables has its header in parts: what the host wrote around what build_tables made
-        const OptState* st  = optimized(it) ? opt_state(it, blob) : nullptr;
-        uint32_t header_len = it.header_len, table_status = 0u;
-        if (st) {
-            header_len = st->prefix_len + st->suffix_len;
-            for (int t = 0; t < 4; ++t) {
-                header_len += st->dht_len[t];
-                table_status = max(table_status, st->table_status[t]);
-            }
-        }
-        const uint64_t size = table_status ? 0u : uint64_t(header_len) + bytes + all.ff + 2u * all.starts + 2u;
-        const bool fits     = size <= it.capacity;
+        // the size is known before a byte is written (jg_encode_device.h: file_size)
+        const FileSize fs    = file_size(items, i, blob, tile_sum, tile_before, counts, count_before);
+        const uint32_t bytes = fs.bytes, header_len = fs.header_len, table_status = fs.table_status;
+        const uint64_t size  = fs.size;
+        const OptState* st   = optimized(it) ? opt_state(it, blob) : nullptr;
+        const bool fits      = size <= it.capacity;
         if (part == 0 && threadIdx.x == 0) {
             d_sizes[i]  = size;
             d_status[i] = table_status ? int(table_status) : fits ? 0 : 1;
@@ -1194,6 +1037,38 @@ hipError_t launch_read_blocks(const ReadItem* d_items, int n, uint32_t tiles, in
 
 hipError_t launch_encode(const Plan& plan, uint8_t* d_scratch, unsigned long long* d_sizes, int* d_status, hipStream_t stream, bool transcode)
 {
+    const Item* items = reinterpret_cast<const Item*>(d_scratch + plan.items_off);
+    if (transcode && plan.oriented) gather_blocks<true><<<plan.tiles, kTileBlocks, 0, stream>>>(reinterpret_cast<Item*>(d_scratch + plan.items_off), plan.n, d_scratch);
+    else if (transcode) gather_blocks<false><<<plan.tiles, kTileBlocks, 0, stream>>>(reinterpret_cast<Item*>(d_scratch + plan.items_off), plan.n, d_scratch);
+    else encode_blocks<<<plan.tiles, kTileBlocks, 0, stream>>>(items, plan.n, d_scratch);
+    const auto finish = [&] { // a transcode call's last launch
+        if (transcode) finish_transcode<<<(uint32_t(plan.n) + 255u) / 256u, 256, 0, stream>>>(items, plan.n, d_sizes, d_status);
+        return hipGetLastError();
+    };
+    launch_table_stages(plan, d_scratch, stream);
+    if (plan.prog.n) { // the progressive items' own launches; the rest of the call follows as it always did
+        hipError_t e = launch_prog_front(plan, d_scratch, stream);
+        if (e == hipSuccess) e = launch_prog_tables(plan, d_scratch, stream);
+        if (e == hipSuccess) e = launch_prog_back(plan, d_scratch, d_sizes, d_status, stream);
+        if (e != hipSuccess) return e;
+        if (plan.chunks == 0u) return finish(); // every item is progressive
+    }
+    launch_size_stages(plan, d_scratch, stream);
+    launch_write_files(plan, d_scratch, d_sizes, d_status, stream);
+    return finish();
+}
+
+int launch_table_stages(const Plan& plan, uint8_t* d_scratch, hipStream_t stream)
+{
+    if (!plan.optimized) return 0;
+    const Item* items = reinterpret_cast<const Item*>(d_scratch + plan.items_off);
+    count_symbols<<<plan.tiles, kTileBlocks, 0, stream>>>(items, plan.n, d_scratch);
+    build_tables<<<uint32_t(plan.n) * 4u, 64, 0, stream>>>(items, plan.n, d_scratch);
+    return 2;
+}
+
+int launch_size_stages(const Plan& plan, uint8_t* d_scratch, hipStream_t stream)
+{
     const Item* items     = reinterpret_cast<const Item*>(d_scratch + plan.items_off);
     const Tables* tables  = reinterpret_cast<const Tables*>(d_scratch + plan.tables_off);
     uint32_t* bits        = reinterpret_cast<uint32_t*>(d_scratch + plan.bits_off);
@@ -1202,32 +1077,25 @@ hipError_t launch_encode(const Plan& plan, uint8_t* d_scratch, unsigned long lon
     Count* counts         = reinterpret_cast<Count*>(d_scratch + plan.count_off);
     Count* count_before   = reinterpret_cast<Count*>(d_scratch + plan.count_before_off);
     const uint32_t chunk_grid = plan.chunks < 4096u ? plan.chunks : 4096u;
-    if (transcode && plan.oriented) gather_blocks<true><<<plan.tiles, kTileBlocks, 0, stream>>>(reinterpret_cast<Item*>(d_scratch + plan.items_off), plan.n, d_scratch);
-    else if (transcode) gather_blocks<false><<<plan.tiles, kTileBlocks, 0, stream>>>(reinterpret_cast<Item*>(d_scratch + plan.items_off), plan.n, d_scratch);
-    else encode_blocks<<<plan.tiles, kTileBlocks, 0, stream>>>(items, plan.n, d_scratch);
-    const auto finish = [&] { // a transcode call's last launch
-        if (transcode) finish_transcode<<<(uint32_t(plan.n) + 255u) / 256u, 256, 0, stream>>>(items, plan.n, d_sizes, d_status);
-        return hipGetLastError();
-    };
-    if (plan.optimized) {
-        count_symbols<<<plan.tiles, kTileBlocks, 0, stream>>>(items, plan.n, d_scratch);
-        build_tables<<<uint32_t(plan.n) * 4u, 64, 0, stream>>>(items, plan.n, d_scratch);
-    }
-    if (plan.prog.n) { // the progressive items' own launches; the rest of the call follows as it always did
-        hipError_t e = launch_prog_front(plan, d_scratch, stream);
-        if (e == hipSuccess) e = launch_prog_tables(plan, d_scratch, stream);
-        if (e == hipSuccess) e = launch_prog_back(plan, d_scratch, d_sizes, d_status, stream);
-        if (e != hipSuccess) return e;
-        if (plan.chunks == 0u) return finish(); // every item is progressive
-    }
     count_bits<<<plan.tiles, kTileBlocks, 0, stream>>>(items, plan.n, tables, d_scratch, bits, tile_sum);
     scan_before<Cursor><<<1, kScanThreads, 0, stream>>>(tile_sum, tile_before, plan.tiles);
     clear_streams<<<chunk_grid, 256, 0, stream>>>(items, plan.n, plan.chunks, d_scratch, tile_sum, tile_before);
     pack_blocks<<<plan.tiles, kTileBlocks, 0, stream>>>(items, plan.n, tables, d_scratch, bits, tile_before);
     count_bytes<<<chunk_grid, 256, 0, stream>>>(items, plan.n, plan.chunks, d_scratch, tile_sum, tile_before, counts);
     scan_before<Count><<<1, kScanThreads, 0, stream>>>(counts, count_before, plan.chunks);
-    write_files<<<chunk_grid, 256, 0, stream>>>(items, plan.n, plan.chunks, d_scratch, d_scratch, tile_sum, tile_before, counts, count_before, d_sizes, d_status);
-    return finish();
+    return 6;
+}
+
+int launch_write_files(const Plan& plan, uint8_t* d_scratch, unsigned long long* d_sizes, int* d_status, hipStream_t stream)
+{
+    const Item* items   = reinterpret_cast<const Item*>(d_scratch + plan.items_off);
+    Cursor* tile_sum    = reinterpret_cast<Cursor*>(d_scratch + plan.tile_sum_off);
+    Cursor* tile_before = reinterpret_cast<Cursor*>(d_scratch + plan.tile_before_off);
+    Count* counts       = reinterpret_cast<Count*>(d_scratch + plan.count_off);
+    Count* count_before = reinterpret_cast<Count*>(d_scratch + plan.count_before_off);
+    write_files<<<plan.chunks < 4096u ? plan.chunks : 4096u, 256, 0, stream>>>(items, plan.n, plan.chunks, d_scratch, d_scratch, tile_sum, tile_before, counts, count_before,
+                                                                             d_sizes, d_status);
+    return 1;
 }
 
 hipError_t launch_prog_tables(const Plan& plan, uint8_t* d_scratch, hipStream_t stream)

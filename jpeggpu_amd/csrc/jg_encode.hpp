@@ -143,6 +143,7 @@ struct Plan {
     uint32_t tiles, chunks;
     uint64_t tables_off, items_off; // in the blob
     uint64_t gather_off;            // in the blob: GatherSrc[n] of a transcode call (jg_transcode.hpp), nothing otherwise
+    uint64_t fit_off;               // in the blob: FitItem[n] of a budget call (jg_encode_fit.hpp), nothing otherwise
     uint64_t blob_bytes;
     uint64_t bits_off;        // uint32[tiles * kTileBlocks]
     uint64_t tile_sum_off;    // Cursor[tiles]: each tile's own function
@@ -155,6 +156,14 @@ struct Plan {
 /// `transcode`: every item's Item::src is its GatherSrc (jg_transcode.hpp); gather_blocks takes the place of encode_blocks and
 /// finish_transcode follows the last launch.
 hipError_t launch_encode(const Plan& plan, uint8_t* d_scratch, unsigned long long* d_sizes, int* d_status, hipStream_t stream, bool transcode = false);
+
+/// The parts of launch_encode behind its first launch, as a budget call enqueues them once per probe (jg_encode_fit.hip);
+/// each returns the number of launches it enqueued. launch_table_stages: launches 1a and 1b if the call has an item with
+/// optimised tables, else nothing. launch_size_stages: launches 2 - 7, after which every item's size is known on the
+/// device. launch_write_files: launch 8.
+int launch_table_stages(const Plan& plan, uint8_t* d_scratch, hipStream_t stream);
+int launch_size_stages(const Plan& plan, uint8_t* d_scratch, hipStream_t stream);
+int launch_write_files(const Plan& plan, uint8_t* d_scratch, unsigned long long* d_sizes, int* d_status, hipStream_t stream);
 
 /// jpeg_gen_optimal_table of n_tables x 256 counts: per table 16 `bits` bytes and 256 `values` bytes, and a status.
 hipError_t launch_tables_from_counts(const uint32_t* d_counts, int n_tables, uint8_t* d_bits_values, int* d_status, hipStream_t stream);
