@@ -1,7 +1,8 @@
 // jg_encode_fit.cpp -- encoding to a byte budget, the host's part (include/jpeggpu/jpeggpu_ext.h: jpeggpu_ext_encode_fit_*):
 // the checks of a call's ranges and the items the encoder's planner sees, each at its quality_max, where every search
-// starts. The plan, the descriptors and the launches are jg_encode.cpp's and jg_encode_fit.hip's (jg_encode_fit.hpp).
+// starts. The plan and the descriptors are jg_encode_plan.cpp's, the launches jg_encode.cpp's and jg_encode_fit.hip's.
 #include "jg_encode_fit.hpp"
+#include "jg_encode_plan.hpp"
 
 #include <new>
 #include <vector>
@@ -34,7 +35,7 @@ size_t jpeggpu_ext_encode_fit_scratch_size(const struct jpeggpu_ext_encode_fit_i
     try {
         std::vector<jpeggpu_ext_encode_item> plain;
         if (plain_items(items, n, plain) != JPEGGPU_SUCCESS) return 0;
-        return jg::enc::encode_fit_scratch(plain.data(), n);
+        return jg::enc::scratch_size_of(plain.data(), nullptr, n, true);
     } catch (const std::bad_alloc&) {
         return 0;
     }
@@ -44,7 +45,7 @@ int jpeggpu_ext_encode_fit_launches(const struct jpeggpu_ext_encode_fit_item* it
 {
     try {
         std::vector<jpeggpu_ext_encode_item> plain;
-        if (plain_items(items, n, plain) != JPEGGPU_SUCCESS || jg::enc::encode_fit_scratch(plain.data(), n) == 0) return 0;
+        if (plain_items(items, n, plain) != JPEGGPU_SUCCESS || jg::enc::scratch_size_of(plain.data(), nullptr, n, true) == 0) return 0;
     } catch (const std::bad_alloc&) {
         return 0;
     }

@@ -15,56 +15,15 @@
 
 #include "jg_encode.hpp"
 
-#include <jpeggpu/jpeggpu.h>
-#include <jpeggpu/jpeggpu_ext.h>
-
 namespace jg {
 namespace enc {
-
-/// Where an item's search stands. In the blob, behind the call's other descriptors; the device moves it on.
-enum FitPhase : int32_t {
-    kFitHigh   = 0, // the probe under way is quality_max
-    kFitLow    = 1, // .. quality_min
-    kFitBisect = 2, // .. (a + b) / 2
-    kFitDone   = 3  // `q` is the chosen quality
-};
-struct FitItem {
-    uint64_t raw_off;    // in d_scratch: int16[blocks][64], the unquantised transform (8 times the DCT), zigzag order, MCU
-                         // stream order, a dummy block's AC zero
-    uint64_t max_bytes;
-    uint32_t dqt_off[2]; // in the blob: the 64 bytes of the item's DQT payloads (luma, chroma), 0: the file has no such table
-    int32_t lo, hi;      // quality_min, quality_max
-    int32_t a, b, best;  // the bisection's state
-    int32_t q;           // the quality of the probe under way: the item's divisors and DQT bytes are this quality's
-    int32_t phase;       // FitPhase
-    int32_t over;        // 1: even quality_min exceeds max_bytes
-    int32_t blocks;      // Item::blocks, which is 0 while a finished item sits out the remaining probes
-    int32_t pad;
-};
-static_assert(sizeof(FitItem) == 64, "FitItem[n] follows the blob's 256-byte grid");
-
-/// Evaluations of size() that the rule needs at most for a range of `widest` qualities: 1 for one quality, 2 for two,
-/// else quality_max, quality_min and the bisection of widest - 2 values: 2 + floor(log2(widest - 2)) + 1. 9 for 1..100.
-inline int fit_probes(int widest)
-{
-    if (widest <= 2) return widest < 1 ? 1 : widest;
-    int steps = 0;
-    for (int m = widest - 2; m; m >>= 1) ++steps;
-    return 2 + steps;
-}
-
-/// Launches of a budget call: the transform; per probe the requantiser, the table stages if an item has optimised tables
-/// (2), the size stages (6) and the decision; then the final pass: requantiser, table stages, size stages, write_files and
-/// the report. 10 + 8 probes, with optimised tables 12 + 10 probes -- whatever n and the image sizes are.
-inline int fit_launches(int probes, bool optimized) { return optimized ? 12 + 10 * probes : 10 + 8 * probes; }
 
 /// Enqueues the call; *launched receives the number of launches.
 hipError_t launch_encode_fit(const Plan& plan, int probes, uint8_t* d_scratch, unsigned long long* d_sizes, int* d_status, int* d_quality, hipStream_t stream,
                              int* launched);
 
-/// jg_encode.cpp: the plan and the descriptors of a budget call, behind the checks of jg_encode_fit.cpp. `items[i]` is
-/// fit[i].item with quality_max as its quality.
-size_t encode_fit_scratch(const jpeggpu_ext_encode_item* items, int n);
+/// jg_encode.cpp: a budget call behind the checks of jg_encode_fit.cpp. `items[i]` is fit[i].item with quality_max as its
+/// quality. (Its scratch size: jg_encode_plan.hpp, scratch_size_of.)
 jpeggpu_status encode_fit_batch(const jpeggpu_ext_encode_item* items, const jpeggpu_ext_encode_fit_item* fit, int n, void* d_scratch, size_t scratch_size,
                                 size_t* d_sizes, int* d_status, int* d_quality, hipStream_t stream);
 

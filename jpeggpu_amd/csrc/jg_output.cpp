@@ -20,43 +20,11 @@ jpeggpu_status launched(hipError_t err) { return err == hipSuccess ? JPEGGPU_SUC
 /// The 256-aligned start of a caller's scratch: what the plans' offsets count from.
 uint8_t* scratch_base(void* d_scratch) { return reinterpret_cast<uint8_t*>(jg::align_up(reinterpret_cast<uintptr_t>(d_scratch), 256)); }
 
-/// Page-locked staging of the descriptors and tables: a ring of four per process, as the batch handle keeps its own.
-/// Never destroyed (the HIP runtime may be gone when static objects are).
-struct Staging {
-    static constexpr int kRing = 4;
-    std::mutex mu;
-    jg::StagingBuffer buf[kRing];
-    hipEvent_t copied[kRing] = {};
-    bool in_use[kRing]       = {};
-    int next                 = 0;
-};
-Staging& staging()
+/// The output stage's staging ring (the encoder keeps its own: a resize call does not wait for an encode call's lock).
+jg::StagingRing& staging()
 {
-    static Staging* s = new Staging;
+    static jg::StagingRing* s = new jg::StagingRing;
     return *s;
-}
-
-/// What every batched call does with its plan's staged part: the ring's next buffer with room for `bytes`, once the copy
-/// that last read it has executed; `fill(pinned bytes)`, which writes them and returns a status; the copy to `d_dst` on
-/// `stream`; the ring moves on. A failure leaves the ring where it was. Called with staging().mu held; the callers hold
-/// it until their kernels are enqueued too.
-template <class Fill>
-jpeggpu_status stage_and_copy(size_t bytes, Fill fill, void* d_dst, hipStream_t stream)
-{
-    Staging& rs = staging();
-    const int r = rs.next;
-    // the staging buffer may still be the source of a copy enqueued kRing calls ago
-    if (rs.in_use[r] && hipEventSynchronize(rs.copied[r]) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
-    rs.in_use[r] = false;
-    if (!rs.buf[r].reserve(bytes)) return JPEGGPU_OUT_OF_HOST_MEMORY;
-    const jpeggpu_status filled = fill(rs.buf[r].ptr);
-    if (filled != JPEGGPU_SUCCESS) return filled;
-    if (!rs.copied[r] && hipEventCreateWithFlags(&rs.copied[r], hipEventDisableTiming) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
-    if (hipMemcpyAsync(d_dst, rs.buf[r].ptr, bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
-    if (hipEventRecord(rs.copied[r], stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
-    rs.in_use[r] = true;
-    rs.next      = (r + 1) % Staging::kRing;
-    return JPEGGPU_SUCCESS;
 }
 
 enum jpeggpu_status planes_to_rgbi_libjpeg(
@@ -92,7 +60,7 @@ enum jpeggpu_status run_resize(
     const int n   = static_cast<int>(p.jobs.size());
     std::lock_guard<std::mutex> lock(staging().mu);
     const jpeggpu_status staged =
-        stage_and_copy(p.head, [&](uint8_t* h) { return jg::fill_resize(p, spec ? spec->flips : nullptr, base, h); }, base, stream);
+        staging().stage_and_copy(p.head, [&](uint8_t* h) { return jg::fill_resize(p, spec ? spec->flips : nullptr, base, h); }, base, stream);
     if (staged != JPEGGPU_SUCCESS) return staged;
     const jg::ResizeJob* d_jobs = reinterpret_cast<const jg::ResizeJob*>(base);
     const int* d_first = reinterpret_cast<const int*>(base + p.off_first);
@@ -332,7 +300,7 @@ enum jpeggpu_status jpeggpu_ext_batch_to_rgb(
     if (!d_scratch || scratch_size < jpeggpu_ext_batch_rgb_scratch_size(n)) return JPEGGPU_INVALID_ARGUMENT;
     uint8_t* base = scratch_base(d_scratch);
     std::lock_guard<std::mutex> lock(staging().mu);
-    const jpeggpu_status staged = stage_and_copy(
+    const jpeggpu_status staged = staging().stage_and_copy(
         p.at.total,
         [&](uint8_t* h) {
             jg::fill_rgb_batch(p, h);
@@ -373,7 +341,7 @@ enum jpeggpu_status jpeggpu_ext_batch_to_gray(
     if (!d_scratch || scratch_size < jpeggpu_ext_batch_gray_scratch_size(n)) return JPEGGPU_INVALID_ARGUMENT;
     uint8_t* base = scratch_base(d_scratch);
     std::lock_guard<std::mutex> lock(staging().mu);
-    const jpeggpu_status staged = stage_and_copy(
+    const jpeggpu_status staged = staging().stage_and_copy(
         p.at.total,
         [&](uint8_t* h) {
             jg::fill_rgb_batch(p, h);
@@ -407,7 +375,7 @@ enum jpeggpu_status jpeggpu_ext_resize_view_to_gray_tensor(
     if (reinterpret_cast<uintptr_t>(dst) % jg::tensor_elem_size(s.type) != 0) return JPEGGPU_INVALID_ARGUMENT;
     uint8_t* base = scratch_base(d_scratch);
     std::lock_guard<std::mutex> lock(staging().mu);
-    const jpeggpu_status staged = stage_and_copy(p.head, [&](uint8_t* h) { return jg::fill_resize(p, s.flips, base, h); }, base, stream);
+    const jpeggpu_status staged = staging().stage_and_copy(p.head, [&](uint8_t* h) { return jg::fill_resize(p, s.flips, base, h); }, base, stream);
     if (staged != JPEGGPU_SUCCESS) return staged;
     return launched(jg::launch_gray_resize(
         reinterpret_cast<const jg::ResizeJob*>(base), reinterpret_cast<const int*>(base + p.off_first), reinterpret_cast<const int*>(base + p.off_first_t), n,
@@ -426,7 +394,7 @@ enum jpeggpu_status jpeggpu_ext_roundtrip_batch(
     if (st != JPEGGPU_SUCCESS) return st;
     if (!d_scratch || scratch_size < p.total + 256) return JPEGGPU_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(staging().mu);
-    const jpeggpu_status staged = stage_and_copy(
+    const jpeggpu_status staged = staging().stage_and_copy(
         p.head,
         [&](uint8_t* h) {
             jg::rt::fill_roundtrip(p, h);
@@ -454,7 +422,7 @@ enum jpeggpu_status jpeggpu_ext_thumbnail_to_rgb(
     if (!dst || !d_scratch || scratch_size < t.total) return JPEGGPU_INVALID_ARGUMENT;
     if (t.tiles > 0) { // the reduction of the items that have factors: one launch
         std::lock_guard<std::mutex> lock(staging().mu);
-        const jpeggpu_status staged = stage_and_copy(
+        const jpeggpu_status staged = staging().stage_and_copy(
             t.head,
             [&](uint8_t* h) {
                 jg::fill_thumbnails(t, h);

@@ -1,6 +1,6 @@
 // jg_quant.h -- jpeg_set_quality's arithmetic (jcparam.c: jpeg_quality_scaling, jpeg_add_quant_table with force_baseline)
 // on the Annex K.1 / K.2 tables, for host and device alike: the host planner writes an item's DQT segments and divisors with
-// it (jg_encode.cpp), the budget search derives them on the device from a quality that lives there (jg_encode_fit.hip).
+// it (jg_encode_plan.cpp), the budget search derives them on the device from a quality that lives there (jg_encode_fit.hip).
 // Plain C++: a host compiler reads it without the HIP headers.
 #ifndef JG_QUANT_H_
 #define JG_QUANT_H_

@@ -159,7 +159,7 @@ def grid_images():
 
 
 def counts(case):
-    """What jg_encode.cpp plans for an item: blocks, restart segments, tiles of the block kernels, the worst-case bound of
+    """What jg_encode_plan.cpp plans for an item: blocks, restart segments, tiles of the block kernels, the worst-case bound of
     its unstuffed stream and the chunks of the byte kernels that cover it."""
     hs, vs = (1, 1) if case["grey"] else {"4:4:4": (1, 1), "4:2:2": (2, 1), "4:2:0": (2, 2)}[case["subsampling"]]
     mcus_x, mcus_y = -(-case["w"] // (8 * hs)), -(-case["h"] // (8 * vs))

@@ -97,7 +97,7 @@ def test_bound_of_optimised_items(L):
 
 
 def _plan_total(items, flags):
-    """jg_encode.cpp's make_plan restated for items without optimised tables: every part starts on a multiple of 256."""
+    """jg_encode_plan.cpp's make_plan restated for items without optimised tables: every part starts on a multiple of 256."""
     assert not any(flags)
     off = 0
 

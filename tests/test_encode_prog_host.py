@@ -1,4 +1,4 @@
-"""The host side of progressive encoding (jg_encode.cpp): the item's layout, argument checks, the header call, the bound
+"""The host side of progressive encoding (jg_encode_plan.cpp): the item's layout, argument checks, the header call, the bound
 against Pillow's pinned files and the restatement's worst inputs, and that nothing changed for items without the flag. No
 device is needed."""
 import ctypes as C
