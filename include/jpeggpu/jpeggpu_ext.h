@@ -32,6 +32,8 @@
  *                                      Image.convert("RGB") makes of files of all five
  *   jpeggpu_ext_set_progressive /      progressive JPEGs (SOF2), per decoder and off by default: their scans are decoded
  *   jpeggpu_ext_get_progressive_info   on the device into coefficient buffers and handed to the IDCT stage
+ *   jpeggpu_ext_set_truncated /        files that end early, per decoder and off by default: decoded as libjpeg finishes them
+ *   jpeggpu_ext_get_truncated          for Pillow under ImageFile.LOAD_TRUNCATED_IMAGES (the rows that are there, grey below)
  *   jpeggpu_ext_resize_to_tensor       the batched resize written as a model's input: uint8, float32, float16 or bfloat16,
  *                                      normalised as ToTensor + Normalize do, items flipped left to right where asked
  *   jpeggpu_ext_resize_view_to_tensor  the evaluation transform: a window of the resize of each item's WHOLE image, zero
@@ -658,6 +660,44 @@ struct jpeggpu_ext_progressive_info {
 };
 enum jpeggpu_status jpeggpu_ext_set_progressive(jpeggpu_decoder_t decoder, int enable);
 enum jpeggpu_status jpeggpu_ext_get_progressive_info(jpeggpu_decoder_t decoder, struct jpeggpu_ext_progressive_info* info);
+
+/* Truncated files (baseline and extended-sequential Huffman frames). OFF by default: a decoder that was not told otherwise
+ * answers a file that ends early as it always did (JPEGGPU_INVALID_JPEG from jpeggpu_decoder_parse_header).
+ * jpeggpu_ext_set_truncated(decoder, 1) takes effect from the next jpeggpu_decoder_parse_header: a file that ends anywhere
+ * behind its first SOS header then parses with JPEGGPU_SUCCESS and decodes to what Pillow returns for it with
+ * ImageFile.LOAD_TRUNCATED_IMAGES set (libjpeg given a fake EOI), through every decode call of this library:
+ *   - the entropy-coded data is what lies in front of the end of the file; a trailing FF -- half of a stuffed FF 00 pair or of
+ *     a marker -- is not data;
+ *   - behind the last real bit the bit reader delivers zero bits. The first MCU that needs a bit that does not exist is
+ *     finished from them (a coefficient whose run of zeros overshoots the block goes to index 63, as in jdhuff.c);
+ *   - every MCU behind that one, to the end of the scan, has no coefficients at all, DC included: samples of 128;
+ *   - restart intervals without data are such MCUs. Where the data ends with an interval and no bit was missing yet -- in
+ *     front of, inside or right behind the restart marker -- the NEXT interval's first MCU is the one decoded from zero bits,
+ *     with the DC predictions reset, and the emptying starts behind it;
+ *   - a file that lacks only its EOI, or only half of it, decodes as the whole file does.
+ * Fewer restart markers than the frame asks for are accepted under the flag; more, or a file cut in front of the end of its
+ * first SOS header, are refused as ever. A whole file parses and decodes under the flag exactly as without it.
+ * Refused under the flag with JPEGGPU_NOT_SUPPORTED: progressive frames (SOF2), also whole ones (libjpeg smooths the blocks
+ * of a progressive file that ends early); jpeggpu_ext_set_segment_shard with more than one rank; a file of
+ * several scans that ends in front of a scan some component needs. jpeggpu_ext_set_device_scan is silently not used while
+ * the flag is set: the host walk is what records where the data ends.
+ *
+ * On the device a truncated image costs THREE launches more per call, whatever the call holds (jg_trunc.hip): one in front
+ * of the Huffman stages and two between the write pass and the IDCT stage, each covering every truncated image of the call
+ * (of the part, where jpeggpu_ext_batch_set_overlap cuts the call into parts). A call without a truncated image launches
+ * what it always launched. The MCU that was finished from zero bits is found on the device and stays there: nothing
+ * synchronises. jpeggpu_ext_get_truncated reports what the host walk of the last parsed image knows. The coefficient routes
+ * (jpeggpu_ext_read_coefficients_batch, jpeggpu_ext_transcode_batch) see the same data units as the IDCT stage: the blocks
+ * behind the cut are all zero. */
+struct jpeggpu_ext_truncated_info {
+    int truncated;              /* 1: the file ended without an EOI marker (all else as below) */
+    int scan;                   /* the scan whose entropy-coded data runs to the end of the file, or -1: the file ended
+                                   behind a whole scan (only the EOI, or trailing segments, are missing) */
+    size_t scan_bytes;          /* bytes of that scan that are present, stuffing and restart markers included; 0 if scan < 0 */
+    int first_missing_interval; /* the first restart interval without any data, or -1: none, or no restart markers */
+};
+enum jpeggpu_status jpeggpu_ext_set_truncated(jpeggpu_decoder_t decoder, int enable);
+enum jpeggpu_status jpeggpu_ext_get_truncated(jpeggpu_decoder_t decoder, struct jpeggpu_ext_truncated_info* info);
 
 /* EXIF orientation. jpeggpu_decoder_parse_header reads the Exif APP1 segments in front of the first scan the way Pillow
  * 12 does and jpeggpu_ext_get_orientation reports the Orientation tag (0x0112) of the last parsed image, 1..8:

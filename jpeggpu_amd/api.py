@@ -107,6 +107,12 @@ class ProgressiveInfo(C.Structure):
                 ("visible_blocks_x", C.c_int * MAX_COMP), ("visible_blocks_y", C.c_int * MAX_COMP)]
 
 
+class TruncatedInfo(C.Structure):
+    """struct jpeggpu_ext_truncated_info: whether the last parsed file ended without its EOI, the scan it ends in (-1: behind
+    a whole scan), that scan's bytes that are present, and the first restart interval without data (-1: none)."""
+    _fields_ = [("truncated", C.c_int), ("scan", C.c_int), ("scan_bytes", C.c_size_t), ("first_missing_interval", C.c_int)]
+
+
 class ResizeItem(C.Structure):
     """struct jpeggpu_ext_resize_item: a decoded image's info and planes, and its crop (NULL: the whole image)."""
     _fields_ = [("info", C.POINTER(ImgInfo)), ("crop", C.POINTER(CropInfo)), ("src", C.POINTER(Img))]
@@ -331,6 +337,9 @@ def lib():
         C.c_void_p]
     L.jpeggpu_ext_set_progressive.argtypes = [dec, C.c_int]
     L.jpeggpu_ext_get_progressive_info.argtypes = [dec, C.POINTER(ProgressiveInfo)]
+    if hasattr(L, "jpeggpu_ext_set_truncated"):  # (a library loaded through JPEGGPU_LIB may be older than this file)
+        L.jpeggpu_ext_set_truncated.argtypes = [dec, C.c_int]
+        L.jpeggpu_ext_get_truncated.argtypes = [dec, C.POINTER(TruncatedInfo)]
     L.jpeggpu_ext_get_orientation.argtypes = [dec, C.POINTER(C.c_int)]
     L.jpeggpu_ext_orient_size.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.jpeggpu_ext_orient_rect.argtypes = [C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4
@@ -576,6 +585,18 @@ class Decoder:
         _check(lib().jpeggpu_ext_get_progressive_info(self._h, C.byref(pi)), "jpeggpu_ext_get_progressive_info")
         return pi
 
+    def set_truncated(self, on: bool = True):
+        """Read files that end early from the next parse_header on, decoded as Pillow does with
+        ImageFile.LOAD_TRUNCATED_IMAGES; off by default, when they are INVALID_JPEG (jpeggpu_ext_set_truncated). Progressive
+        files are NOT_SUPPORTED while it is on."""
+        _check(lib().jpeggpu_ext_set_truncated(self._h, int(on)), "jpeggpu_ext_set_truncated")
+
+    def truncated(self) -> TruncatedInfo:
+        """jpeggpu_ext_get_truncated of the last parsed image."""
+        ti = TruncatedInfo()
+        _check(lib().jpeggpu_ext_get_truncated(self._h, C.byref(ti)), "jpeggpu_ext_get_truncated")
+        return ti
+
     def set_idct(self, method: str):
         """The full-size IDCT of the next parsed images: "reference" (the default) or "islow", libjpeg-turbo's
         jpeg_idct_islow, the transform of Pillow, torchvision and OpenCV (jpeggpu_ext_set_idct)."""
@@ -768,7 +789,7 @@ def _frame_size(info):
 
 def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp=False, device_scan=False, scale=1,
                      idct="reference", crop=None, scale_mode="uniform", return_color=False, progressive=False,
-                     displayed_crop=False, return_orientation=False, luma_only=False):
+                     displayed_crop=False, return_orientation=False, luma_only=False, truncated=False):
     """Convenience wrapper used by tests: full call sequence on torch's current stream, returns the
     planes as torch uint8 tensors on `device` (torch is only the allocator / stream provider). With
     `device_scan` the restart markers are found on the device and a status it reports there is raised.
@@ -780,11 +801,14 @@ def decode_to_planes(data: bytes, device="cuda:0", subseq_bytes=None, return_tmp
     (Decoder.set_progressive); with `return_tmp` the ProgressiveInfo follows the layout. `displayed_crop`: `crop` is in
     displayed coordinates of the file's EXIF orientation (the header is parsed once more to learn it; orient_rect).
     `return_orientation`: Decoder.orientation is appended last. `luma_only`: Decoder.set_luma_only -- of a YCbCr file only
-    plane 0 is allocated, decoded and returned (`planes` has one entry; `info` still describes all components)."""
+    plane 0 is allocated, decoded and returned (`planes` has one entry; `info` still describes all components).
+    `truncated`: Decoder.set_truncated -- a file that ends early is decoded as Pillow does with LOAD_TRUNCATED_IMAGES."""
     import torch
 
     dec = Decoder(subseq_bytes)
     try:
+        if truncated:
+            dec.set_truncated(True)
         if luma_only:
             dec.set_luma_only(True)
         if scale != 1:
@@ -894,7 +918,7 @@ def _needs_replication(info, scale):
     return scale == 8 and (len(set(info.subsampling.x[:n])) > 1 or len(set(info.subsampling.y[:n])) > 1)
 
 
-def decode_to_rgb(data: bytes, device="cuda:0", device_scan=False, crop=None, scale=1, exif_transpose=False):
+def decode_to_rgb(data: bytes, device="cuda:0", device_scan=False, crop=None, scale=1, exif_transpose=False, truncated=False):
     """Decode a JPEG to an (H, W, 3) uint8 tensor on `device` the way libjpeg-turbo does: the ISLOW IDCT at full size, then
     fancy upsampling and the conversion of the file's colour model (Decoder.color_space): grey, YCbCr (jdcolor.c's integer
     conversion), RGB-coded files as they are, CMYK and YCCK by Pillow's rule for Adobe's inverted samples. Meant to equal
@@ -905,10 +929,13 @@ def decode_to_rgb(data: bytes, device="cuda:0", device_scan=False, crop=None, sc
     Pillow; `crop` is then in pixels of that image. Progressive files are decoded too (Decoder.set_progressive).
     `exif_transpose`: the file's EXIF orientation (Decoder.orientation) is applied -- the result is the DISPLAYED image,
     (W, H, 3) for orientations 5..8, and `crop` is in displayed pixels at the scale: what ImageOps.exif_transpose(im) put
-    after draft() and before convert("RGB") and crop() gives. The XMP orientation Pillow falls back to is not read."""
+    after draft() and before convert("RGB") and crop() gives. The XMP orientation Pillow falls back to is not read.
+    `truncated`: a file that ends early gives what Pillow gives with ImageFile.LOAD_TRUNCATED_IMAGES set -- the rows that are
+    there, grey below (Decoder.set_truncated; INTEGRATION.md, "Truncated files"); progressive files are then NOT_SUPPORTED."""
     import torch
 
-    kw = dict(device=device, device_scan=device_scan, idct="islow", scale=scale, scale_mode="libjpeg", return_color=True, progressive=True)
+    kw = dict(device=device, device_scan=device_scan, idct="islow", scale=scale, scale_mode="libjpeg", return_color=True, progressive=True,
+              truncated=truncated)
     if exif_transpose:
         kw.update(displayed_crop=True, return_orientation=True)
     if crop is not None:
@@ -942,18 +969,18 @@ def planes_to_gray(planes, info, crop_info=None, device=None, replicate=False, c
     return out
 
 
-def decode_to_gray(data: bytes, device="cuda:0", crop=None, scale=1, exif_transpose=False):
+def decode_to_gray(data: bytes, device="cuda:0", crop=None, scale=1, exif_transpose=False, truncated=False):
     """Decode a JPEG to an (H, W) uint8 grey tensor on `device` the way libjpeg-turbo does for out_color_space =
     JCS_GRAYSCALE: of a YCbCr file only the luma component goes through the IDCT (Decoder.set_luma_only: ISLOW at full size,
     the reduced IDCTs at `scale` = d in 2, 4, 8 in the libjpeg scale mode), a grey file is its one component, an RGB-coded
     file is decoded whole and converted by jdcolor.c's rgb_gray_convert. Meant to equal np.asarray(im) after
     im.draft("L", (W // d, H // d)) in Pillow; CMYK and YCCK files, which Pillow's draft("L") leaves as they are, raise
     JpegGpuError (NOT_SUPPORTED). `crop` = (x, y, w, h) in pixels of the image at the scale and `exif_transpose` as in
-    decode_to_rgb: ImageOps.exif_transpose(im) and im.crop applied after the draft."""
+    decode_to_rgb: ImageOps.exif_transpose(im) and im.crop applied after the draft. `truncated` as in decode_to_rgb."""
     import torch
 
     kw = dict(device=device, idct="islow", scale=scale, scale_mode="libjpeg", return_color=True, progressive=True, luma_only=True,
-              return_orientation=True, displayed_crop=bool(exif_transpose))
+              return_orientation=True, displayed_crop=bool(exif_transpose), truncated=truncated)
     if crop is not None:
         planes, info, crop_info, color, o = decode_to_planes(data, crop=crop, **kw)
     else:
@@ -1222,25 +1249,31 @@ class BatchDecode:
     (Batch.set_coefficients_only): the front half of transcode_jpeg. `luma_only`: a truth value for all files or one per
     file -- Decoder.set_luma_only; of a YCbCr file only plane 0 is allocated and decoded (`planes[i]` has one entry).
     `device_scan`: a truth value for all files or one per file -- Decoder.set_device_scan(True): the device finds the
-    file's restart markers."""
+    file's restart markers. `truncated`: Decoder.set_truncated for every file -- files that end early are decoded as Pillow
+    does with ImageFile.LOAD_TRUNCATED_IMAGES, whole ones as ever, and `truncated` (the attribute) is then the list of
+    per-file flags: True where the file ended without its EOI (Decoder.truncated), so a loader can count or log them;
+    progressive files are NOT_SUPPORTED under the flag. `subseq_bytes`: None (chosen per file), or 32, 64, 128 or 256 for
+    all files or one per file (Decoder's `subseq_bytes`: what tests fix)."""
 
     def __init__(self, datas, device="cuda:0", hint=None, idct="islow", progressive=True, scales=None, scale_mode="libjpeg", crops=None,
-                 crop_hooks=None, coefficients_only=False, luma_only=False, device_scan=False):
+                 crop_hooks=None, coefficients_only=False, luma_only=False, device_scan=False, truncated=False, subseq_bytes=None):
         import torch
 
         dev = torch.device(device)
         self._stream = torch.cuda.current_stream(dev).cuda_stream
         self.decoders, self.planes, self.infos, self.crop_infos, self.tmps, self._entries = [], [], [], [], [], []
-        self.colors, self.orientations, self.replicates = [], [], []
+        self.colors, self.orientations, self.replicates, self.truncated = [], [], [], []
         self.transferred_bytes, self.batch = 0, None
         try:
             scans = 0
             for i, data in enumerate(datas):
-                dec = Decoder()
+                dec = Decoder(subseq_bytes[i] if isinstance(subseq_bytes, (list, tuple)) else subseq_bytes)
                 self.decoders.append(dec)
                 dec.set_batch_hint(len(datas) if hint is None else hint)
                 dec.set_idct(idct)
                 dec.set_progressive(progressive)
+                if truncated:
+                    dec.set_truncated(True)
                 luma = bool(luma_only[i] if isinstance(luma_only, (list, tuple)) else luma_only)
                 if luma:
                     dec.set_luma_only(True)
@@ -1274,6 +1307,7 @@ class BatchDecode:
                 self.colors.append(dec.color_space())
                 self.orientations.append(dec.orientation())
                 self.replicates.append(_needs_replication(info, scale))
+                self.truncated.append(bool(truncated and dec.truncated().truncated))
             self.batch = Batch(scans)
             if coefficients_only:
                 self.batch.set_coefficients_only(True)
@@ -1326,7 +1360,7 @@ def _per_image_args(n, crops, scales):
 
 
 def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", device="cuda:0", scales=None, exif_transpose=False,
-                   dtype=None, mean=None, std=None, flips=None, mode="RGB"):
+                   dtype=None, mean=None, std=None, flips=None, mode="RGB", truncated=False):
     """A training pipeline's decode: every JPEG of `datas` (of any colour model: decode_to_rgb) decoded with libjpeg-turbo's
     arithmetic (ISLOW IDCT, fancy upsampling), only the rectangle crops[i] = (x, y, w, h) of it (None: the whole image), in ONE jpeggpu_ext_decode_batch
     call, then resized to `size` (int: square; (h, w)) with Pillow's BILINEAR or BICUBIC arithmetic by one
@@ -1348,14 +1382,15 @@ def decode_resized(datas, size, crops=None, filt="bilinear", layout="NHWC", devi
     `datas` is refused where the batch is created: a JpegGpuError from jpeggpu_ext_batch_create (INVALID_ARGUMENT).
     `mode`: "RGB", or "L" -- one channel, n x h x w x 1 or n x 1 x h x w: the files are decoded luma-only (decode_to_gray)
     and resized by one jpeggpu_ext_resize_view_to_gray_tensor call, equal to im.draft("L", ...) in place of draft("RGB") and
-    convert("RGB") above; `mean` and `std` are then one number each (or 1-tuples)."""
+    convert("RGB") above; `mean` and `std` are then one number each (or 1-tuples). `truncated`: files that end early are
+    decoded as Pillow does with ImageFile.LOAD_TRUNCATED_IMAGES (BatchDecode)."""
     import torch
 
     if mode not in ("RGB", "L"):
         raise ValueError("mode %r is not one of RGB, L" % (mode,))
     crops, scales = _per_image_args(len(datas), crops, scales)
     crop_args = dict(crop_hooks=_displayed_crops(crops)) if exif_transpose else dict(crops=crops)
-    with BatchDecode(datas, device, scales=scales, luma_only=mode == "L", **crop_args) as bd:
+    with BatchDecode(datas, device, scales=scales, luma_only=mode == "L", truncated=truncated, **crop_args) as bd:
         replicates = bd.replicates
         if mode == "L":  # only component 0 is upsampled, and nearly always it has the largest factors: nothing to replicate
             replicates = [r and (i.subsampling.x[0], i.subsampling.y[0]) != _max_factors(i) for r, i in zip(replicates, bd.infos)]
@@ -1461,7 +1496,7 @@ def resize_views_to_tensor(planes_list, infos, views, size, crop_infos=None, fil
 
 
 def decode_center_cropped(datas, resize=256, crop=224, filt="bilinear", layout="NHWC", device="cuda:0", scales=None, exif_transpose=False,
-                          dtype=None, mean=None, std=None, mode="RGB"):
+                          dtype=None, mean=None, std=None, mode="RGB", truncated=False):
     """An evaluation pipeline's decode: torchvision's Resize(resize) + CenterCrop(crop) (+ ToTensor + Normalize with `dtype`,
     `mean`, `std` as in decode_resized) of every JPEG of `datas`, equal to Pillow's
     Image.open(f).convert("RGB").resize((rw, rh), filter) cropped (or zero-padded, where the resized image is smaller than
@@ -1491,7 +1526,7 @@ def decode_center_cropped(datas, resize=256, crop=224, filt="bilinear", layout="
         views.append((rw, rh) + center_crop_window(rw, rh, (ch, cw)))  # (the hooks run in the files' order)
         return resize_view_rect(w0, h0, views[-1], (ch, cw), filt, o)
 
-    with BatchDecode(datas, device, scales=scales, crop_hooks=[window] * n, luma_only=mode == "L") as bd:
+    with BatchDecode(datas, device, scales=scales, crop_hooks=[window] * n, luma_only=mode == "L", truncated=truncated) as bd:
         bd.decode()
         kw = dict(colors=bd.colors, orientations=bd.orientations if exif_transpose else [1] * n, replicates=bd.replicates, dtype=dtype,
                   mean=mean, std=std)
@@ -1619,7 +1654,7 @@ def _header_frame_size(data):
         probe.cleanup()
 
 
-def decode_thumbnails(datas, size, resample="bicubic", reducing_gap=2.0, exif_transpose=False, device="cuda:0"):
+def decode_thumbnails(datas, size, resample="bicubic", reducing_gap=2.0, exif_transpose=False, device="cuda:0", truncated=False):
     """Pillow's im.thumbnail(size, resample, reducing_gap) of every JPEG of `datas`, on the GPU: one BatchDecode at the
     scales draft() would pick (thumbnail_plan), then ONE jpeggpu_ext_thumbnail_to_rgb call -- Image.reduce's box averages and
     the resize from Pillow's fractional box -- with nothing on the host in between. `size`: Pillow's (width, height) request;
@@ -1637,7 +1672,7 @@ def decode_thumbnails(datas, size, resample="bicubic", reducing_gap=2.0, exif_tr
     if n == 0:
         raise ValueError("datas is empty")
     plans = [thumbnail_plan(*_header_frame_size(data), size, resample, reducing_gap) for data in datas]
-    with BatchDecode(datas, device, scales=[p.scale for p in plans]) as bd:
+    with BatchDecode(datas, device, scales=[p.scale for p in plans], truncated=truncated) as bd:
         for p, rep in zip(plans, bd.replicates):
             p.replicate = int(bool(rep))
         bd.decode()
@@ -1651,7 +1686,7 @@ def decode_thumbnails(datas, size, resample="bicubic", reducing_gap=2.0, exif_tr
 
 
 def thumbnail_jpeg(datas, size, resample="bicubic", reducing_gap=2.0, exif_transpose=False, device="cuda:0", quality=75, subsampling=None,
-                   optimize=False, progressive=False, restart_interval=0, max_bytes=None, min_quality=1):
+                   optimize=False, progressive=False, restart_interval=0, max_bytes=None, min_quality=1, truncated=False):
     """JPEG in, smaller JPEG out: decode_thumbnails' views encoded by encode_jpeg (one decode batch, one thumbnail call, one
     encode call; the pixels never visit the host). Returns a list of bytes: encode_jpeg's file of each thumbnail, which for a
     source without a COM segment is byte for byte what im.save(f, "JPEG", quality=..., ...) writes after
@@ -1660,7 +1695,7 @@ def thumbnail_jpeg(datas, size, resample="bicubic", reducing_gap=2.0, exif_trans
     would change, in Pillow as here). `max_bytes` (one value or one per file): a size limit -- the encode step is then
     encode_jpeg_fit's search over min_quality..quality, and the function returns (files, qualities); progressive=True is
     not offered with it."""
-    views = decode_thumbnails(datas, size, resample, reducing_gap, exif_transpose, device)
+    views = decode_thumbnails(datas, size, resample, reducing_gap, exif_transpose, device, truncated=truncated)
     if subsampling is None:
         subsampling = ["4:4:4" if v.dim() == 2 else "4:2:0" for v in views]
     if max_bytes is not None:
@@ -1729,7 +1764,8 @@ def batch_to_rgb(planes_list, infos, crop_infos=None, colors=None, orientations=
     return views
 
 
-def decode_batch_to_rgb(datas, device="cuda:0", crops=None, scales=None, exif_transpose=False, layout="HWC"):
+def decode_batch_to_rgb(datas, device="cuda:0", crops=None, scales=None, exif_transpose=False, layout="HWC", truncated=False, subseq_bytes=None,
+                        hint=None):
     """A list of JPEGs in, a list of RGB tensors out, each at its own size (torchvision.io.decode_jpeg on a list; a validation
     loader): every file of `datas` (of any colour model, baseline or progressive) decoded with libjpeg-turbo's arithmetic
     in ONE jpeggpu_ext_decode_batch call and converted by ONE jpeggpu_ext_batch_to_rgb call, with one synchronise at the
@@ -1748,7 +1784,7 @@ def decode_batch_to_rgb(datas, device="cuda:0", crops=None, scales=None, exif_tr
     if n == 0:
         return []
     crop_args = dict(crop_hooks=_displayed_crops(crops)) if exif_transpose else dict(crops=crops)
-    with BatchDecode(datas, device, scales=scales, **crop_args) as bd:
+    with BatchDecode(datas, device, scales=scales, truncated=truncated, subseq_bytes=subseq_bytes, hint=hint, **crop_args) as bd:
         bd.decode()
         out = batch_to_rgb(bd.planes, bd.infos, bd.crop_infos, bd.colors, bd.orientations if exif_transpose else [1] * n, bd.replicates, layout)
         torch.cuda.synchronize(torch.device(device))
@@ -1797,7 +1833,7 @@ def batch_to_gray(planes_list, infos, crop_infos=None, colors=None, orientations
     return [out[start + off:start + off + ow * oh].view(oh, ow) for (ow, oh), off in zip(sizes, offsets)]
 
 
-def decode_batch_to_gray(datas, device="cuda:0", crops=None, scales=None, exif_transpose=False):
+def decode_batch_to_gray(datas, device="cuda:0", crops=None, scales=None, exif_transpose=False, truncated=False):
     """A list of JPEGs in, a list of (h, w) uint8 grey tensors out, each at its own size: every file decoded luma-only in ONE
     jpeggpu_ext_decode_batch call and written by ONE jpeggpu_ext_batch_to_gray call, with one synchronise at the end. Element
     i equals decode_to_gray(datas[i], crop=crops[i], scale=scales[i], exif_transpose=exif_transpose); the arguments are
@@ -1809,7 +1845,7 @@ def decode_batch_to_gray(datas, device="cuda:0", crops=None, scales=None, exif_t
     if n == 0:
         return []
     crop_args = dict(crop_hooks=_displayed_crops(crops)) if exif_transpose else dict(crops=crops)
-    with BatchDecode(datas, device, scales=scales, luma_only=True, **crop_args) as bd:
+    with BatchDecode(datas, device, scales=scales, luma_only=True, truncated=truncated, **crop_args) as bd:
         bd.decode()
         out = batch_to_gray(bd.planes, bd.infos, bd.crop_infos, bd.colors, bd.orientations if exif_transpose else [1] * n, bd.replicates)
         torch.cuda.synchronize(torch.device(device))
@@ -2353,7 +2389,7 @@ def _transcode_windows(n, orientation, exif_transpose, trim, crops, expand, fram
 
 
 def transcode_jpeg_to_device(datas, optimize=False, progressive=False, restart_interval=None, device="cuda:0", capacities=None, orientation=None,
-                             exif_transpose=False, trim=False, crops=None, expand=False, frame="encoder"):
+                             exif_transpose=False, trim=False, crops=None, expand=False, frame="encoder", truncated=False):
     """transcode_jpeg's files left on the device: (buffer, offsets, sizes) as encode_jpeg_to_device returns them.
     `capacities`: the slot sizes to start with (default: twice the source's length, a header and three bytes per block of the
     TARGET's MCUs for restart markers and their padding); if a file is larger, the call is repeated once with the sizes it
@@ -2365,7 +2401,7 @@ def transcode_jpeg_to_device(datas, optimize=False, progressive=False, restart_i
         return None, [], []
     _newer_symbol("jpeggpu_ext_transcode_batch")
     n = len(datas)
-    with BatchDecode(datas, device, coefficients_only=True,
+    with BatchDecode(datas, device, coefficients_only=True, truncated=truncated,
                      crop_hooks=_transcode_windows(n, orientation, exif_transpose, trim, crops, expand, frame)) as bd:
         # (host only: refuses before anything is enqueued or allocated)
         items = _transcode_items(bd, optimize, progressive, restart_interval, orientation, exif_transpose, trim, crops, expand, frame)
@@ -2417,7 +2453,7 @@ def _transcode_blocks(item):
 
 
 def transcode_jpeg(datas, optimize=False, progressive=False, restart_interval=None, device="cuda:0", orientation=None, exif_transpose=False, trim=False,
-                   crops=None, expand=False, frame="encoder"):
+                   crops=None, expand=False, frame="encoder", truncated=False):
     """JPEG files from JPEG files without a pixel in between, as a list of bytes: what jpegtran -optimize, -progressive and
     -restart N do. Each file holds the source's quantised coefficients exactly, in the layout encode_jpeg writes (the
     source's quantisation tables; EXIF, ICC and comments are dropped). `optimize`, `progressive` as in encode_jpeg;
@@ -2445,11 +2481,12 @@ def transcode_jpeg(datas, optimize=False, progressive=False, restart_interval=No
     the one Pillow writes for the cropped pixels. Each cropped file is decoded only as far as its rectangle needs
     (transcode_crop_rects, Decoder.set_crop: the restart segments that hold it, where the file has restart markers).
     One batched decode that stops in front of the IDCT, one jpeggpu_ext_transcode_batch call, one synchronisation and one
-    copy of the files' bytes to the host."""
+    copy of the files' bytes to the host. `truncated`: a source that ends early is taken as libjpeg finishes it (BatchDecode):
+    the new file is whole, its blocks behind the cut all zero."""
     import torch
 
     buf, offsets, sizes = transcode_jpeg_to_device(datas, optimize, progressive, restart_interval, device, None, orientation, exif_transpose, trim, crops,
-                                                   expand, frame)
+                                                   expand, frame, truncated=truncated)
     if not sizes:
         return []
     host = torch.cat([buf[o:o + s] for o, s in zip(offsets, sizes)]).cpu().numpy().tobytes()
@@ -2526,13 +2563,14 @@ def read_coefficients_into(bd, dtype=None, dequantize=False):
     return out
 
 
-def read_coefficients(datas, device="cuda:0", dtype=None, dequantize=False):
+def read_coefficients(datas, device="cuda:0", dtype=None, dequantize=False, truncated=False):
     """The quantised DCT coefficients of JPEG files, on the device: what jpeg_read_coefficients (jpegio.read,
     torchjpeg.codec.read_coefficients) gives on the CPU. Returns one Coefficients per file; `dtype` torch.int16 (default:
     the values exactly), or torch.float32 / torch.float16, which with `dequantize` hold value * table entry (one float32
     multiply; for float16 that product converted once). Dequantised int16 is refused. Every file the decoder reads:
     baseline and progressive, 1..4 components, any sampling, 16-bit tables. One batched decode that stops in front of the
-    IDCT, ONE allocation for all tensors, one read call; nothing synchronises."""
+    IDCT, ONE allocation for all tensors, one read call; nothing synchronises. `truncated`: files that end early are read as
+    libjpeg finishes them (BatchDecode): the blocks behind the cut are all zero, DC included."""
     import torch
 
     datas = list(datas)
@@ -2541,7 +2579,7 @@ def read_coefficients(datas, device="cuda:0", dtype=None, dequantize=False):
     _newer_symbol("jpeggpu_ext_read_coefficients_batch")
     if dequantize and (dtype is None or dtype == torch.int16):
         raise JpegGpuError(Status.INVALID_ARGUMENT, "read_coefficients: dequantised int16 (a 16-bit table overflows it)")
-    with BatchDecode(datas, device, coefficients_only=True) as bd:
+    with BatchDecode(datas, device, coefficients_only=True, truncated=truncated) as bd:
         bd.decode()
         return read_coefficients_into(bd, dtype, dequantize)
 

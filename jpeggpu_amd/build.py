@@ -7,7 +7,7 @@ ROOT = os.path.dirname(_HERE)
 CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libjpeggpu.so")
-SOURCES = ["jg_kernels.hip", "jg_idct.hip", "jg_output.hip", "jg_output_gray.hip", "jg_front.hip", "jg_prog.hip", "jg_encode.hip", "jg_encode_prog.hip", "jg_encode_fit.hip", "jg_roundtrip.hip", "jg_decoder.cpp", "jg_plan.cpp", "jg_output_plan.cpp", "jg_roundtrip_plan.cpp", "jg_batch.cpp", "jg_output.cpp", "jg_reader.cpp", "jg_encode.cpp", "jg_encode_plan.cpp", "jg_encode_fit.cpp", "jg_transcode.cpp", "jg_coefficients.cpp"]
+SOURCES = ["jg_kernels.hip", "jg_idct.hip", "jg_output.hip", "jg_output_gray.hip", "jg_front.hip", "jg_prog.hip", "jg_encode.hip", "jg_encode_prog.hip", "jg_encode_fit.hip", "jg_roundtrip.hip", "jg_trunc.hip", "jg_decoder.cpp", "jg_plan.cpp", "jg_output_plan.cpp", "jg_roundtrip_plan.cpp", "jg_batch.cpp", "jg_output.cpp", "jg_reader.cpp", "jg_encode.cpp", "jg_encode_plan.cpp", "jg_encode_fit.cpp", "jg_transcode.cpp", "jg_coefficients.cpp"]
 
 
 def _mode_path(lib_path):

@@ -6,6 +6,7 @@
 #include "jg_kernels.hpp"
 #include "jg_prog.hpp"
 #include "jg_stage_timer.hpp"
+#include "jg_trunc.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -54,6 +55,8 @@ struct jpeggpu_batch {
     std::vector<jg::FrontParams> fronts;
     std::vector<jg::ProgImage> progs;    // the progressive items of the call (jg_prog.hpp), and their launch extents
     jg::ProgExtent prog_extent;
+    std::vector<jg::TruncRef> truncs;    // the scans of the call whose file ended early (jg_trunc.hpp), in job order,
+    std::vector<int> trunc_job;          // ... and the index of each one's job
     hipEvent_t prog_done        = nullptr; // overlap > 1: the other streams' IDCT waits for the progressive launches
     std::vector<int> order, group_begin; // scratch of decode_batch: items by subsequence size, job ranges of the sizes
     struct Part {                        // ... and the parts of the job array, one launch per stage each
@@ -70,11 +73,11 @@ namespace {
 struct Call {
     const jpeggpu_ext_batch_item* items;
     int num_items;
-    uint8_t* d_scratch; // ScanJob[n], FrontParams[nf], ProgImage[np]
+    uint8_t* d_scratch; // ScanJob[n], FrontParams[nf], ProgImage[np], TruncRef[nt]
     hipStream_t stream;
     bool keep_flows        = false;
     uint32_t front_windows = 0; // most windows of a device-scanned item
-    size_t jbytes = 0, fbytes = 0, pbytes = 0;
+    size_t jbytes = 0, fbytes = 0, pbytes = 0, tbytes = 0;
     int ring = 0; // the staging buffer and the `copied` event of the call
     hipStream_t part_stream[jpeggpu_batch::kMaxOverlap];
 };
@@ -106,6 +109,10 @@ jpeggpu_status gather_jobs(jpeggpu_batch& b, Call& c)
             b.fronts.push_back(jg::front_params(it.decoder->d, it.d_tmp, d_jobs_rw + first_job + static_cast<size_t>(dk), dk));
             c.front_windows = std::max(c.front_windows, b.fronts.back().num_windows);
         }
+        if (const int tk = jg::truncated_scan_index(it.decoder->d); tk >= 0) {
+            b.truncs.push_back(jg::TruncRef{d_jobs_rw + first_job + static_cast<size_t>(tk), jg::trunc_params(it.decoder->d, it.d_tmp)});
+            b.trunc_job.push_back(static_cast<int>(first_job) + tk);
+        }
         if (const Decoder& pd = it.decoder->d; pd.plan.prog.on) {
             b.progs.push_back(jg::ProgImage{static_cast<uint8_t*>(it.d_tmp), pd.plan.off_blob + pd.plan.prog.blob.header});
             jg::extend(b.prog_extent, *reinterpret_cast<const jg::ProgHeader*>(pd.blob + pd.plan.prog.blob.header));
@@ -119,9 +126,9 @@ jpeggpu_status gather_jobs(jpeggpu_batch& b, Call& c)
 /// where the device-side front end of the device-scanned items then completes their jobs.
 jpeggpu_status stage_jobs(jpeggpu_batch& b, Call& c, size_t scratch_size)
 {
-    const size_t n = b.jobs.size(), nf = b.fronts.size(), np = b.progs.size();
-    c.jbytes = sizeof(jg::ScanJob) * n, c.fbytes = sizeof(jg::FrontParams) * nf, c.pbytes = sizeof(jg::ProgImage) * np;
-    if (static_cast<int>(n) > b.max_jobs || scratch_size < c.jbytes + c.fbytes + c.pbytes) return JPEGGPU_INVALID_ARGUMENT;
+    const size_t n = b.jobs.size(), nf = b.fronts.size(), np = b.progs.size(), nt = b.truncs.size();
+    c.jbytes = sizeof(jg::ScanJob) * n, c.fbytes = sizeof(jg::FrontParams) * nf, c.pbytes = sizeof(jg::ProgImage) * np, c.tbytes = sizeof(jg::TruncRef) * nt;
+    if (static_cast<int>(n) > b.max_jobs || scratch_size < c.jbytes + c.fbytes + c.pbytes + c.tbytes) return JPEGGPU_INVALID_ARGUMENT;
     const int r = c.ring = b.next;
     b.next      = (r + 1) % jpeggpu_batch::kRing;
     // the staging buffer may still be the source of a copy enqueued kRing batches ago
@@ -129,8 +136,9 @@ jpeggpu_status stage_jobs(jpeggpu_batch& b, Call& c, size_t scratch_size)
     std::memcpy(b.staging[r], b.jobs.data(), c.jbytes);
     if (nf) std::memcpy(b.staging[r] + c.jbytes, b.fronts.data(), c.fbytes);
     if (np) std::memcpy(b.staging[r] + c.jbytes + c.fbytes, b.progs.data(), c.pbytes);
+    if (nt) std::memcpy(b.staging[r] + c.jbytes + c.fbytes + c.pbytes, b.truncs.data(), c.tbytes);
     if (!b.timer.begin(c.stream, static_cast<size_t>(jg::kNumStages) + 1)) return JPEGGPU_INTERNAL_ERROR;
-    if (hipMemcpyAsync(c.d_scratch, b.staging[r], c.jbytes + c.fbytes + c.pbytes, hipMemcpyHostToDevice, c.stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
+    if (hipMemcpyAsync(c.d_scratch, b.staging[r], c.jbytes + c.fbytes + c.pbytes + c.tbytes, hipMemcpyHostToDevice, c.stream) != hipSuccess) return JPEGGPU_INTERNAL_ERROR;
     if (nf && jg::launch_front_batch(reinterpret_cast<const jg::FrontParams*>(c.d_scratch + c.jbytes), static_cast<int>(nf), c.front_windows, c.stream) != hipSuccess) {
         (void)hipGetLastError();
         return JPEGGPU_INTERNAL_ERROR;
@@ -213,6 +221,17 @@ jpeggpu_status run_stages(jpeggpu_batch& b, const Call& c)
                 (void)hipGetLastError();
                 return JPEGGPU_INTERNAL_ERROR;
             }
+            if ((stage == jg::kStageDestuff || stage == jg::kStageWrite) && !b.truncs.empty()) {
+                // the part's scans whose file ended early (jg_trunc.hpp): a run of the references, which are in job order
+                const auto lo = std::lower_bound(b.trunc_job.begin(), b.trunc_job.end(), p.begin) - b.trunc_job.begin();
+                const auto hi = std::lower_bound(b.trunc_job.begin(), b.trunc_job.end(), p.end) - b.trunc_job.begin();
+                const jg::TruncRef* d_refs = reinterpret_cast<const jg::TruncRef*>(c.d_scratch + c.jbytes + c.fbytes + c.pbytes) + lo;
+                if (hi > lo && (stage == jg::kStageDestuff ? jg::launch_trunc_prepare_batch(d_refs, static_cast<int>(hi - lo), c.part_stream[p.way])
+                                                           : jg::launch_trunc_finish_batch(d_refs, static_cast<int>(hi - lo), c.part_stream[p.way])) != hipSuccess) {
+                    (void)hipGetLastError();
+                    return JPEGGPU_INTERNAL_ERROR;
+                }
+            }
         }
         (void)b.timer.mark(stage, c.stream); // stage times are those of the caller's stream
     }
@@ -232,6 +251,8 @@ jpeggpu_status decode_batch_impl(
     batch->jobs.clear();
     batch->fronts.clear();
     batch->progs.clear();
+    batch->truncs.clear();
+    batch->trunc_job.clear();
     batch->prog_extent = jg::ProgExtent{};
     for (int i = 0; i < num_items; ++i)
         if (!items[i].decoder || !items[i].img) return JPEGGPU_INVALID_ARGUMENT;
@@ -279,6 +300,8 @@ size_t jpeggpu_ext_batch_scratch_size(int max_scans)
     // (a progressive item's descriptor lies behind the jobs and front-end parameters; such an item has a job per component
     // and no front-end parameters, so the same bound holds)
     static_assert(sizeof(jg::ProgImage) <= sizeof(jg::FrontParams), "a progressive item takes the place of front-end parameters");
+    // (so does the one scan a truncated item ends in: such a scan is walked on the host)
+    static_assert(sizeof(jg::TruncRef) <= sizeof(jg::FrontParams), "a truncated item's scan takes the place of front-end parameters");
     return static_cast<size_t>(max_scans > 0 ? max_scans : 0) * (sizeof(jg::ScanJob) + sizeof(jg::FrontParams));
 }
 

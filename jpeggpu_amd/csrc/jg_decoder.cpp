@@ -16,6 +16,7 @@
 #include "jg_selftest_data.h"
 #include "jg_stage_timer.hpp"
 #include "jg_staging.hpp"
+#include "jg_trunc.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -138,6 +139,9 @@ jpeggpu_status jg::do_decode(Decoder& d, jpeggpu_img* img, void* d_tmp, size_t t
             "scan %d: %d chunks, %d subsequences of %d bytes, %d sequences, %d segments\n",
             static_cast<int>(i), job.num_chunks, job.sp.num_subseq, d.subseq_bytes, job.num_seq, job.sp.num_segments);
     }
+    // a file that ended early (jpeggpu_ext_set_truncated): three launches more for the scan it ends in (jg_trunc.hip)
+    const int cut_scan = truncated_scan_index(d);
+    const TruncParams cut = cut_scan >= 0 ? trunc_params(d, d_tmp) : TruncParams{};
     // every stage once, for all scans of the image at a time (they are independent: grid.y = scan)
     for (int stage = 0; stage < kNumStages; ++stage) {
         if (stage == kStageSyncIntra) {
@@ -150,6 +154,8 @@ jpeggpu_status jg::do_decode(Decoder& d, jpeggpu_img* img, void* d_tmp, size_t t
             if (ps != JPEGGPU_SUCCESS) return ps;
         }
         JG_CHECK_HIP(launch_stage_scans(static_cast<Stage>(stage), d.jobs.data(), static_cast<int>(d.jobs.size()), stream));
+        if (cut_scan >= 0 && stage == kStageDestuff) JG_CHECK_HIP(launch_trunc_prepare(d.jobs[static_cast<size_t>(cut_scan)], cut, stream));
+        if (cut_scan >= 0 && stage == kStageWrite) JG_CHECK_HIP(launch_trunc_finish(d.jobs[static_cast<size_t>(cut_scan)], cut, stream));
         (void)d.timer->mark(stage, stream);
     }
     return JPEGGPU_SUCCESS;
@@ -492,6 +498,26 @@ enum jpeggpu_status jpeggpu_ext_set_progressive(jpeggpu_decoder_t decoder, int e
 {
     if (!decoder) return JPEGGPU_INVALID_ARGUMENT;
     decoder->d.progressive = enable != 0;
+    return JPEGGPU_SUCCESS;
+}
+
+enum jpeggpu_status jpeggpu_ext_set_truncated(jpeggpu_decoder_t decoder, int enable)
+{
+    if (!decoder) return JPEGGPU_INVALID_ARGUMENT;
+    decoder->d.truncated = enable != 0;
+    return JPEGGPU_SUCCESS;
+}
+
+enum jpeggpu_status jpeggpu_ext_get_truncated(jpeggpu_decoder_t decoder, struct jpeggpu_ext_truncated_info* info)
+{
+    if (!decoder || !info) return JPEGGPU_INVALID_ARGUMENT;
+    if (!decoder->d.parsed) return JPEGGPU_INVALID_ARGUMENT;
+    const jg::Stream::Truncation& t = decoder->d.reader.s.trunc;
+    std::memset(info, 0, sizeof(*info));
+    info->truncated              = t.no_eoi ? 1 : 0;
+    info->scan                   = t.scan;
+    info->scan_bytes             = t.scan >= 0 ? t.scan_bytes : 0;
+    info->first_missing_interval = t.first_missing_interval;
     return JPEGGPU_SUCCESS;
 }
 

@@ -40,6 +40,7 @@ struct ScanPlan {
     size_t d_win_data = 0, d_win_nmark = 0, d_win_bad = 0, d_win_prefix = 0, d_mark_off = 0;
     size_t d_mk_pos = 0, d_mk_g = 0, d_seg_cnt = 0, d_seg_nch = 0, d_job = 0, d_status = 0;
     uint32_t num_windows = 0;
+    size_t trunc_state = 0; // the scan a truncated file ends in: two words of jg_trunc.hip (TruncParams::state); else not carved
 };
 
 /// A progressive image's part of the plan (jg_prog_core.h): its descriptors in the blob, its coefficient buffers in d_tmp.
@@ -95,6 +96,7 @@ struct Decoder {
     bool parsed         = false;
     int shard_rank = 0, shard_world = 1; // jpeggpu_ext_set_segment_shard
     bool progressive    = false; // jpeggpu_ext_set_progressive: SOF2 frames are read, from the next parse_header on
+    bool truncated      = false; // jpeggpu_ext_set_truncated: files that end early are read, from the next parse_header on
     int device_scan     = 0;     // jpeggpu_ext_set_device_scan: 0 off, 1 on (status via jpeggpu_ext_get_device_status), 2 on and checked by decode
     // jpeggpu_ext_set_scale: planes at 1 / 2^scale_log2. The request takes effect at the next parse_header (`scale_log2`:
     // that of the parsed image); it changes the plane sizes and the IDCT stage only, never the plan or the Huffman path.
@@ -181,6 +183,10 @@ struct Decoder {
 jpeggpu_status build_jobs(
     Decoder& d, const jpeggpu_img* img, void* d_tmp, size_t tmp_size, int max_intra_iters, bool lone, bool keep_flows, std::vector<ScanJob>& jobs,
     bool planes = true);
+/// Index of the scan a parsed truncated file ends in, whose job needs the kernels of jg_trunc.hip, or -1 (a whole file, a
+/// file that lacks only what lies behind its last scan); `tp`: their parameters for that scan's job in `d_tmp`.
+int truncated_scan_index(const Decoder& d);
+TruncParams trunc_params(const Decoder& d, void* d_tmp);
 /// Index of the scan of a parsed image that the device walks (its last one), or -1.
 int device_scan_index(const Decoder& d);
 /// Parameters of the device-side front end for the device-walked scan `k` of a parsed image; `d_job` is the device copy

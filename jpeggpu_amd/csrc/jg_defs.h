@@ -487,6 +487,23 @@ struct ScanJob {
     IdctDraft draft;             // jpeggpu_ext_set_scale_mode: the unit classes of a JPEGGPU_EXT_SCALE_LIBJPEG job (draft.on == 0: none)
 };
 
+/// A scan whose file ended early (jpeggpu_ext_set_truncated), for the kernels of jg_trunc.hip. The host walk gives the segment
+/// the data ends in subsequences of zeros behind its data, and the next restart interval, if there is one, a segment of zeros
+/// alone (jg_reader.cpp, walk_scan); the Huffman stages run over them as over any other data.
+struct TruncParams {
+    int cut_segment;   // entry of the job's segment table the data ends in
+    uint32_t end_bit;  // bits of data that segment has
+    int zero_segment;  // entry of the all-zero segment behind it, or -1
+    int reserved;
+    uint32_t* state;   // [2] in d_tmp: first data unit of the scan that is emptied | the MCU finished from zero bits, or -1
+};
+/// A truncated scan of a batch: its job in device memory.
+struct TruncRef {
+    const ScanJob* job;
+    TruncParams tp;
+};
+static_assert(sizeof(TruncRef) <= 64, "a truncated item's entry takes the place of front-end parameters in a batch's scratch");
+
 /// Everything the kernels of the device-side front end (jg_front.hip) need; all pointers are device memory inside d_tmp.
 struct FrontParams {
     const uint8_t* bytes;      // transferred bytes; offset 0 is the origin of the 4 KiB window grid

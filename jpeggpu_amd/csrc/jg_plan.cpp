@@ -255,6 +255,7 @@ void Decoder::make_plan(PlanTrace* trace)
             sp.d_job        = tmp(sizeof(ScanJob));
             sp.d_status     = tmp(32);
         }
+        if (s.trunc.scan == i) sp.trunc_state = tmp(2 * sizeof(uint32_t));
     }
     for (int i = 0; i < s.num_scans; ++i) {
         p.scan[i].sym    = tmp(sym_buffer_entries(sym_regions(i), sym_region()) * 2 + 256); // symbol stream: a fixed region per subsequence
@@ -288,7 +289,7 @@ jpeggpu_status Decoder::plan_image(jpeggpu_img_info* img_info, const uint8_t* da
     jpeggpu_status st;
     try {
         const int ask = subseq_request > 0 ? subseq_request : -batch_hint; // 0 / -N: chosen per image for N images per call
-        st = reader.parse(data, size, ask, logger, device_scan != 0, shard_rank, shard_world, progressive);
+        st = reader.parse(data, size, ask, logger, device_scan != 0, shard_rank, shard_world, progressive, truncated);
         subseq_bytes = reader.subseq_bytes();
     } catch (const std::bad_alloc&) {
         return JPEGGPU_OUT_OF_HOST_MEMORY;
@@ -311,7 +312,8 @@ jpeggpu_status Decoder::plan_image(jpeggpu_img_info* img_info, const uint8_t* da
         }
         // one host-walked scan with restart markers: keep only the segments that hold the window's MCUs
         const Scan& sc = s.scans[0];
-        if (s.num_scans == 1 && s.restart_interval > 0 && !sc.device_walk && !sc.segments.empty()) {
+        // (not the scan a truncated file ends in: its segment table ends with the data, and jg_trunc.hip counts from MCU 0)
+        if (s.num_scans == 1 && s.restart_interval > 0 && !sc.device_walk && !sc.segments.empty() && s.trunc.scan < 0) {
             const IdctWindow w = scan_window(sc);
             const int m0 = w.my0 * sc.mcus_x + w.mx0, m1 = (w.my0 + w.mcus_y - 1) * sc.mcus_x + w.mx0 + w.mcus_x - 1;
             reader.cut_segments(m0 / sc.mcus_per_segment, m1 / sc.mcus_per_segment + 1);
@@ -527,6 +529,19 @@ jpeggpu_status build_jobs(
         jobs.push_back(job);
     }
     return JPEGGPU_SUCCESS;
+}
+
+int truncated_scan_index(const Decoder& d) { return d.reader.s.trunc.scan; }
+
+TruncParams trunc_params(const Decoder& d, void* d_tmp)
+{
+    const Stream::Truncation& t = d.reader.s.trunc;
+    TruncParams tp{};
+    tp.cut_segment  = t.cut_segment;
+    tp.end_bit      = t.end_bit;
+    tp.zero_segment = t.zero_segment;
+    tp.state        = at<uint32_t>(static_cast<uint8_t*>(d_tmp), d.plan.scan[t.scan].trunc_state);
+    return tp;
 }
 
 int device_scan_index(const Decoder& d)

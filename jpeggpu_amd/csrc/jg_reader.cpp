@@ -608,6 +608,22 @@ jpeggpu_status Reader::read_sos(const Logger& log)
     if (!build_pack(dc_tab_, ac_tab_, scan.table_pack, scan.cursor_off, kMaxTablePack, true) ||
         !build_pack(dc_tab_sync_, ac_tab_sync_, scan.table_pack_sync, scan.cursor_off_sync, kMaxTablePackSync, false))
         return JPEGGPU_INTERNAL_ERROR;
+    if (truncated_) {
+        // What the MCU in flight at a cut needs behind the last real bit: the symbol that straddles it (at most 31 bits), then
+        // every data unit of one MCU decoded from zero bits -- which these tables turn into a known number of bits. Few
+        // zeros matter: data that repeats never lets two decoders of it fall into step, so the flows of the synchronisation
+        // run through such a tail one subsequence after the other.
+        int bits = 64;
+        for (int a = 0; a < ns && bits > 0; ++a) {
+            const ScanComponent& sc = scan.comp[a];
+            const uint16_t* dc = reinterpret_cast<const uint16_t*>(dc_tab_[sc.dc_id].data());
+            const uint16_t* ac = reinterpret_cast<const uint16_t*>(ac_tab_[sc.ac_id].data());
+            const int unit     = zero_unit_bits(dc[0], ac[0]);
+            bits               = unit > 0 ? bits + unit * sc.h * sc.v : 0;
+        }
+        const int worst       = truncation_tail_bytes(scan.du_per_mcu);
+        scan.trunc_tail_bytes = bits > 0 ? std::min((bits + 7) / 8 + 8, worst) : worst;
+    }
     const int total_mcus  = scan.mcus_x * scan.mcus_y;
     scan.mcus_per_segment = s.restart_interval ? s.restart_interval : total_mcus;
     if (s.num_scans == 0) s.first_restart_interval = s.restart_interval;
@@ -896,11 +912,67 @@ jpeggpu_status Reader::walk_scan(Scan& scan, const Logger& log)
 #endif
     };
 
+    const int expect_segments = ceil_div(scan.mcus_x * scan.mcus_y, scan.mcus_per_segment);
+    // The file ends in this scan (jpeggpu_ext_set_truncated): the data of the segment at hand runs up to `dend` -- the end of
+    // the file, or a trailing FF that is half of a stuffed pair or of a marker (libjpeg drops it: INTEGRATION.md, "Truncated
+    // files"). The segment keeps Scan::trunc_tail_bytes of zeros behind its data, from which the MCU in flight at the cut is
+    // finished; if it holds data and is not the scan's last, the next restart interval follows as a segment of zeros alone:
+    // its first MCU is the one decoded from zero bits where this one turns out complete. jg_trunc.hip zeroes those
+    // subsequences, finds the MCU and empties every data unit behind it.
+    const auto cut_here = [&](const uint8_t* dend) -> jpeggpu_status {
+        const int k = static_cast<int>(scan.segments.size());
+        if (k >= expect_segments) return JPEGGPU_INVALID_JPEG; // more restart markers than the geometry has intervals
+        const size_t qo = boff(dend);
+        while (next_win <= qo) {
+            emit(chunk_begin, next_win);
+            chunk_begin = next_win;
+            next_win += kDestuffWin;
+        }
+        if (qo > chunk_begin) emit(chunk_begin, qo);
+        const size_t seg_bytes = chunk_dst - static_cast<size_t>(seg_dst_base);
+        if (seg_bytes > (1u << 27)) return JPEGGPU_NOT_SUPPORTED;
+        const size_t B    = static_cast<size_t>(subseq_bytes_);
+        const size_t tail = static_cast<size_t>(scan.trunc_tail_bytes);
+        Segment seg;
+        seg.subseq_offset = scan.num_subseq;
+        seg.subseq_count  = static_cast<int>((seg_bytes + tail + B - 1) / B);
+        if (seg_bytes > 0) scan.chunks.back().pad_end = static_cast<uint32_t>((static_cast<size_t>(scan.num_subseq) + (seg_bytes + B - 1) / B) * B);
+        scan.num_subseq += seg.subseq_count;
+        scan.segments.push_back(seg);
+        Stream::Truncation& t = s.trunc;
+        t.no_eoi       = true;
+        t.scan         = s.num_scans - 1;
+        t.cut_segment  = k;
+        t.end_bit      = static_cast<uint32_t>(8 * seg_bytes);
+        t.zero_segment = -1;
+        if (seg_bytes > 0 && k + 1 < expect_segments) {
+            Segment z;
+            z.subseq_offset = scan.num_subseq;
+            z.subseq_count  = static_cast<int>((tail + B - 1) / B);
+            scan.num_subseq += z.subseq_count;
+            scan.segments.push_back(z);
+            t.zero_segment = k + 1;
+        }
+        if (static_cast<size_t>(scan.num_subseq) * B > (1u << 31)) return JPEGGPU_NOT_SUPPORTED;
+        t.scan_bytes = static_cast<size_t>(end_ - base_) - scan.begin;
+        t.first_missing_interval = s.restart_interval == 0 ? -1 : (seg_bytes > 0 ? k + 1 : k) < expect_segments ? (seg_bytes > 0 ? k + 1 : k) : -1;
+        cur_     = end_;
+        scan.end = static_cast<size_t>(dend - base_);
+        return JPEGGPU_SUCCESS;
+    };
+    bool cut = false;
+
     while (true) {
         pos = skip_data(pos);
         const uint8_t* q =
             static_cast<const uint8_t*>(std::memchr(pos, 0xFF, static_cast<size_t>(end_ - pos)));
-        if (q == nullptr || q + 1 >= end_) return JPEGGPU_INVALID_JPEG; // no end-of-image marker
+        if (q == nullptr || q + 1 >= end_) { // no end-of-image marker
+            if (!truncated_) return JPEGGPU_INVALID_JPEG;
+            const jpeggpu_status cs = cut_here(q ? q : end_);
+            if (cs != JPEGGPU_SUCCESS) return cs;
+            cut = true;
+            break;
+        }
         const size_t qo = boff(q);
         while (next_win <= qo) {
             emit(chunk_begin, next_win);
@@ -916,8 +988,15 @@ jpeggpu_status Reader::walk_scan(Scan& scan, const Logger& log)
         const uint8_t* mk = q; // skip fill bytes (any number of FF before the marker code)
         while (m == 0xFF) {
             ++mk;
-            if (mk + 1 >= end_) return JPEGGPU_INVALID_JPEG;
+            if (mk + 1 >= end_) break;
             m = mk[1];
+        }
+        if (mk + 1 >= end_) { // fill bytes up to the end of the file
+            if (!truncated_) return JPEGGPU_INVALID_JPEG;
+            const jpeggpu_status cs = cut_here(q);
+            if (cs != JPEGGPU_SUCCESS) return cs;
+            cut = true;
+            break;
         }
         if (m == 0) return JPEGGPU_INVALID_JPEG; // FF FF 00 is not a legal sequence
         // the segment's data ends at q
@@ -947,7 +1026,7 @@ jpeggpu_status Reader::walk_scan(Scan& scan, const Logger& log)
             break;
         }
         pos = mk + 2;
-        if (pos >= end_) return JPEGGPU_INVALID_JPEG;
+        if (pos >= end_ && !truncated_) return JPEGGPU_INVALID_JPEG;
         // next segment
         seg_dst_base    = static_cast<int>(padded_end);
         chunk_dst       = padded_end;
@@ -955,11 +1034,16 @@ jpeggpu_status Reader::walk_scan(Scan& scan, const Logger& log)
         next_win        = (chunk_begin / kDestuffWin + 1) * kDestuffWin;
         ff_in_chunk     = 0;
         seg_first_chunk = scan.chunks.size();
+        if (pos >= end_) { // the file ends with this restart marker: the next interval has no data
+            const jpeggpu_status cs = cut_here(end_);
+            if (cs != JPEGGPU_SUCCESS) return cs;
+            cut = true;
+            break;
+        }
     }
 
-    const int total_mcus = scan.mcus_x * scan.mcus_y;
-    const int expect     = ceil_div(total_mcus, scan.mcus_per_segment);
-    if (static_cast<int>(scan.segments.size()) != expect) {
+    const int expect = expect_segments;
+    if (!cut && static_cast<int>(scan.segments.size()) != expect) {
         log.log(
             "\tscan has %d restart segments, geometry requires %d\n",
             static_cast<int>(scan.segments.size()),
@@ -1053,9 +1137,17 @@ void Reader::cut_segments(int a, int b)
 }
 
 jpeggpu_status Reader::parse(const uint8_t* data, size_t size, int subseq_bytes, const Logger& log, bool device_scan,
-                             int shard_rank, int shard_world, bool progressive)
+                             int shard_rank, int shard_world, bool progressive, bool truncated)
 {
     progressive_ = progressive;
+    truncated_   = truncated;
+    if (truncated) {
+        if (shard_world > 1) {
+            log.log("a segment shard of a file that may end early is not supported\n");
+            return JPEGGPU_NOT_SUPPORTED;
+        }
+        device_scan = false; // only the host walk records where the data ends (jpeggpu_ext.h)
+    }
     std::memset(prog_al_, -1, sizeof(prog_al_));
     std::memset(prog_level_, -1, sizeof(prog_level_));
     if (shard_world > 1 && device_scan) {
@@ -1128,9 +1220,24 @@ jpeggpu_status Reader::parse(const uint8_t* data, size_t size, int subseq_bytes,
     if ((st = read_marker(marker)) != JPEGGPU_SUCCESS) return st;
     if (marker != M_SOI) return JPEGGPU_INVALID_JPEG;
     do {
+        if (truncated_ && s.num_scans > 0) {
+            // Behind a whole scan, a file that ends in front of its EOI or inside the tables or the header of a later scan
+            // ends here: that scan is not there (what it would have coded is refused below).
+            const uint8_t* m = cur_;
+            while (m < end_ && *m == 0xFF) ++m;
+            const bool lone = m < end_ && cur_ < m && (*m == M_EOI || (*m >= M_RST0 && *m <= M_RST7) || *m == M_SOI || *m == 0x01);
+            if (m >= end_ || (cur_ < m && !lone && (end_ - m < 3 || static_cast<size_t>(end_ - m - 1) < static_cast<size_t>(m[1] << 8 | m[2])))) {
+                s.trunc.no_eoi = true;
+                break;
+            }
+        }
         if ((st = read_marker(marker)) != JPEGGPU_SUCCESS) return st;
         log.log("marker 0x%02x\n", marker);
         st = JPEGGPU_SUCCESS;
+        if (marker == M_SOF2 && truncated_) {
+            log.log("\tprogressive frames are not read under jpeggpu_ext_set_truncated\n");
+            return JPEGGPU_NOT_SUPPORTED;
+        }
         if (marker == M_SOF0 || marker == M_SOF1 || (marker == M_SOF2 && progressive_)) {
             if (found_sof_) return JPEGGPU_INVALID_JPEG;
             found_sof_ = true;
@@ -1151,7 +1258,7 @@ jpeggpu_status Reader::parse(const uint8_t* data, size_t size, int subseq_bytes,
             st = read_dht(log);
         } else if (marker == M_SOS) {
             st = read_sos(log);
-            if (st == JPEGGPU_SUCCESS && stop_) break;
+            if (st == JPEGGPU_SUCCESS && (stop_ || s.trunc.scan >= 0)) break;
         } else if (marker == M_DQT) {
             st = read_dqt(log);
         } else if (marker == M_DRI) {
@@ -1173,6 +1280,7 @@ jpeggpu_status Reader::parse(const uint8_t* data, size_t size, int subseq_bytes,
     for (int c = 0; c < s.num_comp; ++c) {
         if (!comp_in_scan_[c]) {
             log.log("\tcomponent with index %d not defined in scan\n", c);
+            if (s.trunc.no_eoi) return JPEGGPU_NOT_SUPPORTED; // the file ended in front of that component's scan
             return JPEGGPU_INVALID_JPEG;
         }
     }

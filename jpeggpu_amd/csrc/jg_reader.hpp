@@ -86,6 +86,8 @@ struct Scan {
     // A component of a progressive frame as the IDCT stage sees it (Stream::progressive): no entropy-coded data of its own
     // (num_subseq == 0, no segments, no chunks); its symbol stream has one region per data unit (jg_prog_core.h).
     int prog_regions = 0;
+    // Read under jpeggpu_ext_set_truncated: zero bytes kept behind the data if the file ends in this scan (truncation_tail)
+    int trunc_tail_bytes = 0;
 };
 
 /// One scan of a progressive frame (T.81 Annex G). The scans do not fit Stream::scans: a file has up to kMaxProgScans of
@@ -138,7 +140,30 @@ struct Stream {
     int num_levels   = 0;
     std::vector<ProgScan> prog_scans;
     int prog_blocks_x[kMaxComp]{}, prog_blocks_y[kMaxComp]{}; // each component's MCU-padded block grid (the coefficient buffer)
+    // A file that ends early, read under jpeggpu_ext_set_truncated (Reader::parse, `truncated`): what the host walk knows.
+    struct Truncation {
+        bool no_eoi = false;        // the file ended without an EOI marker
+        int scan = -1;              // the scan the file ends in (its entropy-coded data runs to the end of the file), or -1
+        int cut_segment = -1;       // ... and the entry of that scan's segment table the data ends in
+        uint32_t end_bit = 0;       // bits of data that segment really has; its other subsequences are zeros (jg_trunc.hip)
+        int zero_segment = -1;      // entry of the all-zero segment behind it (the next restart interval), or -1
+        size_t scan_bytes = 0;      // entropy-coded bytes of that scan that are present, stuffing and markers included
+        int first_missing_interval = -1; // the first restart interval without any data, or -1 (none, or no restart markers)
+    } trunc;
 };
+
+/// Zero bytes kept behind the data of a cut scan, whatever its tables: the MCU in flight at the cut is finished from zero
+/// bits (libjpeg), and a data unit is at most 64 symbols of 16 + 15 bits. Reader::read_sos asks the scan's tables for less.
+inline int truncation_tail_bytes(int du_per_mcu) { return du_per_mcu * 64 * 31 / 8 + 8; }
+/// Bits one data unit takes when it is decoded from zero bits alone, from the first-level entries (jg_defs.h) of its tables
+/// for an all-zero window: the DC table's all-zero code with its magnitude bits, then the AC table's, over and over, until
+/// index 63 is passed -- once, if that code is the end of block. 0: a table whose all-zero code is longer than its index.
+inline int zero_unit_bits(uint32_t dc_entry, uint32_t ac_entry)
+{
+    if ((dc_entry & 31u) == 0 || (ac_entry & 31u) == 0) return 0;
+    const int adv = static_cast<int>((ac_entry & 0x7FFFu) >> 9); // run + 1, or 63: end of block
+    return static_cast<int>(dc_entry & 31u) + static_cast<int>(ac_entry & 31u) * (adv >= 63 ? 1 : (63 + adv - 1) / adv);
+}
 
 /// Requests for a per-image choice (Reader::parse): 0 or -N, N = about how many images share the call (kBatchHintFull:
 /// "a batch", jpeggpu_ext_set_batched).
@@ -194,8 +219,10 @@ struct Reader {
     /// holds for every scan of the image; subseq_bytes() says what it was.
     /// `progressive`: SOF2 frames are read (Huffman-coded, 8-bit samples); the device scan and a segment shard do not
     /// apply to them (the first is ignored, the second refused). Without it they are NOT_SUPPORTED, as in the reference.
+    /// `truncated`: a file that ends anywhere behind its first SOS header is read (Stream::trunc says where it ends); the
+    /// scan it ends in is walked on the host whatever `device_scan` says; a segment shard and SOF2 frames are NOT_SUPPORTED.
     jpeggpu_status parse(const uint8_t* data, size_t size, int subseq_bytes, const Logger& log, bool device_scan = false,
-                         int shard_rank = 0, int shard_world = 1, bool progressive = false);
+                         int shard_rank = 0, int shard_world = 1, bool progressive = false, bool truncated = false);
     int subseq_bytes() const { return subseq_bytes_; }
     /// Keep restart segments [a, b) of the parsed image's single, host-walked scan (jg_reader.cpp).
     void cut_segments(int a, int b);
@@ -218,6 +245,7 @@ struct Reader {
     bool device_scan_ = false;
     bool stop_        = false; // device mode: nothing behind the scan header is parsed on the host
     bool progressive_ = false; // SOF2 is read
+    bool truncated_   = false; // a file that ends early is read
     // progression of a progressive frame, per (component, coefficient): the successive-approximation bit position the
     // coefficient has been coded down to (-1: no scan yet), and the level of the last scan that touched it
     int8_t prog_al_[kMaxComp][64]{};
